@@ -18,7 +18,8 @@ Extra keys (N=1 only, outside the timed region, never `value`): `host_inclusive`
 rr_pipeline_submit/wait incl. PCIe both ways and the fog / environment-map pre-pass), `prepass`, `variants`
 (no tile sharing, angular noise, smaller library calls), `chain` (whole-step HBM fraction), `cpu_baseline` (+ its
 multi-process and C++ legs).  roofline.traffic is measured by two rocprofv3 --pmc passes of this very workload that
-bench.py spawns itself (skip with --no-traffic).
+bench.py spawns itself (skip with --no-traffic).  --dump-outputs DIR: after the timed steps, what the last one computed as
+DIR/<name>.npy (dump_outputs), inputs seeded so that two builds can be compared output for output.
 """
 import argparse
 import contextlib
@@ -117,6 +118,7 @@ class DeviceBatch:
             self.t_counts = torch.zeros((self.n,), dtype=torch.int32, device=dev)
         self.keep = []
         self.status_tensors = []
+        self.outputs = []                   # per frame: (rainy_rgb u8, rainy_mask f64, rainy_mask_i32, drop_status) in HBM
         self.fin = (hb.rr_frame_in * max(self.n, 1))()
         self.fout = (hb.rr_frame_out * max(self.n, 1))()
         self.host = []
@@ -144,6 +146,7 @@ class DeviceBatch:
             o_st = torch.empty((max(len(drops), 1),), dtype=torch.int32, device=dev)
             self.keep += [t_bg, t_env, t_dr, o_rgb, o_m, o_mi, o_st]
             self.status_tensors.append(o_st)
+            self.outputs.append((o_rgb, o_m, o_mi, o_st))
             fi_, fo_ = self.fin[k], self.fout[k]
             fi_.H, fi_.W, fi_.He, fi_.We = H, W, He, We
             fi_.bg = fi_.rainy_bg = t_bg.data_ptr()
@@ -179,6 +182,46 @@ class DeviceBatch:
             ctypes.memmove(ctypes.byref(fin[k]), ctypes.byref(self.fin[a + k]), ctypes.sizeof(hb.rr_frame_in))
             ctypes.memmove(ctypes.byref(fout[k]), ctypes.byref(self.fout[a + k]), ctypes.sizeof(hb.rr_frame_out))
         return fin, fout, n
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, batch, H, W, budget=DUMP_BUDGET_BYTES):
+    """What the timed path handed its caller in its last step, as .npy files: a seeded sample of the batch's frames (all of
+    them when they fit in `budget` bytes), whole frames, or a seeded sample of rows when one frame alone is larger.
+    rainy_rgb float32 [k, h, W, 3], rainy_mask float64 [k, h, W], rainy_mask_i32 float64 [k, h, W], drop_status float32 (the
+    sampled frames' per-drop statuses, concatenated), n_drops float64 [k] (their drop counts), frames / rows float64 (which
+    frames and rows were kept)."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = batch.device_counts() if batch.sims is not None else np.array([len(h[2]) for h in batch.host])
+    rows = np.arange(H)
+    budget -= 1 << 16                      # (room for the .npy headers and the small index arrays)
+    per_px = 3 * 4 + 8 + 8
+    per_frame = H * W * per_px + 4 * int(counts.max(initial=0))
+    k = max(1, min(batch.n, budget // per_frame))
+    if per_frame > budget:                 # one frame alone is over the budget: a seeded sample of its rows
+        nr = max(1, (budget - 4 * int(counts.max(initial=0))) // (W * per_px))
+        rows = np.sort(np.random.RandomState(1).choice(H, min(nr, H), replace=False))
+    frames = np.sort(np.random.RandomState(0).choice(batch.n, k, replace=False)) if k < batch.n else np.arange(batch.n)
+    sel = [batch.outputs[int(i)] for i in frames]
+    rt = None
+    if len(rows) < H:
+        import torch
+        rt = torch.from_numpy(rows).to(sel[0][0].device)
+    pick = (lambda t: t) if rt is None else (lambda t: t.index_select(0, rt))
+    res = {
+        "rainy_rgb": np.stack([pick(o[0]).cpu().numpy().astype(np.float32) for o in sel]),
+        "rainy_mask": np.stack([pick(o[1]).cpu().numpy().astype(np.float64) for o in sel]),
+        "rainy_mask_i32": np.stack([pick(o[2]).cpu().numpy().astype(np.float64) for o in sel]),
+        "drop_status": np.concatenate([o[3].cpu().numpy()[:int(counts[i])].astype(np.float32) for o, i in zip(sel, frames)]),
+        "n_drops": counts[frames].astype(np.float64),
+        "frames": frames.astype(np.float64),
+        "rows": rows.astype(np.float64),
+    }
+    for name, a in res.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {"dir": out_dir, "frames": len(frames), "rows": len(rows), "bytes": int(sum(a.nbytes for a in res.values()))}
 
 
 def timed(torch, dist, world, dev, fn, steps):
@@ -437,6 +480,8 @@ def main():
     ap.add_argument('--scene-dir', default=None, help='(used by the PMC passes) directory of a simulation to reuse')
     ap.add_argument('--no-serial', action='store_true', help='skip the extra pass with the colour branch on the main stream (per-kernel durations without overlap)')
     ap.add_argument('--phases', action='store_true', help='(phase-clock build of the library) print the per-phase wave cycles')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last step computed '
+                    '(rank 0\'s frames, a seeded sample within 64 MB) as DIR/<name>.npy in float32 / float64')
     ap.add_argument('--inner', action='store_true', help='(used by the PMC passes) timed loop only, no extras, no JSON')
     args = ap.parse_args()
     if args.inner or args.sweep:
@@ -543,6 +588,7 @@ def main():
     elapsed = timed(torch, dist, world, dev, render, args.steps)
     rh.profile(False)
     assert rh.synchronize(), "tile arena regrew inside the timed region"
+    dumped = dump_outputs(args.dump_outputs, batch, H, W) if args.dump_outputs and rank == 0 else None
     stats = rh.profile_read()
     if args.phases and hasattr(rh.lib, 'rr_debug_phases'):         # phase-clock build of the library (scripts/phase_timing.sh)
         buf = (ctypes.c_ulonglong * 64)()
@@ -951,6 +997,8 @@ def main():
                                     for k, v in sorted((valu or {}).items(), key=lambda kv: -kv[1]["valu_util"])} if valu else None},
         }
         out.update(extras)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if "host_inclusive" in extras:                         # SURVEY 8(d)'s own rate (H2D of the inputs and D2H of the outputs included), at the top level
             out["host_inclusive_frames_per_s"] = extras["host_inclusive"].get("frames_per_s")
         if single and not args.no_driver and not strong and not is_sim and args.workload == 'kitti100':

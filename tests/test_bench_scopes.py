@@ -47,3 +47,37 @@ def test_every_kernel_of_a_timing_scope_maps_to_it():
     assert len(pairs) > 30 and ('k_blur_fused', 'k_blur_fused_dma') in pairs and ('k_blur_cols', 'k_blur<1>') in pairs, sorted(pairs)
     bad = sorted((n, k) for n, k in pairs if bench.scope_of_name('void (anonymous namespace)::' + k + '(args)') != n)
     assert not bad, bad
+
+
+def test_output_dump_is_seeded_and_within_budget(tmp_path):
+    """--dump-outputs: float32 / float64 files only, at most 64 MB in all, the same files for the same outputs (the frame and
+    row samples are seeded), whole frames while one fits and a row sample of the frame when it does not."""
+    import numpy as np
+    import torch
+    bench = _bench()
+
+    class Batch:
+        sims = None
+
+    def batch(n, H, W, nd):
+        b = Batch()
+        b.n, b.host = n, [(None, None, np.zeros(nd))] * n
+        g = torch.Generator().manual_seed(n)
+        b.outputs = [(torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, generator=g), torch.rand(H, W, dtype=torch.float64, generator=g),
+                      torch.randint(0, 9, (H, W), dtype=torch.int32, generator=g), torch.randint(0, 3, (nd,), dtype=torch.int32, generator=g))
+                     for _ in range(n)]
+        return b
+    for n, H, W, nd, whole in ((40, 375, 1242, 8000, True), (3, 1200, 2400, 100, False)):
+        b = batch(n, H, W, nd)
+        got = [bench.dump_outputs(str(tmp_path / ('%d_%d' % (n, k))), b, H, W) for k in range(2)]
+        files = sorted(os.listdir(got[0]['dir']))
+        assert files == sorted(os.listdir(got[1]['dir'])) and 'rainy_rgb.npy' in files and 'rainy_mask.npy' in files
+        assert sum(os.path.getsize(os.path.join(got[0]['dir'], f)) for f in files) <= bench.DUMP_BUDGET_BYTES
+        for f in files:
+            a, c = np.load(os.path.join(got[0]['dir'], f)), np.load(os.path.join(got[1]['dir'], f))
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, c), f
+        assert (got[0]['rows'] == H) == whole and 1 <= got[0]['frames'] <= n
+        fr = np.load(os.path.join(got[0]['dir'], 'frames.npy')).astype(int)
+        rgb = np.load(os.path.join(got[0]['dir'], 'rainy_rgb.npy'))
+        rows = np.load(os.path.join(got[0]['dir'], 'rows.npy')).astype(int)
+        assert np.array_equal(rgb[-1], b.outputs[fr[-1]][0].numpy()[rows].astype(np.float32))
