@@ -344,22 +344,22 @@ int rr_generate_drops(rr_ctx* ctx, int32_t n, const rr_sim_frame* frames, int32_
                       int32_t* n_out);
 int rr_sizeof_sim_frame(void);
 
-/* Options.  1-4 and 6 are tuning / A-B switches: NONE of them changes a result bit (tests/test_gpu_properties.py); 7 trades
- * float64 for float in the colour channels only.  Unknown
- * options or values are RR_E_ARG.  The library reads no environment variables. */
+/* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
+ * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does
+ * nothing).  Unknown options or values are RR_E_ARG.  The library reads no environment variables. */
 enum {
-  RR_OPT_DEDUP = 1,                 /* 1 (default): drops with bit-identical raw-tile parameters share one tile inside a batch */
+  RR_OPT_DEDUP = 1,                 /* tuning: 1 (default): drops with bit-identical raw-tile parameters share one tile inside a batch */
   RR_OPT_GENERAL_FOV = 2,           /* 1: force the general colour path (prefix table in HBM) that maps taller than 1024 rows,
-                                     *    wider than 4096 columns or with He*We >= 2^22 always take; default 0 */
-  RR_OPT_FOV_THREADS = 3,           /* workgroup size of the FOV-sum kernel: 0 (library's choice), 512 or 1024 */
-  RR_OPT_FOV_DROPS_PER_THREAD = 4,  /* drops per thread of the FOV-sum kernel: 0 (library's choice), 1, 2, 4 or 8 */
+                                     *    wider than 4096 columns or with He*We >= 2^22 always take; default 0.  The colour sums
+                                     *    are added in another order: rainy_image within 1 LSB, mask and statuses the same */
+  RR_OPT_FOV_THREADS = 3,           /* retired: only 0 or 1024 is accepted */
+  RR_OPT_FOV_DROPS_PER_THREAD = 4,  /* tuning: drops per thread of the FOV-sum kernel: 0 (library's choice), 1, 2, 4 or 8 */
   /* NOT a tuning switch -- a feature the reference only sketches (common/drop_depth_map.py, dead code behind
    * USE_DEPTH_WEIGHTING = 0, generator.py:20): with 1, a drop is not composited at pixels whose scene depth
    * (rr_frame_in.depth / the pre-pass' depth) is smaller than the drop's distance |world z|.  Default 0: the reference's
    * output.  Excluded from every parity run. */
   RR_OPT_DEPTH_OCCLUSION = 5,
-  RR_OPT_BLUR_WORKGROUPS = 6,       /* tuning: workgroups per CU the fused defocus blur is sized for (LDS tiles + registers):
-                                     * 0 (library's choice = 4), 3, 4 or 5 */
+  RR_OPT_BLUR_WORKGROUPS = 6,       /* retired: only 0 or 4 is accepted */
   /* Colour arithmetic of the compositor.  rainy_mask is a float64 sum in drop order in either case (bit-exact); the three
    * colour channels of rainy_image only have to land within 1 LSB of a uint8 (BASELINE.json), so by default they are
    * blended in float whenever no frame of the batch asks for the float64 composite (rr_frame_out.rainy_bg_out == NULL).
@@ -374,10 +374,7 @@ enum {
    * requests -- 90 vs 40 GB/s both ways, scripts/probes/pcie_probe.hip -- but it takes compute units from the rendering
    * kernels it runs beside: measured slower end to end). */
   RR_OPT_COPY_KERNELS = 8,
-  /* tuning: 1 (default) the tile kernels stage a streak texture from a copy that already carries its 2-texel zero border
-   * (made once by rr_set_streak_db*: 16-byte copies into LDS); 0 they build the border and place the texels byte by byte.
-   * The LDS contents are the same bytes. */
-  RR_OPT_PADDED_TEXTURES = 9,
+  RR_OPT_PADDED_TEXTURES = 9,       /* retired: only 1 is accepted */
   /* precision of the colour branch: 0 float64 throughout (the reference's arithmetic), 1 float32 always, 2 (default) float32
    * whenever the compositor blends float colours (no frame of the batch asks for the float64 composite: the same switch as
    * RR_OPT_COMPOSITE_F64's default).  Float32 = the field-of-view vertices (every predicate that decides a drop's status or
@@ -391,9 +388,7 @@ enum {
                                      * 2 (r05): incremental cursors over per-edge records (a quarter of the instructions per row, no
                                      * faster: profiles/r05_ab_log.md); 0: the edge-parallel kernel for every drop.  The spans are the
                                      * same: identical results. */
-  RR_OPT_COMPOSITE_WAVES = 11,      /* tuning: waves per SIMD the float compositor's register allocation is held to: 0 (library's
-                                     * choice), 4..8 (more waves in flight hide more of the alpha-sample latency; 4 and 5 only with
-                                     * RR_OPT_COMPOSITE_BATCH) */
+  RR_OPT_COMPOSITE_WAVES = 11,      /* retired: only 0 is accepted */
   RR_OPT_PIPELINE_F32 = 13,         /* 1 (default): rr_pipeline_* hand the fog layer and the xyY map from the pre-pass to the hot path
                                      * as float32 unless pre_out asks for float64 copies (see rr_pipeline_frames); 0: float64 */
   RR_OPT_WILD_PIXELS = 14,          /* 1: rainy_bg may hold values outside [0, 1] (a third party's array; the fog pre-pass ends with a
@@ -408,27 +403,16 @@ enum {
                                      * the IDAT payload as it is.  A file whose stream would not fit its buffer (incompressible pixels)
                                      * keeps its scanlines (first byte = a filter type, never 'R').  rr_png_write_scanlines /
                                      * rr_io_write_frames take either form.  Default 0 (scanlines). */
-  RR_OPT_COMPOSITE_U16 = 16,        /* tuning (r05): 1 (default) the float compositor leaves the composite before the mean shift in the
-                                     * library's scratch as three 16-bit codes in one 8-byte word per pixel (rint(v * 65534); 65535 = "outside [0, 1]:
-                                     * take the pixel's own rainy_bg value", which is then what the composite holds) instead of three
-                                     * floats: one store per pixel, two thirds of the bytes written there and read back by the final pass.  The code is 2^-17 off at
-                                     * most (an LSB of rainy_image is 2^-8): the image contract (+-1 LSB) holds, the mask never sees it.
-                                     * Ignored with RR_OPT_WILD_PIXELS, and whenever a caller asks for the composite itself. */
-  RR_OPT_BLUR_DMA = 17,             /* tuning (r05): 1 (default) the fused defocus blur stages its raw sub-tiles and weight tables with
-                                     * gfx950 LDS-DMA loads (global_load_lds: no registers in between), issued a sub-tile AHEAD: they land
-                                     * while the current sub-tile's column pass runs; 0: the r04 kernel (loads through registers at the
-                                     * start of every sub-tile) -- since r06 only in -DRR_EXPERIMENTS builds of the library, RR_E_ARG
-                                     * otherwise.  Same results. */
+  RR_OPT_COMPOSITE_U16 = 16,        /* retired: only 1 is accepted */
+  RR_OPT_BLUR_DMA = 17,             /* retired: only 1 is accepted */
   RR_OPT_FOV_FILL_RULE = 18,        /* which restatement of cv2.fillConvexPoly (bad_weather.py:388) decides the texels of a drop's field of
-                                     * view: 0 (default) the row-span rule of the fast colour kernels (nearest x of every edge on the
-                                     * row, min / max); 1 OpenCV 3.2's own algorithm -- Bresenham outline + 16.16 edge walkers, in closed
+                                     * view: 1 (default) OpenCV 3.2's own algorithm -- Bresenham outline + 16.16 edge walkers, in closed
                                      * form per edge and row (csrc/rr_device.h fov_rowspan_cv) -- for the closed polygons it is defined
-                                     * for; takes the general (slow) colour path.  Colour only: a drop's colour constants move by
-                                     * <= 0.3 %, rainy_image by <= 1 LSB on 1.4 % of its values (README, profiles/r05_fill_rule_study.txt);
-                                     * mask and statuses are the same. */
-  RR_OPT_BIN_ROWS = 19,             /* tuning (r05): 1 (default) the ordered per-tile drop lists are made by a workgroup per ROW of coarse
-                                     * tiles (drops filtered by row first, then a wave per tile); 0: a workgroup per coarse tile that
-                                     * tests every drop (r04).  Same lists. */
+                                     * for, on the fast colour path as well as the general one (polygons it is not defined for, the
+                                     * wrapping ones above all, keep the span rule); 0 the row-span rule (nearest x of every edge on the
+                                     * row, min / max).  Colour only: a drop's colour constants move by <= 0.3 %, rainy_image by <= 1 LSB
+                                     * on 1.4 % of its values (README, profiles/r05_fill_rule_study.txt); mask and statuses are the same. */
+  RR_OPT_BIN_ROWS = 19,             /* retired: only 1 is accepted */
   RR_OPT_COLOUR_STREAM = 21,        /* tuning (r05): two chains of the step that only meet in k_colour run on two streams of the library.
                                      * 1 (default): the FOV chain (polygons, spans, sums over the environment map) on the second stream
                                      * beside plan .. tiles .. blur; 0: one in-order stream (r04).  (2 was the other split -- plan .. lists
@@ -445,10 +429,7 @@ enum {
   RR_OPT_ROWS_SHARES = 23,          /* tuning (r06): k_tile_rows' workgroups take the batch's tile list in shares of equal estimated cost off a
                                      * device-wide counter; this many shares per workgroup (1 .. 8, default 2): more shares even out the
                                      * workgroups, fewer leave less waiting at a share's end */
-  RR_OPT_COMPOSITE_BATCH = 20       /* tuning (r05): 1 (default) the float compositor keeps the records of 64 list entries at a time in
-                                     * vector registers (a lane per entry) and runs its alpha samples two entries ahead of the blend;
-                                     * 0: a scalar record fetch per entry, samples one entry ahead (r04).  Same operations in the same
-                                     * order: same bits. */
+  RR_OPT_COMPOSITE_BATCH = 20       /* retired: only 1 is accepted */
 };
 int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value);
 

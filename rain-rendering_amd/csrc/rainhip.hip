@@ -19,15 +19,15 @@
 //                      walks for rotate + flip + INTER_AREA, a lane per pixel for the Big drops' bicubic warpPerspective
 //     k_tile_generic / k_tile_big / k_tile   what k_tile_rows does not take: rare modes; Big tiles of more than 8192 pixels, a
 //                      thread per pixel; integer-ratio and oversized rotate tiles, a workgroup per tile
-//     k_blur_weights, k_blur_small, k_blur_fused_dma (-DRR_EXPERIMENTS: k_blur_fused), k_blur_big_weights, k_blur<0|1>
+//     k_blur_weights, k_blur_small, k_blur_fused_dma, k_blur_big_weights, k_blur<0|1>
 //                      separable defocus blur of the effective tile: a wave per small tile; LDS sub-tiles staged by
 //                      LDS-DMA for radii 5..48; zero-skipping taps for larger ones
 //     -- join --
 //     k_colour         band partials -> colour constants, compositor records, bbox, status
-//     k_bin_rows (k_bin), [k_pad_visits], k_composite32 (k_composite)
+//     k_bin_rows (k_bin: frames wider than 4096 px), [k_pad_visits], k_composite32 (k_composite: float64 colours)
 //                      ordered per-tile drop lists (ballot compaction, no atomics); float64 mask in drop order, float
 //                      (or float64) colours, tile sums
-//     k_means, k_finalize16 (k_finalize), [k_png_image, k_png_mask, k_pngz_blocks, k_pngz_pack]
+//     k_means, k_finalize16 (k_finalize: a float or float64 composite), [k_png_image, k_png_mask, k_pngz_blocks, k_pngz_pack]
 //                      mean-contrast shift, clip, truncating u8 quantisation; optional PNG scanlines / zlib streams
 //   elsewhere: k_particles / k_particle_draws (drop tables born on the device), k_png_unfilter (input files' scanlines),
 //   k_pad_textures, k_pair_textures, k_copy_pieces / k_copy_small (batched copies, descriptors)
@@ -233,7 +233,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   double* colpart;                  // [frame][COL_PARTS][5][drops] FOV partial sums per envmap row band
   double* wtab;                     // [frame][drops][2][BR_MAX+1] normalised Gaussian half tables of the blurred drops (k_blur_weights)
   double* wtab_big;                 // [frame][SLOW_CAP][2][MAX_R+1] the same for the first SLOW_CAP large-radius drops of a frame (k_blur_big_weights)
-  const uint8_t* tex_pad;           // the textures with their 2-texel zero border, as k_tile stages them (k_pad_textures); NULL: staged byte by byte
+  const uint8_t* tex_pad;           // the textures with their 2-texel zero border, as k_tile stages them (k_pad_textures)
   const int64_t* tex_poff;          // [texture] offset of its padded copy (a multiple of 16)
   uint4* fov_erec;                  // [frame][n_fov][drops] k_fov_dda's edge records (rr_device.h dda_edge_record: 16 bytes)
   uint32_t* fov_pix;                // [frame][n_fov][drops] k_fov_dda's vertex pixels, x | y << 16 (a wave stores 256 contiguous bytes per vertex)
@@ -258,7 +258,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   uint4* lrec;                      // [frame][drops] ListRec: the drop's work-list classes, made once by k_plan (r06; k_lists read the plans twice)
   int32_t* canon;                   // [frame][drops] batch-global index of the drop whose raw tile this drop uses
   int32_t* htab;                    // [2*frames*drops] open-addressing table of k_dedup (0 = empty, else index+1)
-  int32_t blur_bx, blur_by;         // LDS capacities (doubles) of the fused blur's two staging tiles (RR_OPT_BLUR_WORKGROUPS)
+  int32_t blur_bx, blur_by;         // LDS capacities (doubles) of the fused blur's two staging tiles (rr_device.h BLUR_BX / BLUR_BY)
   // k_tile_rows (r06): the rotate + INTER_AREA tiles of the WHOLE batch in one list, bucketed by texture
   int32_t* rows_list;               // [frame][drops] frame-local indices of the drops k_tile_rows renders (k_lists)
   int32_t* rows_n;                  // [frame][2] their number: rotate + INTER_AREA tiles, Big tiles
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) void k_env_consts(Dims dm, const double* prefi
 }
 
 // blur work layout: rr_device.h (blur_layout, blur_is_small -- host-compiled too, so that the CPU tier can sweep them)
-// blurred drops neither k_blur_small nor k_blur_fused can take (radius > BR_MAX): two global passes
+// blurred drops neither k_blur_small nor k_blur_fused_dma can take (radius > BR_MAX): two global passes
 // through one extra padded scratch tile
 __device__ inline bool blur_is_slow(const DropPlan& p, const Scratch& sc) {
   return p.r1 > 0 && !blur_is_small(p) && !blur_layout(p, sc.blur_bx, sc.blur_by).fused;
@@ -1073,7 +1073,6 @@ __device__ inline double readlane_f64(double v, int l) {
 // issued before the look-ups of the current one.  Band partials go to colpart[frame][band][5][drop]; the half-1
 // workgroup of chunk 0 also leaves the band's row totals (sum w, sum Y*w) for the frame constants.  LDS: P as one array
 // of double2: 16-byte entries spread a wave's random look-ups over all 64 banks.
-constexpr int FOV_EMAX = 2;
 template <int DPT, int EMAX>
 __global__ __launch_bounds__(1024) void k_fov_sums(const FrameDesc* frames, Dims dm, int max_drops, int Hp, int Dp, int rpb, int nchunk, Scratch sc) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
@@ -1720,9 +1719,9 @@ __global__ __launch_bounds__(256) void k_pair_textures(const uint8_t* texels, co
   }
 }
 
-// The textures once more, each with its 2-texel zero border and pitch w + 4 -- byte for byte what load_tex_padded builds in
-// LDS -- made when the database is set: a tile then stages its texture with 16-byte copies (three per thread for a 32x320
-// texture) instead of placing 10 K bytes one by one (four index computations and four one-byte LDS writes per dword).
+// The textures once more, each with its 2-texel zero border and pitch w + 4 -- the LDS image k_tile and k_tile_generic
+// sample -- made when the database is set: a tile then stages its texture with 16-byte copies (three per thread for a
+// 32x320 texture).
 __global__ __launch_bounds__(256) void k_pad_textures(const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w,
                                                       const int64_t* tex_off, const int64_t* tex_poff, uint8_t* pad) {
   const int i = blockIdx.x, sh = tex_h[i], sw = tex_w[i], P = sw + 4;
@@ -1740,45 +1739,6 @@ __device__ inline void load_tex_copy(uint8_t* s_tex, const uint8_t* gpad, int sh
   const uint4* g = reinterpret_cast<const uint4*>(gpad);
   uint4* d = reinterpret_cast<uint4*>(s_tex);
   for (int k = threadIdx.x; k < n16; k += 256) d[k] = g[k];
-}
-
-// texture -> LDS with a 2-texel zero border (pitch sw+4).  Border texels are zeroed directly,
-// the interior is copied with independent dword loads (textures are 16-byte aligned by
-// pack_streak_db; unaligned bases fall back to byte loads).  Caller syncs afterwards.
-__device__ inline void load_tex_padded(uint8_t* s_tex, const uint8_t* gtex, int sh, int sw) {
-  const int t = threadIdx.x, P = sw + 4;
-  for (int k = t; k < 4 * P; k += 256) {               // two rows above, two below
-    const int r = k / P, x = k - r * P;
-    s_tex[(r < 2 ? r : sh + r) * P + x] = 0;
-  }
-  for (int k = t; k < 4 * sh; k += 256) {               // two columns left, two right
-    const int y = k >> 2, c = k & 3;
-    s_tex[(y + 2) * P + (c < 2 ? c : sw + c)] = 0;
-  }
-  const int nbytes = sh * sw;
-  const float inv_sw = 1.0f / (float)sw;
-  if ((reinterpret_cast<uintptr_t>(gtex) & 3u) == 0) {
-    const uint32_t* g4 = reinterpret_cast<const uint32_t*>(gtex);
-    const int nd = nbytes >> 2;
-    for (int k = t; k < nd; k += 256) {
-      const uint32_t v = g4[k];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int idx = 4 * k + j;
-        const int y = (int)(((float)idx + 0.5f) * inv_sw), x = idx - y * sw;
-        s_tex[(y + 2) * P + (x + 2)] = (uint8_t)(v >> (8 * j));
-      }
-    }
-    for (int idx = (nd << 2) + t; idx < nbytes; idx += 256) {
-      const int y = (int)(((float)idx + 0.5f) * inv_sw), x = idx - y * sw;
-      s_tex[(y + 2) * P + (x + 2)] = gtex[idx];
-    }
-  } else {
-    for (int idx = t; idx < nbytes; idx += 256) {
-      const int y = (int)(((float)idx + 0.5f) * inv_sw), x = idx - y * sw;
-      s_tex[(y + 2) * P + (x + 2)] = gtex[idx];
-    }
-  }
 }
 
 // fixed-point bilinear sample of the padded LDS texture (same arithmetic as rot_sample; valid
@@ -1851,10 +1811,7 @@ __global__ __launch_bounds__(256) void k_tile_generic(const FrameDesc* frames, i
   // Staging the texture in LDS costs one pass over all its texels; a small Big tile (bicubic: 16 taps
   // per output pixel) touches fewer texels than that, and the 50 textures (~350 KB) live in L2 anyway
   const bool tex_fits = (sh + 4) * P <= TEX_LDS && !(p.kind == KIND_BIG && p.tw * p.th * 12 < sh * sw);
-  if (tex_fits) {
-    if (sc.tex_pad) load_tex_copy(s_tex, sc.tex_pad + sc.tex_poff[p.tex], sh, sw);
-    else load_tex_padded(s_tex, gtex, sh, sw);
-  }
+  if (tex_fits) load_tex_copy(s_tex, sc.tex_pad + sc.tex_poff[p.tex], sh, sw);
   double* A0 = sc.arena + p.a0_off;      // raw tile, pitch tw
   // integer-ratio INTER_AREA (ResizeAreaFast): the per-pixel chain is sequential by definition;
   // keep it short with the LDS fixed-point sampler
@@ -2001,10 +1958,8 @@ __global__ __launch_bounds__(256) void k_tile(const FrameDesc* frames, int max_d
   __syncthreads();
   const DropPlan& p = sp;
   const int sh = tex_h[p.tex], sw = tex_w[p.tex];
-  const uint8_t* gtex = texels + tex_off[p.tex];
   const int P = sw + 4;
-  if (sc.tex_pad) load_tex_copy(s_tex, sc.tex_pad + sc.tex_poff[p.tex], sh, sw);
-  else load_tex_padded(s_tex, gtex, sh, sw);
+  load_tex_copy(s_tex, sc.tex_pad + sc.tex_poff[p.tex], sh, sw);
   double* A0 = sc.arena + p.a0_off;
   const int tw = p.tw, th = p.th;
   const double sy_scale = p.scale_y;
@@ -2957,202 +2912,30 @@ __device__ inline void blur_n(const double* c0, int st, W hw, int r, double (&ac
   }
 }
 
-#ifdef RR_EXPERIMENTS                // (r04's register-staged form: the LDS-DMA kernel below replaced it in r05; kept for A/B builds, RR_OPT_BLUR_DMA 0)
 // ---------------------------------------------------------------------------
-// fused defocus blur: both axes of the separable filter through LDS
+// fused defocus blur: both axes of the separable filter through LDS, staged by LDS-DMA a sub-tile ahead
 // ---------------------------------------------------------------------------
-// WPE = waves per SIMD the register allocation is held to (= workgroups per CU; the LDS capacities in sc.blur_bx / blur_by
-// are chosen to match, see above).  LDS (dynamic): hw1 | hw2 | X[blur_bx] | Y[blur_by].
-template <int WPE>
-__global__ __launch_bounds__(256, WPE) void k_blur_fused(const FrameDesc* frames, int max_drops, Scratch sc) {
-  const int f = blockIdx.y, t = threadIdx.x;
-  extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-  double* hw1 = s_dyn;
-  double* hw2 = s_dyn + (BR_MAX + 1);
-  double* X = s_dyn + 2 * (BR_MAX + 1);                                 // 98 doubles in front: X and Y stay 16-byte aligned
-  double* Y = X + sc.blur_bx;
-  const int n_items = sc.counts[f * 8 + 2];
-  if ((int)blockIdx.x >= n_items) return;
-  // r04: the item record and the plan of the NEXT item travel ahead of the current one's arithmetic, by vector loads (lane l
-  // reads dword l of the record; the fields come out by v_readlane): the load phase of an item was a chain of three
-  // dependent round trips (item -> plan -> raw tile), 48 % of the kernel's wave time, and only the last one is left.
-  // (Scalar loads cannot do this: they share the LDS operations' counter and return out of order.)
-  const int lane = t & 63, G = gridDim.x;
-  const global_ptr<const uint32_t> items_w = as_global(reinterpret_cast<const uint32_t*>(sc.blur_items + (int64_t)f * max_drops * BLUR_ITEMS_PER_DROP));
-  const DropPlan* plans = sc.plan + (int64_t)f * max_drops;
-  auto load_item = [&](int item) { return items_w[(int64_t)item * 4 + (lane & 3)]; };
-  auto load_plan = [&](int i) { return as_global(reinterpret_cast<const uint32_t*>(plans + i))[lane]; };
-  struct PlanView {                   // the plan fields this kernel uses, wave-uniform
-    int r1, r2, ew, eh, tw, th, epitch, epad;
-    long long a0_off, a1_off;
-  };
-  auto unpack = [&](uint32_t pv) {
-    auto F = [&](size_t byte_off) { return (int)__builtin_amdgcn_readlane((int)pv, (int)(byte_off / 4)); };
-    PlanView o;
-    o.r1 = F(offsetof(DropPlan, r1)); o.r2 = F(offsetof(DropPlan, r2)); o.ew = F(offsetof(DropPlan, ew)); o.eh = F(offsetof(DropPlan, eh));
-    o.tw = F(offsetof(DropPlan, tw)); o.th = F(offsetof(DropPlan, th)); o.epitch = F(offsetof(DropPlan, epitch)); o.epad = F(offsetof(DropPlan, epad));
-    o.a0_off = (long long)(((unsigned long long)(unsigned)F(offsetof(DropPlan, a0_off) + 4) << 32) | (unsigned)F(offsetof(DropPlan, a0_off)));
-    o.a1_off = (long long)(((unsigned long long)(unsigned)F(offsetof(DropPlan, a1_off) + 4) << 32) | (unsigned)F(offsetof(DropPlan, a1_off)));
-    return o;
-  };
-  uint32_t iv_cur = load_item(blockIdx.x);
-  uint32_t pv_cur = load_plan((int)__builtin_amdgcn_readlane((int)iv_cur, 0));
-  uint32_t iv_nxt = ((int)blockIdx.x + G < n_items) ? load_item(blockIdx.x + G) : 0u;
-  int cur = -1;
-  PH_DECL
-  for (int it = blockIdx.x; it < n_items; it += G) {                    // grid-stride over (drop, sub-tile range) items
-  const int4 item = make_int4((int)__builtin_amdgcn_readlane((int)iv_cur, 0), (int)__builtin_amdgcn_readlane((int)iv_cur, 1),
-                              (int)__builtin_amdgcn_readlane((int)iv_cur, 2), (int)__builtin_amdgcn_readlane((int)iv_cur, 3));
-  const int64_t gi = (int64_t)f * max_drops + item.x;
-  const PlanView p = unpack(pv_cur);
-  {                                   // the next item's plan (its record arrived an item ago) and the record after that
-    const uint32_t pv_n = (it + G < n_items) ? load_plan((int)__builtin_amdgcn_readlane((int)iv_nxt, 0)) : 0u;
-    const uint32_t iv_n = (it + 2 * G < n_items) ? load_item(it + 2 * G) : 0u;
-    iv_cur = iv_nxt;
-    pv_cur = pv_n;
-    iv_nxt = iv_n;
-  }
-  BlurLayout L{1, item.w & 0xffff, item.w >> 16, 0};               // computed once, by k_lists
-  const int r1 = p.r1, r2 = p.r2, pw = p.ew, ph = p.eh;            // the tile being produced is the EFFECTIVE tile
-  // the weight tables depend on the drop only; they are fetched by waves 0 and 1 while the first
-  // batch of tile loads is in flight (every item ends with a barrier, so the old tables are free)
-  bool need_tables = cur != item.x;
-  const double* src = sc.arena + p.a0_off;          // raw tile (tw x th); the pad is implicit zeros
-  double* dst = sc.arena + p.a1_off;                // finished effective tile (ew x eh); raw sits at (r2, r1) inside it
-  const int tw = p.tw, th = p.th;
-  const int ntx = (pw + L.wo - 1) / L.wo;
-  for (int st = item.y; st < item.y + item.z; st++) {
-    const int sty = st / ntx, stx = st - sty * ntx;
-    const int y0 = sty * L.ho, x0 = stx * L.wo;
-    {
-      const int ho = imin(L.ho, ph - y0);
-      const int wo = imin(L.wo, pw - x0);
-      const int hop = (ho + 3) & ~3;                      // rows/columns padded to the 4-output blocks
-      const int wi = wo + 2 * r2, hi = hop + 2 * r1;      // LDS input tile with zero halos (+ slack rows)
-      const int yp = blur_y_pitch(wo, r2);                // odd pitch of the row-pass result
-      // Only the columns under the raw tile carry data through the row pass (it filters along y: a column
-      // without raw pixels stays exactly zero).  X holds those wd columns, the row pass runs over them; Y is
-      // cleared as a whole first (wide stores, no index arithmetic) and the row pass writes its columns over it.
-      const int xa = imax(0, 2 * r2 - x0), xb = imin(wi, tw + 2 * r2 - x0);   // data columns of the haloed sub-tile
-      const int wd = imax(xb - xa, 0);                    // 0: the sub-tile lies beside the raw tile (all zeros)
-      const int wdd = imax(wd, 1);
-      const float inv_wd = 1.0f / (float)wdd;
-      // data columns of the haloed tile -> LDS; eight independent global loads in flight per thread.  By the
-      // choice of xa / xb every column is inside the raw tile; only the row needs a test.  (row, column) of the
-      // thread's first element by one float division, the following ones (256 apart) incrementally.
-      const int nx = wd * hi;
-      const int dq = (int)((256.0f + 0.5f) * inv_wd), dr = 256 - dq * wdd;
-      const int xs = x0 - 2 * r2 + xa, ys = y0 - 2 * r1;
-      int yy = (int)(((float)t + 0.5f) * inv_wd), xc = t - yy * wdd;
-      for (int base = t; base < nx || need_tables; base += 2048) {
-        double v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-          const int y = ys + yy;
-          v[k] = (base + 256 * k < nx && (unsigned)y < (unsigned)th) ? src[y * tw + (xs + xc)] : 0.0;
-          xc += dr;
-          yy += dq;
-          if (xc >= wdd) { xc -= wdd; yy += 1; }
-        }
-        if (need_tables) {
-          const double* wt = sc.wtab + gi * 2 * (BR_MAX + 1);                // built by k_blur_weights
-          if (t <= r1) hw1[t] = wt[t];
-          if (t >= 64 && t - 64 <= r2 && r2 > 0) hw2[t - 64] = wt[(BR_MAX + 1) + t - 64];
-          need_tables = false;           // (the barrier after the tile load publishes the tables)
-          cur = item.x;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-          if (base + 256 * k < nx) X[base + 256 * k] = v[k];
-      }
-      {
-        const int nz2 = (yp * hop + 1) >> 1;              // Y := 0, two doubles per store (capacity is even: no overrun)
-        double2* Y2 = reinterpret_cast<double2*>(Y);
-        for (int i = t; i < nz2; i += 256) Y2[i] = make_double2(0.0, 0.0);
-      }
-      PH(0)                                         // plan, tables, raw sub-tile -> LDS (issue)
-      __syncthreads();
-      PH(1)                                         // barrier: the loads land
-      // axis 0 (rows, sigma = c): symmetric correlate1d.  A thread owns data column xc and FOUR consecutive
-      // rows; as the tap distance shrinks the upper/lower operand windows slide by one row, so each
-      // step needs two new LDS values instead of eight (register rotation).  Lanes run along x.
-      {
-        const int nrb = hop >> 2;
-        const int nv = nrb * wd;
-        for (int idx = t; idx < nv; idx += 256) {
-          const int rb = (int)(((float)idx + 0.5f) * inv_wd), xq = idx - rb * wd;
-          const double* c0 = X + (4 * rb + r1) * wd + xq;                     // centre of the first of the four rows
-          double acc0, acc1, acc2, acc3;
-          blur4(c0, wd, [&](int k) { return hw1[k]; }, r1, acc0, acc1, acc2, acc3);
-          double* o = Y + 4 * rb * yp + xa + xq;                              // Y has hop rows: the slack rows are never read
-          o[0] = acc0;
-          o[yp] = acc1;
-          o[2 * yp] = acc2;
-          o[3 * yp] = acc3;
-        }
-      }
-      PH(2)                                         // row pass
-      __syncthreads();
-      PH(3)
-      // axis 1 (columns, sigma = c/2): a thread owns row y and four consecutive columns; lanes run
-      // down the rows (odd pitch -> distinct banks).
-      {
-        const int ncb = (wo + 3) >> 2;
-        const int nh = ncb * ho;
-        const float inv_ho = 1.0f / (float)ho;
-        for (int idx = t; idx < nh; idx += 256) {
-          const int cb = (int)(((float)idx + 0.5f) * inv_ho), yq = idx - cb * ho;
-          const double* c0 = Y + yq * yp + 4 * cb + r2;                       // centre of the first of the four columns
-          double acc0, acc1, acc2, acc3;
-          if (r2 > 0) {
-            blur4(c0, 1, [&](int k) { return hw2[k]; }, r2, acc0, acc1, acc2, acc3);
-          } else {
-            acc0 = c0[0]; acc1 = c0[1]; acc2 = c0[2]; acc3 = c0[3];
-          }
-          const int xo = 4 * cb;
-          double* o = dst + (int64_t)(y0 + yq) * p.epitch + p.epad + (x0 + xo);
-          if (xo + 3 < wo) {
-            o[0] = acc0; o[1] = acc1; o[2] = acc2; o[3] = acc3;
-          } else {
-            o[0] = acc0;
-            if (xo + 1 < wo) o[1] = acc1;
-            if (xo + 2 < wo) o[2] = acc2;
-          }
-        }
-      }
-      PH(4)                                         // column pass + store
-      __syncthreads();
-      PH(5)
-    }
-  }
-  }
-  PH_FLUSH(3)
-}
-
-#endif
-
-// ---------------------------------------------------------------------------
-// fused defocus blur, staged by LDS-DMA a sub-tile ahead (r05; the default)
-// ---------------------------------------------------------------------------
-// k_blur_fused spends 47 % of its wave time in the load phase of a sub-tile (a round trip to memory through registers,
-// nothing else to do meanwhile) and its software-pipelined form died of register pressure (r04: 168 VGPRs).  gfx950's
-// LDS-DMA loads (global_load_lds_dword: every lane names a global address, the 64 dwords land side by side in LDS, no
-// register in between) make the pipeline free:
+// A workgroup takes (drop, sub-tile range) items grid-stride.  blur_layout cuts a drop's effective tile into sub-tiles whose
+// haloed input X and row-pass result Y fit the LDS capacities sc.blur_bx / blur_by (rr_device.h BLUR_BX / BLUR_BY: four
+// workgroups per CU, the register budget __launch_bounds__(256, 4) holds the kernel to).  LDS (dynamic): two generations of
+// weight tables hw1 | hw2, X[blur_bx], Y[blur_by].  Loaded through registers, a sub-tile's load phase is a round trip to
+// memory with nothing else to do (47 % of the wave time).  gfx950's LDS-DMA loads (global_load_lds_dword: every lane names
+// a global address, the 64 dwords land side by side in LDS, no register in between) make the pipeline free:
 //   barrier A | row pass (X, hw1 -> Y) | barrier B | ISSUE the next sub-tile's loads into X | column pass (Y, hw2 -> HBM)
 //   | barrier C | clear Y | wait for the loads, zero the halo rows | barrier A ...
 // X is dead after the row pass, so the next sub-tile's raw data (same item or the next item of the workgroup) travels
 // while the column pass, its stores and the clearing of Y run.  The weight tables of a new drop travel the same way into
 // the other of two table slots (the column pass still reads the current drop's hw2).
+//   * X holds only the data columns of the haloed sub-tile (those under the raw tile: a column without raw pixels stays
+//     exactly zero through the row pass); Y is cleared as a whole and the row pass writes its columns over it;
 //   * an element of X is two dwords: lanes 2j, 2j + 1 of a wave carry element j of its 32-element piece; a round of the four
-//     waves moves 128 consecutive elements of X; (row, column) of a lane's element by the incremental division of the
-//     r04 loader.  Rows of the haloed tile outside the raw tile are not loaded (lanes masked) and zeroed after the wait;
+//     waves moves 128 consecutive elements of X; (row, column) of a lane's element by one float division, the following
+//     ones incrementally.  Rows of the haloed tile outside the raw tile are not loaded (lanes masked) and zeroed after the wait;
 //   * the loads are issued by inline assembly (M0 = LDS address of the wave's piece): the compiler neither counts them nor
 //     orders LDS reads behind them -- a counted wait of its own can only wait longer; the one wait that matters is the
 //     explicit vmcnt(0) in front of barrier A;
 //   * item records and plans travel two items ahead (vector loads, fields by v_readlane), as the plan of the next item is
 //     needed a sub-tile early.
-// Arithmetic, fold order and the LDS images of X, Y and the tables are k_blur_fused's: the tiles are the same bits
-// (tests/test_gpu_properties.py, RR_OPT_BLUR_DMA 0 / 1).
 __device__ inline void glds_dword(const void* src, uint32_t lds_byte) {     // LDS[lds_byte + 4 * lane] <- *(const uint32_t*)src, asynchronously
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
@@ -3167,8 +2950,7 @@ __device__ inline void glds_dwordx4(const void* src, uint32_t lds_byte) {   // L
                : "v"(src), "s"(__builtin_amdgcn_readfirstlane((int)lds_byte))
                : "memory");
 }
-template <int WPE>
-__global__ __launch_bounds__(256, WPE) void k_blur_fused_dma(const FrameDesc* frames, int max_drops, Scratch sc) {
+__global__ __launch_bounds__(256, 4) void k_blur_fused_dma(const FrameDesc* frames, int max_drops, Scratch sc) {
   const int f = blockIdx.y, t = threadIdx.x, lane = t & 63, G = gridDim.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
@@ -3201,7 +2983,7 @@ __global__ __launch_bounds__(256, WPE) void k_blur_fused_dma(const FrameDesc* fr
     return make_int4((int)__builtin_amdgcn_readlane((int)iv, 0), (int)__builtin_amdgcn_readlane((int)iv, 1),
                      (int)__builtin_amdgcn_readlane((int)iv, 2), (int)__builtin_amdgcn_readlane((int)iv, 3));
   };
-  struct Geo {                        // one sub-tile (wave-uniform), k_blur_fused's quantities
+  struct Geo {                        // one sub-tile (wave-uniform)
     int y0, x0, ho, wo, hop, hi, yp, xa, wd, nx, xs, ys, e_lo, e_hi;
   };
   auto geo = [&](const PlanView& p, int Lwo, int Lho, int st) {
@@ -3321,7 +3103,10 @@ __global__ __launch_bounds__(256, WPE) void k_blur_fused_dma(const FrameDesc* fr
     PH(0)
     __syncthreads();                                      // A
     PH(1)
-    {                                                     // axis 0 (rows): as k_blur_fused
+    // axis 0 (rows, sigma = c): symmetric correlate1d.  A thread owns data column xq and FOUR consecutive rows; as the tap
+    // distance shrinks the upper / lower operand windows slide by one row, so each step needs two new LDS values instead of
+    // eight (register rotation).  Lanes run along x.
+    {
       const int wd = g.wd, nrb = g.hop >> 2, nv = nrb * wd;
       const float inv_wd = 1.0f / (float)imax(wd, 1);
       for (int idx = t; idx < nv; idx += 256) {
@@ -3345,7 +3130,9 @@ __global__ __launch_bounds__(256, WPE) void k_blur_fused_dma(const FrameDesc* fr
       stage(np, ng, nitem.x, ntb != tb, ntb);
     }
     PH(6)                                                 // the next sub-tile's loads issued
-    {                                                     // axis 1 (columns) -> global: as k_blur_fused
+    // axis 1 (columns, sigma = c/2) -> global: a thread owns row yq and four consecutive columns; lanes run down the rows
+    // (odd pitch -> distinct banks).
+    {
       const int ncb = (g.wo + 3) >> 2, nh = ncb * g.ho;
       const float inv_ho = 1.0f / (float)g.ho;
       double* dst = sc.arena + p.a1_off;
@@ -3730,7 +3517,7 @@ __global__ __launch_bounds__(256) void k_bin(const FrameDesc* frames, Dims dm, i
 // x 7200 drops per KITTI frame, two block barriers per 256 tests).  Here the drops are taken in segments of BIN_SEG: the
 // workgroup first keeps, in drop order, the ones that reach its 64-pixel row of the frame (a quarter of them) with their x
 // range in LDS; then every WAVE takes tiles of the row by itself and walks that short list with ballots -- no block barrier,
-// a third of the tests.  Same lists, same order (tests/test_gpu_properties.py compares every output with RR_OPT_BIN_ROWS 0).
+// a third of the tests.  Same lists, same order.
 constexpr int BIN_SEG = 8192;
 __global__ __launch_bounds__(256) void k_bin_rows(const FrameDesc* frames, Dims dm, int max_drops, int ctiles_x, int nct, Scratch sc) {
   const int f = blockIdx.y, cty = blockIdx.x;
@@ -4025,8 +3812,7 @@ __device__ inline float2_t pk_fma_clamp(float2_t a, float2_t b, float2_t c) {
   asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
 }
-template <int WPE, bool BATCH>      // WPE: waves per SIMD the register allocation is held to (RR_OPT_COMPOSITE_WAVES); BATCH: RR_OPT_COMPOSITE_BATCH
-__global__ __launch_bounds__(256, WPE) void k_composite32(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int tiles_x,
+__global__ __launch_bounds__(256, 5) void k_composite32(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int tiles_x,
                                                      int tiles_y, int ctiles_x, int nct, int64_t arena_cap, Scratch sc) {
   const int f = blockIdx.y;
   const int ntiles = tiles_x * tiles_y, per_xcd = (ntiles + 7) / 8;
@@ -4154,13 +3940,11 @@ __global__ __launch_bounds__(256, WPE) void k_composite32(const FrameDesc* frame
     PH(2)
     const int* lst = s_list[wave];
     total = __builtin_amdgcn_readfirstlane(total);
-    if constexpr (BATCH) {
-    // r05: the records of up to 64 list entries at a time live in twelve VECTOR registers, lane j holding entry j's (three
+    // The records of up to 64 list entries at a time live in twelve VECTOR registers, lane j holding entry j's (three
     // 16-byte loads per lane, all 64 records in flight at once), and an entry's fields reach the scalar registers by
     // v_readlane when they are needed.  The entry loop then holds no scalar load and no LDS read: nothing in it waits on
-    // lgkmcnt (the scalar record fetch of the r04 loop, issued a step ahead, had to be complete at the top of the next
-    // step -- scalar loads return out of order, any wait on them is a wait for all), one record set is live instead of
-    // three, and the alpha samples run TWO entries ahead of the blend instead of one.
+    // lgkmcnt (scalar loads return out of order, any wait on them is a wait for all), and the alpha samples run TWO entries
+    // ahead of the blend.
     for (int sub = 0; sub < total; sub += 64) {
       const int nb = imin(64, total - sub);
       const int my = lst[sub + imin(lane, nb - 1)];               // this lane's entry: its drop
@@ -4228,7 +4012,7 @@ __global__ __launch_bounds__(256, WPE) void k_composite32(const FrameDesc* frame
       issue(1, A10, A11, b1);
       // Whole triples in a loop without an early exit (a `break` between the steps becomes, after the compiler has
       // structurised the loop, an edge from the middle of the body back to its header -- never taken, but the wait-count
-      // pass then opens EVERY iteration with vmcnt(0): the r04 loop had that wait), the last one or two entries behind it.
+      // pass then opens EVERY iteration with vmcnt(0)), the last one or two entries behind it.
       // Every step issues exactly two loads: the counts are static.
       int e = 0;
       for (; e + 3 <= nb; e += 3) {
@@ -4246,106 +4030,16 @@ __global__ __launch_bounds__(256, WPE) void k_composite32(const FrameDesc* frame
       asm volatile("" ::"v"(A00), "v"(A01), "v"(A10), "v"(A11));
       PH(4)
     }
-    } else {
-    struct RecS {
-      uint32_t xx, yy;
-      int ox, oy, pitch, slow;
-      long long off;
-      float te, k0, k1, k2;
-      double z;
-    };
-    auto fetch = [&](int idx) {
-      const const_ptr<CompRec32> r = as_constant(comp) + __builtin_amdgcn_readfirstlane(idx);
-      const uint32_t ps = r->pitch_slow;
-      RecS o{r->xx, r->yy, 0, 0, (int)(ps & 0x7fffffffu), (int)(ps >> 31), (long long)r->base, r->te, r->kg[0], r->kg[1], r->kg[2], r->zdist};
-      return o;
-    };
-    // Three stages, as in k_composite: entry e is blended while the samples of entry e + 1 are in flight and the record of
-    // entry e + 2 is fetched.  Every lane loads two samples per entry (a pixel outside the footprint reads the tile's first
-    // sample -- one line for all of them -- and its value is replaced by 0), so the number of loads in flight is known.
-    auto step = [&](int e, const RecS& rcur, double Acur0, double Acur1, int icur, const RecS& rnext, double& An0, double& An1, int& inext,
-                    RecS& rfetch, int& i_nn, int& i_cur_next) {
-      {
-        const int x0 = (int)(rnext.xx & 0xffffu), x1 = (int)(rnext.xx >> 16), y0 = (int)(rnext.yy & 0xffffu), y1 = (int)(rnext.yy >> 16);
-        const bool inx = (px >= x0) & (px < x1) & (e + 1 < total);
-        const bool in0 = inx & live0 & (py0 >= y0) & (py0 < y1), in1 = inx & live1 & (py1 >= y0) & (py1 < y1);
-        // outside the footprint: the frame's zero line (k_scan) -- the sample IS 0.0, nothing to select afterwards
-        const int64_t o0 = in0 ? rnext.off + ((int64_t)(py0 + rnext.oy) * rnext.pitch + (px + rnext.ox)) : zero_at;
-        const int64_t o1 = in1 ? rnext.off + ((int64_t)(py1 + rnext.oy) * rnext.pitch + (px + rnext.ox)) : zero_at;
-        An0 = arena[o0];
-        An1 = arena[o1];
-        inext = (in0 ? 1 : 0) | (in1 ? 2 : 0);
-      }
-      rfetch = fetch(i_nn);
-      i_cur_next = i_nn;
-      i_nn = lst[e + 3 < total ? e + 3 : 0];
-      bool v0 = (icur & 1) != 0, v1 = (icur & 2) != 0;
-      if (has_depth) {                                            // depth-occlusion option: hidden where the drop is behind the scene
-        v0 = v0 && !(rcur.z > scene0);
-        v1 = v1 && !(rcur.z > scene1);
-      }
-      double A0 = Acur0, A1 = Acur1;                              // (0.0 outside the footprint)
-      if (has_depth) {
-        A0 = v0 ? Acur0 : 0.0;
-        A1 = v1 ? Acur1 : 0.0;
-      }
-      if (slow_wave | rcur.slow) {                                // (wave-uniform) literal float64 blend, pixel by pixel
-        const const_ptr<CompRec> r64 = as_constant(comp64) + __builtin_amdgcn_readfirstlane(icur >> 2);
-        const double K[3] = {r64->K[0], r64->K[1], r64->K[2]};
-        const double tau = r64->tau_one, g = r64->g;
-        if (v0) {
-          double c[3] = {(double)c0.x, (double)c1.x, (double)c2.x};
-          blend_pixel(Acur0, tau, cam.exposure_s, g, K, c, m0);
-          c0.x = (float)c[0]; c1.x = (float)c[1]; c2.x = (float)c[2];
-        }
-        if (v1) {
-          double c[3] = {(double)c0.y, (double)c1.y, (double)c2.y};
-          blend_pixel(Acur1, tau, cam.exposure_s, g, K, c, m1);
-          c0.y = (float)c[0]; c1.y = (float)c[1]; c2.y = (float)c[2];
-        }
-      } else {
-        const float2_t Af = {(float)A0, (float)A1};
-        const float2_t u = __builtin_elementwise_fma(Af, float2_t{-rcur.te, -rcur.te}, one2);      // 1 - A te
-        c0 = pk_fma_clamp(u, c0, Af * rcur.k0);                   // clamp((1 - A te) c + A kg, 0, 1)
-        c1 = pk_fma_clamp(u, c1, Af * rcur.k1);
-        c2 = pk_fma_clamp(u, c2, Af * rcur.k2);
-        m0 = m0 + A0;                                             // (+ 0.0 outside the footprint: the mask keeps its bits)
-        m1 = m1 + A1;
-      }
-    };
-    if (total > 0) {
-      // icur packs the two "inside" bits with the drop index (for the rare float64 path): (index << 2) | bits
-      int idx0 = lst[0], idx1 = lst[total > 1 ? 1 : 0];
-      RecS R0 = fetch(idx0), R1 = fetch(idx1), R2 = R0;
-      int i_nn = lst[total > 2 ? 2 : 0];
-      int in0 = 0, in1 = 0, in2 = 0, id0 = idx0, id1 = idx1, id2 = 0;
-      double A00, A01, A10 = 0.0, A11 = 0.0, A20 = 0.0, A21 = 0.0;
-      {
-        const int x0 = (int)(R0.xx & 0xffffu), x1 = (int)(R0.xx >> 16), y0 = (int)(R0.yy & 0xffffu), y1 = (int)(R0.yy >> 16);
-        const bool inx = (px >= x0) & (px < x1);
-        const bool a = inx & live0 & (py0 >= y0) & (py0 < y1), b = inx & live1 & (py1 >= y0) & (py1 < y1);
-        A00 = arena[a ? R0.off + ((int64_t)(py0 + R0.oy) * R0.pitch + (px + R0.ox)) : zero_at];
-        A01 = arena[b ? R0.off + ((int64_t)(py1 + R0.oy) * R0.pitch + (px + R0.ox)) : zero_at];
-        in0 = (a ? 1 : 0) | (b ? 2 : 0);
-      }
-      for (int e = 0; e < total; e += 3) {
-        step(e, R0, A00, A01, in0 | (id0 << 2), R1, A10, A11, in1, R2, i_nn, id2);
-        if (e + 1 >= total) break;
-        step(e + 1, R1, A10, A11, in1 | (id1 << 2), R2, A20, A21, in2, R0, i_nn, id0);
-        if (e + 2 >= total) break;
-        step(e + 2, R2, A20, A21, in2 | (id2 << 2), R0, A00, A01, in0, R1, i_nn, id1);
-      }
-    }
-    }
     PH(4)
     __syncthreads();
     PH(5)
   }
   // The composite before the mean shift goes to the library's scratch (this compositor only runs when no caller wants it):
-  // as three floats per pixel, or (r05, RR_OPT_COMPOSITE_U16, default) as three 16-bit codes in an 8-byte word -- one store per pixel, two thirds of the bytes here and in
-  // k_finalize.  A value in [0, 1] becomes rint(v * 65534) (error <= 2^-17, an LSB of the uint8 image is 2^-8); anything
-  // else -- only possible where no drop was blended, every blend ends with a clamp, or where the input was NaN -- becomes
-  // the code 65535: k_finalize then takes the pixel's channel from rainy_bg itself, which is what this lane holds.
+  // as three 16-bit codes in an 8-byte word -- one store per pixel, two thirds of the bytes of three floats here and in
+  // k_finalize16 -- or, with RR_OPT_WILD_PIXELS, as three floats.  A value in [0, 1] becomes rint(v * 65534) (error <=
+  // 2^-17, an LSB of the uint8 image is 2^-8); anything else -- only possible where no drop was blended, every blend ends
+  // with a clamp, or where the input was NaN -- becomes the code 65535: k_finalize16 then takes the pixel's channel from
+  // rainy_bg itself, which is what this lane holds.
   auto code16 = [](float v) -> uint32_t { return (v >= 0.f && v <= 1.f) ? (uint32_t)(v * 65534.0f + 0.5f) : 65535u; };
   // (r06) The tile's sums FIRST, the pixel stores last: __syncthreads() carries a full memory fence, and with the stores in
   // front of it every wave sat at the barrier until its six stores per lane had been acknowledged -- the phase clocks gave
@@ -4440,7 +4134,7 @@ __global__ __launch_bounds__(256) void k_means(Dims dm, int ntiles, Scratch sc) 
 }
 
 // generator.py:461-466 + matplotlib's float->uint8 truncation
-// The same for the 16-bit composite codes of k_composite32 (RR_OPT_COMPOSITE_U16), FOUR pixels per thread: 24 bytes in by
+// The same for the 16-bit composite codes of k_composite32, FOUR pixels per thread: 24 bytes in by
 // three 8-byte loads, 12 bytes out by one 12-byte store (a thread per pixel moved its 6 + 3 bytes with three 2-byte loads
 // and three byte stores and was slower than the float form it replaces, which reads twice the bytes).  The last pixels of a
 // frame (H * W is not a multiple of four) and a frame whose uint8 image does not start on a 4-byte boundary take scalar
@@ -5042,7 +4736,6 @@ struct rr_ctx {
   int64_t* d_tex_off = nullptr;
   uint8_t* d_tex_pad = nullptr;      // padded copies (k_pad_textures) + their offsets
   int64_t* d_tex_poff = nullptr;
-  bool padded_tex = true;            // RR_OPT_PADDED_TEXTURES
   uint8_t* d_tex_pair = nullptr;     // pair textures (k_pair_textures) + their offsets: what k_tile_rows stages
   int64_t* d_tex_qoff = nullptr;
   int tile_rows = 2;                 // RR_OPT_TILE_ROWS: rotate + INTER_AREA tiles by row walks, a wave per tile (k_tile_rows); 2: the Big (bicubic) tiles as well
@@ -5059,16 +4752,11 @@ struct rr_ctx {
   size_t pad_cap = 0;                // elements of each
   bool pipe_f32 = true;              // RR_OPT_PIPELINE_F32: float32 hand-over from the pre-pass to the hot path inside rr_pipeline_*
   bool dda_attr = false;
-  bool bin_rows = true;              // RR_OPT_BIN_ROWS
   int fill_rule = 1;                 // RR_OPT_FOV_FILL_RULE: 1 (default since r06) OpenCV's fillConvexPoly; 0 the span rule of rounds 1-5
-  bool composite_u16 = true;         // RR_OPT_COMPOSITE_U16
-  bool blur_dma = true;              // RR_OPT_BLUR_DMA
   int fov_dda = 1;                   // RR_OPT_FOV_DDA: a thread per drop for the polygons of the float colour branch (1: k_fov_dda, 2: k_fov_walk)
-  int comp_waves = 0;                // RR_OPT_COMPOSITE_WAVES: waves per SIMD the float compositor's registers are held to (0: the kernel's own choice)
   int colour_stream = 1;             // RR_OPT_COLOUR_STREAM: 0 one stream; 1 the FOV chain on a second stream
   hipStream_t s_col = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool comp_batch = true;            // RR_OPT_COMPOSITE_BATCH: list entries' records 64 at a time in vector registers, samples two entries ahead
   int n_tex = 0;
   std::vector<int32_t> h_tex_h, h_tex_w;   // host copies of the database's metadata (rr_bcast_streak_db hands them to the other contexts)
   std::vector<int64_t> h_tex_off;
@@ -5150,8 +4838,7 @@ struct rr_ctx {
   bool prof = false;
   // options (rr_set_option): none of them changes a result bit
   bool dedup = true;                 // RR_OPT_DEDUP: share bit-identical raw tiles inside a batch (k_dedup)
-  int fov_threads = 0, fov_dpt = 0;  // RR_OPT_FOV_THREADS / RR_OPT_FOV_DROPS_PER_THREAD: 0 = chosen by the library
-  int blur_wg = 0;                   // RR_OPT_BLUR_WORKGROUPS: workgroups per CU of the fused blur (3, 4 or 5); 0: the library's choice (4)
+  int fov_dpt = 0;                   // RR_OPT_FOV_DROPS_PER_THREAD: 0 = chosen by the library
   bool general_fov = false;          // RR_OPT_GENERAL_FOV: force the general colour path (prefix table in HBM)
   int fov_f32 = 2;                   // RR_OPT_FOV_F32: float32 vertices / prefix rows / sums in the colour branch (image within 1 LSB): 0 never,
                                      // 1 always, 2 (default) whenever the compositor blends float colours (no float64 composite asked for)
@@ -5483,7 +5170,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     fd.ext = in[f].ext;
     fd.colour_out = out[f].drop_colour;
     fd.n_drops_dev = in[f].n_drops_dev;
-    fd.comp_f32 = use32 ? ((ctx->composite_u16 && !ctx->wild_pixels) ? 2 : 1) : 0;
+    fd.comp_f32 = use32 ? (ctx->wild_pixels ? 1 : 2) : 0;
     fd.in_types = in[f].in_types;
     any_dev_count = any_dev_count || in[f].n_drops_dev;
     fd.n_drops = in[f].n_drops;
@@ -5499,19 +5186,18 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
   const int ntiles = tiles_x * tiles_y;
   Scratch sc = ctx->sc;
   sc.overflow = ctx->sc.overflow + ovf_idx;
-  sc.tex_pad = ctx->padded_tex ? ctx->d_tex_pad : nullptr;
+  sc.tex_pad = ctx->d_tex_pad;
   sc.tex_poff = ctx->d_tex_poff;
   sc.tex_pair = ctx->d_tex_pair;
   sc.tex_qoff = ctx->d_tex_qoff;
   sc.n_tex = ctx->n_tex;
   sc.rows_on = (ctx->tile_rows && ctx->d_tex_pair && ctx->n_tex <= RW_TEX_MAX) ? 1 : 0;
-  sc.big_on = (sc.rows_on && ctx->tile_rows >= 2 && ctx->padded_tex && ctx->d_tex_pad && 2 * ctx->n_tex <= RW_TEX_MAX) ? 1 : 0;
+  sc.big_on = (sc.rows_on && ctx->tile_rows >= 2 && 2 * ctx->n_tex <= RW_TEX_MAX) ? 1 : 0;
   sc.n_buckets = sc.big_on ? 2 * ctx->n_tex : ctx->n_tex;
   // k_tile_rows: one workgroup of 16 waves per CU (the LDS holds one texture + 16 wave-private tables); fewer for small batches
   const int rows_wgs = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ctx->n_cu, RW_SHARE_MAX / ctx->rows_shares), ((int64_t)n * max_drops + 31) / 32));
-  const int blur_wg = ctx->blur_wg ? ctx->blur_wg : 4;      // workgroups per CU the fused blur is sized for
-  sc.blur_bx = blur_wg == 3 ? 3072 : (blur_wg == 5 ? 2304 : 2816);
-  sc.blur_by = blur_wg == 5 ? 1600 : 2048;
+  sc.blur_bx = BLUR_BX;
+  sc.blur_by = BLUR_BY;
   // One in-order stream: FOV spans -> plan -> scan -> dedup -> lists -> FOV sums -> colour -> tiles -> blur ->
   // composite -> finalise.
   // Work-list kernels take their items grid-stride, the list lengths only exist on the device: with many frames per call
@@ -5602,8 +5288,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
       const size_t row_bytes = ((size_t)(dm.We + 1) * 2 + 16 * 2) * sizeof(double);      // P + wave totals
       // a wave owns ceil(We / waves) columns (rounded up to even), in passes of 128
       auto passes = [&](int nt) { return ((((dm.We + nt / 64 - 1) / (nt / 64)) + 1) / 2 * 2 + 127) / 128; };
-      int NT = ctx->fov_threads ? ctx->fov_threads : 1024;
-      if (passes(NT) > FOV_EMAX) NT = 1024;
+      const int NT = 1024;
       const bool e1 = passes(NT) <= 1;
       const int DPT = ctx->fov_dpt ? ctx->fov_dpt : (max_drops <= NT ? 1 : (max_drops <= 2 * NT ? 2 : (max_drops <= 4 * NT ? 4 : 8)));
       const int rpb = ((dm.He + COL_PARTS - 1) / COL_PARTS + 3) & ~3;
@@ -5717,19 +5402,9 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     }
     {
       ProfScope ps(ctx, s, "k_blur_fused");
-      const size_t lds = sizeof(double) * (size_t)(2 * (BR_MAX + 1) + sc.blur_bx + sc.blur_by);
+      const size_t lds = sizeof(double) * (size_t)(4 * (BR_MAX + 1) + sc.blur_bx + sc.blur_by);     // two generations of weight tables | X | Y
       const dim3 grid(imin((max_drops + 1) / 2, grid_cap(4096)), n);
-      if (ctx->blur_dma) {                                 // r05: staged a sub-tile ahead by LDS-DMA; + a second generation of weight tables
-        const size_t lds2 = lds + sizeof(double) * 2 * (BR_MAX + 1);
-        if (blur_wg == 3) hipLaunchKernelGGL(k_blur_fused_dma<3>, grid, dim3(256), lds2, s, ctx->d_frames, D, sc);
-        else if (blur_wg == 5) hipLaunchKernelGGL(k_blur_fused_dma<5>, grid, dim3(256), lds2, s, ctx->d_frames, D, sc);
-        else hipLaunchKernelGGL(k_blur_fused_dma<4>, grid, dim3(256), lds2, s, ctx->d_frames, D, sc);
-      }
-#ifdef RR_EXPERIMENTS
-      else if (blur_wg == 3) hipLaunchKernelGGL(k_blur_fused<3>, grid, dim3(256), lds, s, ctx->d_frames, D, sc);
-      else if (blur_wg == 5) hipLaunchKernelGGL(k_blur_fused<5>, grid, dim3(256), lds, s, ctx->d_frames, D, sc);
-      else hipLaunchKernelGGL(k_blur_fused<4>, grid, dim3(256), lds, s, ctx->d_frames, D, sc);
-#endif
+      hipLaunchKernelGGL(k_blur_fused_dma, grid, dim3(256), lds, s, ctx->d_frames, D, sc);
     }
     {
       ProfScope ps(ctx, s, "k_blur_big_weights");
@@ -5752,7 +5427,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
   const int ctiles_x = (dm.W + CTILE - 1) / CTILE, nct = ctiles_x * ((dm.H + CTILE - 1) / CTILE);
   {
     ProfScope ps(ctx, s, "k_bin");
-    if (ctx->bin_rows && ctiles_x <= 64)
+    if (ctiles_x <= 64)                                    // (k_bin_rows: up to 64 coarse tiles per row, frames up to 4096 px wide)
       hipLaunchKernelGGL(k_bin_rows, dim3(nct / ctiles_x, n), dim3(256), 0, s, ctx->d_frames, dm, D, ctiles_x, nct, sc);
     else
       hipLaunchKernelGGL(k_bin, dim3(nct, n), dim3(256), 0, s, ctx->d_frames, dm, D, ctiles_x, nct, sc);
@@ -5783,14 +5458,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     ntiles_c = tiles_x * tiles_y32;
     ProfScope ps(ctx, s, "k_composite");
     const dim3 grid(((ntiles_c + 7) / 8) * 8, n);
-#define RR_COMP32(W, B) hipLaunchKernelGGL((k_composite32<W, B>), grid, dim3(256), 0, s, ctx->d_frames, dm, ctx->cam, D, tiles_x, tiles_y32, ctiles_x, nct, ctx->arena_cap, sc)
-    const int cw = ctx->comp_waves ? ctx->comp_waves : (ctx->comp_batch ? 5 : 6);
-    if (ctx->comp_batch) {
-      if (cw == 8) RR_COMP32(8, true); else if (cw == 7) RR_COMP32(7, true); else if (cw == 6) RR_COMP32(6, true); else if (cw == 5) RR_COMP32(5, true); else RR_COMP32(4, true);
-    } else {
-      if (cw == 8) RR_COMP32(8, false); else if (cw == 7) RR_COMP32(7, false); else RR_COMP32(6, false);
-    }
-#undef RR_COMP32
+    hipLaunchKernelGGL(k_composite32, grid, dim3(256), 0, s, ctx->d_frames, dm, ctx->cam, D, tiles_x, tiles_y32, ctiles_x, nct, ctx->arena_cap, sc);
   } else {
     ProfScope ps(ctx, s, "k_composite");
     hipLaunchKernelGGL(k_composite, dim3(((ntiles + 7) / 8) * 8, n), dim3(256), 0, s, ctx->d_frames, dm, ctx->cam, D, tiles_x, tiles_y, ctiles_x, nct,
@@ -5802,7 +5470,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
   }
   {
     ProfScope ps(ctx, s, "k_finalize");
-    if (use32 && ctx->composite_u16 && !ctx->wild_pixels)       // (every frame's comp_f32 is 2: the coded composite, four pixels per thread)
+    if (use32 && !ctx->wild_pixels)                        // (every frame's comp_f32 is 2: the coded composite, four pixels per thread)
       hipLaunchKernelGGL(k_finalize16, dim3((unsigned)(((int64_t)dm.H * dm.W + 1023) / 1024), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
     else
       hipLaunchKernelGGL(k_finalize, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
@@ -6237,6 +5905,7 @@ const char* rr_last_error(rr_ctx* ctx) { return ctx ? ctx->err.c_str() : "null c
 
 static int set_db_meta(rr_ctx* ctx, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off, int32_t n_tex) {
   int rc;
+  ctx->have_db = false;                 // until every table below exists: the tile kernels stage from the padded copies
   if ((rc = dev_alloc(ctx, ctx->d_tex_h, (size_t)n_tex))) return rc;
   if ((rc = dev_alloc(ctx, ctx->d_tex_w, (size_t)n_tex))) return rc;
   if ((rc = dev_alloc(ctx, ctx->d_tex_off, (size_t)n_tex))) return rc;
@@ -6247,7 +5916,6 @@ static int set_db_meta(rr_ctx* ctx, const int32_t* tex_h, const int32_t* tex_w, 
   ctx->h_tex_h.assign(tex_h, tex_h + n_tex);
   ctx->h_tex_w.assign(tex_w, tex_w + n_tex);
   ctx->h_tex_off.assign(tex_off, tex_off + n_tex);
-  ctx->have_db = true;
   {                                     // the padded copies k_tile / k_tile_generic stage from
     std::vector<int64_t> poff((size_t)n_tex);
     int64_t total = 0;
@@ -6291,6 +5959,7 @@ static int set_db_meta(rr_ctx* ctx, const int32_t* tex_h, const int32_t* tex_w, 
     if ((rc = dev_alloc(ctx, ctx->d_ratio_db, r.size() < 4 ? 4 : r.size()))) return rc;
     HIPCHK(hipMemcpy(ctx->d_ratio_db, r.data(), sizeof(double) * r.size(), hipMemcpyHostToDevice));
   }
+  ctx->have_db = true;
   return RR_OK;
 }
 
@@ -7389,29 +7058,13 @@ int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value) {
     case RR_OPT_DEPTH_OCCLUSION: ctx->depth_occlusion = value != 0; return RR_OK;
     case RR_OPT_COMPOSITE_F64: ctx->composite_f64 = value != 0; return RR_OK;
     case RR_OPT_COPY_KERNELS: ctx->copy_kernels = value != 0; return RR_OK;
-    case RR_OPT_PADDED_TEXTURES: ctx->padded_tex = value != 0; return RR_OK;
     case RR_OPT_TILE_ROWS: ctx->tile_rows = value < 0 ? 0 : (value > 2 ? 2 : value); return RR_OK;
     case RR_OPT_ROWS_SHARES: ctx->rows_shares = value < 1 ? 1 : (value > 8 ? 8 : value); return RR_OK;
     case RR_OPT_FOV_FILL_RULE: ctx->fill_rule = value == 1 ? 1 : 0; return RR_OK;
-    case RR_OPT_BIN_ROWS: ctx->bin_rows = value != 0; return RR_OK;
-    case RR_OPT_COMPOSITE_U16: ctx->composite_u16 = value != 0; return RR_OK;
-    case RR_OPT_BLUR_DMA:
-#ifdef RR_EXPERIMENTS
-      ctx->blur_dma = value != 0;
-      return RR_OK;
-#else
-      if (value == 0) break;                                  // the register-staged kernel is only in -DRR_EXPERIMENTS builds
-      return RR_OK;
-#endif
     case RR_OPT_FOV_DDA: ctx->fov_dda = value != 0 ? 1 : 0; return RR_OK;       // (2 was k_fov_walk, r05: measured, no faster, removed in r06)
     case RR_OPT_PIPELINE_F32: ctx->pipe_f32 = value != 0; return RR_OK;
     case RR_OPT_WILD_PIXELS: ctx->wild_pixels = value != 0; return RR_OK;
     case RR_OPT_PNG_DEFLATE: ctx->png_deflate = value != 0; return RR_OK;
-    case RR_OPT_COMPOSITE_WAVES:
-      if (value != 0 && (value < 4 || value > 8)) break;
-      ctx->comp_waves = value;
-      return RR_OK;
-    case RR_OPT_COMPOSITE_BATCH: ctx->comp_batch = value != 0; return RR_OK;
     case RR_OPT_COLOUR_STREAM:
       if (value < 0 || value > 2) break;
       ctx->colour_stream = value ? 1 : 0;                   // (2: r05's other split, measured slower and removed in r06 -- runs as 1)
@@ -7420,18 +7073,19 @@ int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value) {
       if (value < 0 || value > 2) break;
       ctx->fov_f32 = value;
       return RR_OK;
-    case RR_OPT_FOV_THREADS:
-      if (value != 0 && value != 512 && value != 1024) break;
-      ctx->fov_threads = value;
-      return RR_OK;
-    case RR_OPT_BLUR_WORKGROUPS:
-      if (value != 0 && value != 3 && value != 4 && value != 5) break;
-      ctx->blur_wg = value;
-      return RR_OK;
     case RR_OPT_FOV_DROPS_PER_THREAD:
       if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) break;
       ctx->fov_dpt = value;
       return RR_OK;
+    // retired (include/rainhip.h): only the value the library runs with is accepted, and it changes nothing
+    case RR_OPT_PADDED_TEXTURES: case RR_OPT_COMPOSITE_U16: case RR_OPT_BLUR_DMA: case RR_OPT_BIN_ROWS: case RR_OPT_COMPOSITE_BATCH:
+      if (value != 1) break;
+      return RR_OK;
+    case RR_OPT_FOV_THREADS: case RR_OPT_BLUR_WORKGROUPS: case RR_OPT_COMPOSITE_WAVES: {        // 0 = the library's choice
+      const int32_t own = option == RR_OPT_FOV_THREADS ? 1024 : (option == RR_OPT_BLUR_WORKGROUPS ? 4 : 0);
+      if (value != 0 && value != own) break;
+      return RR_OK;
+    }
     default: break;
   }
   ctx->err = "rr_set_option: unknown option or value";

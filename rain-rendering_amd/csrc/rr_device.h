@@ -1531,10 +1531,12 @@ RR_HD void blend_pixel(double A, double tau_one, double exposure, double g, cons
 // (tests/test_blur_layout.py sweeps these on the host: every sub-tile must fit the capacities)
 // ---------------------------------------------------------------------------
 // blur work layout (needed by k_colour to know where the finished tile will live)
-// LDS capacities of the fused blur (doubles): input sub-tile incl. halo / result of the row (axis 0) pass.  They set how
-// many workgroups share a CU (160 KB of LDS; the kernel is compiled for the matching register budget):
-//   3 per CU: 3072 + 2048     4 per CU: 2816 + 2048 (default)     5 per CU: 2304 + 1600
-// Smaller tiles mean more sub-tiles per drop (more halo re-loaded), more workgroups mean better latency hiding.
+// LDS capacities of the fused blur (doubles): input sub-tile incl. halo / result of the row (axis 0) pass.  With the two
+// generations of weight tables in front they let four workgroups share a CU (160 KB of LDS), the register budget
+// k_blur_fused_dma is compiled for.  Smaller tiles mean more sub-tiles per drop (more halo re-loaded), more workgroups
+// mean better latency hiding.
+constexpr int BLUR_BX = 2816;
+constexpr int BLUR_BY = 2048;
 constexpr int BR_MAX = 48;          // largest axis-0 radius the fused kernel takes
 
 struct BlurLayout {

@@ -514,7 +514,7 @@ int emu_prepass(int H, int W, const void* bg, const void* depth, int depth_f64, 
 }
 
 // The blur work split of one drop (rr_device.h: blur_is_small, blur_layout).  out = {small, fused, wo, ho}; returns the
-// number of sub-tiles whose LDS footprint -- computed the way k_blur_fused / k_blur_small index their tiles --
+// number of sub-tiles whose LDS footprint -- computed the way k_blur_fused_dma / k_blur_small index their tiles --
 // exceeds a capacity (must be 0).
 int emu_blur_layout(int ew, int eh, int r1, int r2, int tw, int th, int bx, int by, int32_t* out) {
   DropPlan p{};
@@ -526,7 +526,7 @@ int emu_blur_layout(int ew, int eh, int r1, int r2, int tw, int th, int bx, int 
   if (small) {                                     // k_blur_small: X = tw x (php + 2 r1), Y = pitch x php
     const int php = (eh + 3) & ~3;
     if (tw * (php + 2 * r1) > BS_X || blur_y_pitch(ew, r2) * php > BS_Y || r1 > 63 || r2 > 63) bad++;
-  } else if (L.fused) {                            // k_blur_fused: per sub-tile X = wd x (hop + 2 r1), Y = pitch x hop
+  } else if (L.fused) {                            // k_blur_fused_dma: per sub-tile X = wd x (hop + 2 r1), Y = pitch x hop
     if (L.wo < 1 || L.ho < 1 || L.wo > 0xffff || L.ho > 0x7fff) return 1 << 30;
     const int ntx = (ew + L.wo - 1) / L.wo, nty = (eh + L.ho - 1) / L.ho;
     for (int sty = 0; sty < nty; sty++)
@@ -541,6 +541,12 @@ int emu_blur_layout(int ew, int eh, int r1, int r2, int tw, int th, int bx, int 
       }
   }
   return bad;
+}
+
+// The LDS capacities the library launches the fused blur with (rr_device.h): out = {BLUR_BX, BLUR_BY}.
+void emu_blur_capacities(int32_t* out) {
+  out[0] = BLUR_BX;
+  out[1] = BLUR_BY;
 }
 
 // The compositor's short blend divides by the launch's exposure through its reciprocal: q0 = a * y, q = fma(fma(-q0, d, a), y, q0)

@@ -1,13 +1,12 @@
 """CPU tier: the defocus-blur work split (rr_device.h: blur_is_small / blur_layout, compiled for the host by
 tests/hostemu) swept over tile shapes and radii: every sub-tile the blur kernels would stage must fit the LDS capacities
-they are launched with, for each of the three capacity presets (RR_OPT_BLUR_WORKGROUPS 3 / 4 / 5)."""
+they are launched with (rr_device.h BLUR_BX / BLUR_BY, exported by the host build)."""
 import ctypes
 import os
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-PRESETS = ((3072, 2048), (2816, 2048), (2304, 1600))       # rainhip.hip: enqueue(), blur_wg = 3, 4, 5
 
 
 def _lib():
@@ -16,11 +15,23 @@ def _lib():
     lib = ctypes.CDLL(os.path.join(HERE, 'hostemu', 'libhostemu.so'))
     lib.emu_blur_layout.argtypes = [ctypes.c_int] * 8 + [ctypes.c_void_p]
     lib.emu_blur_layout.restype = ctypes.c_int
+    lib.emu_blur_capacities.argtypes = [ctypes.c_void_p]
+    lib.emu_blur_capacities.restype = None
     return lib
+
+
+def _capacities(lib):
+    cap = np.zeros(2, np.int32)
+    lib.emu_blur_capacities(cap.ctypes.data)
+    return int(cap[0]), int(cap[1])
 
 
 def test_every_subtile_fits_the_lds_capacities():
     lib = _lib()
+    bx, by = _capacities(lib)
+    # four workgroups per CU: two generations of weight tables (2 x 2 x 49 doubles) + X + Y in a quarter of 160 KB of LDS;
+    # Y is cleared two doubles per store
+    assert 8 * (4 * 49 + bx + by) <= 160 * 1024 // 4 and by % 2 == 0, (bx, by)
     out = np.zeros(4, np.int32)
     rng = np.random.RandomState(11)
     cases = []
@@ -38,14 +49,13 @@ def test_every_subtile_fits_the_lds_capacities():
     n_small = n_fused = n_slow = 0
     for (tw, th, r1, r2) in cases:
         ew, eh = tw + 2 * r2, th + 2 * r1
-        for bx, by in PRESETS:
-            bad = lib.emu_blur_layout(ew, eh, r1, r2, tw, th, bx, by, out.ctypes.data)
-            assert bad == 0, (tw, th, r1, r2, bx, by, out.tolist(), bad)
-            small, fused, wo, ho = out.tolist()
-            if r1 > 48:
-                assert not fused and not small, (tw, th, r1, r2)
-            if fused and not small:
-                assert 1 <= wo <= ew and 1 <= ho <= eh
+        bad = lib.emu_blur_layout(ew, eh, r1, r2, tw, th, bx, by, out.ctypes.data)
+        assert bad == 0, (tw, th, r1, r2, bx, by, out.tolist(), bad)
+        small, fused, wo, ho = out.tolist()
+        if r1 > 48:
+            assert not fused and not small, (tw, th, r1, r2)
+        if fused and not small:
+            assert 1 <= wo <= ew and 1 <= ho <= eh
         n_small += small
         n_fused += bool(fused and not small)
         n_slow += bool(not fused and not small)
@@ -56,7 +66,8 @@ def test_kitti_shaped_drops_mostly_take_one_band():
     """The shapes the 100 mm/hr KITTI workload is made of (raw tile ~17x30, radii ~10 / 5): the default capacities take
     the median drop in one piece."""
     lib = _lib()
+    bx, by = _capacities(lib)
     out = np.zeros(4, np.int32)
-    assert lib.emu_blur_layout(15 + 10, 27 + 18, 9, 5, 15, 27, 2816, 2048, out.ctypes.data) == 0
+    assert lib.emu_blur_layout(15 + 10, 27 + 18, 9, 5, 15, 27, bx, by, out.ctypes.data) == 0
     small, fused, wo, ho = out.tolist()
     assert (small, fused) == (0, 1) and (wo, ho) == (25, 45)

@@ -97,17 +97,14 @@ def test_raw_tile_dedup_is_invisible(setup):
         assert np.array_equal(two[0][k], base[k]) and np.array_equal(two[1][k], base[k]), k
 
 
-def test_colour_path_options_do_not_change_results(setup):
-    """The FOV-sum kernel's workgroup size / drops per thread, the LDS tile sizes of the fused blur and the general colour path (prefix table in HBM, what
-    maps beyond 1024 rows / 4096 columns take) are tuning switches: the mask must be identical, the image within
-    1 LSB (the colour sums are added in a different order), the statuses equal."""
+def test_fov_options_and_retired_options(setup):
+    """The FOV-sum kernel's drops per thread and the general colour path (prefix table in HBM, what maps beyond 1024 rows /
+    4096 columns take): the mask must be identical, the image within 1 LSB (the colour sums are added in a different
+    order), the statuses equal.  The retired options accept only the value the library runs with, which changes no bit."""
     sc, bg, env, drops, rh, base = setup
     fr = dict(bg=bg, rainy_bg=bg, env_xyY=env, omega=sc.omega, drops=drops)
-    for opts in ({h.hb.RR_OPT_FOV_THREADS: 512, h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 1},
-                 {h.hb.RR_OPT_FOV_THREADS: 512, h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 4},
-                 {h.hb.RR_OPT_FOV_THREADS: 1024, h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 2},
-                 {h.hb.RR_OPT_FOV_THREADS: 1024, h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 8},
-                 {h.hb.RR_OPT_BLUR_WORKGROUPS: 3}, {h.hb.RR_OPT_BLUR_WORKGROUPS: 5},
+    for opts in ({h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 1}, {h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 2},
+                 {h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 4}, {h.hb.RR_OPT_FOV_DROPS_PER_THREAD: 8},
                  {h.hb.RR_OPT_GENERAL_FOV: 1}):
         alt = h.hb.RainHip(0)
         try:
@@ -122,10 +119,17 @@ def test_colour_path_options_do_not_change_results(setup):
         assert np.array_equal(out['mask'], base['mask']) and np.array_equal(out['mask_i32'], base['mask_i32']), opts
         assert np.abs(out['image_u8'].astype(int) - base['image_u8'].astype(int)).max() <= 1, opts
         assert np.abs(out['rainy_bg'] - base['rainy_bg']).max() < 1e-9, opts
-    # texture staging from the pre-padded copies (default) or byte by byte: the same LDS bytes, so every output bit equal
+    # retired options: (option, the accepted value, another value)
+    retired = ((h.hb.RR_OPT_FOV_THREADS, 1024, 512), (h.hb.RR_OPT_BLUR_WORKGROUPS, 4, 5),
+               (h.hb.RR_OPT_PADDED_TEXTURES, 1, 0), (h.hb.RR_OPT_COMPOSITE_WAVES, 0, 6),
+               (h.hb.RR_OPT_COMPOSITE_U16, 1, 0), (h.hb.RR_OPT_BLUR_DMA, 1, 0),
+               (h.hb.RR_OPT_BIN_ROWS, 1, 0), (h.hb.RR_OPT_COMPOSITE_BATCH, 1, 0))
     alt = h.hb.RainHip(0)
     try:
-        alt.set_option(h.hb.RR_OPT_PADDED_TEXTURES, 0)
+        for opt, ok, bad in retired:
+            alt.set_option(opt, ok)
+            with pytest.raises(RuntimeError):
+                alt.set_option(opt, bad)
         alt.set_streak_db(sc.db.streaks_light)
         alt.set_camera(sc.cam)
         out = alt.render_frames([fr])[0]
@@ -253,14 +257,11 @@ def test_thread_per_drop_polygons_equal_the_edge_parallel_kernel(setup, tmp_path
                 assert np.array_equal(outs[0][k], outs[1][k]), (rule, k)
 
 
-def test_composite_codes_and_blur_prefetch(setup):
-    """r05 tuning switches of the float-colour route.  RR_OPT_BLUR_DMA (the fused blur's sub-tiles staged a sub-tile ahead by
-    LDS-DMA loads), RR_OPT_BIN_ROWS (how the ordered per-tile drop lists are made) and RR_OPT_COMPOSITE_BATCH (how the
-    compositor gets at its list entries' records) and RR_OPT_COLOUR_STREAM (which of the step's two chains runs on the library's
-    second stream, or everything on one in-order stream) change no bit.  RR_OPT_COMPOSITE_U16 (the composite before the mean shift as 16-bit codes
-    instead of floats) keeps mask and statuses and moves the uint8 image by at most 1 LSB on a few pixels in a thousand;
-    values outside [0, 1] -- a pixel no drop was blended into -- go through the code 65535 and come out as
-    before."""
+def test_colour_stream_and_composite_codes(setup):
+    """The float-colour route.  RR_OPT_COLOUR_STREAM (which of the step's two chains runs on the library's second stream, or
+    everything on one in-order stream) changes no bit.  The composite before the mean shift is kept as 16-bit codes; values
+    outside [0, 1] -- a pixel no drop was blended into -- go through the code 65535 and come out as the float64
+    compositor's: mask and statuses the same, the uint8 image within 1 LSB."""
     sc, bg, env, drops, rh, base = setup
     fr = dict(bg=bg, rainy_bg=bg, env_xyY=env, omega=sc.omega, drops=drops)
     wild = bg.copy()
@@ -270,52 +271,36 @@ def test_composite_codes_and_blur_prefetch(setup):
     wild[310:320, 40:50] = 0.0
     frw = dict(fr, bg=wild, rainy_bg=wild)
     ref = rh.render_frames([fr, frw], want_composite=False)
-    for opt, off, on in ((h.hb.RR_OPT_BLUR_DMA, 0, 1), (h.hb.RR_OPT_BIN_ROWS, 0, 1), (h.hb.RR_OPT_COMPOSITE_BATCH, 0, 1),
-                         (h.hb.RR_OPT_COLOUR_STREAM, 0, 1), (h.hb.RR_OPT_COMPOSITE_U16, 0, 1)):
-        try:
-            rh.set_option(opt, off)
-        except RuntimeError:
-            assert opt == h.hb.RR_OPT_BLUR_DMA         # r04's register-staged kernel: -DRR_EXPERIMENTS builds only (r06)
-            continue
-        try:
-            alt = rh.render_frames([fr, frw], want_composite=False)
-        finally:
-            rh.set_option(opt, on)
-        for a, b in zip(ref, alt):
-            for k in ('status', 'mask', 'mask_i32'):
-                assert np.array_equal(a[k], b[k]), (opt, k)
-            d = np.abs(a['image_u8'].astype(int) - b['image_u8'].astype(int))
-            if opt != h.hb.RR_OPT_COMPOSITE_U16:
-                assert d.max() == 0
-            else:
-                assert d.max() <= 1 and (d != 0).mean() < 4e-3, (d.max(), (d != 0).mean())
+    rh.set_option(h.hb.RR_OPT_COLOUR_STREAM, 0)
+    try:
+        alt = rh.render_frames([fr, frw], want_composite=False)
+    finally:
+        rh.set_option(h.hb.RR_OPT_COLOUR_STREAM, 1)
+    for a, b in zip(ref, alt):
+        for k in ('status', 'mask', 'mask_i32', 'image_u8'):
+            assert np.array_equal(a[k], b[k]), k
+    # the wild-valued frame through the 16-bit codes against the float64 compositor of the same frame
+    w64 = rh.render_frames([frw], want_composite=True)[0]
+    for k in ('status', 'mask', 'mask_i32'):
+        assert np.array_equal(ref[1][k], w64[k]), k
+    assert np.abs(ref[1]['image_u8'].astype(int) - w64['image_u8'].astype(int)).max() <= 1
     # the coded composite against the float64 compositor and the host build (the 1-LSB bar of BASELINE.json)
     assert np.abs(ref[0]['image_u8'].astype(int) - base['image_u8'].astype(int)).max() <= 1
 
 
-def test_compositor_record_batches(setup):
-    """The float compositor holds the records of 64 list entries at a time (RR_OPT_COMPOSITE_BATCH) and takes a coarse tile's
-    list in pieces of 256.  A frame whose drops are 100 streaks repeated 80 times makes every list that is not empty longer
-    than a batch and many longer than a piece: same bits as the entry-at-a-time compositor at every register allocation,
-    and the mask of the float64 compositor."""
+def test_compositor_long_lists_match_float64(setup):
+    """The float compositor holds the records of 64 list entries at a time and takes a coarse tile's list in pieces of 256.
+    A frame whose drops are 100 streaks repeated 80 times makes every list that is not empty longer than a batch and many
+    longer than a piece: the mask and statuses of the float64 compositor, the image within 1 LSB."""
     sc, bg, env, drops, rh, base = setup
     dense = np.concatenate([drops[:100]] * 80)
     fr = dict(bg=bg, rainy_bg=bg, env_xyY=env, omega=sc.omega, drops=dense)
     ref = rh.render_frames([fr], want_composite=False)[0]
     f64 = rh.render_frames([fr])[0]
     assert np.array_equal(ref['mask'], f64['mask']) and np.array_equal(ref['status'], f64['status'])
+    assert np.array_equal(ref['mask_i32'], f64['mask_i32'])
     assert np.abs(ref['image_u8'].astype(int) - f64['image_u8'].astype(int)).max() <= 1
     assert ref['mask'].max() > 40.0                                       # (80 copies of a streak on top of each other)
-    for batch, waves in ((0, 0), (0, 8), (1, 4), (1, 6), (1, 8)):
-        rh.set_option(h.hb.RR_OPT_COMPOSITE_BATCH, batch)
-        rh.set_option(h.hb.RR_OPT_COMPOSITE_WAVES, waves)
-        try:
-            alt = rh.render_frames([fr], want_composite=False)[0]
-        finally:
-            rh.set_option(h.hb.RR_OPT_COMPOSITE_BATCH, 1)
-            rh.set_option(h.hb.RR_OPT_COMPOSITE_WAVES, 0)
-        for k in ('status', 'mask', 'mask_i32', 'image_u8'):
-            assert np.array_equal(ref[k], alt[k]), (batch, waves, k)
 
 
 def test_fill_rule_option(setup):
