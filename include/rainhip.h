@@ -453,8 +453,8 @@ int rr_host_free(rr_ctx* ctx, void* p);
 
 /* Work-list sizes of frame `frame` of the last batch (after completion): out[0] drops whose raw tile went
  * through the rotate+resize kernels (k_tile_rows + k_tile), [1] through the generic kernel, [2] fused-blur work items, [3] slow-blur
- * drops, [4] small-blur drops, [5] Big drops (bicubic warp kernel), [6] their pixels, [7] drops that re-used
- * another drop's bit-identical raw tile (k_dedup). */
+ * drops, [4] small-blur drops, [5] Big drops (bicubic warp: k_tile_big and, with RR_OPT_TILE_ROWS 2, k_tile_rows), [6] the
+ * pixels of those Big tiles (sum of tw x th), [7] drops that re-used another drop's bit-identical raw tile (k_dedup). */
 int rr_batch_counts(rr_ctx* ctx, int32_t frame, int32_t out[8]);
 
 /* Per-kernel timing with HIP events on the launch stream (off by default). */

@@ -249,7 +249,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   int4* bbox;                       // [frame][drops] footprint (x0,y0,x1,y1), empty when not composited
   uint16_t* clist;                  // [frame][coarse tiles][drops] ordered drop indices per 64x64 coarse tile
   int32_t* ccount;                  // [frame][coarse tiles]
-  int32_t* counts;                  // [frame][8] = #rot, #gen, #blur items, #slow, #small, -, -, #duplicate raw tiles
+  int32_t* counts;                  // [frame][8] = #rot, #gen, #blur items, #slow, #small, #big, their pixels (k_tile_big), #duplicate raw tiles
   int32_t* list_big;                // [frame][drops] Big drops (bicubic warp) rendered by k_tile_big, one thread per pixel
   int32_t* big_off;                 // [frame][drops+1] exclusive prefix of their tile sizes, in pixels
   int32_t* bigs_list;               // [frame][drops] the frame's Big drops (k_plan) for k_plan_big: the 8 x 8 solve of their homography
@@ -261,7 +261,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   int32_t blur_bx, blur_by;         // LDS capacities (doubles) of the fused blur's two staging tiles (rr_device.h BLUR_BX / BLUR_BY)
   // k_tile_rows (r06): the rotate + INTER_AREA tiles of the WHOLE batch in one list, bucketed by texture
   int32_t* rows_list;               // [frame][drops] frame-local indices of the drops k_tile_rows renders (k_lists)
-  int32_t* rows_n;                  // [frame][2] their number: rotate + INTER_AREA tiles, Big tiles
+  int32_t* rows_n;                  // [frame][3] their number: rotate + INTER_AREA tiles, Big tiles; the Big tiles' pixels
   int32_t* rows_hist;               // [RW_TEX_MAX] tiles per texture, batch-wide (zeroed per call)
   unsigned long long* rows_cost;    // [RW_TEX_MAX] their estimated cost (behind rows_hist: one memset)
   int32_t* rows_next;               // [1] the next share of the list (behind rows_cost: the same memset)
@@ -2672,8 +2672,8 @@ __global__ __launch_bounds__(1024) void k_lists(const FrameDesc* frames, int max
     __syncthreads();
   }
   // #rot-fast (general), #generic, #fused blur items, #slow blur, #small blur, #rot-fast (integer ratio), #big, big pixels, #row-walk tiles
-  constexpr int NC = 10;             // (+ Big tiles that ride in the row-walk list)
-  int c[NC] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  constexpr int NC = 11;             // (+ Big tiles that ride in the row-walk list, and their pixels)
+  int c[NC] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = i0; i < i1; i++) {
     const uint4 r = sc.lrec[base + i];
     const uint32_t cls = r.x & 15u, bcls = (r.x >> 4) & 7u;
@@ -2682,6 +2682,7 @@ __global__ __launch_bounds__(1024) void k_lists(const FrameDesc* frames, int max
     if (sc.canon[base + i] == (int)(base + i)) {         // duplicates of another drop's raw tile render nothing
       if (cls == LC_BIG_LDS) {
         c[9]++;
+        c[10] += sc.plan[base + i].tw * sc.plan[base + i].th;     // (r.y holds its cost, not its pixels)
         atomicAdd(&s_hist[sc.n_tex + tex], 1);
         atomicAdd(&s_cost[sc.n_tex + tex], (int)r.y);
       } else if (cls == LC_BIG) { c[6]++; c[7] += (int)r.y; }
@@ -2702,7 +2703,7 @@ __global__ __launch_bounds__(1024) void k_lists(const FrameDesc* frames, int max
   for (int k = 0; k < NC; k++) sh[t][k] = c[k];
   __syncthreads();
   for (int ofs = 1; ofs < 1024; ofs <<= 1) {
-    int v[NC] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int v[NC] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (t >= ofs)
       for (int k = 0; k < NC; k++) v[k] = sh[t - ofs][k];
     __syncthreads();
@@ -2757,8 +2758,9 @@ __global__ __launch_bounds__(1024) void k_lists(const FrameDesc* frames, int max
     sc.counts[f * 8 + 5] = sh[1023][6];
     sc.counts[f * 8 + 6] = sh[1023][7];
     boff[sh[1023][6]] = sh[1023][7];
-    sc.rows_n[2 * f] = sh[1023][8];
-    sc.rows_n[2 * f + 1] = sh[1023][9];
+    sc.rows_n[3 * f] = sh[1023][8];
+    sc.rows_n[3 * f + 1] = sh[1023][9];
+    sc.rows_n[3 * f + 2] = sh[1023][10];
   }
   if (sc.rows_on) {                  // the frame's place inside the batch-wide buckets (any order of the frames will do)
     for (int k = t; k < sc.n_buckets; k += 1024) {
@@ -2774,7 +2776,7 @@ __global__ __launch_bounds__(1024) void k_lists(const FrameDesc* frames, int max
 __global__ __launch_bounds__(1024) void k_rows_scatter(int max_drops, Scratch sc) {
   const int f = blockIdx.x, t = threadIdx.x;
   __shared__ int s_start[RW_TEX_MAX], s_rank[RW_TEX_MAX];
-  const int nf = sc.rows_n[2 * f] + sc.rows_n[2 * f + 1];
+  const int nf = sc.rows_n[3 * f] + sc.rows_n[3 * f + 1];
   if (nf == 0) return;
   const int own = t < sc.n_buckets ? sc.rows_hist[t] : 0;
   s_start[t] = own;
@@ -5000,7 +5002,7 @@ int ensure_scratch(rr_ctx* ctx, int n, int max_drops, const Dims& dm, bool need_
     if ((rc = dev_alloc(ctx, ctx->sc.list_rot, fd))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.rows_list, fd))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.rows_sorted, fd))) return rc;
-    if ((rc = dev_alloc(ctx, ctx->sc.rows_n, (size_t)F * 2))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->sc.rows_n, (size_t)F * 3))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.rows_hist, (size_t)RW_TEX_MAX * 3 + 16))) return rc;      // + RW_TEX_MAX 8-byte cost sums + the share counter
     ctx->sc.rows_cost = reinterpret_cast<unsigned long long*>(ctx->sc.rows_hist + RW_TEX_MAX);
     ctx->sc.rows_next = ctx->sc.rows_hist + 3 * RW_TEX_MAX;
@@ -7098,11 +7100,12 @@ int rr_batch_counts(rr_ctx* ctx, int32_t frame, int32_t out[8]) {
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, ctx->sc.counts + (size_t)frame * 8, sizeof(int32_t) * 8, hipMemcpyDeviceToHost));
   int32_t rows = 0;                    // the row-walk kernel's share of the rotate + resize tiles (k_lists writes it with or without the option)
-  int32_t rows2[2] = {0, 0};
-  HIPCHK(hipMemcpy(rows2, ctx->sc.rows_n + 2 * (size_t)frame, sizeof(int32_t) * 2, hipMemcpyDeviceToHost));
-  rows = rows2[0];
+  int32_t rows3[3] = {0, 0, 0};
+  HIPCHK(hipMemcpy(rows3, ctx->sc.rows_n + 3 * (size_t)frame, sizeof(int32_t) * 3, hipMemcpyDeviceToHost));
+  rows = rows3[0];
   out[0] += rows;
-  out[5] += rows2[1];                  // Big tiles rendered by k_tile_rows
+  out[5] += rows3[1];                  // Big tiles rendered by k_tile_rows
+  out[6] += rows3[2];                  // ... and their pixels
   return RR_OK;
 }
 

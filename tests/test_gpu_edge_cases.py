@@ -11,16 +11,11 @@ import helpers as h
 pytestmark = pytest.mark.gpu
 
 H, W = 400, 300
-FPX = 6e-3 / 4.65e-6
 
 
 def _drop(pid, x0, y0, x1, y1, iw1, iw2, depth):
-    """Streak from image (x0,y0) to (x1,y1) in TOP-LEFT pixel coordinates; the XML carries
-    bottom-left y (the loader flips it, bad_weather.py:221-222)."""
-    X = (x0 - W / 2) * depth / FPX
-    Y = ((H - y0) - H / 2) * depth / FPX
-    return dict(pid=pid, wp1=(X, Y, -depth), wp2=(X + 0.001, Y - 0.01, -depth + 0.005), wd1=0.002, wd2=0.002,
-                ip1=(x0, H - y0), ip2=(x1, H - y1), iw1=iw1, iw2=iw2)
+    """Streak from image (x0,y0) to (x1,y1) in TOP-LEFT pixel coordinates (helpers.streak)."""
+    return h.streak(pid, x0, y0, x1, y1, iw1, iw2, depth, H, W)
 
 
 def _frames():

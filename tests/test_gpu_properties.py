@@ -3,6 +3,7 @@ the host-emulation comparison where the numpy oracle would take minutes."""
 import numpy as np
 import pytest
 
+import blur_routes as br
 import helpers as h
 
 pytestmark = pytest.mark.gpu
@@ -84,13 +85,18 @@ def test_raw_tile_dedup_is_invisible(setup):
     c0, c1 = rh.batch_counts(0), rh.batch_counts(1)
     ok = int(np.count_nonzero(base['status'] == 0))
     assert c0[7] + c1[7] > ok                                              # > one frame's worth of duplicates
-    assert (c0[0] + c0[1] + c0[5]) + (c1[0] + c1[1] + c1[5]) + (c0[7] + c1[7]) >= 2 * ok   # every composited drop has a tile
+    recs = br.classify_drops(sc, drops)
+    tiles = sum(r['live'] for r in recs)                                   # drops with a raw tile (>= the composited ones)
+    assert tiles >= ok
+    for c in (c0, c1):                                                     # each renders its own tile or shares another's
+        assert c[0] + c[1] + c[5] + c[7] == tiles, c
     plain = h.hb.RainHip(0)
     plain.set_option(h.hb.RR_OPT_DEDUP, 0)
     plain.set_streak_db(sc.db.streaks_light)
     plain.set_camera(sc.cam)
     ref = plain.render_frames([fr])[0]
     assert plain.batch_counts(0)[7] == 0
+    assert plain.batch_counts(0)[2:7] == br.expected_counts(recs)          # blur work lists, Big tiles and their pixels, exactly
     plain.close()
     for k in ('mask', 'mask_i32', 'image_u8', 'status', 'rainy_bg'):
         assert np.array_equal(ref[k], base[k]), k

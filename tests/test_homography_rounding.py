@@ -9,17 +9,12 @@ down) and counts the pixels of every Big tile whose X or Y changes: the fraction
 of the other solver's result.  A changed coordinate moves one bicubic tap table entry (1/32 px): an alpha change of the
 order of 1e-3 of the texture's local contrast -- it could move a float64 mask bit, which is why README does not call the Big
 branch bit-exact against a real cv2, only against the oracle."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import helpers as h
 
-PLAN_DTYPE = np.dtype([(k, '<i4') for k in ('status kind tex flip tw th shift pw ph r1 r2 vis_x0 vis_y0 vis_w vis_h crop_x crop_y ew bw0 nW nH '
-                                            'rs_mode isx isy eh epitch epad').split()] + [('pad_', '<i4'), ('a0_off', '<i8'), ('a1_off', '<i8'),
-                      ('sig1', '<f8'), ('sig2', '<f8'), ('tau_one', '<f8'), ('g', '<f8'), ('mi', '<f8', (9,)), ('ma', '<f8', (6,)),
-                      ('scale_x', '<f8'), ('scale_y', '<f8'), ('inv_sx', '<f8'), ('inv_sy', '<f8')])
+PLAN_DTYPE = h.PLAN_DTYPE
 
 
 def _coords(mi, tw, th, bw0):
@@ -46,15 +41,7 @@ def _nudge(m, signs, ulps):
 
 
 def big_drop_rounding_census(sc, frame=0, ulps=4):
-    emu = h.hostemu()
-    assert emu.emu_sizeof_plan() == PLAN_DTYPE.itemsize
-    texels, hs, ws, offs = h.hb.pack_streak_db(sc.db.streaks_light)
-    drops = np.ascontiguousarray(sc.product_drops(frame))
-    n = len(drops)
-    plans = np.zeros(n, PLAN_DTYPE)
-    poly, npts, sizes = np.zeros(n * 72, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
-    emu.emu_plan(h._p(drops), n, ctypes.byref(sc.cam), sc.H, sc.W, sc.He, sc.We, h._p(hs), h._p(ws), ctypes.c_double(1.0), h._p(plans),
-                 h._p(poly), h._p(npts), h._p(sizes))
+    plans, sizes = h.emu_plan(sc, sc.product_drops(frame))
     big = np.nonzero((plans['kind'] == 0) & (plans['status'] == 0) & (sizes > 0))[0]
     rng = np.random.RandomState(7)
     patterns = [np.ones(9), -np.ones(9)] + [rng.choice([-1.0, 1.0], 9) for _ in range(16)]
