@@ -14,12 +14,19 @@ database from rank 0 at start-up.  Rank 0 prints ONE JSON line.
   --total-frames T   strong scaling: ONE T-frame sequence, frames idx[rank::world] per rank (sharding.shard), a step
                      renders the rank's share in chunks of --batch; value = T * steps / time
 
-Extra keys (N=1 only, outside the timed region, never `value`): `host_inclusive` (pinned, three-stream
-rr_pipeline_submit/wait incl. PCIe both ways and the fog / environment-map pre-pass), `prepass`, `variants`
-(no tile sharing, angular noise, smaller library calls), `chain` (whole-step HBM fraction), `cpu_baseline` (+ its
-multi-process and C++ legs).  roofline.traffic is measured by two rocprofv3 --pmc passes of this very workload that
-bench.py spawns itself (skip with --no-traffic).  --dump-outputs DIR: after the timed steps, what the last one computed as
-DIR/<name>.npy (dump_outputs), inputs seeded so that two builds can be compared output for output.
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: `value`, `ms_per_step`,
+the per-kernel HIP-event times of the timed steps and what follows from them (`roofline`, `chain`) -- nothing that needs a
+run of its own.  Its particles are simulated on worker processes and handed to the product loader as records, without
+the particles file (lean_scene).
+
+--full adds everything else, outside the timed region, never `value`: `overlap` (one more pass with the colour branch on
+the caller's stream), roofline.traffic (two rocprofv3 --pmc passes of this very workload that bench.py spawns itself) and
+`valu` (a third pass), and for N=1: `host_inclusive` (pinned, three-stream rr_pipeline_submit/wait incl. PCIe both ways
+and the fog / environment-map pre-pass), `prepass`, `png_on_device`, `variants` (no tile sharing, angular noise, smaller
+library calls, other input precisions), `driver_end_to_end`, `cpu_baseline` (+ its multi-process and C++ legs).
+--no-serial / --no-traffic / --no-variants / --no-prepass / --no-driver / --no-cpu-baseline leave single legs out of it.
+--dump-outputs DIR: after the timed steps, what the last one computed as DIR/<name>.npy (dump_outputs), inputs seeded so
+that two builds can be compared output for output.
 """
 import argparse
 import contextlib
@@ -101,6 +108,89 @@ def algorithmic_bytes(H, W, He, We, N):
     return 27 * H * W + 16 * He * We + 64 * N
 
 
+def frame_drops(sc, i, noise_std=0.0):
+    """sc.product_drops(i, noise_std, 1 if noise_std else 0): the frame filter and the drop table of frame i, the draws of
+    np.random.seed(i) taken from the library's copy of the legacy generator (pack_drops seed=i: the same numbers, without
+    a Python call per drop)."""
+    frames = list(sc.db.streaks_simulator.values())
+    fr = frames[i % len(frames)]
+    hb = importlib.import_module('rain-rendering_amd.hip_backend')
+    idx = hb.filter_streaks(fr.table, sc.W, sc.H)
+    return hb.pack_drops(fr.table, idx, sc.db, noise_std, 1.0 if noise_std else 0.0, seed=i)
+
+
+def _simulated_frames(job):
+    """Frames [a, b) of synthetic.simulate_to_xml's sequence (a worker process): per frame (id, t, d, pid, values), values
+    = wp1, wp2, wd1, wd2, ip1, ip2, iw1, iw2 as float64 -- the doubles the particles file would parse back to (its numbers
+    are written with 17 significant digits)."""
+    a, b, n_drops, W, H, focal_mm, pix_um, exposure_ms, seed0, far_fraction = job
+    synthetic = importlib.import_module('rain-rendering_amd.synthetic')
+    out = []
+    for fi in range(a, b):
+        fr = synthetic.simulate_particles(1, n_drops, W, H, focal_mm, pix_um, exposure_ms, seed0=seed0 + fi, far_fraction=far_fraction)[0]
+        ds = fr['drops']
+        vals = np.array([tuple(d['wp1']) + tuple(d['wp2']) + (d['wd1'], d['wd2']) + tuple(d['ip1']) + tuple(d['ip2']) + (d['iw1'], d['iw2'])
+                         for d in ds], np.float64).reshape(len(ds), 14)
+        out.append((fi, fr['t'], fi * 100000, np.array([d['pid'] for d in ds], np.int64), vals))
+    return out
+
+
+def start_simulation(n_frames, n_drops, W, H, cam, seed0, render_scale, workers, far_fraction=0.02):
+    """Starts simulating what scenes.Scene(.., n_drops, n_frames, cam, seed0, render_scale) would write to its particles
+    file, on `workers` fresh interpreters (nothing of this process, which may come to hold a GPU context, is forked).
+    Returns a function that waits for the frames and returns them in order (cancel=True: drops the jobs not yet started)."""
+    common = (int(n_drops), int(W * render_scale), int(H * render_scale), float(cam['focal_mm']), float(cam['pix_um']),
+              float(cam['exposure_ms']), int(seed0), float(far_fraction))
+    if workers <= 1 or n_frames < 16:
+        frames = _simulated_frames((0, n_frames) + common)
+        return lambda cancel=False: frames
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    per = max(1, min(8, n_frames // (4 * workers)))                 # (a few jobs per worker: they end together)
+    pool = ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context('spawn'))
+    jobs = [pool.submit(_simulated_frames, (a, min(a + per, n_frames)) + common) for a in range(0, n_frames, per)]
+
+    def result(cancel=False):
+        try:
+            return None if cancel else [fr for j in jobs for fr in j.result()]
+        finally:
+            pool.shutdown(wait=not cancel, cancel_futures=True)
+    return result
+
+
+def lean_scene(scenes, tmpdir, H, W, cam, render_scale, frames):
+    """scenes.Scene(tmpdir, H, W, ...) of the frames start_simulation made, without its particles file: the records go to the
+    product loader's records path (DBManager.load_streaks_from_records) instead of through the XML text (1.5 GB for the
+    headline's 512 frames) written and parsed again.  The same doubles, so the same drop tables (tests/test_bench_scopes.py
+    compares the two)."""
+    bw = scenes.bw
+    recs = np.zeros(len(frames), bw.PARTICLE_FRAME_DTYPE)
+    drops = np.zeros(sum(len(f[3]) for f in frames), bw.PARTICLE_DTYPE)
+    at = 0
+    for k, (fi, t, d, pid, vals) in enumerate(frames):
+        n = len(pid)
+        recs[k] = (fi, t, d, n, at, n)
+        dr = drops[at:at + n]
+        dr['pid'] = pid
+        dr['wp1'], dr['wp2'] = vals[:, 0:3], vals[:, 3:6]
+        dr['wd1'], dr['wd2'] = vals[:, 6], vals[:, 7]
+        dr['ip1'], dr['ip2'] = vals[:, 8:10], vals[:, 10:12]
+        dr['iw1'], dr['iw2'] = vals[:, 12], vals[:, 13]
+        at += n
+    sc = scenes.Scene.__new__(scenes.Scene)
+    sc.H, sc.W, sc.cam_settings, sc.render_scale = H, W, cam, render_scale
+    sc.tex_dir, sc.norm = scenes.synthetic.write_streak_db(os.path.join(str(tmpdir), 'rainstreakdb'))
+    sc.xml = None
+    sc.He, sc.We = H, scenes.synthetic.envmap_width(cam['focal_mm'], W)
+    sc.db = bw.DBManager(streaks_path=sc.tex_dir, streaks_path_xml=None, norm_coeff_path=sc.norm)
+    sc.db.load_streak_database()
+    sc.db.load_streaks_from_records(recs, drops, 'kitti', {"render_scale": render_scale}, [W, H])
+    sc.omega = scenes.solid_angle.get_solid_angles(np.zeros((sc.He, sc.We)))
+    sc.cam = scenes.hb.make_camera(cam['focal_mm'] / 1000., cam['f_number'], cam['exposure_ms'])
+    sc.ocam = dict(focal_m=cam['focal_mm'] / 1000., f_number=cam['f_number'], exposure_ms=cam['exposure_ms'])
+    return sc
+
+
 class DeviceBatch:
     """n frames resident in HBM as torch tensors + the ctypes descriptors rr_render_frames_device takes."""
 
@@ -132,7 +222,7 @@ class DeviceBatch:
             bg, env = inputs[k]
             inputs[k] = None
             if sims is None:
-                drops = sc.product_drops(di, noise_std=noise_std, noise_scale=1.0 if noise_std else 0.0)
+                drops = frame_drops(sc, di, noise_std=noise_std)
                 t_dr = torch.from_numpy(drops.view(np.uint8).reshape(-1)).to(dev)
             else:
                 drops = np.zeros(self.cap, hb.DROP_DTYPE)           # (length = capacity; the records are made on the device)
@@ -483,16 +573,44 @@ def main():
     ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last step computed '
                     '(rank 0\'s frames, a seeded sample within 64 MB) as DIR/<name>.npy in float32 / float64')
     ap.add_argument('--inner', action='store_true', help='(used by the PMC passes) timed loop only, no extras, no JSON')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: the one-stream pass, the PMC passes, '
+                    'variants, pre-pass, PNG and host-inclusive legs, the driver end to end, the CPU baselines')
     args = ap.parse_args()
     if args.inner or args.sweep:
         args.no_cpu_baseline = args.no_prepass = args.no_variants = args.no_traffic = args.no_driver = True
-
-    import torch
-    import torch.distributed as dist
+    if not args.full:
+        args.no_cpu_baseline = args.no_prepass = args.no_variants = args.no_traffic = args.no_driver = args.no_serial = True
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+    scenes = importlib.import_module('rain-rendering_amd.scenes')       # (no library load: that is build()'s)
+    sharding = importlib.import_module('rain-rendering_amd.sharding')
+    hb, synthetic = scenes.hb, scenes.synthetic
+
+    wl = WORKLOADS[args.workload]
+    H, W, B = wl['H'], wl['W'], args.batch
+    is_sim = bool(wl.get('sim'))
+    N = 16 if is_sim else synthetic.DROPS_PER_RATE[wl['rate']]      # (in-kernel particles: the scene's XML is a stub, never rendered)
+    cam = getattr(scenes, wl['cam'])
+    strong = args.total_frames > 0
+    # frames of this rank: weak = its own B frames (seeded by rank); strong = its share of ONE sequence
+    if strong:
+        my_frames = sharding.shard(list(range(args.total_frames)), rank, world)
+        n_sim, seed0 = args.total_frames, 3000
+    else:
+        my_frames = list(range(B))
+        n_sim, seed0 = B, 3000 + 1000 * rank
+    # the particles file is what the CPU legs and the PMC passes read: --full and --scene-dir write / reuse it (scenes.Scene);
+    # a plain run simulates the same particles on worker processes while torch and the device start up
+    lean = not args.full and not args.scene_dir
+    simulated = start_simulation(1 if is_sim else n_sim, N, W, H, cam, seed0, wl['rs'],
+                                 max(1, min(16, os.cpu_count() or 1) // world)) if lean else None
+
+    import torch
+    import torch.distributed as dist
     if not torch.cuda.is_available():
+        if simulated is not None:
+            simulated(cancel=True)
         raise SystemExit("bench.py needs a GPU: the hot path has no CPU fallback")
     # test hooks (one-GPU smoke test of the N>1 path): RAIN_BENCH_DEVICE pins every rank to one device,
     # RAIN_BENCH_BACKEND=gloo replaces RCCL (which refuses two ranks on one GPU)
@@ -513,26 +631,13 @@ def main():
         ge.build()
     if world > 1:
         dist.barrier()
-    scenes = importlib.import_module('rain-rendering_amd.scenes')
-    sharding = importlib.import_module('rain-rendering_amd.sharding')
-    hb, synthetic = scenes.hb, scenes.synthetic
 
-    wl = WORKLOADS[args.workload]
-    H, W, B = wl['H'], wl['W'], args.batch
-    is_sim = bool(wl.get('sim'))
-    N = 16 if is_sim else synthetic.DROPS_PER_RATE[wl['rate']]      # (in-kernel particles: the scene's XML is a stub, never rendered)
-    cam = getattr(scenes, wl['cam'])
-    strong = args.total_frames > 0
-    # frames of this rank: weak = its own B frames (seeded by rank); strong = its share of ONE sequence
-    if strong:
-        my_frames = sharding.shard(list(range(args.total_frames)), rank, world)
-        n_sim, seed0 = args.total_frames, 3000
-    else:
-        my_frames = list(range(B))
-        n_sim, seed0 = B, 3000 + 1000 * rank
     tmp = args.scene_dir or tempfile.mkdtemp(prefix='rainbench_r%d_' % rank)
     with contextlib.redirect_stdout(sys.stderr):       # loaders print like the reference's do; stdout carries the JSON line only
-        sc = scenes.Scene(tmp, H, W, N, n_frames=1 if is_sim else n_sim, cam=cam, seed0=seed0, render_scale=wl['rs'])
+        if lean:
+            sc = lean_scene(scenes, tmp, H, W, cam, wl['rs'], simulated())
+        else:
+            sc = scenes.Scene(tmp, H, W, N, n_frames=1 if is_sim else n_sim, cam=cam, seed0=seed0, render_scale=wl['rs'])
     He, We = sc.He, sc.We
     sims = None
     if is_sim:
@@ -610,6 +715,8 @@ def main():
                                                               for q in range(8) if row[q])))
     if args.inner:
         rh.close()
+        if not args.scene_dir:
+            shutil.rmtree(tmp, ignore_errors=True)
         return
     if args.sweep and rank == 0:
         def line(tag, el, st):
@@ -899,7 +1006,7 @@ def main():
         # the scopes launched on the library's second stream: mode 1 the FOV chain, mode 2 the bookkeeping chain + k_colour
         COLOUR = (('k_fov_spans', 'k_fov_sums', 'k_fov_poly', 'k_env_prefix', 'k_fov_sums_general') if colour_mode == 1 else
                   ('k_plan', 'k_scan', 'k_dedup', 'k_lists', 'k_colour'))
-        overlapped = {k: v for k, v in per_launch.items() if k in COLOUR} if stats_serial is not None else {}
+        overlapped = {k: v for k, v in per_launch.items() if k in COLOUR} if colour_mode != 0 else {}
         per_main = {k: v for k, v in per_launch.items() if k not in overlapped}
         dom_name = max(per_main, key=per_main.get)
         avg_ms = per_main[dom_name]
@@ -983,15 +1090,16 @@ def main():
             "chain": {"ms_per_call_sum_of_kernels": chain_ms, "algorithmic_GBps": alg / (chain_ms * 1e-3) / 1e9,
                       "frac_of_hbm_peak": alg / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "kernels_ms_per_call": {k: v for k, v in sorted(per_main.items(), key=lambda kv: -kv[1])},
-            "overlap": None if per_serial is None else {
+            "overlap": None if colour_mode == 0 else {
                 "what": "the FOV chain (polygons, spans, sums over the environment map) runs on a second stream of the library beside plan .. "
                         "tiles .. blur (RR_OPT_COLOUR_STREAM 1).  kernels_ms_per_call: the caller's stream's kernels in the timed region; "
                         "colour_branch_ms_between_events: the second stream's kernels between their event pairs -- including the time their "
-                        "workgroups waited for room on the CUs, not a cost; kernels_ms_per_call_one_stream: the same step with the option 0, "
-                        "every kernel alone on the device",
-                "ms_per_step": 1e3 * elapsed / args.steps, "ms_per_step_one_stream": 1e3 * elapsed_serial / args.steps,
+                        "workgroups waited for room on the CUs, not a cost; kernels_ms_per_call_one_stream (--full): the same step with the "
+                        "option 0, every kernel alone on the device",
+                "ms_per_step": 1e3 * elapsed / args.steps,
+                "ms_per_step_one_stream": 1e3 * elapsed_serial / args.steps if per_serial is not None else None,
                 "colour_branch_ms_between_events": {k: v for k, v in sorted(overlapped.items(), key=lambda kv: -kv[1])},
-                "kernels_ms_per_call_one_stream": {k: v for k, v in sorted(per_serial.items(), key=lambda kv: -kv[1])}},
+                "kernels_ms_per_call_one_stream": {k: v for k, v in sorted(per_serial.items(), key=lambda kv: -kv[1])} if per_serial is not None else None},
             "valu": {"what": valu_how, "dominant_kernel": dom_valu["valu_util"] if dom_valu else None,
                      "per_kernel": {k: {"valu_util": round(v["valu_util"], 4), "waiting": round(v["waiting"], 4) if v["waiting"] is not None else None}
                                     for k, v in sorted((valu or {}).items(), key=lambda kv: -kv[1]["valu_util"])} if valu else None},
@@ -1010,6 +1118,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     rh.close()
+    if not args.scene_dir:
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == '__main__':

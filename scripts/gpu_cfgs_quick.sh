@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-LEAN="--steps 5 --warmup 2 --no-cpu-baseline --no-prepass --no-variants --no-traffic"
+LEAN="--steps 5 --warmup 2 --full --no-cpu-baseline --no-prepass --no-variants --no-traffic"
 for WL in "nuscenes1 64" "nuscenes5 64" "nuscenes25 64" "nuscenes100 64" "kitti25 128" "cityscapes50 32"; do set -- $WL
  timeout -k 10 400 python bench.py --workload $1 --batch $2 $LEAN > gpurun_out/r06g2_bench_$1.json 2> gpurun_out/r06g2_bench_$1.err
  python - <<PY

@@ -6,7 +6,7 @@ TAG=${1:-copyenv}; shift
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out; mkdir -p $OUT; cd $REPO
 : > $OUT/${TAG}.txt
 for E in "$@"; do
-  env $E timeout -k 10 300 python bench.py --batch 128 --steps 3 --warmup 1 --no-cpu-baseline --no-variants --no-traffic --no-driver > $OUT/${TAG}_tmp.json 2> $OUT/${TAG}_tmp.err
+  env $E timeout -k 10 300 python bench.py --batch 128 --steps 3 --warmup 1 --full --no-cpu-baseline --no-variants --no-traffic --no-driver > $OUT/${TAG}_tmp.json 2> $OUT/${TAG}_tmp.err
   python - <<PY | tee -a $OUT/${TAG}.txt
 import json
 try:

@@ -3,7 +3,7 @@
 # not stop the next).  Results land in gpurun_out/; copy what is to be judged into profiles/.
 #   scripts/gpu_full_measure.sh <tag> a     (~12 min of box time)
 #     1. pytest -m gpu                                          -> <tag>_gpu_tests.log
-#     2. python bench.py (the driver's line: roofline, valu, cpu_baseline, variants, host-inclusive pipeline, pre-pass)
+#     2. python bench.py --full (the driver's line: roofline, valu, cpu_baseline, variants, host-inclusive pipeline, pre-pass)
 #                                                               -> <tag>_bench_default.json
 #     3. rocprofv3 kernel stats + PMC passes (scripts/gpu_pmc.sh: FETCH_SIZE and WRITE_SIZE in passes of their own,
 #        VALU / wait / LDS / L2 counters)                       -> pmc_<tag>/summary.json, pmc_<tag>.txt
@@ -20,7 +20,7 @@ OUT=$REPO/gpurun_out; mkdir -p $OUT $OUT/pmc_$TAG
 cd $REPO
 if [ "$PART" = "a" ]; then
   timeout -k 10 1200 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_gpu_tests.log 2>&1; echo "tests exit $?"; tail -3 $OUT/${TAG}_gpu_tests.log
-  timeout -k 10 900 python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "bench exit $?"; tail -c 300 $OUT/${TAG}_bench_default.json
+  timeout -k 10 900 python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "bench exit $?"; tail -c 300 $OUT/${TAG}_bench_default.json
   # kernel stats of the default step (colour branch on the second stream: its kernels' durations include waiting for room) ...
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/pmc_$TAG/stats_overlap -- python $REPO/bench.py --steps 3 --warmup 1 --inner > $OUT/pmc_$TAG.overlap.log 2>&1); echo "stats (overlap) exit $?"
   # ... and stats + counters with everything on one stream (RR_OPT_COLOUR_STREAM 0): every kernel alone on the device
@@ -30,7 +30,7 @@ if [ "$PART" = "a" ]; then
     "TCC_HIT_sum TCC_MISS_sum" > $OUT/pmc_$TAG.txt 2>&1; echo "pmc exit $?"; grep -A12 "== pmc" $OUT/pmc_$TAG.txt | cut -c1-300
   timeout -k 10 600 scripts/phase_timing.sh $TAG > $OUT/${TAG}_phases.log 2>&1; echo "phases exit $?"; grep -A6 "^PHASES" $OUT/${TAG}_phases.log | cut -c1-400
 else
-  LEAN="--steps 5 --warmup 2 --no-cpu-baseline --no-prepass --no-variants --no-traffic"
+  LEAN="--steps 5 --warmup 2 --full --no-cpu-baseline --no-prepass --no-variants --no-traffic"
   for WL in "kitti25 128" "cityscapes50 32" "cityscapes50_rs2 128" "nuscenes1 64" "nuscenes5 64" "nuscenes25 64" "nuscenes100 64" "nuscenes200 64" "nuscenes200x 64"; do
     set -- $WL
     timeout -k 10 400 python bench.py --workload $1 --batch $2 $LEAN > $OUT/${TAG}_bench_$1.json 2> $OUT/${TAG}_bench_$1.err; echo "$1 exit $?"

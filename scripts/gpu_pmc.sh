@@ -10,7 +10,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (PMC_LEGS=1: not only the hot path -- the bench line's pre-pass / PNG / host-inclusive legs run too, so their kernels are profiled)
-if [ "${PMC_LEGS:-0}" = "1" ]; then INNER=""; else INNER="--inner"; fi
+if [ "${PMC_LEGS:-0}" = "1" ]; then INNER="--full"; else INNER="--inner"; fi
 BENCH="python $REPO/bench.py --steps 3 --warmup 1 $INNER $BARGS"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats.log 2>&1
 i=0

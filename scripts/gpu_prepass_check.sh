@@ -4,7 +4,7 @@
 TAG=${1:-pre}; shift
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out; mkdir -p $OUT; cd $REPO
 timeout -k 10 900 python -m pytest tests/test_gpu_prepass.py tests/test_gpu_pipeline_async.py tests/test_gpu_driver.py -m gpu -q > $OUT/${TAG}_tests.log 2>&1; echo "tests exit $?"; tail -12 $OUT/${TAG}_tests.log
-timeout -k 10 900 python bench.py --batch 256 --steps 5 --warmup 2 --no-cpu-baseline --no-variants --no-traffic --no-driver "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit $?"
+timeout -k 10 900 python bench.py --batch 256 --steps 5 --warmup 2 --full --no-cpu-baseline --no-variants --no-traffic --no-driver "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit $?"
 python - <<PY
 import json
 try:

@@ -81,3 +81,31 @@ def test_output_dump_is_seeded_and_within_budget(tmp_path):
         rgb = np.load(os.path.join(got[0]['dir'], 'rainy_rgb.npy'))
         rows = np.load(os.path.join(got[0]['dir'], 'rows.npy')).astype(int)
         assert np.array_equal(rgb[-1], b.outputs[fr[-1]][0].numpy()[rows].astype(np.float32))
+
+
+def test_plain_run_scene_renders_the_inputs_of_the_particles_file(tmp_path):
+    """A plain run hands the simulated particles to the product loader as records (lean_scene) and draws the drop tables'
+    random numbers from the library's generator (frame_drops): the same drop tables, byte for byte, as scenes.Scene's
+    particles file and Scene.product_drops give -- both render scales, with and without angular noise, far drops included."""
+    import contextlib
+    import importlib
+    import numpy as np
+    bench = _bench()
+    scenes = importlib.import_module('rain-rendering_amd.scenes')
+    for H, W, N, nf, cam, rs, seed0 in ((96, 160, 300, 20, scenes.KITTI, 1, 3000), (128, 256, 200, 7, scenes.CITYSCAPES, 2, 4000)):
+        with contextlib.redirect_stdout(None):
+            ref = scenes.Scene(str(tmp_path / ('xml_%d' % rs)), H, W, N, n_frames=nf, cam=cam, seed0=seed0, render_scale=rs)
+        sim = bench.start_simulation(nf, N, W, H, cam, seed0, rs, workers=1)
+        got = bench.lean_scene(scenes, str(tmp_path / ('lean_%d' % rs)), H, W, cam, rs, sim())
+        assert (got.H, got.W, got.He, got.We) == (ref.H, ref.W, ref.He, ref.We)
+        assert np.array_equal(got.omega, ref.omega) and bytes(got.cam) == bytes(ref.cam) and got.ocam == ref.ocam
+        assert list(got.db.streaks_simulator) == list(ref.db.streaks_simulator) == list(range(nf))
+        assert np.array_equal(got.db.ratio, ref.db.ratio)
+        far = 0
+        for i in range(nf):
+            for noise in (0.0, 3.0):
+                a = ref.product_drops(i, noise_std=noise, noise_scale=1.0 if noise else 0.0)
+                b = bench.frame_drops(got, i, noise_std=noise)
+                assert len(a) > 0 and a.tobytes() == b.tobytes(), (rs, i, noise)
+            far += int((np.abs(a['wps'][:, 2]) > 10.0).sum())
+        assert far > 0
