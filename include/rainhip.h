@@ -306,10 +306,22 @@ int rr_pipeline_frames(rr_ctx* ctx, int32_t n, const rr_prepass_in* pre, const r
  *      length, type) and the frame filter of Generator.run (generator.py:413-420), keeping the particle order,
  *   3. makes the renderer's per-drop random draws (np.random.seed(draw_seed), one randint per drop, one normal per
  *      non-Big drop: bad_weather.py:252-264, generator.py:136) from numpy's legacy MT19937 stream, like rr_host_frame_draws,
- * and leaves rr_drop[] records in HBM: no XML, no host drop table, no PCIe traffic.  Angular noise (--noise_std) is not
- * offered on this path (the reference's default is 0); the rotation terms are rot_cos = -dy / n, rot_sin = -|dx| / n
- * (n = |end - start|): the values cos / sin(-(theta) * pi / 180), theta = acos(-dy / n), take when evaluated exactly.
- * Everything derived from transcendentals (the diameter distribution) is tabulated once by the host. */
+ * and leaves rr_drop[] records in HBM: no XML, no host drop table, no PCIe traffic.  Without angular noise the rotation
+ * terms are rot_cos = -dy / n, rot_sin = -|dx| / n (n = |end - start|): the values cos / sin(-(theta) * pi / 180),
+ * theta = acos(-dy / n), take when evaluated exactly.  Everything derived from transcendentals (the diameter distribution)
+ * is tabulated once by the host.
+ *
+ * Angular noise (--noise_std / --noise_scale, generator.py:136-163): the reference turns the end points of a simulated
+ * frame's streaks IN PLACE, so a rendered frame inherits the turns of every earlier frame of the run that used the same
+ * simulated frame.  rr_set_particle_noise describes the run; a frame with run_pos = p >= 1 is its entry p - 1 and gets
+ * the simulated frame's pristine streaks stepped through every earlier entry with the same `frame`, in run order, then
+ * through its own entry: frame filter on the current end points, the entry's draws over the kept streaks (the normal
+ * deviate formed with det_log), the kept non-Big streaks turned by (0 + noise_std g) noise_scale degrees about their
+ * midpoints (det_sincos; truncated toward zero).  Its records carry the turned end points and the rotation terms
+ * cos / sin(-(theta + noise)) of the end points before the turn, as the angle sum of the exact terms above and
+ * det_sincos(noise) (tools/particles.py expected_records states it bit for bit).  The context keeps every simulated
+ * frame's current state: entries applied in order advance it, an entry older than the state restarts it from the
+ * pristine streaks.  State updates follow the order of the calls (an event chains calls on different streams). */
 typedef struct rr_sim_frame {
   int32_t sensor_w, sensor_h;     /* cam_CCD_WH (db.py): the simulator's sensor in pixels; rendered frame = sensor / render_scale */
   int32_t render_scale;           /* settings["render_scale"] (bad_weather.py:208-211) */
@@ -318,7 +330,7 @@ typedef struct rr_sim_frame {
   uint32_t frame;                 /* simulated frame number (a word of the Philox counter) */
   uint32_t draw_seed;             /* np.random.seed(...) of the renderer's per-drop draws (generator.py:318) */
   int32_t table;                  /* diameter table of this frame's fall rate / camera (rr_set_particle_tables) */
-  int32_t reserved;
+  int32_t run_pos;                /* angular noise (rr_set_particle_noise): 0 none; p >= 1 this frame is entry p - 1 of the run */
   double fpx;                     /* focal length / pixel size (cam_focal, cam_CCD_pixsize) */
   double exposure_s;              /* cam_exposure / 1000 */
   double speed_mps;               /* sim_steps["cam_motion"] / 3.6 */
@@ -343,6 +355,14 @@ int rr_generate_drops_device(rr_ctx* ctx, int32_t n, const rr_sim_frame* frames,
 int rr_generate_drops(rr_ctx* ctx, int32_t n, const rr_sim_frame* frames, int32_t H, int32_t W, rr_drop* drops_out, int32_t cap,
                       int32_t* n_out);
 int rr_sizeof_sim_frame(void);
+
+/* The run's order for angular noise on device-generated tables: entry p = (simulated frame id run_frame[p] (= the
+ * rr_sim_frame.frame of the frames that use it), draw seed run_seed[p]).  Host arrays, copied.  Drops the state the context
+ * holds of an earlier run: call it between runs, with no call of the generator in flight.  noise_std or noise_scale 0
+ * (or n_run 0) turns the noise off: records are then those of a run without it.  A frame whose run_pos is out of range or
+ * names an entry whose frame / seed differ from its own is RR_E_ARG. */
+int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int32_t n_run, const uint32_t* run_frame,
+                          const uint32_t* run_seed);
 
 /* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
  * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does

@@ -406,8 +406,6 @@ class Generator:
                 if self.device_particles:
                     # no particle file: the settings of the run's simulated frames (tools/particles.sim_frames: what
                     # simulate() would have written to XML, as rr_sim_frame records) + the diameter tables they refer to
-                    if bool(self.noise_std) and bool(self.noise_scale):
-                        raise NotImplementedError("--device_particles: angular noise is not offered on the device-generated path")
                     from ..tools import particles
                     opts = self.sim_options[sequence]
                     n_sim = particles.n_sim_frames(opts)
@@ -432,6 +430,16 @@ class Generator:
                 # just rendered, and the shares would neither partition nor cover the run).  Then this rank's share.
                 work, frames_exist_nb = sharding.rank0_decides(
                     lambda: self._work_list(files, depth_files, idx, out_dir, out_seq_dir, n_sim), self.rank, self.world)
+                if self.device_particles:
+                    # angular noise turns a simulated frame's streaks in place (generator.py:152-161): the library replays the
+                    # WHOLE run's history per simulated frame, including the entries other ranks render -- so the run table is
+                    # the global work list, and a frame names its entry by run_pos
+                    noisy = bool(self.noise_std) and bool(self.noise_scale)
+                    f_all = [it['f_name_idx'] for it in work]
+                    run_frame, run_seed = particles.run_table(sims, n_sim, f_all) if noisy else ((), ())
+                    hip.set_particle_noise(self.noise_std if noisy else 0.0, self.noise_scale if noisy else 0.0, run_frame, run_seed)
+                    for p, it in enumerate(work):
+                        it['run_pos'] = p + 1 if noisy else 0
                 work = sharding.shard(work, self.rank, self.world)
                 self._mark('work list')
                 sim_t0 = time.time()
@@ -457,13 +465,14 @@ class Generator:
 
     def _run_batches(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None):
         """The frames of one (sequence, weather) run through the asynchronous pipeline.  The common case -- 8-bit PNG
-        images, 16-bit PNG depth whose scaled size is the frame's, no angular noise, no environment-map files -- takes
+        images, 16-bit PNG depth whose scaled size is the frame's, no angular noise (unless the drop tables are made on the
+        device), no environment-map files -- takes
         the batch-native route (one library call per batch and stage, nothing per frame under the interpreter lock);
         everything else the general one (per-frame Python on an I/O thread pool)."""
         ds = self.settings["depth_scale"]
         B = self._cap_batch(B, imH, imW, frame_render_dict, sims)
         native = (work and int(rs) == rs and rs >= 1 and int(ds) == ds and ds >= 1 and
-                  not (bool(self.noise_std) and bool(self.noise_scale)) and not self.save_envmap and
+                  (sims is not None or not (bool(self.noise_std) and bool(self.noise_scale))) and not self.save_envmap and
                   os.environ.get('RAIN_NATIVE_IO', '1') != '0' and
                   all(it['image_file'].endswith('.png') and it['depth_file'].endswith('.png') for it in work))
         if native:
@@ -695,6 +704,7 @@ class Generator:
                         f_idx = items[k]['f_name_idx']
                         sl.sim_recs[k][0] = sims[f_idx % n_sim]
                         sl.sim_recs[k]['draw_seed'] = f_idx
+                        sl.sim_recs[k]['run_pos'] = items[k]['run_pos']    # angular noise: its entry in the run (0: none)
                     else:
                         sl.prep.set_drop_count(k, nd)
                 sl.t_submit = time.time()

@@ -43,6 +43,7 @@
 #include <cstring>
 #include <string>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "rainhip.h"
@@ -4499,8 +4500,9 @@ __global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int6
 // so that the stores are whole lines; tex_index temporarily holds the first texture of the drop's block of ten.
 constexpr int DROP_DW = (int)(sizeof(rr_drop) / 4);
 __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int H, int W, const double* dgrid, const double* cdf_tabs,
-                                                    int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out) {
+                                                    int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run) {
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (skip_run && sims[f].run_pos != 0) return;               // angular noise: k_noise_chains makes this frame
   __shared__ rr_sim_frame s_sf;
   __shared__ int s_cnt[8];
   __shared__ uint32_t s_stage[8][64 * DROP_DW];            // per wave: 64 records (57 KB)
@@ -4567,21 +4569,24 @@ __device__ inline uint32_t mt_temper(uint32_t y) {
   y ^= (y >> 18);
   return y;
 }
-__global__ __launch_bounds__(64) void k_particle_draws(const rr_sim_frame* sims, rr_drop* out, int cap, const int32_t* n_out) {
-  const int f = blockIdx.x, lane = threadIdx.x;
-  __shared__ uint32_t key[624];
-  const int n = imin(n_out[f], cap);
-  rr_drop* drops = out + (int64_t)f * cap;
-  {                                                          // init_genrand (numpy _legacy_seeding): sequential by definition
-    uint32_t seed = sims[f].draw_seed;
-    if (lane == 0)
-      for (int pos = 0; pos < 624; pos++) {
-        key[pos] = seed;
-        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)pos + 1u;
+// numpy's legacy MT19937 stream consumed by one wave (all methods wave-uniform); `key` is 624 words of wave-private LDS
+struct MtWave {
+  uint32_t* key;
+  int lane;
+  int pos = 624;                                              // next state word (624: regenerate first)
+  uint32_t cur = 0;                                           // lane l: tempered word pos0 + l of the current group
+  int avail = 0, taken = 0;                                   // words in the group / already handed out
+  bool has_gauss = false;                                     // legacy gauss: the second deviate of a polar pair is cached
+  double gauss = 0.0;
+  __device__ MtWave(uint32_t* k, int l, uint32_t seed) : key(k), lane(l) {
+    if (lane == 0)                                            // init_genrand (numpy _legacy_seeding): sequential by definition
+      for (int p = 0; p < 624; p++) {
+        key[p] = seed;
+        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)p + 1u;
       }
+    wave_lds_sync();
   }
-  wave_lds_sync();
-  auto regenerate = [&]() {                                   // mt19937_gen: three dependent sweeps + the last word
+  __device__ void regenerate() {                              // mt19937_gen: three dependent sweeps + the last word
     const uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, MATRIX_A = 0x9908b0dfu;
     auto sweep = [&](int a, int b, int ofs) {
       for (int k0 = a; k0 < b; k0 += 64) {
@@ -4604,11 +4609,8 @@ __global__ __launch_bounds__(64) void k_particle_draws(const rr_sim_frame* sims,
       key[623] = key[396] ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
     }
     wave_lds_sync();
-  };
-  int pos = 624;                                              // next state word (624: regenerate first)
-  uint32_t cur = 0;                                           // lane l: tempered word pos0 + l of the current group
-  int avail = 0, taken = 0;                                   // words in the group / already handed out
-  auto next_u32 = [&]() -> uint32_t {                         // wave-uniform
+  }
+  __device__ uint32_t next_u32() {
     if (taken == avail) {
       if (pos == 624) {
         regenerate();
@@ -4620,12 +4622,46 @@ __global__ __launch_bounds__(64) void k_particle_draws(const rr_sim_frame* sims,
       taken = 0;
     }
     return (uint32_t)__builtin_amdgcn_readlane((int)cur, taken++);
-  };
-  auto next_double = [&]() -> double {
+  }
+  __device__ double next_double() {
     const int32_t a = (int32_t)(next_u32() >> 5), b = (int32_t)(next_u32() >> 6);
     return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-  };
-  bool has_gauss = false;
+  }
+  __device__ int randint10(int lo) {                          // randint(lo, lo + 10): masked rejection, rng = 9, mask = 15
+    uint32_t v;
+    do {
+      v = next_u32() & 15u;
+    } while (v > 9u);
+    return lo + (int)v;
+  }
+  // legacy gauss (polar Box-Muller, second deviate cached).  FORM = false follows the words and the cache only (a normal
+  // with a standard deviation of 0 never uses its value); FORM = true makes the deviate (rr_particles.h polar_factor).
+  template <bool FORM>
+  __device__ double gauss_deviate() {
+    if (has_gauss) {
+      has_gauss = false;
+      return FORM ? gauss : 0.0;
+    }
+    double x1, x2, r2;
+    do {
+      x1 = 2.0 * next_double() - 1.0;
+      x2 = 2.0 * next_double() - 1.0;
+      r2 = x1 * x1 + x2 * x2;
+    } while (r2 >= 1.0 || r2 == 0.0);
+    has_gauss = true;
+    if (!FORM) return 0.0;
+    const double f = rrsim::polar_factor(r2);
+    gauss = f * x1;
+    return f * x2;
+  }
+};
+__global__ __launch_bounds__(64) void k_particle_draws(const rr_sim_frame* sims, rr_drop* out, int cap, const int32_t* n_out, int skip_run) {
+  const int f = blockIdx.x, lane = threadIdx.x;
+  if (skip_run && sims[f].run_pos != 0) return;               // angular noise: k_noise_chains makes this frame
+  __shared__ uint32_t key[624];
+  const int n = imin(n_out[f], cap);
+  rr_drop* drops = out + (int64_t)f * cap;
+  MtWave mt(key, lane, sims[f].draw_seed);
   for (int base = 0; base < n; base += 64) {
     const int i = base + lane;
     int lo = 0, big = 1;
@@ -4638,26 +4674,93 @@ __global__ __launch_bounds__(64) void k_particle_draws(const rr_sim_frame* sims,
     const int cnt = imin(64, n - base);
     for (int k = 0; k < cnt; k++) {
       const int lo_k = __builtin_amdgcn_readlane(lo, k), big_k = __builtin_amdgcn_readlane(big, k);
-      uint32_t v;                                             // randint(lo, lo + 10): masked rejection, rng = 9, mask = 15
-      do {
-        v = next_u32() & 15u;
-      } while (v > 9u);
-      if (lane == k) mine = lo_k + (int)v;
-      if (!big_k) {                                           // legacy gauss (polar Box-Muller, second deviate cached)
-        if (has_gauss) {
-          has_gauss = false;
-        } else {
-          double r2;
-          do {
-            const double x1 = 2.0 * next_double() - 1.0;
-            const double x2 = 2.0 * next_double() - 1.0;
-            r2 = x1 * x1 + x2 * x2;
-          } while (r2 >= 1.0 || r2 == 0.0);
-          has_gauss = true;
-        }
-      }
+      const int v = mt.randint10(lo_k);
+      if (lane == k) mine = v;
+      if (!big_k) (void)mt.gauss_deviate<false>();
     }
     if (i < n) as_global(reinterpret_cast<int32_t*>(drops + i))[7] = mine;
+  }
+}
+
+// k_noise_chains: angular noise (rr_set_particle_noise) on device-generated tables.  The reference turns the end points of a
+// simulated frame's streaks IN PLACE (generator.py:152-161), so a rendered frame sees the turns of every earlier frame of the
+// run that used the same simulated frame.  The context holds, per simulated frame, its pristine records (k_particles) and
+// its current state (kept streaks, turned end points, tex_index = first texture of the block of ten); the host plans, in
+// submission order, which history entries each call must apply (NoiseOp) so that every simulated frame of the call forms
+// ONE chain of steps, run by one wave: the steps of a chain are sequential by nature (each walks numpy's MT19937 stream
+// over the streaks the previous step kept), the chains are independent.  One step:
+//   frame filter on the current end points (compaction in place, particle order kept), the frame's draws over the kept
+//   streaks (randint + the formed normal deviate per non-Big streak, wave-uniform on the scalar side), then lane-parallel
+//   the rotation (rr_particles.h noise_rotate); the state keeps the turned streak, the frame's output (if any) gets the
+//   record with its texture and rotation terms.
+struct NoiseChain {
+  const rr_drop* pristine;
+  rr_drop* state;
+  const int32_t* n_pristine;         // k_particles' count of the pristine records
+  int32_t* n_state;
+  int32_t op0, nop;
+};
+struct NoiseOp {
+  uint32_t seed;                     // np.random.seed of the entry's draws
+  int32_t out_f;                     // frame of the call that receives the records, -1: a history entry (state only)
+  int32_t from_pristine;             // 1: the step starts from the pristine records (a new or reset chain)
+  int32_t pad;
+};
+__global__ __launch_bounds__(64) void k_noise_chains(const NoiseChain* chains, const NoiseOp* ops, int H, int W, double noise_std,
+                                                     double noise_scale, rr_drop* out, int cap, int32_t* n_out) {
+  const int lane = threadIdx.x;
+  __shared__ uint32_t key[624];
+  const NoiseChain ch = chains[blockIdx.x];
+  for (int o = 0; o < ch.nop; o++) {
+    const NoiseOp op = ops[ch.op0 + o];
+    const rr_drop* src = op.from_pristine ? ch.pristine : ch.state;
+    const int n = op.from_pristine ? *ch.n_pristine : *ch.n_state;
+    rr_drop* fout = op.out_f >= 0 ? out + (int64_t)op.out_f * cap : nullptr;
+    MtWave mt(key, lane, op.seed);
+    int kept = 0;
+    for (int base = 0; base < n; base += 64) {
+      const int i = base + lane;
+      rr_drop d;
+      bool keep = false;
+      if (i < n) {
+        d = src[i];
+        keep = rrsim::drop_in_frame(d, W, H);
+      }
+      const unsigned long long bal = __ballot(keep);
+      int tex = 0;
+      double g = 0.0;
+      for (unsigned long long b = bal; b; b &= b - 1) {       // the kept streaks of the group, in particle order
+        const int k = __builtin_ctzll(b);
+        const int lo_k = __builtin_amdgcn_readlane(keep ? d.tex_index : 0, k);
+        const int big_k = __builtin_amdgcn_readlane(keep ? (d.type == 0) : 1, k);
+        const int v = mt.randint10(lo_k);
+        const double gk = big_k ? 0.0 : mt.gauss_deviate<true>();
+        if (lane == k) {
+          tex = v;
+          g = gk;
+        }
+      }
+      // every record of the group is in registers before any store: the compaction writes at or below the slots it read
+      const int at = kept + __popcll(bal & ((1ull << lane) - 1ull));
+      if (keep) {
+        rr_drop r = d;
+        if (d.type != 0) rrsim::noise_rotate(r, rrsim::noise_degrees(g, noise_std, noise_scale));
+        rr_drop st = r;
+        st.tex_index = d.tex_index;
+        ch.state[at] = st;
+        if (fout && at < cap) {
+          r.tex_index = tex;
+          fout[at] = r;
+        }
+      }
+      kept += __popcll(bal);
+    }
+    __syncthreads();                                          // this step's state is complete before the next one reads it
+    if (lane == 0) {
+      *ch.n_state = kept;
+      if (op.out_f >= 0) n_out[op.out_f] = kept;
+    }
+    __syncthreads();
   }
 }
 
@@ -4770,6 +4873,25 @@ struct rr_ctx {
   rr_sim_frame* d_sims = nullptr;
   int cap_sims = 0;
   rr_drop* d_gen_drops = nullptr;    // staging of rr_generate_drops (host-pointer variant)
+  // angular noise on device-generated tables (rr_set_particle_noise, k_noise_chains)
+  double noise_std = 0.0, noise_scale = 0.0;
+  std::vector<uint32_t> run_frame, run_seed;
+  std::vector<int32_t> run_chain;                                       // entry p: its index among its simulated frame's entries
+  std::unordered_map<uint32_t, std::vector<uint32_t>> chain_seeds;      // simulated frame id -> seeds of its entries, in run order
+  struct NoiseState {                // one simulated frame's streaks as the calls enqueued so far leave them
+    rr_sim_frame sig;                // its settings (draw_seed, run_pos zeroed): other settings under the same id start afresh
+    int H = 0, W = 0;
+    rr_drop *pristine = nullptr, *state = nullptr;
+    int32_t *n_pristine = nullptr, *n_state = nullptr;
+    int32_t applied = 0;             // entries of its chain applied to `state`
+    bool valid = false;              // `state` holds something (else the next step starts from `pristine`)
+  };
+  std::unordered_map<uint32_t, NoiseState> noise_states;
+  std::vector<void*> noise_blocks;   // device memory of the states
+  uint8_t* d_noise_desc = nullptr;   // fresh states' rr_sim_frame records + NoiseChain + NoiseOp of a call
+  size_t cap_noise_desc = 0;
+  hipEvent_t ev_noise = nullptr;     // behind the last k_noise_chains: the next call's stream waits for it
+  bool ev_noise_used = false;
   int32_t* d_gen_counts = nullptr;
   size_t cap_gen_drops = 0, cap_gen_counts = 0;
   uint8_t* d_lut = nullptr;         // [256][4] RGBA colour map of the rain-mask PNG (rr_set_colormap)
@@ -4794,7 +4916,7 @@ struct rr_ctx {
     hipEvent_t ev[N] = {};
     bool used[N] = {};
     int next = 0;
-  } ring_frames, ring_pre, ring_sims;
+  } ring_frames, ring_pre, ring_sims, ring_noise;
   // last launch (for rr_synchronize bookkeeping)
   int last_n = 0;
   // host-pointer entry points: device staging per pipeline slot (slot 0 serves the synchronous calls)
@@ -5658,6 +5780,130 @@ int enqueue_prepass(rr_ctx* ctx, int n, const rr_prepass_in* in, const rr_prepas
   return RR_OK;
 }
 
+// the held states of every simulated frame (a new run, new diameter tables or a new streak database)
+int noise_states_drop(rr_ctx* ctx) {
+  if (ctx->noise_blocks.empty() && ctx->noise_states.empty()) return RR_OK;
+  HIPCHK(hipDeviceSynchronize());
+  for (void* b : ctx->noise_blocks) HIPCHK(hipFree(b));
+  ctx->noise_blocks.clear();
+  ctx->noise_states.clear();
+  return RR_OK;
+}
+
+// The frames of a call with angular noise (run_pos >= 1): plan, per simulated frame, the steps from its held state (or its
+// pristine streaks) to each of its frames -- in run order, one chain per simulated frame -- and enqueue them (k_noise_chains).
+// The plan is made here, in call order, so the held states follow the order of the calls whatever the streams.
+int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr_drop* drops_out, int cap, int32_t* n_out, hipStream_t s) {
+  std::vector<uint32_t> ids;                                            // simulated frames of the call, first appearance first
+  std::unordered_map<uint32_t, std::vector<std::pair<int32_t, int>>> frames_of;   // id -> (index in its chain, frame of the call)
+  for (int f = 0; f < n; f++) {
+    if (sims[f].run_pos == 0) continue;
+    const uint32_t id = sims[f].frame;
+    auto& v = frames_of[id];
+    if (v.empty()) ids.push_back(id);
+    v.push_back({ctx->run_chain[sims[f].run_pos - 1], f});
+  }
+  // states to make: simulated frames never seen, or seen with other settings
+  std::vector<rr_sim_frame> fresh;
+  std::vector<uint32_t> fresh_id;
+  int32_t stride = 1;
+  for (uint32_t id : ids) {
+    rr_sim_frame sig = sims[frames_of[id][0].second];
+    sig.draw_seed = 0;
+    sig.run_pos = 0;
+    auto it = ctx->noise_states.find(id);
+    if (it == ctx->noise_states.end() || memcmp(&it->second.sig, &sig, sizeof sig) != 0 || it->second.H != H || it->second.W != W) {
+      fresh.push_back(sig);
+      fresh_id.push_back(id);
+      stride = imax(stride, sig.n_particles);
+    }
+  }
+  const int m = (int)fresh.size();
+  if (m > 0) {                       // one block: pristine records, state records, pristine counts, state counts
+    const size_t recs = (size_t)m * (size_t)stride;
+    void* blk = nullptr;
+    HIPCHK(hipMalloc(&blk, 2 * recs * sizeof(rr_drop) + 2 * (size_t)m * sizeof(int32_t)));
+    ctx->noise_blocks.push_back(blk);
+    rr_drop* P = static_cast<rr_drop*>(blk);
+    int32_t* C = reinterpret_cast<int32_t*>(P + 2 * recs);
+    for (int i = 0; i < m; i++) {
+      rr_ctx::NoiseState st;
+      st.sig = fresh[i];
+      st.H = H;
+      st.W = W;
+      st.pristine = P + (size_t)i * stride;
+      st.state = P + recs + (size_t)i * stride;
+      st.n_pristine = C + i;
+      st.n_state = C + m + i;
+      ctx->noise_states[fresh_id[i]] = st;
+    }
+  }
+  // the plan: per chain, its frames in run order; an entry older than the held state restarts from the pristine streaks
+  std::vector<NoiseChain> chains;
+  std::vector<NoiseOp> ops;
+  for (uint32_t id : ids) {
+    rr_ctx::NoiseState& st = ctx->noise_states[id];
+    auto& v = frames_of[id];
+    std::stable_sort(v.begin(), v.end(), [](const std::pair<int32_t, int>& a, const std::pair<int32_t, int>& b) { return a.first < b.first; });
+    const std::vector<uint32_t>& seeds = ctx->chain_seeds[id];
+    NoiseChain ch{st.pristine, st.state, st.n_pristine, st.n_state, (int32_t)ops.size(), 0};
+    int32_t a = st.valid ? st.applied : 0;
+    int32_t from_p = st.valid ? 0 : 1;
+    for (const auto& cf : v) {
+      if (a > cf.first) {
+        a = 0;
+        from_p = 1;
+      }
+      for (; a <= cf.first; a++) {
+        ops.push_back(NoiseOp{seeds[a], a == cf.first ? cf.second : -1, from_p, 0});
+        from_p = 0;
+      }
+    }
+    st.applied = a;
+    st.valid = true;
+    ch.nop = (int32_t)ops.size() - ch.op0;
+    chains.push_back(ch);
+  }
+  // descriptors: [fresh rr_sim_frame][NoiseChain][NoiseOp], one copy kernel
+  const size_t b_sims = sizeof(rr_sim_frame) * (size_t)m, b_ch = sizeof(NoiseChain) * chains.size(), b_ops = sizeof(NoiseOp) * ops.size();
+  static_assert(sizeof(rr_sim_frame) % 8 == 0 && sizeof(NoiseChain) % 8 == 0 && sizeof(NoiseOp) % 4 == 0, "descriptor alignment");
+  const size_t bytes = b_sims + b_ch + b_ops;
+  int rc;
+  if (ctx->ev_noise_used) HIPCHK(hipStreamWaitEvent(s, ctx->ev_noise, 0));   // the previous call's chains (and descriptors) first
+  if (bytes > ctx->cap_noise_desc) {
+    HIPCHK(hipDeviceSynchronize());
+    if ((rc = dev_alloc(ctx, ctx->d_noise_desc, bytes + bytes / 2))) return rc;
+    ctx->cap_noise_desc = bytes + bytes / 2;
+  }
+  int ring_idx;
+  void* host;
+  if ((rc = ring_acquire(ctx, ctx->ring_noise, bytes, ring_idx, host))) return rc;
+  uint8_t* h8 = static_cast<uint8_t*>(host);
+  if (m) memcpy(h8, fresh.data(), b_sims);
+  memcpy(h8 + b_sims, chains.data(), b_ch);
+  memcpy(h8 + b_sims + b_ch, ops.data(), b_ops);
+  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_noise_desc),
+                     (int)(bytes / 4));
+  if ((rc = ring_commit(ctx, ctx->ring_noise, ring_idx, s))) return rc;
+  if (m > 0) {                       // pristine streaks of the fresh states: filtered, tex_index = first texture of the block of ten
+    ProfScope ps(ctx, s, "k_particles");
+    rr_drop* P = ctx->noise_states[fresh_id[0]].pristine;
+    hipLaunchKernelGGL(k_particles, dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
+                       ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P, stride, ctx->noise_states[fresh_id[0]].n_pristine, 0);
+  }
+  {
+    ProfScope ps(ctx, s, "k_noise_chains");
+    hipLaunchKernelGGL(k_noise_chains, dim3((unsigned)chains.size()), dim3(64), 0, s, reinterpret_cast<const NoiseChain*>(ctx->d_noise_desc + b_sims),
+                       reinterpret_cast<const NoiseOp*>(ctx->d_noise_desc + b_sims + b_ch), H, W, ctx->noise_std, ctx->noise_scale, drops_out,
+                       cap, n_out);
+  }
+  HIPCHK(hipGetLastError());
+  if (!ctx->ev_noise) HIPCHK(hipEventCreateWithFlags(&ctx->ev_noise, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(ctx->ev_noise, s));
+  ctx->ev_noise_used = true;
+  return RR_OK;
+}
+
 // particle generator + packer of n frames (device output); see include/rainhip.h
 int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr_drop* drops_out, int cap, int32_t* n_out, hipStream_t s) {
   if (n <= 0 || !sims || !drops_out || !n_out || cap <= 0 || H <= 0 || W <= 0) {
@@ -5681,6 +5927,24 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       return RR_E_ARG;
     }
   }
+  const bool noise_on = ctx->noise_std != 0.0 && ctx->noise_scale != 0.0;
+  int n_noisy = 0;
+  for (int f = 0; f < n; f++) {
+    const rr_sim_frame& sf = sims[f];
+    if (sf.run_pos == 0) continue;
+    if (sf.run_pos < 0 || sf.run_pos > (int)ctx->run_frame.size()) {
+      ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) + ") is outside the run of " +
+                 std::to_string(ctx->run_frame.size()) + " entries given to rr_set_particle_noise";
+      return RR_E_ARG;
+    }
+    if (ctx->run_frame[sf.run_pos - 1] != sf.frame || ctx->run_seed[sf.run_pos - 1] != sf.draw_seed) {
+      ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) + "): the run's entry is simulated frame " +
+                 std::to_string(ctx->run_frame[sf.run_pos - 1]) + " with seed " + std::to_string(ctx->run_seed[sf.run_pos - 1]) +
+                 ", the record says frame " + std::to_string(sf.frame) + " with seed " + std::to_string(sf.draw_seed);
+      return RR_E_ARG;
+    }
+    n_noisy += noise_on;
+  }
   int rc;
   if (n > ctx->cap_sims) {
     HIPCHK(hipDeviceSynchronize());
@@ -5694,16 +5958,19 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
   hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_sims),
                      (int)(sizeof(rr_sim_frame) * (size_t)n / 4));
   if ((rc = ring_commit(ctx, ctx->ring_sims, ring_idx, s))) return rc;
-  {
-    ProfScope ps(ctx, s, "k_particles");
-    hipLaunchKernelGGL(k_particles, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db,
-                       drops_out, cap, n_out);
-  }
-  {
-    ProfScope ps(ctx, s, "k_particle_draws");
-    hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out);
+  if (n_noisy < n) {                                         // frames with angular noise are left to k_noise_chains
+    {
+      ProfScope ps(ctx, s, "k_particles");
+      hipLaunchKernelGGL(k_particles, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db,
+                         drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
+    }
+    {
+      ProfScope ps(ctx, s, "k_particle_draws");
+      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
+    }
   }
   HIPCHK(hipGetLastError());
+  if (n_noisy > 0) return enqueue_noise(ctx, n, sims, H, W, drops_out, cap, n_out, s);
   return RR_OK;
 }
 
@@ -5839,7 +6106,10 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_sims);
   hipFree(ctx->d_gen_drops);
   hipFree(ctx->d_gen_counts);
-  for (auto* r : {&ctx->ring_frames, &ctx->ring_pre, &ctx->ring_sims})
+  for (void* b : ctx->noise_blocks) hipFree(b);
+  hipFree(ctx->d_noise_desc);
+  if (ctx->ev_noise) hipEventDestroy(ctx->ev_noise);
+  for (auto* r : {&ctx->ring_frames, &ctx->ring_pre, &ctx->ring_sims, &ctx->ring_noise})
     for (int k = 0; k < rr_ctx::DescRing::N; k++) {
       if (r->host[k]) hipHostFree(r->host[k]);
       if (r->ev[k]) hipEventDestroy(r->ev[k]);
@@ -5958,6 +6228,7 @@ static int set_db_meta(rr_ctx* ctx, const int32_t* tex_h, const int32_t* tex_w, 
     std::sort(r.begin(), r.end());
     r.erase(std::unique(r.begin(), r.end()), r.end());
     ctx->n_ratio = (int)r.size();
+    if ((rc = noise_states_drop(ctx))) return rc;     // pristine streaks carry the texture blocks
     if ((rc = dev_alloc(ctx, ctx->d_ratio_db, r.size() < 4 ? 4 : r.size()))) return rc;
     HIPCHK(hipMemcpy(ctx->d_ratio_db, r.data(), sizeof(double) * r.size(), hipMemcpyHostToDevice));
   }
@@ -6228,6 +6499,7 @@ int rr_set_particle_tables(rr_ctx* ctx, int32_t n_tables, int32_t n_grid, const 
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipDeviceSynchronize());
   int rc;
+  if ((rc = noise_states_drop(ctx))) return rc;       // pristine streaks come from the tables
   if ((rc = dev_alloc(ctx, ctx->d_dgrid, (size_t)n_grid))) return rc;
   if ((rc = dev_alloc(ctx, ctx->d_cdf, (size_t)n_tables * n_grid))) return rc;
   HIPCHK(hipMemcpy(ctx->d_dgrid, d_grid, sizeof(double) * n_grid, hipMemcpyHostToDevice));
@@ -6271,6 +6543,29 @@ int rr_generate_drops(rr_ctx* ctx, int32_t n, const rr_sim_frame* frames, int32_
 }
 
 int rr_sizeof_sim_frame(void) { return (int)sizeof(rr_sim_frame); }
+
+int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int32_t n_run, const uint32_t* run_frame, const uint32_t* run_seed) {
+  if (!ctx) return RR_E_ARG;
+  if (n_run < 0 || (n_run > 0 && (!run_frame || !run_seed)) || !std::isfinite(noise_std) || !std::isfinite(noise_scale)) {
+    ctx->err = "rr_set_particle_noise: bad argument (n_run >= 0 entries, both tables, finite noise_std / noise_scale)";
+    return RR_E_ARG;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = noise_states_drop(ctx))) return rc;
+  ctx->noise_std = noise_std;
+  ctx->noise_scale = noise_scale;
+  ctx->run_frame.assign(run_frame, run_frame + n_run);
+  ctx->run_seed.assign(run_seed, run_seed + n_run);
+  ctx->run_chain.resize(n_run);
+  ctx->chain_seeds.clear();
+  for (int32_t p = 0; p < n_run; p++) {
+    auto& v = ctx->chain_seeds[run_frame[p]];
+    ctx->run_chain[p] = (int32_t)v.size();
+    v.push_back(run_seed[p]);
+  }
+  return RR_OK;
+}
 
 }  // extern "C"
 

@@ -132,6 +132,47 @@ RR_HD double det_exp(double x) {
   return ldexp(p, (int)k);
 }
 
+// log(x), 0 < x < 1, from frexp / + - * / (tools/particles.py det_log: fdlibm's log1p polynomial in s = f / (2 + f))
+RR_HD double det_log(double x) {
+  int e;
+  double m = frexp(x, &e);                                  // exact: x = m 2^e, m in [0.5, 1)
+  if (m < 0.70710678118654752440) {
+    m = m * 2.0;
+    e = e - 1;
+  }
+  const double k = (double)e;
+  const double f = m - 1.0;                                 // exact (Sterbenz)
+  const double hfsq = 0.5 * f * f;
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  const double w = z * z;
+  const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
+  const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
+  const double r = t2 + t1;
+  return k * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + r) + k * 1.90821492927058770002e-10)) - f);
+}
+
+// sin(x), cos(x) (tools/particles.py det_sincos): Cody-Waite reduction by pi/2 in three parts (exact k pi/2 for |k| < 2^20),
+// musl's kernels on [-pi/4, pi/4], the quadrant from k without integer conversion of a possibly huge k
+RR_HD void det_sincos(double x, double& sn, double& cn) {
+  const double k = rint(x * 6.36619772367581382433e-01);
+  const double r = ((x - k * 1.57079632673412561417e+00) - k * 6.07710050630396597660e-11) - k * 2.02226624879595063154e-21;
+  const double z = r * r;
+  const double w = z * z;
+  const double rs = (8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 + z * 2.75573137070700676789e-06)) +
+                    (z * w) * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10);
+  const double sr = r + (z * r) * (-1.66666666666666324348e-01 + z * rs);
+  const double rc = z * (4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * 2.48015872894767294178e-05)) +
+                    (w * w) * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11));
+  const double hz = 0.5 * z;
+  const double wc = 1.0 - hz;
+  const double cr = wc + (((1.0 - wc) - hz) + z * rc);
+  const double q = k - 4.0 * rint(k * 0.25);               // {-2 .. 2}, exact
+  const int qi = (q == q) ? (((int)q) & 3) : 0;            // NaN (x = inf / NaN): r is NaN already
+  sn = qi == 0 ? sr : (qi == 1 ? cr : (qi == 2 ? -sr : -cr));
+  cn = qi == 0 ? cr : (qi == 1 ? -sr : (qi == 2 ? -cr : sr));
+}
+
 // un-normalised gaussian weight phi(i) for tap distance i (scipy _gaussian_kernel1d)
 RR_HD double gauss_phi(double sigma, int i) {
   double sigma2 = sigma * sigma;

@@ -148,6 +148,39 @@ RR_HD bool derive_drop(const Particle& p, int render_scale, int W, int H, rr_dro
          max_width < m && length < m && (in_s || in_e);                        // generator.py:413-420
 }
 
+// ---- angular noise (--noise_std, generator.py:136-163) on a run's device-generated tables (tools/particles.py noise_step)
+// the frame filter of Generator.run (generator.py:413-420) on a record's CURRENT end points (a rotated streak may leave)
+RR_HD bool drop_in_frame(const rr_drop& d, int W, int H) {
+  const int64_t m = H > W ? H : W;
+  const bool in_s = 0 <= d.x0 && d.x0 < W && 0 <= d.y0 && d.y0 < H, in_e = 0 <= d.x1 && d.x1 < W && 0 <= d.y1 && d.y1 < H;
+  return 1 <= d.max_width && d.max_width < m && 1 <= d.length && d.length < m && (in_s || in_e);
+}
+
+// numpy's legacy_gauss: the accepted polar pair (x1, x2), r2 = x1^2 + x2^2, yields f x2 now and f x1 for the next call
+RR_HD double polar_factor(double r2) { return sqrt(-2.0 * rr::det_log(r2) / r2); }
+
+// the noise angle of a non-Big drop in degrees: normal(0, noise_std) * noise_scale (generator.py:136)
+RR_HD double noise_degrees(double g, double noise_std, double noise_scale) { return (0.0 + noise_std * g) * noise_scale; }
+
+// a kept non-Big drop turned by noise_deg: rotation terms cos / sin(-(theta + noise) * pi / 180) as the angle sum of the exact
+// cos / sin(-theta) = -dy / n, -|dx| / n (derive_drop) of the end points BEFORE the turn and det_sincos(noise); the end
+// points turned about their midpoint in hip_backend.pack_frame's operation order, truncated toward zero (numpy's int64 store)
+RR_HD void noise_rotate(rr_drop& d, double noise_deg) {
+  double sn, cn;
+  rr::det_sincos(noise_deg * 0.017453292519943295, sn, cn);   // np.deg2rad: x * (pi / 180)
+  const double sx = (double)d.x0, sy = (double)d.y0, ex = (double)d.x1, ey = (double)d.y1;
+  const double fx = sx - ex, fy = sy - ey;
+  const double n1 = sqrt(fx * fx + fy * fy);
+  const double c0 = (fx / n1) * 0.0 + (fy / n1) * -1.0, s0 = -(fabs(fx) / n1);
+  d.rot_cos = c0 * cn + s0 * sn;
+  d.rot_sin = s0 * cn - c0 * sn;
+  const double mx = (ex + sx) / 2.0, my = (ey + sy) / 2.0;
+  d.x0 = (int32_t)(int64_t)(((sx - mx) * cn - (sy - my) * sn) + mx);
+  d.y0 = (int32_t)(int64_t)(((sx - mx) * sn + (sy - my) * cn) + my);
+  d.x1 = (int32_t)(int64_t)(((ex - mx) * cn - (ey - my) * sn) + mx);
+  d.y1 = (int32_t)(int64_t)(((ex - mx) * sn + (ey - my) * cn) + my);
+}
+
 // the block of ten textures take_drop_texture draws from (bad_weather.py:250-265): NaN falls through to the last one
 RR_HD int texture_bucket(double ratio, const double* ratio_db) {
   int b = 4;

@@ -54,7 +54,7 @@ DROP_DTYPE = np.dtype([
 # numpy mirror of rr_sim_frame (the particle generator's per-frame settings, include/rainhip.h)
 SIM_FRAME_DTYPE = np.dtype([
     ('sensor_w', '<i4'), ('sensor_h', '<i4'), ('render_scale', '<i4'), ('n_particles', '<i4'),
-    ('key0', '<u4'), ('key1', '<u4'), ('frame', '<u4'), ('draw_seed', '<u4'), ('table', '<i4'), ('reserved', '<i4'),
+    ('key0', '<u4'), ('key1', '<u4'), ('frame', '<u4'), ('draw_seed', '<u4'), ('table', '<i4'), ('run_pos', '<i4'),
     ('fpx', '<f8'), ('exposure_s', '<f8'), ('speed_mps', '<f8'), ('wind_sigma', '<f8'), ('margin', '<f8'), ('min_px', '<f8'),
     ('z_far', '<f8'),
 ], align=True)
@@ -132,7 +132,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_particle', 'rr_sizeof_particle_frame', 'rr_set_colormap', 'rr_host_frame_draws', 'rr_host_assemble_drops',
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
-           'rr_sizeof_sim_frame']
+           'rr_sizeof_sim_frame', 'rr_set_particle_noise']
 
 _lib = None
 
@@ -224,6 +224,8 @@ def load_library(path=None):
     lib.rr_generate_drops_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     lib.rr_set_solid_angles.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    lib.rr_set_particle_noise.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
+                                          ctypes.c_void_p]
     lib.rr_generate_drops.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
@@ -806,6 +808,16 @@ class RainHip:
         c = np.ascontiguousarray(np.atleast_2d(cdf), np.float64)
         assert c.shape[1] == len(d)
         self._check(self.lib.rr_set_particle_tables(self.h, c.shape[0], len(d), _ptr(d), _ptr(c)), 'rr_set_particle_tables')
+
+    def set_particle_noise(self, noise_std, noise_scale, run_frame=(), run_seed=()):
+        """rr_set_particle_noise: angular noise on device-generated tables.  Entry p of the run is simulated frame run_frame[p]
+        drawn with seed run_seed[p] (tools/particles.run_table); a SIM_FRAME_DTYPE record with run_pos = p + 1 is that entry.
+        Drops the state of an earlier run."""
+        rf = np.ascontiguousarray(run_frame, np.uint32)
+        rs = np.ascontiguousarray(run_seed, np.uint32)
+        assert rf.shape == rs.shape and rf.ndim == 1
+        self._check(self.lib.rr_set_particle_noise(self.h, float(noise_std), float(noise_scale), len(rf), _ptr(rf), _ptr(rs)),
+                    'rr_set_particle_noise')
 
     def generate_drops_device(self, sims, H, W, drops_ptr, cap, n_out_ptr, stream=None):
         """rr_generate_drops_device: sims = SIM_FRAME_DTYPE records (host); drops_ptr / n_out_ptr = DEVICE addresses of

@@ -63,6 +63,166 @@ def det_exp(x):
     return np.ldexp(p, k.astype(np.int64))
 
 
+# ---- angular noise (--noise_std) on device-generated tables: the same statement in rr_device.h / rr_particles.h ---------
+# log and sin / cos in the style of det_exp: + - * / sqrt rint and exact power-of-two scaling only, so that numpy, g++ and
+# gfx950 agree to the bit.  Polynomials of fdlibm / musl (public domain): within an ulp of the exact value.
+_LG = (6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01, 2.222219843214978396e-01,
+       1.818357216161805012e-01, 1.531383769920937332e-01, 1.479819860511658591e-01)
+_LN2_HI, _LN2_LO = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+_S = (-1.66666666666666324348e-01, 8.33333333332248946124e-03, -1.98412698298579493134e-04, 2.75573137070700676789e-06,
+      -2.50507602534068634195e-08, 1.58969099521155010221e-10)
+_C = (4.16666666666666019037e-02, -1.38888888888741095749e-03, 2.48015872894767294178e-05, -2.75573143513906633035e-07,
+      2.08757232129817482790e-09, -1.13596475577881948265e-11)
+_INV_PIO2, _PIO2_1, _PIO2_2, _PIO2_2T = 6.36619772367581382433e-01, 1.57079632673412561417e+00, 6.07710050630396597660e-11, \
+    2.02226624879595063154e-21
+DEG2RAD = np.pi / 180                                     # np.deg2rad(x) is x * (pi / 180)
+
+
+def det_log(x):
+    """log(x) for 0 < x < 1 (the polar method's r2): x = m 2^e by frexp (exact), m in [sqrt(1/2), sqrt(2)), then fdlibm's
+    log1p polynomial in s = f / (2 + f), f = m - 1 (exact).  rr_device.h det_log is the same sequence of operations."""
+    x = np.asarray(x, np.float64)
+    m, e = np.frexp(x)
+    lo = m < 0.70710678118654752440
+    m = np.where(lo, m * 2.0, m)
+    k = (e - lo).astype(np.float64)
+    f = m - 1.0
+    hfsq = 0.5 * f * f
+    s = f / (2.0 + f)
+    z = s * s
+    w = z * z
+    t1 = w * (_LG[1] + w * (_LG[3] + w * _LG[5]))
+    t2 = z * (_LG[0] + w * (_LG[2] + w * (_LG[4] + w * _LG[6])))
+    r = t2 + t1
+    return k * _LN2_HI - ((hfsq - (s * (hfsq + r) + k * _LN2_LO)) - f)
+
+
+def det_sincos(x):
+    """(sin x, cos x): Cody-Waite reduction by pi/2 in three parts (k pi/2 exact for |k| < 2^20, i.e. |x| < 1.6e6, some
+    9e7 degrees), then musl's kernels on [-pi/4, pi/4].  Same bits everywhere for any finite x; NaN for inf / NaN."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid='ignore'):
+        return _det_sincos(x)
+
+
+def _det_sincos(x):
+    k = np.rint(x * _INV_PIO2)
+    r = ((x - k * _PIO2_1) - k * _PIO2_2) - k * _PIO2_2T
+    z = r * r
+    w = z * z
+    rs = (_S[1] + z * (_S[2] + z * _S[3])) + (z * w) * (_S[4] + z * _S[5])
+    sr = r + (z * r) * (_S[0] + z * rs)
+    rc = z * (_C[0] + z * (_C[1] + z * _C[2])) + (w * w) * (_C[3] + z * (_C[4] + z * _C[5]))
+    hz = 0.5 * z
+    wc = 1.0 - hz
+    cr = wc + (((1.0 - wc) - hz) + z * rc)
+    q = k - 4.0 * np.rint(k * 0.25)                       # quadrant in {-2 .. 2}, exact (0 beyond 2^53)
+    qi = np.where(np.isfinite(q), q, 0).astype(np.int64) & 3
+    sn = np.select([qi == 0, qi == 1, qi == 2], [sr, cr, -sr], -cr)
+    cn = np.select([qi == 0, qi == 1, qi == 2], [cr, -sr, -cr], sr)
+    return sn, cn
+
+
+def polar_factor(r2):
+    """numpy's legacy_gauss: the polar pair (x1, x2) with r2 = x1^2 + x2^2 in (0, 1) gives f * x2 now and f * x1 next."""
+    return np.sqrt(-2.0 * det_log(r2) / r2)
+
+
+def legacy_draws(seed, tex_lo, is_big):
+    """One frame's drop loop for np.random.seed(seed): per drop randint(lo, lo + 10), per non-Big drop the legacy normal
+    deviate (0 for Big drops) -- numpy's stream word for word, the deviate with det_log instead of libm's log."""
+    rs = np.random.RandomState(int(seed))
+    words, at = [], [0]
+
+    def u32():
+        if at[0] == len(words):
+            words.extend(rs.randint(0, 2 ** 32, size=4096, dtype=np.uint32).tolist())
+        at[0] += 1
+        return words[at[0] - 1]
+
+    def dbl():
+        a, b = u32() >> 5, u32() >> 6
+        return (a * 67108864.0 + b) / 9007199254740992.0
+    n = len(tex_lo)
+    tex = np.zeros(n, np.int32)
+    g = np.zeros(n, np.float64)
+    cached = None
+    for i, (lo, big) in enumerate(zip(np.asarray(tex_lo).tolist(), np.asarray(is_big).tolist())):
+        v = u32() & 15
+        while v > 9:
+            v = u32() & 15
+        tex[i] = lo + v
+        if big:
+            continue
+        if cached is not None:
+            g[i], cached = cached, None
+            continue
+        while True:
+            x1, x2 = 2.0 * dbl() - 1.0, 2.0 * dbl() - 1.0
+            r2 = x1 * x1 + x2 * x2
+            if r2 < 1.0 and r2 != 0.0:
+                break
+        f = float(polar_factor(r2))
+        cached = f * x1
+        g[i] = f * x2
+    return tex, g
+
+
+def noise_degrees(g, noise_std, noise_scale):
+    """normal(0, noise_std) * noise_scale in the reference's operation order (generator.py:136)."""
+    return (0.0 + noise_std * np.asarray(g, np.float64)) * noise_scale
+
+
+def noise_rotation(s, e, noise_deg):
+    """Rotation terms and rotated end points of streaks (start / end: (n, 2) integer positions) turned by noise_deg:
+    rot_cos / rot_sin = cos / sin(-(theta + noise) * pi / 180) (generator.py:138-163) as the angle sum of the exact
+    cos / sin(-theta) = -dy / n, -|dx| / n and det_sincos(noise); the end points turned about their midpoint in
+    hip_backend.pack_frame's operation order and truncated toward zero like numpy's int64 store."""
+    s = np.asarray(s).astype(np.float64)
+    e = np.asarray(e).astype(np.float64)
+    sn, cn = det_sincos(np.asarray(noise_deg, np.float64) * DEG2RAD)
+    with np.errstate(all='ignore'):
+        d = s - e
+        n1 = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+        c0 = (d[:, 0] / n1) * 0.0 + (d[:, 1] / n1) * -1.0
+        s0 = -(np.abs(d[:, 0]) / n1)
+        rot_cos = c0 * cn + s0 * sn
+        rot_sin = s0 * cn - c0 * sn
+    mx = (e[:, 0] + s[:, 0]) / 2
+    my = (e[:, 1] + s[:, 1]) / 2
+    s2 = np.stack([(s[:, 0] - mx) * cn - (s[:, 1] - my) * sn + mx, (s[:, 0] - mx) * sn + (s[:, 1] - my) * cn + my], axis=1).astype(np.int64)
+    e2 = np.stack([(e[:, 0] - mx) * cn - (e[:, 1] - my) * sn + mx, (e[:, 0] - mx) * sn + (e[:, 1] - my) * cn + my], axis=1).astype(np.int64)
+    return rot_cos, rot_sin, s2, e2
+
+
+def noise_step(table, imW, imH, ratio_db, seed, noise_std, noise_scale):
+    """One frame of a run with angular noise on a StreakTable, in place: the frame filter on the current end points, the
+    frame's draws over the kept streaks, the rotation of the kept non-Big ones.  Returns the frame's DROP_DTYPE records
+    (rotation terms from the end points before the step, end points after it) -- what the device's chain step makes."""
+    from .. import hip_backend
+    idx = hip_backend.filter_streaks(table, imW, imH)
+    out = np.zeros(len(idx), hip_backend.DROP_DTYPE)
+    if len(idx) == 0:
+        return out
+    r = table.ratio[idx]
+    b = np.full(len(idx), 4, np.int32)
+    for k in (3, 2, 1, 0):                                # take_drop_texture's blocks of ten (NaN: the last one)
+        b = np.where(r < ratio_db[k], k, b)
+    types = table.type[idx]
+    tex, g = legacy_draws(seed, 10 * b, types == 0)
+    nb = types != 0
+    rot_cos, rot_sin, s2, e2 = noise_rotation(table.ips[idx], table.ipe[idx], noise_degrees(g, noise_std, noise_scale))
+    table.ips[idx[nb]] = s2[nb]
+    table.ipe[idx[nb]] = e2[nb]
+    out['x0'], out['y0'] = table.ips[idx, 0], table.ips[idx, 1]
+    out['x1'], out['y1'] = table.ipe[idx, 0], table.ipe[idx, 1]
+    out['max_width'], out['length'], out['type'], out['tex_index'] = table.max_width[idx], table.length[idx], types, tex
+    out['iw1'], out['iw2'], out['wps'], out['wpe'] = table.iw1[idx], table.iw2[idx], table.wps[idx], table.wpe[idx]
+    out['rot_cos'] = np.where(nb, rot_cos, 1.0)
+    out['rot_sin'] = np.where(nb, rot_sin, 0.0)
+    return out
+
+
 def terminal_velocity(d_mm):
     """m/s (Atlas, Srivastava & Sekhon 1973)."""
     return 9.65 - 10.3 * det_exp(-0.6 * np.asarray(d_mm, np.float64))
@@ -259,29 +419,61 @@ def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=N
     return sims, dgrid, cdf
 
 
-def expected_records(sims, dgrid, cdf, db, dataset='kitti'):
+def _loaded_table(s, dgrid, cdf, db, dataset):
+    """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
+    (the loader's derived fields) on the rendered frame."""
+    from ..common import bad_weather as bw
+    cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
+                               speed=float(s['speed_mps'])))()
+    seed = int(s['key0']) | (int(s['key1']) << 32)
+    rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
+                         float(s['margin']), float(s['min_px']), float(s['z_far']))
+    fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
+    fr[0] = (0, 0, 0, len(rec), 0, len(rec))
+    m = bw.DBManager()
+    m.ratio = db.ratio
+    rs = int(s['render_scale'])
+    W, H = int(s['sensor_w']) // rs, int(s['sensor_h']) // rs
+    m.load_streaks_from_records(fr, rec, dataset, {"render_scale": rs}, [W, H])
+    return m.streaks_simulator[0].table, m, W, H
+
+
+def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
-    with the streak database loaded (texture ratios)."""
+    with the streak database loaded (texture ratios).
+
+    Angular noise (noise_std and noise_scale both non-zero, rr_set_particle_noise): `run` = (run_frame, run_seed), the
+    run's entries in order.  A frame with run_pos p >= 1 is entry p - 1: its simulated frame's pristine streaks are
+    stepped (noise_step) through every earlier entry of the same simulated frame, in run order, then through its own
+    entry, whose records it gets -- the reference's in-place rotation of the shared table (generator.py:152-161)
+    replayed from scratch, so the result depends on nothing but the frame."""
     from .. import hip_backend
-    from ..common import bad_weather as bw
+    noisy = bool(noise_std) and bool(noise_scale)
     out = []
     for s in sims:
-        cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
-                                   speed=float(s['speed_mps'])))()
-        seed = int(s['key0']) | (int(s['key1']) << 32)
-        rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
-                             float(s['margin']), float(s['min_px']), float(s['z_far']))
-        fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
-        fr[0] = (0, 0, 0, len(rec), 0, len(rec))
-        m = bw.DBManager()
-        m.ratio = db.ratio
-        rs = int(s['render_scale'])
-        W, H = int(s['sensor_w']) // rs, int(s['sensor_h']) // rs
-        m.load_streaks_from_records(fr, rec, dataset, {"render_scale": rs}, [W, H])
-        out.append(hip_backend.pack_frame(m.streaks_simulator[0].table, m, W, H, int(s['draw_seed']), rotation='exact'))
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset)
+        p = int(s['run_pos'])
+        if not noisy or p == 0:
+            out.append(hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact'))
+            continue
+        run_frame, run_seed = (np.asarray(v).astype(np.int64) for v in run)
+        assert 1 <= p <= len(run_frame) and run_frame[p - 1] == int(s['frame']) and run_seed[p - 1] == int(s['draw_seed']), \
+            'run_pos %d does not name this frame' % p
+        ratio_db = np.asarray(db.ratio, np.float64)
+        for j in range(p - 1):
+            if run_frame[j] == run_frame[p - 1]:
+                noise_step(table, W, H, ratio_db, int(run_seed[j]), noise_std, noise_scale)
+        out.append(noise_step(table, W, H, ratio_db, int(s['draw_seed']), noise_std, noise_scale))
     return out
+
+
+def run_table(sims, n_sim, f_name_idx):
+    """(run_frame, run_seed) of a run whose entries are the frames f_name_idx in order (generator.py:304-321: simulated
+    frame f % n_sim, draws seeded with f): rr_set_particle_noise's table."""
+    f = np.asarray(f_name_idx, np.int64)
+    return np.asarray(sims['frame'], np.uint32)[f % n_sim], f.astype(np.uint32)
 
 
 def write_xml(path, frames, drops):

@@ -1,0 +1,270 @@
+"""GPU tier: angular noise (--noise_std / --noise_scale) on drop tables born on the device (rr_set_particle_noise,
+rr_sim_frame.run_pos, k_noise_chains).
+
+  1. device records == tools/particles.expected_records with noise, every field bit for bit: nuScenes 100 / 200 mm/hr,
+     KITTI 100, Cityscapes at render scale 2; two noise settings; histories of 0, 1 and 5 earlier entries;
+  2. the state the context holds: entries in run order (several per call, a simulated frame twice in one call), then out
+     of order (a reset), and a second context that only sees every other entry (rank 1 of 2);
+  3. rr_pipeline_submit with sim + run_pos renders what the same frames render from the uploaded host-statement records;
+  4. main.py --device_particles --noise_std on KITTI-sized frames, single rank and two ranks on GPU 0."""
+import importlib
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import helpers as h
+
+pytestmark = pytest.mark.gpu
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+db = importlib.import_module('rain-rendering_amd.common.db')
+
+
+def _options(dataset, **kw):
+    o = dict(db.settings(dataset))
+    o.pop('sequences', None)
+    o.update(kw)
+    return o
+
+
+def _rh(sc):
+    rh = h.hb.RainHip(0)
+    rh.set_streak_db(sc.db.streaks_light)
+    rh.set_camera(sc.cam)
+    return rh
+
+
+def _entries(sims, f_idx, entries):
+    """records of the run entries `entries` of a run whose entry p is frame f_idx[p]"""
+    n_sim = len(sims)
+    fr = sims[np.asarray(f_idx)[entries] % n_sim].copy()
+    fr['draw_seed'] = np.asarray(f_idx)[entries]
+    fr['run_pos'] = np.asarray(entries) + 1
+    return fr
+
+
+def _canon(a):
+    """a field with every NaN as the one quiet NaN: a streak turned to zero length has NaN rotation terms (0 / 0, as in the
+    reference), whose sign bit is the machine's (x86 and gfx950 differ); every other bit must agree"""
+    a = np.array(a)
+    if a.dtype.kind == 'f':
+        a[np.isnan(a)] = np.nan
+    return a.tobytes()
+
+
+def _same(got, want, what):
+    assert len(got) == len(want), '%s: %d drops on the device, %d on the host' % (what, len(got), len(want))
+    for name in h.hb.DROP_DTYPE.names:
+        assert _canon(got[name]) == _canon(want[name]), '%s: %s' % (what, name)
+
+
+@pytest.mark.parametrize("noise_std,noise_scale", [(3.0, 1.0), (10.0, 0.5)])
+@pytest.mark.parametrize("dataset,rs,rate", [('nuscenes', 1, 100), ('nuscenes', 1, 200), ('kitti', 1, 100), ('cityscapes', 2, 50)])
+def test_device_records_equal_host_statement_with_noise(tmp_path, built, dataset, rs, rate, noise_std, noise_scale):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0])})
+    sims, dgrid, cdf = particles.sim_frames(opt, rate, 2, render_scale=rs, seed=99)
+    f_idx = list(range(12))                                   # entry p: simulated frame p % 2, seed p
+    run = particles.run_table(sims, 2, f_idx)
+    fr = _entries(sims, f_idx, [0, 2, 10, 1])                 # histories of 0, 1 and 5 entries (and 0 for the other frame)
+    want = particles.expected_records(fr, dgrid, cdf, sc.db, noise_std=noise_std, noise_scale=noise_scale, run=run)
+    W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_noise(noise_std, noise_scale, *run)
+        got, cnt = rh.generate_drops(fr, H, W)
+        # noise off: run_pos changes nothing
+        rh.set_particle_noise(0.0, noise_scale, *run)
+        quiet, _ = rh.generate_drops(fr, H, W)
+    finally:
+        rh.close()
+    for k, p in enumerate((0, 2, 10, 1)):
+        assert int(cnt[k]) == len(want[k]) > 20
+        _same(got[k], want[k], 'entry %d' % p)
+        assert (want[k]['type'] != 0).sum() > 10
+    plain = fr.copy()
+    plain['run_pos'] = 0
+    for k, w in enumerate(particles.expected_records(plain, dgrid, cdf, sc.db)):
+        _same(quiet[k], w, 'noise off, frame %d' % k)
+    assert got[2].tobytes() != quiet[2].tobytes()
+
+
+def test_held_state_in_order_out_of_order_and_per_rank(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _options('kitti')
+    sims, dgrid, cdf = particles.sim_frames(opt, 100, 3, seed=5, count=3000)
+    f_idx = list(range(10))
+    run = particles.run_table(sims, 3, f_idx)
+    want = particles.expected_records(_entries(sims, f_idx, list(range(10))), dgrid, cdf, sc.db, noise_std=4.0, noise_scale=1.0, run=run)
+    W, H = opt["cam_CCD_WH"]
+    a, b = _rh(sc), _rh(sc)
+    try:
+        for rh in (a, b):
+            rh.set_particle_tables(dgrid, cdf)
+            rh.set_particle_noise(4.0, 1.0, *run)
+        # in order, several entries per call, simulated frame 0 twice in the first call (entries 0 and 3)
+        for call in ([0, 1, 2, 3], [4, 5, 6, 7, 8, 9], [2, 7], [9, 0, 6]):       # then out of order: resets
+            got, _ = a.generate_drops(_entries(sims, f_idx, call), H, W)
+            for k, p in enumerate(call):
+                _same(got[k], want[p], 'context A, entry %d of call %s' % (p, call))
+        for call in ([1, 3], [5, 7, 9]):                      # rank 1 of 2: the other entries are replayed, not rendered
+            got, _ = b.generate_drops(_entries(sims, f_idx, call), H, W)
+            for k, p in enumerate(call):
+                _same(got[k], want[p], 'context B, entry %d' % p)
+        # a run_pos the run does not have, or one that names another frame / seed
+        bad = _entries(sims, f_idx, [3])
+        bad['run_pos'] = 11
+        with pytest.raises(RuntimeError, match='run_pos'):
+            a.generate_drops(bad, H, W)
+        bad['run_pos'] = 2
+        with pytest.raises(RuntimeError, match='run_pos'):
+            a.generate_drops(bad, H, W)
+    finally:
+        a.close()
+        b.close()
+
+
+def test_noisy_generated_tables_through_the_async_pipeline(tmp_path, built):
+    fogmod = importlib.import_module('rain-rendering_amd.common.add_attenuation')
+    envmod = importlib.import_module('rain-rendering_amd.common.envmap')
+    imgops = importlib.import_module('rain-rendering_amd.common.imgops')
+    H, W = 225, 400
+    sc = h.Scene(tmp_path, H, W, 10, cam=h.NUSCENES)
+    opt = _options('nuscenes', cam_CCD_WH=[W, H])
+    sims, dgrid, cdf = particles.sim_frames(opt, 100, 2, seed=3, count=900)
+    f_idx = list(range(6))
+    run = particles.run_table(sims, 2, f_idx)
+    fr = _entries(sims, f_idx, f_idx)
+    want = particles.expected_records(fr, dgrid, cdf, sc.db, noise_std=5.0, noise_scale=1.0, run=run)
+    cs = sc.cam_settings
+    consts = fogmod.FogRain(rain_intensity=100, focal=cs['focal_mm'] / 1000., f_number=cs['f_number'], angle=90, exposure=cs['exposure_ms'],
+                            camera_gain=1.0).constants()
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_noise(5.0, 1.0, *run)
+        rh.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+        we = rh.set_envmap_geometry(H, W, *envmod.EnvironmentMapGenerator(cs['focal_mm'] / 1000., W, H).device_tables(H, W))
+        omega = h.solid_angle.get_solid_angles(np.empty((H, we, 0)))
+        bgs = [np.ascontiguousarray((h.synthetic.make_frame(i, H, W) * 255).astype(np.uint8)) for i in range(6)]
+        depth = (np.linspace(80, 2, H, dtype=np.float32)[:, None] * np.ones((1, W), np.float32))
+        outs_g, outs_r = [], []
+        for slot, part in enumerate(([0, 1, 2], [3, 4, 5])):  # two slots: the state follows the order of submission
+            gen = [dict(bg_u8=bgs[i], depth=depth, fog=consts, omega=omega, sim=fr[i:i + 1], drops_cap=900) for i in part]
+            og = [dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W)), status=np.zeros(900, np.int32), n_drops=np.zeros(1, np.int32))
+                  for _ in part]
+            rh.pipeline_submit(slot, gen, og)
+            outs_g.append((slot, gen, og))
+        for slot, gen, og in outs_g:
+            while not rh.pipeline_wait(slot):
+                rh.pipeline_submit(slot, gen, og)
+        ref = [dict(bg_u8=bgs[i], depth=depth, fog=consts, omega=omega, drops=want[i]) for i in range(6)]
+        outs_r = [dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W)), status=np.zeros(len(want[i]), np.int32)) for i in range(6)]
+        rh.pipeline_submit(2, ref, outs_r)
+        while not rh.pipeline_wait(2):
+            rh.pipeline_submit(2, ref, outs_r)
+    finally:
+        rh.close()
+    og = outs_g[0][2] + outs_g[1][2]
+    for i in range(6):
+        n = int(og[i]['n_drops'][0])
+        assert n == len(want[i]) > 100
+        assert np.array_equal(og[i]['status'][:n], outs_r[i]['status'])
+        assert og[i]['mask'].tobytes() == outs_r[i]['mask'].tobytes() and og[i]['image_u8'].tobytes() == outs_r[i]['image_u8'].tobytes()
+        assert og[i]['mask'].max() > 0
+
+
+_WRAPPER = '''import importlib, os, sys
+sys.path.insert(0, {root!r})
+importlib.import_module('rain-rendering_amd.tools.particles').n_sim_frames = lambda options: 3
+main = importlib.import_module('rain-rendering_amd.main')
+main.main(sys.argv[1:])
+'''
+
+
+def test_main_device_particles_with_angular_noise(tmp_path, built):
+    """`main.py --dataset kitti --device_particles --noise_std 3 --noise_scale 1`: 10 KITTI-sized frames over 3 simulated
+    frames (so every simulated frame is used up to four times), batches of 4: every PNG is the render of the host
+    statement's records; two ranks on GPU 0 write the same bytes."""
+    tmp = str(tmp_path)
+    H, W, n = 375, 1242, 10
+    src = os.path.join(tmp, 'source')
+    h.synthetic.write_dataset(src, 'kitti', os.path.join('data_object', 'training'), n, H, W)
+    tex_dir, norm = h.synthetic.write_streak_db(os.path.join(tmp, 'rainstreakdb'))
+    wrapper = os.path.join(tmp, 'run_main.py')                # the driver with 3 simulated frames per sequence
+    with open(wrapper, 'w') as fh:
+        fh.write(_WRAPPER.format(root=h.ROOT))
+    common = ['--dataset', 'kitti', '-k', src, '-d', src, '-r', os.path.join(tmp, 'particles'), '-sd', os.path.join(tmp, 'rainstreakdb'),
+              '-i', '100', '--noverbose', '--device_particles', '--noise_std', '3', '--noise_scale', '1']
+    env = dict(os.environ, RAIN_BATCH='4')
+    r = subprocess.run([sys.executable, wrapper] + common + ['--output', os.path.join(tmp, 'out1')], env=env, cwd=h.ROOT, capture_output=True,
+                       timeout=900)
+    assert r.returncode == 0, (r.stdout.decode()[-3000:], r.stderr.decode()[-3000:])
+    sub = os.path.join('kitti', 'data_object', 'training', 'rain', '100mm')
+    out1 = os.path.join(tmp, 'out1', sub)
+    assert not os.path.exists(os.path.join(tmp, 'particles'))
+
+    # the host statement's records of the same run, rendered through the library
+    imgops = importlib.import_module('rain-rendering_amd.common.imgops')
+    fogmod = importlib.import_module('rain-rendering_amd.common.add_attenuation')
+    envmod = importlib.import_module('rain-rendering_amd.common.envmap')
+    st = db.settings('kitti')
+    opts = db.sim('kitti', 'data_object', os.path.join(tmp, 'particles', 'kitti'))['options']
+    sims, dgrid, cdf = particles.sim_frames(opts, 100, 3, render_scale=1, seed=0)
+    run = particles.run_table(sims, 3, list(range(n)))
+    streaks = h.bw.DBManager(streaks_path=tex_dir, norm_coeff_path=norm)
+    streaks.load_streak_database()
+    want = particles.expected_records(_entries(sims, list(range(n)), list(range(n))), dgrid, cdf, streaks, noise_std=3.0, noise_scale=1.0,
+                                      run=run)
+    focal = st['cam_focal'] / 1000.
+    consts = fogmod.FogRain(rain_intensity=100, focal=focal, f_number=st['cam_f_number'], angle=90, exposure=st['cam_exposure'],
+                            camera_gain=st['cam_gain']).constants()
+    rh = h.hb.RainHip(0)
+    try:
+        rh.set_streak_db(streaks.streaks_light)
+        rh.set_camera(h.hb.make_camera(focal, st['cam_f_number'], st['cam_exposure']))
+        rh.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+        rh.set_colormap(imgops.viridis_lut())
+        we = rh.set_envmap_geometry(H, W, *envmod.EnvironmentMapGenerator(focal, W, H).device_tables(H, W))
+        omega = h.solid_angle.get_solid_angles(np.empty((H, we, 0)))
+        frames, outs = [], []
+        for i in range(n):
+            img_dir = os.path.join(src, 'kitti', 'data_object', 'training', 'image_2')
+            bg8 = imgops.imread_bgr(os.path.join(img_dir, '%06d.png' % i))
+            depth = imgops.imread_unchanged(os.path.join(img_dir, 'depth', '%06d.png' % i)).astype(np.float32) / 256.
+            frames.append(dict(bg_u8=np.ascontiguousarray(bg8), depth=np.ascontiguousarray(depth), fog=consts, omega=omega, drops=want[i]))
+            outs.append(dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W)), status=np.zeros(max(len(want[i]), 1), np.int32)))
+        rh.pipeline_submit(0, frames, outs)
+        while not rh.pipeline_wait(0):
+            rh.pipeline_submit(0, frames, outs)
+    finally:
+        rh.close()
+    for i in range(n):
+        name = '%06d.png' % i
+        got = np.array(Image.open(os.path.join(out1, 'rainy_image', name)))
+        assert got.shape == (H, W, 4) and np.array_equal(got[..., :3], outs[i]['image_u8']), name
+        ref_mask = os.path.join(tmp, 'ref_mask.png')
+        imgops.imsave_scalar(ref_mask, outs[i]['mask'])
+        assert np.array_equal(np.array(Image.open(os.path.join(out1, 'rain_mask', name))), np.array(Image.open(ref_mask))), name
+        assert outs[i]['mask'].max() > 0
+
+    # two ranks on GPU 0: each replays the entries the other renders
+    with socket.socket() as s_:
+        s_.bind(('127.0.0.1', 0))
+        port = s_.getsockname()[1]
+    env2 = dict(env, RAIN_DEVICE='0', RAIN_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
+    r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
+                        '--master-port', str(port), wrapper] + common + ['--output', os.path.join(tmp, 'out2')],
+                       env=env2, cwd=h.ROOT, capture_output=True, timeout=900)
+    assert r.returncode == 0, (r.stdout.decode()[-3000:], r.stderr.decode()[-3000:])
+    for kind in ('rainy_image', 'rain_mask'):
+        a, b = os.path.join(out1, kind), os.path.join(tmp, 'out2', sub, kind)
+        assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ['%06d.png' % i for i in range(n)]
+        for f in os.listdir(a):
+            assert open(os.path.join(a, f), 'rb').read() == open(os.path.join(b, f), 'rb').read(), (kind, f)
