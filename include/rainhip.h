@@ -364,6 +364,38 @@ int rr_sizeof_sim_frame(void);
 int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int32_t n_run, const uint32_t* run_frame,
                           const uint32_t* run_seed);
 
+/* ---------------------------------------------------------------------------------------
+ * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
+ * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`
+ * (NULL = the ctx stream)
+ *     particles (rr_generate_drops_device semantics: tables and counts stay on the device)
+ *  -> ingest (k_planar_in: planar RGB -> the interleaved BGR image, RR_IN_BG_U8 / RR_IN_BG_F32; values moved, not converted)
+ *  -> pre-pass (fog layer + xyY map handed over as float32, the resident solid angles: rr_pipeline_frames' defaults)
+ *  -> hot path -> planar finalize (k_finalize_planar: rainy_out in the images' layout and dtype, mask_out = float(mask_f64))
+ * and then waits on `stream` for the 4-byte arena-overflow flag: when the tile arena had to grow, the batch is enqueued once more.
+ * So the call returns after the batch is complete -- a host wait on the caller's stream.  For the same records and input values
+ * the result is bit for bit what rr_pipeline_frames gives: rainy_out bytes == rainy_rgb (planar), float32 rainy_out == those
+ * bytes / 255.0f (what ToTensor makes of the PNG the driver writes).  Not offered: angular noise (run_pos must be 0), the 'white'
+ * strategy, opacity attenuation.  Needs the streak database, camera, pre-pass kernels, particle tables, the envmap geometry of
+ * H x W and the solid angles of the H x rr_envmap_width() map (rr_set_solid_angles).  The caller's current device is restored.
+ * Scratch in the context, grown to the largest batch seen and never shrunk, per frame about
+ *     3 H W (bytes; 12 H W for float32) + 12 H W (fog layer) + 12 H We (map) + 8 H W (mask) + 112 drops_cap  bytes
+ * (KITTI 1242 x 375 with bytes: about 23 MB per frame) on top of the hot path's own per-batch scratch. */
+enum { RR_TENSOR_U8 = 0, RR_TENSOR_F32 = 1 };
+typedef struct {
+  int32_t n, H, W, dtype;                /* dtype: RR_TENSOR_*; images and rainy_out share it */
+  const void* images;                    /* DEVICE, [n,3,H,W] planar RGB, contiguous: bytes, or float32 in [0,1] */
+  const float* depth;                    /* DEVICE, [n,H,W] metres */
+  const struct rr_sim_frame* sims;       /* HOST, n records (frame, draw_seed, table, ...) */
+  const double* fog;                     /* HOST, n x the four pre-pass constants (beta_ext, beta_hg, irr_num, irr_den) */
+  int32_t drops_cap;                     /* drop-table capacity per frame */
+  int32_t reserved;
+  void* rainy_out;                       /* DEVICE, [n,3,H,W] planar RGB, same dtype as images */
+  float* mask_out;                       /* DEVICE, [n,H,W]: float32(rainy_mask) */
+} rr_tensor_batch;
+int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream);
+int rr_sizeof_tensor_batch(void);
+
 /* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
  * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does
  * nothing).  Unknown options or values are RR_E_ARG.  The library reads no environment variables. */

@@ -1,0 +1,225 @@
+"""Rain on PyTorch image batches that already live on the GPU: the augmentation form of the renderer.
+
+    aug = RainAugment(dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence='data_object/training')
+    rainy, mask = aug(images, depth, intensity=25, frame_index=idx)
+
+`images` is [B, 3, H, W] planar RGB on the GPU, uint8 (torchvision.io.decode_png) or float32 in [0, 1] (ToTensor); `depth` is
+[B, H, W] or [B, 1, H, W] float32 metres.  `rainy` comes back like `images` (same dtype and layout), `mask` as float32
+[B, 1, H, W] (rainy_mask).  Image i is rendered as frame frame_index[i] of a `main.py --device_particles` run on that dataset and
+sequence at its intensity: simulated frame f % n_sim, drawn with seed f (generator.py:304-321).  The uint8 result is the RGB of
+the PNG that run writes; the float32 result is that byte / 255, what ToTensor makes of the file.
+
+One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
+finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
+constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
+angular noise (it depends on the order of a run, which random access does not have), the 'white' strategy and opacity
+attenuation.
+
+This module imports torch; the package's __init__ does not."""
+import numbers
+import os
+
+import numpy as np
+import torch
+
+from . import hip_backend
+from .common import add_attenuation, envmap, imgops, solid_angle
+from .common import db as dbmod
+from .common.bad_weather import DBManager
+from .tools import particles
+
+
+def sim_options(dataset, sequence=None):
+    """The particle simulation options of `sequence` (common.db.sim, what main.py --device_particles hands the generator); with
+    no sequence the dataset's own settings, without any sequence-specific entry."""
+    if sequence is not None:
+        return dbmod.sim(dataset, sequence, '')['options']
+    opts = dict(dbmod.settings(dataset))
+    opts.pop('sequences', None)
+    return opts
+
+
+def _as_list(v, B, name, kind):
+    """A number (one value for every image) or B values, as a list of Python numbers."""
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, numbers.Number) or (isinstance(v, np.ndarray) and v.ndim == 0):
+        vals = [v.item() if isinstance(v, np.ndarray) else v] * B
+    else:
+        try:
+            vals = list(np.asarray(v).reshape(-1).tolist())
+        except Exception:
+            raise TypeError("%s must be a number or a sequence of %d numbers" % (name, B))
+        if len(vals) != B:
+            raise ValueError("%s: %d values for a batch of %d images" % (name, len(vals), B))
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, numbers.Number):
+            raise TypeError("%s must hold numbers, got %r" % (name, x))
+        if kind == 'index' and x != int(x):
+            raise TypeError("%s must hold integers, got %r" % (name, x))
+    return vals
+
+
+class RainAugment:
+    """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
+
+    def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0):
+        self.dataset, self.sequence, self.seed = dataset, sequence, int(seed)
+        st = dbmod.settings(dataset)
+        self.settings = st
+        self.options = sim_options(dataset, sequence)
+        self.render_scale = int(st['render_scale'])
+        self.focal = st['cam_focal'] / 1000.
+        self.f_number, self.exposure, self.camera_gain = st['cam_f_number'], st['cam_exposure'], st['cam_gain']
+        self.n_sim = particles.n_sim_frames(self.options)
+        light_db = os.path.join(streaks_db, 'env_light_database')
+        self.db = DBManager(streaks_path=os.path.join(light_db, 'size32'),
+                            norm_coeff_path=os.path.join(light_db, 'txt', 'normalized_env_max.txt'))
+        self.db.load_streak_database()
+        if device is not None:
+            device = torch.device(device) if not isinstance(device, int) else torch.device('cuda', device)
+            if device.type != 'cuda':
+                raise ValueError("RainAugment renders on a GPU: device must be a CUDA (HIP) device, got %s" % device)
+            if device.index is None:
+                device = torch.device('cuda', torch.cuda.current_device())
+        self.device = device                     # None: the current device at the first call
+        self._hip = None
+        self._rates = {}                         # intensity -> (sims, cdf tables, fog constants)
+        self._unions = {}                        # sorted intensities -> (d_grid, cdf of all their tables, table offset per intensity)
+        self._tables_key = None                  # the union the context holds
+        self._geom = None                        # (H, W) whose envmap geometry and solid angles the context holds
+
+    # ---- host side: what a call sends (no GPU needed) ----------------------------------------------------------------
+    def frame_size(self):
+        """(H, W) of the frames this dataset's simulation renders (sensor size / render_scale)."""
+        sims = self._rate(self._first_rate())[0]
+        return int(sims[0]['sensor_h']) // self.render_scale, int(sims[0]['sensor_w']) // self.render_scale
+
+    def _first_rate(self):
+        return next(iter(self._rates)) if self._rates else 25.0
+
+    def _rate(self, rate):
+        """The driver's run set-up at one intensity (common/generator.py: sim_frames at seed `seed`, FogRain.constants)."""
+        rate = float(rate)
+        if rate not in self._rates:
+            sims, dgrid, cdf = particles.sim_frames(self.options, rate, self.n_sim, render_scale=self.render_scale, seed=self.seed)
+            fog = add_attenuation.FogRain(rain_intensity=rate, focal=self.focal, f_number=self.f_number, angle=90,
+                                          exposure=self.exposure, camera_gain=self.camera_gain).constants()
+            self._rates[rate] = (sims, dgrid, np.atleast_2d(cdf), tuple(float(v) for v in fog))
+        return self._rates[rate]
+
+    def _union(self, rates):
+        key = tuple(sorted(set(float(r) for r in rates)))
+        if key not in self._unions:
+            tabs, offs, dgrid = [], {}, None
+            for r in key:
+                _, dg, cdf, _ = self._rate(r)
+                assert dgrid is None or np.array_equal(dgrid, dg), "diameter grids of one context must agree"
+                dgrid = dg
+                offs[r] = sum(len(t) for t in tabs)
+                tabs.append(cdf)
+            self._unions[key] = (dgrid, np.ascontiguousarray(np.concatenate(tabs)), offs)
+        return key, self._unions[key]
+
+    def plan(self, intensity, frame_index, B=None):
+        """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
+        union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key)."""
+        if B is None:
+            B = len(np.atleast_1d(np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index)))
+        rates = [float(r) for r in _as_list(intensity, B, 'intensity', 'rate')]
+        idx = [int(f) for f in _as_list(frame_index, B, 'frame_index', 'index')]
+        if any(not (r > 0) or not np.isfinite(r) for r in rates):
+            raise ValueError("intensity must be positive (mm/hr), got %r" % (rates,))
+        if any(f < 0 or f >= 2 ** 32 for f in idx):
+            raise ValueError("frame_index must hold integers in [0, 2^32), got %r" % (idx,))
+        key, (dgrid, cdf, offs) = self._union(rates)
+        sims = np.zeros(B, hip_backend.SIM_FRAME_DTYPE)
+        fog = np.zeros((B, 4), np.float64)
+        n_max = 0
+        for i, (r, f) in enumerate(zip(rates, idx)):
+            rs, _, _, fc = self._rate(r)
+            sims[i] = rs[f % self.n_sim]                     # simulated frame f % n_sim with the draws of frame f (generator.py:318-321)
+            sims[i]['draw_seed'] = f
+            sims[i]['table'] = int(rs[f % self.n_sim]['table']) + offs[r]
+            sims[i]['run_pos'] = 0
+            fog[i] = fc
+        for r in key:
+            n_max = max(n_max, int(self._rate(r)[0]['n_particles'].max()))
+        # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
+        drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
+        return dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key)
+
+    # ---- the call ----------------------------------------------------------------------------------------------------
+    def _validate(self, images, depth):
+        if not isinstance(images, torch.Tensor) or not isinstance(depth, torch.Tensor):
+            raise TypeError("images and depth must be torch tensors")
+        if images.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("images must be uint8 or float32, got %s" % images.dtype)
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1 or images.shape[2] < 1 or images.shape[3] < 1:
+            raise ValueError("images must be [B, 3, H, W] (planar RGB), got %s" % (tuple(images.shape),))
+        B, _, H, W = images.shape
+        if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, H, W), (B, 1, H, W)):
+            raise ValueError("depth must be float32 [B, H, W] or [B, 1, H, W] = %s, got %s %s" % ((B, H, W), depth.dtype, tuple(depth.shape)))
+        return B, H, W
+
+    def _check_device(self, images, depth):
+        for name, t in (('images', images), ('depth', depth)):
+            if t.device.type != 'cuda':
+                raise ValueError("%s must be on the GPU (a CUDA / HIP tensor), got a %s tensor" % (name, t.device.type))
+        dev = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        for name, t in (('images', images), ('depth', depth)):
+            if t.device != dev:
+                raise ValueError("%s is on %s, the augmenter's context on %s" % (name, t.device, dev))
+        return dev
+
+    def _context(self, dev, H, W, key, dgrid, cdf):
+        if self._hip is None:
+            hip = hip_backend.RainHip(dev.index)
+            hip.set_streak_db(self.db.streaks_light)
+            hip.set_camera(hip_backend.make_camera(self.focal, self.f_number, self.exposure))
+            hip.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            self._hip, self.device = hip, dev
+        if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
+            self._hip.set_particle_tables(dgrid, cdf)
+            self._tables_key = key
+        if self._geom != (H, W):                 # envmap geometry + resident solid angles, per frame size
+            we = self._hip.set_envmap_geometry(H, W, *envmap.EnvironmentMapGenerator(self.focal, W, H).device_tables(H, W))
+            self._hip.set_solid_angles(solid_angle.get_solid_angles(np.empty((H, we, 0))))
+            self._geom = (H, W)
+        return self._hip
+
+    def __call__(self, images, depth, intensity, frame_index):
+        B, H, W = self._validate(images, depth)
+        p = self.plan(intensity, frame_index, B)
+        fh, fw = int(p['sims'][0]['sensor_h']) // self.render_scale, int(p['sims'][0]['sensor_w']) // self.render_scale
+        if (H, W) != (fh, fw):
+            raise ValueError("%s%s renders %d x %d frames (H x W), the images are %d x %d" %
+                             (self.dataset, '' if self.sequence is None else '/' + self.sequence, fh, fw, H, W))
+        dev = self._check_device(images, depth)
+        images = images.contiguous()
+        depth = depth.reshape(B, H, W).contiguous()
+        with torch.cuda.device(dev):
+            hip = self._context(dev, H, W, p['key'], p['d_grid'], p['cdf'])
+            rainy = torch.empty((B, 3, H, W), dtype=images.dtype, device=dev)
+            mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+            sims = np.ascontiguousarray(p['sims'])
+            fog = np.ascontiguousarray(p['fog'])
+            b = hip_backend.rr_tensor_batch()
+            b.n, b.H, b.W = B, H, W
+            b.dtype = hip_backend.RR_TENSOR_F32 if images.dtype == torch.float32 else hip_backend.RR_TENSOR_U8
+            b.images, b.depth = images.data_ptr(), depth.data_ptr()
+            b.sims, b.fog = sims.ctypes.data, fog.ctypes.data
+            b.drops_cap = p['drops_cap']
+            b.rainy_out, b.mask_out = rainy.data_ptr(), mask.data_ptr()
+            stream = torch.cuda.current_stream(dev)
+            if not stream.cuda_stream:
+                # the legacy default stream is handle 0, which the library reads as "the context's own stream": what torch has
+                # queued on it (the inputs) is finished first, and the call's own wait covers the outputs
+                stream.synchronize()
+            hip.augment_frames_device(b, stream.cuda_stream)
+        return rainy, mask
+
+    def close(self):
+        if self._hip is not None:
+            self._hip.close()
+            self._hip = None

@@ -81,10 +81,13 @@ struct FrameDesc {
   const rr_ext_tile* ext;          // optional: caller-made tiles / FOV polygons per drop (device pointers inside)
   double* colour_out;              // optional: n_drops * 3 colour constants (rr_frame_out.drop_colour)
   const int32_t* n_drops_dev;      // optional: the drop count lives on the device (k_patch_counts)
+  void* planar;                    // rr_augment_frames_device: [3][H][W] RGB out (bytes, or floats with planar_f32) instead of rgb
+  float* mask_f32;                 // ... and float(mask_f64), H*W (k_finalize_planar)
   int32_t comp_f32, in_types;      // comp_out holds floats (the float-colour compositor wrote it); element types of the inputs
   int32_t depth_f64;
   int32_t n_drops;
   int32_t strategy;
+  int32_t planar_f32;
   double opacity;
 };
 
@@ -4136,7 +4139,43 @@ __global__ __launch_bounds__(256) void k_means(Dims dm, int ntiles, Scratch sc) 
   }
 }
 
-// generator.py:461-466 + matplotlib's float->uint8 truncation
+// generator.py:461-466 + matplotlib's float->uint8 truncation: the R G B bytes of one pixel from its BGR composite and the
+// frame's mean shift.  Every finalize kernel (k_finalize16, k_finalize, k_finalize_planar) goes through this one function.
+__device__ inline void finalize_rgb(const double c[3], double diff, uint32_t rgb[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) rgb[k] = (uint32_t)(uint8_t)(int)(clip01(c[2 - k] - diff) * 255.0);      // BGR -> RGB
+}
+// a pixel's 16-bit composite codes (k_composite32) as float64 BGR; code 65535 = the pixel's own rainy_bg value
+__device__ inline void comp_from_codes(const FrameDesc& fr, int64_t pix, const uint32_t q[3], bool valid, double c[3]) {
+  bool special = false;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    c[k] = (double)q[k] * (1.0 / 65534.0);
+    special = special || q[k] == 65535u;
+  }
+  if (special && valid) {
+    double in[3];
+    load_px3(fr.rainy_bg, rainy_kind(fr), pix, in);
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+      if (q[k] == 65535u) c[k] = (double)(float)in[k];
+  }
+}
+// pixel `pix` of the composite as float64 BGR, in whichever form the compositor left it (comp_f32 2: codes, 1: float, 0: float64)
+__device__ inline void comp_load(const FrameDesc& fr, int64_t pix, double c[3]) {
+  if (fr.comp_f32 == 2) {
+    const u32x2_t w = as_global(reinterpret_cast<const u32x2_t*>(fr.comp_out))[pix];
+    const uint32_t q[3] = {w.x & 0xffffu, w.x >> 16, w.y & 0xffffu};
+    comp_from_codes(fr, pix, q, true, c);
+  } else if (fr.comp_f32) {
+    const global_ptr<const float> s = as_global(reinterpret_cast<const float*>(fr.comp_out)) + pix * 3;
+    c[0] = (double)s[0]; c[1] = (double)s[1]; c[2] = (double)s[2];
+  } else {
+    const global_ptr<const double> s = as_global((const double*)fr.comp_out) + pix * 3;
+    c[0] = s[0]; c[1] = s[1]; c[2] = s[2];
+  }
+}
+
 // The same for the 16-bit composite codes of k_composite32, FOUR pixels per thread: 24 bytes in by
 // three 8-byte loads, 12 bytes out by one 12-byte store (a thread per pixel moved its 6 + 3 bytes with three 2-byte loads
 // and three byte stores and was slower than the float form it replaces, which reads twice the bytes).  The last pixels of a
@@ -4164,25 +4203,13 @@ __global__ __launch_bounds__(256) void k_finalize16(const FrameDesc* frames, Dim
 #pragma unroll
   for (int px = 0; px < 4; px++) {
     double c[3];
-    bool special = false;
+    uint32_t rgb[3];
+    comp_from_codes(fr, pix0 + px, q + px * 3, px < cnt, c);
+    finalize_rgb(c, diff, rgb);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      c[k] = (double)q[px * 3 + k] * (1.0 / 65534.0);
-      special = special || q[px * 3 + k] == 65535u;
-    }
-    if (special && px < cnt) {
-      double in[3];
-      load_px3(fr.rainy_bg, rainy_kind(fr), pix0 + px, in);
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-        if (q[px * 3 + k] == 65535u) c[k] = (double)(float)in[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const double v = clip01(c[2 - k] - diff);      // BGR -> RGB
-      const uint32_t byte = (uint32_t)(uint8_t)(int)(v * 255.0);
       const int bi = px * 3 + k;
-      out[bi >> 2] |= byte << (8 * (bi & 3));
+      out[bi >> 2] |= rgb[k] << (8 * (bi & 3));
     }
   }
   if (cnt == 4 && (reinterpret_cast<uintptr_t>(fr.rgb) & 3u) == 0) {
@@ -4201,29 +4228,13 @@ __global__ __launch_bounds__(256) void k_finalize(const FrameDesc* frames, Dims 
   const double diff = sc.means[f * 4 + 0] - sc.means[f * 4 + 1];
   const global_ptr<uint8_t> o = as_global(fr.rgb) + pix * 3;
   double c[3];
-  if (fr.comp_f32 == 2) {                          // 16-bit codes (k_composite32): 65535 = the pixel's own rainy_bg value
-    const u32x2_t w = as_global(reinterpret_cast<const u32x2_t*>(fr.comp_out))[pix];
-    const uint32_t q0 = w.x & 0xffffu, q1 = w.x >> 16, q2 = w.y & 0xffffu;
-    c[0] = (double)q0 * (1.0 / 65534.0); c[1] = (double)q1 * (1.0 / 65534.0); c[2] = (double)q2 * (1.0 / 65534.0);
-    if (q0 == 65535u || q1 == 65535u || q2 == 65535u) {
-      double in[3];
-      load_px3(fr.rainy_bg, rainy_kind(fr), pix, in);
-      if (q0 == 65535u) c[0] = (double)(float)in[0];
-      if (q1 == 65535u) c[1] = (double)(float)in[1];
-      if (q2 == 65535u) c[2] = (double)(float)in[2];
-    }
-  } else if (fr.comp_f32) {
-    const global_ptr<const float> s = as_global(reinterpret_cast<const float*>(fr.comp_out)) + pix * 3;
-    c[0] = (double)s[0]; c[1] = (double)s[1]; c[2] = (double)s[2];
-  } else {
-    const global_ptr<const double> s = as_global((const double*)fr.comp_out) + pix * 3;
-    c[0] = s[0]; c[1] = s[1]; c[2] = s[2];
-  }
-  for (int k = 0; k < 3; k++) {
-    double v = clip01(c[2 - k] - diff);      // BGR -> RGB
-    o[k] = (uint8_t)(int)(v * 255.0);
-  }
+  uint32_t rgb[3];
+  comp_load(fr, pix, c);
+  finalize_rgb(c, diff, rgb);
+  for (int k = 0; k < 3; k++) o[k] = (uint8_t)rgb[k];
 }
+
+#include "rr_tensor.h"
 
 // ---------------------------------------------------------------------------
 // the two PNG files of a frame, ready for deflate  
@@ -4982,6 +4993,10 @@ struct rr_ctx {
   std::vector<ProfEntry> prof_pending;
   std::vector<rr_kernel_stat> prof_stats;
   std::vector<hipEvent_t> ev_pool;
+  // rr_augment_frames_device: one block of scratch (interleaved image, fog layer, xyY map, float64 mask, drop tables, counts),
+  // grown to the largest batch seen, never shrunk
+  char* d_aug = nullptr;
+  size_t aug_bytes = 0;
 };
 
 namespace {
@@ -5210,7 +5225,17 @@ int grow_arena(rr_ctx* ctx) {
   return RR_OK;
 }
 
-int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, hipStream_t s, int ovf_idx = 0) {
+// rr_augment_frames_device: frame f's image goes to rgb + f * rgb_stride as [3][H][W] planes (bytes, or float32 with f32) and its
+// mask to mask + f * H * W as float32, both written by k_finalize_planar instead of rr_frame_out.rainy_rgb
+struct PlanarOut {
+  char* rgb;
+  float* mask;
+  int64_t rgb_stride;
+  int f32;
+};
+
+int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, hipStream_t s, int ovf_idx = 0,
+            const PlanarOut* planar = nullptr) {
   if (!ctx->have_cam || !ctx->have_db) {
     ctx->err = "streak DB and camera must be set before rendering";
     return RR_E_STATE;
@@ -5244,7 +5269,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
       return RR_E_STATE;
     }
     if (in[f].n_drops < 0 || in[f].n_drops > 65536 || !in[f].bg || !in[f].rainy_bg || !in[f].env_xyY ||
-        (in[f].n_drops > 0 && !in[f].drops) || !out[f].rainy_rgb) {
+        (in[f].n_drops > 0 && !in[f].drops) || (!out[f].rainy_rgb && !(planar && out[f].mask_f64))) {
       ctx->err = "null frame pointer or n_drops outside [0, 2^16] (generator.py:425)";
       return RR_E_ARG;
     }
@@ -5294,6 +5319,9 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     fd.ext = in[f].ext;
     fd.colour_out = out[f].drop_colour;
     fd.n_drops_dev = in[f].n_drops_dev;
+    fd.planar = planar ? planar->rgb + (size_t)f * planar->rgb_stride : nullptr;
+    fd.mask_f32 = planar ? planar->mask + (size_t)f * dm.H * dm.W : nullptr;
+    fd.planar_f32 = planar ? planar->f32 : 0;
     fd.comp_f32 = use32 ? (ctx->wild_pixels ? 1 : 2) : 0;
     fd.in_types = in[f].in_types;
     any_dev_count = any_dev_count || in[f].n_drops_dev;
@@ -5592,9 +5620,12 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     ProfScope ps(ctx, s, "k_means");
     hipLaunchKernelGGL(k_means, dim3(n), dim3(256), 0, s, dm, ntiles_c, sc);
   }
-  {
+  if (planar) {
+    ProfScope ps(ctx, s, "k_finalize_planar");
+    hipLaunchKernelGGL(k_finalize_planar, dim3((unsigned)(((int64_t)dm.H * dm.W + 1023) / 1024), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
+  } else {
     ProfScope ps(ctx, s, "k_finalize");
-    if (use32 && !ctx->wild_pixels)                        // (every frame's comp_f32 is 2: the coded composite, four pixels per thread)
+    if (use32 && !ctx->wild_pixels)                      // (every frame's comp_f32 is 2: the coded composite, four pixels per thread)
       hipLaunchKernelGGL(k_finalize16, dim3((unsigned)(((int64_t)dm.H * dm.W + 1023) / 1024), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
     else
       hipLaunchKernelGGL(k_finalize, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
@@ -6022,9 +6053,9 @@ int rr_create(rr_ctx** out, int device) {
   build_cubic_tab(tab);
   if (hipMalloc((void**)&ctx->d_ctab, sizeof(tab)) != hipSuccess ||
       hipMemcpy(ctx->d_ctab, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess ||
-      // arena-overflow flags (one per pipeline slot + one for the device-pointer calls) and the sticky largest need
-      hipMalloc((void**)&ctx->sc.overflow, sizeof(int32_t) * (1 + RR_PIPE_SLOTS)) != hipSuccess ||
-      hipMemset(ctx->sc.overflow, 0, sizeof(int32_t) * (1 + RR_PIPE_SLOTS)) != hipSuccess ||
+      // arena-overflow flags (one per pipeline slot + one for the device-pointer calls + AUG_FLAG) and the sticky largest need
+      hipMalloc((void**)&ctx->sc.overflow, sizeof(int32_t) * (2 + RR_PIPE_SLOTS)) != hipSuccess ||
+      hipMemset(ctx->sc.overflow, 0, sizeof(int32_t) * (2 + RR_PIPE_SLOTS)) != hipSuccess ||
       hipMalloc((void**)&ctx->sc.need_max, sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->sc.need_max, 0, sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     rr_destroy(ctx);
@@ -6100,6 +6131,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->sc.need_max);
   hipFree(ctx->d_omega);
   hipFree(ctx->d_omega32);
+  hipFree(ctx->d_aug);
   hipFree(ctx->d_dgrid);
   hipFree(ctx->d_cdf);
   hipFree(ctx->d_ratio_db);
@@ -7139,9 +7171,153 @@ int run_host(rr_ctx* ctx, int32_t n, const rr_prepass_in* pre, const rr_frame_in
   }
 }
 
+constexpr int AUG_FLAG = 1 + RR_PIPE_SLOTS;      // rr_augment_frames_device's own arena-overflow flag
+
+// particles -> ingest -> pre-pass -> hot path -> planar finalize, on `s`, then the overflow check (see include/rainhip.h)
+int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
+  const int n = b->n, H = b->H, W = b->W, cap = b->drops_cap;
+  if (n <= 0 || H <= 0 || W <= 0 || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32) || !b->images || !b->depth || !b->sims ||
+      !b->fog || !b->rainy_out || !b->mask_out || cap <= 0 || cap > 65536) {
+    ctx->err = "rr_augment_frames_device: bad argument (sizes, dtype, a null pointer, or drops_cap outside [1, 2^16])";
+    return RR_E_ARG;
+  }
+  for (int f = 0; f < n; f++)
+    if (b->sims[f].run_pos != 0) {
+      ctx->err = "rr_augment_frames_device: angular noise is not offered (rr_sim_frame.run_pos must be 0)";
+      return RR_E_ARG;
+    }
+  if (!ctx->have_eg || ctx->eg.H != H || ctx->eg.W != W) {
+    ctx->err = "rr_augment_frames_device: rr_set_envmap_geometry must be called for this frame size";
+    return RR_E_STATE;
+  }
+  const int We = ctx->eg.We;
+  if (!ctx->d_omega || !ctx->d_omega32 || ctx->omega_He != H || ctx->omega_We != We) {
+    ctx->err = "rr_augment_frames_device: rr_set_solid_angles must be called for the H x rr_envmap_width() map";
+    return RR_E_STATE;
+  }
+  const size_t px = (size_t)H * W, el = b->dtype == RR_TENSOR_F32 ? 4 : 1;
+  auto rnd = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t s_bg = rnd(px * 3 * el), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
+  const size_t b_drops = rnd((size_t)n * cap * sizeof(rr_drop)), b_counts = rnd((size_t)n * 4);
+  const size_t need = (size_t)n * (s_bg + s_rainy + s_env + s_mask) + b_drops + b_counts;
+  if (need > ctx->aug_bytes) {
+    HIPCHK(hipDeviceSynchronize());
+    if (ctx->d_aug) HIPCHK(hipFree(ctx->d_aug));
+    ctx->d_aug = nullptr;
+    ctx->aug_bytes = 0;
+    HIPCHK(hipMalloc((void**)&ctx->d_aug, need));
+    ctx->aug_bytes = need;
+  }
+  char* const bg = ctx->d_aug;
+  char* const rainy = bg + (size_t)n * s_bg;
+  char* const env = rainy + (size_t)n * s_rainy;
+  char* const mask = env + (size_t)n * s_env;
+  rr_drop* const drops = reinterpret_cast<rr_drop*>(mask + (size_t)n * s_mask);
+  int32_t* const counts = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(drops) + b_drops);
+  const int bg_type = b->dtype == RR_TENSOR_F32 ? RR_IN_BG_F32 : RR_IN_BG_U8;
+  // the descriptors rr_pipeline_frames builds for the same frames by default: float32 hand-over, resident solid angles
+  std::vector<rr_prepass_in> pin(n);
+  std::vector<rr_prepass_out> pout(n);
+  std::vector<rr_frame_in> din(n);
+  std::vector<rr_frame_out> dout(n);
+  for (int f = 0; f < n; f++) {
+    rr_prepass_in& p = pin[f];
+    memset(&p, 0, sizeof p);
+    p.H = H;
+    p.W = W;
+    p.bg = bg + (size_t)f * s_bg;
+    p.depth = b->depth + (size_t)f * px;
+    p.depth_f64 = 0;
+    p.mode = 0;
+    p.beta_ext = b->fog[4 * f + 0];
+    p.beta_hg = b->fog[4 * f + 1];
+    p.irr_num = b->fog[4 * f + 2];
+    p.irr_den = b->fog[4 * f + 3];
+    p.in_types = bg_type;
+    rr_prepass_out& po = pout[f];
+    memset(&po, 0, sizeof po);
+    po.rainy_bg = rainy + (size_t)f * s_rainy;
+    po.env_xyY = env + (size_t)f * s_env;
+    po.out_types = RR_OUT_RAINY_F32 | RR_OUT_ENV_F32;
+    rr_frame_in& fi = din[f];
+    memset(&fi, 0, sizeof fi);
+    fi.H = H;
+    fi.W = W;
+    fi.He = H;
+    fi.We = We;
+    fi.bg = p.bg;
+    fi.rainy_bg = po.rainy_bg;
+    fi.env_xyY = po.env_xyY;
+    fi.omega = nullptr;
+    fi.drops = drops + (size_t)f * cap;
+    fi.n_drops = cap;
+    fi.opacity_attenuation = 1.0;
+    fi.depth = p.depth;
+    fi.depth_f64 = 0;
+    fi.in_types = bg_type | RR_IN_RAINY_F32 | RR_IN_ENV_F32;
+    fi.n_drops_dev = counts + f;
+    rr_frame_out& fo = dout[f];
+    memset(&fo, 0, sizeof fo);
+    fo.mask_f64 = reinterpret_cast<double*>(mask + (size_t)f * s_mask);
+  }
+  const PlanarOut pl{static_cast<char*>(b->rainy_out), b->mask_out, (int64_t)(px * 3 * el), b->dtype == RR_TENSOR_F32 ? 1 : 0};
+  const int64_t total = (int64_t)n * 3 * (int64_t)px;
+  for (int attempt = 0;; attempt++) {
+    int rc;
+    if ((rc = enqueue_particles(ctx, n, b->sims, H, W, drops, cap, counts, s))) return rc;
+    {
+      ProfScope ps(ctx, s, "k_planar_in");
+      if (el == 1) {
+        const int64_t lanes = ((int64_t)px + 15) / 16;
+        hipLaunchKernelGGL(k_planar_in<0>, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, b->images, (void*)bg, (int64_t)px,
+                           (int64_t)s_bg, total);
+      } else {
+        const int64_t lanes = ((int64_t)px + 3) / 4;
+        hipLaunchKernelGGL(k_planar_in<1>, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, b->images, (void*)bg, (int64_t)px,
+                           (int64_t)(s_bg / 4), total);
+      }
+    }
+    if ((rc = enqueue_prepass(ctx, n, pin.data(), pout.data(), s))) return rc;
+    hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, ctx->sc.overflow + AUG_FLAG, 0);
+    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, AUG_FLAG, &pl))) return rc;
+    int32_t ovf = 0;
+    HIPCHK(hipMemcpyAsync(&ovf, ctx->sc.overflow + AUG_FLAG, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!ovf) return RR_OK;
+    if ((rc = grow_arena(ctx))) return rc;
+    if (attempt == 2) {
+      ctx->err = "rr_augment_frames_device: tile arena overflow after two regrowths";
+      return RR_E_ARENA;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int rr_sizeof_tensor_batch(void) { return (int)sizeof(rr_tensor_batch); }
+
+int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream) {
+  if (!ctx) return RR_E_ARG;
+  if (!b) {
+    ctx->err = "rr_augment_frames_device: null batch";
+    return RR_E_ARG;
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  struct Restore {                     // the caller's current device, whatever way the call ends
+    int d;
+    ~Restore() {
+      if (d >= 0) (void)hipSetDevice(d);
+    }
+  } restore{prev};
+  HIPCHK(hipSetDevice(ctx->device));
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const int rc = augment(ctx, b, s);
+  if (rc) (void)hipStreamSynchronize(s);        // (nothing of a failed call may keep writing the caller's tensors)
+  return rc;
+}
 
 int rr_render_frames(rr_ctx* ctx, int32_t n, const rr_frame_in* in, const rr_frame_out* out) {
   if (!ctx) return RR_E_ARG;

@@ -122,6 +122,16 @@ class rr_prepass_out(ctypes.Structure):
                 ('out_types', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+RR_TENSOR_U8, RR_TENSOR_F32 = 0, 1                       # rr_tensor_batch.dtype
+
+
+class rr_tensor_batch(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                ('images', ctypes.c_void_p), ('depth', ctypes.c_void_p), ('sims', ctypes.c_void_p), ('fog', ctypes.c_void_p),
+                ('drops_cap', ctypes.c_int32), ('reserved', ctypes.c_int32), ('rainy_out', ctypes.c_void_p),
+                ('mask_out', ctypes.c_void_p)]
+
+
 EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_streak_db', 'rr_set_streak_db_device',
            'rr_set_camera', 'rr_render_frames', 'rr_render_frames_device', 'rr_synchronize', 'rr_profile_enable',
            'rr_profile_reset', 'rr_profile_read', 'rr_sizeof_drop', 'rr_sizeof_camera', 'rr_sizeof_frame_in',
@@ -132,7 +142,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_particle', 'rr_sizeof_particle_frame', 'rr_set_colormap', 'rr_host_frame_draws', 'rr_host_assemble_drops',
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
-           'rr_sizeof_sim_frame', 'rr_set_particle_noise']
+           'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch']
 
 _lib = None
 
@@ -228,7 +238,9 @@ def load_library(path=None):
                                           ctypes.c_void_p]
     lib.rr_generate_drops.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
+    assert lib.rr_sizeof_tensor_batch() == ctypes.sizeof(rr_tensor_batch), (lib.rr_sizeof_tensor_batch(), ctypes.sizeof(rr_tensor_batch))
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
     assert lib.rr_sizeof_prepass_out() == ctypes.sizeof(rr_prepass_out)
     assert lib.rr_sizeof_prepass_kernels() == ctypes.sizeof(rr_prepass_kernels)
@@ -1084,6 +1096,12 @@ class RainHip:
         rc = self.lib.rr_render_frames_device(self.h, n, fin, fout, ctypes.c_void_p(stream) if stream else None)
         self._check(rc, 'rr_render_frames_device')
 
+    def augment_frames_device(self, batch, stream=None):
+        """rr_augment_frames_device: `batch` an rr_tensor_batch (device pointers for the tensors, host pointers for the records
+        and the fog constants).  Returns once the batch is complete on `stream` (augment.RainAugment is the user-facing form)."""
+        self._check(self.lib.rr_augment_frames_device(self.h, ctypes.byref(batch), ctypes.c_void_p(stream) if stream else None),
+                    'rr_augment_frames_device')
+
     def synchronize(self):
         """Returns True if the batch completed, False if the tile arena had to be regrown
         (re-enqueue the batch)."""
@@ -1106,8 +1124,8 @@ class RainHip:
         self.lib.rr_profile_reset(self.h)
 
     def profile_read(self):
-        buf = (rr_kernel_stat * 32)()
-        n = self._check(self.lib.rr_profile_read(self.h, buf, 32), 'rr_profile_read')
+        buf = (rr_kernel_stat * 64)()
+        n = self._check(self.lib.rr_profile_read(self.h, buf, 64), 'rr_profile_read')
         return {buf[i].name.decode(): (buf[i].launches, buf[i].total_ms) for i in range(n)}
 
 
