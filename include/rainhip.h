@@ -364,6 +364,28 @@ int rr_sizeof_sim_frame(void);
 int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int32_t n_run, const uint32_t* run_frame,
                           const uint32_t* run_seed);
 
+/* The particle model of the records the context generates from now on (every entry point that takes rr_sim_frame records).
+ *   RR_PARTICLES_IID (default): every simulated frame draws a fresh, independent set of particles, as described above.
+ *   RR_PARTICLES_FIELD: a persistent particle field for video (rain-rendering_amd/tools/particles.py states it bit for bit,
+ *     make_field_particles).  A record then reads: n_particles = the run's number of particle SLOTS (about three per
+ *     expected particle), frame = the TIME index k of the frame (t = k / cam_hz seconds; it need not wrap with the
+ *     simulated frames), every other field as before: the settings in force at that time.  Slot j keeps its diameter and
+ *     phase; it lives in the axis-aligned box that bounds the (margin-enlarged) frustum up to z_max(D): half sides
+ *     ((1/2 + margin) sensor / fpx) z_max, depth 0 .. z_max, and falls through it once every T = box height / v(D).  Life
+ *     g = floor(t / T + phase) is a word of the Philox counter of the life's lateral start, start depth and wind; the
+ *     position is the start moved by (wind, -v(D), speed_mps) x the life's age, modulo the box sideways and in depth;
+ *     slots outside the frustum are culled.  At any one time the kept particles have the i.i.d. model's law; a particle
+ *     kept in frames k and k + 1 in the same life has moved by its velocity / cam_hz.  No state: frame k alone, in any
+ *     batch or on any device has the same bits.  A frame's records are in ascending slot order; the per-drop draws
+ *     (draw_seed) keep their meaning.  Where two frames' settings differ the field may jump.
+ * cam_hz: frames per second (> 0, finite) with RR_PARTICLES_FIELD; ignored (pass 0) with RR_PARTICLES_IID.
+ * RR_E_ARG: unknown model, bad cam_hz, or RR_PARTICLES_FIELD while angular noise is on (rr_set_particle_noise with non-zero
+ * noise_std and noise_scale; likewise turning the noise on under the field model, or a record with run_pos != 0): the
+ * reference's noise turns a shared simulated frame in place and has no meaning for moving particles.
+ * Call it between runs, with no call of the generator in flight. */
+enum { RR_PARTICLES_IID = 0, RR_PARTICLES_FIELD = 1 };
+int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz);
+
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`
@@ -481,6 +503,9 @@ enum {
   RR_OPT_ROWS_SHARES = 23,          /* tuning (r06): k_tile_rows' workgroups take the batch's tile list in shares of equal estimated cost off a
                                      * device-wide counter; this many shares per workgroup (1 .. 8, default 2): more shares even out the
                                      * workgroups, fewer leave less waiting at a share's end */
+  RR_OPT_FIELD_CHUNKS = 24,         /* tuning: workgroups that share one frame's slots in the field model's particle kernel
+                                     * (rr_set_particle_model): 0 (default: the library sizes it so that a small batch still fills
+                                     * the chip, one per frame for large batches) or 1 .. 64.  Same bits. */
   RR_OPT_COMPOSITE_BATCH = 20       /* retired: only 1 is accepted */
 };
 int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value);

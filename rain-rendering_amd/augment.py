@@ -9,6 +9,12 @@
 sequence at its intensity: simulated frame f % n_sim, drawn with seed f (generator.py:304-321).  The uint8 result is the RGB of
 the PNG that run writes; the float32 result is that byte / 255, what ToTensor makes of the file.
 
+`particle_model='field'` (default 'iid') renders the frames of a `main.py --device_particles --particle_model field` run instead:
+a persistent particle field (tools/particles.py) in which frame f + 1 shows the drops of frame f a little lower and closer.
+`frame_index[i]` is then the TIME index of image i (time f / cam_hz, settings of simulated frame f % n_sim), so a video clip of T
+frames is `frame_index = k0 + arange(T)`; a [B, T, 3, H, W] batch is flattened to [B * T, 3, H, W] with one index per frame
+(INTEGRATION.md section C).  Frames remain random-access: any index, in any batch, gives the same bits.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -63,7 +69,10 @@ def _as_list(v, B, name, kind):
 class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
-    def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0):
+    def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid'):
+        if particle_model not in particles.MODELS:
+            raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
+        self.particle_model = particle_model
         self.dataset, self.sequence, self.seed = dataset, sequence, int(seed)
         st = dbmod.settings(dataset)
         self.settings = st
@@ -102,7 +111,8 @@ class RainAugment:
         """The driver's run set-up at one intensity (common/generator.py: sim_frames at seed `seed`, FogRain.constants)."""
         rate = float(rate)
         if rate not in self._rates:
-            sims, dgrid, cdf = particles.sim_frames(self.options, rate, self.n_sim, render_scale=self.render_scale, seed=self.seed)
+            sims, dgrid, cdf = particles.sim_frames(self.options, rate, self.n_sim, render_scale=self.render_scale, seed=self.seed,
+                                                    model=self.particle_model)
             fog = add_attenuation.FogRain(rain_intensity=rate, focal=self.focal, f_number=self.f_number, angle=90,
                                           exposure=self.exposure, camera_gain=self.camera_gain).constants()
             self._rates[rate] = (sims, dgrid, np.atleast_2d(cdf), tuple(float(v) for v in fog))
@@ -140,6 +150,8 @@ class RainAugment:
             rs, _, _, fc = self._rate(r)
             sims[i] = rs[f % self.n_sim]                     # simulated frame f % n_sim with the draws of frame f (generator.py:318-321)
             sims[i]['draw_seed'] = f
+            if self.particle_model == 'field':               # the field's time is the frame index itself: a clip is k0 + arange(T)
+                sims[i]['frame'] = f
             sims[i]['table'] = int(rs[f % self.n_sim]['table']) + offs[r]
             sims[i]['run_pos'] = 0
             fog[i] = fc
@@ -147,7 +159,8 @@ class RainAugment:
             n_max = max(n_max, int(self._rate(r)[0]['n_particles'].max()))
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
-        return dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key)
+        return dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
+                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]))
 
     # ---- the call ----------------------------------------------------------------------------------------------------
     def _validate(self, images, depth):
@@ -178,6 +191,7 @@ class RainAugment:
             hip.set_streak_db(self.db.streaks_light)
             hip.set_camera(hip_backend.make_camera(self.focal, self.f_number, self.exposure))
             hip.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            hip.set_particle_model(self.particle_model, self.options["cam_hz"])
             self._hip, self.device = hip, dev
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)

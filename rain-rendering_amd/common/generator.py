@@ -76,6 +76,12 @@ class Generator:
         self.db = None
         self.renderer = None
         self.device_particles = bool(getattr(args, 'device_particles', False))     # drop tables generated on the GPU (no XML)
+        self.particle_model = getattr(args, 'particle_model', 'iid') or 'iid'       # 'field': persistent particles (tools/particles.py)
+        if self.particle_model != 'iid' and not self.device_particles:
+            raise ValueError("--particle_model %s needs --device_particles" % self.particle_model)
+        if self.particle_model == 'field' and bool(self.noise_std):
+            raise ValueError("--noise_std has no meaning with --particle_model field: the reference's angular noise turns a shared "
+                             "simulated frame in place, the field model's particles move from frame to frame")
         self.sim_options = getattr(args, 'sim_options', {})
         self.batch = int(os.environ.get('RAIN_BATCH', '128'))     # frames per library call (three calls in flight); bench.py's host-inclusive leg uses the same
         self.rank, self.world = sharding.rank_world()
@@ -409,8 +415,9 @@ class Generator:
                     from ..tools import particles
                     opts = self.sim_options[sequence]
                     n_sim = particles.n_sim_frames(opts)
-                    sims, dgrid, cdf = particles.sim_frames(opts, fallrate, n_sim, render_scale=rs, seed=0)
+                    sims, dgrid, cdf = particles.sim_frames(opts, fallrate, n_sim, render_scale=rs, seed=0, model=self.particle_model)
                     hip.set_particle_tables(dgrid, cdf)
+                    hip.set_particle_model(self.particle_model, opts["cam_hz"])
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)
@@ -704,6 +711,8 @@ class Generator:
                         f_idx = items[k]['f_name_idx']
                         sl.sim_recs[k][0] = sims[f_idx % n_sim]
                         sl.sim_recs[k]['draw_seed'] = f_idx
+                        if self.particle_model == 'field':       # the field's time is the frame's own index (it does not wrap)
+                            sl.sim_recs[k]['frame'] = f_idx
                         sl.sim_recs[k]['run_pos'] = items[k]['run_pos']    # angular noise: its entry in the run (0: none)
                     else:
                         sl.prep.set_drop_count(k, nd)

@@ -29,7 +29,7 @@
 //                      (or float64) colours, tile sums
 //     k_means, k_finalize16 (k_finalize: a float or float64 composite), [k_png_image, k_png_mask, k_pngz_blocks, k_pngz_pack]
 //                      mean-contrast shift, clip, truncating u8 quantisation; optional PNG scanlines / zlib streams
-//   elsewhere: k_particles / k_particle_draws (drop tables born on the device), k_png_unfilter (input files' scanlines),
+//   elsewhere: k_particles / k_field_particles / k_particle_draws (drop tables born on the device), k_png_unfilter (input files' scanlines),
 //   k_pad_textures, k_pair_textures, k_copy_pieces / k_copy_small (batched copies, descriptors)
 // rr_prepass.h holds the fog / environment-map pre-pass kernels, rr_host.cpp the host-only helpers.
 #include <hip/hip_runtime.h>
@@ -4564,6 +4564,83 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
   if (t == 0) n_out[f] = base_out;
 }
 
+// k_field_particles: the FIELD model (rr_set_particle_model, rr_particles.h make_field_particle).  A frame walks its SLOTS;
+// about one slot in three is inside the frustum and goes on to derive_drop.  The records of a frame stay in ascending slot
+// order, as k_particles keeps particle order, with the same ballot + prefix popcount + LDS staging.  A frame evaluates
+// three times as many candidates as the i.i.d. model, so a frame's slots may be shared out over gridDim.x workgroups
+// (chunk c = slots [c, c + 1) * chunk_slots): COUNT = true only counts a chunk's records into chunk_cnt[f][c]; the store
+// pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
+// twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
+// batches fill the chip by themselves) there is no count pass.
+template <bool COUNT>
+__global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
+                                                          const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
+                                                          int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
+  const int f = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  __shared__ rr_sim_frame s_sf;
+  __shared__ int s_cnt[8];
+  __shared__ int s_base;
+  if (t < (int)(sizeof(rr_sim_frame) / 4)) reinterpret_cast<uint32_t*>(&s_sf)[t] = reinterpret_cast<const uint32_t*>(sims + f)[t];
+  if (t == 0) {
+    int b = 0;
+    if (!COUNT)
+      for (int k = 0; k < c; k++) b += chunk_cnt[f * nchunk + k];
+    s_base = b;
+  }
+  __syncthreads();
+  const rr_sim_frame sf = s_sf;
+  const double* cdf = cdf_tabs + (int64_t)sf.table * n_grid;
+  double rdb[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) rdb[k] = ratio_db[k];
+  const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
+  int base_out = s_base;
+  for (int base = first; base < last; base += 512) {
+    const int j = base + t;
+    bool keep = false;
+    rr_drop d;
+    if (j < last) {
+      rrsim::Particle p;
+      double life;
+      if (rrsim::make_field_particle(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life)) {
+        double ratio;
+        keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
+        d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+      }
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base_out, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+      const int n = s_cnt[w];
+      if (w < wave) off += n;
+      tot += n;
+    }
+    if constexpr (!COUNT) {
+      __shared__ uint32_t s_stage[8][64 * DROP_DW];          // per wave: 64 records (57 KB)
+      const int nw = __popcll(bal);                          // records of this wave: consecutive output slots from `off`
+      if (keep) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
+        uint32_t* dst = s_stage[wave] + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
+#pragma unroll
+        for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
+      }
+      wave_lds_sync();
+      const int room = imax(imin(nw, cap - off), 0);        // what does not fit is not stored (the count still says so)
+      uint32_t* o = reinterpret_cast<uint32_t*>(out + (int64_t)f * cap + off);
+      for (int k = lane; k < room * DROP_DW; k += 64) o[k] = s_stage[wave][k];
+    }
+    base_out += tot;
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (COUNT) chunk_cnt[f * nchunk + c] = base_out;
+    else if (c == nchunk - 1) n_out[f] = base_out;
+  }
+}
+
 // k_particle_draws: the renderer's per-drop random draws of one frame (np.random.seed(draw_seed); per drop one
 // randint(lo, lo + 10), per non-Big drop one normal(0, 0): bad_weather.py:252-264, generator.py:136) from numpy's legacy
 // MT19937 stream, bit for bit what rr_host_frame_draws makes on the host.  The stream is sequential by nature (how many
@@ -4886,6 +4963,12 @@ struct rr_ctx {
   rr_drop* d_gen_drops = nullptr;    // staging of rr_generate_drops (host-pointer variant)
   // angular noise on device-generated tables (rr_set_particle_noise, k_noise_chains)
   double noise_std = 0.0, noise_scale = 0.0;
+  // the field model (rr_set_particle_model, k_field_particles)
+  int particle_model = RR_PARTICLES_IID;
+  double cam_hz = 0.0;
+  int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
+  int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
+  size_t cap_field_cnt = 0;
   std::vector<uint32_t> run_frame, run_seed;
   std::vector<int32_t> run_chain;                                       // entry p: its index among its simulated frame's entries
   std::unordered_map<uint32_t, std::vector<uint32_t>> chain_seeds;      // simulated frame id -> seeds of its entries, in run order
@@ -5959,10 +6042,16 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     }
   }
   const bool noise_on = ctx->noise_std != 0.0 && ctx->noise_scale != 0.0;
+  const bool field = ctx->particle_model == RR_PARTICLES_FIELD;
   int n_noisy = 0;
   for (int f = 0; f < n; f++) {
     const rr_sim_frame& sf = sims[f];
     if (sf.run_pos == 0) continue;
+    if (field) {
+      ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
+                 "): angular noise is not defined for the field model (rr_set_particle_model)";
+      return RR_E_ARG;
+    }
     if (sf.run_pos < 0 || sf.run_pos > (int)ctx->run_frame.size()) {
       ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) + ") is outside the run of " +
                  std::to_string(ctx->run_frame.size()) + " entries given to rr_set_particle_noise";
@@ -5989,7 +6078,39 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
   hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_sims),
                      (int)(sizeof(rr_sim_frame) * (size_t)n / 4));
   if ((rc = ring_commit(ctx, ctx->ring_sims, ring_idx, s))) return rc;
-  if (n_noisy < n) {                                         // frames with angular noise are left to k_noise_chains
+  if (field) {
+    // workgroups per frame: one (no count pass) when the frames alone give every compute unit a workgroup -- measured: at 256
+    // frames two chunks cost 1.4 x one, the second pass buys nothing on a full chip --, otherwise enough chunks of whole
+    // 512-slot rounds to give every compute unit two
+    int max_slots = 0;
+    for (int f = 0; f < n; f++) max_slots = imax(max_slots, sims[f].n_particles);
+    if (max_slots > (1 << 30)) {                             // (the chunk bounds are formed in int)
+      ctx->err = "rr_sim_frame.n_particles: more than 2^30 slots under the field model";
+      return RR_E_ARG;
+    }
+    const int rounds = imax((max_slots + 511) / 512, 1);
+    int chunks = ctx->field_chunks > 0 ? ctx->field_chunks : (n >= ctx->n_cu ? 1 : (2 * ctx->n_cu + n - 1) / n);
+    chunks = imax(1, imin(imin(chunks, 64), rounds));
+    const int chunk_slots = ((rounds + chunks - 1) / chunks) * 512;
+    chunks = (rounds * 512 + chunk_slots - 1) / chunk_slots;
+    if (chunks > 1 && (size_t)n * (size_t)chunks > ctx->cap_field_cnt) {
+      HIPCHK(hipDeviceSynchronize());
+      if ((rc = dev_alloc(ctx, ctx->d_field_cnt, (size_t)n * (size_t)chunks))) return rc;
+      ctx->cap_field_cnt = (size_t)n * (size_t)chunks;
+    }
+    {
+      ProfScope ps(ctx, s, "k_field_particles");
+      if (chunks > 1)
+        hipLaunchKernelGGL(k_field_particles<true>, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf,
+                           ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      hipLaunchKernelGGL(k_field_particles<false>, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf,
+                         ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+    }
+    {
+      ProfScope ps(ctx, s, "k_particle_draws");
+      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, 0);
+    }
+  } else if (n_noisy < n) {                                  // frames with angular noise are left to k_noise_chains
     {
       ProfScope ps(ctx, s, "k_particles");
       hipLaunchKernelGGL(k_particles, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db,
@@ -6138,6 +6259,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_sims);
   hipFree(ctx->d_gen_drops);
   hipFree(ctx->d_gen_counts);
+  hipFree(ctx->d_field_cnt);
   for (void* b : ctx->noise_blocks) hipFree(b);
   hipFree(ctx->d_noise_desc);
   if (ctx->ev_noise) hipEventDestroy(ctx->ev_noise);
@@ -6582,6 +6704,11 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
     ctx->err = "rr_set_particle_noise: bad argument (n_run >= 0 entries, both tables, finite noise_std / noise_scale)";
     return RR_E_ARG;
   }
+  if (ctx->particle_model == RR_PARTICLES_FIELD && noise_std != 0.0 && noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_noise: angular noise is not defined for the field model (rr_set_particle_model): the reference's noise "
+               "turns a shared simulated frame in place";
+    return RR_E_ARG;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   if ((rc = noise_states_drop(ctx))) return rc;
@@ -6596,6 +6723,27 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
     ctx->run_chain[p] = (int32_t)v.size();
     v.push_back(run_seed[p]);
   }
+  return RR_OK;
+}
+
+int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz) {
+  if (!ctx) return RR_E_ARG;
+  if (model != RR_PARTICLES_IID && model != RR_PARTICLES_FIELD) {
+    ctx->err = "rr_set_particle_model: unknown model " + std::to_string(model) + " (RR_PARTICLES_IID or RR_PARTICLES_FIELD)";
+    return RR_E_ARG;
+  }
+  if (model == RR_PARTICLES_FIELD) {
+    if (!std::isfinite(cam_hz) || !(cam_hz > 0)) {
+      ctx->err = "rr_set_particle_model: the field model needs cam_hz > 0 (frames per second)";
+      return RR_E_ARG;
+    }
+    if (ctx->noise_std != 0.0 && ctx->noise_scale != 0.0) {
+      ctx->err = "rr_set_particle_model: the field model has no angular noise; turn it off first (rr_set_particle_noise with noise_std 0)";
+      return RR_E_ARG;
+    }
+  }
+  ctx->particle_model = model;
+  ctx->cam_hz = model == RR_PARTICLES_FIELD ? cam_hz : 0.0;
   return RR_OK;
 }
 
@@ -7533,6 +7681,10 @@ int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value) {
     case RR_OPT_COPY_KERNELS: ctx->copy_kernels = value != 0; return RR_OK;
     case RR_OPT_TILE_ROWS: ctx->tile_rows = value < 0 ? 0 : (value > 2 ? 2 : value); return RR_OK;
     case RR_OPT_ROWS_SHARES: ctx->rows_shares = value < 1 ? 1 : (value > 8 ? 8 : value); return RR_OK;
+    case RR_OPT_FIELD_CHUNKS:
+      if (value < 0 || value > 64) break;
+      ctx->field_chunks = value;
+      return RR_OK;
     case RR_OPT_FOV_FILL_RULE: ctx->fill_rule = value == 1 ? 1 : 0; return RR_OK;
     case RR_OPT_FOV_DDA: ctx->fov_dda = value != 0 ? 1 : 0; return RR_OK;       // (2 was k_fov_walk, r05: measured, no faster, removed in r06)
     case RR_OPT_PIPELINE_F32: ctx->pipe_f32 = value != 0; return RR_OK;

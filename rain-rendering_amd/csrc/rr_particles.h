@@ -4,7 +4,7 @@
 // `__host__ __device__` like rr_device.h: k_particles (rainhip.hip) runs these functions on gfx950, tests/hostemu
 // compiles them with g++, and rain-rendering_amd/tools/particles.py states the same arithmetic in numpy (its bit-exact
 // host statement; the model itself is documented there).  IEEE double, the evaluation order spelled out, no FMA
-// contraction, + - * / sqrt rint only (sqrt is correctly rounded on gfx950 and in numpy); the one transcendental -- exp
+// contraction, + - * / sqrt rint floor only (sqrt is correctly rounded on gfx950 and in numpy); the one transcendental -- exp
 // in the terminal velocity -- is rr::det_exp.
 //
 //   reference side: tools/simulation.py drives a closed-source simulator with the settings of common/db.py:41-70;
@@ -90,6 +90,69 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
   p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
   p.iw1 = (wd * sf.fpx) / depth;
   p.iw2 = (wd * sf.fpx) / depth2;
+}
+
+// ---- the FIELD model (rr_set_particle_model, tools/particles.py make_field_particles): a persistent particle field ----
+// sf.n_particles is the run's number of particle SLOTS and sf.frame the TIME index k (t = k / cam_hz).  Slot j has a
+// diameter D and a phase for good (block (j, 0, 0, 1)); it lives in the axis-aligned box that bounds its frustum (half
+// sides bx = hx z_max, by = hy z_max, depth 0 .. z_max) and falls through it once every T = 2 by / v(D) seconds.  The
+// number of completed falls g = floor(t / T + phase) is a word of the counter of the life's own draws (blocks
+// (j, g mod 2^32, 1 | 2, 2 + g / 2^32): lateral start, start depth, wind), so every life of a slot is a new drop; the
+// fractional part is its age.  Inside a life the position is the start moved by velocity x elapsed time, modulo the box
+// on the two lateral axes: a translation of a uniform law, hence uniform in the box at every t; what lies outside the
+// (margin-enlarged) frustum is culled (two slots in three).  Everything is a function of (key, j, k) and the settings.
+// Returns whether the particle is inside the frustum; `life` = g.
+RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
+                               Particle& p, double& life) {
+  uint32_t a[4] = {j, 0u, 0u, 1u};
+  philox4x32_10(a, sf.key0, sf.key1);
+  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
+  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
+  const double phase = unit32(a[1]);
+  const double wd = D * 1e-3;
+  const double z_max = rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far);
+  const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;   // frustum half-widths at unit depth
+  const double bx = hx * z_max, by = hy * z_max;
+  const double wx = 2.0 * bx, wy = 2.0 * by;
+  const double v = terminal_velocity(D);
+  const double T = wy / v;
+  const double t = (double)sf.frame / cam_hz;
+  const double s = t / T + phase;
+  const double g = floor(s);
+  const double age = s - g;
+  const double tau = age * T;                               // seconds since the life began
+  const double g_hi = floor(g * (1.0 / 4294967296.0)), g_lo = g - g_hi * 4294967296.0;
+  uint32_t b[4] = {j, (uint32_t)g_lo, 1u, 2u + (uint32_t)g_hi}, c[4] = {j, (uint32_t)g_lo, 2u, 2u + (uint32_t)g_hi};
+  philox4x32_10(b, sf.key0, sf.key1);
+  philox4x32_10(c, sf.key0, sf.key1);
+  const double s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0;
+  const double wind = (s4 * 1.7320508075688772) * sf.wind_sigma;
+  const double qx = unit32(b[0]) + (wind * tau) / wx;       // box coordinates in units of the box: wrapped into [0, 1)
+  const double qz = unit32(b[1]) - (sf.speed_mps * tau) / z_max;
+  const double fx = qx - floor(qx), fz = qz - floor(qz);
+  const double X = fx * wx - bx;
+  const double Y = by - age * wy;
+  const double zr = fz * z_max;                             // depth in the box
+  const double ax = hx * zr, ay = hy * zr;
+  const bool inside = -ax <= X && X <= ax && -ay <= Y && Y <= ay;
+  const double depth = rr::dmax(zr, 0.05);
+  const double Z = -depth;
+  const double e = sf.exposure_s;
+  const double X2 = X + wind * e;
+  const double Y2 = Y - v * e;
+  const double Z2 = Z + sf.speed_mps * e;
+  const double depth2 = rr::dmax(-Z2, 0.05);
+  life = g;
+  p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
+  p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
+  p.wd = wd;
+  p.ip1[0] = W / 2.0 + (sf.fpx * X) / depth;
+  p.ip1[1] = H / 2.0 + (sf.fpx * Y) / depth;
+  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
+  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
+  p.iw1 = (wd * sf.fpx) / depth;
+  p.iw2 = (wd * sf.fpx) / depth2;
+  return inside;
 }
 
 // ceil(sqrt(n)) of a non-negative integer, exactly (np.ceil(np.sqrt(.)) of the loader gives the same: a non-integer root

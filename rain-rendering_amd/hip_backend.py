@@ -36,6 +36,9 @@ RR_OPT_COMPOSITE_BATCH = 20
 RR_OPT_COLOUR_STREAM = 21
 RR_OPT_TILE_ROWS = 22
 RR_OPT_ROWS_SHARES = 23
+RR_OPT_FIELD_CHUNKS = 24
+RR_PARTICLES_IID, RR_PARTICLES_FIELD = 0, 1              # rr_set_particle_model
+PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD}
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
 RR_IN_BG_PNG_ROWS, RR_DEPTH_PNG_ROWS = 32, 3              # a file's filtered scanlines (rr_io_read_frames_rows): un-filtered on the device
 RR_DEPTH_U16 = 2                                        # rr_prepass_in.depth_f64: the uint16 samples of the depth file (metres = sample / 256)
@@ -142,7 +145,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_particle', 'rr_sizeof_particle_frame', 'rr_set_colormap', 'rr_host_frame_draws', 'rr_host_assemble_drops',
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
-           'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch']
+           'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model']
 
 _lib = None
 
@@ -238,6 +241,7 @@ def load_library(path=None):
                                           ctypes.c_void_p]
     lib.rr_generate_drops.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    lib.rr_set_particle_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
     assert lib.rr_sizeof_tensor_batch() == ctypes.sizeof(rr_tensor_batch), (lib.rr_sizeof_tensor_batch(), ctypes.sizeof(rr_tensor_batch))
@@ -830,6 +834,15 @@ class RainHip:
         assert rf.shape == rs.shape and rf.ndim == 1
         self._check(self.lib.rr_set_particle_noise(self.h, float(noise_std), float(noise_scale), len(rf), _ptr(rf), _ptr(rs)),
                     'rr_set_particle_noise')
+
+    def set_particle_model(self, model='iid', cam_hz=0.0):
+        """rr_set_particle_model: 'iid' (default: independent particles per simulated frame) or 'field' (the persistent field
+        of tools/particles.py: records then carry the slot count in n_particles and the time index in frame; cam_hz = frames
+        per second).  Not together with angular noise."""
+        if model not in PARTICLE_MODELS:
+            raise ValueError("particle model %r: expected one of %s" % (model, ', '.join(PARTICLE_MODELS)))
+        self._check(self.lib.rr_set_particle_model(self.h, PARTICLE_MODELS[model], float(cam_hz) if model == 'field' else 0.0),
+                    'rr_set_particle_model')
 
     def generate_drops_device(self, sims, H, W, drops_ptr, cap, n_out_ptr, stream=None):
         """rr_generate_drops_device: sims = SIM_FRAME_DTYPE records (host); drops_ptr / n_out_ptr = DEVICE addresses of

@@ -56,6 +56,10 @@ _FLAGS = [
     (('--force_particles',), dict(action='store_true', help='(reference only) re-run the particle simulator')),
     (('--device_particles',), dict(action='store_true', help='simulate the rain particles on the GPU, frame by frame (no particle '
                                                              'file is read or written; this build only)')),
+    (('--particle_model',), dict(type=str, default='iid', choices=['iid', 'field'],
+                                 help="with --device_particles: 'iid' draws independent particles for every simulated frame; 'field' is "
+                                      "a persistent particle field for video: frame k + 1 shows the drops of frame k a little lower and "
+                                      "closer (not with --noise_std)")),
 ]
 
 
@@ -70,6 +74,12 @@ def _derive(ns):
     """The fields the reference computes after parsing (main.py:131-161)."""
     if ns.force_particles and ns.conflict_strategy == "skip":
         raise AssertionError("If particles simulator is forced, cannot skip")
+    if getattr(ns, 'particle_model', 'iid') != 'iid':
+        if not ns.device_particles:
+            raise SystemExit("--particle_model %s needs --device_particles (the particle files hold the i.i.d. model)" % ns.particle_model)
+        if ns.noise_std:
+            raise SystemExit("--noise_std cannot be combined with --particle_model field: the reference's angular noise turns a shared "
+                             "simulated frame in place and has no meaning for particles that move from frame to frame")
     ns.verbose = not ns.noverbose
     light_db = _J(ns.streaks_db, 'env_light_database')
     ns.texture = _J(light_db, 'size32')

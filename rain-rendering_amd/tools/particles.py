@@ -16,7 +16,7 @@ The model is stated twice, with identical bits:
     renderer's per-drop random draws and leaves ``rr_drop[]`` records in HBM (``rr_generate_drops_device``, or
     ``rr_frame_in.sim`` in the host-pointer entry points).  ``sim_frames`` / ``diameter_tables`` below describe a run to
     the library; ``expected_records`` is what it must produce (tests/test_gpu_particles.py: bit for bit).
-Arithmetic shared by both: IEEE double with the evaluation order spelled out, + - * / sqrt rint only (exp through
+Arithmetic shared by both: IEEE double with the evaluation order spelled out, + - * / sqrt rint floor only (exp through
 ``det_exp``: the same operations on every machine), random numbers from the counter-based Philox4x32-10 -- particle i of
 frame k is a pure function of (seed, k, i), so any lane of any GPU can make it.
 
@@ -32,6 +32,32 @@ conventions the loader undoes, bad_weather.py:221-224):
     vehicle's speed (``sim_steps['cam_motion']``, km/h); the streak is the path covered during the exposure, both ends
     projected through the pinhole camera;
   * image widths are D f / (pixel z) at either end.
+
+Two particle models share all of the above.  The default, i.i.d. model (``model='iid'``) draws a fresh, independent set of
+particles for every simulated frame.  The FIELD model (``model='field'``, ``make_field_particles``; ``rr_set_particle_model``
+in the library) is a persistent, stateless particle field for video:
+  * a run has a fixed number of particle SLOTS, drawn once per distinct settings of the run (``field_slot_counts``: Poisson
+    around three times the expected count, because a slot lives in the axis-aligned box that bounds its frustum and a
+    pyramid fills a third of its bounding box).  Slot j has a diameter D_j (same table, same ``sample_diameter``, hence the
+    same z_max(D) cut) and a phase for good: Philox block (j, 0, 0, 1);
+  * the box of a slot has half sides bx = hx z_max, by = hy z_max (hx, hy: the margin-enlarged frustum's half-widths at unit
+    depth) and depth 0 .. z_max.  The slot falls through it once every T = 2 by / v(D) seconds.  At time t = k / cam_hz the
+    number of completed falls is g = floor(t / T + phase) (the slot's LIFE) and the fractional part its age.  A life's own
+    draws (lateral start, start depth, wind) come from blocks (j, g mod 2^32, 1 | 2, 2 + g / 2^32): every life of a slot
+    is a new drop, nothing recurs;
+  * inside a life the position is the start moved by velocity x elapsed time: v(D) down, the life's wind sideways, the
+    vehicle's speed towards the camera; the two lateral axes wrap modulo the box.  A translation modulo the box keeps a
+    uniform law uniform, so at every single t the particles inside the frustum (the others are culled, two slots in
+    three) are uniform by volume up to z_max(D) with the i.i.d. model's expected count: the two models are equal in law
+    frame by frame, and differ in that frame k + 1 of the field shows frame k's drops a little lower and closer;
+  * the streak of a frame is the path covered during the exposure from the position at t_k, both ends projected;
+  * the TIME is the rendered frame's index f itself (it does not wrap); the SETTINGS of frame f are those of simulated frame
+    f % n_sim.  Motion is continuous across frames whose settings agree; where the settings of two consecutive frames
+    differ (``sim_mode == "steps"``: speed, focal length, exposure or fall rate per step) the boxes, periods and tables
+    differ and the field may jump;
+  * particle (slot j, frame k) is a pure function of (seed, j, k) and the settings: any frame can be made alone, in any
+    batch, on any rank, with the same bits.  The kept records of a frame are in ascending slot order.  Angular noise
+    (``--noise_std``) is not defined for the field model.
 """
 import os
 
@@ -299,6 +325,14 @@ def _frame_settings(options, fallrate, k, min_px, z_far, margin):
     return cam, rate
 
 
+MODELS = ('iid', 'field')
+
+
+def _check_model(model):
+    if model not in MODELS:
+        raise ValueError("particle model %r: expected one of %s" % (model, ', '.join(MODELS)))
+
+
 def _key(seed):
     seed = int(seed)
     return seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
@@ -359,11 +393,131 @@ def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05,
     return rec
 
 
-def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None):
+def _settings_key(cam, rate):
+    return (rate, cam.fpx, cam.W, cam.H)
+
+
+def field_slot_counts(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, count=None):
+    """Particle slots of the field model per simulated frame: ONE Poisson draw per distinct settings (fall rate, camera)
+    of the run around three times the expected count -- frames with the same settings share their slots -- or
+    3 * `count` (`count`: the expected number of particles in the frustum, as for the i.i.d. model)."""
+    out = np.zeros(n_frames, np.int64)
+    drawn = {}
+    for k in range(n_frames):
+        if count is not None:
+            out[k] = 3 * int(count)
+            continue
+        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
+        tk = _settings_key(cam, rate)
+        if tk not in drawn:
+            mean = expected_count(cam, rate, min_px, z_far, margin)[0]
+            drawn[tk] = int(np.random.RandomState((int(seed) * 1000003 + 999983 + len(drawn)) % (2 ** 32)).poisson(3.0 * mean))
+        out[k] = drawn[tk]
+    return out
+
+
+def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
+                         cull=True):
+    """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
+    of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
+    life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
+    rec = np.zeros(n_slots, PARTICLE_DTYPE)
+    if n_slots == 0:
+        return rec, np.zeros(0, np.float64)
+    j = np.arange(n_slots, dtype=np.uint64)
+    k0, k1 = _key(seed)
+    a = philox4x32(j, 0, 0, 1, k0, k1)
+    W, H = float(cam.W), float(cam.H)
+    D = sample_diameter(dgrid, cdf, unit32(a[0]))
+    phase = unit32(a[1])
+    wd = D * 1e-3
+    z_max = np.minimum((wd * cam.fpx) / min_px, z_far)
+    hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
+    bx, by = hx * z_max, hy * z_max
+    wx, wy = 2.0 * bx, 2.0 * by
+    v = terminal_velocity(D)
+    T = wy / v
+    t = float(int(k) & 0xFFFFFFFF) / float(cam_hz)
+    s = t / T + phase
+    g = np.floor(s)
+    age = s - g
+    tau = age * T
+    g_hi = np.floor(g * (1.0 / 4294967296.0))
+    g_lo = g - g_hi * 4294967296.0
+    c1, c3 = g_lo.astype(np.uint64), np.uint64(2) + g_hi.astype(np.uint64)
+    b = philox4x32(j, c1, 1, c3, k0, k1)
+    c = philox4x32(j, c1, 2, c3, k0, k1)
+    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
+    wind = (s4 * 1.7320508075688772) * wind_sigma
+    qx = unit32(b[0]) + (wind * tau) / wx
+    qz = unit32(b[1]) - (cam.speed * tau) / z_max
+    fx, fz = qx - np.floor(qx), qz - np.floor(qz)
+    X = fx * wx - bx
+    Y = by - age * wy
+    zr = fz * z_max
+    ax, ay = hx * zr, hy * zr
+    inside = (-ax <= X) & (X <= ax) & (-ay <= Y) & (Y <= ay)
+    depth = np.maximum(zr, 0.05)
+    Z = -depth
+    e = cam.exposure
+    X2 = X + wind * e
+    Y2 = Y - v * e
+    Z2 = Z + cam.speed * e
+    depth2 = np.maximum(-Z2, 0.05)
+    rec['pid'] = np.arange(n_slots)
+    rec['wp1'] = np.stack([X, Y, Z], axis=1)
+    rec['wp2'] = np.stack([X2, Y2, Z2], axis=1)
+    rec['wd1'] = rec['wd2'] = wd
+    rec['ip1'] = np.stack([W / 2.0 + (cam.fpx * X) / depth, H / 2.0 + (cam.fpx * Y) / depth], axis=1)
+    rec['ip2'] = np.stack([W / 2.0 + (cam.fpx * X2) / depth2, H / 2.0 + (cam.fpx * Y2) / depth2], axis=1)
+    rec['iw1'] = (wd * cam.fpx) / depth
+    rec['iw2'] = (wd * cam.fpx) / depth2
+    if cull:
+        return rec[inside], g[inside]
+    return rec, g
+
+
+def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0):
+    """Velocity (n, 3) in m/s (x right, y up, z towards the camera) of the given slots in the given lives, and the slots'
+    boxes (n, 3): full width, full height, depth -- what tests compare a track's displacement with."""
+    j = np.asarray(slots, np.uint64)
+    g = np.asarray(lives, np.float64)
+    k0, k1 = _key(seed)
+    D = sample_diameter(dgrid, cdf, unit32(philox4x32(j, 0, 0, 1, k0, k1)[0]))
+    z_max = np.minimum(((D * 1e-3) * cam.fpx) / min_px, z_far)
+    hx, hy = ((0.5 + margin) * float(cam.W)) / cam.fpx, ((0.5 + margin) * float(cam.H)) / cam.fpx
+    g_hi = np.floor(g * (1.0 / 4294967296.0))
+    g_lo = g - g_hi * 4294967296.0
+    c = philox4x32(j, g_lo.astype(np.uint64), 2, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)
+    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
+    wind = (s4 * 1.7320508075688772) * wind_sigma
+    vel = np.stack([wind, -terminal_velocity(D), np.full(len(j), float(cam.speed))], axis=1)
+    return vel, np.stack([2.0 * (hx * z_max), 2.0 * (hy * z_max), z_max], axis=1)
+
+
+def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
+                cull=True):
+    """Frame `k` of a field-model run ALONE: (PARTICLE_DTYPE records with pid = slot id, life per record) of the particles
+    inside the frustum -- the identity of a frame's particles.  Time index k, settings of simulated frame k % n_sim
+    (n_sim: n_sim_frames(options) by default).  `generate(..., model='field')` is these frames one after the other."""
+    n_sim = n_sim_frames(options) if n_sim is None else int(n_sim)
+    ks = int(k) % n_sim
+    cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
+    _, dgrid, cdf, _ = expected_count(cam, rate, min_px, z_far, margin)
+    n_slots = int(field_slot_counts(options, fallrate, ks + 1, seed, min_px, z_far, margin, count)[ks])
+    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull)
+
+
+def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid'):
     """(frames, drops) record arrays of `n_frames` camera frames.  `count`: force that many drops per frame instead
-    of the Poisson-distributed physical count."""
+    of the Poisson-distributed physical count.  model='field': the persistent field (module docstring), frame k at time
+    k / cam_hz under the settings of simulated frame k; pid is then the slot id."""
     frames = np.zeros(n_frames, PARTICLE_FRAME_DTYPE)
-    counts = frame_counts(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
+    _check_model(model)
+    if model == 'field':
+        counts = field_slot_counts(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
+    else:
+        counts = frame_counts(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
     chunks = []
     first = 0
     tables = {}
@@ -374,7 +528,11 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
             tables[tk] = expected_count(cam, rate, min_px, z_far, margin)
         _, dgrid, cdf, _ = tables[tk]
         n = int(counts[k])
-        rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far)
+        if model == 'field':
+            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far)
+            n = len(rec)
+        else:
+            rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far)
         frames[k] = (k, int(round(cam.exposure * 1e6)), int(round(k * 1e6 / cam.hz)), n, first, n)
         chunks.append(rec)
         first += n
@@ -398,13 +556,16 @@ def diameter_tables(options, fallrate, n_frames, min_px=1.0, z_far=15.0, margin=
 
 
 def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=None, min_px=1.0, z_far=15.0, margin=0.05,
-               wind_sigma=1.0, count=None, frame_ids=None):
+               wind_sigma=1.0, count=None, frame_ids=None, model='iid'):
     """SIM_FRAME_DTYPE records (hip_backend: the numpy mirror of rr_sim_frame) of `n_frames` camera frames + the tables
     they refer to: (sims, d_grid, cdf).  draw_seeds: np.random.seed(...) of the renderer's per-drop draws per frame
-    (generator.py:318: the frame's index; default: the frame number)."""
+    (generator.py:318: the frame's index; default: the frame number).  model='field' (rr_set_particle_model): n_particles
+    is the run's slot count under the frame's settings and `frame` the TIME index; a rendered frame f of a run takes the
+    record of simulated frame f % n_sim with frame = f (field_run_sims)."""
     from .. import hip_backend
+    _check_model(model)
     dgrid, cdf, tab = diameter_tables(options, fallrate, n_frames, min_px, z_far, margin)
-    counts = frame_counts(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
+    counts = (field_slot_counts if model == 'field' else frame_counts)(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
     sims = np.zeros(n_frames, hip_backend.SIM_FRAME_DTYPE)
     k0, k1 = _key(seed)
     for k in range(n_frames):
@@ -419,15 +580,29 @@ def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=N
     return sims, dgrid, cdf
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset):
+def field_run_sims(sims, f_idx):
+    """The records of rendered frames `f_idx` of a field-model run: the settings of simulated frame f % len(sims), the time
+    index and the draw seed f."""
+    f = np.asarray(f_idx, np.int64)
+    out = np.ascontiguousarray(sims[f % len(sims)])
+    out['frame'] = f.astype(np.uint32)
+    out['draw_seed'] = f.astype(np.uint32)
+    return out
+
+
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame."""
     from ..common import bad_weather as bw
     cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
                                speed=float(s['speed_mps'])))()
     seed = int(s['key0']) | (int(s['key1']) << 32)
-    rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
-                         float(s['margin']), float(s['min_px']), float(s['z_far']))
+    if model == 'field':
+        rec, _ = make_field_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
+                                      float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']))
+    else:
+        rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
+                             float(s['margin']), float(s['min_px']), float(s['z_far']))
     fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
     fr[0] = (0, 0, 0, len(rec), 0, len(rec))
     m = bw.DBManager()
@@ -438,7 +613,7 @@ def _loaded_table(s, dgrid, cdf, db, dataset):
     return m.streaks_simulator[0].table, m, W, H
 
 
-def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None):
+def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -448,12 +623,18 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     run's entries in order.  A frame with run_pos p >= 1 is entry p - 1: its simulated frame's pristine streaks are
     stepped (noise_step) through every earlier entry of the same simulated frame, in run order, then through its own
     entry, whose records it gets -- the reference's in-place rotation of the shared table (generator.py:152-161)
-    replayed from scratch, so the result depends on nothing but the frame."""
+    replayed from scratch, so the result depends on nothing but the frame.
+
+    model='field' with the run's `cam_hz` (rr_set_particle_model): the records of the field model's frames
+    (make_field_particles: slots inside the frustum in ascending order, then the same loader, filter and draws)."""
     from .. import hip_backend
+    _check_model(model)
     noisy = bool(noise_std) and bool(noise_scale)
+    if model == 'field' and (noisy or cam_hz is None):
+        raise ValueError("the field model needs cam_hz and has no angular noise")
     out = []
     for s in sims:
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz)
         p = int(s['run_pos'])
         if not noisy or p == 0:
             out.append(hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact'))
@@ -506,7 +687,7 @@ def n_sim_frames(options):
     return n_steps if options.get("sim_mode") == "steps" and n_steps else int(options["sim_duration"] * options["cam_hz"])
 
 
-def simulate(sim, weather, n_frames=None, seed=0, force_recompute=False):
+def simulate(sim, weather, n_frames=None, seed=0, force_recompute=False, model='iid'):
     """The role of the reference's tools/particles_simulation.process for ONE sequence: `sim` = common.db.sim(...)
     ({"path", "options"}), `weather` = {"weather": "rain", "fallrate": R}.  Writes
     <sim path>/<weather>/<R>mm/sim_camera0.xml unless it exists; returns its path."""
@@ -517,5 +698,5 @@ def simulate(sim, weather, n_frames=None, seed=0, force_recompute=False):
         return path
     if n_frames is None:
         n_frames = n_sim_frames(options)
-    frames, drops = generate(options, weather["fallrate"], n_frames, seed=seed)
+    frames, drops = generate(options, weather["fallrate"], n_frames, seed=seed, model=model)
     return write_xml(path, frames, drops)

@@ -24,6 +24,9 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--intensity', type=float, default=25.0)
+    ap.add_argument('--compare_models', type=int, default=0, metavar='ROUNDS',
+                    help="also time particle_model 'iid' against 'field' at B = 32 (uint8) in this many interleaved rounds of --steps "
+                         "calls; adds the key particle_models (frames/s: median, min, max over the rounds)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -76,6 +79,25 @@ def main():
                     aug.plan(args.intensity, rng.randint(0, 1 << 20, Bh), Bh)
                 out['host_ms_per_call']['%s_B%d' % (dt, Bh)] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
         aug.close()
+        if args.compare_models > 0:
+            B = min(32, Bmax)
+            augs = {m: augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model=m) for m in ('iid', 'field')}
+            rates = {m: [] for m in augs}
+            k0 = 0
+            for r in range(args.warmup + args.compare_models):
+                for m, a in augs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for s_ in range(args.steps):              # clips: consecutive indices, the same ones for both models
+                        a(img8[:B], depth[:B], args.intensity, k0 + s_ * B + np.arange(B))
+                    torch.cuda.synchronize()
+                    if r >= args.warmup:
+                        rates[m].append(B * args.steps / (time.perf_counter() - t0))
+                k0 += args.steps * B
+            out['particle_models'] = dict(B=B, rounds=args.compare_models, fps={
+                m: dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1)) for m, v in rates.items()})
+            for a in augs.values():
+                a.close()
     print(json.dumps(out))
 
 
