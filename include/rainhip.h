@@ -383,8 +383,35 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
  * noise_std and noise_scale; likewise turning the noise on under the field model, or a record with run_pos != 0): the
  * reference's noise turns a shared simulated frame in place and has no meaning for moving particles.
  * Call it between runs, with no call of the generator in flight. */
-enum { RR_PARTICLES_IID = 0, RR_PARTICLES_FIELD = 1 };
+enum { RR_PARTICLES_IID = 0, RR_PARTICLES_FIELD = 1, RR_PARTICLES_RIG = 2 };
 int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz);
+
+/* RR_PARTICLES_RIG: the field model for a camera rig -- ONE persistent field in the rig's frame seen by up to RR_MAX_VIEWS
+ * cameras (stereo, surround; tools/particles.py make_rig_particles states it bit for bit, rain-rendering_amd/rig.py builds
+ * the views).  A view is p_cam = R (p_rig - c): R row-major, rig -> camera, orthonormal with determinant +1; c the camera's
+ * centre in the rig frame, metres.  The rig frame is the single camera's: x right, y up, looking along -z, drops gain
+ * +speed_mps in z.  All views share intrinsics and settings.  box = {r, r_y, o_y} from the host (Rig.box): a slot's box is
+ * [-b, b)^2 in x and z, b = r z_max(D), and [-b_y, b_y) in y, b_y = r_y z_max(D) + o_y; x and z wrap modulo 2 b and a
+ * view looks at the lattice image nearest to its camera, so r must be at least the horizontal reach of every view's
+ * (margin-enlarged) frustum per unit depth.  The records' n_particles and table are the rig's own (rig_slot_counts,
+ * rig_tables: density N(D) per unit volume of the box).
+ * active[n_active]: the views a batch renders, distinct numbers in 0 .. n_views - 1 (NULL: all n_views in order, n_active
+ * ignored).  Under RR_PARTICLES_RIG (rr_set_particle_model(ctx, RR_PARTICLES_RIG, cam_hz), after this call) the batch of
+ * every entry point that takes rr_sim_frame records holds n_active consecutive frames per instant: frame i is view
+ * active[i % n_active] of instant i / n_active, and the records of one instant agree in every field but draw_seed.  Frame
+ * (k, v) is a pure function of (key, k, v): active = {1} gives the tables of view 1 under active = {0, 1}, bit for bit.
+ * RR_E_ARG: n_views outside 1 .. RR_MAX_VIEWS; R off orthonormal (an entry of R R^T - I, or det R - 1, beyond 1e-9 in
+ * magnitude) or not finite; a bad active list; box values that are not finite, r or r_y not positive, o_y negative; and,
+ * when generating: a batch that is not a multiple of n_active, records of one instant that disagree, angular noise,
+ * RR_PARTICLES_RIG selected before a rig is set.  Call it between runs, with no call of the generator in flight. */
+#define RR_MAX_VIEWS 8
+typedef struct {
+  double R[9];                    /* rig -> camera, row-major */
+  double c[3];                    /* camera centre in the rig frame, metres */
+} rr_rig_view;
+int rr_set_particle_rig(rr_ctx* ctx, int32_t n_views, const rr_rig_view* views, const double box[3], int32_t n_active,
+                        const int32_t* active);
+int rr_sizeof_rig_view(void);
 
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,

@@ -15,6 +15,12 @@ a persistent particle field (tools/particles.py) in which frame f + 1 shows the 
 frames is `frame_index = k0 + arange(T)`; a [B, T, 3, H, W] batch is flattened to [B * T, 3, H, W] with one index per frame
 (INTEGRATION.md section C).  Frames remain random-access: any index, in any batch, gives the same bits.
 
+`particle_model='rig'` with `rig=Rig...` (rig.py) renders the cameras of a rig looking at ONE such field (stereo, surround): `images`
+is [B, V, 3, H, W], `depth` [B, V, H, W] or [B, V, 1, H, W], with one `frame_index` (the instant) and one `intensity` per B; `rainy`
+comes back [B, V, 3, H, W], `mask` [B, V, 1, H, W].  View v of instant f is frame f of a `main.py --device_particles
+--particle_model rig --rig ... --rig_view v` run.  `views=[...]` restricts the call to a subset of the rig's views (V = len(views),
+in that order) with the same bits per view.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -32,6 +38,7 @@ from . import hip_backend
 from .common import add_attenuation, envmap, imgops, solid_angle
 from .common import db as dbmod
 from .common.bad_weather import DBManager
+from . import rig as rigmod
 from .tools import particles
 
 
@@ -69,10 +76,20 @@ def _as_list(v, B, name, kind):
 class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
-    def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid'):
+    def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
+                 rig=None, views=None):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
+        if (particle_model == 'rig') != (rig is not None):
+            raise ValueError("particle_model='rig' and rig= go together (rig.Rig)")
+        if rig is None and views is not None:
+            raise ValueError("views= selects views of a rig: it needs particle_model='rig'")
+        self.rig, self.views = rig, None
+        if rig is not None:
+            if not isinstance(rig, rigmod.Rig):
+                raise TypeError("rig must be a rig.Rig, got %r" % (type(rig).__name__,))
+            self.views = rigmod.check_active(views, len(rig))
         self.dataset, self.sequence, self.seed = dataset, sequence, int(seed)
         st = dbmod.settings(dataset)
         self.settings = st
@@ -112,7 +129,7 @@ class RainAugment:
         rate = float(rate)
         if rate not in self._rates:
             sims, dgrid, cdf = particles.sim_frames(self.options, rate, self.n_sim, render_scale=self.render_scale, seed=self.seed,
-                                                    model=self.particle_model)
+                                                    model=self.particle_model, rig=self.rig)
             fog = add_attenuation.FogRain(rain_intensity=rate, focal=self.focal, f_number=self.f_number, angle=90,
                                           exposure=self.exposure, camera_gain=self.camera_gain).constants()
             self._rates[rate] = (sims, dgrid, np.atleast_2d(cdf), tuple(float(v) for v in fog))
@@ -133,7 +150,9 @@ class RainAugment:
 
     def plan(self, intensity, frame_index, B=None):
         """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
-        union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key)."""
+        union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key).  Under the
+        rig model B counts instants: sims and fog hold V = len(views) consecutive entries per instant (view views[i % V] of
+        instant i // V), plus views, rig_views and rig_box (what rr_set_particle_rig gets)."""
         if B is None:
             B = len(np.atleast_1d(np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index)))
         rates = [float(r) for r in _as_list(intensity, B, 'intensity', 'rate')]
@@ -150,7 +169,7 @@ class RainAugment:
             rs, _, _, fc = self._rate(r)
             sims[i] = rs[f % self.n_sim]                     # simulated frame f % n_sim with the draws of frame f (generator.py:318-321)
             sims[i]['draw_seed'] = f
-            if self.particle_model == 'field':               # the field's time is the frame index itself: a clip is k0 + arange(T)
+            if self.particle_model in ('field', 'rig'):      # the field's time is the frame index itself: a clip is k0 + arange(T)
                 sims[i]['frame'] = f
             sims[i]['table'] = int(rs[f % self.n_sim]['table']) + offs[r]
             sims[i]['run_pos'] = 0
@@ -159,8 +178,13 @@ class RainAugment:
             n_max = max(n_max, int(self._rate(r)[0]['n_particles'].max()))
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
-        return dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
-                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]))
+        out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
+                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]))
+        if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
+            V = len(self.views)
+            out.update(sims=np.repeat(sims, V), fog=np.repeat(fog, V, axis=0), views=list(self.views),
+                       rig_views=self.rig.as_records(), rig_box=particles.rig_run_box(self.options, self._first_rate(), self.n_sim, self.rig))
+        return out
 
     # ---- the call ----------------------------------------------------------------------------------------------------
     def _validate(self, images, depth):
@@ -168,6 +192,15 @@ class RainAugment:
             raise TypeError("images and depth must be torch tensors")
         if images.dtype not in (torch.uint8, torch.float32):
             raise TypeError("images must be uint8 or float32, got %s" % images.dtype)
+        if self.rig is not None:
+            V = len(self.views)
+            if images.dim() != 5 or images.shape[1] != V or images.shape[2] != 3 or min(images.shape) < 1:
+                raise ValueError("images must be [B, V = %d, 3, H, W] (planar RGB per view), got %s" % (V, tuple(images.shape)))
+            B, _, _, H, W = images.shape
+            if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, V, H, W), (B, V, 1, H, W)):
+                raise ValueError("depth must be float32 [B, V, H, W] or [B, V, 1, H, W] = %s, got %s %s" %
+                                 ((B, V, H, W), depth.dtype, tuple(depth.shape)))
+            return B, H, W
         if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1 or images.shape[2] < 1 or images.shape[3] < 1:
             raise ValueError("images must be [B, 3, H, W] (planar RGB), got %s" % (tuple(images.shape),))
         B, _, H, W = images.shape
@@ -185,12 +218,14 @@ class RainAugment:
                 raise ValueError("%s is on %s, the augmenter's context on %s" % (name, t.device, dev))
         return dev
 
-    def _context(self, dev, H, W, key, dgrid, cdf):
+    def _context(self, dev, H, W, key, dgrid, cdf, p=None):
         if self._hip is None:
             hip = hip_backend.RainHip(dev.index)
             hip.set_streak_db(self.db.streaks_light)
             hip.set_camera(hip_backend.make_camera(self.focal, self.f_number, self.exposure))
             hip.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            if self.rig is not None:
+                hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])
             hip.set_particle_model(self.particle_model, self.options["cam_hz"])
             self._hip, self.device = hip, dev
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
@@ -210,10 +245,13 @@ class RainAugment:
             raise ValueError("%s%s renders %d x %d frames (H x W), the images are %d x %d" %
                              (self.dataset, '' if self.sequence is None else '/' + self.sequence, fh, fw, H, W))
         dev = self._check_device(images, depth)
-        images = images.contiguous()
+        V = None if self.rig is None else len(self.views)
+        if V is not None:                                    # the library's batch: V consecutive frames per instant
+            B = B * V
+        images = images.reshape(B, 3, H, W).contiguous()
         depth = depth.reshape(B, H, W).contiguous()
         with torch.cuda.device(dev):
-            hip = self._context(dev, H, W, p['key'], p['d_grid'], p['cdf'])
+            hip = self._context(dev, H, W, p['key'], p['d_grid'], p['cdf'], p)
             rainy = torch.empty((B, 3, H, W), dtype=images.dtype, device=dev)
             mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
             sims = np.ascontiguousarray(p['sims'])
@@ -231,6 +269,8 @@ class RainAugment:
                 # queued on it (the inputs) is finished first, and the call's own wait covers the outputs
                 stream.synchronize()
             hip.augment_frames_device(b, stream.cuda_stream)
+        if V is not None:
+            return rainy.reshape(B // V, V, 3, H, W), mask.reshape(B // V, V, 1, H, W)
         return rainy, mask
 
     def close(self):

@@ -79,7 +79,14 @@ class Generator:
         self.particle_model = getattr(args, 'particle_model', 'iid') or 'iid'       # 'field': persistent particles (tools/particles.py)
         if self.particle_model != 'iid' and not self.device_particles:
             raise ValueError("--particle_model %s needs --device_particles" % self.particle_model)
-        if self.particle_model == 'field' and bool(self.noise_std):
+        self.rig, self.rig_view = None, int(getattr(args, 'rig_view', 0) or 0)
+        if self.particle_model == 'rig':
+            from ..rig import Rig, check_active
+            if getattr(args, 'rig', None) is None:
+                raise ValueError("--particle_model rig needs --rig")
+            self.rig = Rig.from_spec(args.rig)
+            check_active([self.rig_view], len(self.rig))
+        if self.particle_model in ('field', 'rig') and bool(self.noise_std):
             raise ValueError("--noise_std has no meaning with --particle_model field: the reference's angular noise turns a shared "
                              "simulated frame in place, the field model's particles move from frame to frame")
         self.sim_options = getattr(args, 'sim_options', {})
@@ -415,8 +422,12 @@ class Generator:
                     from ..tools import particles
                     opts = self.sim_options[sequence]
                     n_sim = particles.n_sim_frames(opts)
-                    sims, dgrid, cdf = particles.sim_frames(opts, fallrate, n_sim, render_scale=rs, seed=0, model=self.particle_model)
+                    sims, dgrid, cdf = particles.sim_frames(opts, fallrate, n_sim, render_scale=rs, seed=0, model=self.particle_model,
+                                                            rig=self.rig)
                     hip.set_particle_tables(dgrid, cdf)
+                    if self.rig is not None:                     # this run renders ONE view of the rig: its camera folder
+                        hip.set_particle_rig(self.rig.as_records(), particles.rig_run_box(opts, fallrate, n_sim, self.rig),
+                                             active=[self.rig_view])
                     hip.set_particle_model(self.particle_model, opts["cam_hz"])
                     frame_render_dict = []
                 else:
@@ -711,7 +722,7 @@ class Generator:
                         f_idx = items[k]['f_name_idx']
                         sl.sim_recs[k][0] = sims[f_idx % n_sim]
                         sl.sim_recs[k]['draw_seed'] = f_idx
-                        if self.particle_model == 'field':       # the field's time is the frame's own index (it does not wrap)
+                        if self.particle_model in ('field', 'rig'):    # the field's time is the frame's own index (it does not wrap)
                             sl.sim_recs[k]['frame'] = f_idx
                         sl.sim_recs[k]['run_pos'] = items[k]['run_pos']    # angular noise: its entry in the run (0: none)
                     else:

@@ -4641,6 +4641,105 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
   }
 }
 
+// k_rig_particles: the RIG model (rr_set_particle_rig, rr_particles.h make_rig_slot / rig_view_particle): one field, seen
+// by the n_active views of an instant.  Grid (chunks, instants).  A thread evaluates its slot's rig-frame state ONCE -- the
+// diameter look-up, three Philox blocks, the life, the wrap: what one k_field_particles launch per view would repeat --
+// and then walks the views: transform, cull, derive_drop, ballot + prefix popcount, LDS staging, whole-line stores into
+// that view's table (frame instant * n_active + a).  The ONE staging buffer is reused view after view (it is
+// wave-private: no barrier), so the kernel has k_field_particles' LDS and occupancy.  The wave totals of a step go through
+// s_cnt[step parity]: a wave that runs ahead writes the other half, and cannot reach the step after that before every wave
+// has passed this step's barrier -- one barrier per view step.  Every wave keeps its own copy of the views' running output
+// positions (s_run[wave]), so advancing them needs no barrier either.  COUNT and chunk_cnt ([frame][chunk]) as in
+// k_field_particles.  The views travel as a kernel argument: wave-uniform, read through the scalar path.
+struct RigViews {                    // the ACTIVE views in batch order, and the box
+  double R[RR_MAX_VIEWS][9];
+  double c[RR_MAX_VIEWS][3];
+  double box[3];
+  int n_active;
+};
+template <bool COUNT>
+__global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
+                                                        const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
+                                                        rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
+  const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int na = rv.n_active;
+  __shared__ rr_sim_frame s_sf;
+  __shared__ int s_cnt[2][8];
+  __shared__ int s_run[8][RR_MAX_VIEWS];
+  if (t < (int)(sizeof(rr_sim_frame) / 4))
+    reinterpret_cast<uint32_t*>(&s_sf)[t] = reinterpret_cast<const uint32_t*>(sims + (int64_t)inst * na)[t];
+  if (t < na) {
+    int b = 0;
+    if (!COUNT)
+      for (int k = 0; k < c; k++) b += chunk_cnt[((int64_t)inst * na + t) * nchunk + k];
+#pragma unroll
+    for (int w = 0; w < 8; w++) s_run[w][t] = b;
+  }
+  __syncthreads();
+  const rr_sim_frame sf = s_sf;
+  const double* cdf = cdf_tabs + (int64_t)sf.table * n_grid;
+  double rdb[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) rdb[k] = ratio_db[k];
+  const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
+  int step = 0;
+  for (int base = first; base < last; base += 512) {
+    const int j = base + t;
+    const bool valid = j < last;
+    rrsim::RigSlot q;
+    if (valid) rrsim::make_rig_slot(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q);
+    for (int a = 0; a < na; a++, step++) {
+      bool keep = false;
+      rr_drop d;
+      if (valid) {
+        rrsim::Particle p;
+        if (rrsim::rig_view_particle(sf, q, rv.box, rv.R[a], rv.c[a], p)) {
+          double ratio;
+          keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
+          d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+        }
+      }
+      const unsigned long long bal = __ballot(keep);
+      const int par = step & 1;
+      // the record's place in the wave's stage depends on the wave's own ballot only: it is staged BEFORE the barrier, so
+      // that no record is held in registers across it
+      __shared__ uint32_t s_stage[COUNT ? 1 : 8][64 * DROP_DW];   // per wave: 64 records (57 KB), one buffer for all views
+      if constexpr (!COUNT) {
+        if (keep) {
+          const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
+          uint32_t* dst = s_stage[wave] + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
+#pragma unroll
+          for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
+        }
+      }
+      if (lane == 0) s_cnt[par][wave] = __popcll(bal);
+      __syncthreads();
+      const int run = __builtin_amdgcn_readfirstlane(s_run[wave][a]);     // (wave-uniform: kept on the scalar side)
+      int off = run, tot = 0;
+#pragma unroll
+      for (int w = 0; w < 8; w++) {
+        const int n = __builtin_amdgcn_readfirstlane(s_cnt[par][w]);
+        if (w < wave) off += n;
+        tot += n;
+      }
+      if constexpr (!COUNT) {
+        const int room = imax(imin(__popcll(bal), cap - off), 0);   // what does not fit is not stored (the count still says so)
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + ((int64_t)inst * na + a) * cap + off);
+        for (int k = lane; k < room * DROP_DW; k += 64) o[k] = s_stage[wave][k];
+      }
+      wave_lds_sync();                                       // the stage and s_run[wave][a] are read before they are written again
+      if (lane == 0) s_run[wave][a] = run + tot;
+    }
+  }
+  wave_lds_sync();
+  if (t < na) {
+    const int64_t f = (int64_t)inst * na + t;
+    if (COUNT) chunk_cnt[f * nchunk + c] = s_run[0][t];
+    else if (c == nchunk - 1) n_out[f] = s_run[0][t];
+  }
+}
+
 // k_particle_draws: the renderer's per-drop random draws of one frame (np.random.seed(draw_seed); per drop one
 // randint(lo, lo + 10), per non-Big drop one normal(0, 0): bad_weather.py:252-264, generator.py:136) from numpy's legacy
 // MT19937 stream, bit for bit what rr_host_frame_draws makes on the host.  The stream is sequential by nature (how many
@@ -4969,6 +5068,11 @@ struct rr_ctx {
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
   size_t cap_field_cnt = 0;
+  // the rig model (rr_set_particle_rig, k_rig_particles)
+  int rig_n_views = 0, rig_n_active = 0;
+  rr_rig_view rig_views[RR_MAX_VIEWS];
+  int32_t rig_active[RR_MAX_VIEWS];
+  double rig_box[3] = {0.0, 0.0, 0.0};
   std::vector<uint32_t> run_frame, run_seed;
   std::vector<int32_t> run_chain;                                       // entry p: its index among its simulated frame's entries
   std::unordered_map<uint32_t, std::vector<uint32_t>> chain_seeds;      // simulated frame id -> seeds of its entries, in run order
@@ -6042,14 +6146,31 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     }
   }
   const bool noise_on = ctx->noise_std != 0.0 && ctx->noise_scale != 0.0;
-  const bool field = ctx->particle_model == RR_PARTICLES_FIELD;
+  const bool rig = ctx->particle_model == RR_PARTICLES_RIG;
+  const bool field = ctx->particle_model == RR_PARTICLES_FIELD || rig;
+  if (rig) {
+    const int na = ctx->rig_n_active;
+    if (na <= 0 || n % na != 0) {
+      ctx->err = "rig model: a batch of " + std::to_string(n) + " frames is not a multiple of the " + std::to_string(na) +
+                 " active views (rr_set_particle_rig): n_active consecutive frames per instant";
+      return RR_E_ARG;
+    }
+    for (int f = 0; f < n; f++) {
+      rr_sim_frame a = sims[f - f % na], b = sims[f];
+      a.draw_seed = b.draw_seed = 0;
+      if (memcmp(&a, &b, sizeof a) != 0) {
+        ctx->err = "rig model: the records of one instant must agree in every field but draw_seed (frame " + std::to_string(f) + ")";
+        return RR_E_ARG;
+      }
+    }
+  }
   int n_noisy = 0;
   for (int f = 0; f < n; f++) {
     const rr_sim_frame& sf = sims[f];
     if (sf.run_pos == 0) continue;
     if (field) {
       ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
-                 "): angular noise is not defined for the field model (rr_set_particle_model)";
+                 "): angular noise is not defined for the field and rig models (rr_set_particle_model)";
       return RR_E_ARG;
     }
     if (sf.run_pos < 0 || sf.run_pos > (int)ctx->run_frame.size()) {
@@ -6089,7 +6210,8 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       return RR_E_ARG;
     }
     const int rounds = imax((max_slots + 511) / 512, 1);
-    int chunks = ctx->field_chunks > 0 ? ctx->field_chunks : (n >= ctx->n_cu ? 1 : (2 * ctx->n_cu + n - 1) / n);
+    const int n_wg = rig ? n / ctx->rig_n_active : n;          // workgroups per chunk: frames, or the rig's instants
+    int chunks = ctx->field_chunks > 0 ? ctx->field_chunks : (n_wg >= ctx->n_cu ? 1 : (2 * ctx->n_cu + n_wg - 1) / n_wg);
     chunks = imax(1, imin(imin(chunks, 64), rounds));
     const int chunk_slots = ((rounds + chunks - 1) / chunks) * 512;
     chunks = (rounds * 512 + chunk_slots - 1) / chunk_slots;
@@ -6098,7 +6220,22 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       if ((rc = dev_alloc(ctx, ctx->d_field_cnt, (size_t)n * (size_t)chunks))) return rc;
       ctx->cap_field_cnt = (size_t)n * (size_t)chunks;
     }
-    {
+    if (rig) {
+      RigViews rv;
+      memset(&rv, 0, sizeof rv);
+      rv.n_active = ctx->rig_n_active;
+      for (int a = 0; a < rv.n_active; a++) {
+        memcpy(rv.R[a], ctx->rig_views[ctx->rig_active[a]].R, sizeof rv.R[a]);
+        memcpy(rv.c[a], ctx->rig_views[ctx->rig_active[a]].c, sizeof rv.c[a]);
+      }
+      memcpy(rv.box, ctx->rig_box, sizeof rv.box);
+      ProfScope ps(ctx, s, "k_rig_particles");
+      if (chunks > 1)
+        hipLaunchKernelGGL(k_rig_particles<true>, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid,
+                           ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      hipLaunchKernelGGL(k_rig_particles<false>, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid,
+                         ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+    } else {
       ProfScope ps(ctx, s, "k_field_particles");
       if (chunks > 1)
         hipLaunchKernelGGL(k_field_particles<true>, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf,
@@ -6704,8 +6841,8 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
     ctx->err = "rr_set_particle_noise: bad argument (n_run >= 0 entries, both tables, finite noise_std / noise_scale)";
     return RR_E_ARG;
   }
-  if (ctx->particle_model == RR_PARTICLES_FIELD && noise_std != 0.0 && noise_scale != 0.0) {
-    ctx->err = "rr_set_particle_noise: angular noise is not defined for the field model (rr_set_particle_model): the reference's noise "
+  if (ctx->particle_model != RR_PARTICLES_IID && noise_std != 0.0 && noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_noise: angular noise is not defined for the field and rig models (rr_set_particle_model): the reference's noise "
                "turns a shared simulated frame in place";
     return RR_E_ARG;
   }
@@ -6728,22 +6865,78 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
 
 int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz) {
   if (!ctx) return RR_E_ARG;
-  if (model != RR_PARTICLES_IID && model != RR_PARTICLES_FIELD) {
-    ctx->err = "rr_set_particle_model: unknown model " + std::to_string(model) + " (RR_PARTICLES_IID or RR_PARTICLES_FIELD)";
+  if (model != RR_PARTICLES_IID && model != RR_PARTICLES_FIELD && model != RR_PARTICLES_RIG) {
+    ctx->err = "rr_set_particle_model: unknown model " + std::to_string(model) + " (RR_PARTICLES_IID, RR_PARTICLES_FIELD or RR_PARTICLES_RIG)";
     return RR_E_ARG;
   }
-  if (model == RR_PARTICLES_FIELD) {
+  if (model != RR_PARTICLES_IID) {
     if (!std::isfinite(cam_hz) || !(cam_hz > 0)) {
-      ctx->err = "rr_set_particle_model: the field model needs cam_hz > 0 (frames per second)";
+      ctx->err = "rr_set_particle_model: the field and rig models need cam_hz > 0 (frames per second)";
       return RR_E_ARG;
     }
     if (ctx->noise_std != 0.0 && ctx->noise_scale != 0.0) {
-      ctx->err = "rr_set_particle_model: the field model has no angular noise; turn it off first (rr_set_particle_noise with noise_std 0)";
+      ctx->err = "rr_set_particle_model: the field and rig models have no angular noise; turn it off first (rr_set_particle_noise with noise_std 0)";
+      return RR_E_ARG;
+    }
+    if (model == RR_PARTICLES_RIG && ctx->rig_n_views == 0) {
+      ctx->err = "rr_set_particle_model: RR_PARTICLES_RIG needs a rig first (rr_set_particle_rig)";
       return RR_E_ARG;
     }
   }
   ctx->particle_model = model;
-  ctx->cam_hz = model == RR_PARTICLES_FIELD ? cam_hz : 0.0;
+  ctx->cam_hz = model != RR_PARTICLES_IID ? cam_hz : 0.0;
+  return RR_OK;
+}
+
+int rr_sizeof_rig_view(void) { return (int)sizeof(rr_rig_view); }
+
+int rr_set_particle_rig(rr_ctx* ctx, int32_t n_views, const rr_rig_view* views, const double box[3], int32_t n_active, const int32_t* active) {
+  if (!ctx) return RR_E_ARG;
+  if (n_views < 1 || n_views > RR_MAX_VIEWS || !views || !box) {
+    ctx->err = "rr_set_particle_rig: n_views must be 1 .. " + std::to_string(RR_MAX_VIEWS) + ", with views and box";
+    return RR_E_ARG;
+  }
+  for (int v = 0; v < n_views; v++) {
+    const double* R = views[v].R;
+    bool ok = std::isfinite(views[v].c[0]) && std::isfinite(views[v].c[1]) && std::isfinite(views[v].c[2]);
+    for (int k = 0; k < 9; k++) ok = ok && std::isfinite(R[k]);
+    for (int i = 0; ok && i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        const double dot = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2];
+        ok = ok && fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-9;
+      }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    if (!ok || !(fabs(det - 1.0) <= 1e-9)) {
+      ctx->err = "rr_set_particle_rig: view " + std::to_string(v) + ": R must be finite and orthonormal with determinant +1 (within 1e-9), c finite";
+      return RR_E_ARG;
+    }
+  }
+  if (!std::isfinite(box[0]) || !std::isfinite(box[1]) || !std::isfinite(box[2]) || !(box[0] > 0) || !(box[1] > 0) || !(box[2] >= 0)) {
+    ctx->err = "rr_set_particle_rig: box = {r, r_y, o_y} must be finite with r > 0, r_y > 0, o_y >= 0";
+    return RR_E_ARG;
+  }
+  int32_t act[RR_MAX_VIEWS];
+  int na = n_views;
+  if (active) {
+    na = n_active;
+    bool ok = na >= 1 && na <= n_views;
+    for (int a = 0; ok && a < na; a++) {
+      ok = active[a] >= 0 && active[a] < n_views;
+      for (int k = 0; ok && k < a; k++) ok = active[k] != active[a];
+      if (ok) act[a] = active[a];
+    }
+    if (!ok) {
+      ctx->err = "rr_set_particle_rig: active must hold 1 .. n_views distinct view numbers in 0 .. n_views - 1";
+      return RR_E_ARG;
+    }
+  } else {
+    for (int a = 0; a < na; a++) act[a] = a;
+  }
+  ctx->rig_n_views = n_views;
+  ctx->rig_n_active = na;
+  memcpy(ctx->rig_views, views, sizeof(rr_rig_view) * (size_t)n_views);
+  memcpy(ctx->rig_active, act, sizeof(int32_t) * (size_t)na);
+  memcpy(ctx->rig_box, box, sizeof ctx->rig_box);
   return RR_OK;
 }
 

@@ -155,6 +155,90 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   return inside;
 }
 
+// ---- the RIG model (rr_set_particle_rig, tools/particles.py make_rig_particles): one field, several cameras ----
+// The field model with the slot's box in the RIG frame: the square [-b, b)^2 in x and z, b = r z_max, and [-by, by) in y,
+// by = r_y z_max + o_y (box = {r, r_y, o_y} from the host: the reach of all views' frusta per unit depth).  x and z wrap
+// modulo 2 b: the world is that lattice.  make_rig_slot is the part no view enters -- the diameter look-up, the three
+// Philox blocks, the life, the wrap -- and is evaluated ONCE per slot and instant; rig_view_particle then looks at the
+// slot through one view: the lattice image nearest to the camera, turned by R, culled against the frustum.
+struct RigSlot {
+  double X, Y, Z;                 // position in the rig frame
+  double wind, v;                 // rig-frame velocity (wind, -v, speed_mps)
+  double wd, z_max;               // diameter (m), farthest depth shown (the box's half side in x and z is box[0] z_max)
+  double life;
+};
+
+RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
+                         uint32_t j, RigSlot& q) {
+  uint32_t a[4] = {j, 0u, 0u, 1u};
+  philox4x32_10(a, sf.key0, sf.key1);
+  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
+  const double phase = unit32(a[1]);
+  const double wd = D * 1e-3;
+  const double z_max = rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far);
+  const double b = box[0] * z_max;
+  const double by = box[1] * z_max + box[2];
+  const double w = 2.0 * b, wy = 2.0 * by;
+  const double v = terminal_velocity(D);
+  const double T = wy / v;
+  const double t = (double)sf.frame / cam_hz;
+  const double s = t / T + phase;
+  const double g = floor(s);
+  const double age = s - g;
+  const double tau = age * T;
+  const double g_hi = floor(g * (1.0 / 4294967296.0)), g_lo = g - g_hi * 4294967296.0;
+  uint32_t bb[4] = {j, (uint32_t)g_lo, 1u, 2u + (uint32_t)g_hi}, cc[4] = {j, (uint32_t)g_lo, 2u, 2u + (uint32_t)g_hi};
+  philox4x32_10(bb, sf.key0, sf.key1);
+  philox4x32_10(cc, sf.key0, sf.key1);
+  const double s4 = ((unit32(cc[0]) + unit32(cc[1])) + (unit32(cc[2]) + unit32(cc[3]))) - 2.0;
+  const double wind = (s4 * 1.7320508075688772) * sf.wind_sigma;
+  const double qx = unit32(bb[0]) + (wind * tau) / w;
+  const double qz = unit32(bb[1]) + (sf.speed_mps * tau) / w;   // the vehicle's motion: drops gain +speed in z
+  const double fx = qx - floor(qx), fz = qz - floor(qz);
+  q.X = fx * w - b;
+  q.Y = by - age * wy;
+  q.Z = fz * w - b;
+  q.wind = wind;
+  q.v = v;
+  q.wd = wd;
+  q.z_max = z_max;
+  q.life = g;
+}
+
+// slot q as the view (R row-major rig -> camera, c the camera's centre) sees it; returns whether the view keeps it
+RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R, const double* c, Particle& p) {
+  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
+  const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;
+  const double b = box[0] * q.z_max, w = 2.0 * b;
+  double dx = q.X - c[0], dz = q.Z - c[2];
+  const double dy = q.Y - c[1];
+  dx = dx - floor((dx + b) / w) * w;                      // the lattice image nearest to the camera
+  dz = dz - floor((dz + b) / w) * w;
+  const double xc = (R[0] * dx + R[1] * dy) + R[2] * dz;
+  const double yc = (R[3] * dx + R[4] * dy) + R[5] * dz;
+  const double zc = (R[6] * dx + R[7] * dy) + R[8] * dz;
+  const double zr = -zc;                                    // depth along the view's axis
+  const double ax = hx * zr, ay = hy * zr;
+  const bool inside = zr > 0.0 && zr <= q.z_max && -ax <= xc && xc <= ax && -ay <= yc && yc <= ay;
+  const double depth = rr::dmax(zr, 0.05);
+  const double e = sf.exposure_s;
+  const double ex = dx + q.wind * e, ey = dy + (-q.v) * e, ez = dz + sf.speed_mps * e;
+  const double X2 = (R[0] * ex + R[1] * ey) + R[2] * ez;
+  const double Y2 = (R[3] * ex + R[4] * ey) + R[5] * ez;
+  const double Z2 = (R[6] * ex + R[7] * ey) + R[8] * ez;
+  const double depth2 = rr::dmax(-Z2, 0.05);
+  p.wp1[0] = xc; p.wp1[1] = yc; p.wp1[2] = -depth;
+  p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
+  p.wd = q.wd;
+  p.ip1[0] = W / 2.0 + (sf.fpx * xc) / depth;
+  p.ip1[1] = H / 2.0 + (sf.fpx * yc) / depth;
+  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
+  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
+  p.iw1 = (q.wd * sf.fpx) / depth;
+  p.iw2 = (q.wd * sf.fpx) / depth2;
+  return inside;
+}
+
 // ceil(sqrt(n)) of a non-negative integer, exactly (np.ceil(np.sqrt(.)) of the loader gives the same: a non-integer root
 // is further from an integer than the rounding error of a correctly rounded sqrt)
 RR_HD int64_t ceil_sqrt(int64_t n) {

@@ -37,8 +37,9 @@ RR_OPT_COLOUR_STREAM = 21
 RR_OPT_TILE_ROWS = 22
 RR_OPT_ROWS_SHARES = 23
 RR_OPT_FIELD_CHUNKS = 24
-RR_PARTICLES_IID, RR_PARTICLES_FIELD = 0, 1              # rr_set_particle_model
-PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD}
+RR_PARTICLES_IID, RR_PARTICLES_FIELD, RR_PARTICLES_RIG = 0, 1, 2      # rr_set_particle_model
+PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD, 'rig': RR_PARTICLES_RIG}
+RR_MAX_VIEWS = 8
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
 RR_IN_BG_PNG_ROWS, RR_DEPTH_PNG_ROWS = 32, 3              # a file's filtered scanlines (rr_io_read_frames_rows): un-filtered on the device
 RR_DEPTH_U16 = 2                                        # rr_prepass_in.depth_f64: the uint16 samples of the depth file (metres = sample / 256)
@@ -52,6 +53,10 @@ DROP_DTYPE = np.dtype([
     ('wps', '<f8', (3,)), ('wpe', '<f8', (3,)),
     ('rot_cos', '<f8'), ('rot_sin', '<f8'),
 ], align=True)
+
+
+# numpy mirror of rr_rig_view (rr_set_particle_rig): R row-major rig -> camera, c the camera's centre in the rig frame
+RIG_VIEW_DTYPE = np.dtype([('R', '<f8', (9,)), ('c', '<f8', (3,))], align=True)
 
 
 # numpy mirror of rr_sim_frame (the particle generator's per-frame settings, include/rainhip.h)
@@ -145,7 +150,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_particle', 'rr_sizeof_particle_frame', 'rr_set_colormap', 'rr_host_frame_draws', 'rr_host_assemble_drops',
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
-           'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model']
+           'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
+           'rr_set_particle_rig', 'rr_sizeof_rig_view']
 
 _lib = None
 
@@ -243,6 +249,8 @@ def load_library(path=None):
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_set_particle_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
+    lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
     assert lib.rr_sizeof_tensor_batch() == ctypes.sizeof(rr_tensor_batch), (lib.rr_sizeof_tensor_batch(), ctypes.sizeof(rr_tensor_batch))
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
@@ -841,8 +849,18 @@ class RainHip:
         per second).  Not together with angular noise."""
         if model not in PARTICLE_MODELS:
             raise ValueError("particle model %r: expected one of %s" % (model, ', '.join(PARTICLE_MODELS)))
-        self._check(self.lib.rr_set_particle_model(self.h, PARTICLE_MODELS[model], float(cam_hz) if model == 'field' else 0.0),
+        self._check(self.lib.rr_set_particle_model(self.h, PARTICLE_MODELS[model], float(cam_hz) if model != 'iid' else 0.0),
                     'rr_set_particle_model')
+
+    def set_particle_rig(self, views, box, active=None):
+        """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =
+        the views a batch renders, in batch order (default: all).  Select the model with set_particle_model('rig', cam_hz)."""
+        v = np.ascontiguousarray(views, RIG_VIEW_DTYPE)
+        b = np.ascontiguousarray(box, np.float64).reshape(-1)
+        assert b.shape == (3,)
+        a = None if active is None else np.ascontiguousarray(active, np.int32).reshape(-1)
+        self._check(self.lib.rr_set_particle_rig(self.h, len(v), _ptr(v), _ptr(b), 0 if a is None else len(a), None if a is None else _ptr(a)),
+                    'rr_set_particle_rig')
 
     def generate_drops_device(self, sims, H, W, drops_ptr, cap, n_out_ptr, stream=None):
         """rr_generate_drops_device: sims = SIM_FRAME_DTYPE records (host); drops_ptr / n_out_ptr = DEVICE addresses of

@@ -56,10 +56,14 @@ _FLAGS = [
     (('--force_particles',), dict(action='store_true', help='(reference only) re-run the particle simulator')),
     (('--device_particles',), dict(action='store_true', help='simulate the rain particles on the GPU, frame by frame (no particle '
                                                              'file is read or written; this build only)')),
-    (('--particle_model',), dict(type=str, default='iid', choices=['iid', 'field'],
+    (('--particle_model',), dict(type=str, default='iid', choices=['iid', 'field', 'rig'],
                                  help="with --device_particles: 'iid' draws independent particles for every simulated frame; 'field' is "
                                       "a persistent particle field for video: frame k + 1 shows the drops of frame k a little lower and "
-                                      "closer (not with --noise_std)")),
+                                      "closer (not with --noise_std); 'rig' is that field seen by one camera of a rig (--rig, --rig_view)")),
+    (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
+                                                   "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
+    (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
+                                                     "camera folder with the same seed gives a coherent set")),
 ]
 
 
@@ -80,6 +84,8 @@ def _derive(ns):
         if ns.noise_std:
             raise SystemExit("--noise_std cannot be combined with --particle_model field: the reference's angular noise turns a shared "
                              "simulated frame in place and has no meaning for particles that move from frame to frame")
+    if (getattr(ns, 'particle_model', 'iid') == 'rig') != (getattr(ns, 'rig', None) is not None):
+        raise SystemExit("--particle_model rig and --rig go together")
     ns.verbose = not ns.noverbose
     light_db = _J(ns.streaks_db, 'env_light_database')
     ns.texture = _J(light_db, 'size32')

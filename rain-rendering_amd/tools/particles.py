@@ -325,7 +325,7 @@ def _frame_settings(options, fallrate, k, min_px, z_far, margin):
     return cam, rate
 
 
-MODELS = ('iid', 'field')
+MODELS = ('iid', 'field', 'rig')
 
 
 def _check_model(model):
@@ -508,12 +508,190 @@ def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.0
     return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull)
 
 
+# ---- the RIG model: one field, several cameras (module docstring) --------------------------------------------------
+def rig_expected_count(cam, fallrate, box, min_px=1.0, z_far=15.0, n_grid=N_GRID):
+    """(expected number of SLOTS, diameter grid, its sampling CDF, z_max per diameter) of the rig model: N(D) times the volume
+    of the slot's box (2 r z_max)^2 (2 (r_y z_max + o_y)), `box` = (r, r_y, o_y)."""
+    r, r_y, o_y = (float(v) for v in box)
+    lam = mp_lambda(fallrate)
+    d = np.linspace(D_MIN, D_MAX, n_grid)
+    z_max = np.minimum(d * 1e-3 * cam.fpx / min_px, z_far)
+    w = 2.0 * (r * z_max)
+    vol = (w * w) * (2.0 * (r_y * z_max + o_y))
+    dens = N0 * det_exp(-lam * d) * vol
+    cdf = np.concatenate([[0.0], np.cumsum(0.5 * (dens[1:] + dens[:-1]) * np.diff(d))])
+    total = float(cdf[-1])
+    cdf = cdf / cdf[-1]
+    cdf[-1] = 1.0
+    return total, d, cdf, z_max
+
+
+def _rig_box(rig, cam, margin):
+    return tuple(float(v) for v in rig.box(cam, margin))
+
+
+def rig_run_box(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=0.05):
+    """The ONE box (r, r_y, o_y) of a run (rr_set_particle_rig holds one): Rig.box of the run's camera.  A run whose simulated
+    frames change the camera (cam_focal steps) has no single box and is refused."""
+    boxes = {_rig_box(rig, _frame_settings(options, fallrate, k, min_px, z_far, margin)[0], margin) for k in range(n_frames)}
+    if len(boxes) != 1:
+        raise ValueError("the rig model needs one camera for the whole run: the focal length changes between simulated frames")
+    return boxes.pop()
+
+
+def rig_slot_counts(options, fallrate, n_frames, rig, seed=0, min_px=1.0, z_far=15.0, margin=0.05, count=None):
+    """Particle slots of the rig model per simulated frame: ONE Poisson draw per distinct settings of the run around the
+    expected number of slots (rig_expected_count) -- or, with `count` (the expected number of particles in ONE view's frustum,
+    as for the other models), count x expected slots / expected particles, rounded."""
+    out = np.zeros(n_frames, np.int64)
+    drawn = {}
+    for k in range(n_frames):
+        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
+        tk = _settings_key(cam, rate)
+        if tk not in drawn:
+            mean = rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far)[0]
+            if count is not None:
+                drawn[tk] = int(round(int(count) * mean / expected_count(cam, rate, min_px, z_far, margin)[0]))
+            else:
+                drawn[tk] = int(np.random.RandomState((int(seed) * 1000003 + 999979 + len(drawn)) % (2 ** 32)).poisson(mean))
+        out[k] = drawn[tk]
+    return out
+
+
+def rig_tables(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=0.05):
+    """diameter_tables for the rig model: (d_grid, cdf [n_tables, N_GRID], table index per frame)."""
+    keys, tabs, idx = {}, [], np.zeros(n_frames, np.int32)
+    dgrid = None
+    for k in range(n_frames):
+        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
+        tk = _settings_key(cam, rate)
+        if tk not in keys:
+            _, dgrid, cdf, _ = rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far)
+            keys[tk] = len(tabs)
+            tabs.append(cdf)
+        idx[k] = keys[tk]
+    return dgrid, np.ascontiguousarray(np.stack(tabs)), idx
+
+
+def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0):
+    """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters: dict(D, z_max, b
+    (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
+    r, r_y, o_y = (float(v) for v in box)
+    j = np.arange(n_slots, dtype=np.uint64)
+    k0, k1 = _key(seed)
+    a = philox4x32(j, 0, 0, 1, k0, k1)
+    D = sample_diameter(dgrid, cdf, unit32(a[0]))
+    phase = unit32(a[1])
+    wd = D * 1e-3
+    z_max = np.minimum((wd * cam.fpx) / min_px, z_far)
+    b = r * z_max
+    by = r_y * z_max + o_y
+    w, wy = 2.0 * b, 2.0 * by
+    v = terminal_velocity(D)
+    T = wy / v
+    t = float(int(k) & 0xFFFFFFFF) / float(cam_hz)
+    s = t / T + phase
+    g = np.floor(s)
+    age = s - g
+    tau = age * T
+    g_hi = np.floor(g * (1.0 / 4294967296.0))
+    g_lo = g - g_hi * 4294967296.0
+    c1, c3 = g_lo.astype(np.uint64), np.uint64(2) + g_hi.astype(np.uint64)
+    bb = philox4x32(j, c1, 1, c3, k0, k1)
+    cc = philox4x32(j, c1, 2, c3, k0, k1)
+    s4 = ((unit32(cc[0]) + unit32(cc[1])) + (unit32(cc[2]) + unit32(cc[3]))) - 2.0
+    wind = (s4 * 1.7320508075688772) * wind_sigma
+    qx = unit32(bb[0]) + (wind * tau) / w
+    qz = unit32(bb[1]) + (cam.speed * tau) / w
+    fx, fz = qx - np.floor(qx), qz - np.floor(qz)
+    X = fx * w - b
+    Y = by - age * wy
+    Z = fz * w - b
+    return dict(D=D, wd=wd, z_max=z_max, b=b, by=by, life=g, pos=np.stack([X, Y, Z], axis=1),
+                vel=np.stack([wind, -v, np.full(n_slots, float(cam.speed))], axis=1))
+
+
+def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
+                       cull=True, image=(0, 0)):
+    """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
+    statement of rr_particles.h make_rig_slot + rig_view_particle (same operations, same order).  `box` = (r, r_y, o_y).
+    Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
+    view keeps, in ascending slot order.  `image` = (ix, iz) looks at the lattice image ix, iz periods away from the nearest
+    one instead (tests: with the host's r no such image is ever inside the frustum)."""
+    rec = np.zeros(n_slots, PARTICLE_DTYPE)
+    if n_slots == 0:
+        return rec, np.zeros(0, np.float64)
+    R = [float(v) for v in np.asarray(view[0], np.float64).reshape(9)]
+    c = [float(v) for v in np.asarray(view[1], np.float64).reshape(3)]
+    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far)
+    W, H = float(cam.W), float(cam.H)
+    hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
+    b, z_max, wd = st['b'], st['z_max'], st['wd']
+    w = 2.0 * b
+    dx = st['pos'][:, 0] - c[0]
+    dy = st['pos'][:, 1] - c[1]
+    dz = st['pos'][:, 2] - c[2]
+    dx = dx - np.floor((dx + b) / w) * w                       # the lattice image nearest to the camera
+    dz = dz - np.floor((dz + b) / w) * w
+    if image[0] or image[1]:
+        dx = dx + float(image[0]) * w
+        dz = dz + float(image[1]) * w
+    xc = (R[0] * dx + R[1] * dy) + R[2] * dz
+    yc = (R[3] * dx + R[4] * dy) + R[5] * dz
+    zc = (R[6] * dx + R[7] * dy) + R[8] * dz
+    zr = -zc                                                    # depth along the view's axis
+    ax, ay = hx * zr, hy * zr
+    inside = (zr > 0.0) & (zr <= z_max) & (-ax <= xc) & (xc <= ax) & (-ay <= yc) & (yc <= ay)
+    depth = np.maximum(zr, 0.05)
+    e = cam.exposure
+    ex = dx + st['vel'][:, 0] * e
+    ey = dy + st['vel'][:, 1] * e
+    ez = dz + st['vel'][:, 2] * e
+    X2 = (R[0] * ex + R[1] * ey) + R[2] * ez
+    Y2 = (R[3] * ex + R[4] * ey) + R[5] * ez
+    Z2 = (R[6] * ex + R[7] * ey) + R[8] * ez
+    depth2 = np.maximum(-Z2, 0.05)
+    rec['pid'] = np.arange(n_slots)
+    rec['wp1'] = np.stack([xc, yc, -depth], axis=1)
+    rec['wp2'] = np.stack([X2, Y2, Z2], axis=1)
+    rec['wd1'] = rec['wd2'] = wd
+    rec['ip1'] = np.stack([W / 2.0 + (cam.fpx * xc) / depth, H / 2.0 + (cam.fpx * yc) / depth], axis=1)
+    rec['ip2'] = np.stack([W / 2.0 + (cam.fpx * X2) / depth2, H / 2.0 + (cam.fpx * Y2) / depth2], axis=1)
+    rec['iw1'] = (wd * cam.fpx) / depth
+    rec['iw2'] = (wd * cam.fpx) / depth2
+    if cull:
+        return rec[inside], st['life'][inside]
+    return rec, st['life']
+
+
+def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
+              cull=True, image=(0, 0)):
+    """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame."""
+    n_sim = n_sim_frames(options) if n_sim is None else int(n_sim)
+    ks = int(k) % n_sim
+    cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
+    box = _rig_box(rig, cam, margin)
+    _, dgrid, cdf, _ = rig_expected_count(cam, rate, box, min_px, z_far)
+    n_slots = int(rig_slot_counts(options, fallrate, ks + 1, rig, seed, min_px, z_far, margin, count)[ks])
+    return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, rig.views[int(view)], box, wind_sigma, margin, min_px, z_far,
+                              cull, image)
+
+
+def rig_run_sims(sims, k_idx, n_active):
+    """The records of instants `k_idx` of a rig-model run, n_active consecutive records per instant (frame i = active view
+    i % n_active of instant i / n_active): field_run_sims with every instant repeated."""
+    return field_run_sims(sims, np.repeat(np.asarray(k_idx, np.int64), int(n_active)))
+
+
 def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid'):
     """(frames, drops) record arrays of `n_frames` camera frames.  `count`: force that many drops per frame instead
     of the Poisson-distributed physical count.  model='field': the persistent field (module docstring), frame k at time
-    k / cam_hz under the settings of simulated frame k; pid is then the slot id."""
+    k / cam_hz under the settings of simulated frame k; pid is then the slot id.  (The rig model has no particle file: its
+    frames are made per view, rig_frame.)"""
     frames = np.zeros(n_frames, PARTICLE_FRAME_DTYPE)
     _check_model(model)
+    if model == 'rig':
+        raise ValueError("particle model 'rig' writes no particle file: use rig_frame / expected_records (one table per view)")
     if model == 'field':
         counts = field_slot_counts(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
     else:
@@ -556,16 +734,25 @@ def diameter_tables(options, fallrate, n_frames, min_px=1.0, z_far=15.0, margin=
 
 
 def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=None, min_px=1.0, z_far=15.0, margin=0.05,
-               wind_sigma=1.0, count=None, frame_ids=None, model='iid'):
+               wind_sigma=1.0, count=None, frame_ids=None, model='iid', rig=None):
     """SIM_FRAME_DTYPE records (hip_backend: the numpy mirror of rr_sim_frame) of `n_frames` camera frames + the tables
     they refer to: (sims, d_grid, cdf).  draw_seeds: np.random.seed(...) of the renderer's per-drop draws per frame
     (generator.py:318: the frame's index; default: the frame number).  model='field' (rr_set_particle_model): n_particles
     is the run's slot count under the frame's settings and `frame` the TIME index; a rendered frame f of a run takes the
-    record of simulated frame f % n_sim with frame = f (field_run_sims)."""
+    record of simulated frame f % n_sim with frame = f (field_run_sims).  model='rig' with `rig` (rig.Rig): likewise with the
+    rig's own tables and slot counts (rig_tables, rig_slot_counts); an instant's views share its record up to draw_seed
+    (rig_run_sims)."""
     from .. import hip_backend
     _check_model(model)
-    dgrid, cdf, tab = diameter_tables(options, fallrate, n_frames, min_px, z_far, margin)
-    counts = (field_slot_counts if model == 'field' else frame_counts)(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
+    if model == 'rig':
+        if rig is None:
+            raise ValueError("particle model 'rig' needs rig= (rig.Rig)")
+        rig_run_box(options, fallrate, n_frames, rig, min_px, z_far, margin)
+        dgrid, cdf, tab = rig_tables(options, fallrate, n_frames, rig, min_px, z_far, margin)
+        counts = rig_slot_counts(options, fallrate, n_frames, rig, seed, min_px, z_far, margin, count)
+    else:
+        dgrid, cdf, tab = diameter_tables(options, fallrate, n_frames, min_px, z_far, margin)
+        counts = (field_slot_counts if model == 'field' else frame_counts)(options, fallrate, n_frames, seed, min_px, z_far, margin, count)
     sims = np.zeros(n_frames, hip_backend.SIM_FRAME_DTYPE)
     k0, k1 = _key(seed)
     for k in range(n_frames):
@@ -590,14 +777,18 @@ def field_run_sims(sims, f_idx):
     return out
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None):
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame."""
     from ..common import bad_weather as bw
     cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
                                speed=float(s['speed_mps'])))()
     seed = int(s['key0']) | (int(s['key1']) << 32)
-    if model == 'field':
+    if model == 'rig':
+        rec, _ = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
+                                    rig.views[int(view)], _rig_box(rig, cam, float(s['margin'])), float(s['wind_sigma']),
+                                    float(s['margin']), float(s['min_px']), float(s['z_far']))
+    elif model == 'field':
         rec, _ = make_field_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
                                       float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']))
     else:
@@ -613,7 +804,8 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None):
     return m.streaks_simulator[0].table, m, W, H
 
 
-def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None):
+def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
+                     rig=None, view=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -626,15 +818,26 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     replayed from scratch, so the result depends on nothing but the frame.
 
     model='field' with the run's `cam_hz` (rr_set_particle_model): the records of the field model's frames
-    (make_field_particles: slots inside the frustum in ascending order, then the same loader, filter and draws)."""
+    (make_field_particles: slots inside the frustum in ascending order, then the same loader, filter and draws).
+
+    model='rig' with `rig` (rig.Rig) and `cam_hz` (rr_set_particle_rig): record i is the frame of view `view[i % len(view)]`
+    -- `view`: the active list as the library gets it (default: every view of the rig in order), or one view's number for
+    records that are all of that view."""
     from .. import hip_backend
     _check_model(model)
     noisy = bool(noise_std) and bool(noise_scale)
-    if model == 'field' and (noisy or cam_hz is None):
-        raise ValueError("the field model needs cam_hz and has no angular noise")
+    if model in ('field', 'rig') and (noisy or cam_hz is None):
+        raise ValueError("the %s model needs cam_hz and has no angular noise" % model)
+    views = [0]
+    if model == 'rig':
+        if rig is None:
+            raise ValueError("particle model 'rig' needs rig= (rig.Rig)")
+        views = list(range(len(rig.views))) if view is None else [int(v) for v in np.atleast_1d(view)]
+        if len(sims) % len(views):
+            raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
-    for s in sims:
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz)
+    for i, s in enumerate(sims):
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)])
         p = int(s['run_pos'])
         if not noisy or p == 0:
             out.append(hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact'))

@@ -27,6 +27,9 @@ def main():
     ap.add_argument('--compare_models', type=int, default=0, metavar='ROUNDS',
                     help="also time particle_model 'iid' against 'field' at B = 32 (uint8) in this many interleaved rounds of --steps "
                          "calls; adds the key particle_models (frames/s: median, min, max over the rounds)")
+    ap.add_argument('--rig', default=None, metavar='SPEC',
+                    help="also time RainAugment(particle_model='rig') for this rig ('stereo:0.54' or a JSON file) at 32 frames per call "
+                         "(uint8, 32 / V instants); adds the key rig (frames/s over --steps calls)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -98,6 +101,22 @@ def main():
                 m: dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1)) for m, v in rates.items()})
             for a in augs.values():
                 a.close()
+        if args.rig:
+            rig = importlib.import_module('rain-rendering_amd.rig').Rig.from_spec(args.rig)
+            V = len(rig)
+            Bi = max(min(32, Bmax) // V, 1)
+            a = augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model='rig', rig=rig)
+            x = img8[:Bi * V].reshape(Bi, V, 3, H, W)
+            d = depth[:Bi * V].reshape(Bi, V, H, W)
+            for r in range(args.warmup + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for s_ in range(args.steps):
+                    a(x, d, args.intensity, r * args.steps * Bi + s_ * Bi + np.arange(Bi))
+                torch.cuda.synchronize()
+                dt_ = time.perf_counter() - t0
+            out['rig'] = dict(spec=args.rig, views=V, instants_per_call=Bi, frames_per_call=Bi * V, fps=round(Bi * V * args.steps / dt_, 1))
+            a.close()
     print(json.dumps(out))
 
 
