@@ -413,6 +413,26 @@ int rr_set_particle_rig(rr_ctx* ctx, int32_t n_views, const rr_rig_view* views, 
                         const int32_t* active);
 int rr_sizeof_rig_view(void);
 
+/* How the per-drop draws of the records the context generates from now on are made (every entry point that takes
+ * rr_sim_frame records: rr_generate_drops[_device], rr_frame_in.sim, rr_pipeline_*, rr_augment_frames_device).
+ *   RR_DRAWS_STREAM (default): step 3 above -- numpy's legacy stream seeded with draw_seed, replayed by one wave per frame
+ *     (k_particle_draws); the records of a run that writes the reference's files.
+ *   RR_DRAWS_COUNTER: the texture pick comes from the drop's own Philox counter, and the generator writes the final
+ *     tex_index itself (no k_particle_draws):
+ *         pick = (w * 10) >> 32 in 64-bit, w = word 2 of the drop's Philox block 1 -- counter (i, frame, 1, 0) under
+ *         RR_PARTICLES_IID, the life's block (j, g_lo, 1, 2 + g_hi) under RR_PARTICLES_FIELD and RR_PARTICLES_RIG: a word the
+ *         generator computes anyway and no other draw reads;
+ *         tex_index = 10 * texture_bucket(ratio) + pick.
+ *     Under the field and rig models the pick is a function of (key, slot, life): the same in every frame of a drop's life
+ *     and in every view of the rig.  (The ratio bucket comes from the projected size and can still differ between frames
+ *     or views.)  Under the i.i.d. model it is a function of (key, frame, particle index).  draw_seed is ignored.  Every
+ *     other field of a record is the stream mode's (tools/particles.py expected_records(draws='counter') states it).
+ * RR_E_ARG: unknown mode; RR_DRAWS_COUNTER while angular noise is on (the noise needs the stream's normal deviates and run
+ * order), likewise turning the noise on under RR_DRAWS_COUNTER (rr_set_particle_noise), or a record with run_pos != 0.
+ * Call it between runs, with no call of the generator in flight. */
+enum { RR_DRAWS_STREAM = 0, RR_DRAWS_COUNTER = 1 };
+int rr_set_particle_draws(rr_ctx* ctx, int32_t mode);
+
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`

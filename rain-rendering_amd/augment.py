@@ -21,6 +21,11 @@ comes back [B, V, 3, H, W], `mask` [B, V, 1, H, W].  View v of instant f is fram
 --particle_model rig --rig ... --rig_view v` run.  `views=[...]` restricts the call to a subset of the rig's views (V = len(views),
 in that order) with the same bits per view.
 
+`draws='counter'` (default 'stream') takes every drop's texture pick from the drop's own Philox counter instead of the run's numpy
+stream (tools/particles.py, `main.py --particle_draws counter`): under 'field' and 'rig' a drop then keeps its streak pattern in every
+frame of its life and in every view, and the device skips its one serial pass (0.15 ms of a KITTI 25 mm/hr call).  The frames are those of
+a `--particle_draws counter` run; 'stream' remains the mode that matches a run that writes the reference's files.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -77,10 +82,13 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None):
+                 rig=None, views=None, draws='stream'):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
+        if draws not in particles.DRAWS:
+            raise ValueError("draws %r: expected one of %s" % (draws, ', '.join(particles.DRAWS)))
+        self.draws = draws
         if (particle_model == 'rig') != (rig is not None):
             raise ValueError("particle_model='rig' and rig= go together (rig.Rig)")
         if rig is None and views is not None:
@@ -179,7 +187,7 @@ class RainAugment:
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
         out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
-                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]))
+                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
             out.update(sims=np.repeat(sims, V), fog=np.repeat(fog, V, axis=0), views=list(self.views),
@@ -227,6 +235,7 @@ class RainAugment:
             if self.rig is not None:
                 hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])
             hip.set_particle_model(self.particle_model, self.options["cam_hz"])
+            hip.set_particle_draws(self.draws)
             self._hip, self.device = hip, dev
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)

@@ -89,6 +89,14 @@ class Generator:
         if self.particle_model in ('field', 'rig') and bool(self.noise_std):
             raise ValueError("--noise_std has no meaning with --particle_model field: the reference's angular noise turns a shared "
                              "simulated frame in place, the field model's particles move from frame to frame")
+        self.particle_draws = getattr(args, 'particle_draws', 'stream') or 'stream'   # 'counter': the pick from the drop's own counter
+        if self.particle_draws not in ('stream', 'counter'):
+            raise ValueError("--particle_draws %r: expected stream or counter" % (self.particle_draws,))
+        if self.particle_draws != 'stream' and not self.device_particles:
+            raise ValueError("--particle_draws %s needs --device_particles" % self.particle_draws)
+        if self.particle_draws != 'stream' and bool(self.noise_std):
+            raise ValueError("--noise_std cannot be combined with --particle_draws counter: the angular noise needs the stream's normal "
+                             "deviates and the order of the run")
         self.sim_options = getattr(args, 'sim_options', {})
         self.batch = int(os.environ.get('RAIN_BATCH', '128'))     # frames per library call (three calls in flight); bench.py's host-inclusive leg uses the same
         self.rank, self.world = sharding.rank_world()
@@ -429,6 +437,9 @@ class Generator:
                         hip.set_particle_rig(self.rig.as_records(), particles.rig_run_box(opts, fallrate, n_sim, self.rig),
                                              active=[self.rig_view])
                     hip.set_particle_model(self.particle_model, opts["cam_hz"])
+                    if self.particle_draws != 'stream':          # (the noise is off: refused above)
+                        hip.set_particle_noise(0.0, 0.0)
+                    hip.set_particle_draws(self.particle_draws)
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)

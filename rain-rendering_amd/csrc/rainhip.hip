@@ -4509,7 +4509,11 @@ __global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int6
 // (rr_particles.h), and the survivors are written IN PARTICLE ORDER (the reference composites in file order): ballot +
 // prefix popcount inside a wave, the wave totals through LDS, a running base per frame.  The record goes out through LDS
 // so that the stores are whole lines; tex_index temporarily holds the first texture of the drop's block of ten.
+// CTR (rr_set_particle_draws RR_DRAWS_COUNTER; also a parameter of k_field_particles and k_rig_particles): the record leaves
+// with its FINAL tex_index -- the block's first texture plus rrsim::texture_pick of the word the generator already has
+// (word 2 of the drop's Philox block 1) -- and no k_particle_draws follows.  CTR = false is the kernel as it was.
 constexpr int DROP_DW = (int)(sizeof(rr_drop) / 4);
+template <bool CTR>
 __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int H, int W, const double* dgrid, const double* cdf_tabs,
                                                     int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run) {
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -4532,10 +4536,12 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
     rr_drop d;
     if (i < sf.n_particles) {
       rrsim::Particle p;
-      rrsim::make_particle(sf, dgrid, cdf, n_grid, (uint32_t)i, p);
+      uint32_t pw = 0;
+      rrsim::make_particle(sf, dgrid, cdf, n_grid, (uint32_t)i, p, CTR ? &pw : nullptr);
       double ratio;
       keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
       d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+      if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_cnt[wave] = __popcll(bal);
@@ -4572,7 +4578,7 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
 // pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
 // twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
 // batches fill the chip by themselves) there is no count pass.
-template <bool COUNT>
+template <bool COUNT, bool CTR>
 __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
                                                           const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
                                                           int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
@@ -4602,10 +4608,12 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
     if (j < last) {
       rrsim::Particle p;
       double life;
-      if (rrsim::make_field_particle(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life)) {
+      uint32_t pw = 0;
+      if (rrsim::make_field_particle(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr)) {
         double ratio;
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
         d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+        if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
       }
     }
     const unsigned long long bal = __ballot(keep);
@@ -4657,7 +4665,7 @@ struct RigViews {                    // the ACTIVE views in batch order, and the
   double box[3];
   int n_active;
 };
-template <bool COUNT>
+template <bool COUNT, bool CTR>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
                                                         rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
@@ -4689,15 +4697,25 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
     const bool valid = j < last;
     rrsim::RigSlot q;
     if (valid) rrsim::make_rig_slot(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q);
+    // CTR: the slot's pick (0 .. 9) is live across the view loop, where the stream kernel has no register to spare.  It
+    // takes the place of z_max, which every view step forms again from the diameter (the same expression as make_rig_slot's:
+    // the same bits); the empty asm keeps the compiler from hoisting that back out of the loop.
+    int pick = 0;
+    if constexpr (CTR) pick = valid ? rrsim::texture_pick(q.pick_word) : 0;
     for (int a = 0; a < na; a++, step++) {
       bool keep = false;
       rr_drop d;
       if (valid) {
+        if constexpr (CTR) {
+          asm volatile("" : "+v"(q.wd));
+          q.z_max = rr::dmin((q.wd * sf.fpx) / sf.min_px, sf.z_far);
+        }
         rrsim::Particle p;
         if (rrsim::rig_view_particle(sf, q, rv.box, rv.R[a], rv.c[a], p)) {
           double ratio;
           keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
           d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+          if constexpr (CTR) d.tex_index += pick;             // one pick for every view of the slot
         }
       }
       const unsigned long long bal = __ballot(keep);
@@ -5064,6 +5082,7 @@ struct rr_ctx {
   double noise_std = 0.0, noise_scale = 0.0;
   // the field model (rr_set_particle_model, k_field_particles)
   int particle_model = RR_PARTICLES_IID;
+  int particle_draws = RR_DRAWS_STREAM;   // rr_set_particle_draws: the texture pick from numpy's stream, or from the drop's own counter
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
@@ -6106,7 +6125,7 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   if (m > 0) {                       // pristine streaks of the fresh states: filtered, tex_index = first texture of the block of ten
     ProfScope ps(ctx, s, "k_particles");
     rr_drop* P = ctx->noise_states[fresh_id[0]].pristine;
-    hipLaunchKernelGGL(k_particles, dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
+    hipLaunchKernelGGL(k_particles<false>, dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
                        ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P, stride, ctx->noise_states[fresh_id[0]].n_pristine, 0);
   }
   {
@@ -6164,10 +6183,16 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
     }
   }
+  const bool ctr = ctx->particle_draws == RR_DRAWS_COUNTER;
   int n_noisy = 0;
   for (int f = 0; f < n; f++) {
     const rr_sim_frame& sf = sims[f];
     if (sf.run_pos == 0) continue;
+    if (ctr) {
+      ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
+                 "): angular noise needs the stream's deviates and run order; it is not defined under RR_DRAWS_COUNTER (rr_set_particle_draws)";
+      return RR_E_ARG;
+    }
     if (field) {
       ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
                  "): angular noise is not defined for the field and rig models (rr_set_particle_model)";
@@ -6230,30 +6255,38 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
       memcpy(rv.box, ctx->rig_box, sizeof rv.box);
       ProfScope ps(ctx, s, "k_rig_particles");
-      if (chunks > 1)
-        hipLaunchKernelGGL(k_rig_particles<true>, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid,
-                           ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
-      hipLaunchKernelGGL(k_rig_particles<false>, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid,
-                         ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      };
+      if (chunks > 1) launch(k_rig_particles<true, false>);   // (a count does not depend on the draws)
+      if (ctr) launch(k_rig_particles<false, true>);
+      else launch(k_rig_particles<false, false>);
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
-      if (chunks > 1)
-        hipLaunchKernelGGL(k_field_particles<true>, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf,
-                           ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
-      hipLaunchKernelGGL(k_field_particles<false>, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf,
-                         ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+      };
+      if (chunks > 1) launch(k_field_particles<true, false>);
+      if (ctr) launch(k_field_particles<false, true>);
+      else launch(k_field_particles<false, false>);
     }
-    {
+    if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
       hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, 0);
     }
   } else if (n_noisy < n) {                                  // frames with angular noise are left to k_noise_chains
     {
       ProfScope ps(ctx, s, "k_particles");
-      hipLaunchKernelGGL(k_particles, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db,
-                         drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
+      if (ctr)
+        hipLaunchKernelGGL(k_particles<true>, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                           ctx->d_ratio_db, drops_out, cap, n_out, 0);
+      else
+        hipLaunchKernelGGL(k_particles<false>, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                           ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
     }
-    {
+    if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
       hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
     }
@@ -6846,6 +6879,11 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
                "turns a shared simulated frame in place";
     return RR_E_ARG;
   }
+  if (ctx->particle_draws == RR_DRAWS_COUNTER && noise_std != 0.0 && noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_noise: angular noise needs the stream's normal deviates and run order; select RR_DRAWS_STREAM first "
+               "(rr_set_particle_draws)";
+    return RR_E_ARG;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   if ((rc = noise_states_drop(ctx))) return rc;
@@ -6885,6 +6923,21 @@ int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz) {
   }
   ctx->particle_model = model;
   ctx->cam_hz = model != RR_PARTICLES_IID ? cam_hz : 0.0;
+  return RR_OK;
+}
+
+int rr_set_particle_draws(rr_ctx* ctx, int32_t mode) {
+  if (!ctx) return RR_E_ARG;
+  if (mode != RR_DRAWS_STREAM && mode != RR_DRAWS_COUNTER) {
+    ctx->err = "rr_set_particle_draws: unknown mode " + std::to_string(mode) + " (RR_DRAWS_STREAM or RR_DRAWS_COUNTER)";
+    return RR_E_ARG;
+  }
+  if (mode == RR_DRAWS_COUNTER && ctx->noise_std != 0.0 && ctx->noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_draws: angular noise needs the stream's normal deviates and run order; turn it off first "
+               "(rr_set_particle_noise with noise_std 0)";
+    return RR_E_ARG;
+  }
+  ctx->particle_draws = mode;
   return RR_OK;
 }
 

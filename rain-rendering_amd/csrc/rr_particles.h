@@ -53,8 +53,13 @@ RR_HD double sample_diameter(const double* dgrid, const double* cdf, int n, doub
   return dgrid[lo] + (u - cdf[lo]) * slope;
 }
 
-// particle i of frame sf: three Philox blocks, counter = (i, frame, block, 0)
-RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const double* cdf, int n_grid, uint32_t i, Particle& p) {
+// The counter-based texture pick (rr_set_particle_draws RR_DRAWS_COUNTER, tools/particles.py counter_picks): word 2 of the
+// drop's Philox block 1 -- which no other draw reads -- scaled to 0 .. 9; tex_index = 10 * texture_bucket(ratio) + pick.
+RR_HD int texture_pick(uint32_t w) { return (int)(((uint64_t)w * 10u) >> 32); }
+
+// particle i of frame sf: three Philox blocks, counter = (i, frame, block, 0); *pick_word = the pick's word (b[2])
+RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const double* cdf, int n_grid, uint32_t i, Particle& p,
+                         uint32_t* pick_word = nullptr) {
   uint32_t a[4] = {i, sf.frame, 0u, 0u}, b[4] = {i, sf.frame, 1u, 0u}, c[4] = {i, sf.frame, 2u, 0u};
   philox4x32_10(a, sf.key0, sf.key1);
   philox4x32_10(b, sf.key0, sf.key1);
@@ -90,6 +95,7 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
   p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
   p.iw1 = (wd * sf.fpx) / depth;
   p.iw2 = (wd * sf.fpx) / depth2;
+  if (pick_word) *pick_word = b[2];
 }
 
 // ---- the FIELD model (rr_set_particle_model, tools/particles.py make_field_particles): a persistent particle field ----
@@ -101,9 +107,9 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
 // fractional part is its age.  Inside a life the position is the start moved by velocity x elapsed time, modulo the box
 // on the two lateral axes: a translation of a uniform law, hence uniform in the box at every t; what lies outside the
 // (margin-enlarged) frustum is culled (two slots in three).  Everything is a function of (key, j, k) and the settings.
-// Returns whether the particle is inside the frustum; `life` = g.
+// Returns whether the particle is inside the frustum; `life` = g; *pick_word = word 2 of the life's block 1 (texture_pick).
 RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
-                               Particle& p, double& life) {
+                               Particle& p, double& life, uint32_t* pick_word = nullptr) {
   uint32_t a[4] = {j, 0u, 0u, 1u};
   philox4x32_10(a, sf.key0, sf.key1);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
@@ -143,6 +149,7 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   const double Z2 = Z + sf.speed_mps * e;
   const double depth2 = rr::dmax(-Z2, 0.05);
   life = g;
+  if (pick_word) *pick_word = b[2];
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
   p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
   p.wd = wd;
@@ -166,6 +173,7 @@ struct RigSlot {
   double wind, v;                 // rig-frame velocity (wind, -v, speed_mps)
   double wd, z_max;               // diameter (m), farthest depth shown (the box's half side in x and z is box[0] z_max)
   double life;
+  uint32_t pick_word;             // word 2 of the life's block 1 (texture_pick): one pick for every view and frame of the life
 };
 
 RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
@@ -203,6 +211,7 @@ RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box
   q.wd = wd;
   q.z_max = z_max;
   q.life = g;
+  q.pick_word = bb[2];
 }
 
 // slot q as the view (R row-major rig -> camera, c the camera's centre) sees it; returns whether the view keeps it

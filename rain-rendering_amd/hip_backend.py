@@ -39,6 +39,8 @@ RR_OPT_ROWS_SHARES = 23
 RR_OPT_FIELD_CHUNKS = 24
 RR_PARTICLES_IID, RR_PARTICLES_FIELD, RR_PARTICLES_RIG = 0, 1, 2      # rr_set_particle_model
 PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD, 'rig': RR_PARTICLES_RIG}
+RR_DRAWS_STREAM, RR_DRAWS_COUNTER = 0, 1                              # rr_set_particle_draws
+PARTICLE_DRAWS = {'stream': RR_DRAWS_STREAM, 'counter': RR_DRAWS_COUNTER}
 RR_MAX_VIEWS = 8
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
 RR_IN_BG_PNG_ROWS, RR_DEPTH_PNG_ROWS = 32, 3              # a file's filtered scanlines (rr_io_read_frames_rows): un-filtered on the device
@@ -151,7 +153,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view']
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws']
 
 _lib = None
 
@@ -248,6 +250,7 @@ def load_library(path=None):
     lib.rr_generate_drops.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_set_particle_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
+    lib.rr_set_particle_draws.argtypes = [ctypes.c_void_p, ctypes.c_int32]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
@@ -851,6 +854,14 @@ class RainHip:
             raise ValueError("particle model %r: expected one of %s" % (model, ', '.join(PARTICLE_MODELS)))
         self._check(self.lib.rr_set_particle_model(self.h, PARTICLE_MODELS[model], float(cam_hz) if model != 'iid' else 0.0),
                     'rr_set_particle_model')
+
+    def set_particle_draws(self, draws='stream'):
+        """rr_set_particle_draws: 'stream' (default: the texture pick from numpy's stream seeded with draw_seed) or 'counter'
+        (from the drop's own Philox counter, tools/particles.counter_picks: coherent over a drop's life and across a rig's views;
+        no serial pass on the device).  Not together with angular noise."""
+        if draws not in PARTICLE_DRAWS:
+            raise ValueError("particle draws %r: expected one of %s" % (draws, ', '.join(PARTICLE_DRAWS)))
+        self._check(self.lib.rr_set_particle_draws(self.h, PARTICLE_DRAWS[draws]), 'rr_set_particle_draws')
 
     def set_particle_rig(self, views, box, active=None):
         """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =

@@ -60,6 +60,11 @@ _FLAGS = [
                                  help="with --device_particles: 'iid' draws independent particles for every simulated frame; 'field' is "
                                       "a persistent particle field for video: frame k + 1 shows the drops of frame k a little lower and "
                                       "closer (not with --noise_std); 'rig' is that field seen by one camera of a rig (--rig, --rig_view)")),
+    (('--particle_draws',), dict(type=str, default='stream', choices=['stream', 'counter'],
+                                 help="with --device_particles: 'stream' picks every drop's texture from numpy's stream seeded per frame, "
+                                      "like the reference; 'counter' takes the pick from the drop's own random counter: a drop keeps its "
+                                      "texture over its life (--particle_model field) and across the views of a rig, and the GPU skips its "
+                                      "one serial pass (not with --noise_std)")),
     (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
                                                    "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
     (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
@@ -86,6 +91,13 @@ def _derive(ns):
                              "simulated frame in place and has no meaning for particles that move from frame to frame")
     if (getattr(ns, 'particle_model', 'iid') == 'rig') != (getattr(ns, 'rig', None) is not None):
         raise SystemExit("--particle_model rig and --rig go together")
+    if getattr(ns, 'particle_draws', 'stream') != 'stream':
+        if not ns.device_particles:
+            raise SystemExit("--particle_draws %s needs --device_particles (a particle file's frames are drawn from numpy's stream)" %
+                             ns.particle_draws)
+        if ns.noise_std:
+            raise SystemExit("--noise_std cannot be combined with --particle_draws counter: the angular noise needs the stream's normal "
+                             "deviates and the order of the run")
     ns.verbose = not ns.noverbose
     light_db = _J(ns.streaks_db, 'env_light_database')
     ns.texture = _J(light_db, 'size32')

@@ -58,6 +58,17 @@ in the library) is a persistent, stateless particle field for video:
   * particle (slot j, frame k) is a pure function of (seed, j, k) and the settings: any frame can be made alone, in any
     batch, on any rank, with the same bits.  The kept records of a frame are in ascending slot order.  Angular noise
     (``--noise_std``) is not defined for the field model.
+
+Per-drop draws (``draws=``, ``rr_set_particle_draws`` in the library).  ``'stream'`` (default) is the renderer's own: numpy's
+legacy stream seeded per frame picks one of the ten textures of the drop's ratio bucket (``randint(lo, lo + 10)``), in
+drop order -- what a run that writes the reference's files needs.  ``'counter'`` (``counter_picks``) takes the pick from
+the drop's own Philox counter instead: ``pick = (w * 10) >> 32`` with w = word 2 of the drop's block 1 -- (i, frame, 1, 0),
+or the life's block (j, g_lo, 1, 2 + g_hi) under the field and rig models; a word the generator computes anyway and no
+other draw reads -- and ``tex_index = 10 * texture_bucket(ratio) + pick``.  Under the field and rig models the pick is a
+function of (seed, slot, life): a drop keeps its texture in every frame of its life and in every view of the rig (the
+ratio BUCKET comes from the projected size and can still differ between frames or views).  Under the i.i.d. model it is a
+function of (seed, frame, particle index).  ``draw_seed`` is ignored.  Angular noise needs the stream's normal deviates
+and run order and is refused with counter draws.
 """
 import os
 
@@ -326,6 +337,35 @@ def _frame_settings(options, fallrate, k, min_px, z_far, margin):
 
 
 MODELS = ('iid', 'field', 'rig')
+
+
+DRAWS = ('stream', 'counter')
+
+
+def _check_draws(draws, noisy=False):
+    if draws not in DRAWS:
+        raise ValueError("particle draws %r: expected one of %s" % (draws, ', '.join(DRAWS)))
+    if draws == 'counter' and noisy:
+        raise ValueError("counter draws have no angular noise: the noise needs the stream's normal deviates and run order")
+
+
+def texture_pick(w):
+    """rr_particles.h texture_pick: a 32-bit word scaled to 0 .. 9, (w * 10) >> 32 in 64-bit."""
+    return ((np.asarray(w).astype(np.uint64) * np.uint64(10)) >> np.uint64(32)).astype(np.int64)
+
+
+def counter_picks(seed, pid, frame=None, life=None):
+    """The counter-based texture pick (0 .. 9) of particles `pid`: texture_pick of word 2 of the drop's Philox block 1.
+    i.i.d. model: `frame` = the simulated frame, block (pid, frame, 1, 0).  Field and rig models: `life` = the life g of every
+    slot `pid` (make_field_particles / make_rig_particles return it), block (pid, g_lo, 1, 2 + g_hi)."""
+    j = np.asarray(pid).astype(np.uint64)
+    k0, k1 = _key(seed)
+    if life is None:
+        return texture_pick(philox4x32(j, int(frame) & 0xFFFFFFFF, 1, 0, k0, k1)[2])
+    g = np.asarray(life, np.float64)
+    g_hi = np.floor(g * (1.0 / 4294967296.0))
+    g_lo = g - g_hi * 4294967296.0
+    return texture_pick(philox4x32(j, g_lo.astype(np.uint64), 1, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)[2])
 
 
 def _check_model(model):
@@ -777,20 +817,22 @@ def field_run_sims(sims, f_idx):
     return out
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0):
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream'):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
-    (the loader's derived fields) on the rendered frame."""
+    (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
+    texture pick of every row (counter_picks of the row's particle)."""
     from ..common import bad_weather as bw
     cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
                                speed=float(s['speed_mps'])))()
     seed = int(s['key0']) | (int(s['key1']) << 32)
+    life = None
     if model == 'rig':
-        rec, _ = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
+        rec, life = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
                                     rig.views[int(view)], _rig_box(rig, cam, float(s['margin'])), float(s['wind_sigma']),
                                     float(s['margin']), float(s['min_px']), float(s['z_far']))
     elif model == 'field':
-        rec, _ = make_field_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
-                                      float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']))
+        rec, life = make_field_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
+                                         float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']))
     else:
         rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
                              float(s['margin']), float(s['min_px']), float(s['z_far']))
@@ -801,11 +843,15 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
     rs = int(s['render_scale'])
     W, H = int(s['sensor_w']) // rs, int(s['sensor_h']) // rs
     m.load_streaks_from_records(fr, rec, dataset, {"render_scale": rs}, [W, H])
-    return m.streaks_simulator[0].table, m, W, H
+    table = m.streaks_simulator[0].table
+    if draws == 'counter':
+        picks = counter_picks(seed, rec['pid'], int(s['frame']), life)
+        table.pick = picks[np.searchsorted(rec['pid'], table.pid)]      # (pid ascends: particle index, or slot)
+    return table, m, W, H
 
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
-                     rig=None, view=None):
+                     rig=None, view=None, draws='stream'):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -822,10 +868,14 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
 
     model='rig' with `rig` (rig.Rig) and `cam_hz` (rr_set_particle_rig): record i is the frame of view `view[i % len(view)]`
     -- `view`: the active list as the library gets it (default: every view of the rig in order), or one view's number for
-    records that are all of that view."""
+    records that are all of that view.
+
+    draws='counter' (rr_set_particle_draws RR_DRAWS_COUNTER): the same records with tex_index = 10 * texture_bucket(ratio) +
+    counter_picks of the drop instead of the stream's randint; draw_seed is ignored; no angular noise, no run_pos."""
     from .. import hip_backend
     _check_model(model)
     noisy = bool(noise_std) and bool(noise_scale)
+    _check_draws(draws, noisy)
     if model in ('field', 'rig') and (noisy or cam_hz is None):
         raise ValueError("the %s model needs cam_hz and has no angular noise" % model)
     views = [0]
@@ -837,8 +887,17 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)])
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws)
         p = int(s['run_pos'])
+        if draws == 'counter':
+            if p != 0:
+                raise ValueError("counter draws: run_pos must be 0 (frame %d)" % i)
+            rec = hip_backend.pack_frame(table, m, W, H, 0, rotation='exact')
+            keep = hip_backend.filter_streaks(table, W, H)
+            assert len(keep) == len(rec)
+            rec['tex_index'] = 10 * m.texture_bucket(table.ratio[keep]) + table.pick[keep]
+            out.append(rec)
+            continue
         if not noisy or p == 0:
             out.append(hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact'))
             continue
