@@ -553,6 +553,12 @@ enum {
   RR_OPT_FIELD_CHUNKS = 24,         /* tuning: workgroups that share one frame's slots in the field model's particle kernel
                                      * (rr_set_particle_model): 0 (default: the library sizes it so that a small batch still fills
                                      * the chip, one per frame for large batches) or 1 .. 64.  Same bits. */
+  RR_OPT_FOV_ORDER = 25,            /* tuning: which drops share a wave of the thread-per-drop polygon walk (k_fov_dda).  A wave runs the
+                                     * walk's vertex path on every row on which one of its 64 polygons has a vertex, so 1 (default)
+                                     * sorts a frame's drops by (distance from the camera in 0.25 m buckets, top row of the polygon)
+                                     * before the walk: neighbours on the map, of like size, share vertex rows.  0: table order, through
+                                     * the same kernels (every sort key is 0).  Same bits.  (bench.py --sweep restores the options it does
+                                     * not know to 0: after a sweep this one is off until it is set again.) */
   RR_OPT_COMPOSITE_BATCH = 20       /* retired: only 1 is accepted */
 };
 int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value);

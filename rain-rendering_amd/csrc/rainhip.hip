@@ -4,8 +4,10 @@
 //
 // The chain of one call (grid.y = frame; DESIGN.md section 5 has the measurements):
 //   second stream (RR_OPT_COLOUR_STREAM), the colour branch -- three numbers per drop:
-//     k_fov_dda        a thread per drop, no LDS: FOV polygon in float with error bounds, row spans by two cursors under OpenCV's
-//                      fill rule (16-byte edge records)  (k_fov_spans<NCH, false>: edge-parallel, float64 / caller-made polygons)
+//     k_fov_vertices   a thread per drop, no LDS: FOV polygon in float with error bounds, its classification, the drop's sort key
+//     k_fov_sort       a workgroup per frame: the drops in the order of their keys (RR_OPT_FOV_ORDER) -- slot -> drop and back
+//     k_fov_dda        a thread per slot, no LDS: row spans by two cursors under OpenCV's fill rule (16-byte edge records); the
+//                      span columns are slots  (k_fov_spans<NCH, false>: edge-parallel, float64 / caller-made polygons)
 //     k_fov_spans<NCH, true>   the drops float cannot decide and the wrapping polygons, from the frame's list, in float64
 //     k_fov_sums32 / k_fov_sums   workgroup (frame, band of map rows, chunk of drops): prefix rows in LDS, P[xr+1] - P[xl]
 //     (general path, maps beyond the fast path's limits or RR_OPT_FOV_FILL_RULE: k_fov_poly_general, k_env_prefix,
@@ -234,7 +236,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   int32_t* list_slow;               // [frame][drops]  blurred drops the fused kernel cannot take
   int4* blur_items;                 // [frame][8*drops] (drop, first sub-tile, #sub-tiles, -)
   int32_t* list_small;              // [frame][drops]  blurred drops handled one wave each (k_blur_small)
-  double* colpart;                  // [frame][COL_PARTS][5][drops] FOV partial sums per envmap row band
+  double* colpart;                  // [frame][COL_PARTS][5][drops] FOV partial sums per envmap row band (fov_slots: [slot] in place of [drop])
   double* wtab;                     // [frame][drops][2][BR_MAX+1] normalised Gaussian half tables of the blurred drops (k_blur_weights)
   double* wtab_big;                 // [frame][SLOW_CAP][2][MAX_R+1] the same for the first SLOW_CAP large-radius drops of a frame (k_blur_big_weights)
   const uint8_t* tex_pad;           // the textures with their 2-texel zero border, as k_tile stages them (k_pad_textures)
@@ -243,6 +245,10 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   uint32_t* fov_pix;                // [frame][n_fov][drops] k_fov_dda's vertex pixels, x | y << 16 (a wave stores 256 contiguous bytes per vertex)
   int32_t* fov_list;                // [frame][drops] drops k_fov_dda leaves to k_fov_spans (wrapping polygons, float64 decisions)
   int32_t* fov_list_n;              // [frame] their number
+  uint4* fov_rec;                   // [frame][drops] k_fov_vertices' record of a drop: (ytop, ybot, top vertex x | y << 16, ktop | mine << 8 | on_map << 9 | sort key << 16)
+  int32_t* fov_order;               // [frame][slot] -> drop: the order in which k_fov_dda's lanes take the drops (k_fov_sort); a span column is a SLOT
+  int32_t* fov_slot;                // [frame][drop] -> slot: its inverse (k_fov_sort's temporary between its two passes)
+  int32_t fov_slots;                // the span columns are slots (the k_fov_dda route); 0: a drop's column is its index
   uint8_t* blended;                 // [frame][drop] 1: the drop is composited (k_colour)
   int32_t* pad_first;               // RR_OPT_WILD_PIXELS only (else null), [frame][H*W]: lowest index of a composited drop whose padded
   int32_t* eff_first;               //   rectangle covers the pixel OUTSIDE / INSIDE the tile the compositor blends (k_pad_visits)
@@ -833,11 +839,12 @@ __global__ __launch_bounds__(256) void k_fov_spans(const FrameDesc* frames, Dims
   }
   // spans[frame][row][drop]
   bool have[FOV_GROUPS];                                       // (cross-lane reads stay outside the divergent stores)
-  int dk[FOV_GROUPS];                                          // the drop of group k
+  int dk[FOV_GROUPS];                                          // the span column of group k's drop: from the list, its slot (k_fov_sort)
+  const int col = (from_list && act) ? sc.fov_slot[gi] : dg;
 #pragma unroll
   for (int k = 0; k < FOV_GROUPS; k++) {
     have[k] = k < G && __builtin_amdgcn_readfirstlane(__shfl(m, k < G ? k * N : 0)) > 0;
-    dk[k] = __builtin_amdgcn_readfirstlane(__shfl(dg, k < G ? k * N : 0));
+    dk[k] = __builtin_amdgcn_readfirstlane(__shfl(col, k < G ? k * N : 0));
   }
 #pragma unroll
   for (int c = 0; c < NCH; c++) {
@@ -881,7 +888,38 @@ __global__ __launch_bounds__(256) void k_fov_spans(const FrameDesc* frames, Dims
 #define RR_DDA_WAVES 1          // waves per workgroup: 1 (r06: no LDS, no barrier -- single waves fit into whatever a CU has free: 5.57 -> 5.31 ms alone, step 27.9 -> 27.6)
 #endif
 constexpr int DDA_WAVES = RR_DDA_WAVES;
-__global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int Hp, int Dp, int cv_rule, Scratch sc) {
+// wave64 min / max of an int on DPP (cross-lane moves inside the VALU, no LDS crossbar): a lane without a source, and a row the
+// mask leaves out, keeps its own value -- min(v, v) = v.  Lane 63 holds the wave's result.
+template <int CTRL, int ROW_MASK>
+__device__ inline int dpp_keep_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false); }
+__device__ inline int wave_min_scan_i32(int v) {
+  v = imin(v, dpp_keep_i32<0x111, 0xf>(v));               // row_shr:1, 2, 4, 8
+  v = imin(v, dpp_keep_i32<0x112, 0xf>(v));
+  v = imin(v, dpp_keep_i32<0x114, 0xf>(v));
+  v = imin(v, dpp_keep_i32<0x118, 0xf>(v));
+  v = imin(v, dpp_keep_i32<0x142, 0xa>(v));               // row_bcast:15 into rows 1 and 3
+  v = imin(v, dpp_keep_i32<0x143, 0xc>(v));               // row_bcast:31 into rows 2 and 3
+  return v;
+}
+__device__ inline int wave_max_scan_i32(int v) {
+  v = imax(v, dpp_keep_i32<0x111, 0xf>(v));
+  v = imax(v, dpp_keep_i32<0x112, 0xf>(v));
+  v = imax(v, dpp_keep_i32<0x114, 0xf>(v));
+  v = imax(v, dpp_keep_i32<0x118, 0xf>(v));
+  v = imax(v, dpp_keep_i32<0x142, 0xa>(v));
+  v = imax(v, dpp_keep_i32<0x143, 0xc>(v));
+  return v;
+}
+
+// Part 1 (in table order): a drop's vertices and what float can say about its polygon.  Leaves the vertex pixels, npts
+// (or the drop's entry in the frame's list for k_fov_spans), the drop's record and its sort key (fov_rec) for k_fov_sort.
+// The key of a drop k_fov_dda walks: (distance in 0.25 m buckets, top row of the polygon) -- drops that are near each
+// other on the map and of similar size meet their polygons' vertices on the same rows (scripts/fov_order_model.py: some
+// lane of a wave stands on a vertex row on 0.60 of the wave's rows instead of 0.89 in table order).  A pure function of
+// the drop's record and the camera.  Every other drop: FOV_KEY_LAST, behind all of them.  ordered == 0
+// (RR_OPT_FOV_ORDER 0): every key is 0 and the stable sort leaves the table order.
+constexpr uint32_t FOV_KEY_LAST = 0xffffu;
+__global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_vertices(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int ordered, Scratch sc) {
   const int f = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const FrameDesc& fr = frames[f];
   const int N = cam.n_fov;
@@ -892,12 +930,14 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* fra
   const bool act = i < fr.n_drops;
   const int64_t gi = (int64_t)f * max_drops + (act ? i : 0);
   if (fr.strategy == 1) {                                      // 'white': the FOV is computed by the reference but never used
-    if (act) sc.npts[gi] = -1;
+    if (act) {
+      sc.npts[gi] = -1;
+      sc.fov_rec[gi] = make_uint4(0u, 0u, 0u, (ordered ? FOV_KEY_LAST : 0u) << 16);
+    }
     return;
   }
   // vertex k's pixel, x | y << 16, in global memory ([frame][vertex][drop]: 256 contiguous bytes per wave and vertex, read
   // back from L2 when the edge records are made)
-  uint4* const erec = sc.fov_erec + (int64_t)f * N * max_drops + (act ? i : 0);
   uint32_t* const gpix = sc.fov_pix + (int64_t)f * N * max_drops + (act ? i : 0);
   auto pixv = [&](int kk) -> uint32_t& { return gpix[(int64_t)kk * max_drops]; };
   uint32_t top_xy = 0;
@@ -907,10 +947,12 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* fra
   int ktop = 0, ytop = 1 << 30, ybot = -(1 << 30), r_first = 0;
   bool spread = false, on_map = true;
   int turns = 0, dir = 0, dir_first = 0;                       // sign changes of the vertices' row sequence (a closed monotone curve: 2)
+  float dist = 0.f;                                            // of the drop's mid-point from the camera, metres
   if (act) {
     FovSetup32 F;
     const rr_drop d = load_drop(fr.drops + i);
     fov_setup32(d, (float)cam.fov_cos, (float)cam.fov_sin, F, uns);
+    dist = sqrtf(F.pos[0] * F.pos[0] + F.pos[1] * F.pos[1] + F.pos[2] * F.pos[2]);
     float az_prev = 0.f, er_prev = 0.f, az0 = 0.f, er0 = 0.f;
     int y_prev = 0, y0v = 0;
     for (int k = 0; k < N; k++) {
@@ -965,22 +1007,48 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* fra
   const bool wrap = count_true == 1 || count_false == 1;
   const bool undecided = (uns & ~128) != 0 || count_true == 0 || count_false == 0 || (!wrap && !spread);
   const bool monotone = turns <= 2;
-  const bool mine = act && !certain_fail && !undecided && !wrap && monotone;     // a sure, closed, monotone N-gon: spans below
+  const bool mine = act && !certain_fail && !undecided && !wrap && monotone;     // a sure, closed, monotone N-gon: k_fov_dda's
   if (act && certain_fail) sc.npts[gi] = 0;
   if (act && !certain_fail && !mine) {                         // float64 / the general edge walk: k_fov_spans, from the list
     const int pos = atomicAdd(&sc.fov_list_n[f], 1);
     sc.fov_list[(int64_t)f * max_drops + pos] = i;
   }
   if (mine) sc.npts[gi] = N;
-  if (__ballot(mine) == 0ull) return;
-  // ---- 2. spans of the sure drops: two cursors down from the top vertex (rr_device.h DdaCursors) ----
-  // The records of the edges {k, k + 1} (upper end first) go to global memory, [frame][edge][drop], 16 bytes each: the
+  if (act) {
+    uint32_t key = 0u;
+    if (ordered) {
+      const int bucket = (int)fminf(fmaxf(dist * 4.0f, 0.f), 62.0f);      // (NaN: 0)
+      key = mine ? ((uint32_t)bucket << 10) | (uint32_t)imin(imax(ytop, 0), 1023) : FOV_KEY_LAST;
+    }
+    sc.fov_rec[gi] = make_uint4((uint32_t)ytop, (uint32_t)ybot, top_xy, (uint32_t)ktop | (mine ? 256u : 0u) | (on_map ? 512u : 0u) | (key << 16));
+  }
+}
+
+// Part 2, a lane per SLOT (k_fov_sort: slot -> drop): the spans of the sure drops, two cursors down from the top vertex
+// (rr_device.h DdaCursors).  The wave executes the vertex path of a row when any one of its 64 cursor pairs stands on a
+// vertex -- 220 of the ~300 instructions per row -- which is why the drops of a wave are chosen to share vertex rows.
+__global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int Hp, int Dp, int cv_rule, Scratch sc) {
+  const int f = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const FrameDesc& fr = frames[f];
+  const int N = cam.n_fov;
+  if (fr.strategy == 1) return;
+  const int s = (blockIdx.x * DDA_WAVES + wave) * 64 + lane;   // this lane's slot: its span column and the place of its edge records
+  const bool act = s < fr.n_drops;
+  const int i = act ? sc.fov_order[(int64_t)f * max_drops + s] : 0;      // its drop
+  const uint4 dr = act ? sc.fov_rec[(int64_t)f * max_drops + i] : make_uint4(0u, 0u, 0u, 0u);
+  const bool mine = act && (dr.w & 256u);
+  if (__ballot(mine) == 0ull) return;                          // (the drops of other routes lie behind all of this kernel's)
+  const int ytop = (int)dr.x, ybot = (int)dr.y, ktop = (int)(dr.w & 255u);
+  const uint32_t top_xy = dr.z;
+  uint4* const erec = sc.fov_erec + (int64_t)f * N * max_drops + s;
+  const uint32_t* const gpix = sc.fov_pix + (int64_t)f * N * max_drops + i;
+  auto pixv = [&](int kk) -> uint32_t { return gpix[(int64_t)kk * max_drops]; };
+  // The records of the edges {k, k + 1} (upper end first) go to global memory, [frame][edge][slot], 16 bytes each: the
   // walker's step, the packed outline constants, the edge's pixels on its first row and its lower end.  A wave stores 1 KB
   // per edge in one piece, a cursor loads its next record an edge (~30 rows) ahead.  (In LDS they left room for 10 waves per
   // CU instead of 24: 7.8 ms against 5.5 -- r06 A/B log.)  Round 6, second form: with the first row's pixels and the lower
-  // end in the record a lane that takes an edge evaluates neither DdaCursors' pixels() nor a vertex fetch -- the path the whole
-  // wave walks through on the 89 % of the rows on which one of its 64 cursors meets a vertex.
-  const bool cvr = cv_rule && on_map;                          // (a vertex off the map: the span rule, like the oracle)
+  // end in the record a lane that takes an edge evaluates neither DdaCursors' pixels() nor a vertex fetch.
+  const bool cvr = cv_rule && (dr.w & 512u);                   // (a vertex off the map: the span rule, like the oracle)
   if (mine) {
     const uint32_t vfirst = pixv(0);
     uint32_t va = vfirst;
@@ -1000,13 +1068,22 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* fra
   };
   DdaCursors<decltype(rec)> cur;
   if (mine) cur.init(rec, N, ktop, top_xy);
-  uint32_t* out = sc.spans + (int64_t)f * Hp * Dp + i;
-  for (int y = 0; y < Hp; y++) {
+  uint32_t* out = sc.spans + (int64_t)f * Hp * Dp + s;
+  // the rows above and below every polygon of the wave: zeros, no cursor call
+  // (both clamped to [0, Hp] here: no store of this kernel depends on where another function puts a vertex; the wave's
+  // minimum / maximum by DPP scans, lane 63 holds them)
+  const int wtop = __builtin_amdgcn_readlane(wave_min_scan_i32(mine ? imin(imax(ytop, 0), Hp) : Hp), 63);
+  const int wend = imax(__builtin_amdgcn_readlane(wave_max_scan_i32(mine ? imin(imax(ybot + 1, 0), Hp) : 0), 63), wtop);
+  for (int y = 0; y < wtop; y++)
+    if (mine) out[(int64_t)y * Dp] = 0u;
+  for (int y = wtop; y < wend; y++) {
     int lo = 1 << 30, hi = -(1 << 30);
     if (mine && y >= ytop && y <= ybot) cur.row(rec, y, lo, hi);
     const int a = imax(lo, 0), b = imin(hi, dm.We - 1);
     if (mine) out[(int64_t)y * Dp] = (y < dm.He && a <= b) ? ((uint32_t)a | ((uint32_t)(b + 1) << 16)) : 0u;
   }
+  for (int y = wend; y < Hp; y++)
+    if (mine) out[(int64_t)y * Dp] = 0u;
 }
 
 // ---- wave64 scans on DPP (cross-lane moves inside the VALU; __shfl_* would go through the LDS crossbar) ----
@@ -1246,6 +1323,76 @@ __device__ inline uint32_t wave_incl_scan_u32(uint32_t v) {              // (zer
 }
 __device__ inline float readlane_f32(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
+// The order in which k_fov_dda's lanes take a frame's drops: a stable sort of the drops by the 16-bit key k_fov_vertices
+// left in their records (ties keep the table order: the permutation is a function of the keys alone).  One workgroup per
+// frame, two counting passes of 8 bits (least significant first).  A pass: wave w owns a contiguous piece of the pass's
+// input and counts its digits into its own column of the [digit][wave] table; the table's exclusive prefix, read digit by
+// digit and wave by wave, is where wave w's first element of a digit goes; the wave then takes its piece 64 elements at a
+// time, in order, and a lane's place is the column's counter plus the number of lower lanes with the same digit (eight
+// ballots).  fov_slot is the temporary between the passes and ends as the inverse (drop -> slot).
+constexpr int FOV_SORT_WAVES = 16;
+__global__ __launch_bounds__(64 * FOV_SORT_WAVES) void k_fov_sort(const FrameDesc* frames, int max_drops, Scratch sc) {
+  __shared__ uint32_t s_cnt[256 * FOV_SORT_WAVES];
+  __shared__ uint32_t s_wtot[FOV_SORT_WAVES];
+  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int n = imin(frames[f].n_drops, max_drops);
+  const uint4* recs = sc.fov_rec + (int64_t)f * max_drops;
+  int32_t* order = sc.fov_order + (int64_t)f * max_drops;
+  int32_t* slot = sc.fov_slot + (int64_t)f * max_drops;
+  const int per = (n + 64 * FOV_SORT_WAVES - 1) / (64 * FOV_SORT_WAVES) * 64;
+  const int p0 = imin(wave * per, n), p1 = imin(p0 + per, n);
+  for (int pass = 0; pass < 2; pass++) {
+    const int32_t* src = slot;                                 // (pass 1; pass 0 reads the table order)
+    int32_t* dst = pass == 0 ? slot : order;
+    const int shift = 16 + 8 * pass;
+    for (int e = t; e < 256 * FOV_SORT_WAVES; e += 64 * FOV_SORT_WAVES) s_cnt[e] = 0u;
+    __syncthreads();
+    for (int p = p0 + lane; p < p1; p += 64) {
+      const int idx = pass == 0 ? p : src[p];
+      atomicAdd(&s_cnt[((recs[idx].w >> shift) & 255u) * FOV_SORT_WAVES + wave], 1u);
+    }
+    __syncthreads();
+    {                                                          // exclusive prefix of the table: four consecutive entries per thread
+      uint32_t c[4], sum = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; k++) { c[k] = s_cnt[4 * t + k]; sum += c[k]; }
+      const uint32_t incl = wave_incl_scan_u32(sum);
+      if (lane == 63) s_wtot[wave] = incl;
+      __syncthreads();
+      uint32_t run = incl - sum;
+      for (int w = 0; w < wave; w++) run += s_wtot[w];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { s_cnt[4 * t + k] = run; run += c[k]; }
+    }
+    __syncthreads();
+    for (int c = p0; c < p1; c += 64) {
+      const int p = c + lane;
+      const bool valid = p < p1;
+      const int idx = valid ? (pass == 0 ? p : src[p]) : 0;
+      const uint32_t digit = valid ? (recs[idx].w >> shift) & 255u : 0u;
+      unsigned long long peers = __ballot(valid);              // the lanes with this lane's digit
+#pragma unroll
+      for (int b = 0; b < 8; b++) {
+        const bool bit = (digit >> b) & 1u;
+        const unsigned long long bal = __ballot(bit);
+        peers &= bit ? bal : ~bal;
+      }
+      const int rank = __popcll(peers & ((1ull << lane) - 1ull)), np = __popcll(peers);
+      uint32_t* cnt = &s_cnt[digit * FOV_SORT_WAVES + wave];
+      const uint32_t at = *cnt;
+      wave_lds_sync();                                         // every lane has read its counter before a digit's last lane moves it
+      if (valid) {
+        dst[at + rank] = idx;
+        if (rank == np - 1) *cnt = at + (uint32_t)np;
+      }
+      wave_lds_sync();
+    }
+    __syncthreads();                                           // (the other waves' stores to dst: the next pass / the inverse reads them)
+  }
+  for (int p = t; p < n; p += 64 * FOV_SORT_WAVES) slot[order[p]] = p;
+}
+
 // r05: the kernel's time per map row was 4.75 us for 1 us of vector work: with ONE workgroup per CU nothing covers the
 // latency of the next row's loads (issued a lookup phase ahead) nor that of the span pieces (four rows at a time, used at
 // once).  Measured with the loads replaced by arithmetic: 3.8 ms -> 2.7 (no row loads) / 3.1 (no span loads) / 1.8 (neither).
@@ -1272,10 +1419,11 @@ __global__ __launch_bounds__(1024) void k_fov_sums32(const FrameDesc* frames, Di
   const int Cw = (((We + nw - 1) / nw) + 1) & ~1;
   const int cw0 = wave * Cw;
   uint32_t sp[DPT];
+  auto drop_of = [&](int i) { return sc.fov_slots ? sc.fov_order[(int64_t)f * max_drops + i] : i; };
 #pragma unroll
   for (int d = 0; d < DPT; d++) {
-    const int i = d0 + d * NT + t;
-    sp[d] = 4u * (uint32_t)((i < d1 && sc.npts[(int64_t)f * max_drops + i] > 0) ? i : max_drops);      // byte offset inside a span row
+    const int i = d0 + d * NT + t;                         // a span column: the slot of a drop (k_fov_sort) or the drop itself
+    sp[d] = 4u * (uint32_t)((i < d1 && sc.npts[(int64_t)f * max_drops + drop_of(i)] > 0) ? i : max_drops);      // byte offset inside a span row
   }
   if (t == 0) s_P[0] = make_float4(0.f, 0.f, 0.f, 0.f);
   float S[DPT][4];
@@ -1403,7 +1551,7 @@ __global__ __launch_bounds__(1024) void k_fov_sums32(const FrameDesc* frames, Di
 #pragma unroll
   for (int d = 0; d < DPT; d++) {
     const int i = d0 + d * NT + t;
-    if (i < d1) {
+    if (i < d1) {                                          // (at the span column's index -- a slot with sc.fov_slots: k_colour takes the drops in the same order)
       float* o = reinterpret_cast<float*>(sc.colpart) + ((int64_t)(f * COL_PARTS + band) * 5) * max_drops + i;      // (sc.colpart_f32)
 #pragma unroll
       for (int k = 0; k < 4; k++) o[(int64_t)max_drops * k] = S[d][k];
@@ -1482,9 +1630,10 @@ __global__ __launch_bounds__(256) void k_fov_sums_general(const FrameDesc* frame
 // compositor record.
 __global__ __launch_bounds__(256) void k_colour(const FrameDesc* frames, Dims dm, int max_drops, double cam_exposure, Scratch sc) {
   const int f = blockIdx.y;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int s = blockIdx.x * 256 + threadIdx.x;          // where the drop's band partials lie: its slot (k_fov_sort) with sc.fov_slots, else its index
   const FrameDesc& fr = frames[f];
-  if (i >= fr.n_drops) return;
+  if (s >= fr.n_drops) return;
+  const int i = sc.fov_slots ? sc.fov_order[(int64_t)f * max_drops + s] : s;      // (partials read side by side; a drop's plan and records are whole structures either way)
   const int64_t gi = (int64_t)f * max_drops + i;
   const DropPlan& p = sc.plan[gi];
   CompRec rec;
@@ -1519,7 +1668,7 @@ __global__ __launch_bounds__(256) void k_colour(const FrameDesc* frames, Dims dm
     bool any = false;
     double sumW = 0.0, sumY = 0.0;                       // whole-map sums (bad_weather.py:403-404), band order
     for (int b = 0; b < COL_PARTS; b++) {
-      const int64_t at = ((int64_t)(f * COL_PARTS + b) * 5) * max_drops + i;
+      const int64_t at = ((int64_t)(f * COL_PARTS + b) * 5) * max_drops + s;
       if (sc.colpart_f32) {                                // (wave-uniform) float partials: the same values, read as they were summed
         const float* part = reinterpret_cast<const float*>(sc.colpart) + at;
         for (int k = 0; k < 4; k++) S[k] += (double)part[(int64_t)max_drops * k];
@@ -5064,6 +5213,7 @@ struct rr_ctx {
   bool dda_attr = false;
   int fill_rule = 1;                 // RR_OPT_FOV_FILL_RULE: 1 (default since r06) OpenCV's fillConvexPoly; 0 the span rule of rounds 1-5
   int fov_dda = 1;                   // RR_OPT_FOV_DDA: a thread per drop for the polygons of the float colour branch (1: k_fov_dda, 2: k_fov_walk)
+  int fov_order = 1;                 // RR_OPT_FOV_ORDER: 1 k_fov_dda's waves take the drops sorted by (distance bucket, top row); 0 in table order (same kernels)
   int colour_stream = 1;             // RR_OPT_COLOUR_STREAM: 0 one stream; 1 the FOV chain on a second stream
   hipStream_t s_col = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -5356,6 +5506,9 @@ int ensure_scratch(rr_ctx* ctx, int n, int max_drops, const Dims& dm, bool need_
     if ((rc = dev_alloc(ctx, ctx->sc.fov_erec, general ? 1 : fd * (size_t)(ctx->cam.n_fov > 0 ? ctx->cam.n_fov : RR_MAX_FOV)))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.fov_pix, general ? 1 : fd * (size_t)(ctx->cam.n_fov > 0 ? ctx->cam.n_fov : RR_MAX_FOV)))) return rc;
     ctx->erec_nfov = ctx->cam.n_fov;
+    if ((rc = dev_alloc(ctx, ctx->sc.fov_rec, general ? 1 : fd))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->sc.fov_order, general ? 1 : fd))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->sc.fov_slot, general ? 1 : fd))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.fov_list_n, (size_t)F))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.list_gen, fd))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.list_slow, fd))) return rc;
@@ -5566,7 +5719,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     const bool fast = fov_fast_path(ctx, dm);
     const bool cv_rule = ctx->fill_rule == 1;              // RR_OPT_FOV_FILL_RULE: OpenCV's fillConvexPoly where it applies
     // r05 (RR_OPT_COLOUR_STREAM): two chains that only meet in k_colour can run on two streams of the library.
-    //   the FOV chain   k_fov_dda -> k_fov_spans (the list) -> k_fov_sums32: three numbers per drop; integer issue, then
+    //   the FOV chain   k_fov_vertices -> k_fov_sort -> k_fov_dda -> k_fov_spans (the list) -> k_fov_sums32: three numbers per drop; integer issue, then
     //                   one 1024-thread workgroup per CU waiting on loads
     //   bookkeeping     k_plan -> k_scan -> k_dedup -> k_lists (-> k_colour): chains of dependent loads, small workgroups
     // 1 (default): the FOV chain on the second stream beside plan .. tiles .. blur, k_colour behind the blur: 31.3 ms per 512
@@ -5604,23 +5757,36 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
       ~Join() { (void)now(); }
     } join{ctx, s, ctx->s_col, fs != s};
     const int Hp = ctx->scratch_hp, Dp = (D + 1 + 7) & ~7;
+    bool fov_dda = false;                                    // the thread-per-drop route
+    if (fast) {
+      bool any_ext = false;
+      for (int f = 0; f < n; f++) any_ext = any_ext || in[f].ext != nullptr;
+      fov_dda = fov32 && ctx->fov_dda != 0 && !any_ext;
+    }
+    sc.fov_slots = fov_dda ? 1 : 0;
+    const dim3 dgrid((max_drops + 64 * DDA_WAVES - 1) / (64 * DDA_WAVES), n);
+    // that route's first two kernels (timing scopes of their own): vertices and classification in table order, then the
+    // frame's drops sorted by their keys (RR_OPT_FOV_ORDER 0: every key is 0, the order is the table's)
+    if (fov_dda) {
+      ProfScope ps(ctx, fs, "k_fov_vertices");
+      HIPCHK(hipMemsetAsync(sc.fov_list_n, 0, sizeof(int32_t) * (size_t)n, fs));
+      hipLaunchKernelGGL(k_fov_vertices, dgrid, dim3(64 * DDA_WAVES), 0, fs, ctx->d_frames, dm, ctx->cam, D, ctx->fov_order, sc);
+    }
+    if (fov_dda) {
+      ProfScope ps(ctx, fs, "k_fov_sort");
+      hipLaunchKernelGGL(k_fov_sort, dim3(n), dim3(64 * FOV_SORT_WAVES), 0, fs, ctx->d_frames, D, sc);
+    }
     if (fast) {
       ProfScope ps(ctx, fs, "k_fov_spans");
       const int G = imin(64 / ctx->cam.n_fov, FOV_GROUPS);
       // float colour branch: a thread per drop (k_fov_dda) for the polygons float decides and that do not wrap; the rest
       // (a fraction of a percent) through the frame's list to k_fov_spans in float64.  Caller-made polygons (rr_ext_tile)
       // and the float64 colour branch: k_fov_spans for every drop.
-      bool any_ext = false;
-      for (int f = 0; f < n; f++) any_ext = any_ext || in[f].ext != nullptr;
-      const bool dda = fov32 && ctx->fov_dda != 0 && !any_ext;
+      const bool dda = fov_dda;
       const int v32 = fov32 ? 1 : 0;
       const dim3 grid((max_drops + 4 * G - 1) / (4 * G), n);
       if (dda) {
-        HIPCHK(hipMemsetAsync(sc.fov_list_n, 0, sizeof(int32_t) * (size_t)n, fs));
-        {
-          hipLaunchKernelGGL(k_fov_dda, dim3((max_drops + 64 * DDA_WAVES - 1) / (64 * DDA_WAVES), n), dim3(64 * DDA_WAVES), 0, fs, ctx->d_frames, dm, ctx->cam, D, Hp, Dp,
-                             cv_rule ? 1 : 0, sc);
-        }
+        hipLaunchKernelGGL(k_fov_dda, dgrid, dim3(64 * DDA_WAVES), 0, fs, ctx->d_frames, dm, ctx->cam, D, Hp, Dp, cv_rule ? 1 : 0, sc);      // the walk, a lane per slot
         const dim3 lgrid(imin((int)grid.x, 8), n);           // the list is short: a few workgroups per frame walk it, in float64
         if (dm.He <= 384)
           hipLaunchKernelGGL((k_fov_spans<6, true>), lgrid, dim3(256), 0, fs, ctx->d_frames, dm, ctx->cam, D, Hp, Dp, 0, cv_rule ? 1 : 0, sc);
@@ -6377,6 +6543,9 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->sc.list_rot);
   hipFree(ctx->sc.fov_erec);
   hipFree(ctx->sc.fov_pix);
+  hipFree(ctx->sc.fov_rec);
+  hipFree(ctx->sc.fov_order);
+  hipFree(ctx->sc.fov_slot);
   hipFree(ctx->sc.rows_list);
   hipFree(ctx->sc.rows_sorted);
   hipFree(ctx->sc.rows_n);
@@ -7933,6 +8102,7 @@ int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value) {
       return RR_OK;
     case RR_OPT_FOV_FILL_RULE: ctx->fill_rule = value == 1 ? 1 : 0; return RR_OK;
     case RR_OPT_FOV_DDA: ctx->fov_dda = value != 0 ? 1 : 0; return RR_OK;       // (2 was k_fov_walk, r05: measured, no faster, removed in r06)
+    case RR_OPT_FOV_ORDER: ctx->fov_order = value != 0 ? 1 : 0; return RR_OK;
     case RR_OPT_PIPELINE_F32: ctx->pipe_f32 = value != 0; return RR_OK;
     case RR_OPT_WILD_PIXELS: ctx->wild_pixels = value != 0; return RR_OK;
     case RR_OPT_PNG_DEFLATE: ctx->png_deflate = value != 0; return RR_OK;

@@ -37,6 +37,7 @@ RR_OPT_COLOUR_STREAM = 21
 RR_OPT_TILE_ROWS = 22
 RR_OPT_ROWS_SHARES = 23
 RR_OPT_FIELD_CHUNKS = 24
+RR_OPT_FOV_ORDER = 25
 RR_PARTICLES_IID, RR_PARTICLES_FIELD, RR_PARTICLES_RIG = 0, 1, 2      # rr_set_particle_model
 PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD, 'rig': RR_PARTICLES_RIG}
 RR_DRAWS_STREAM, RR_DRAWS_COUNTER = 0, 1                              # rr_set_particle_draws
