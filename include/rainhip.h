@@ -433,6 +433,27 @@ int rr_sizeof_rig_view(void);
 enum { RR_DRAWS_STREAM = 0, RR_DRAWS_COUNTER = 1 };
 int rr_set_particle_draws(rr_ctx* ctx, int32_t mode);
 
+/* Streak jitter: every drop of the records the context generates from now on gets a tilt of its own (every entry point that
+ * takes rr_sim_frame records, every particle model, both draw modes).  It is NOT the reference's angular noise
+ * (rr_set_particle_noise), whose deviates come from a run's sequential stream: here
+ *     g = sqrt(-2 det_log(u1)) cos(2 pi u2)   -- Box-Muller on the drop's Philox block 3 under the frame's key: counter
+ *         (i, frame, 3, 0) under RR_PARTICLES_IID, the life's block (j, g_lo, 3, 2 + g_hi) under RR_PARTICLES_FIELD and
+ *         RR_PARTICLES_RIG (no other draw reads a block 3); u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 1) 2^-53 in (0, 1],
+ *         u2 = (w2 + 1/2) 2^-32; a standard normal deviate, |g| < 8.6;
+ *     after the derived fields and the frame filter (both on the unturned end points) every kept non-Big record is turned by
+ *     jitter_deg * g degrees the way the angular noise turns one: rotation terms cos / sin(-(theta + angle)) by the angle sum
+ *     with det_sincos, end points about their midpoint, truncated toward zero.  Big drops are untouched.
+ * The kept set, the counts, length, max_width, tex_index and the world positions do not depend on it; a streak turned to zero
+ * length gets NaN rotation terms, as under the angular noise.  Under the field and rig models g is a function of
+ * (key, slot, life): a drop keeps its tilt in every frame of its life and in every view of the rig.  The particle kernels do
+ * it themselves (kept lanes only): no further launch.  tools/particles.py expected_records(jitter=) states the records bit
+ * for bit.  jitter_deg = 0 (default): off, the records and the kernels are those without it.
+ * RR_E_ARG: jitter_deg negative or not finite; a non-zero jitter while angular noise is on, likewise turning the noise on
+ * (rr_set_particle_noise) while the jitter is on; and, when generating with the jitter on, a record with run_pos != 0.
+ * rr_augment_frames_device accepts a context with the jitter on.  Call it between runs, with no call of the generator in
+ * flight. */
+int rr_set_particle_jitter(rr_ctx* ctx, double jitter_deg);
+
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`
@@ -444,8 +465,8 @@ int rr_set_particle_draws(rr_ctx* ctx, int32_t mode);
  * and then waits on `stream` for the 4-byte arena-overflow flag: when the tile arena had to grow, the batch is enqueued once more.
  * So the call returns after the batch is complete -- a host wait on the caller's stream.  For the same records and input values
  * the result is bit for bit what rr_pipeline_frames gives: rainy_out bytes == rainy_rgb (planar), float32 rainy_out == those
- * bytes / 255.0f (what ToTensor makes of the PNG the driver writes).  Not offered: angular noise (run_pos must be 0), the 'white'
- * strategy, opacity attenuation.  Needs the streak database, camera, pre-pass kernels, particle tables, the envmap geometry of
+ * bytes / 255.0f (what ToTensor makes of the PNG the driver writes).  Not offered: angular noise (run_pos must be 0; the streak
+ * jitter of rr_set_particle_jitter is), the 'white' strategy, opacity attenuation.  Needs the streak database, camera, pre-pass kernels, particle tables, the envmap geometry of
  * H x W and the solid angles of the H x rr_envmap_width() map (rr_set_solid_angles).  The caller's current device is restored.
  * Scratch in the context, grown to the largest batch seen and never shrunk, per frame about
  *     3 H W (bytes; 12 H W for float32) + 12 H W (fog layer) + 12 H We (map) + 8 H W (mask) + 112 drops_cap  bytes

@@ -26,11 +26,16 @@ stream (tools/particles.py, `main.py --particle_draws counter`): under 'field' a
 frame of its life and in every view, and the device skips its one serial pass (0.15 ms of a KITTI 25 mm/hr call).  The frames are those of
 a `--particle_draws counter` run; 'stream' remains the mode that matches a run that writes the reference's files.
 
+`jitter=DEG` (default 0: off) turns every streak by DEG degrees times a standard normal deviate of the drop's own, taken from the
+drop's Philox counter (tools/particles.py counter_jitter, `main.py --streak_jitter DEG`): streaks no longer all line up with the
+projected fall direction, and under 'field' and 'rig' a drop keeps its tilt in every frame of its life and in every view.  It works
+with every particle model and both draws, inside the particle kernels: no further pass on the device.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
-angular noise (it depends on the order of a run, which random access does not have), the 'white' strategy and opacity
-attenuation.
+the 'white' strategy and opacity attenuation.  The reference's `--noise_std` depends on the order of a run, which random access
+does not have: `jitter` is the per-drop tilt that random access, moving particles and shared views can have.
 
 This module imports torch; the package's __init__ does not."""
 import numbers
@@ -82,13 +87,16 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream'):
+                 rig=None, views=None, draws='stream', jitter=0.0):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
         if draws not in particles.DRAWS:
             raise ValueError("draws %r: expected one of %s" % (draws, ', '.join(particles.DRAWS)))
         self.draws = draws
+        if isinstance(jitter, bool) or not isinstance(jitter, numbers.Number) or not np.isfinite(jitter) or jitter < 0:
+            raise ValueError("jitter %r: expected a finite number of degrees >= 0" % (jitter,))
+        self.jitter = float(jitter)
         if (particle_model == 'rig') != (rig is not None):
             raise ValueError("particle_model='rig' and rig= go together (rig.Rig)")
         if rig is None and views is not None:
@@ -158,7 +166,8 @@ class RainAugment:
 
     def plan(self, intensity, frame_index, B=None):
         """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
-        union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key).  Under the
+        union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key, particle_model,
+        cam_hz, draws, jitter: what expected_records needs to state the call's drop tables).  Under the
         rig model B counts instants: sims and fog hold V = len(views) consecutive entries per instant (view views[i % V] of
         instant i // V), plus views, rig_views and rig_box (what rr_set_particle_rig gets)."""
         if B is None:
@@ -187,7 +196,7 @@ class RainAugment:
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
         out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
-                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws)
+                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
             out.update(sims=np.repeat(sims, V), fog=np.repeat(fog, V, axis=0), views=list(self.views),
@@ -236,6 +245,7 @@ class RainAugment:
                 hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])
             hip.set_particle_model(self.particle_model, self.options["cam_hz"])
             hip.set_particle_draws(self.draws)
+            hip.set_particle_jitter(self.jitter)
             self._hip, self.device = hip, dev
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)

@@ -97,6 +97,14 @@ class Generator:
         if self.particle_draws != 'stream' and bool(self.noise_std):
             raise ValueError("--noise_std cannot be combined with --particle_draws counter: the angular noise needs the stream's normal "
                              "deviates and the order of the run")
+        self.streak_jitter = float(getattr(args, 'streak_jitter', 0.0) or 0.0)        # degrees per unit of the drop's own normal deviate
+        if not np.isfinite(self.streak_jitter) or self.streak_jitter < 0:
+            raise ValueError("--streak_jitter %r: expected a finite number of degrees >= 0" % (self.streak_jitter,))
+        if self.streak_jitter and not self.device_particles:
+            raise ValueError("--streak_jitter needs --device_particles")
+        if self.streak_jitter and bool(self.noise_std):
+            raise ValueError("--streak_jitter cannot be combined with --noise_std: the jitter is a function of the drop, the angular "
+                             "noise of the order of the run")
         self.sim_options = getattr(args, 'sim_options', {})
         self.batch = int(os.environ.get('RAIN_BATCH', '128'))     # frames per library call (three calls in flight); bench.py's host-inclusive leg uses the same
         self.rank, self.world = sharding.rank_world()
@@ -440,6 +448,9 @@ class Generator:
                     if self.particle_draws != 'stream':          # (the noise is off: refused above)
                         hip.set_particle_noise(0.0, 0.0)
                     hip.set_particle_draws(self.particle_draws)
+                    if self.streak_jitter:                       # (likewise)
+                        hip.set_particle_noise(0.0, 0.0)
+                    hip.set_particle_jitter(self.streak_jitter)
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)

@@ -4661,10 +4661,15 @@ __global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int6
 // CTR (rr_set_particle_draws RR_DRAWS_COUNTER; also a parameter of k_field_particles and k_rig_particles): the record leaves
 // with its FINAL tex_index -- the block's first texture plus rrsim::texture_pick of the word the generator already has
 // (word 2 of the drop's Philox block 1) -- and no k_particle_draws follows.  CTR = false is the kernel as it was.
+// JIT (rr_set_particle_jitter; also a parameter of the store passes of k_field_particles and k_rig_particles): a lane whose
+// record is kept and non-Big makes the drop's Philox block 3, its normal deviate (rrsim::jitter_deviate) and turns the record
+// by jitter_deg * g (rrsim::noise_rotate) before it is staged: after the cull and the filter, so only kept lanes pay, and the
+// counts do not depend on it.  JIT = false is the kernel as it was (jitter_deg is not read).
 constexpr int DROP_DW = (int)(sizeof(rr_drop) / 4);
-template <bool CTR>
+template <bool CTR, bool JIT>
 __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int H, int W, const double* dgrid, const double* cdf_tabs,
-                                                    int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run) {
+                                                    int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run,
+                                                    double jitter_deg) {
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   if (skip_run && sims[f].run_pos != 0) return;               // angular noise: k_noise_chains makes this frame
   __shared__ rr_sim_frame s_sf;
@@ -4691,6 +4696,8 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
       keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
       d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
       if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
+      if constexpr (JIT)
+        if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::particle_jitter(sf, (uint32_t)i));
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_cnt[wave] = __popcll(bal);
@@ -4727,10 +4734,11 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
 // pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
 // twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
 // batches fill the chip by themselves) there is no count pass.
-template <bool COUNT, bool CTR>
+template <bool COUNT, bool CTR, bool JIT>
 __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
                                                           const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
-                                                          int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
+                                                          int32_t* n_out, int32_t* chunk_cnt, int chunk_slots, double jitter_deg) {
+  static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   const int f = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   __shared__ rr_sim_frame s_sf;
   __shared__ int s_cnt[8];
@@ -4763,6 +4771,8 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
         d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
         if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
+        if constexpr (JIT)
+          if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::life_jitter(sf, (uint32_t)j, life));
       }
     }
     const unsigned long long bal = __ballot(keep);
@@ -4814,10 +4824,12 @@ struct RigViews {                    // the ACTIVE views in batch order, and the
   double box[3];
   int n_active;
 };
-template <bool COUNT, bool CTR>
+template <bool COUNT, bool CTR, bool JIT>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
-                                                        rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots) {
+                                                        rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots,
+                                                        double jitter_deg) {
+  static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int na = rv.n_active;
@@ -4865,6 +4877,8 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
           keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
           d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
           if constexpr (CTR) d.tex_index += pick;             // one pick for every view of the slot
+          if constexpr (JIT)                                  // one tilt for every view: made here from (j, life), not carried
+            if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::life_jitter(sf, (uint32_t)j, q.life));
         }
       }
       const unsigned long long bal = __ballot(keep);
@@ -5233,6 +5247,7 @@ struct rr_ctx {
   // the field model (rr_set_particle_model, k_field_particles)
   int particle_model = RR_PARTICLES_IID;
   int particle_draws = RR_DRAWS_STREAM;   // rr_set_particle_draws: the texture pick from numpy's stream, or from the drop's own counter
+  double jitter_deg = 0.0;                // rr_set_particle_jitter: degrees per unit of the drop's own normal deviate; 0: none
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
@@ -6291,8 +6306,8 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   if (m > 0) {                       // pristine streaks of the fresh states: filtered, tex_index = first texture of the block of ten
     ProfScope ps(ctx, s, "k_particles");
     rr_drop* P = ctx->noise_states[fresh_id[0]].pristine;
-    hipLaunchKernelGGL(k_particles<false>, dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
-                       ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P, stride, ctx->noise_states[fresh_id[0]].n_pristine, 0);
+    hipLaunchKernelGGL((k_particles<false, false>), dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
+                       ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P, stride, ctx->noise_states[fresh_id[0]].n_pristine, 0, 0.0);
   }
   {
     ProfScope ps(ctx, s, "k_noise_chains");
@@ -6350,10 +6365,16 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     }
   }
   const bool ctr = ctx->particle_draws == RR_DRAWS_COUNTER;
+  const bool jit = ctx->jitter_deg != 0.0;
   int n_noisy = 0;
   for (int f = 0; f < n; f++) {
     const rr_sim_frame& sf = sims[f];
     if (sf.run_pos == 0) continue;
+    if (jit) {
+      ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
+                 "): the streak jitter (rr_set_particle_jitter) is a function of the drop, not of a run's order; run_pos must be 0";
+      return RR_E_ARG;
+    }
     if (ctr) {
       ctx->err = "rr_sim_frame.run_pos " + std::to_string(sf.run_pos) + " (frame " + std::to_string(f) +
                  "): angular noise needs the stream's deviates and run order; it is not defined under RR_DRAWS_COUNTER (rr_set_particle_draws)";
@@ -6423,20 +6444,26 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       ProfScope ps(ctx, s, "k_rig_particles");
       auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg);
       };
-      if (chunks > 1) launch(k_rig_particles<true, false>);   // (a count does not depend on the draws)
-      if (ctr) launch(k_rig_particles<false, true>);
-      else launch(k_rig_particles<false, false>);
+      if (chunks > 1) launch(k_rig_particles<true, false, false>);   // (a count depends neither on the draws nor on the jitter)
+      if (jit) {
+        if (ctr) launch(k_rig_particles<false, true, true>);
+        else launch(k_rig_particles<false, false, true>);
+      } else if (ctr) launch(k_rig_particles<false, true, false>);
+      else launch(k_rig_particles<false, false, false>);
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
       auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots);
+                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg);
       };
-      if (chunks > 1) launch(k_field_particles<true, false>);
-      if (ctr) launch(k_field_particles<false, true>);
-      else launch(k_field_particles<false, false>);
+      if (chunks > 1) launch(k_field_particles<true, false, false>);
+      if (jit) {
+        if (ctr) launch(k_field_particles<false, true, true>);
+        else launch(k_field_particles<false, false, true>);
+      } else if (ctr) launch(k_field_particles<false, true, false>);
+      else launch(k_field_particles<false, false, false>);
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
@@ -6445,12 +6472,15 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
   } else if (n_noisy < n) {                                  // frames with angular noise are left to k_noise_chains
     {
       ProfScope ps(ctx, s, "k_particles");
-      if (ctr)
-        hipLaunchKernelGGL(k_particles<true>, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, 0);
-      else
-        hipLaunchKernelGGL(k_particles<false>, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
+      auto launch = [&](auto kern, int skip_run) {
+        hipLaunchKernelGGL(kern, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out,
+                           cap, n_out, skip_run, ctx->jitter_deg);
+      };
+      if (jit) {                                             // (no frame has run_pos != 0 under the jitter)
+        if (ctr) launch(k_particles<true, true>, 0);
+        else launch(k_particles<false, true>, 0);
+      } else if (ctr) launch(k_particles<true, false>, 0);
+      else launch(k_particles<false, false>, n_noisy > 0 ? 1 : 0);
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
@@ -7053,6 +7083,11 @@ int rr_set_particle_noise(rr_ctx* ctx, double noise_std, double noise_scale, int
                "(rr_set_particle_draws)";
     return RR_E_ARG;
   }
+  if (ctx->jitter_deg != 0.0 && noise_std != 0.0 && noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_noise: angular noise cannot be combined with the streak jitter; turn the jitter off first "
+               "(rr_set_particle_jitter with 0)";
+    return RR_E_ARG;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   if ((rc = noise_states_drop(ctx))) return rc;
@@ -7107,6 +7142,21 @@ int rr_set_particle_draws(rr_ctx* ctx, int32_t mode) {
     return RR_E_ARG;
   }
   ctx->particle_draws = mode;
+  return RR_OK;
+}
+
+int rr_set_particle_jitter(rr_ctx* ctx, double jitter_deg) {
+  if (!ctx) return RR_E_ARG;
+  if (!std::isfinite(jitter_deg) || jitter_deg < 0.0) {
+    ctx->err = "rr_set_particle_jitter: the jitter is a finite number of degrees >= 0";
+    return RR_E_ARG;
+  }
+  if (jitter_deg != 0.0 && ctx->noise_std != 0.0 && ctx->noise_scale != 0.0) {
+    ctx->err = "rr_set_particle_jitter: the streak jitter cannot be combined with angular noise; turn the noise off first "
+               "(rr_set_particle_noise with noise_std 0)";
+    return RR_E_ARG;
+  }
+  ctx->jitter_deg = jitter_deg;
   return RR_OK;
 }
 

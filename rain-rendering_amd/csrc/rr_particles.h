@@ -337,6 +337,35 @@ RR_HD void noise_rotate(rr_drop& d, double noise_deg) {
   d.y1 = (int32_t)(int64_t)(((ex - mx) * sn + (ey - my) * cn) + my);
 }
 
+// ---- streak jitter (rr_set_particle_jitter, tools/particles.py counter_jitter): a normal deviate of the drop's own ----
+// Box-Muller on three words of the drop's Philox block 3: u1 has 53 bits in (0, 1] (every step exact), u2 = unit32(w2),
+// g = sqrt(-2 det_log(u1)) cos(2 pi u2): + - * / sqrt, det_log and det_sincos only.  |g| < 8.6; u1 = 1 gives 0.
+RR_HD double jitter_deviate(const uint32_t w[4]) {
+  const double u1 = (((double)(w[0] >> 5) * 67108864.0 + (double)(w[1] >> 6)) + 1.0) * (1.0 / 9007199254740992.0);
+  double sn, cn;
+  rr::det_sincos(6.283185307179586 * unit32(w[2]), sn, cn);
+  return sqrt(-2.0 * rr::det_log(u1)) * cn;
+}
+// Block 3 of the drop under the frame's key.  The generators read blocks 0, 1 and 2 of a counter (make_particle:
+// (i, frame, 0 | 1 | 2, 0); the field and rig models: (j, 0, 0, 1) and the life's (j, g_lo, 1 | 2, 2 + g_hi)); nothing else
+// reads a block 3.  i.i.d. model: particle i of frame sf.frame.
+RR_HD double particle_jitter(const rr_sim_frame& sf, uint32_t i) {
+  uint32_t w[4] = {i, sf.frame, 3u, 0u};
+  philox4x32_10(w, sf.key0, sf.key1);
+  return jitter_deviate(w);
+}
+// field and rig models: slot j in its life g -- the same tilt in every frame of the life and in every view
+RR_HD double life_jitter(const rr_sim_frame& sf, uint32_t j, double life) {
+  const double g_hi = floor(life * (1.0 / 4294967296.0)), g_lo = life - g_hi * 4294967296.0;
+  uint32_t w[4] = {j, (uint32_t)g_lo, 3u, 2u + (uint32_t)g_hi};
+  philox4x32_10(w, sf.key0, sf.key1);
+  return jitter_deviate(w);
+}
+// a kept record turned by jitter_deg * g degrees (noise_rotate); Big drops are left alone
+RR_HD void jitter_drop(rr_drop& d, double jitter_deg, double g) {
+  if (d.type != 0) noise_rotate(d, jitter_deg * g);
+}
+
 // the block of ten textures take_drop_texture draws from (bad_weather.py:250-265): NaN falls through to the last one
 RR_HD int texture_bucket(double ratio, const double* ratio_db) {
   int b = 4;

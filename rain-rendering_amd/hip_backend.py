@@ -154,7 +154,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws']
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter']
 
 _lib = None
 
@@ -252,6 +252,7 @@ def load_library(path=None):
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_set_particle_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
     lib.rr_set_particle_draws.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    lib.rr_set_particle_jitter.argtypes = [ctypes.c_void_p, ctypes.c_double]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
@@ -863,6 +864,12 @@ class RainHip:
         if draws not in PARTICLE_DRAWS:
             raise ValueError("particle draws %r: expected one of %s" % (draws, ', '.join(PARTICLE_DRAWS)))
         self._check(self.lib.rr_set_particle_draws(self.h, PARTICLE_DRAWS[draws]), 'rr_set_particle_draws')
+
+    def set_particle_jitter(self, deg=0.0):
+        """rr_set_particle_jitter: every kept non-Big streak is turned by deg x a standard normal deviate of the drop's own
+        (tools/particles.counter_jitter: Philox block 3 of the drop; one tilt over a drop's life and across a rig's views), by
+        the particle kernels themselves.  0 (default): off.  Every model, both draws; not together with angular noise."""
+        self._check(self.lib.rr_set_particle_jitter(self.h, float(deg)), 'rr_set_particle_jitter')
 
     def set_particle_rig(self, views, box, active=None):
         """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =

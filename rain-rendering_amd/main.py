@@ -9,6 +9,7 @@ Missing particle files are produced by this build's own generator (tools/particl
 reference would start its external, closed-source simulator."""
 import argparse
 import glob
+import math
 import os
 import sys
 import warnings
@@ -65,6 +66,10 @@ _FLAGS = [
                                       "like the reference; 'counter' takes the pick from the drop's own random counter: a drop keeps its "
                                       "texture over its life (--particle_model field) and across the views of a rig, and the GPU skips its "
                                       "one serial pass (not with --noise_std)")),
+    (('--streak_jitter',), dict(type=float, default=0.0,
+                                help="with --device_particles: turn every streak by DEG degrees times a standard normal deviate of the "
+                                     "drop's own (from its random counter: a drop keeps its tilt over its life and across the views of a "
+                                     "rig); any --particle_model and --particle_draws; 0: off (not with --noise_std)")),
     (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
                                                    "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
     (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
@@ -98,6 +103,15 @@ def _derive(ns):
         if ns.noise_std:
             raise SystemExit("--noise_std cannot be combined with --particle_draws counter: the angular noise needs the stream's normal "
                              "deviates and the order of the run")
+    jitter = getattr(ns, 'streak_jitter', 0.0) or 0.0
+    if not math.isfinite(jitter) or jitter < 0:
+        raise SystemExit("--streak_jitter %r: expected a finite number of degrees >= 0" % (jitter,))
+    if jitter:
+        if not ns.device_particles:
+            raise SystemExit("--streak_jitter needs --device_particles (the jitter is made by the GPU's particle generator)")
+        if ns.noise_std:
+            raise SystemExit("--streak_jitter cannot be combined with --noise_std: the jitter is a function of the drop, the angular "
+                             "noise of the order of the run")
     ns.verbose = not ns.noverbose
     light_db = _J(ns.streaks_db, 'env_light_database')
     ns.texture = _J(light_db, 'size32')

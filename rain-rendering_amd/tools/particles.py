@@ -69,6 +69,15 @@ function of (seed, slot, life): a drop keeps its texture in every frame of its l
 ratio BUCKET comes from the projected size and can still differ between frames or views).  Under the i.i.d. model it is a
 function of (seed, frame, particle index).  ``draw_seed`` is ignored.  Angular noise needs the stream's normal deviates
 and run order and is refused with counter draws.
+
+Streak jitter (``jitter=DEG``, ``rr_set_particle_jitter`` in the library; ``counter_jitter``).  Every drop has a standard normal
+deviate g of its own: Box-Muller on its Philox block 3 -- (i, frame, 3, 0), or the life's block (j, g_lo, 3, 2 + g_hi) under the
+field and rig models; the generators read blocks 0 .. 2 (and (j, 0, 0, 1) for a slot), nothing else reads block 3.  After
+the loader's derived fields and the frame filter, every kept non-Big streak is turned by ``jitter * g`` degrees the way the
+angular noise turns one (``noise_rotation``: rotation terms by the angle sum, end points about the midpoint, truncated).  The
+kept set, sizes, texture and world positions do not depend on it.  Under the field and rig models g is a function of
+(seed, slot, life): a drop keeps its tilt in every frame of its life and in every view.  It is not ``--noise_std`` (whose
+deviates come from the run's sequential stream) and is refused together with it.
 """
 import os
 
@@ -366,6 +375,58 @@ def counter_picks(seed, pid, frame=None, life=None):
     g_hi = np.floor(g * (1.0 / 4294967296.0))
     g_lo = g - g_hi * 4294967296.0
     return texture_pick(philox4x32(j, g_lo.astype(np.uint64), 1, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)[2])
+
+
+def jitter_deviate(w0, w1, w2):
+    """rr_particles.h jitter_deviate: a standard normal deviate from three 32-bit words by Box-Muller.  u1 has 53 bits in
+    (0, 1] (every step exact), u2 = unit32(w2); g = sqrt(-2 det_log(u1)) * cos(2 pi u2) with det_log / det_sincos: + - * / sqrt
+    only, the same bits in numpy, g++ and on gfx950.  |g| <= sqrt(2 * 53 * ln 2) < 8.6; u1 = 1 gives 0."""
+    a = (np.asarray(w0).astype(np.uint64) >> np.uint64(5)).astype(np.float64)
+    b = (np.asarray(w1).astype(np.uint64) >> np.uint64(6)).astype(np.float64)
+    u1 = ((a * 67108864.0 + b) + 1.0) * (1.0 / 9007199254740992.0)
+    _, cn = det_sincos(6.283185307179586 * unit32(w2))
+    return np.sqrt(-2.0 * det_log(u1)) * cn
+
+
+def counter_jitter(seed, pid, frame=None, life=None):
+    """The streak-jitter deviate (standard normal) of particles `pid`: jitter_deviate of the drop's Philox block 3, which no
+    other draw reads.  i.i.d. model: `frame` = the simulated frame, block (pid, frame, 3, 0).  Field and rig models: `life` = the
+    life g of every slot `pid`, block (pid, g_lo, 3, 2 + g_hi) -- laid out like the life's blocks 1 and 2."""
+    j = np.asarray(pid).astype(np.uint64)
+    k0, k1 = _key(seed)
+    if life is None:
+        w = philox4x32(j, int(frame) & 0xFFFFFFFF, 3, 0, k0, k1)
+    else:
+        g = np.asarray(life, np.float64)
+        g_hi = np.floor(g * (1.0 / 4294967296.0))
+        g_lo = g - g_hi * 4294967296.0
+        w = philox4x32(j, g_lo.astype(np.uint64), 3, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)
+    return jitter_deviate(w[0], w[1], w[2])
+
+
+def _check_jitter(jitter, noisy=False, run=None):
+    jitter = float(jitter)
+    if not np.isfinite(jitter) or jitter < 0:
+        raise ValueError("streak jitter %r: expected a finite number of degrees >= 0" % jitter)
+    if jitter and (noisy or run is not None):
+        raise ValueError("streak jitter cannot be combined with angular noise (noise_std / noise_scale / run): the jitter is a "
+                         "function of the drop, the noise of the run's order")
+    return jitter
+
+
+def jitter_records(rec, g, jitter):
+    """Turn the kept non-Big records of one frame (DROP_DTYPE, in place) by jitter * g degrees: rr_particles.h noise_rotate on
+    each.  `g`: the deviate of every record.  Big records are left alone; a streak of zero length gets NaN rotation terms."""
+    nb = rec['type'] != 0
+    if not nb.any():
+        return rec
+    s = np.stack([rec['x0'], rec['y0']], axis=1)
+    e = np.stack([rec['x1'], rec['y1']], axis=1)
+    rot_cos, rot_sin, s2, e2 = noise_rotation(s, e, float(jitter) * np.asarray(g, np.float64))
+    rec['rot_cos'][nb], rec['rot_sin'][nb] = rot_cos[nb], rot_sin[nb]
+    rec['x0'][nb], rec['y0'][nb] = s2[nb, 0], s2[nb, 1]
+    rec['x1'][nb], rec['y1'][nb] = e2[nb, 0], e2[nb, 1]
+    return rec
 
 
 def _check_model(model):
@@ -817,10 +878,10 @@ def field_run_sims(sims, f_idx):
     return out
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream'):
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
-    texture pick of every row (counter_picks of the row's particle)."""
+    texture pick of every row (counter_picks of the row's particle); with `jitter`, `jitter_g`: the row's counter_jitter."""
     from ..common import bad_weather as bw
     cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
                                speed=float(s['speed_mps'])))()
@@ -847,11 +908,14 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
     if draws == 'counter':
         picks = counter_picks(seed, rec['pid'], int(s['frame']), life)
         table.pick = picks[np.searchsorted(rec['pid'], table.pid)]      # (pid ascends: particle index, or slot)
+    if jitter:
+        gs = counter_jitter(seed, rec['pid'], int(s['frame']), life)
+        table.jitter_g = gs[np.searchsorted(rec['pid'], table.pid)]
     return table, m, W, H
 
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
-                     rig=None, view=None, draws='stream'):
+                     rig=None, view=None, draws='stream', jitter=0.0):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -871,10 +935,15 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     records that are all of that view.
 
     draws='counter' (rr_set_particle_draws RR_DRAWS_COUNTER): the same records with tex_index = 10 * texture_bucket(ratio) +
-    counter_picks of the drop instead of the stream's randint; draw_seed is ignored; no angular noise, no run_pos."""
+    counter_picks of the drop instead of the stream's randint; draw_seed is ignored; no angular noise, no run_pos.
+
+    jitter=DEG (rr_set_particle_jitter; every model, both draws): the records above, then every kept non-Big one turned by
+    DEG * counter_jitter of its drop (jitter_records).  jitter=0: the records above.  Not with noise_std / noise_scale / run, and
+    run_pos must be 0."""
     from .. import hip_backend
     _check_model(model)
     noisy = bool(noise_std) and bool(noise_scale)
+    jitter = _check_jitter(jitter, noisy, run)
     _check_draws(draws, noisy)
     if model in ('field', 'rig') and (noisy or cam_hz is None):
         raise ValueError("the %s model needs cam_hz and has no angular noise" % model)
@@ -887,8 +956,18 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter)
         p = int(s['run_pos'])
+        if jitter:
+            if p != 0:
+                raise ValueError("streak jitter: run_pos must be 0 (frame %d)" % i)
+            rec = hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact')
+            keep = hip_backend.filter_streaks(table, W, H)
+            assert len(keep) == len(rec)
+            if draws == 'counter':
+                rec['tex_index'] = 10 * m.texture_bucket(table.ratio[keep]) + table.pick[keep]
+            out.append(jitter_records(rec, table.jitter_g[keep], jitter))
+            continue
         if draws == 'counter':
             if p != 0:
                 raise ValueError("counter draws: run_pos must be 0 (frame %d)" % i)

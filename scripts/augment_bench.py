@@ -3,7 +3,8 @@
 frames/s of a whole call at B = 8, 32, 128 KITTI-sized frames (1242 x 375) at 25 mm/hr for uint8 and float32 batches, the time
 of the two tensor-layout kernels (k_planar_in, k_finalize_planar) per frame from rr_profile_read, and the host time per call
 spent outside the GPU (input checks, record building, descriptor).  Synthetic streak database and images.  --draws counter times
-RainAugment(draws='counter') (the texture pick from the drop's own counter: no k_particle_draws pass) in every leg."""
+RainAugment(draws='counter') (the texture pick from the drop's own counter: no k_particle_draws pass) in every leg; --jitter DEG
+times RainAugment(jitter=DEG) (the per-drop streak jitter, made by the particle kernels)."""
 import argparse
 import importlib
 import json
@@ -32,18 +33,19 @@ def main():
                     help="also time RainAugment(particle_model='rig') for this rig ('stereo:0.54' or a JSON file) at 32 frames per call "
                          "(uint8, 32 / V instants); adds the key rig (frames/s over --steps calls)")
     ap.add_argument('--draws', default='stream', choices=['stream', 'counter'], help="RainAugment(draws=...) of every leg")
+    ap.add_argument('--jitter', type=float, default=0.0, metavar='DEG', help="RainAugment(jitter=...) of every leg (0: off)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
     synthetic = importlib.import_module('rain-rendering_amd.synthetic')
     augment = importlib.import_module('rain-rendering_amd.augment')
     dev = torch.device('cuda', 0)
-    out = dict(workload='RainAugment kitti %g mm/hr' % args.intensity, draws=args.draws, steps=args.steps, fps={}, kernel_ms_per_frame={},
+    out = dict(workload='RainAugment kitti %g mm/hr' % args.intensity, draws=args.draws, jitter=args.jitter, steps=args.steps, fps={}, kernel_ms_per_frame={},
                host_ms_per_call={})
     with tempfile.TemporaryDirectory() as tmp:
         db = os.path.join(tmp, 'rainstreakdb')
         synthetic.write_streak_db(db)
-        aug = augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', draws=args.draws)
+        aug = augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', draws=args.draws, jitter=args.jitter)
         H, W = aug.frame_size()
         Bmax = max(int(b) for b in args.batches.split(','))
         base = np.stack([(synthetic.make_frame(i, H, W)[..., ::-1] * 255).astype(np.uint8) for i in range(8)])
@@ -86,7 +88,7 @@ def main():
         aug.close()
         if args.compare_models > 0:
             B = min(32, Bmax)
-            augs = {m: augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model=m, draws=args.draws) for m in ('iid', 'field')}
+            augs = {m: augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model=m, draws=args.draws, jitter=args.jitter) for m in ('iid', 'field')}
             rates = {m: [] for m in augs}
             k0 = 0
             for r in range(args.warmup + args.compare_models):
@@ -107,7 +109,7 @@ def main():
             rig = importlib.import_module('rain-rendering_amd.rig').Rig.from_spec(args.rig)
             V = len(rig)
             Bi = max(min(32, Bmax) // V, 1)
-            a = augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model='rig', rig=rig, draws=args.draws)
+            a = augment.RainAugment('kitti', streaks_db=db, sequence='data_object/training', particle_model='rig', rig=rig, draws=args.draws, jitter=args.jitter)
             x = img8[:Bi * V].reshape(Bi, V, 3, H, W)
             d = depth[:Bi * V].reshape(Bi, V, H, W)
             for r in range(args.warmup + 1):

@@ -1,0 +1,317 @@
+"""CPU tier: per-drop streak jitter (tools/particles.py counter_jitter / expected_records(jitter=), rr_particles.h jitter_deviate /
+particle_jitter / life_jitter, rr_set_particle_jitter) -- every drop is turned by jitter x a normal deviate of its own counter.
+
+  1. the g++ build of the RR_HD statement (tests/hostemu/jitter_emu.cpp: the code the JIT kernels run) == numpy, bit for bit, for
+     the i.i.d., field and rig models and both draws;
+  2. what the jitter does not touch: the kept set, every field but the end points and the rotation terms, Big records;
+  3. coherence: a field slot keeps its deviate from frame k to k + 1 inside one life, a rig slot in both stereo views; other lives
+     and other slots have other deviates; the stream noise turns one drop differently in two frames (the control);
+  4. law: Kolmogorov-Smirnov against N(0, 1), |g| <= 8.6, det_log / det_sincos on the deviate's domain;
+  5. every refusal of the Python layer and of the driver's argument handling;  6. RainAugment.plan carries the jitter."""
+import ctypes
+import importlib
+import math
+import os
+
+import numpy as np
+import pytest
+
+import helpers as h
+from test_particle_draws_host import KITTI_STEREO, MODEL_ID, _kept, _options, _p, _run
+from test_particle_noise_host import _ulp
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+db = importlib.import_module('rain-rendering_amd.common.db')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+JITTER = 5.0
+KS_C = 1.95                 # tests/test_particle_field_host.py _same_law: P(sqrt(n) D > 1.95) = 1e-3 for a sample of the law
+TURNED = ('x0', 'y0', 'x1', 'y1', 'rot_cos', 'rot_sin')
+
+
+@pytest.fixture(scope='module')
+def emu(built):
+    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libjitteremu.so'))
+    V, I, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
+    lib.rr_emu_jitter_deviates.argtypes = [V, I, V, V, V]
+    lib.rr_emu_jitter_records.argtypes = [I, I, D, V, D, V, V, V, V, I, I, I, V, V, V, I]
+    lib.rr_emu_jitter_records.restype = I
+    return lib
+
+
+def _same_field(a, b):
+    """Bytes equal; NaN rotation terms are compared as NaN (their sign and payload are the machine's)."""
+    if a.dtype.kind == 'f':
+        return a.shape == b.shape and bool(np.all((_ulp(a, b) == 0) | (np.isnan(a) & np.isnan(b))))
+    return a.tobytes() == b.tobytes()
+
+
+def _turn_deg(rec, plain):
+    """The angle (degrees) every non-Big record of `rec` was turned by, from its rotation terms and those of the unturned record
+    `plain`: the terms are the angle sum c0 cn + s0 sn, s0 cn - c0 sn of the unturned (c0, s0) and the turn's (cn, sn)."""
+    nb = plain['type'] != 0
+    c0, s0, rc, rs = plain['rot_cos'][nb], plain['rot_sin'][nb], rec['rot_cos'][nb], rec['rot_sin'][nb]
+    return np.degrees(np.arctan2(s0 * rc - c0 * rs, c0 * rc + s0 * rs)), nb
+
+
+# ---- 1. g++ == numpy -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("model", ['iid', 'field', 'rig'])
+def test_gxx_build_equals_numpy(tmp_path, emu, model):
+    sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
+    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    hz = float(opt['cam_hz'])
+    rig = KITTI_STEREO if model == 'rig' else None
+    V = len(rig) if rig is not None else 1
+    seed = 1234 + 2 ** 40
+    sims, dgrid, cdf, kw = _run(model, opt, 25, [0, 1, 2 ** 31 + 5], seed, rig)
+    want = {d: particles.expected_records(sims, dgrid, cdf, sc.db, draws=d, jitter=JITTER, **kw) for d in ('counter', 'stream')}
+    assert len(want['counter']) == 3 * V
+    W, H = opt["cam_CCD_WH"]
+    ratio_db = np.ascontiguousarray(np.asarray(sc.db.ratio, np.float64)[:4])
+    tab = np.ascontiguousarray(cdf[0])
+    cam = particles.FrameCamera(opt, 0)
+    box = np.array(rig.box(cam), np.float64) if rig is not None else np.zeros(3)
+    views = rig.as_records() if rig is not None else None
+    for i, s in enumerate(sims):
+        one = np.ascontiguousarray(sims[i:i + 1])
+        n = int(s['n_particles'])
+        # the deviate of every particle / slot, kept or not
+        pid = np.arange(n, dtype=np.uint32)
+        g = np.zeros(n)
+        if model == 'iid':
+            emu.rr_emu_jitter_deviates(_p(one), n, _p(pid), None, _p(g))
+            ref = particles.counter_jitter(seed, pid, frame=int(s['frame']))
+        else:
+            if model == 'field':
+                _, life = particles.make_field_particles(cam, dgrid, tab, n, int(s['frame']), seed, hz, cull=False)
+            else:
+                life = particles.rig_state(cam, dgrid, tab, n, int(s['frame']), seed, hz, box)['life']
+            life = np.ascontiguousarray(life, np.float64)
+            emu.rr_emu_jitter_deviates(_p(one), n, _p(pid), _p(life), _p(g))
+            ref = particles.counter_jitter(seed, pid, life=life)
+        assert g.tobytes() == ref.tobytes() and np.abs(g).max() <= 8.6 and g.std() > 0.9
+        # the finished records
+        view = views[i % V:i % V + 1] if views is not None else None
+        for draws in ('counter', 'stream'):
+            out, g_out = np.zeros(n, h.hb.DROP_DTYPE), np.zeros(n)
+            k = emu.rr_emu_jitter_records(MODEL_ID[model], int(draws == 'counter'), JITTER, _p(one), hz, _p(view) if view is not None else None,
+                                          _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(out), _p(g_out), n)
+            w = want[draws][i]
+            assert k == len(w) > 100, (i, draws, k, len(w))
+            for name in h.hb.DROP_DTYPE.names:
+                if name == 'tex_index' and draws == 'stream':      # (the particle kernel leaves the block's first texture to k_particle_draws)
+                    assert np.array_equal(out[:k][name], w[name] // 10 * 10), (i, draws, name)
+                else:
+                    assert _same_field(out[:k][name], w[name]), (i, draws, name)
+
+
+# ---- 2. what the jitter does not touch -----------------------------------------------------------------------------
+@pytest.mark.parametrize("model", ['iid', 'field', 'rig'])
+@pytest.mark.parametrize("draws", ['stream', 'counter'])
+def test_only_end_points_and_rotation_terms_move(tmp_path, model, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _options('kitti')
+    rig = KITTI_STEREO if model == 'rig' else None
+    sims, dgrid, cdf, kw = _run(model, opt, 100, [7, 8], 11, rig)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
+    zero = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=0, **kw)
+    turned = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=JITTER, **kw)
+    n_big = n_small = 0
+    for a, z, b in zip(plain, zero, turned):
+        assert a.tobytes() == z.tobytes()                     # jitter = 0: today's records
+        assert len(a) == len(b) > 100                         # the same kept set
+        for name in h.hb.DROP_DTYPE.names:
+            if name not in TURNED:
+                assert a[name].tobytes() == b[name].tobytes(), name
+        big = a['type'] == 0
+        assert a[big].tobytes() == b[big].tobytes()           # Big records: byte-identical
+        assert np.all((a['rot_cos'][~big] != b['rot_cos'][~big]) | (a['rot_sin'][~big] != b['rot_sin'][~big]))
+        deg, _ = _turn_deg(b, a)
+        assert np.abs(deg).max() <= 8.6 * JITTER + 1e-9 and deg.std() > 0.5 * JITTER
+        n_big += int(big.sum())
+        n_small += int((~big).sum())
+    assert n_big > 0 and n_small > 100, (n_big, n_small)
+
+
+# ---- 3. coherence --------------------------------------------------------------------------------------------------
+N_CLIP = 12
+
+
+@pytest.fixture(scope='module')
+def clips(tmp_path_factory):
+    """(a) a 12-frame field clip and (b) 12 stereo instants with the jitter on: per frame {slot: (life, turn in degrees)}, the turn
+    read back from the records' rotation terms."""
+    sc = h.Scene(tmp_path_factory.mktemp('jitter'), 64, 96, 10)
+    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    frames = 50 + np.arange(N_CLIP)
+    out = {}
+    for model, rig in (('field', None), ('rig', KITTI_STEREO)):
+        sims, dgrid, cdf, kw = _run(model, opt, 25, frames, 77, rig)
+        V = 2 if rig is not None else 1
+        plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', **kw)
+        turned = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', jitter=JITTER, **kw)
+        per = []
+        for i, s in enumerate(sims):
+            pid, life = _kept(s, dgrid, cdf, sc.db, model, opt['cam_hz'], rig, i % V)
+            deg, nb = _turn_deg(turned[i], plain[i])
+            assert len(pid) == len(plain[i])
+            per.append({int(j): (float(g), float(d)) for j, g, d in zip(pid[nb], life[nb], deg)})
+        out[model] = (per, 77)
+    return out
+
+
+@pytest.mark.parametrize("model,step,stride", [('field', 1, 1), ('rig', 1, 2)], ids=['field-next-frame', 'rig-other-view'])
+def test_a_drop_keeps_its_tilt(clips, model, step, stride):
+    """Field: a slot kept in frames k and k + 1 in one life.  Rig: a slot kept by both stereo views of one instant (records 2 i and
+    2 i + 1).  The turn read back from the two records is the same angle -- jitter x counter_jitter of (slot, life) -- up to the
+    rounding of reading it back (1e-9 degrees against turns of degrees); across lives it is another one."""
+    per, seed = clips[model]
+    same, other = [], []
+    for i in range(0, len(per) - step, stride):
+        a, b = per[i], per[i + step]
+        for j in sorted(set(a) & set(b)):
+            (same if a[j][0] == b[j][0] else other).append((j, a[j][0], a[j][1], b[j][1]))
+    same = np.array(same)
+    print('%s: %d pairs in one life, %d across lives' % (model, len(same), len(other)))
+    assert len(same) >= 100
+    assert np.abs(same[:, 2] - same[:, 3]).max() < 1e-9
+    want = JITTER * particles.counter_jitter(seed, same[:, 0].astype(np.int64), life=same[:, 1])
+    assert np.abs(same[:, 2] - want).max() < 1e-9
+    assert len(set(np.round(same[:, 2], 6).tolist())) > 0.5 * len(set(same[:, 0].tolist()))       # other slots: other tilts
+    for j, _, da, db_ in other:
+        assert abs(da - db_) > 1e-6, j
+
+
+def test_other_lives_and_other_slots_have_other_deviates():
+    seed, n = 5, 20000
+    j = np.arange(n)
+    a = particles.counter_jitter(seed, j, life=np.full(n, 3.0))
+    b = particles.counter_jitter(seed, j, life=np.full(n, 4.0))
+    c = particles.counter_jitter(seed, j, life=np.full(n, 3.0 + 2.0 ** 32))      # g_hi enters the counter
+    d = particles.counter_jitter(seed, j, frame=3)                               # the i.i.d. model's block is another one
+    assert not np.any(a == b) and not np.any(a == c) and not np.any(a == d) and len(np.unique(a)) == n
+    for x, y in ((a, b), (a, c), (a, d), (a[:-1], a[1:])):
+        assert abs(np.corrcoef(x, y)[0, 1]) < 4.0 / np.sqrt(n)                   # four standard errors of an empty correlation
+    assert np.array_equal(a, particles.counter_jitter(seed, j, life=np.full(n, 3.0)))
+    assert not np.any(a == particles.counter_jitter(seed + 1, j, life=np.full(n, 3.0)))
+
+
+def test_the_stream_noise_has_no_such_coherence(tmp_path):
+    """The control: the reference's angular noise turns the SAME streak (one simulated frame, pristine end points) by another
+    angle in another rendered frame -- its deviate belongs to the frame's stream, not to the drop."""
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _options('kitti')
+    sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=77)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db)[0]
+    turns = []
+    for seed in (0, 1):                                       # the first entry of a run, drawn with the seeds of two rendered frames
+        s = sims.copy()
+        s['draw_seed'], s['run_pos'] = seed, 1
+        rec = particles.expected_records(s, dgrid, cdf, sc.db, noise_std=JITTER, noise_scale=1.0, run=([0], [seed]))[0]
+        assert len(rec) == len(plain) > 100
+        turns.append(_turn_deg(rec, plain)[0])
+    assert np.mean(np.abs(turns[0] - turns[1]) < 1e-9) < 0.5
+    # the jitter, the same two rendered frames: the same angle for every streak
+    a, b = (particles.expected_records(s, dgrid, cdf, sc.db, jitter=JITTER)[0] for s in (sims, _reseeded(sims, 1)))
+    assert np.array_equal(_turn_deg(a, plain)[0], _turn_deg(b, plain)[0])
+
+
+def _reseeded(sims, seed):
+    s = sims.copy()
+    s['draw_seed'] = seed
+    return s
+
+
+# ---- 4. law --------------------------------------------------------------------------------------------------------
+def _ks_normal(x):
+    """sqrt(n) D of the one-sample Kolmogorov-Smirnov statistic against N(0, 1)."""
+    x = np.sort(np.asarray(x, np.float64))
+    n = len(x)
+    cdf = 0.5 * (1.0 + np.array([math.erf(v / math.sqrt(2.0)) for v in x.tolist()]))
+    d = max(np.max(np.arange(1, n + 1) / n - cdf), np.max(cdf - np.arange(n) / n))
+    return float(d * np.sqrt(n))
+
+
+@pytest.mark.parametrize("model", ['iid', 'field'])
+def test_the_deviates_are_standard_normal(model):
+    n = 40000
+    j = np.arange(n)
+    g = particles.counter_jitter(2024, j, frame=7) if model == 'iid' else particles.counter_jitter(2024, j, life=np.full(n, 12.0))
+    control = np.random.RandomState(2024).normal(size=n)      # numpy's own sample through the same threshold
+    ks, ks_control = _ks_normal(g), _ks_normal(control)
+    print('%s: sqrt(n) D = %.3f (numpy.normal: %.3f), mean %.4f, std %.4f, max |g| %.3f' % (model, ks, ks_control, g.mean(), g.std(), np.abs(g).max()))
+    assert ks_control < KS_C
+    assert ks < KS_C
+    assert np.abs(g).max() <= 8.6
+    assert _ks_normal(1.1 * g) > KS_C                         # the test can tell: a tenth more spread fails it
+
+
+def test_the_deviate_at_the_ends_of_its_domain():
+    """u1 = 2^-53 (words 0) is the longest tail: |g| = sqrt(2 * 53 ln 2) = 8.57 at most; u1 = 1 (all bits set) gives 0.  det_log on
+    (0, 1] and det_sincos on [0, 2 pi] keep the 2 ulp of libm DESIGN section 2 states for them."""
+    full = 2 ** 32 - 1
+    w0 = np.array([0, 0, full, full, 0, 31, 123456789], np.uint32)
+    w1 = np.array([0, 0, full, full, 63, 0, 987654321], np.uint32)
+    w2 = np.array([0, 2 ** 31, 0, full, full, 5, 42], np.uint32)
+    g = particles.jitter_deviate(w0, w1, w2)
+    assert np.all(np.isfinite(g)) and np.abs(g).max() <= 8.6
+    assert abs(abs(g[0]) - math.sqrt(2 * 53 * math.log(2))) < 1e-6 and g[1] < -8.5      # cos(pi (1 + 2^-32)) = -1
+    assert g[2] == 0 and g[3] == 0
+    rs = np.random.RandomState(3)
+    u1 = np.concatenate([[2.0 ** -53, 2.0 ** -52, 0.5, 1.0 - 2.0 ** -53, 1.0], (rs.randint(0, 2 ** 53, 200000) + 1.0) * 2.0 ** -53,
+                         2.0 ** -rs.uniform(0, 53, 100000)])
+    assert u1.min() > 0 and u1.max() <= 1
+    assert _ulp(particles.det_log(u1), np.log(u1)).max() <= 2
+    x = 6.283185307179586 * particles.unit32(np.concatenate([[0, full], rs.randint(0, 2 ** 32, 300000)]).astype(np.uint32))
+    sn, cn = particles.det_sincos(x)
+    assert _ulp(cn, np.cos(x)).max() <= 2 and _ulp(sn, np.sin(x)).max() <= 2
+
+
+# ---- 5. refusals ---------------------------------------------------------------------------------------------------
+def test_refusals(tmp_path):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _options('kitti')
+    sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(sims, dgrid, cdf, sc.db, jitter=2.0, noise_std=2.0, noise_scale=1.0, run=([0], [0]))
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(sims, dgrid, cdf, sc.db, jitter=2.0, run=([0], [0]))
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(sims, dgrid, cdf, sc.db, jitter=2.0, noise_std=2.0, noise_scale=1.0)
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(sims, dgrid, cdf, sc.db, jitter=-1.0)
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(sims, dgrid, cdf, sc.db, jitter=float('nan'))
+    bad = sims.copy()
+    bad['run_pos'] = 1
+    with pytest.raises(ValueError, match='jitter'):
+        particles.expected_records(bad, dgrid, cdf, sc.db, jitter=2.0)
+    # the driver's argument handling (before it looks at any path)
+    main = importlib.import_module('rain-rendering_amd.main')
+    common = ['--dataset', 'kitti', '-k', str(tmp_path), '-i', '25']
+    with pytest.raises(SystemExit, match='--streak_jitter needs --device_particles'):
+        main._derive(main._parse(common + ['--streak_jitter', '5']))
+    with pytest.raises(SystemExit, match='--streak_jitter cannot be combined with --noise_std'):
+        main._derive(main._parse(common + ['--streak_jitter', '5', '--device_particles', '--noise_std', '2']))
+    with pytest.raises(SystemExit, match='--streak_jitter'):
+        main._derive(main._parse(common + ['--streak_jitter', '-1', '--device_particles']))
+    assert main._parse(common).streak_jitter == 0.0
+
+
+def test_rain_augment_plan_carries_the_jitter(tmp_path):
+    augment = importlib.import_module('rain-rendering_amd.augment')
+    root = str(tmp_path)
+    h.synthetic.write_streak_db(os.path.join(root, 'rainstreakdb'))
+    kw = dict(streaks_db=os.path.join(root, 'rainstreakdb'), sequence='data_object/training')
+    aug = augment.RainAugment('kitti', particle_model='field', draws='counter', jitter=JITTER, **kw)
+    p = aug.plan(25, [4, 11])
+    assert p['jitter'] == JITTER and p['draws'] == 'counter' and p['particle_model'] == 'field'
+    assert augment.RainAugment('kitti', **kw).plan(25, [4])['jitter'] == 0.0
+    # the plan states the call's drop tables: expected_records takes it as it is
+    recs = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws=p['draws'],
+                                      jitter=p['jitter'])
+    plain = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws=p['draws'])
+    assert len(recs[0]) == len(plain[0]) > 100 and recs[0].tobytes() != plain[0].tobytes()
+    for bad in (-1.0, float('inf'), 'five', True):
+        with pytest.raises(ValueError, match='jitter'):
+            augment.RainAugment('kitti', jitter=bad, **kw)
