@@ -413,6 +413,30 @@ int rr_set_particle_rig(rr_ctx* ctx, int32_t n_views, const rr_rig_view* views, 
                         const int32_t* active);
 int rr_sizeof_rig_view(void);
 
+/* A camera TRAJECTORY for the rig model: the rig's world (slots, lives, wind, fall, wrap: unchanged) seen from a rig that
+ * moves and turns (tools/particles.py make_rig_particles view_end=; rain-rendering_amd/trajectory.py composes the poses).
+ * Instant i of the table belongs to time index frame[i] (rr_sim_frame.frame; strictly ascending, any gaps) and holds one
+ * rr_traj_pose per view OF THE RIG (n_views of rr_set_particle_rig, not n_active): world -> camera at t_k, p_cam =
+ * R0 (p - c0), and at t_k + exposure, (R1, c1); both already composed with the rig's views on the host.  The start of the
+ * streak is rr_set_particle_rig's view (R0, c0); its end is R1 ((d + velocity x exposure) - (c1 - c0)) with d the start's
+ * wrapped offset: the same lattice image, never wrapped again.  A pose with R1 == R0 and c1 == c0 gives the rig model's
+ * bits for the view (R0, c0).  rr_sim_frame.speed_mps stays a drift of the world: pass 0, the trajectory says how the
+ * camera moves.  The box of rr_set_particle_rig must hold every pose's frustum (Trajectory.box).
+ * Called after rr_set_particle_rig (a later rr_set_particle_rig with another n_views drops the table), between runs, with
+ * no call of the generator in flight; the table is copied to the device here, and a batch sends one row number per
+ * instant along with its records.  n_instants = 0 turns the trajectory off: the rig model is then exactly what it was.
+ * While a table is set, the views' own R and c are not read.  Angular noise stays refused as under the rig model; counter
+ * draws and the streak jitter work unchanged.
+ * RR_E_ARG: no rig set; frame not strictly ascending; an R off orthonormal (1e-9, as rr_set_particle_rig) or a number that
+ * is not finite; |c| > 1e6 m; n_instants > 2^20 (or negative); and, when generating under RR_PARTICLES_RIG, an instant
+ * whose rr_sim_frame.frame the table does not hold. */
+typedef struct {
+  double R0[9], c0[3];            /* world -> camera at t_k: row-major rotation, camera centre (metres) */
+  double R1[9], c1[3];            /* the same at t_k + exposure */
+} rr_traj_pose;                   /* 192 bytes */
+int rr_set_particle_trajectory(rr_ctx* ctx, int32_t n_instants, const uint32_t* frame, const rr_traj_pose* poses);
+int rr_sizeof_traj_pose(void);
+
 /* How the per-drop draws of the records the context generates from now on are made (every entry point that takes
  * rr_sim_frame records: rr_generate_drops[_device], rr_frame_in.sim, rr_pipeline_*, rr_augment_frames_device).
  *   RR_DRAWS_STREAM (default): step 3 above -- numpy's legacy stream seeded with draw_seed, replayed by one wave per frame

@@ -21,6 +21,11 @@ comes back [B, V, 3, H, W], `mask` [B, V, 1, H, W].  View v of instant f is fram
 --particle_model rig --rig ... --rig_view v` run.  `views=[...]` restricts the call to a subset of the rig's views (V = len(views),
 in that order) with the same bits per view.
 
+`trajectory=Trajectory...` (trajectory.py; needs `particle_model='rig'`, a single camera is `rig=Rig.from_spec('mono')`) moves and
+turns the rig through the field: `frame_index[i]` also selects the pose (an index outside the trajectory is a ValueError), the streak
+is the drop's path relative to the camera over the exposure, and the frames are those of a `main.py ... --trajectory FILE` run.
+`set_trajectory()` swaps the trajectory between batches.
+
 `draws='counter'` (default 'stream') takes every drop's texture pick from the drop's own Philox counter instead of the run's numpy
 stream (tools/particles.py, `main.py --particle_draws counter`): under 'field' and 'rig' a drop then keeps its streak pattern in every
 frame of its life and in every view, and the device skips its one serial pass (0.15 ms of a KITTI 25 mm/hr call).  The frames are those of
@@ -49,6 +54,7 @@ from .common import add_attenuation, envmap, imgops, solid_angle
 from .common import db as dbmod
 from .common.bad_weather import DBManager
 from . import rig as rigmod
+from .trajectory import Trajectory
 from .tools import particles
 
 
@@ -87,7 +93,7 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream', jitter=0.0):
+                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
@@ -114,6 +120,7 @@ class RainAugment:
         self.focal = st['cam_focal'] / 1000.
         self.f_number, self.exposure, self.camera_gain = st['cam_f_number'], st['cam_exposure'], st['cam_gain']
         self.n_sim = particles.n_sim_frames(self.options)
+        self.trajectory = self._check_trajectory(trajectory)
         light_db = os.path.join(streaks_db, 'env_light_database')
         self.db = DBManager(streaks_path=os.path.join(light_db, 'size32'),
                             norm_coeff_path=os.path.join(light_db, 'txt', 'normalized_env_max.txt'))
@@ -130,6 +137,23 @@ class RainAugment:
         self._unions = {}                        # sorted intensities -> (d_grid, cdf of all their tables, table offset per intensity)
         self._tables_key = None                  # the union the context holds
         self._geom = None                        # (H, W) whose envmap geometry and solid angles the context holds
+        self._traj_set = trajectory is None      # whether the context holds the current trajectory's box and table
+
+    def _check_trajectory(self, trajectory):
+        if trajectory is None:
+            return None
+        if self.rig is None:
+            raise ValueError("trajectory= needs particle_model='rig' (a single camera: rig=Rig.from_spec('mono'))")
+        if not isinstance(trajectory, Trajectory):
+            raise TypeError("trajectory must be a trajectory.Trajectory, got %r" % (type(trajectory).__name__,))
+        return trajectory.at_rate(self.options["cam_hz"])    # frame_index counts frames of the run: row f is t = f / cam_hz
+
+    def set_trajectory(self, trajectory):
+        """Another trajectory (or None: the rig stands still) from the next call on: between batches, with no call in flight.  The
+        slot counts and tables follow its box, so frames made under different trajectories share no drops."""
+        self.trajectory = self._check_trajectory(trajectory)
+        self._rates, self._unions, self._tables_key = {}, {}, None
+        self._traj_set = False
 
     # ---- host side: what a call sends (no GPU needed) ----------------------------------------------------------------
     def frame_size(self):
@@ -145,7 +169,7 @@ class RainAugment:
         rate = float(rate)
         if rate not in self._rates:
             sims, dgrid, cdf = particles.sim_frames(self.options, rate, self.n_sim, render_scale=self.render_scale, seed=self.seed,
-                                                    model=self.particle_model, rig=self.rig)
+                                                    model=self.particle_model, rig=self.rig, trajectory=self.trajectory)
             fog = add_attenuation.FogRain(rain_intensity=rate, focal=self.focal, f_number=self.f_number, angle=90,
                                           exposure=self.exposure, camera_gain=self.camera_gain).constants()
             self._rates[rate] = (sims, dgrid, np.atleast_2d(cdf), tuple(float(v) for v in fog))
@@ -199,8 +223,16 @@ class RainAugment:
                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
+            box_rig = self.rig if self.trajectory is None else self.trajectory.bind(self.rig)
             out.update(sims=np.repeat(sims, V), fog=np.repeat(fog, V, axis=0), views=list(self.views),
-                       rig_views=self.rig.as_records(), rig_box=particles.rig_run_box(self.options, self._first_rate(), self.n_sim, self.rig))
+                       rig_views=self.rig.as_records(), rig_box=particles.rig_run_box(self.options, self._first_rate(), self.n_sim, box_rig))
+            if self.trajectory is not None:                  # frame_index selects the pose
+                if any(f >= len(self.trajectory) for f in idx):
+                    raise ValueError("frame_index %r is outside the trajectory's %d poses" % ([f for f in idx if f >= len(self.trajectory)],
+                                                                                              len(self.trajectory)))
+                if len(set(sims['exposure_s'].tolist())) != 1:
+                    raise ValueError("a trajectory needs one exposure for the whole batch")
+                out.update(trajectory=self.trajectory, traj_poses=self.trajectory.compose(self.rig, float(sims[0]['exposure_s'])))
         return out
 
     # ---- the call ----------------------------------------------------------------------------------------------------
@@ -247,6 +279,10 @@ class RainAugment:
             hip.set_particle_draws(self.draws)
             hip.set_particle_jitter(self.jitter)
             self._hip, self.device = hip, dev
+        if self.rig is not None and not self._traj_set:      # (the previous call has finished: no kernel reads the old table)
+            self._hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])      # the box is the trajectory's
+            self._hip.set_particle_trajectory(p.get('traj_poses'))
+            self._traj_set = True
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)
             self._tables_key = key

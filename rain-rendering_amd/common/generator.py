@@ -86,6 +86,13 @@ class Generator:
                 raise ValueError("--particle_model rig needs --rig")
             self.rig = Rig.from_spec(args.rig)
             check_active([self.rig_view], len(self.rig))
+        self.trajectory = None
+        if getattr(args, 'trajectory', None) is not None:
+            from ..trajectory import Trajectory
+            if self.rig is None:
+                raise ValueError("--trajectory needs --particle_model rig (a single camera: --rig mono)")
+            self.trajectory = args.trajectory if isinstance(args.trajectory, Trajectory) else \
+                Trajectory.from_file(args.trajectory, convention=getattr(args, 'trajectory_convention', 'kitti') or 'kitti')
         if self.particle_model in ('field', 'rig') and bool(self.noise_std):
             raise ValueError("--noise_std has no meaning with --particle_model field: the reference's angular noise turns a shared "
                              "simulated frame in place, the field model's particles move from frame to frame")
@@ -438,12 +445,25 @@ class Generator:
                     from ..tools import particles
                     opts = self.sim_options[sequence]
                     n_sim = particles.n_sim_frames(opts)
+                    traj = self.trajectory
+                    if traj is not None:                         # row f is rendered frame f: too few rows end the run before any GPU work
+                        f_last = (len(files) if self.frame_end is None else min(self.frame_end, len(files))) - 1
+                        if self.frames:
+                            f_last = int(np.max(np.clip(self.frames, 0, f_last)))
+                        if f_last >= len(traj):
+                            raise ValueError("--trajectory holds %d poses, the run renders frame %d" % (len(traj), f_last))
+                        traj = traj.at_rate(opts["cam_hz"])      # a row per rendered frame: the run's frame rate
                     sims, dgrid, cdf = particles.sim_frames(opts, fallrate, n_sim, render_scale=rs, seed=0, model=self.particle_model,
-                                                            rig=self.rig)
+                                                            rig=self.rig, trajectory=traj)
                     hip.set_particle_tables(dgrid, cdf)
                     if self.rig is not None:                     # this run renders ONE view of the rig: its camera folder
-                        hip.set_particle_rig(self.rig.as_records(), particles.rig_run_box(opts, fallrate, n_sim, self.rig),
+                        box_rig = self.rig if traj is None else traj.bind(self.rig)
+                        hip.set_particle_rig(self.rig.as_records(), particles.rig_run_box(opts, fallrate, n_sim, box_rig),
                                              active=[self.rig_view])
+                        # every rank sets the whole table: any frame can be made on any rank
+                        if traj is not None and len(set(sims['exposure_s'].tolist())) != 1:
+                            raise ValueError("--trajectory needs one exposure for the whole run: cam_exposure changes between simulated frames")
+                        hip.set_particle_trajectory(None if traj is None else traj.compose(self.rig, float(sims[0]['exposure_s'])))
                     hip.set_particle_model(self.particle_model, opts["cam_hz"])
                     if self.particle_draws != 'stream':          # (the noise is off: refused above)
                         hip.set_particle_noise(0.0, 0.0)

@@ -4824,11 +4824,28 @@ struct RigViews {                    // the ACTIVE views in batch order, and the
   double box[3];
   int n_active;
 };
-template <bool COUNT, bool CTR, bool JIT>
+// TRAJ (rr_set_particle_trajectory): the views' poses come from the device table instead of `rv` -- rv.R and rv.c are not read.
+// The workgroup reads its instant's row (tj.rows[instant], sent with the batch's records) and view step a takes pose
+// row * n_views + active[a]: (R0, c0) for the cull (rrsim::traj_view_start), then, for the lanes the cull left only, (R1, c1)
+// for the end of the streak (rrsim::traj_view_end).  One pose is live at a time, its second half after the first; the
+// addresses are wave-uniform and the table is never written by a kernel (constant address space): scalar loads.  The count pass
+// and the store pass read the same row and the count pass needs R0 and c0 only.  TRAJ = false is the kernel as it was: the
+// argument is an empty struct behind every other one.
+typedef double __attribute__((address_space(4))) const_f64;
+template <bool TRAJ>
+struct TrajArgs {};
+template <>
+struct TrajArgs<true> {
+  const rr_traj_pose* poses;                  // [n_instants][n_views]
+  const int32_t* rows;                        // the batch's row per instant
+  int32_t active[RR_MAX_VIEWS];               // the rig's number of the batch's view a
+  int32_t n_views;
+};
+template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
                                                         rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots,
-                                                        double jitter_deg) {
+                                                        double jitter_deg, const TrajArgs<TRAJ> tj) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -4852,6 +4869,8 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
 #pragma unroll
   for (int k = 0; k < 4; k++) rdb[k] = ratio_db[k];
   const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
+  int row = 0;
+  if constexpr (TRAJ) row = tj.rows[inst];
   int step = 0;
   for (int base = first; base < last; base += 512) {
     const int j = base + t;
@@ -4872,7 +4891,26 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
           q.z_max = rr::dmin((q.wd * sf.fpx) / sf.min_px, sf.z_far);
         }
         rrsim::Particle p;
-        if (rrsim::rig_view_particle(sf, q, rv.box, rv.R[a], rv.c[a], p)) {
+        bool inside;
+        if constexpr (TRAJ) {
+          // the pose as 24 doubles of the constant address space (R0, c0, R1, c1): the table is read-only for every kernel
+          const const_f64* ps = (const const_f64*)reinterpret_cast<const double*>(tj.poses + ((int64_t)row * tj.n_views + tj.active[a]));
+          double p0[12], dd[3];
+#pragma unroll
+          for (int k = 0; k < 12; k++) p0[k] = ps[k];
+          inside = rrsim::traj_view_start(sf, q, rv.box, p0, p0 + 9, dd, p);
+          if (inside) {                                       // (c0 is read again here rather than kept across the cull)
+            double c0[3], p1[12];
+#pragma unroll
+            for (int k = 0; k < 3; k++) c0[k] = ps[9 + k];
+#pragma unroll
+            for (int k = 0; k < 12; k++) p1[k] = ps[12 + k];
+            rrsim::traj_view_end(sf, q, dd, c0, p1, p1 + 9, p);
+          }
+        } else {
+          inside = rrsim::rig_view_particle(sf, q, rv.box, rv.R[a], rv.c[a], p);
+        }
+        if (inside) {
           double ratio;
           keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
           d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
@@ -5257,6 +5295,10 @@ struct rr_ctx {
   rr_rig_view rig_views[RR_MAX_VIEWS];
   int32_t rig_active[RR_MAX_VIEWS];
   double rig_box[3] = {0.0, 0.0, 0.0};
+  // the trajectory of the rig model (rr_set_particle_trajectory): the time indices on the host, the poses on the device
+  std::vector<uint32_t> traj_frame;
+  rr_traj_pose* d_traj = nullptr;
+  std::vector<int32_t> traj_rows;    // a batch's row per instant (scratch of enqueue_particles)
   std::vector<uint32_t> run_frame, run_seed;
   std::vector<int32_t> run_chain;                                       // entry p: its index among its simulated frame's entries
   std::unordered_map<uint32_t, std::vector<uint32_t>> chain_seeds;      // simulated frame id -> seeds of its entries, in run order
@@ -6364,6 +6406,22 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
     }
   }
+  // under a trajectory every instant names a row of the table (binary search over the ascending time indices)
+  const bool traj = rig && !ctx->traj_frame.empty();
+  const int n_rows = traj ? n / ctx->rig_n_active : 0;
+  if (traj) {
+    ctx->traj_rows.resize((size_t)n_rows);
+    for (int i = 0; i < n_rows; i++) {
+      const uint32_t k = sims[(size_t)i * ctx->rig_n_active].frame;
+      const auto it = std::lower_bound(ctx->traj_frame.begin(), ctx->traj_frame.end(), k);
+      if (it == ctx->traj_frame.end() || *it != k) {
+        ctx->err = "rig model: rr_sim_frame.frame " + std::to_string(k) + " (instant " + std::to_string(i) +
+                   ") is not in the trajectory's table of " + std::to_string(ctx->traj_frame.size()) + " instants (rr_set_particle_trajectory)";
+        return RR_E_ARG;
+      }
+      ctx->traj_rows[(size_t)i] = (int32_t)(it - ctx->traj_frame.begin());
+    }
+  }
   const bool ctr = ctx->particle_draws == RR_DRAWS_COUNTER;
   const bool jit = ctx->jitter_deg != 0.0;
   int n_noisy = 0;
@@ -6399,17 +6457,21 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     n_noisy += noise_on;
   }
   int rc;
-  if (n > ctx->cap_sims) {
+  // the trajectory's rows travel behind the records, in the same buffer and the same copy: n_rows int32 <= n records' room
+  const int n_buf = n + (traj ? (int)(((size_t)n_rows * sizeof(int32_t) + sizeof(rr_sim_frame) - 1) / sizeof(rr_sim_frame)) : 0);
+  const size_t sims_bytes = sizeof(rr_sim_frame) * (size_t)n + sizeof(int32_t) * (size_t)n_rows;
+  if (n_buf > ctx->cap_sims) {
     HIPCHK(hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, ctx->d_sims, (size_t)n))) return rc;
-    ctx->cap_sims = n;
+    if ((rc = dev_alloc(ctx, ctx->d_sims, (size_t)n_buf))) return rc;
+    ctx->cap_sims = n_buf;
   }
   int ring_idx;
   void* host;
-  if ((rc = ring_acquire(ctx, ctx->ring_sims, sizeof(rr_sim_frame) * (size_t)n, ring_idx, host))) return rc;
+  if ((rc = ring_acquire(ctx, ctx->ring_sims, sims_bytes, ring_idx, host))) return rc;
   memcpy(host, sims, sizeof(rr_sim_frame) * (size_t)n);
+  if (traj) memcpy(static_cast<uint8_t*>(host) + sizeof(rr_sim_frame) * (size_t)n, ctx->traj_rows.data(), sizeof(int32_t) * (size_t)n_rows);
   hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_sims),
-                     (int)(sizeof(rr_sim_frame) * (size_t)n / 4));
+                     (int)(sims_bytes / 4));
   if ((rc = ring_commit(ctx, ctx->ring_sims, ring_idx, s))) return rc;
   if (field) {
     // workgroups per frame: one (no count pass) when the frames alone give every compute unit a workgroup -- measured: at 256
@@ -6444,14 +6506,32 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       ProfScope ps(ctx, s, "k_rig_particles");
       auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg);
+                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, TrajArgs<false>{});
       };
-      if (chunks > 1) launch(k_rig_particles<true, false, false>);   // (a count depends neither on the draws nor on the jitter)
-      if (jit) {
-        if (ctr) launch(k_rig_particles<false, true, true>);
-        else launch(k_rig_particles<false, false, true>);
-      } else if (ctr) launch(k_rig_particles<false, true, false>);
-      else launch(k_rig_particles<false, false, false>);
+      if (traj) {                                            // the same passes, the poses from the table (rv.R, rv.c unread)
+        TrajArgs<true> tj;
+        tj.poses = ctx->d_traj;
+        tj.rows = reinterpret_cast<const int32_t*>(ctx->d_sims + n);
+        tj.n_views = ctx->rig_n_views;
+        for (int a = 0; a < RR_MAX_VIEWS; a++) tj.active[a] = a < rv.n_active ? ctx->rig_active[a] : 0;
+        auto launch_t = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj);
+        };
+        if (chunks > 1) launch_t(k_rig_particles<true, false, false, true>);
+        if (jit) {
+          if (ctr) launch_t(k_rig_particles<false, true, true, true>);
+          else launch_t(k_rig_particles<false, false, true, true>);
+        } else if (ctr) launch_t(k_rig_particles<false, true, false, true>);
+        else launch_t(k_rig_particles<false, false, false, true>);
+      } else {
+        if (chunks > 1) launch(k_rig_particles<true, false, false>);   // (a count depends neither on the draws nor on the jitter)
+        if (jit) {
+          if (ctr) launch(k_rig_particles<false, true, true>);
+          else launch(k_rig_particles<false, false, true>);
+        } else if (ctr) launch(k_rig_particles<false, true, false>);
+        else launch(k_rig_particles<false, false, false>);
+      }
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
       auto launch = [&](auto kern) {
@@ -6626,6 +6706,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_cdf);
   hipFree(ctx->d_ratio_db);
   hipFree(ctx->d_sims);
+  hipFree(ctx->d_traj);
   hipFree(ctx->d_gen_drops);
   hipFree(ctx->d_gen_counts);
   hipFree(ctx->d_field_cnt);
@@ -7204,11 +7285,76 @@ int rr_set_particle_rig(rr_ctx* ctx, int32_t n_views, const rr_rig_view* views, 
   } else {
     for (int a = 0; a < na; a++) act[a] = a;
   }
+  if (n_views != ctx->rig_n_views) ctx->traj_frame.clear();    // a trajectory's table has one pose per view of the OLD rig
   ctx->rig_n_views = n_views;
   ctx->rig_n_active = na;
   memcpy(ctx->rig_views, views, sizeof(rr_rig_view) * (size_t)n_views);
   memcpy(ctx->rig_active, act, sizeof(int32_t) * (size_t)na);
   memcpy(ctx->rig_box, box, sizeof ctx->rig_box);
+  return RR_OK;
+}
+
+int rr_sizeof_traj_pose(void) { return (int)sizeof(rr_traj_pose); }
+
+int rr_set_particle_trajectory(rr_ctx* ctx, int32_t n_instants, const uint32_t* frame, const rr_traj_pose* poses) {
+  if (!ctx) return RR_E_ARG;
+  if (ctx->rig_n_views == 0) {
+    ctx->err = "rr_set_particle_trajectory: no rig set (rr_set_particle_rig first: the table holds one pose per view of the rig)";
+    return RR_E_ARG;
+  }
+  if (n_instants < 0 || n_instants > (1 << 20)) {
+    ctx->err = "rr_set_particle_trajectory: n_instants must be 0 .. 2^20, got " + std::to_string(n_instants);
+    return RR_E_ARG;
+  }
+  if (n_instants == 0) {
+    ctx->traj_frame.clear();
+    return RR_OK;
+  }
+  if (!frame || !poses) {
+    ctx->err = "rr_set_particle_trajectory: frame and poses must be given";
+    return RR_E_ARG;
+  }
+  for (int32_t i = 1; i < n_instants; i++)
+    if (frame[i] <= frame[i - 1]) {
+      ctx->err = "rr_set_particle_trajectory: frame must be strictly ascending (instant " + std::to_string(i) + ": " + std::to_string(frame[i]) +
+                 " after " + std::to_string(frame[i - 1]) + ")";
+      return RR_E_ARG;
+    }
+  const int nv = ctx->rig_n_views;
+  for (int64_t i = 0; i < (int64_t)n_instants * nv; i++)
+    for (int end = 0; end < 2; end++) {
+      const double* R = end ? poses[i].R1 : poses[i].R0;
+      const double* c = end ? poses[i].c1 : poses[i].c0;
+      const std::string where = "rr_set_particle_trajectory: instant " + std::to_string(i / nv) + ", view " + std::to_string(i % nv) +
+                                (end ? ", end of the exposure: " : ", start of the exposure: ");
+      bool ok = std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]);
+      for (int k = 0; k < 9; k++) ok = ok && std::isfinite(R[k]);
+      if (!ok) {
+        ctx->err = where + "R and c must be finite";
+        return RR_E_ARG;
+      }
+      for (int a = 0; ok && a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+          const double dot = R[3 * a] * R[3 * b] + R[3 * a + 1] * R[3 * b + 1] + R[3 * a + 2] * R[3 * b + 2];
+          ok = ok && fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-9;
+        }
+      const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+      if (!ok || !(fabs(det - 1.0) <= 1e-9)) {
+        ctx->err = where + "R must be orthonormal with determinant +1 (within 1e-9)";
+        return RR_E_ARG;
+      }
+      if (sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) > 1e6) {
+        ctx->err = where + "|c| is beyond 1e6 m";
+        return RR_E_ARG;
+      }
+    }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipDeviceSynchronize());                            // (between runs: nothing of the context is in flight)
+  ctx->traj_frame.clear();
+  int rc;
+  if ((rc = dev_alloc(ctx, ctx->d_traj, (size_t)n_instants * (size_t)nv))) return rc;
+  HIPCHK(hipMemcpy(ctx->d_traj, poses, sizeof(rr_traj_pose) * (size_t)n_instants * (size_t)nv, hipMemcpyHostToDevice));
+  ctx->traj_frame.assign(frame, frame + n_instants);
   return RR_OK;
 }
 

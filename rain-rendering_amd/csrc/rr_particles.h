@@ -248,6 +248,54 @@ RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const dou
   return inside;
 }
 
+// ---- the rig model under a TRAJECTORY (rr_set_particle_trajectory, tools/particles.py make_rig_particles view_end=) ----
+// The view has one pose (R0, c0) at t_k and another (R1, c1) at t_k + exposure: the streak is the drop's path relative to a
+// camera that moves and turns while the shutter is open.  traj_view_start is rig_view_particle's first half word for word
+// (nearest lattice image, turn by R0, cull) and hands on the wrapped offset d; traj_view_end moves d by the drop's velocity
+// x exposure, subtracts the camera's own displacement c1 - c0 -- the same lattice image as the start, never wrapped again --
+// and turns it by R1.  With R1 == R0 and c1 == c0 the subtraction is - 0.0 and the pair gives rig_view_particle's bits.  Two
+// functions, so that a kernel calls the second for the lanes the cull left only and R1, c1 are not live across it.
+RR_HD bool traj_view_start(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R0, const double* c0, double d[3],
+                           Particle& p) {
+  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
+  const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;
+  const double b = box[0] * q.z_max, w = 2.0 * b;
+  double dx = q.X - c0[0], dz = q.Z - c0[2];
+  const double dy = q.Y - c0[1];
+  dx = dx - floor((dx + b) / w) * w;                      // the lattice image nearest to the camera at t_k
+  dz = dz - floor((dz + b) / w) * w;
+  const double xc = (R0[0] * dx + R0[1] * dy) + R0[2] * dz;
+  const double yc = (R0[3] * dx + R0[4] * dy) + R0[5] * dz;
+  const double zc = (R0[6] * dx + R0[7] * dy) + R0[8] * dz;
+  const double zr = -zc;
+  const double ax = hx * zr, ay = hy * zr;
+  const bool inside = zr > 0.0 && zr <= q.z_max && -ax <= xc && xc <= ax && -ay <= yc && yc <= ay;
+  const double depth = rr::dmax(zr, 0.05);
+  d[0] = dx; d[1] = dy; d[2] = dz;
+  p.wp1[0] = xc; p.wp1[1] = yc; p.wp1[2] = -depth;
+  p.wd = q.wd;
+  p.ip1[0] = W / 2.0 + (sf.fpx * xc) / depth;
+  p.ip1[1] = H / 2.0 + (sf.fpx * yc) / depth;
+  p.iw1 = (q.wd * sf.fpx) / depth;
+  return inside;
+}
+RR_HD void traj_view_end(const rr_sim_frame& sf, const RigSlot& q, const double d[3], const double* c0, const double* R1, const double* c1,
+                         Particle& p) {
+  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
+  const double e = sf.exposure_s;
+  const double ex = (d[0] + q.wind * e) - (c1[0] - c0[0]);
+  const double ey = (d[1] + (-q.v) * e) - (c1[1] - c0[1]);
+  const double ez = (d[2] + sf.speed_mps * e) - (c1[2] - c0[2]);
+  const double X2 = (R1[0] * ex + R1[1] * ey) + R1[2] * ez;
+  const double Y2 = (R1[3] * ex + R1[4] * ey) + R1[5] * ez;
+  const double Z2 = (R1[6] * ex + R1[7] * ey) + R1[8] * ez;
+  const double depth2 = rr::dmax(-Z2, 0.05);
+  p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
+  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
+  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
+  p.iw2 = (q.wd * sf.fpx) / depth2;
+}
+
 // ceil(sqrt(n)) of a non-negative integer, exactly (np.ceil(np.sqrt(.)) of the loader gives the same: a non-integer root
 // is further from an integer than the rounding error of a correctly rounded sqrt)
 RR_HD int64_t ceil_sqrt(int64_t n) {

@@ -62,6 +62,10 @@ DROP_DTYPE = np.dtype([
 RIG_VIEW_DTYPE = np.dtype([('R', '<f8', (9,)), ('c', '<f8', (3,))], align=True)
 
 
+# numpy mirror of rr_traj_pose (rr_set_particle_trajectory): world -> camera at t_k (R0, c0) and at t_k + exposure (R1, c1)
+from .trajectory import POSE_DTYPE as TRAJ_POSE_DTYPE  # noqa: E402
+
+
 # numpy mirror of rr_sim_frame (the particle generator's per-frame settings, include/rainhip.h)
 SIM_FRAME_DTYPE = np.dtype([
     ('sensor_w', '<i4'), ('sensor_h', '<i4'), ('render_scale', '<i4'), ('n_particles', '<i4'),
@@ -154,7 +158,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter']
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_trajectory',
+           'rr_sizeof_traj_pose']
 
 _lib = None
 
@@ -256,6 +261,8 @@ def load_library(path=None):
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
+    lib.rr_set_particle_trajectory.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    assert lib.rr_sizeof_traj_pose() == TRAJ_POSE_DTYPE.itemsize == 192, (lib.rr_sizeof_traj_pose(), TRAJ_POSE_DTYPE.itemsize)
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
     assert lib.rr_sizeof_tensor_batch() == ctypes.sizeof(rr_tensor_batch), (lib.rr_sizeof_tensor_batch(), ctypes.sizeof(rr_tensor_batch))
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
@@ -880,6 +887,21 @@ class RainHip:
         a = None if active is None else np.ascontiguousarray(active, np.int32).reshape(-1)
         self._check(self.lib.rr_set_particle_rig(self.h, len(v), _ptr(v), _ptr(b), 0 if a is None else len(a), None if a is None else _ptr(a)),
                     'rr_set_particle_rig')
+
+    def set_particle_trajectory(self, poses=None, frame=None):
+        """rr_set_particle_trajectory: `poses` = [n_instants, n_views of the rig] TRAJ_POSE_DTYPE records (Trajectory.compose),
+        `frame` = the time index of every instant, strictly ascending (default 0 .. n_instants - 1).  After set_particle_rig.
+        poses=None (or empty) turns the trajectory off."""
+        if poses is None or len(poses) == 0:
+            self._check(self.lib.rr_set_particle_trajectory(self.h, 0, None, None), 'rr_set_particle_trajectory')
+            return
+        po = np.ascontiguousarray(poses, TRAJ_POSE_DTYPE)
+        if po.ndim == 1:
+            po = po.reshape(-1, 1)
+        assert po.ndim == 2
+        fr = np.arange(len(po), dtype=np.uint32) if frame is None else np.ascontiguousarray(frame, np.uint32).reshape(-1)
+        assert len(fr) == len(po), (len(fr), len(po))
+        self._check(self.lib.rr_set_particle_trajectory(self.h, len(po), _ptr(fr), _ptr(po)), 'rr_set_particle_trajectory')
 
     def generate_drops_device(self, sims, H, W, drops_ptr, cap, n_out_ptr, stream=None):
         """rr_generate_drops_device: sims = SIM_FRAME_DTYPE records (host); drops_ptr / n_out_ptr = DEVICE addresses of

@@ -70,8 +70,15 @@ _FLAGS = [
                                 help="with --device_particles: turn every streak by DEG degrees times a standard normal deviate of the "
                                      "drop's own (from its random counter: a drop keeps its tilt over its life and across the views of a "
                                      "rig); any --particle_model and --particle_draws; 0: off (not with --noise_std)")),
-    (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
+    (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'mono' (one camera), 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
                                                    "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
+    (('--trajectory',), dict(type=str, default=None,
+                             help="with --device_particles --particle_model rig (a single camera: --rig mono): a poses file, 12 numbers per "
+                                  "line (the 3 x 4 camera-to-world matrix, row by row, as KITTI odometry's poses.txt); row f is the pose of "
+                                  "rendered frame f: the rain field is seen from a camera that moves and turns along it")),
+    (('--trajectory_convention',), dict(type=str, default='kitti', choices=['kitti', 'native'],
+                                        help="axes of --trajectory: 'kitti' (x right, y down, z forward) or 'native' (x right, y up, "
+                                             "looking along -z)")),
     (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
                                                      "camera folder with the same seed gives a coherent set")),
 ]
@@ -96,6 +103,8 @@ def _derive(ns):
                              "simulated frame in place and has no meaning for particles that move from frame to frame")
     if (getattr(ns, 'particle_model', 'iid') == 'rig') != (getattr(ns, 'rig', None) is not None):
         raise SystemExit("--particle_model rig and --rig go together")
+    if getattr(ns, 'trajectory', None) is not None and (getattr(ns, 'particle_model', 'iid') != 'rig' or not ns.device_particles):
+        raise SystemExit("--trajectory needs --device_particles --particle_model rig (a single camera: --rig mono)")
     if getattr(ns, 'particle_draws', 'stream') != 'stream':
         if not ns.device_particles:
             raise SystemExit("--particle_draws %s needs --device_particles (a particle file's frames are drawn from numpy's stream)" %

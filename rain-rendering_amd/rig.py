@@ -93,10 +93,13 @@ class Rig:
 
     @classmethod
     def from_spec(cls, spec):
-        """The driver's --rig: 'stereo:<baseline in metres>' or the path of a JSON file {"views": [{"R": [9 or 3 x 3], "c": [3]}, ...]}."""
+        """The driver's --rig: 'mono' (one identity view: a single camera, so that it can have a trajectory),
+        'stereo:<baseline in metres>' or the path of a JSON file {"views": [{"R": [9 or 3 x 3], "c": [3]}, ...]}."""
         if isinstance(spec, Rig):
             return spec
         spec = str(spec)
+        if spec == 'mono':
+            return cls([(np.eye(3), [0.0, 0.0, 0.0])])
         if spec.startswith('stereo:'):
             try:
                 return cls.stereo(float(spec[len('stereo:'):]))

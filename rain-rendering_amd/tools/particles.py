@@ -59,6 +59,21 @@ in the library) is a persistent, stateless particle field for video:
     batch, on any rank, with the same bits.  The kept records of a frame are in ascending slot order.  Angular noise
     (``--noise_std``) is not defined for the field model.
 
+The RIG model (``model='rig'``, ``make_rig_particles``; ``rr_set_particle_rig``) is the field model in the frame of a camera
+rig: one lattice world (a slot's box wraps in x and z), each view p_cam = R (p_rig - c) looks at the lattice image nearest to
+its camera (rig.py).
+
+A TRAJECTORY (``trajectory=``, ``make_rig_particles(view_end=)``; ``rr_set_particle_trajectory``, trajectory.py) moves and turns
+the rig through that unchanged world.  Every (time index k, view) has two world -> camera poses, composed with the rig's views
+on the host: (R0, c0) at t_k and (R1, c1) at t_k + exposure.  The view step, in this order:
+    d = (X, Y, Z) - c0; dx, dz wrapped to the nearest image; (xc, yc, zc) = R0 d; cull        -- the rig model's, word for word
+    e = (d + (wind, -v, speed_mps) exposure) - (c1 - c0)                                         -- the camera's own displacement
+    (X2, Y2, Z2) = R1 e                                            -- the same lattice image as the start, never wrapped again
+and everything downstream (projection, the loader's fields, bucket, pick, jitter) is unchanged.  With R1 == R0 and c1 == c0 the
+subtraction is - 0.0: the rig model's bits for the view (R0, c0).  speed_mps remains a drift of the world; ``sim_frames`` writes
+0 under a trajectory, because the trajectory says how the camera moves.  The slot counts and tables take ``Trajectory.box``: the
+reach of all headings and the altitude range.  The rotation during the exposure is taken at its two ends only.
+
 Per-drop draws (``draws=``, ``rr_set_particle_draws`` in the library).  ``'stream'`` (default) is the renderer's own: numpy's
 legacy stream seeded per frame picks one of the ten textures of the drop's ratio bucket (``randint(lo, lo + 10)``), in
 drop order -- what a run that writes the reference's files needs.  ``'counter'`` (``counter_picks``) takes the pick from
@@ -713,12 +728,16 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
 
 
 def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                       cull=True, image=(0, 0)):
+                       cull=True, image=(0, 0), view_end=None):
     """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
     statement of rr_particles.h make_rig_slot + rig_view_particle (same operations, same order).  `box` = (r, r_y, o_y).
     Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
     view keeps, in ascending slot order.  `image` = (ix, iz) looks at the lattice image ix, iz periods away from the nearest
-    one instead (tests: with the host's r no such image is ever inside the frustum)."""
+    one instead (tests: with the host's r no such image is ever inside the frustum).
+
+    `view_end` = (R1, c1): the view's pose at the END of the exposure (a trajectory, module docstring; rr_particles.h
+    traj_view_start + traj_view_end): the streak's end is R1 ((d + velocity x exposure) - (c1 - c)), d the start's wrapped
+    offset.  With view_end equal to `view` the subtraction is - 0.0: the bits of view_end=None."""
     rec = np.zeros(n_slots, PARTICLE_DTYPE)
     if n_slots == 0:
         return rec, np.zeros(0, np.float64)
@@ -748,6 +767,12 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
     ex = dx + st['vel'][:, 0] * e
     ey = dy + st['vel'][:, 1] * e
     ez = dz + st['vel'][:, 2] * e
+    if view_end is not None:                                    # the camera's own displacement; the same lattice image, not re-wrapped
+        c1 = [float(v) for v in np.asarray(view_end[1], np.float64).reshape(3)]
+        ex = ex - (c1[0] - c[0])
+        ey = ey - (c1[1] - c[1])
+        ez = ez - (c1[2] - c[2])
+        R = [float(v) for v in np.asarray(view_end[0], np.float64).reshape(9)]
     X2 = (R[0] * ex + R[1] * ey) + R[2] * ez
     Y2 = (R[3] * ex + R[4] * ey) + R[5] * ez
     Z2 = (R[6] * ex + R[7] * ey) + R[8] * ez
@@ -765,17 +790,33 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
     return rec, st['life']
 
 
+def _traj_cam(cam):
+    """The camera of a frame under a trajectory: speed 0 -- the trajectory says how the camera moves."""
+    out = FrameCamera.__new__(FrameCamera)
+    out.__dict__.update(cam.__dict__)
+    out.speed = 0.0
+    return out
+
+
 def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-              cull=True, image=(0, 0)):
-    """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame."""
+              cull=True, image=(0, 0), trajectory=None, box=None):
+    """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame.  With
+    `trajectory` (trajectory.Trajectory): the view's composed poses of time index k, the trajectory's box and slot counts, speed 0.
+    `box`: another box than the run's (tests)."""
     n_sim = n_sim_frames(options) if n_sim is None else int(n_sim)
     ks = int(k) % n_sim
     cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
-    box = _rig_box(rig, cam, margin)
-    _, dgrid, cdf, _ = rig_expected_count(cam, rate, box, min_px, z_far)
-    n_slots = int(rig_slot_counts(options, fallrate, ks + 1, rig, seed, min_px, z_far, margin, count)[ks])
-    return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, rig.views[int(view)], box, wind_sigma, margin, min_px, z_far,
-                              cull, image)
+    src = rig if trajectory is None else trajectory.bind(rig)
+    run_box = _rig_box(src, cam, margin)
+    _, dgrid, cdf, _ = rig_expected_count(cam, rate, run_box, min_px, z_far)
+    n_slots = int(rig_slot_counts(options, fallrate, ks + 1, src, seed, min_px, z_far, margin, count)[ks])
+    box = run_box if box is None else tuple(float(v) for v in box)
+    if trajectory is None:
+        return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, rig.views[int(view)], box, wind_sigma, margin, min_px,
+                                  z_far, cull, image)
+    po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
+    return make_rig_particles(_traj_cam(cam), dgrid, cdf, n_slots, k, seed, cam.hz, (po['R0'], po['c0']), box, wind_sigma, margin,
+                              min_px, z_far, cull, image, view_end=(po['R1'], po['c1']))
 
 
 def rig_run_sims(sims, k_idx, n_active):
@@ -835,19 +876,24 @@ def diameter_tables(options, fallrate, n_frames, min_px=1.0, z_far=15.0, margin=
 
 
 def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=None, min_px=1.0, z_far=15.0, margin=0.05,
-               wind_sigma=1.0, count=None, frame_ids=None, model='iid', rig=None):
+               wind_sigma=1.0, count=None, frame_ids=None, model='iid', rig=None, trajectory=None):
     """SIM_FRAME_DTYPE records (hip_backend: the numpy mirror of rr_sim_frame) of `n_frames` camera frames + the tables
     they refer to: (sims, d_grid, cdf).  draw_seeds: np.random.seed(...) of the renderer's per-drop draws per frame
     (generator.py:318: the frame's index; default: the frame number).  model='field' (rr_set_particle_model): n_particles
     is the run's slot count under the frame's settings and `frame` the TIME index; a rendered frame f of a run takes the
     record of simulated frame f % n_sim with frame = f (field_run_sims).  model='rig' with `rig` (rig.Rig): likewise with the
     rig's own tables and slot counts (rig_tables, rig_slot_counts); an instant's views share its record up to draw_seed
-    (rig_run_sims)."""
+    (rig_run_sims).  With `trajectory` (trajectory.Trajectory; rig model only): the slot counts and tables take
+    Trajectory.box, and speed_mps is 0 -- the trajectory says how the camera moves."""
     from .. import hip_backend
     _check_model(model)
+    if trajectory is not None and model != 'rig':
+        raise ValueError("a trajectory needs particle model 'rig' (a single camera: Rig.from_spec('mono'))")
     if model == 'rig':
         if rig is None:
             raise ValueError("particle model 'rig' needs rig= (rig.Rig)")
+        if trajectory is not None:
+            rig = trajectory.bind(rig)
         rig_run_box(options, fallrate, n_frames, rig, min_px, z_far, margin)
         dgrid, cdf, tab = rig_tables(options, fallrate, n_frames, rig, min_px, z_far, margin)
         counts = rig_slot_counts(options, fallrate, n_frames, rig, seed, min_px, z_far, margin, count)
@@ -863,7 +909,7 @@ def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=N
         s['key0'], s['key1'], s['frame'] = k0, k1, k if frame_ids is None else frame_ids[k]
         s['draw_seed'] = k if draw_seeds is None else draw_seeds[k]
         s['table'] = tab[k]
-        s['fpx'], s['exposure_s'], s['speed_mps'] = cam.fpx, cam.exposure, cam.speed
+        s['fpx'], s['exposure_s'], s['speed_mps'] = cam.fpx, cam.exposure, 0.0 if trajectory is not None else cam.speed
         s['wind_sigma'], s['margin'], s['min_px'], s['z_far'] = wind_sigma, margin, min_px, z_far
     return sims, dgrid, cdf
 
@@ -878,7 +924,7 @@ def field_run_sims(sims, f_idx):
     return out
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0):
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0, trajectory=None):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
     texture pick of every row (counter_picks of the row's particle); with `jitter`, `jitter_g`: the row's counter_jitter."""
@@ -887,7 +933,16 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
                                speed=float(s['speed_mps'])))()
     seed = int(s['key0']) | (int(s['key1']) << 32)
     life = None
-    if model == 'rig':
+    if model == 'rig' and trajectory is not None:
+        po = trajectory.compose(rig, cam.exposure)
+        if int(s['frame']) >= len(po):
+            raise ValueError("time index %d is outside the trajectory's %d poses" % (int(s['frame']), len(po)))
+        po = po[int(s['frame']), int(view)]
+        rec, life = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
+                                       (po['R0'], po['c0']), _rig_box(trajectory.bind(rig), cam, float(s['margin'])),
+                                       float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']),
+                                       view_end=(po['R1'], po['c1']))
+    elif model == 'rig':
         rec, life = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
                                     rig.views[int(view)], _rig_box(rig, cam, float(s['margin'])), float(s['wind_sigma']),
                                     float(s['margin']), float(s['min_px']), float(s['z_far']))
@@ -915,7 +970,7 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
 
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
-                     rig=None, view=None, draws='stream', jitter=0.0):
+                     rig=None, view=None, draws='stream', jitter=0.0, trajectory=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -937,6 +992,9 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     draws='counter' (rr_set_particle_draws RR_DRAWS_COUNTER): the same records with tex_index = 10 * texture_bucket(ratio) +
     counter_picks of the drop instead of the stream's randint; draw_seed is ignored; no angular noise, no run_pos.
 
+    trajectory= (trajectory.Trajectory; model='rig', rr_set_particle_trajectory): record i is view view[i % len(view)] under the
+    composed poses of time index sims[i]['frame'] (make_rig_particles view_end=), in the trajectory's box.
+
     jitter=DEG (rr_set_particle_jitter; every model, both draws): the records above, then every kept non-Big one turned by
     DEG * counter_jitter of its drop (jitter_records).  jitter=0: the records above.  Not with noise_std / noise_scale / run, and
     run_pos must be 0."""
@@ -945,6 +1003,8 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     noisy = bool(noise_std) and bool(noise_scale)
     jitter = _check_jitter(jitter, noisy, run)
     _check_draws(draws, noisy)
+    if trajectory is not None and model != 'rig':
+        raise ValueError("a trajectory needs particle model 'rig'")
     if model in ('field', 'rig') and (noisy or cam_hz is None):
         raise ValueError("the %s model needs cam_hz and has no angular noise" % model)
     views = [0]
@@ -956,7 +1016,7 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory)
         p = int(s['run_pos'])
         if jitter:
             if p != 0:

@@ -1,0 +1,410 @@
+"""CPU tier: the rig particle model under a camera TRAJECTORY (tools/particles.py make_rig_particles view_end=, rr_particles.h
+traj_view_start / traj_view_end, trajectory.py) -- the rig's lattice world seen from a rig that moves and turns.
+
+  1. the g++ build of the RR_HD statement (tests/hostemu/traj_emu.cpp: the code k_rig_particles<.., TRAJ> runs) == numpy, bit for bit;
+  2. a trajectory whose two ends coincide == the rig model with those composed views; an identity trajectory == the rig model;
+  3. coherence: on an arc a slot kept in frames k and k + 1 in one life has moved in the WORLD by (wind, -v, 0) / cam_hz;
+  4. every frame of the arc has the i.i.d. model's law (the thresholds and the control of tests/test_particle_field_host.py);
+  5. no double vision over the whole arc with Trajectory.box's r; 1 % less and another lattice image is visible;
+  6. a camera yawing in place: streaks displaced horizontally by fpx yaw_rate exposure at the image centre, sign included;
+  7. every refusal of trajectory.py, the file reader, both conventions;  8. the ABI layout of rr_traj_pose."""
+import ctypes
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import helpers as h
+import test_particle_field_host as tf                     # _sample / _same_law / N_LAW: the law test's thresholds and control
+import test_particle_rig_host as tr                       # _world / _world_bound / _state_bounds: the rounding bounds of the rig's world
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+rigmod = importlib.import_module('rain-rendering_amd.rig')
+trajmod = importlib.import_module('rain-rendering_amd.trajectory')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+U = 2.0 ** -53
+_options, _p = tr._options, tr._p
+MONO = rigmod.Rig.from_spec('mono')
+RIGS = [('stereo', tr.KITTI_STEREO), ('ring6', tr.RING6), ('mono', MONO)]
+
+
+def _pose(yaw_deg, pitch_deg=0.0, t=(0.0, 0.0, 0.0)):
+    """rig -> world, native frame: yaw counter-clockwise seen from above, then pitch (positive looks up)."""
+    P = np.zeros((3, 4))
+    P[:, :3] = rigmod._rot_y(yaw_deg) @ rigmod._rot_x(pitch_deg)
+    P[:, 3] = t
+    return P
+
+
+def arc(n, speed=10.0, yaw_rate_deg=20.0, hz=10.0, origin=(0.0, 0.0, 0.0)):
+    """A left-hand bend at constant speed: heading psi_k = yaw_rate k / hz, on a circle of radius speed / yaw_rate."""
+    om = np.deg2rad(yaw_rate_deg)
+    rad = speed / om
+    poses = []
+    for k in range(n):
+        psi = om * k / hz
+        # forward is rot_y(psi) (0, 0, -1) = (-sin psi, 0, -cos psi); the centre of the circle lies to the left, at (-rad, 0, 0)
+        poses.append(_pose(np.rad2deg(psi), 0.0, (origin[0] - rad + rad * np.cos(psi), origin[1], origin[2] - rad * np.sin(psi))))
+    return trajmod.Trajectory(np.array(poses), hz, 'native')
+
+
+ARC = arc(24)
+
+
+@pytest.fixture(scope='module')
+def emu(built):
+    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libtrajemu.so'))
+    lib.rr_emu_traj_particles.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.rr_emu_traj_records.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+    return lib
+
+
+# ---- 1. g++ == numpy -----------------------------------------------------------------------------------------------
+def _pinned_trajectory():
+    """Instants 0, 2, 4, 6: yaw 0, 90, 180 and 37 degrees (the last two pitched), |c| = 0, 1e3, 1e5 and 1e5 m; each is followed
+    by a pose 2 degrees and a few decimetres further, so that both ends of its exposure differ."""
+    pins = [(0.0, 0.0, 0.0), (90.0, 0.0, 1e3), (180.0, 7.0, 1e5), (37.0, -4.0, 1e5)]
+    poses = []
+    for yaw, pitch, dist in pins:
+        d = np.array([0.6, 0.0, -0.8]) * dist
+        poses.append(_pose(yaw, pitch, d))
+        poses.append(_pose(yaw + 2.0, pitch + 0.5, d + np.array([0.3, 0.02, -0.9])))
+    return trajmod.Trajectory(np.array(poses), 10.0, 'native')
+
+
+@pytest.mark.parametrize("name,rig", RIGS, ids=[n for n, _ in RIGS])
+def test_gxx_build_equals_numpy(tmp_path, emu, name, rig):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    traj = _pinned_trajectory()
+    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    hz = float(opt['cam_hz'])
+    V = len(rig)
+    sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=rig, trajectory=traj)
+    assert np.all(sims['speed_mps'] == 0.0)                       # the trajectory says how the camera moves
+    sims = particles.rig_run_sims(sims, [0, 2, 4, 6], V)
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, model='rig', cam_hz=hz, rig=rig, trajectory=traj)
+    cam = particles._traj_cam(particles.FrameCamera(opt, 0))
+    box = np.array(traj.box(rig, cam), np.float64)
+    poses = traj.compose(rig, cam.exposure)
+    W, H = opt["cam_CCD_WH"]
+    ratio_db = np.ascontiguousarray(np.asarray(sc.db.ratio, np.float64)[:4])
+    tab = np.ascontiguousarray(cdf[0])
+    total = 0
+    for i, s in enumerate(sims):
+        v, k = i % V, int(s['frame'])
+        n = int(s['n_particles'])
+        seed = int(s['key0']) | (int(s['key1']) << 32)
+        po = np.ascontiguousarray(poses[k, v:v + 1])
+        assert po['R0'].tobytes() != po['R1'].tobytes() and po['c0'].tobytes() != po['c1'].tobytes()
+        kw = dict(view_end=(po['R1'][0], po['c1'][0]))
+        rec, life = particles.make_rig_particles(cam, dgrid, tab, n, k, seed, hz, (po['R0'][0], po['c0'][0]), box, cull=False, **kw)
+        kept, _ = particles.make_rig_particles(cam, dgrid, tab, n, k, seed, hz, (po['R0'][0], po['c0'][0]), box, **kw)
+        one = np.ascontiguousarray(sims[i:i + 1])
+        out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
+        emu.rr_emu_traj_particles(_p(one), hz, _p(po), _p(box), _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
+        for nm, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
+            assert out[:, cols].tobytes() == np.ascontiguousarray(rec[nm]).tobytes(), (nm, i)
+        assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
+        assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == life.tobytes()
+        assert np.array_equal(np.nonzero(ins)[0], kept['pid']) and len(kept) > 100
+        got = np.zeros(n, h.hb.DROP_DTYPE)
+        m = emu.rr_emu_traj_records(_p(one), hz, _p(po), _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(got), n)
+        assert m == len(want[i]) > 50
+        got = got[:m]
+        for nm in h.hb.DROP_DTYPE.names:
+            if nm == 'tex_index':                                 # the draws pick one of the block of ten
+                assert np.array_equal(got[nm], want[i][nm] // 10 * 10)
+            else:
+                assert got[nm].tobytes() == want[i][nm].tobytes(), (nm, i)
+        total += m
+    print('%s: %d records compared' % (name, total))
+
+
+# ---- 2. coincident ends == the rig model -------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,rig", RIGS, ids=[n for n, _ in RIGS])
+def test_coincident_ends_give_the_rig_models_bits(name, rig):
+    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    cam = particles.FrameCamera(opt, 0)                           # speed 30 km/h stays in the formula as a drift of the world
+    box = rig.box(cam)
+    _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
+    n = 5000
+    # the same pose twice: compose hands out the start pose as the end pose, bit for bit
+    still = trajmod.Trajectory(np.array([_pose(37.0, 5.0, (1e3, 0.4, -2e3))] * 2), 10.0)
+    po = still.compose(rig, cam.exposure)
+    assert po['R0'].tobytes() == po['R1'].tobytes() and po['c0'].tobytes() == po['c1'].tobytes()
+    big = tuple(np.maximum(still.box(rig, cam), box))
+    for v in range(len(rig)):
+        view = (po['R0'][0, v], po['c0'][0, v])
+        a, la = particles.make_rig_particles(cam, dgrid, cdf, n, 9, 5, cam.hz, view, big, cull=False)
+        b, lb = particles.make_rig_particles(cam, dgrid, cdf, n, 9, 5, cam.hz, view, big, cull=False, view_end=(po['R1'][0, v], po['c1'][0, v]))
+        assert a.tobytes() == b.tobytes() and la.tobytes() == lb.tobytes()
+    # the identity trajectory is the rig model itself: the rig's own views, the rig's own box
+    ident = trajmod.Trajectory(np.array([_pose(0.0)] * 3), 10.0)
+    assert tuple(ident.box(rig, cam)) == tuple(box)
+    pi = ident.compose(rig, cam.exposure)
+    for v in range(len(rig)):
+        assert pi['R0'][1, v].tobytes() == rig.views[v][0].tobytes() and pi['c0'][1, v].tobytes() == rig.views[v][1].tobytes()
+        a, _ = particles.rig_frame(opt, 25, 1, rig, v, seed=4, count=300)
+        o0 = _options('kitti')                                    # rig_frame(trajectory=) takes speed 0
+        b, _ = particles.rig_frame(o0, 25, 1, rig, v, seed=4, count=300, trajectory=ident)
+        c, _ = particles.rig_frame(o0, 25, 1, rig, v, seed=4, count=300)
+        assert len(b) > 100 and b.tobytes() == c.tobytes() and a.tobytes() != b.tobytes()
+
+
+# ---- 3. coherence ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("origin", [(0.0, 0.0, 0.0), (1e3, 0.0, -1e3)], ids=['origin', 'c1e3'])
+def test_world_positions_move_by_velocity_over_cam_hz(origin):
+    """KITTI stereo on the arc (10 m/s, 20 deg/s, 10 Hz).  A slot kept by a view in frames k and k + 1 in one life: its world
+    position R0^T p_cam + c0 has moved by (wind, -v, 0) / cam_hz modulo the lattice period in x and z.  The tolerance is the
+    rounding bound of the rig's own motion test -- the rig-frame state (tr._state_bounds, from tf._track_bounds' operation
+    count) plus the two recovered positions (tr._world_bound: 14 roundings of values bounded by |p|_1 + |c|_1 + 1.5 w, and 3 x
+    the orthonormality defect of the composed R0, measured on the input matrix) -- with |c| the camera's distance from the
+    world's origin, which enters through |c|_1."""
+    rig = tr.KITTI_STEREO
+    traj = arc(40, origin=origin)
+    opt = _options('kitti')
+    cam = particles._traj_cam(particles.FrameCamera(opt, 0))
+    box = traj.box(rig, cam)
+    _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
+    n_slots = int(particles.rig_slot_counts(opt, 25, 1, traj.bind(rig), seed=11)[0])
+    po = traj.compose(rig, cam.exposure)
+    dt = 1.0 / cam.hz
+    total = 0
+    worst = 0.0
+    for k in range(39):
+        st = particles.rig_state(cam, dgrid, cdf, n_slots, k, 11, cam.hz, box)
+        assert np.all(st['vel'][:, 2] == 0.0)
+        for v in range(len(rig)):
+            ra, la = particles.rig_frame(opt, 25, k, rig, v, seed=11, trajectory=traj)
+            rb, lb = particles.rig_frame(opt, 25, k + 1, rig, v, seed=11, trajectory=traj)
+            _, ia, ib = np.intersect1d(ra['pid'], rb['pid'], return_indices=True)
+            ok = (la[ia] == lb[ib]) & (ra['wp1'][ia, 2] < -0.05) & (rb['wp1'][ib, 2] < -0.05)
+            ra, rb, life = ra[ia[ok]], rb[ib[ok]], la[ia[ok]]
+            if len(ra) == 0:
+                continue
+            va = (po['R0'][k, v].reshape(3, 3), po['c0'][k, v])
+            vb = (po['R0'][k + 1, v].reshape(3, 3), po['c0'][k + 1, v])
+            vel = st['vel'][ra['pid']]
+            w, wy = 2.0 * st['b'][ra['pid']], 2.0 * st['by'][ra['pid']]
+            r = (tr._world(rb, vb) - tr._world(ra, va)) - vel * dt
+            m = np.rint(r[:, [0, 2]] / w[:, None])
+            r[:, 0] -= m[:, 0] * w
+            r[:, 2] -= m[:, 1] * w
+            bound = tr._state_bounds(vel, w, wy, life, dt) + (tr._world_bound(ra, va, w) + tr._world_bound(rb, vb, w))[:, None] \
+                + (2.0 * U * w * (1.0 + np.abs(m).max(axis=1)))[:, None]
+            worst = max(worst, float((np.abs(r) / bound).max()))
+            assert np.all(np.abs(r) <= bound), (k, v, (np.abs(r) / bound).max(axis=0))
+            total += len(ra)
+    print('%d tracks compared, worst |residual| / bound %.3f' % (total, worst))
+    assert total >= 100
+
+
+# ---- 4. the law of every frame of the arc ----------------------------------------------------------------------------------
+def _arc_sample(rig, view, seed0):
+    """tf._sample on the arc: N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own, frame i at pose i % len(ARC)."""
+    opt = _options('kitti')
+    cam = particles.FrameCamera(opt, 0)
+    counts, D, depth, px, py = [], [], [], [], []
+    for i in range(tf.N_LAW):
+        rec, _ = particles.rig_frame(opt, 25, i % len(ARC), rig, view, seed=seed0 + i, trajectory=ARC)
+        counts.append(len(rec))
+        D.append(rec['wd1'] * 1e3)
+        depth.append(-rec['wp1'][:, 2])
+        px.append(rec['ip1'][:, 0])
+        py.append(rec['ip1'][:, 1])
+    return dict(cam=cam, counts=np.array(counts), D=np.concatenate(D), depth=np.concatenate(depth), px=np.concatenate(px), py=np.concatenate(py))
+
+
+def test_every_frame_of_the_arc_has_the_iid_models_law():
+    iid_a, iid_b = tf._sample('iid', 1000), tf._sample('iid', 5000)
+    control = tf._same_law(iid_a, iid_b)
+    assert all(v < 1 for v in control.values()), control
+    mean = particles.expected_count(iid_a['cam'], 25)[0]
+    for name, rig, views in (('stereo', tr.KITTI_STEREO, (0, 1)), ('mono', MONO, (0,))):
+        for v in views:
+            s = _arc_sample(rig, v, 13000 + 1000 * v + (500 if rig is MONO else 0))
+            got, got_b = tf._same_law(s, iid_a), tf._same_law(s, iid_b)
+            print('%s view %d on the arc: mean count %.1f (model %.1f); statistic / threshold vs iid: %s; vs iid (other seeds): %s'
+                  % (name, v, s['counts'].mean(), mean, got, got_b))
+            assert abs(s['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
+            assert all(x < 1 for x in got.values()), (name, v, got)
+            assert all(x < 1 for x in got_b.values()), (name, v, got_b)
+
+
+# ---- 5. no double vision -----------------------------------------------------------------------------------------------
+def test_the_nearest_image_is_the_only_visible_one_over_the_arc():
+    """With r from Trajectory.box every frustum of the arc lies inside the lattice cell centred on its camera.  With r 1 % smaller
+    a far corner of the frustum of the pose that attains r sticks out: a lattice image other than the nearest passes the cull."""
+    rig = tr.KITTI_STEREO
+    traj = arc(24)                                                # headings 0 .. 46 degrees: r is attained where a far corner
+    opt = _options('kitti')                                       # points along an axis of the lattice
+    cam = particles._traj_cam(particles.FrameCamera(opt, 0))
+    box = traj.box(rig, cam)
+    assert box[0] > rig.box(cam)[0]                               # the reach of all headings, not of the rig alone
+    hx = ((0.5 + 0.05) * cam.W) / cam.fpx
+    assert box[0] <= np.sqrt(hx * hx + 1.0) * (1.0 + 4 * U)
+    _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
+    po = traj.compose(rig, cam.exposure)
+    others = [(ix, iz) for ix in (-1, 0, 1) for iz in (-1, 0, 1) if (ix, iz) != (0, 0)]
+    tight = (0.99 * box[0], box[1], box[2])
+    reach = [max(np.abs(po['R0'][k, 0].reshape(3, 3).T @ np.array([sx * hx, 0.0, -1.0]))[[0, 2]].max() for sx in (-1, 1)) for k in range(len(traj))]
+    k_max = int(np.argmax(reach))
+    seen_tight = 0
+    for k in range(0, len(traj), 3):
+        for v in range(len(rig)):
+            view, end = (po['R0'][k, v], po['c0'][k, v]), (po['R1'][k, v], po['c1'][k, v])
+            near, _ = particles.make_rig_particles(cam, dgrid, cdf, 60000, k, 77, cam.hz, view, box, view_end=end)
+            assert len(np.unique(near['pid'])) == len(near) > 500
+            for img in others:
+                far, _ = particles.make_rig_particles(cam, dgrid, cdf, 60000, k, 77, cam.hz, view, box, image=img, view_end=end)
+                assert len(far) == 0, (k, v, img, len(far))
+    view, end = (po['R0'][k_max, 0], po['c0'][k_max, 0]), (po['R1'][k_max, 0], po['c1'][k_max, 0])
+    for img in others:
+        assert len(particles.make_rig_particles(cam, dgrid, cdf, 400000, k_max, 77, cam.hz, view, box, image=img, view_end=end)[0]) == 0
+        seen_tight += len(particles.make_rig_particles(cam, dgrid, cdf, 400000, k_max, 77, cam.hz, view, tight, image=img, view_end=end)[0])
+    print('pose %d attains r = %.4f: %d slots visible through another image with r 1 %% too small' % (k_max, box[0], seen_tight))
+    assert seen_tight > 0
+
+
+# ---- 6. streak direction -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("yaw_rate", [20.0, -20.0], ids=['left', 'right'])
+def test_a_camera_yawing_in_place_displaces_streaks_horizontally(yaw_rate):
+    """No wind (wind_sigma = 0), no ego-motion: the drops only fall, so a streak's horizontal extent is the camera's doing.  A yaw
+    of psi = yaw_rate x exposure about the vertical (positive: counter-clockwise seen from above, a left turn) moves a point at
+    the horizontal angle theta from tan(theta) to tan(theta + psi) on the sensor: to the RIGHT for a left turn, whatever its
+    height.  ip2.x - ip1.x = fpx (tan(theta + psi) - tan(theta)) = fpx psi (1 + tan^2 theta) + fpx psi^2 tan theta (1 + tan^2 theta)
+    + O(psi^3); at the image centre (|tan theta| <= T = 0.02) it is fpx psi within fpx |psi| (2 T^2 + 2 |psi| T + psi^2): twice the
+    first neglected terms."""
+    opt = _options('kitti')
+    cam = particles._traj_cam(particles.FrameCamera(opt, 0))
+    hz = float(cam.hz)
+    traj = trajmod.Trajectory(np.array([_pose(yaw_rate * k / hz) for k in range(3)]), hz)
+    psi = np.deg2rad(yaw_rate) * cam.exposure
+    rec, _ = particles.rig_frame(opt, 25, 1, MONO, 0, seed=8, count=30000, wind_sigma=0.0, trajectory=traj)
+    T = 0.02
+    tan_theta = (rec['ip1'][:, 0] - cam.W / 2.0) / cam.fpx
+    sel = (np.abs(tan_theta) <= T) & (rec['wp1'][:, 2] < -0.05) & (rec['wp2'][:, 2] < -0.05)
+    assert sel.sum() >= 200
+    dx = (rec['ip2'][:, 0] - rec['ip1'][:, 0])[sel]
+    want = cam.fpx * psi
+    tol = cam.fpx * abs(psi) * (2 * T * T + 2 * abs(psi) * T + psi * psi) + 8 * U * cam.W
+    print('yaw rate %+g deg/s, exposure %g s: dx = %.6f .. %.6f px, fpx psi = %.6f px, tolerance %.2e px' % (yaw_rate, cam.exposure, dx.min(), dx.max(), want, tol))
+    assert np.all(np.abs(dx - want) <= tol)
+    assert np.all(np.sign(dx) == np.sign(yaw_rate))
+
+
+# ---- 7. trajectory.py: refusals, the reader, conventions ------------------------------------------------------------------
+def test_refusals_reader_and_conventions(tmp_path):
+    T = trajmod.Trajectory
+    good = np.array([_pose(0.0), _pose(2.0, 0.0, (0.0, 0.0, -1.0))])
+    for bad, match in ((np.zeros((2, 3, 3)), 'N, 3, 4'), (np.zeros((0, 3, 4)), 'N >= 1'), ('abc', 'poses'), (np.zeros((3, 4)), 'N, 3, 4')):
+        with pytest.raises(ValueError, match=match):
+            T(bad, 10.0)
+    with pytest.raises(ValueError, match='convention'):
+        T(good, 10.0, 'ros')
+    for hz in (0.0, -1.0, np.nan, 'x'):
+        with pytest.raises(ValueError, match='hz'):
+            T(good, hz)
+    b = good.copy(); b[1, 0, 3] = np.inf
+    with pytest.raises(ValueError, match='pose 1.*finite'):
+        T(b, 10.0)
+    b = good.copy(); b[1, :, :3] *= 1.001
+    with pytest.raises(ValueError, match='pose 1.*orthonormal'):
+        T(b, 10.0)
+    b = good.copy(); b[0, :, :3] = np.diag([1.0, 1.0, -1.0])          # a reflection
+    with pytest.raises(ValueError, match='pose 0.*orthonormal'):
+        T(b, 10.0)
+    b = good.copy(); b[1, :, 3] = (8e5, 0.0, 8e5)
+    with pytest.raises(ValueError, match='1e\\+06 m'):
+        T(b, 10.0)
+    b4 = np.zeros((2, 4, 4)); b4[:, :3] = good; b4[:, 3, 3] = 1.0
+    assert T(b4, 10.0).compose(MONO, 0.002).tobytes() == T(good, 10.0).compose(MONO, 0.002).tobytes()
+    b4[1, 3, 0] = 0.5
+    with pytest.raises(ValueError, match='bottom row'):
+        T(b4, 10.0)
+    with pytest.raises(ValueError, match='170 degrees'):
+        T(np.array([_pose(0.0), _pose(175.0)]), 10.0).compose(MONO, 0.002)
+    with pytest.raises(ValueError, match='exposure'):
+        T(good, 10.0).compose(MONO, -1.0)
+    # a composed centre beyond 1e6 m although the rig's origin is inside; a view that is no rotation is the rig's own refusal
+    far = T(np.array([_pose(0.0, 0.0, (999999.5, 0.0, 0.0))]), 10.0)
+    with pytest.raises(ValueError, match='beyond'):
+        far.compose(rigmod.Rig([(np.eye(3), [1.0, 0.0, 0.0])]), 0.002)
+    with pytest.raises(ValueError, match='POSE_DTYPE'):
+        trajmod.check_poses(np.zeros(3))
+    po = np.array(T(good, 10.0).compose(tr.KITTI_STEREO, 0.002))
+    po['R1'][1, 1, 4] = np.nan
+    with pytest.raises(ValueError, match=r'pose \(1, 1\), R1.*finite'):
+        trajmod.check_poses(po)
+    po = np.array(T(good, 10.0).compose(tr.KITTI_STEREO, 0.002))
+    po['R0'][0, 1] *= 1.0 + 1e-8
+    with pytest.raises(ValueError, match=r'pose \(0, 1\), R0.*orthonormal'):
+        trajmod.check_poses(po)
+    with pytest.raises(ValueError, match="model 'rig'"):
+        particles.sim_frames(_options('kitti'), 25, 1, model='field', trajectory=T(good, 10.0))
+    with pytest.raises(ValueError, match="model 'rig'"):
+        particles.expected_records([], None, None, None, model='iid', trajectory=T(good, 10.0))
+    # a single pose stands still; the last pose extrapolates from the one before
+    one = T(good[:1], 10.0).compose(MONO, 0.002)
+    assert one['R0'].tobytes() == one['R1'].tobytes() and one['c0'].tobytes() == one['c1'].tobytes()
+    two = T(good, 10.0).compose(MONO, 0.01)                       # a tenth of the way
+    assert np.allclose(two['c1'][0, 0], (0.0, 0.0, -0.1), atol=1e-15) and np.allclose(two['c1'][1, 0], (0.0, 0.0, -1.1), atol=1e-15)
+    assert np.allclose(two['R1'][0, 0].reshape(3, 3), rigmod._rot_y(0.2).T, atol=1e-15)
+    assert np.allclose(two['R1'][1, 0].reshape(3, 3), rigmod._rot_y(2.2).T, atol=1e-15)
+    # conventions: a KITTI pose (x right, y down, z forward) that drives forward and turns LEFT is the native left turn
+    a = np.deg2rad(2.0)
+    kitti = np.zeros((2, 3, 4)); kitti[0, :, :3] = np.eye(3)
+    kitti[1, :, :3] = [[np.cos(a), 0.0, -np.sin(a)], [0.0, 1.0, 0.0], [np.sin(a), 0.0, np.cos(a)]]    # heading towards -x: left
+    kitti[1, :, 3] = (0.0, 0.3, 1.0)                             # one metre forward, 0.3 m DOWN
+    tk, tn = T(kitti, 10.0, 'kitti'), T(np.array([_pose(0.0), _pose(2.0, 0.0, (0.0, -0.3, -1.0))]), 10.0)
+    assert np.allclose(tk.R, tn.R, atol=1e-15) and np.array_equal(tk.t, tn.t)
+    # the reader: 12 numbers per line, blank lines and comments skipped, few digits re-orthonormalised
+    path = os.path.join(str(tmp_path), 'poses.txt')
+    with open(path, 'w') as fh:
+        fh.write('# synthesised\n\n')
+        for P in kitti:
+            fh.write(' '.join('%.6e' % x for x in P.reshape(-1)) + '\n')
+    rd = T.from_file(path)
+    assert len(rd) == 2 and rd.hz == 10.0 and rd.convention == 'kitti'
+    assert np.allclose(rd.R, tk.R, atol=2e-6) and np.allclose(rd.t, tk.t, atol=1e-6)
+    assert np.abs(rd.R[1] @ rd.R[1].T - np.eye(3)).max() <= rigmod.ORTHO_TOL
+    with pytest.raises(ValueError, match='orthonormal'):
+        T.from_file(path, orthonormalise=False)                   # six digits are not a rotation to 1e-12
+    with open(path, 'a') as fh:
+        fh.write('1 0 0 0 0 1 0 0 0 0 1\n')
+    with pytest.raises(ValueError, match=r'poses.txt:5: a pose has 12 numbers, got 11'):
+        T.from_file(path)
+    with open(path, 'w') as fh:
+        fh.write('1 0 0 0 0 1 0 0 0 0 one 0\n')
+    with pytest.raises(ValueError, match='not a number'):
+        T.from_file(path)
+    with open(path, 'w') as fh:
+        fh.write('\n')
+    with pytest.raises(ValueError, match='no pose'):
+        T.from_file(path)
+    # levelled: the start altitude leaves both ends; the box no longer grows with the climb
+    opt = _options('kitti')
+    cam = particles.FrameCamera(opt, 0)
+    hill = T(np.array([_pose(0.0, 0.0, (0.0, 3.0 * k, -1.0 * k)) for k in range(4)]), 10.0)
+    lv = hill.levelled()
+    ph, pl = hill.compose(MONO, cam.exposure), lv.compose(MONO, cam.exposure)
+    assert np.all(pl['c0'][:, 0, 1] == 0.0) and np.allclose(pl['c1'][:, 0, 1], 3.0 * cam.exposure * 10.0, rtol=1e-12)
+    assert np.array_equal(pl['c0'][:, 0, [0, 2]], ph['c0'][:, 0, [0, 2]]) and pl['R0'].tobytes() == ph['R0'].tobytes()
+    assert hill.box(MONO, cam)[2] >= 9.0 and lv.box(MONO, cam)[2] < 0.1
+    assert 'BETWEEN frames' in T.levelled.__doc__
+    assert len(rigmod.Rig.from_spec('mono')) == 1 and MONO.as_records().tobytes() == rigmod.Rig([(np.eye(3), [0, 0, 0])]).as_records().tobytes()
+
+
+# ---- 8. ABI ----------------------------------------------------------------------------------------------------------------
+def test_abi_layout(built, emu):
+    lib = h.hb.load_library()
+    assert lib.rr_sizeof_traj_pose() == 192 == h.hb.TRAJ_POSE_DTYPE.itemsize == emu.rr_emu_sizeof_traj_pose()
+    offs = {k: v[1] for k, v in h.hb.TRAJ_POSE_DTYPE.fields.items()}
+    assert offs == {'R0': 0, 'c0': 72, 'R1': 96, 'c1': 168}
+    assert h.hb.TRAJ_POSE_DTYPE is trajmod.POSE_DTYPE
+    assert 'rr_set_particle_trajectory' in h.hb.EXPORTS and hasattr(lib, 'rr_set_particle_trajectory')
+    assert lib.rr_version() == 400                                # the existing ABI is unchanged
+    assert lib.rr_sizeof_rig_view() == 96 and lib.rr_sizeof_sim_frame() == h.hb.SIM_FRAME_DTYPE.itemsize
