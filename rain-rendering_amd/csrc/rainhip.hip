@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -4666,6 +4667,48 @@ __global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int6
 // by jitter_deg * g (rrsim::noise_rotate) before it is staged: after the cull and the filter, so only kept lanes pay, and the
 // counts do not depend on it.  JIT = false is the kernel as it was (jitter_deg is not read).
 constexpr int DROP_DW = (int)(sizeof(rr_drop) / 4);
+
+// ---- the tail the three particle kernels share: finish the record, compact the kept ones, store whole lines.  No helper holds a
+// barrier: where a kernel synchronises, and why, is written in its own body. ----
+// Finish the record of a candidate that reached derive_drop: the first texture of its ratio bucket, CTR: plus the drop's pick,
+// JIT: a kept non-Big record turned by jitter_deg * deviate() -- the caller's deviate (particle_jitter or life_jitter), made for
+// those lanes only.
+template <bool CTR, bool JIT, class Deviate>
+__device__ inline void finish_record(rr_drop& d, bool keep, double ratio, const double* rdb, int pick, double jitter_deg, Deviate deviate) {
+  d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
+  if constexpr (CTR) d.tex_index += pick;
+  if constexpr (JIT)
+    if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * deviate());
+}
+// a kept lane's record into its wave's stage, at the lane's prefix popcount of the wave's ballot
+__device__ inline void stage_record(uint32_t* stage, unsigned long long bal, int lane, bool keep, const rr_drop& d) {
+  if (keep) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
+    uint32_t* dst = stage + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
+#pragma unroll
+    for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
+  }
+}
+// from the eight waves' counts of a step: off += the records of the waves below this one, tot = the step's records.  UNIFORM: the
+// counts are taken to the scalar side (the caller's `wave` and `off` are wave-uniform)
+template <bool UNIFORM>
+__device__ inline void wave_offsets(const int* cnt, int wave, int& off, int& tot) {
+  tot = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+    const int n = UNIFORM ? __builtin_amdgcn_readfirstlane(cnt[w]) : cnt[w];
+    if (w < wave) off += n;
+    tot += n;
+  }
+}
+// the wave's nw staged records to consecutive places of the frame's table from `off`, in whole lines; what does not fit under
+// `cap` is not stored (the count still says so)
+__device__ inline void store_staged(const uint32_t* stage, int nw, rr_drop* table, int off, int cap, int lane) {
+  const int room = imax(imin(nw, cap - off), 0);
+  uint32_t* o = reinterpret_cast<uint32_t*>(table + off);
+  for (int k = lane; k < room * DROP_DW; k += 64) o[k] = stage[k];
+}
+
 template <bool CTR, bool JIT>
 __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int H, int W, const double* dgrid, const double* cdf_tabs,
                                                     int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run,
@@ -4694,32 +4737,17 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
       rrsim::make_particle(sf, dgrid, cdf, n_grid, (uint32_t)i, p, CTR ? &pw : nullptr);
       double ratio;
       keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
-      d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
-      if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
-      if constexpr (JIT)
-        if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::particle_jitter(sf, (uint32_t)i));
+      finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::particle_jitter(sf, (uint32_t)i); });
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_cnt[wave] = __popcll(bal);
     __syncthreads();
-    int off = base_out, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-      const int c = s_cnt[w];
-      if (w < wave) off += c;
-      tot += c;
-    }
+    int off = base_out, tot;
+    wave_offsets<false>(s_cnt, wave, off, tot);
     const int nw = __popcll(bal);                            // records of this wave: consecutive output slots from `off`
-    if (keep) {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
-      uint32_t* dst = s_stage[wave] + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
-#pragma unroll
-      for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
-    }
+    stage_record(s_stage[wave], bal, lane, keep, d);
     wave_lds_sync();
-    const int room = imax(imin(nw, cap - off), 0);          // what does not fit is not stored (the count still says so)
-    uint32_t* o = reinterpret_cast<uint32_t*>(fout + off);
-    for (int k = lane; k < room * DROP_DW; k += 64) o[k] = s_stage[wave][k];
+    store_staged(s_stage[wave], nw, fout, off, cap, lane);
     base_out += tot;
     __syncthreads();
   }
@@ -4769,35 +4797,20 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
       if (rrsim::make_field_particle(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr)) {
         double ratio;
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
-        d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
-        if constexpr (CTR) d.tex_index += rrsim::texture_pick(pw);
-        if constexpr (JIT)
-          if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::life_jitter(sf, (uint32_t)j, life));
+        finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::life_jitter(sf, (uint32_t)j, life); });
       }
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_cnt[wave] = __popcll(bal);
     __syncthreads();
-    int off = base_out, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-      const int n = s_cnt[w];
-      if (w < wave) off += n;
-      tot += n;
-    }
+    int off = base_out, tot;
+    wave_offsets<false>(s_cnt, wave, off, tot);
     if constexpr (!COUNT) {
       __shared__ uint32_t s_stage[8][64 * DROP_DW];          // per wave: 64 records (57 KB)
       const int nw = __popcll(bal);                          // records of this wave: consecutive output slots from `off`
-      if (keep) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
-        uint32_t* dst = s_stage[wave] + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
-#pragma unroll
-        for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
-      }
+      stage_record(s_stage[wave], bal, lane, keep, d);
       wave_lds_sync();
-      const int room = imax(imin(nw, cap - off), 0);        // what does not fit is not stored (the count still says so)
-      uint32_t* o = reinterpret_cast<uint32_t*>(out + (int64_t)f * cap + off);
-      for (int k = lane; k < room * DROP_DW; k += 64) o[k] = s_stage[wave][k];
+      store_staged(s_stage[wave], nw, out + (int64_t)f * cap, off, cap, lane);
     }
     base_out += tot;
     __syncthreads();
@@ -4913,10 +4926,8 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
         if (inside) {
           double ratio;
           keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
-          d.tex_index = 10 * rrsim::texture_bucket(ratio, rdb);
-          if constexpr (CTR) d.tex_index += pick;             // one pick for every view of the slot
-          if constexpr (JIT)                                  // one tilt for every view: made here from (j, life), not carried
-            if (keep && d.type != 0) rrsim::noise_rotate(d, jitter_deg * rrsim::life_jitter(sf, (uint32_t)j, q.life));
+          // one pick for every view of the slot; one tilt for every view: made here from (j, life), not carried
+          finish_record<CTR, JIT>(d, keep, ratio, rdb, pick, jitter_deg, [&] { return rrsim::life_jitter(sf, (uint32_t)j, q.life); });
         }
       }
       const unsigned long long bal = __ballot(keep);
@@ -4924,29 +4935,13 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
       // the record's place in the wave's stage depends on the wave's own ballot only: it is staged BEFORE the barrier, so
       // that no record is held in registers across it
       __shared__ uint32_t s_stage[COUNT ? 1 : 8][64 * DROP_DW];   // per wave: 64 records (57 KB), one buffer for all views
-      if constexpr (!COUNT) {
-        if (keep) {
-          const uint32_t* src = reinterpret_cast<const uint32_t*>(&d);
-          uint32_t* dst = s_stage[wave] + __popcll(bal & ((1ull << lane) - 1ull)) * DROP_DW;
-#pragma unroll
-          for (int k = 0; k < DROP_DW; k++) dst[k] = src[k];
-        }
-      }
+      if constexpr (!COUNT) stage_record(s_stage[wave], bal, lane, keep, d);
       if (lane == 0) s_cnt[par][wave] = __popcll(bal);
       __syncthreads();
       const int run = __builtin_amdgcn_readfirstlane(s_run[wave][a]);     // (wave-uniform: kept on the scalar side)
-      int off = run, tot = 0;
-#pragma unroll
-      for (int w = 0; w < 8; w++) {
-        const int n = __builtin_amdgcn_readfirstlane(s_cnt[par][w]);
-        if (w < wave) off += n;
-        tot += n;
-      }
-      if constexpr (!COUNT) {
-        const int room = imax(imin(__popcll(bal), cap - off), 0);   // what does not fit is not stored (the count still says so)
-        uint32_t* o = reinterpret_cast<uint32_t*>(out + ((int64_t)inst * na + a) * cap + off);
-        for (int k = lane; k < room * DROP_DW; k += 64) o[k] = s_stage[wave][k];
-      }
+      int off = run, tot;
+      wave_offsets<true>(s_cnt[par], wave, off, tot);
+      if constexpr (!COUNT) store_staged(s_stage[wave], __popcll(bal), out + ((int64_t)inst * na + a) * cap, off, cap, lane);
       wave_lds_sync();                                       // the stage and s_run[wave][a] are read before they are written again
       if (lane == 0) s_run[wave][a] = run + tot;
     }
@@ -6364,6 +6359,16 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   return RR_OK;
 }
 
+// fn(CTR, JIT) with the run's draw mode and jitter as compile-time constants (std::bool_constant): the one place where the
+// store pass of a particle kernel family is chosen
+template <class F>
+void with_draws(bool ctr, bool jit, F fn) {
+  if (ctr && jit) fn(std::true_type{}, std::true_type{});
+  else if (ctr) fn(std::true_type{}, std::false_type{});
+  else if (jit) fn(std::false_type{}, std::true_type{});
+  else fn(std::false_type{}, std::false_type{});
+}
+
 // particle generator + packer of n frames (device output); see include/rainhip.h
 int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr_drop* drops_out, int cap, int32_t* n_out, hipStream_t s) {
   if (n <= 0 || !sims || !drops_out || !n_out || cap <= 0 || H <= 0 || W <= 0) {
@@ -6504,34 +6509,24 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
       memcpy(rv.box, ctx->rig_box, sizeof rv.box);
       ProfScope ps(ctx, s, "k_rig_particles");
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, TrajArgs<false>{});
-      };
-      if (traj) {                                            // the same passes, the poses from the table (rv.R, rv.c unread)
-        TrajArgs<true> tj;
-        tj.poses = ctx->d_traj;
-        tj.rows = reinterpret_cast<const int32_t*>(ctx->d_sims + n);
-        tj.n_views = ctx->rig_n_views;
-        for (int a = 0; a < RR_MAX_VIEWS; a++) tj.active[a] = a < rv.n_active ? ctx->rig_active[a] : 0;
-        auto launch_t = [&](auto kern) {
+      auto passes = [&](auto with_traj) {                    // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
+        constexpr bool TRAJ = decltype(with_traj)::value;
+        TrajArgs<TRAJ> tj;
+        if constexpr (TRAJ) {
+          tj.poses = ctx->d_traj;
+          tj.rows = reinterpret_cast<const int32_t*>(ctx->d_sims + n);
+          tj.n_views = ctx->rig_n_views;
+          for (int a = 0; a < RR_MAX_VIEWS; a++) tj.active[a] = a < rv.n_active ? ctx->rig_active[a] : 0;
+        }
+        auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
                              ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj);
         };
-        if (chunks > 1) launch_t(k_rig_particles<true, false, false, true>);
-        if (jit) {
-          if (ctr) launch_t(k_rig_particles<false, true, true, true>);
-          else launch_t(k_rig_particles<false, false, true, true>);
-        } else if (ctr) launch_t(k_rig_particles<false, true, false, true>);
-        else launch_t(k_rig_particles<false, false, false, true>);
-      } else {
-        if (chunks > 1) launch(k_rig_particles<true, false, false>);   // (a count depends neither on the draws nor on the jitter)
-        if (jit) {
-          if (ctr) launch(k_rig_particles<false, true, true>);
-          else launch(k_rig_particles<false, false, true>);
-        } else if (ctr) launch(k_rig_particles<false, true, false>);
-        else launch(k_rig_particles<false, false, false>);
-      }
+        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ>);   // (a count depends neither on the draws nor on the jitter)
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ>); });
+      };
+      if (traj) passes(std::true_type{});
+      else passes(std::false_type{});
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
       auto launch = [&](auto kern) {
@@ -6539,11 +6534,7 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
                            ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg);
       };
       if (chunks > 1) launch(k_field_particles<true, false, false>);
-      if (jit) {
-        if (ctr) launch(k_field_particles<false, true, true>);
-        else launch(k_field_particles<false, false, true>);
-      } else if (ctr) launch(k_field_particles<false, true, false>);
-      else launch(k_field_particles<false, false, false>);
+      with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value>); });
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
@@ -6552,15 +6543,11 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
   } else if (n_noisy < n) {                                  // frames with angular noise are left to k_noise_chains
     {
       ProfScope ps(ctx, s, "k_particles");
-      auto launch = [&](auto kern, int skip_run) {
-        hipLaunchKernelGGL(kern, dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out,
-                           cap, n_out, skip_run, ctx->jitter_deg);
-      };
-      if (jit) {                                             // (no frame has run_pos != 0 under the jitter)
-        if (ctr) launch(k_particles<true, true>, 0);
-        else launch(k_particles<false, true>, 0);
-      } else if (ctr) launch(k_particles<true, false>, 0);
-      else launch(k_particles<false, false>, n_noisy > 0 ? 1 : 0);
+      // skip_run: frames with run_pos != 0 are k_noise_chains' (none under the jitter or the counter draws: refused above)
+      with_draws(ctr, jit, [&](auto c, auto j) {
+        hipLaunchKernelGGL((k_particles<decltype(c)::value, decltype(j)::value>), dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid,
+                           ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0, ctx->jitter_deg);
+      });
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");

@@ -57,6 +57,24 @@ RR_HD double sample_diameter(const double* dgrid, const double* cdf, int n, doub
 // drop's Philox block 1 -- which no other draw reads -- scaled to 0 .. 9; tex_index = 10 * texture_bucket(ratio) + pick.
 RR_HD int texture_pick(uint32_t w) { return (int)(((uint64_t)w * 10u) >> 32); }
 
+// z_max(D): only drops that can show at least min_px wide are simulated (wd: the diameter in metres)
+RR_HD double slot_z_max(const rr_sim_frame& sf, double wd) { return rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far); }
+
+// horizontal wind from one Philox block: a centred sum of four uniforms scaled to unit variance (bell-shaped, bounded), times wind_sigma
+RR_HD double block_wind(const uint32_t c[4], double wind_sigma) {
+  const double s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0;
+  return (s4 * 1.7320508075688772) * wind_sigma;
+}
+
+// the pinhole projection of one streak end at camera-frame (X, Y), `depth` in front of the camera: sensor position (origin
+// bottom-left) and image width of a drop of diameter wd
+RR_HD void project(const rr_sim_frame& sf, double X, double Y, double depth, double wd, double ip[2], double& iw) {
+  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
+  ip[0] = W / 2.0 + (sf.fpx * X) / depth;
+  ip[1] = H / 2.0 + (sf.fpx * Y) / depth;
+  iw = (wd * sf.fpx) / depth;
+}
+
 // particle i of frame sf: three Philox blocks, counter = (i, frame, block, 0); *pick_word = the pick's word (b[2])
 RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const double* cdf, int n_grid, uint32_t i, Particle& p,
                          uint32_t* pick_word = nullptr) {
@@ -65,10 +83,9 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
   philox4x32_10(b, sf.key0, sf.key1);
   philox4x32_10(c, sf.key0, sf.key1);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
-  // diameter (mm) from the table; only drops that can show at least min_px wide are simulated: depth <= z_max(D)
-  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
+  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));   // diameter (mm) from the table
   const double wd = D * 1e-3;
-  const double z_max = rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far);
+  const double z_max = slot_z_max(sf, wd);
   // uniform in the frustum's volume: the depth's density is 3 z^2 / z_max^3, the law of the largest of three uniforms
   const double u1 = unit32(a[1]), u2 = unit32(a[2]), u3 = unit32(a[3]);
   const double depth = rr::dmax(z_max * rr::dmax(rr::dmax(u1, u2), u3), 0.05);
@@ -79,22 +96,17 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
   const double X = ((px - W / 2.0) * depth) / sf.fpx;
   const double Y = ((py - H / 2.0) * depth) / sf.fpx;
   const double Z = -depth;
-  // horizontal wind: a centred sum of four uniforms scaled to unit variance (bell-shaped, bounded), times wind_sigma
-  const double s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0;
-  const double wind = (s4 * 1.7320508075688772) * sf.wind_sigma;
+  const double wind = block_wind(c, sf.wind_sigma);
   const double t = sf.exposure_s;
   const double X2 = X + wind * t;
   const double Y2 = Y - terminal_velocity(D) * t;
   const double Z2 = Z + sf.speed_mps * t;
-  const double depth2 = rr::dmax(-Z2, 0.05);
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
   p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
   p.wd = wd;
   p.ip1[0] = px; p.ip1[1] = py;
-  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
-  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
   p.iw1 = (wd * sf.fpx) / depth;
-  p.iw2 = (wd * sf.fpx) / depth2;
+  project(sf, X2, Y2, rr::dmax(-Z2, 0.05), wd, p.ip2, p.iw2);
   if (pick_word) *pick_word = b[2];
 }
 
@@ -107,58 +119,83 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
 // fractional part is its age.  Inside a life the position is the start moved by velocity x elapsed time, modulo the box
 // on the two lateral axes: a translation of a uniform law, hence uniform in the box at every t; what lies outside the
 // (margin-enlarged) frustum is culled (two slots in three).  Everything is a function of (key, j, k) and the settings.
+// The field and the rig model share slot_draw and slot_fall; they differ in the box, the drift in depth and the placement.
+
+// the counter of block `block` of slot j's life g: (j, g mod 2^32, block, 2 + g / 2^32)
+RR_HD void life_counter(uint32_t j, double life, uint32_t block, uint32_t out[4]) {
+  const double g_hi = floor(life * (1.0 / 4294967296.0)), g_lo = life - g_hi * 4294967296.0;
+  out[0] = j; out[1] = (uint32_t)g_lo; out[2] = block; out[3] = 2u + (uint32_t)g_hi;
+}
+
+struct SlotDraw {                 // what slot j is for good: Philox block (j, 0, 0, 1)
+  double D, phase;                // diameter (mm), phase of the fall in [0, 1)
+  double wd, z_max;               // diameter (m), farthest depth shown
+};
+RR_HD SlotDraw slot_draw(const rr_sim_frame& sf, const double* dgrid, const double* cdf, int n_grid, uint32_t j) {
+  uint32_t a[4] = {j, 0u, 0u, 1u};
+  philox4x32_10(a, sf.key0, sf.key1);
+  SlotDraw s;
+  s.D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
+  s.phase = unit32(a[1]);
+  s.wd = s.D * 1e-3;
+  s.z_max = slot_z_max(sf, s.wd);
+  return s;
+}
+
+struct SlotFall {                 // where slot j is in its fall through a box of height wy at time index sf.frame
+  double v;                       // terminal velocity, m/s
+  double life, age, tau;          // completed falls g, the fraction of the current one, seconds since it began
+  double wind;                    // the life's wind (block 2)
+  uint32_t b[4];                  // the life's block 1: lateral start, start depth, the texture pick's word
+};
+RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, double D, double wy, double phase) {
+  SlotFall f;
+  f.v = terminal_velocity(D);
+  const double T = wy / f.v;
+  const double t = (double)sf.frame / cam_hz;
+  const double s = t / T + phase;
+  f.life = floor(s);
+  f.age = s - f.life;
+  f.tau = f.age * T;
+  uint32_t c[4];
+  life_counter(j, f.life, 1u, f.b);
+  life_counter(j, f.life, 2u, c);
+  philox4x32_10(f.b, sf.key0, sf.key1);
+  philox4x32_10(c, sf.key0, sf.key1);
+  f.wind = block_wind(c, sf.wind_sigma);
+  return f;
+}
+
 // Returns whether the particle is inside the frustum; `life` = g; *pick_word = word 2 of the life's block 1 (texture_pick).
 RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
                                Particle& p, double& life, uint32_t* pick_word = nullptr) {
-  uint32_t a[4] = {j, 0u, 0u, 1u};
-  philox4x32_10(a, sf.key0, sf.key1);
+  const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
-  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
-  const double phase = unit32(a[1]);
-  const double wd = D * 1e-3;
-  const double z_max = rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far);
   const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;   // frustum half-widths at unit depth
-  const double bx = hx * z_max, by = hy * z_max;
+  const double bx = hx * s.z_max, by = hy * s.z_max;
   const double wx = 2.0 * bx, wy = 2.0 * by;
-  const double v = terminal_velocity(D);
-  const double T = wy / v;
-  const double t = (double)sf.frame / cam_hz;
-  const double s = t / T + phase;
-  const double g = floor(s);
-  const double age = s - g;
-  const double tau = age * T;                               // seconds since the life began
-  const double g_hi = floor(g * (1.0 / 4294967296.0)), g_lo = g - g_hi * 4294967296.0;
-  uint32_t b[4] = {j, (uint32_t)g_lo, 1u, 2u + (uint32_t)g_hi}, c[4] = {j, (uint32_t)g_lo, 2u, 2u + (uint32_t)g_hi};
-  philox4x32_10(b, sf.key0, sf.key1);
-  philox4x32_10(c, sf.key0, sf.key1);
-  const double s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0;
-  const double wind = (s4 * 1.7320508075688772) * sf.wind_sigma;
-  const double qx = unit32(b[0]) + (wind * tau) / wx;       // box coordinates in units of the box: wrapped into [0, 1)
-  const double qz = unit32(b[1]) - (sf.speed_mps * tau) / z_max;
+  const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
+  const double qx = unit32(f.b[0]) + (f.wind * f.tau) / wx;   // box coordinates in units of the box: wrapped into [0, 1)
+  const double qz = unit32(f.b[1]) - (sf.speed_mps * f.tau) / s.z_max;
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   const double X = fx * wx - bx;
-  const double Y = by - age * wy;
-  const double zr = fz * z_max;                             // depth in the box
+  const double Y = by - f.age * wy;
+  const double zr = fz * s.z_max;                           // depth in the box
   const double ax = hx * zr, ay = hy * zr;
   const bool inside = -ax <= X && X <= ax && -ay <= Y && Y <= ay;
   const double depth = rr::dmax(zr, 0.05);
   const double Z = -depth;
   const double e = sf.exposure_s;
-  const double X2 = X + wind * e;
-  const double Y2 = Y - v * e;
+  const double X2 = X + f.wind * e;
+  const double Y2 = Y - f.v * e;
   const double Z2 = Z + sf.speed_mps * e;
-  const double depth2 = rr::dmax(-Z2, 0.05);
-  life = g;
-  if (pick_word) *pick_word = b[2];
+  life = f.life;
+  if (pick_word) *pick_word = f.b[2];
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
   p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
-  p.wd = wd;
-  p.ip1[0] = W / 2.0 + (sf.fpx * X) / depth;
-  p.ip1[1] = H / 2.0 + (sf.fpx * Y) / depth;
-  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
-  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
-  p.iw1 = (wd * sf.fpx) / depth;
-  p.iw2 = (wd * sf.fpx) / depth2;
+  p.wd = s.wd;
+  project(sf, X, Y, depth, s.wd, p.ip1, p.iw1);
+  project(sf, X2, Y2, rr::dmax(-Z2, 0.05), s.wd, p.ip2, p.iw2);
   return inside;
 }
 
@@ -178,44 +215,30 @@ struct RigSlot {
 
 RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
                          uint32_t j, RigSlot& q) {
-  uint32_t a[4] = {j, 0u, 0u, 1u};
-  philox4x32_10(a, sf.key0, sf.key1);
-  const double D = sample_diameter(dgrid, cdf, n_grid, unit32(a[0]));
-  const double phase = unit32(a[1]);
-  const double wd = D * 1e-3;
-  const double z_max = rr::dmin((wd * sf.fpx) / sf.min_px, sf.z_far);
-  const double b = box[0] * z_max;
-  const double by = box[1] * z_max + box[2];
+  const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
+  const double b = box[0] * s.z_max;
+  const double by = box[1] * s.z_max + box[2];
   const double w = 2.0 * b, wy = 2.0 * by;
-  const double v = terminal_velocity(D);
-  const double T = wy / v;
-  const double t = (double)sf.frame / cam_hz;
-  const double s = t / T + phase;
-  const double g = floor(s);
-  const double age = s - g;
-  const double tau = age * T;
-  const double g_hi = floor(g * (1.0 / 4294967296.0)), g_lo = g - g_hi * 4294967296.0;
-  uint32_t bb[4] = {j, (uint32_t)g_lo, 1u, 2u + (uint32_t)g_hi}, cc[4] = {j, (uint32_t)g_lo, 2u, 2u + (uint32_t)g_hi};
-  philox4x32_10(bb, sf.key0, sf.key1);
-  philox4x32_10(cc, sf.key0, sf.key1);
-  const double s4 = ((unit32(cc[0]) + unit32(cc[1])) + (unit32(cc[2]) + unit32(cc[3]))) - 2.0;
-  const double wind = (s4 * 1.7320508075688772) * sf.wind_sigma;
-  const double qx = unit32(bb[0]) + (wind * tau) / w;
-  const double qz = unit32(bb[1]) + (sf.speed_mps * tau) / w;   // the vehicle's motion: drops gain +speed in z
+  const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
+  const double qx = unit32(f.b[0]) + (f.wind * f.tau) / w;
+  const double qz = unit32(f.b[1]) + (sf.speed_mps * f.tau) / w;   // the vehicle's motion: drops gain +speed in z
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   q.X = fx * w - b;
-  q.Y = by - age * wy;
+  q.Y = by - f.age * wy;
   q.Z = fz * w - b;
-  q.wind = wind;
-  q.v = v;
-  q.wd = wd;
-  q.z_max = z_max;
-  q.life = g;
-  q.pick_word = bb[2];
+  q.wind = f.wind;
+  q.v = f.v;
+  q.wd = s.wd;
+  q.z_max = s.z_max;
+  q.life = f.life;
+  q.pick_word = f.b[2];
 }
 
-// slot q as the view (R row-major rig -> camera, c the camera's centre) sees it; returns whether the view keeps it
-RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R, const double* c, Particle& p) {
+// The START of slot q's streak as the view (R row-major rig -> camera, c the camera's centre) sees it: the lattice image nearest
+// to the camera, turned by R, culled, projected; d = the wrapped offset from the camera.  Returns whether the view keeps the slot.
+// The rig at rest (rig_view_particle) and the rig under a trajectory (with traj_view_end) share it; it keeps the name it had.
+RR_HD bool traj_view_start(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R, const double* c, double d[3],
+                          Particle& p) {
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
   const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;
   const double b = box[0] * q.z_max, w = 2.0 * b;
@@ -230,70 +253,42 @@ RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const dou
   const double ax = hx * zr, ay = hy * zr;
   const bool inside = zr > 0.0 && zr <= q.z_max && -ax <= xc && xc <= ax && -ay <= yc && yc <= ay;
   const double depth = rr::dmax(zr, 0.05);
-  const double e = sf.exposure_s;
-  const double ex = dx + q.wind * e, ey = dy + (-q.v) * e, ez = dz + sf.speed_mps * e;
+  d[0] = dx; d[1] = dy; d[2] = dz;
+  p.wp1[0] = xc; p.wp1[1] = yc; p.wp1[2] = -depth;
+  p.wd = q.wd;
+  project(sf, xc, yc, depth, q.wd, p.ip1, p.iw1);
+  return inside;
+}
+// The END of the streak: the offset e from the camera at the end of the exposure, turned by R and projected.
+RR_HD void rig_view_end(const rr_sim_frame& sf, const RigSlot& q, double ex, double ey, double ez, const double* R, Particle& p) {
   const double X2 = (R[0] * ex + R[1] * ey) + R[2] * ez;
   const double Y2 = (R[3] * ex + R[4] * ey) + R[5] * ez;
   const double Z2 = (R[6] * ex + R[7] * ey) + R[8] * ez;
-  const double depth2 = rr::dmax(-Z2, 0.05);
-  p.wp1[0] = xc; p.wp1[1] = yc; p.wp1[2] = -depth;
   p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
-  p.wd = q.wd;
-  p.ip1[0] = W / 2.0 + (sf.fpx * xc) / depth;
-  p.ip1[1] = H / 2.0 + (sf.fpx * yc) / depth;
-  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
-  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
-  p.iw1 = (q.wd * sf.fpx) / depth;
-  p.iw2 = (q.wd * sf.fpx) / depth2;
+  project(sf, X2, Y2, rr::dmax(-Z2, 0.05), q.wd, p.ip2, p.iw2);
+}
+// slot q through a view at rest: the start moved by the drop's velocity x exposure.  (NOT traj_view_end with c1 == c0: the bits
+// would agree, but the subtraction cannot be folded away and this is the path of every run without a trajectory.)
+RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R, const double* c, Particle& p) {
+  double d[3];
+  const bool inside = traj_view_start(sf, q, box, R, c, d, p);
+  const double e = sf.exposure_s;
+  rig_view_end(sf, q, d[0] + q.wind * e, d[1] + (-q.v) * e, d[2] + sf.speed_mps * e, R, p);
   return inside;
 }
 
 // ---- the rig model under a TRAJECTORY (rr_set_particle_trajectory, tools/particles.py make_rig_particles view_end=) ----
 // The view has one pose (R0, c0) at t_k and another (R1, c1) at t_k + exposure: the streak is the drop's path relative to a
-// camera that moves and turns while the shutter is open.  traj_view_start is rig_view_particle's first half word for word
-// (nearest lattice image, turn by R0, cull) and hands on the wrapped offset d; traj_view_end moves d by the drop's velocity
-// x exposure, subtracts the camera's own displacement c1 - c0 -- the same lattice image as the start, never wrapped again --
-// and turns it by R1.  With R1 == R0 and c1 == c0 the subtraction is - 0.0 and the pair gives rig_view_particle's bits.  Two
-// functions, so that a kernel calls the second for the lanes the cull left only and R1, c1 are not live across it.
-RR_HD bool traj_view_start(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R0, const double* c0, double d[3],
-                           Particle& p) {
-  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
-  const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;
-  const double b = box[0] * q.z_max, w = 2.0 * b;
-  double dx = q.X - c0[0], dz = q.Z - c0[2];
-  const double dy = q.Y - c0[1];
-  dx = dx - floor((dx + b) / w) * w;                      // the lattice image nearest to the camera at t_k
-  dz = dz - floor((dz + b) / w) * w;
-  const double xc = (R0[0] * dx + R0[1] * dy) + R0[2] * dz;
-  const double yc = (R0[3] * dx + R0[4] * dy) + R0[5] * dz;
-  const double zc = (R0[6] * dx + R0[7] * dy) + R0[8] * dz;
-  const double zr = -zc;
-  const double ax = hx * zr, ay = hy * zr;
-  const bool inside = zr > 0.0 && zr <= q.z_max && -ax <= xc && xc <= ax && -ay <= yc && yc <= ay;
-  const double depth = rr::dmax(zr, 0.05);
-  d[0] = dx; d[1] = dy; d[2] = dz;
-  p.wp1[0] = xc; p.wp1[1] = yc; p.wp1[2] = -depth;
-  p.wd = q.wd;
-  p.ip1[0] = W / 2.0 + (sf.fpx * xc) / depth;
-  p.ip1[1] = H / 2.0 + (sf.fpx * yc) / depth;
-  p.iw1 = (q.wd * sf.fpx) / depth;
-  return inside;
-}
+// camera that moves and turns while the shutter is open.  traj_view_start with (R0, c0) hands on the wrapped offset d;
+// traj_view_end moves d by the drop's velocity x exposure, subtracts the camera's own displacement c1 - c0 -- the same lattice
+// image as the start, never wrapped again -- and turns it by R1.  With R1 == R0 and c1 == c0 the subtraction is - 0.0 and the
+// pair gives rig_view_particle's bits.  Two calls, so that a kernel makes the second for the lanes the cull left only and R1, c1
+// are not live across it.
 RR_HD void traj_view_end(const rr_sim_frame& sf, const RigSlot& q, const double d[3], const double* c0, const double* R1, const double* c1,
                          Particle& p) {
-  const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
   const double e = sf.exposure_s;
-  const double ex = (d[0] + q.wind * e) - (c1[0] - c0[0]);
-  const double ey = (d[1] + (-q.v) * e) - (c1[1] - c0[1]);
-  const double ez = (d[2] + sf.speed_mps * e) - (c1[2] - c0[2]);
-  const double X2 = (R1[0] * ex + R1[1] * ey) + R1[2] * ez;
-  const double Y2 = (R1[3] * ex + R1[4] * ey) + R1[5] * ez;
-  const double Z2 = (R1[6] * ex + R1[7] * ey) + R1[8] * ez;
-  const double depth2 = rr::dmax(-Z2, 0.05);
-  p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
-  p.ip2[0] = W / 2.0 + (sf.fpx * X2) / depth2;
-  p.ip2[1] = H / 2.0 + (sf.fpx * Y2) / depth2;
-  p.iw2 = (q.wd * sf.fpx) / depth2;
+  rig_view_end(sf, q, (d[0] + q.wind * e) - (c1[0] - c0[0]), (d[1] + (-q.v) * e) - (c1[1] - c0[1]),
+               (d[2] + sf.speed_mps * e) - (c1[2] - c0[2]), R1, p);
 }
 
 // ceil(sqrt(n)) of a non-negative integer, exactly (np.ceil(np.sqrt(.)) of the loader gives the same: a non-integer root
@@ -303,6 +298,13 @@ RR_HD int64_t ceil_sqrt(int64_t n) {
   while (s * s < n) s++;
   while (s > 0 && (s - 1) * (s - 1) >= n) s--;
   return s;
+}
+
+// cos / sin of -(theta), theta = acos(-fy / n) the angle of the streak (fx, fy) = start - end, evaluated exactly: -fy / n, -|fx| / n
+RR_HD void exact_rotation(double fx, double fy, double& c, double& s) {
+  const double n1 = sqrt(fx * fx + fy * fy);
+  c = (fx / n1) * 0.0 + (fy / n1) * -1.0;
+  s = -(fabs(fx) / n1);
 }
 
 // The loader's derived fields (DBManager.load_streaks_from_xml, bad_weather.py:208-241) and the frame filter
@@ -336,15 +338,12 @@ RR_HD bool derive_drop(const Particle& p, int render_scale, int W, int H, rr_dro
   d.wps[0] = p.wp1[0]; d.wps[1] = p.wp1[1]; d.wps[2] = p.wp1[2] * -1.0;      // bad_weather.py:223-224
   d.wpe[0] = p.wp2[0]; d.wpe[1] = p.wp2[1]; d.wpe[2] = p.wp2[2] * -1.0;
   // rotation of the streak texture (non-Big): cos / sin of -(theta) with theta = acos(-dy / n) (generator.py:138-145,163)
-  // evaluated exactly: cos = -dy / n, sin = -|dx| / n, n = |start - end| over the integer positions
+  // evaluated exactly (exact_rotation) over the integer positions
   if (type == 0) {
     d.rot_cos = 1.0;
     d.rot_sin = 0.0;
   } else {
-    const double fx = (double)ddx, fy = (double)ddy;
-    const double n1 = sqrt(fx * fx + fy * fy);
-    d.rot_cos = (fx / n1) * 0.0 + (fy / n1) * -1.0;
-    d.rot_sin = -(fabs(fx) / n1);
+    exact_rotation((double)ddx, (double)ddy, d.rot_cos, d.rot_sin);
   }
   const int64_t m = H > W ? H : W;
   const bool in_s = 0 <= x0 && x0 < W && 0 <= y0 && y0 < H, in_e = 0 <= x1 && x1 < W && 0 <= y1 && y1 < H;
@@ -367,15 +366,14 @@ RR_HD double polar_factor(double r2) { return sqrt(-2.0 * rr::det_log(r2) / r2);
 RR_HD double noise_degrees(double g, double noise_std, double noise_scale) { return (0.0 + noise_std * g) * noise_scale; }
 
 // a kept non-Big drop turned by noise_deg: rotation terms cos / sin(-(theta + noise) * pi / 180) as the angle sum of the exact
-// cos / sin(-theta) = -dy / n, -|dx| / n (derive_drop) of the end points BEFORE the turn and det_sincos(noise); the end
+// cos / sin(-theta) = -dy / n, -|dx| / n (exact_rotation) of the end points BEFORE the turn and det_sincos(noise); the end
 // points turned about their midpoint in hip_backend.pack_frame's operation order, truncated toward zero (numpy's int64 store)
 RR_HD void noise_rotate(rr_drop& d, double noise_deg) {
   double sn, cn;
   rr::det_sincos(noise_deg * 0.017453292519943295, sn, cn);   // np.deg2rad: x * (pi / 180)
   const double sx = (double)d.x0, sy = (double)d.y0, ex = (double)d.x1, ey = (double)d.y1;
-  const double fx = sx - ex, fy = sy - ey;
-  const double n1 = sqrt(fx * fx + fy * fy);
-  const double c0 = (fx / n1) * 0.0 + (fy / n1) * -1.0, s0 = -(fabs(fx) / n1);
+  double c0, s0;
+  exact_rotation(sx - ex, sy - ey, c0, s0);
   d.rot_cos = c0 * cn + s0 * sn;
   d.rot_sin = s0 * cn - c0 * sn;
   const double mx = (ex + sx) / 2.0, my = (ey + sy) / 2.0;
@@ -396,7 +394,7 @@ RR_HD double jitter_deviate(const uint32_t w[4]) {
 }
 // Block 3 of the drop under the frame's key.  The generators read blocks 0, 1 and 2 of a counter (make_particle:
 // (i, frame, 0 | 1 | 2, 0); the field and rig models: (j, 0, 0, 1) and the life's (j, g_lo, 1 | 2, 2 + g_hi)); nothing else
-// reads a block 3.  i.i.d. model: particle i of frame sf.frame.
+// reads a block 3 (life_counter).  i.i.d. model: particle i of frame sf.frame.
 RR_HD double particle_jitter(const rr_sim_frame& sf, uint32_t i) {
   uint32_t w[4] = {i, sf.frame, 3u, 0u};
   philox4x32_10(w, sf.key0, sf.key1);
@@ -404,8 +402,8 @@ RR_HD double particle_jitter(const rr_sim_frame& sf, uint32_t i) {
 }
 // field and rig models: slot j in its life g -- the same tilt in every frame of the life and in every view
 RR_HD double life_jitter(const rr_sim_frame& sf, uint32_t j, double life) {
-  const double g_hi = floor(life * (1.0 / 4294967296.0)), g_lo = life - g_hi * 4294967296.0;
-  uint32_t w[4] = {j, (uint32_t)g_lo, 3u, 2u + (uint32_t)g_hi};
+  uint32_t w[4];
+  life_counter(j, life, 3u, w);
   philox4x32_10(w, sf.key0, sf.key1);
   return jitter_deviate(w);
 }

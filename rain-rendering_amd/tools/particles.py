@@ -331,17 +331,21 @@ class FrameCamera:
         self.hz = options["cam_hz"]
 
 
-def expected_count(cam, fallrate, min_px=1.0, z_far=15.0, margin=0.05, n_grid=N_GRID):
-    """(expected visible drops per frame, diameter grid, its sampling CDF, z_max per diameter)."""
-    lam = mp_lambda(fallrate)
-    d = np.linspace(D_MIN, D_MAX, n_grid)
-    z_max = np.minimum(d * 1e-3 * cam.fpx / min_px, z_far)
-    area = (1 + 2 * margin) ** 2 * cam.W * cam.H / cam.fpx ** 2          # frustum cross-section at unit depth
-    dens = N0 * det_exp(-lam * d) * area * z_max ** 3 / 3.0              # drops per mm of diameter
+def _diameter_cdf(dens, d):
+    """(total, sampling CDF) of a density `dens` (drops per mm of diameter) on the grid `d`: trapezoid rule."""
     cdf = np.concatenate([[0.0], np.cumsum(0.5 * (dens[1:] + dens[:-1]) * np.diff(d))])
     total = float(cdf[-1])
     cdf = cdf / cdf[-1]
     cdf[-1] = 1.0
+    return total, cdf
+
+
+def expected_count(cam, fallrate, min_px=1.0, z_far=15.0, margin=0.05, n_grid=N_GRID):
+    """(expected visible drops per frame, diameter grid, its sampling CDF, z_max per diameter)."""
+    d = np.linspace(D_MIN, D_MAX, n_grid)
+    z_max = np.minimum(d * 1e-3 * cam.fpx / min_px, z_far)
+    area = (1 + 2 * margin) ** 2 * cam.W * cam.H / cam.fpx ** 2          # frustum cross-section at unit depth
+    total, cdf = _diameter_cdf(N0 * det_exp(-mp_lambda(fallrate) * d) * area * z_max ** 3 / 3.0, d)
     return total, d, cdf, z_max
 
 
@@ -378,18 +382,26 @@ def texture_pick(w):
     return ((np.asarray(w).astype(np.uint64) * np.uint64(10)) >> np.uint64(32)).astype(np.int64)
 
 
+def _life_counter(j, life, block):
+    """rr_particles.h life_counter: the counter (j, g mod 2^32, block, 2 + g / 2^32) of block `block` of the slots' lives g."""
+    g = np.asarray(life, np.float64)
+    g_hi = np.floor(g * (1.0 / 4294967296.0))
+    g_lo = g - g_hi * 4294967296.0
+    return j, g_lo.astype(np.uint64), block, np.uint64(2) + g_hi.astype(np.uint64)
+
+
+def _drop_block(seed, pid, block, frame, life):
+    """Philox block `block` of the drops `pid`: (pid, frame, block, 0) of the i.i.d. model, or the life's (_life_counter)."""
+    j = np.asarray(pid).astype(np.uint64)
+    counter = (j, int(frame) & 0xFFFFFFFF, block, 0) if life is None else _life_counter(j, life, block)
+    return philox4x32(*counter, *_key(seed))
+
+
 def counter_picks(seed, pid, frame=None, life=None):
     """The counter-based texture pick (0 .. 9) of particles `pid`: texture_pick of word 2 of the drop's Philox block 1.
     i.i.d. model: `frame` = the simulated frame, block (pid, frame, 1, 0).  Field and rig models: `life` = the life g of every
     slot `pid` (make_field_particles / make_rig_particles return it), block (pid, g_lo, 1, 2 + g_hi)."""
-    j = np.asarray(pid).astype(np.uint64)
-    k0, k1 = _key(seed)
-    if life is None:
-        return texture_pick(philox4x32(j, int(frame) & 0xFFFFFFFF, 1, 0, k0, k1)[2])
-    g = np.asarray(life, np.float64)
-    g_hi = np.floor(g * (1.0 / 4294967296.0))
-    g_lo = g - g_hi * 4294967296.0
-    return texture_pick(philox4x32(j, g_lo.astype(np.uint64), 1, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)[2])
+    return texture_pick(_drop_block(seed, pid, 1, frame, life)[2])
 
 
 def jitter_deviate(w0, w1, w2):
@@ -407,15 +419,7 @@ def counter_jitter(seed, pid, frame=None, life=None):
     """The streak-jitter deviate (standard normal) of particles `pid`: jitter_deviate of the drop's Philox block 3, which no
     other draw reads.  i.i.d. model: `frame` = the simulated frame, block (pid, frame, 3, 0).  Field and rig models: `life` = the
     life g of every slot `pid`, block (pid, g_lo, 3, 2 + g_hi) -- laid out like the life's blocks 1 and 2."""
-    j = np.asarray(pid).astype(np.uint64)
-    k0, k1 = _key(seed)
-    if life is None:
-        w = philox4x32(j, int(frame) & 0xFFFFFFFF, 3, 0, k0, k1)
-    else:
-        g = np.asarray(life, np.float64)
-        g_hi = np.floor(g * (1.0 / 4294967296.0))
-        g_lo = g - g_hi * 4294967296.0
-        w = philox4x32(j, g_lo.astype(np.uint64), 3, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)
+    w = _drop_block(seed, pid, 3, frame, life)
     return jitter_deviate(w[0], w[1], w[2])
 
 
@@ -468,12 +472,38 @@ def frame_counts(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, ma
     return out
 
 
+def _slot_z_max(cam, wd, min_px, z_far):
+    """rr_particles.h slot_z_max: only drops that can show at least min_px wide are simulated (wd: the diameter in metres)."""
+    return np.minimum((wd * cam.fpx) / min_px, z_far)
+
+
+def _block_wind(c, wind_sigma):
+    """rr_particles.h block_wind: a centred sum of the block's four uniforms scaled to unit variance, times wind_sigma."""
+    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
+    return (s4 * 1.7320508075688772) * wind_sigma
+
+
+def _project(cam, X, Y, depth, wd):
+    """rr_particles.h project: (sensor position (n, 2), image width) of one streak end at camera-frame (X, Y), `depth` away."""
+    W, H = float(cam.W), float(cam.H)
+    return np.stack([W / 2.0 + (cam.fpx * X) / depth, H / 2.0 + (cam.fpx * Y) / depth], axis=1), (wd * cam.fpx) / depth
+
+
+def _records(n, wp1, wp2, wd, ip1, iw1, ip2, iw2):
+    rec = np.zeros(n, PARTICLE_DTYPE)
+    rec['pid'] = np.arange(n)
+    rec['wp1'] = np.stack(wp1, axis=1)
+    rec['wp2'] = np.stack(wp2, axis=1)
+    rec['wd1'] = rec['wd2'] = wd
+    rec['ip1'], rec['iw1'], rec['ip2'], rec['iw2'] = ip1, iw1, ip2, iw2
+    return rec
+
+
 def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0):
     """The n particles of simulated frame `frame` as PARTICLE_DTYPE records: the numpy statement of
     rr_particles.h make_particle (same operations, same order)."""
-    rec = np.zeros(n, PARTICLE_DTYPE)
     if n == 0:
-        return rec
+        return np.zeros(0, PARTICLE_DTYPE)
     i = np.arange(n, dtype=np.uint64)
     k0, k1 = _key(seed)
     a = philox4x32(i, frame, 0, 0, k0, k1)
@@ -482,7 +512,7 @@ def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05,
     W, H = float(cam.W), float(cam.H)
     D = sample_diameter(dgrid, cdf, unit32(a[0]))                                # mm
     wd = D * 1e-3
-    z_max = np.minimum((wd * cam.fpx) / min_px, z_far)
+    z_max = _slot_z_max(cam, wd, min_px, z_far)
     u1, u2, u3 = unit32(a[1]), unit32(a[2]), unit32(a[3])
     depth = np.maximum(z_max * np.maximum(np.maximum(u1, u2), u3), 0.05)        # uniform in the frustum volume
     lo_x, hi_x, lo_y, hi_y = -margin * W, (1.0 + margin) * W, -margin * H, (1.0 + margin) * H
@@ -491,66 +521,59 @@ def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05,
     X = ((px - W / 2.0) * depth) / cam.fpx
     Y = ((py - H / 2.0) * depth) / cam.fpx
     Z = -depth
-    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
-    wind = (s4 * 1.7320508075688772) * wind_sigma
+    wind = _block_wind(c, wind_sigma)
     t = cam.exposure
     X2 = X + wind * t
     Y2 = Y - terminal_velocity(D) * t
     Z2 = Z + cam.speed * t
-    depth2 = np.maximum(-Z2, 0.05)
-    rec['pid'] = np.arange(n)
-    rec['wp1'] = np.stack([X, Y, Z], axis=1)
-    rec['wp2'] = np.stack([X2, Y2, Z2], axis=1)
-    rec['wd1'] = rec['wd2'] = wd
-    rec['ip1'] = np.stack([px, py], axis=1)
-    rec['ip2'] = np.stack([W / 2.0 + (cam.fpx * X2) / depth2, H / 2.0 + (cam.fpx * Y2) / depth2], axis=1)
-    rec['iw1'] = (wd * cam.fpx) / depth
-    rec['iw2'] = (wd * cam.fpx) / depth2
-    return rec
+    ip2, iw2 = _project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd)
+    return _records(n, [X, Y, Z], [X2, Y2, Z2], wd, np.stack([px, py], axis=1), (wd * cam.fpx) / depth, ip2, iw2)
 
 
 def _settings_key(cam, rate):
     return (rate, cam.fpx, cam.W, cam.H)
 
 
+def _per_settings(options, fallrate, n_frames, min_px, z_far, margin, make):
+    """make(cam, rate, n) once per distinct settings (fall rate, camera) of the run, n = the distinct settings before it:
+    (what it returned in first-use order, its index per simulated frame)."""
+    keys, made, idx = {}, [], np.zeros(n_frames, np.int32)
+    for k in range(n_frames):
+        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
+        tk = _settings_key(cam, rate)
+        if tk not in keys:
+            keys[tk] = len(made)
+            made.append(make(cam, rate, len(made)))
+        idx[k] = keys[tk]
+    return made, idx
+
+
+def _poisson(seed, salt, mean):
+    return int(np.random.RandomState((int(seed) * 1000003 + salt) % (2 ** 32)).poisson(mean))
+
+
 def field_slot_counts(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, count=None):
     """Particle slots of the field model per simulated frame: ONE Poisson draw per distinct settings (fall rate, camera)
     of the run around three times the expected count -- frames with the same settings share their slots -- or
     3 * `count` (`count`: the expected number of particles in the frustum, as for the i.i.d. model)."""
-    out = np.zeros(n_frames, np.int64)
-    drawn = {}
-    for k in range(n_frames):
-        if count is not None:
-            out[k] = 3 * int(count)
-            continue
-        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
-        tk = _settings_key(cam, rate)
-        if tk not in drawn:
-            mean = expected_count(cam, rate, min_px, z_far, margin)[0]
-            drawn[tk] = int(np.random.RandomState((int(seed) * 1000003 + 999983 + len(drawn)) % (2 ** 32)).poisson(3.0 * mean))
-        out[k] = drawn[tk]
-    return out
+    if count is not None:
+        return np.full(n_frames, 3 * int(count), np.int64)
+    drawn, idx = _per_settings(options, fallrate, n_frames, min_px, z_far, margin, lambda cam, rate, n: _poisson(
+        seed, 999983 + n, 3.0 * expected_count(cam, rate, min_px, z_far, margin)[0]))
+    return np.asarray(drawn, np.int64)[idx]
 
 
-def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                         cull=True):
-    """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
-    of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
-    life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
-    rec = np.zeros(n_slots, PARTICLE_DTYPE)
-    if n_slots == 0:
-        return rec, np.zeros(0, np.float64)
-    j = np.arange(n_slots, dtype=np.uint64)
-    k0, k1 = _key(seed)
-    a = philox4x32(j, 0, 0, 1, k0, k1)
-    W, H = float(cam.W), float(cam.H)
+def _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far):
+    """rr_particles.h slot_draw: what slot j is for good, from block (j, 0, 0, 1): (D in mm, phase, wd in m, z_max)."""
+    a = philox4x32(j, 0, 0, 1, *key)
     D = sample_diameter(dgrid, cdf, unit32(a[0]))
-    phase = unit32(a[1])
     wd = D * 1e-3
-    z_max = np.minimum((wd * cam.fpx) / min_px, z_far)
-    hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
-    bx, by = hx * z_max, hy * z_max
-    wx, wy = 2.0 * bx, 2.0 * by
+    return D, unit32(a[1]), wd, _slot_z_max(cam, wd, min_px, z_far)
+
+
+def _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma):
+    """rr_particles.h slot_fall: where slot j is in its fall through a box of height wy at time index k:
+    (v, life g, age, tau, the life's block 1, the life's wind)."""
     v = terminal_velocity(D)
     T = wy / v
     t = float(int(k) & 0xFFFFFFFF) / float(cam_hz)
@@ -558,13 +581,26 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     g = np.floor(s)
     age = s - g
     tau = age * T
-    g_hi = np.floor(g * (1.0 / 4294967296.0))
-    g_lo = g - g_hi * 4294967296.0
-    c1, c3 = g_lo.astype(np.uint64), np.uint64(2) + g_hi.astype(np.uint64)
-    b = philox4x32(j, c1, 1, c3, k0, k1)
-    c = philox4x32(j, c1, 2, c3, k0, k1)
-    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
-    wind = (s4 * 1.7320508075688772) * wind_sigma
+    b = philox4x32(*_life_counter(j, g, 1), *key)
+    c = philox4x32(*_life_counter(j, g, 2), *key)
+    return v, g, age, tau, b, _block_wind(c, wind_sigma)
+
+
+def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
+                         cull=True):
+    """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
+    of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
+    life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
+    if n_slots == 0:
+        return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
+    j = np.arange(n_slots, dtype=np.uint64)
+    key = _key(seed)
+    D, phase, wd, z_max = _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far)
+    W, H = float(cam.W), float(cam.H)
+    hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
+    bx, by = hx * z_max, hy * z_max
+    wx, wy = 2.0 * bx, 2.0 * by
+    v, g, age, tau, b, wind = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
     qx = unit32(b[0]) + (wind * tau) / wx
     qz = unit32(b[1]) - (cam.speed * tau) / z_max
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
@@ -579,15 +615,7 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     X2 = X + wind * e
     Y2 = Y - v * e
     Z2 = Z + cam.speed * e
-    depth2 = np.maximum(-Z2, 0.05)
-    rec['pid'] = np.arange(n_slots)
-    rec['wp1'] = np.stack([X, Y, Z], axis=1)
-    rec['wp2'] = np.stack([X2, Y2, Z2], axis=1)
-    rec['wd1'] = rec['wd2'] = wd
-    rec['ip1'] = np.stack([W / 2.0 + (cam.fpx * X) / depth, H / 2.0 + (cam.fpx * Y) / depth], axis=1)
-    rec['ip2'] = np.stack([W / 2.0 + (cam.fpx * X2) / depth2, H / 2.0 + (cam.fpx * Y2) / depth2], axis=1)
-    rec['iw1'] = (wd * cam.fpx) / depth
-    rec['iw2'] = (wd * cam.fpx) / depth2
+    rec = _records(n_slots, [X, Y, Z], [X2, Y2, Z2], wd, *_project(cam, X, Y, depth, wd), *_project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd))
     if cull:
         return rec[inside], g[inside]
     return rec, g
@@ -597,16 +625,10 @@ def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin
     """Velocity (n, 3) in m/s (x right, y up, z towards the camera) of the given slots in the given lives, and the slots'
     boxes (n, 3): full width, full height, depth -- what tests compare a track's displacement with."""
     j = np.asarray(slots, np.uint64)
-    g = np.asarray(lives, np.float64)
-    k0, k1 = _key(seed)
-    D = sample_diameter(dgrid, cdf, unit32(philox4x32(j, 0, 0, 1, k0, k1)[0]))
-    z_max = np.minimum(((D * 1e-3) * cam.fpx) / min_px, z_far)
+    key = _key(seed)
+    D, _, _, z_max = _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far)
     hx, hy = ((0.5 + margin) * float(cam.W)) / cam.fpx, ((0.5 + margin) * float(cam.H)) / cam.fpx
-    g_hi = np.floor(g * (1.0 / 4294967296.0))
-    g_lo = g - g_hi * 4294967296.0
-    c = philox4x32(j, g_lo.astype(np.uint64), 2, np.uint64(2) + g_hi.astype(np.uint64), k0, k1)
-    s4 = ((unit32(c[0]) + unit32(c[1])) + (unit32(c[2]) + unit32(c[3]))) - 2.0
-    wind = (s4 * 1.7320508075688772) * wind_sigma
+    wind = _block_wind(philox4x32(*_life_counter(j, lives, 2), *key), wind_sigma)
     vel = np.stack([wind, -terminal_velocity(D), np.full(len(j), float(cam.speed))], axis=1)
     return vel, np.stack([2.0 * (hx * z_max), 2.0 * (hy * z_max), z_max], axis=1)
 
@@ -629,16 +651,11 @@ def rig_expected_count(cam, fallrate, box, min_px=1.0, z_far=15.0, n_grid=N_GRID
     """(expected number of SLOTS, diameter grid, its sampling CDF, z_max per diameter) of the rig model: N(D) times the volume
     of the slot's box (2 r z_max)^2 (2 (r_y z_max + o_y)), `box` = (r, r_y, o_y)."""
     r, r_y, o_y = (float(v) for v in box)
-    lam = mp_lambda(fallrate)
     d = np.linspace(D_MIN, D_MAX, n_grid)
     z_max = np.minimum(d * 1e-3 * cam.fpx / min_px, z_far)
     w = 2.0 * (r * z_max)
     vol = (w * w) * (2.0 * (r_y * z_max + o_y))
-    dens = N0 * det_exp(-lam * d) * vol
-    cdf = np.concatenate([[0.0], np.cumsum(0.5 * (dens[1:] + dens[:-1]) * np.diff(d))])
-    total = float(cdf[-1])
-    cdf = cdf / cdf[-1]
-    cdf[-1] = 1.0
+    total, cdf = _diameter_cdf(N0 * det_exp(-mp_lambda(fallrate) * d) * vol, d)
     return total, d, cdf, z_max
 
 
@@ -659,64 +676,38 @@ def rig_slot_counts(options, fallrate, n_frames, rig, seed=0, min_px=1.0, z_far=
     """Particle slots of the rig model per simulated frame: ONE Poisson draw per distinct settings of the run around the
     expected number of slots (rig_expected_count) -- or, with `count` (the expected number of particles in ONE view's frustum,
     as for the other models), count x expected slots / expected particles, rounded."""
-    out = np.zeros(n_frames, np.int64)
-    drawn = {}
-    for k in range(n_frames):
-        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
-        tk = _settings_key(cam, rate)
-        if tk not in drawn:
-            mean = rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far)[0]
-            if count is not None:
-                drawn[tk] = int(round(int(count) * mean / expected_count(cam, rate, min_px, z_far, margin)[0]))
-            else:
-                drawn[tk] = int(np.random.RandomState((int(seed) * 1000003 + 999979 + len(drawn)) % (2 ** 32)).poisson(mean))
-        out[k] = drawn[tk]
-    return out
+    def draw(cam, rate, n):
+        mean = rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far)[0]
+        if count is not None:
+            return int(round(int(count) * mean / expected_count(cam, rate, min_px, z_far, margin)[0]))
+        return _poisson(seed, 999979 + n, mean)
+    drawn, idx = _per_settings(options, fallrate, n_frames, min_px, z_far, margin, draw)
+    return np.asarray(drawn, np.int64)[idx]
+
+
+def _tables(options, fallrate, n_frames, min_px, z_far, margin, table):
+    """(d_grid, cdf [n_tables, N_GRID], table index per frame): table(cam, rate) = (_, d_grid, cdf, _) per distinct settings."""
+    tabs, idx = _per_settings(options, fallrate, n_frames, min_px, z_far, margin, lambda cam, rate, n: table(cam, rate))
+    return (tabs[-1][1] if tabs else None), np.ascontiguousarray(np.stack([t[2] for t in tabs])), idx
 
 
 def rig_tables(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=0.05):
     """diameter_tables for the rig model: (d_grid, cdf [n_tables, N_GRID], table index per frame)."""
-    keys, tabs, idx = {}, [], np.zeros(n_frames, np.int32)
-    dgrid = None
-    for k in range(n_frames):
-        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
-        tk = _settings_key(cam, rate)
-        if tk not in keys:
-            _, dgrid, cdf, _ = rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far)
-            keys[tk] = len(tabs)
-            tabs.append(cdf)
-        idx[k] = keys[tk]
-    return dgrid, np.ascontiguousarray(np.stack(tabs)), idx
+    return _tables(options, fallrate, n_frames, min_px, z_far, margin,
+                   lambda cam, rate: rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far))
 
 
 def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0):
-    """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters: dict(D, z_max, b
-    (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
+    """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters (rr_particles.h
+    make_rig_slot): dict(D, z_max, b (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
     r, r_y, o_y = (float(v) for v in box)
     j = np.arange(n_slots, dtype=np.uint64)
-    k0, k1 = _key(seed)
-    a = philox4x32(j, 0, 0, 1, k0, k1)
-    D = sample_diameter(dgrid, cdf, unit32(a[0]))
-    phase = unit32(a[1])
-    wd = D * 1e-3
-    z_max = np.minimum((wd * cam.fpx) / min_px, z_far)
+    key = _key(seed)
+    D, phase, wd, z_max = _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far)
     b = r * z_max
     by = r_y * z_max + o_y
     w, wy = 2.0 * b, 2.0 * by
-    v = terminal_velocity(D)
-    T = wy / v
-    t = float(int(k) & 0xFFFFFFFF) / float(cam_hz)
-    s = t / T + phase
-    g = np.floor(s)
-    age = s - g
-    tau = age * T
-    g_hi = np.floor(g * (1.0 / 4294967296.0))
-    g_lo = g - g_hi * 4294967296.0
-    c1, c3 = g_lo.astype(np.uint64), np.uint64(2) + g_hi.astype(np.uint64)
-    bb = philox4x32(j, c1, 1, c3, k0, k1)
-    cc = philox4x32(j, c1, 2, c3, k0, k1)
-    s4 = ((unit32(cc[0]) + unit32(cc[1])) + (unit32(cc[2]) + unit32(cc[3]))) - 2.0
-    wind = (s4 * 1.7320508075688772) * wind_sigma
+    v, g, age, tau, bb, wind = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
     qx = unit32(bb[0]) + (wind * tau) / w
     qz = unit32(bb[1]) + (cam.speed * tau) / w
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
@@ -730,7 +721,7 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
 def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
                        cull=True, image=(0, 0), view_end=None):
     """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
-    statement of rr_particles.h make_rig_slot + rig_view_particle (same operations, same order).  `box` = (r, r_y, o_y).
+    statement of rr_particles.h make_rig_slot + rig_view_particle (traj_view_start, rig_view_end; same operations, same order).  `box` = (r, r_y, o_y).
     Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
     view keeps, in ascending slot order.  `image` = (ix, iz) looks at the lattice image ix, iz periods away from the nearest
     one instead (tests: with the host's r no such image is ever inside the frustum).
@@ -738,9 +729,8 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
     `view_end` = (R1, c1): the view's pose at the END of the exposure (a trajectory, module docstring; rr_particles.h
     traj_view_start + traj_view_end): the streak's end is R1 ((d + velocity x exposure) - (c1 - c)), d the start's wrapped
     offset.  With view_end equal to `view` the subtraction is - 0.0: the bits of view_end=None."""
-    rec = np.zeros(n_slots, PARTICLE_DTYPE)
     if n_slots == 0:
-        return rec, np.zeros(0, np.float64)
+        return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
     R = [float(v) for v in np.asarray(view[0], np.float64).reshape(9)]
     c = [float(v) for v in np.asarray(view[1], np.float64).reshape(3)]
     st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far)
@@ -776,15 +766,8 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
     X2 = (R[0] * ex + R[1] * ey) + R[2] * ez
     Y2 = (R[3] * ex + R[4] * ey) + R[5] * ez
     Z2 = (R[6] * ex + R[7] * ey) + R[8] * ez
-    depth2 = np.maximum(-Z2, 0.05)
-    rec['pid'] = np.arange(n_slots)
-    rec['wp1'] = np.stack([xc, yc, -depth], axis=1)
-    rec['wp2'] = np.stack([X2, Y2, Z2], axis=1)
-    rec['wd1'] = rec['wd2'] = wd
-    rec['ip1'] = np.stack([W / 2.0 + (cam.fpx * xc) / depth, H / 2.0 + (cam.fpx * yc) / depth], axis=1)
-    rec['ip2'] = np.stack([W / 2.0 + (cam.fpx * X2) / depth2, H / 2.0 + (cam.fpx * Y2) / depth2], axis=1)
-    rec['iw1'] = (wd * cam.fpx) / depth
-    rec['iw2'] = (wd * cam.fpx) / depth2
+    rec = _records(n_slots, [xc, yc, -depth], [X2, Y2, Z2], wd, *_project(cam, xc, yc, depth, wd),
+                   *_project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd))
     if cull:
         return rec[inside], st['life'][inside]
     return rec, st['life']
@@ -811,12 +794,12 @@ def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, m
     _, dgrid, cdf, _ = rig_expected_count(cam, rate, run_box, min_px, z_far)
     n_slots = int(rig_slot_counts(options, fallrate, ks + 1, src, seed, min_px, z_far, margin, count)[ks])
     box = run_box if box is None else tuple(float(v) for v in box)
-    if trajectory is None:
-        return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, rig.views[int(view)], box, wind_sigma, margin, min_px,
-                                  z_far, cull, image)
-    po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
-    return make_rig_particles(_traj_cam(cam), dgrid, cdf, n_slots, k, seed, cam.hz, (po['R0'], po['c0']), box, wind_sigma, margin,
-                              min_px, z_far, cull, image, view_end=(po['R1'], po['c1']))
+    pose, view_end = rig.views[int(view)], None
+    if trajectory is not None:
+        po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
+        cam, pose, view_end = _traj_cam(cam), (po['R0'], po['c0']), (po['R1'], po['c1'])
+    return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, pose, box, wind_sigma, margin, min_px, z_far, cull, image,
+                              view_end=view_end)
 
 
 def rig_run_sims(sims, k_idx, n_active):
@@ -843,7 +826,7 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
     tables = {}
     for k in range(n_frames):
         cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
-        tk = (rate, cam.fpx, cam.W, cam.H)
+        tk = _settings_key(cam, rate)
         if tk not in tables:
             tables[tk] = expected_count(cam, rate, min_px, z_far, margin)
         _, dgrid, cdf, _ = tables[tk]
@@ -862,17 +845,7 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
 # ---- the same run described to the library (rr_set_particle_tables / rr_sim_frame) -----------------------------------
 def diameter_tables(options, fallrate, n_frames, min_px=1.0, z_far=15.0, margin=0.05):
     """(d_grid [N_GRID], cdf [n_tables, N_GRID], table index per frame): one table per distinct (fall rate, camera)."""
-    keys, tabs, idx = {}, [], np.zeros(n_frames, np.int32)
-    dgrid = None
-    for k in range(n_frames):
-        cam, rate = _frame_settings(options, fallrate, k, min_px, z_far, margin)
-        tk = (rate, cam.fpx, cam.W, cam.H)
-        if tk not in keys:
-            _, dgrid, cdf, _ = expected_count(cam, rate, min_px, z_far, margin)
-            keys[tk] = len(tabs)
-            tabs.append(cdf)
-        idx[k] = keys[tk]
-    return dgrid, np.ascontiguousarray(np.stack(tabs)), idx
+    return _tables(options, fallrate, n_frames, min_px, z_far, margin, lambda cam, rate: expected_count(cam, rate, min_px, z_far, margin))
 
 
 def sim_frames(options, fallrate, n_frames, render_scale=1, seed=0, draw_seeds=None, min_px=1.0, z_far=15.0, margin=0.05,
@@ -933,25 +906,22 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
                                speed=float(s['speed_mps'])))()
     seed = int(s['key0']) | (int(s['key1']) << 32)
     life = None
-    if model == 'rig' and trajectory is not None:
-        po = trajectory.compose(rig, cam.exposure)
-        if int(s['frame']) >= len(po):
-            raise ValueError("time index %d is outside the trajectory's %d poses" % (int(s['frame']), len(po)))
-        po = po[int(s['frame']), int(view)]
-        rec, life = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
-                                       (po['R0'], po['c0']), _rig_box(trajectory.bind(rig), cam, float(s['margin'])),
-                                       float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']),
-                                       view_end=(po['R1'], po['c1']))
-    elif model == 'rig':
-        rec, life = make_rig_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
-                                    rig.views[int(view)], _rig_box(rig, cam, float(s['margin'])), float(s['wind_sigma']),
-                                    float(s['margin']), float(s['min_px']), float(s['z_far']))
+    k, margin = int(s['frame']), float(s['margin'])
+    tab, n = cdf[int(s['table'])], int(s['n_particles'])
+    kw = dict(wind_sigma=float(s['wind_sigma']), margin=margin, min_px=float(s['min_px']), z_far=float(s['z_far']))
+    if model == 'rig':
+        pose, box, view_end = rig.views[int(view)] if trajectory is None else None, rig, None
+        if trajectory is not None:
+            po = trajectory.compose(rig, cam.exposure)
+            if k >= len(po):
+                raise ValueError("time index %d is outside the trajectory's %d poses" % (k, len(po)))
+            po = po[k, int(view)]
+            pose, box, view_end = (po['R0'], po['c0']), trajectory.bind(rig), (po['R1'], po['c1'])
+        rec, life = make_rig_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), pose, _rig_box(box, cam, margin), view_end=view_end, **kw)
     elif model == 'field':
-        rec, life = make_field_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(cam_hz),
-                                         float(s['wind_sigma']), float(s['margin']), float(s['min_px']), float(s['z_far']))
+        rec, life = make_field_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), **kw)
     else:
-        rec = make_particles(cam, dgrid, cdf[int(s['table'])], int(s['n_particles']), int(s['frame']), seed, float(s['wind_sigma']),
-                             float(s['margin']), float(s['min_px']), float(s['z_far']))
+        rec = make_particles(cam, dgrid, tab, n, k, seed, **kw)
     fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
     fr[0] = (0, 0, 0, len(rec), 0, len(rec))
     m = bw.DBManager()
@@ -1018,24 +988,15 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     for i, s in enumerate(sims):
         table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory)
         p = int(s['run_pos'])
-        if jitter:
+        if jitter or draws == 'counter':
             if p != 0:
-                raise ValueError("streak jitter: run_pos must be 0 (frame %d)" % i)
+                raise ValueError("%s: run_pos must be 0 (frame %d)" % ("streak jitter" if jitter else "counter draws", i))
             rec = hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact')
             keep = hip_backend.filter_streaks(table, W, H)
             assert len(keep) == len(rec)
-            if draws == 'counter':
+            if draws == 'counter':                            # (the stream's pick is overwritten: draw_seed is ignored)
                 rec['tex_index'] = 10 * m.texture_bucket(table.ratio[keep]) + table.pick[keep]
-            out.append(jitter_records(rec, table.jitter_g[keep], jitter))
-            continue
-        if draws == 'counter':
-            if p != 0:
-                raise ValueError("counter draws: run_pos must be 0 (frame %d)" % i)
-            rec = hip_backend.pack_frame(table, m, W, H, 0, rotation='exact')
-            keep = hip_backend.filter_streaks(table, W, H)
-            assert len(keep) == len(rec)
-            rec['tex_index'] = 10 * m.texture_bucket(table.ratio[keep]) + table.pick[keep]
-            out.append(rec)
+            out.append(jitter_records(rec, table.jitter_g[keep], jitter) if jitter else rec)
             continue
         if not noisy or p == 0:
             out.append(hip_backend.pack_frame(table, m, W, H, int(s['draw_seed']), rotation='exact'))
