@@ -3068,6 +3068,11 @@ __device__ inline void blur_n(const double* c0, int st, W hw, int r, double (&ac
   }
 }
 
+// Two consecutive doubles of a finished tile as ONE 16-byte store.  The tile is dense (pitch ew), so a row that starts on an
+// odd element is only 8-byte aligned: the type says so, and gfx950 takes a 16-byte global access at that alignment.
+typedef double double2_a8 __attribute__((ext_vector_type(2), aligned(8)));
+__device__ inline void store2(double* o, double a, double b) { *reinterpret_cast<double2_a8*>(o) = double2_a8{a, b}; }
+
 // ---------------------------------------------------------------------------
 // fused defocus blur: both axes of the separable filter through LDS, staged by LDS-DMA a sub-tile ahead
 // ---------------------------------------------------------------------------
@@ -3286,26 +3291,29 @@ __global__ __launch_bounds__(256, 4) void k_blur_fused_dma(const FrameDesc* fram
       stage(np, ng, nitem.x, ntb != tb, ntb);
     }
     PH(6)                                                 // the next sub-tile's loads issued
-    // axis 1 (columns, sigma = c/2) -> global: a thread owns row yq and four consecutive columns; lanes run down the rows
-    // (odd pitch -> distinct banks).
+    // axis 1 (columns, sigma = c/2) -> global: a thread owns row yq and four consecutive columns; lanes run along the row,
+    // column block fastest, so a wave's store instruction covers whole consecutive rows of the band -- with a full-width
+    // band (nearly all: blur_layout) one contiguous stretch of the finished tile, which plan_drop stores densely.  A
+    // thread's four results leave as two 16-byte stores (store2: 8-byte aligned when ew and the row are odd, which
+    // gfx950 takes).  Lanes next to each other read Y 32 bytes apart: the odd pitch spreads only the rows over the banks.
     {
       const int ncb = (g.wo + 3) >> 2, nh = ncb * g.ho;
-      const float inv_ho = 1.0f / (float)g.ho;
-      double* dst = sc.arena + p.a1_off;
+      const float inv_ncb = 1.0f / (float)ncb;
+      double* dst = sc.arena + p.a1_off + ((int64_t)g.y0 * p.epitch + p.epad + g.x0);
       for (int idx = t; idx < nh; idx += 256) {
-        const int cb = (int)(((float)idx + 0.5f) * inv_ho), yq = idx - cb * g.ho;
-        const double* c0 = Y + yq * g.yp + 4 * cb + r2;
+        const int yq = (int)(((float)idx + 0.5f) * inv_ncb), cb = idx - yq * ncb;
+        const int xo = 4 * cb;
+        const double* c0 = Y + yq * g.yp + xo + r2;
         double acc0, acc1, acc2, acc3;
         if (r2 > 0) {
           blur4(c0, 1, [&](int k) { return hw2[k]; }, r2, acc0, acc1, acc2, acc3);
         } else {
           acc0 = c0[0]; acc1 = c0[1]; acc2 = c0[2]; acc3 = c0[3];
         }
-        const int xo = 4 * cb;
-        double* o = dst + (int64_t)(g.y0 + yq) * p.epitch + p.epad + (g.x0 + xo);
+        double* o = dst + ((int64_t)yq * p.epitch + xo);
         if (xo + 3 < g.wo) {
-          o[0] = acc0; o[1] = acc1; o[2] = acc2; o[3] = acc3;
-        } else {
+          store2(o, acc0, acc1); store2(o + 2, acc2, acc3);
+        } else {                                          // the last, partial block of a row
           o[0] = acc0;
           if (xo + 1 < g.wo) o[1] = acc1;
           if (xo + 2 < g.wo) o[2] = acc2;
@@ -3462,42 +3470,46 @@ __global__ __launch_bounds__(256, 4) void k_blur_small(const FrameDesc* frames, 
     }
     wave_lds_sync();
     PH(1)                                           // row pass
-    // axis 1 (columns) -> global: a lane owns row y and four consecutive columns; lanes run down the rows
+    // axis 1 (columns) -> global: a lane owns row y and one, two or four consecutive columns; lanes run along the row, so
+    // a store instruction covers whole consecutive rows of the (dense) finished tile: a contiguous stretch of it
     const int ncb = (pw + 3) >> 2, nh = ncb * ph;
-    const float inv_ph = 1.0f / (float)ph;
+    const int per_row = (r2 > 0 && nh <= 16) ? pw : (r2 > 0 && nh <= 32) ? (pw + 1) >> 1 : ncb;      // lanes per row
+    const float inv_per_row = 1.0f / (float)per_row;
     if (nh <= 16 && r2 > 0) {                        // (r06) a column per lane: pw * ph <= 64 lanes
       const int idx = lane;
       if (idx < pw * ph) {
-        const int x = (int)(((float)idx + 0.5f) * inv_ph), yq = idx - x * ph;
+        const int yq = (int)(((float)idx + 0.5f) * inv_per_row), x = idx - yq * pw;
         double a[1];
         blur_n<1>(Y + (__mul24(yq, yp) + x + r2), 1, [&](int k) { return readlane_f64(w2, r2 - k); }, r2, a);
         tile[(int64_t)yq * cur.epitch + cur.epad + x] = a[0];
       }
     } else if (nh <= 32 && r2 > 0) {                 // two columns per lane
-      const int idx = lane, nc2 = (pw + 1) >> 1;
+      const int idx = lane, nc2 = per_row;
       if (idx < nc2 * ph) {
-        const int cb = (int)(((float)idx + 0.5f) * inv_ph), yq = idx - cb * ph, xo = 2 * cb;
+        const int yq = (int)(((float)idx + 0.5f) * inv_per_row), xo = 2 * (idx - yq * nc2);
         double a[2];
         blur_n<2>(Y + (__mul24(yq, yp) + xo + r2), 1, [&](int k) { return readlane_f64(w2, r2 - k); }, r2, a);
         double* o = tile + (int64_t)yq * cur.epitch + cur.epad + xo;
-        o[0] = a[0];
-        if (xo + 1 < pw) o[1] = a[1];
+        if (xo + 1 < pw) {
+          store2(o, a[0], a[1]);
+        } else {
+          o[0] = a[0];
+        }
       }
     } else {
       for (int idx = lane; idx < nh; idx += 64) {
-        const int cb = (int)(((float)idx + 0.5f) * inv_ph), yq = idx - cb * ph;
-        const double* c0 = Y + (__mul24(yq, yp) + 4 * cb + r2);
+        const int yq = (int)(((float)idx + 0.5f) * inv_per_row), xo = 4 * (idx - yq * ncb);
+        const double* c0 = Y + (__mul24(yq, yp) + xo + r2);
         double a0, a1, a2, a3;
         if (r2 > 0) {
           blur4(c0, 1, [&](int k) { return readlane_f64(w2, r2 - k); }, r2, a0, a1, a2, a3);
         } else {
           a0 = c0[0]; a1 = c0[1]; a2 = c0[2]; a3 = c0[3];
         }
-        const int xo = 4 * cb;
         double* o = tile + (int64_t)yq * cur.epitch + cur.epad + xo;
         if (xo + 3 < pw) {
-          o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3;
-        } else {
+          store2(o, a0, a1); store2(o + 2, a2, a3);
+        } else {                                     // the last, partial block of a row
           o[0] = a0;
           if (xo + 1 < pw) o[1] = a1;
           if (xo + 2 < pw) o[2] = a2;
