@@ -478,6 +478,27 @@ int rr_set_particle_draws(rr_ctx* ctx, int32_t mode);
  * flight. */
 int rr_set_particle_jitter(rr_ctx* ctx, double jitter_deg);
 
+/* Mean wind: the air's mean horizontal velocity (wx, wz) in m/s for the records the context generates from now on (every entry
+ * point that takes rr_sim_frame records, every particle model, both draw modes, with or without jitter, rig or trajectory), in
+ * the axes of the particle world: x right, z toward the viewer -- the camera frame under RR_PARTICLES_IID and
+ * RR_PARTICLES_FIELD, the rig frame under RR_PARTICLES_RIG, the lattice's world frame under a trajectory (a rig yawed by 90
+ * degrees sees wx along its own z).  It is added to a drop's horizontal velocity, once:
+ *     vx = wind_life + wx,  vz = speed_mps + wz        -- one IEEE double addition each, no contraction
+ * and (vx, vz) take the place of the life's wind (block_wind, the zero-mean scatter of wind_sigma) and of
+ * rr_sim_frame.speed_mps wherever those enter: the streak's end under every model, and the position inside a life under the
+ * field and rig models (qx = u + vx tau / w_box, qz = u -/+ vz tau / depth-of-box; a translation modulo the box keeps the
+ * uniform law, so a single frame of the field still follows the i.i.d. model's law).  Slot counts, boxes, lives, tables, the
+ * texture pick and the jitter's deviate do not depend on it.  A drop of terminal velocity v falls at atan(wx / v) to the
+ * vertical: small drops lean more than large ones.  The renderer draws such streaks correctly only with RR_OPT_STREAK_LEAN.
+ * The particle kernels take the two numbers as arguments: no further launch.  tools/particles.py expected_records(wind=)
+ * states the records bit for bit.  (0, 0) (default): off -- the records and the kernels are those without it (the sums are
+ * not formed: x + 0.0 is not x for x = -0.0).  Angular noise stays where it is allowed today (RR_PARTICLES_IID).
+ * Not simulated: a streak that starts outside the margin-enlarged field and ends inside it (as for speed_mps); gusts; a
+ * vertical wind.  One wind per context.
+ * RR_E_ARG: a component that is not finite or whose magnitude exceeds 100 m/s.  Call it between runs, with no call of the
+ * generator in flight. */
+int rr_set_particle_wind(rr_ctx* ctx, double wx, double wz);
+
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`
@@ -604,6 +625,15 @@ enum {
                                      * before the walk: neighbours on the map, of like size, share vertex rows.  0: table order, through
                                      * the same kernels (every sort key is 0).  Same bits.  (bench.py --sweep restores the options it does
                                      * not know to 0: after a sweep this one is off until it is set again.) */
+  RR_OPT_STREAK_LEAN = 26,          /* 0 (default): the reference's rule -- a rotated (Medium / Small) tile is flipped when its streak
+                                     * ENDS in the right half of the image (generator.py:165) and its corner is the streak's START
+                                     * (generator.py:171): right for streaks that radiate from the image centre only.  1: both come
+                                     * from the streak's own end points: flip = x1 > x0 (the tile then leans like the streak,
+                                     * whether it runs down or up the image: rr_device.h plan_drop) and the corner
+                                     * (min(x0, x1), min(y0, y1)), so that a uniform slant (rr_set_particle_wind) leans the same way
+                                     * all over the image.  Tile size, rotation terms, resize route, Big drops, external tiles,
+                                     * defocus, crop, 'white' and the raw-tile key (it carries the flip) keep their values.  Every
+                                     * entry point, XML drop tables and angular noise included: the record's end points decide. */
   RR_OPT_COMPOSITE_BATCH = 20       /* retired: only 1 is accepted */
 };
 int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value);

@@ -36,6 +36,12 @@ drop's Philox counter (tools/particles.py counter_jitter, `main.py --streak_jitt
 projected fall direction, and under 'field' and 'rig' a drop keeps its tilt in every frame of its life and in every view.  It works
 with every particle model and both draws, inside the particle kernels: no further pass on the device.
 
+`wind=(wx, wz)` (default (0, 0): off) is the air's mean horizontal velocity in m/s, x right and z toward the viewer in the particle
+world's axes (the camera for 'iid' and 'field', the rig for 'rig', the world under a trajectory; tools/particles.py wind=,
+`main.py --wind WX,WZ`): rain in a 5 m/s cross-wind falls at 40 degrees to the vertical, small drops leaning more than large ones.
+`lean=None` (default) follows the wind: with a non-zero wind the renderer takes a streak tile's lean and corner from the streak
+itself (RR_OPT_STREAK_LEAN), without one it keeps the reference's rule; True / False force either.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -93,7 +99,7 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None):
+                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
@@ -103,6 +109,15 @@ class RainAugment:
         if isinstance(jitter, bool) or not isinstance(jitter, numbers.Number) or not np.isfinite(jitter) or jitter < 0:
             raise ValueError("jitter %r: expected a finite number of degrees >= 0" % (jitter,))
         self.jitter = float(jitter)
+        try:
+            if isinstance(wind, (str, bytes)) or len(wind) != 2 or any(isinstance(v, bool) or not isinstance(v, numbers.Number) for v in wind):
+                raise TypeError
+            self.wind = particles._check_wind(wind)
+        except TypeError:
+            raise ValueError("wind %r: expected two numbers (wx, wz) in m/s" % (wind,))
+        if lean is not None and not isinstance(lean, bool):
+            raise ValueError("lean %r: expected None (follow the wind), True or False" % (lean,))
+        self.lean = bool(self.wind[0] or self.wind[1]) if lean is None else lean
         if (particle_model == 'rig') != (rig is not None):
             raise ValueError("particle_model='rig' and rig= go together (rig.Rig)")
         if rig is None and views is not None:
@@ -191,7 +206,7 @@ class RainAugment:
     def plan(self, intensity, frame_index, B=None):
         """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
         union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key, particle_model,
-        cam_hz, draws, jitter: what expected_records needs to state the call's drop tables).  Under the
+        cam_hz, draws, jitter, wind: what expected_records needs; lean: the renderer's RR_OPT_STREAK_LEAN to state the call's drop tables).  Under the
         rig model B counts instants: sims and fog hold V = len(views) consecutive entries per instant (view views[i % V] of
         instant i // V), plus views, rig_views and rig_box (what rr_set_particle_rig gets)."""
         if B is None:
@@ -220,7 +235,8 @@ class RainAugment:
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
         out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
-                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter)
+                   particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter,
+                   wind=self.wind, lean=self.lean)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
             box_rig = self.rig if self.trajectory is None else self.trajectory.bind(self.rig)
@@ -278,6 +294,8 @@ class RainAugment:
             hip.set_particle_model(self.particle_model, self.options["cam_hz"])
             hip.set_particle_draws(self.draws)
             hip.set_particle_jitter(self.jitter)
+            hip.set_particle_wind(*self.wind)
+            hip.set_option(hip_backend.RR_OPT_STREAK_LEAN, int(self.lean))
             self._hip, self.device = hip, dev
         if self.rig is not None and not self._traj_set:      # (the previous call has finished: no kernel reads the old table)
             self._hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])      # the box is the trajectory's

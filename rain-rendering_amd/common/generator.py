@@ -107,6 +107,15 @@ class Generator:
         self.streak_jitter = float(getattr(args, 'streak_jitter', 0.0) or 0.0)        # degrees per unit of the drop's own normal deviate
         if not np.isfinite(self.streak_jitter) or self.streak_jitter < 0:
             raise ValueError("--streak_jitter %r: expected a finite number of degrees >= 0" % (self.streak_jitter,))
+        # --wind WX,WZ (main.py _wind_and_lean has parsed it): the air's mean horizontal velocity, m/s; --streak_lean: whether the renderer
+        # takes a streak tile's lean and corner from the streak itself (RR_OPT_STREAK_LEAN); 'auto' follows the wind
+        self.wind = tuple(float(v) for v in (getattr(args, 'wind', None) or (0.0, 0.0)))
+        if len(self.wind) != 2 or not all(np.isfinite(v) and abs(v) <= 100.0 for v in self.wind):
+            raise ValueError("--wind %r: expected WX,WZ, two finite numbers of m/s of magnitude <= 100" % (self.wind,))
+        if any(self.wind) and not self.device_particles:
+            raise ValueError("--wind needs --device_particles")
+        lean = getattr(args, 'lean', None)                       # main.py _wind_and_lean has resolved 'auto'
+        self.streak_lean = any(self.wind) if lean is None else bool(lean)
         if self.streak_jitter and not self.device_particles:
             raise ValueError("--streak_jitter needs --device_particles")
         if self.streak_jitter and bool(self.noise_std):
@@ -439,6 +448,7 @@ class Generator:
                 hip.set_colormap(imgops.viridis_lut())
                 fog_const = FOG.constants()
                 sims = None
+                hip.set_option(hip_backend.RR_OPT_STREAK_LEAN, int(self.streak_lean))
                 if self.device_particles:
                     # no particle file: the settings of the run's simulated frames (tools/particles.sim_frames: what
                     # simulate() would have written to XML, as rr_sim_frame records) + the diameter tables they refer to
@@ -471,6 +481,7 @@ class Generator:
                     if self.streak_jitter:                       # (likewise)
                         hip.set_particle_noise(0.0, 0.0)
                     hip.set_particle_jitter(self.streak_jitter)
+                    hip.set_particle_wind(*self.wind)
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)

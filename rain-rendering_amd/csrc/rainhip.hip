@@ -382,7 +382,7 @@ enum { LC_NONE = 0, LC_BIG_LDS = 1, LC_BIG = 2, LC_ROWS = 3, LC_ROT_INT = 4, LC_
 enum { LB_NONE = 0, LB_SMALL = 1, LB_FUSED = 2, LB_SLOW = 3 };
 __device__ inline uint4 make_list_rec(const DropPlan& p, const int32_t* tex_h, const int32_t* tex_w, const Scratch& sc);
 __global__ __launch_bounds__(128) void k_plan(const FrameDesc* frames, Dims dm, rr_camera cam, const int32_t* tex_h,
-                                              const int32_t* tex_w, int max_drops, int use_npts, Scratch sc) {
+                                              const int32_t* tex_w, int max_drops, int use_npts, Scratch sc, int lean) {
   static_assert(sizeof(DropPlan) % 4 == 0, "DropPlan layout");
   const int f = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(128) void k_plan(const FrameDesc* frames, Dims dm, 
       const rr_ext_tile& e = fr.ext[i];
       if (e.alpha) xg = ExtGeom{true, e.tw, e.th, e.min_x, e.min_y};
     }
-    plan_drop<true>(d, cam, dm, tex_h, tex_w, fr.opacity, fr.strategy, p, size, xg);      // (a Big drop's homography: k_plan_big)
+    plan_drop<true>(d, cam, dm, tex_h, tex_w, fr.opacity, fr.strategy, p, size, xg, lean);   // (a Big drop's homography: k_plan_big)
     // the FOV polygon is evaluated for every drop: in the reference its failure is raised before the circle of confusion
     // is looked at (bad_weather.py:363-373 vs :416) -- k_colour gives such a drop its status and keeps it out of the blend.
     // use_npts (the colour branch ran BEFORE this kernel, on the same stream): a drop without a polygon gets no tile either;
@@ -4678,7 +4678,25 @@ __global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int6
 // record is kept and non-Big makes the drop's Philox block 3, its normal deviate (rrsim::jitter_deviate) and turns the record
 // by jitter_deg * g (rrsim::noise_rotate) before it is staged: after the cull and the filter, so only kept lanes pay, and the
 // counts do not depend on it.  JIT = false is the kernel as it was (jitter_deg is not read).
+// WIND (rr_set_particle_wind; a parameter of all three particle kernels, count passes included -- the frame filter reads both
+// end points): the mean wind's two doubles arrive as the kernel's last argument, wave-uniform, and the generators form
+// vx = wind_life + wx, vz = speed_mps + wz (rr_particles.h).  WIND = false is the kernel as it was: the argument is an empty
+// struct behind every other one, like TrajArgs<false>.
 constexpr int DROP_DW = (int)(sizeof(rr_drop) / 4);
+template <bool WIND>
+struct WindArgs {};
+template <>
+struct WindArgs<true> {
+  double x, z;                                // m/s: x right, z toward the viewer, in the particle world's axes
+};
+template <bool WIND>
+__device__ inline double wind_x(const WindArgs<WIND>& w) {
+  if constexpr (WIND) return w.x; else return 0.0;
+}
+template <bool WIND>
+__device__ inline double wind_z(const WindArgs<WIND>& w) {
+  if constexpr (WIND) return w.z; else return 0.0;
+}
 
 // ---- the tail the three particle kernels share: finish the record, compact the kept ones, store whole lines.  No helper holds a
 // barrier: where a kernel synchronises, and why, is written in its own body. ----
@@ -4721,10 +4739,10 @@ __device__ inline void store_staged(const uint32_t* stage, int nw, rr_drop* tabl
   for (int k = lane; k < room * DROP_DW; k += 64) o[k] = stage[k];
 }
 
-template <bool CTR, bool JIT>
+template <bool CTR, bool JIT, bool WIND = false>
 __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int H, int W, const double* dgrid, const double* cdf_tabs,
                                                     int n_grid, const double* ratio_db, rr_drop* out, int cap, int32_t* n_out, int skip_run,
-                                                    double jitter_deg) {
+                                                    double jitter_deg, const WindArgs<WIND> wa) {
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   if (skip_run && sims[f].run_pos != 0) return;               // angular noise: k_noise_chains makes this frame
   __shared__ rr_sim_frame s_sf;
@@ -4746,7 +4764,7 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
     if (i < sf.n_particles) {
       rrsim::Particle p;
       uint32_t pw = 0;
-      rrsim::make_particle(sf, dgrid, cdf, n_grid, (uint32_t)i, p, CTR ? &pw : nullptr);
+      rrsim::make_particle<WIND>(sf, dgrid, cdf, n_grid, (uint32_t)i, p, CTR ? &pw : nullptr, wind_x(wa), wind_z(wa));
       double ratio;
       keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
       finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::particle_jitter(sf, (uint32_t)i); });
@@ -4774,10 +4792,11 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
 // pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
 // twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
 // batches fill the chip by themselves) there is no count pass.
-template <bool COUNT, bool CTR, bool JIT>
+template <bool COUNT, bool CTR, bool JIT, bool WIND = false>
 __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
                                                           const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
-                                                          int32_t* n_out, int32_t* chunk_cnt, int chunk_slots, double jitter_deg) {
+                                                          int32_t* n_out, int32_t* chunk_cnt, int chunk_slots, double jitter_deg,
+                                                          const WindArgs<WIND> wa) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   const int f = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   __shared__ rr_sim_frame s_sf;
@@ -4806,7 +4825,7 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
       rrsim::Particle p;
       double life;
       uint32_t pw = 0;
-      if (rrsim::make_field_particle(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr)) {
+      if (rrsim::make_field_particle<WIND>(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr, wind_x(wa), wind_z(wa))) {
         double ratio;
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
         finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::life_jitter(sf, (uint32_t)j, life); });
@@ -4866,11 +4885,11 @@ struct TrajArgs<true> {
   int32_t active[RR_MAX_VIEWS];               // the rig's number of the batch's view a
   int32_t n_views;
 };
-template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false>
+template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false, bool WIND = false>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
                                                         rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots,
-                                                        double jitter_deg, const TrajArgs<TRAJ> tj) {
+                                                        double jitter_deg, const TrajArgs<TRAJ> tj, const WindArgs<WIND> wa) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -4901,7 +4920,7 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
     const int j = base + t;
     const bool valid = j < last;
     rrsim::RigSlot q;
-    if (valid) rrsim::make_rig_slot(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q);
+    if (valid) rrsim::make_rig_slot<WIND>(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q, wind_x(wa), wind_z(wa));
     // CTR: the slot's pick (0 .. 9) is live across the view loop, where the stream kernel has no register to spare.  It
     // takes the place of z_max, which every view step forms again from the diameter (the same expression as make_rig_slot's:
     // the same bits); the empty asm keeps the compiler from hoisting that back out of the loop.
@@ -4930,10 +4949,10 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
             for (int k = 0; k < 3; k++) c0[k] = ps[9 + k];
 #pragma unroll
             for (int k = 0; k < 12; k++) p1[k] = ps[12 + k];
-            rrsim::traj_view_end(sf, q, dd, c0, p1, p1 + 9, p);
+            rrsim::traj_view_end<WIND>(sf, q, dd, c0, p1, p1 + 9, p);
           }
         } else {
-          inside = rrsim::rig_view_particle(sf, q, rv.box, rv.R[a], rv.c[a], p);
+          inside = rrsim::rig_view_particle<WIND>(sf, q, rv.box, rv.R[a], rv.c[a], p);
         }
         if (inside) {
           double ratio;
@@ -5265,6 +5284,7 @@ struct rr_ctx {
   rrz::BlockMeta* d_pngz_meta = nullptr;
   size_t pngz_cap = 0;               // blocks
   bool pngz_attr = false;
+  int streak_lean = 0;               // RR_OPT_STREAK_LEAN: 1 a rotated tile's flip and corner come from the streak's own end points (plan_drop)
   bool wild_pixels = false;          // RR_OPT_WILD_PIXELS: rainy_bg may hold values outside [0, 1] (k_pad_visits)
   int32_t *d_pad_first = nullptr, *d_eff_first = nullptr;
   size_t pad_cap = 0;                // elements of each
@@ -5293,6 +5313,7 @@ struct rr_ctx {
   int particle_model = RR_PARTICLES_IID;
   int particle_draws = RR_DRAWS_STREAM;   // rr_set_particle_draws: the texture pick from numpy's stream, or from the drop's own counter
   double jitter_deg = 0.0;                // rr_set_particle_jitter: degrees per unit of the drop's own normal deviate; 0: none
+  double wind_x = 0.0, wind_z = 0.0;      // rr_set_particle_wind: the air's mean horizontal velocity, m/s; (0, 0): none
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
@@ -5930,7 +5951,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
       ProfScope ps(ctx, bs, "k_plan");
       HIPCHK(hipMemsetAsync(sc.bigs_n, 0, sizeof(int32_t) * (size_t)n, bs));
       hipLaunchKernelGGL(k_plan, dim3((max_drops + 127) / 128, n), dim3(128), 0, bs, ctx->d_frames, dm, ctx->cam, ctx->d_tex_h,
-                         ctx->d_tex_w, D, fs == bs ? 1 : 0, sc);
+                         ctx->d_tex_w, D, fs == bs ? 1 : 0, sc, ctx->streak_lean);
       hipLaunchKernelGGL(k_plan_big, dim3((max_drops + 127) / 128, n), dim3(128), 0, bs, ctx->d_frames, ctx->d_tex_h, ctx->d_tex_w, D, sc);
     }
     {
@@ -6257,6 +6278,20 @@ int noise_states_drop(rr_ctx* ctx) {
   return RR_OK;
 }
 
+// fn(WIND, WindArgs<WIND>) with the context's mean wind (rr_set_particle_wind) as a compile-time switch: (0, 0) takes the
+// kernels as they were
+template <class F>
+void with_wind(const rr_ctx* ctx, F fn) {
+  if (ctx->wind_x != 0.0 || ctx->wind_z != 0.0) {
+    WindArgs<true> wa;
+    wa.x = ctx->wind_x;
+    wa.z = ctx->wind_z;
+    fn(std::true_type{}, wa);
+  } else {
+    fn(std::false_type{}, WindArgs<false>{});
+  }
+}
+
 // The frames of a call with angular noise (run_pos >= 1): plan, per simulated frame, the steps from its held state (or its
 // pristine streaks) to each of its frames -- in run order, one chain per simulated frame -- and enqueue them (k_noise_chains).
 // The plan is made here, in call order, so the held states follow the order of the calls whatever the streams.
@@ -6355,8 +6390,11 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   if (m > 0) {                       // pristine streaks of the fresh states: filtered, tex_index = first texture of the block of ten
     ProfScope ps(ctx, s, "k_particles");
     rr_drop* P = ctx->noise_states[fresh_id[0]].pristine;
-    hipLaunchKernelGGL((k_particles<false, false>), dim3(m), dim3(512), 0, s, reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid,
-                       ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P, stride, ctx->noise_states[fresh_id[0]].n_pristine, 0, 0.0);
+    with_wind(ctx, [&](auto wnd, auto wa) {
+      hipLaunchKernelGGL((k_particles<false, false, decltype(wnd)::value>), dim3(m), dim3(512), 0, s,
+                         reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P,
+                         stride, ctx->noise_states[fresh_id[0]].n_pristine, 0, 0.0, wa);
+    });
   }
   {
     ProfScope ps(ctx, s, "k_noise_chains");
@@ -6521,8 +6559,8 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
       memcpy(rv.box, ctx->rig_box, sizeof rv.box);
       ProfScope ps(ctx, s, "k_rig_particles");
-      auto passes = [&](auto with_traj) {                    // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
-        constexpr bool TRAJ = decltype(with_traj)::value;
+      auto passes = [&](auto with_traj, auto with_wnd, auto wa) {   // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
+        constexpr bool TRAJ = decltype(with_traj)::value, WIND = decltype(with_wnd)::value;
         TrajArgs<TRAJ> tj;
         if constexpr (TRAJ) {
           tj.poses = ctx->d_traj;
@@ -6532,21 +6570,26 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
         }
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj);
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa);
         };
-        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ>);   // (a count depends neither on the draws nor on the jitter)
-        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ>); });
+        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND>);   // (a count depends neither on the draws nor on the jitter)
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND>); });
       };
-      if (traj) passes(std::true_type{});
-      else passes(std::false_type{});
+      with_wind(ctx, [&](auto wnd, auto wa) {
+        if (traj) passes(std::true_type{}, wnd, wa);
+        else passes(std::false_type{}, wnd, wa);
+      });
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                           ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg);
-      };
-      if (chunks > 1) launch(k_field_particles<true, false, false>);
-      with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value>); });
+      with_wind(ctx, [&](auto wnd, auto wa) {
+        constexpr bool WIND = decltype(wnd)::value;
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa);
+        };
+        if (chunks > 1) launch(k_field_particles<true, false, false, WIND>);
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND>); });
+      });
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
@@ -6556,9 +6599,11 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     {
       ProfScope ps(ctx, s, "k_particles");
       // skip_run: frames with run_pos != 0 are k_noise_chains' (none under the jitter or the counter draws: refused above)
-      with_draws(ctr, jit, [&](auto c, auto j) {
-        hipLaunchKernelGGL((k_particles<decltype(c)::value, decltype(j)::value>), dim3(n), dim3(512), 0, s, ctx->d_sims, H, W, ctx->d_dgrid,
-                           ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0, ctx->jitter_deg);
+      with_wind(ctx, [&](auto wnd, auto wa) {
+        with_draws(ctr, jit, [&](auto c, auto j) {
+          hipLaunchKernelGGL((k_particles<decltype(c)::value, decltype(j)::value, decltype(wnd)::value>), dim3(n), dim3(512), 0, s, ctx->d_sims, H, W,
+                             ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0, ctx->jitter_deg, wa);
+        });
       });
     }
     if (!ctr) {
@@ -7237,6 +7282,22 @@ int rr_set_particle_jitter(rr_ctx* ctx, double jitter_deg) {
     return RR_E_ARG;
   }
   ctx->jitter_deg = jitter_deg;
+  return RR_OK;
+}
+
+int rr_set_particle_wind(rr_ctx* ctx, double wx, double wz) {
+  if (!ctx) return RR_E_ARG;
+  if (!std::isfinite(wx) || !std::isfinite(wz) || fabs(wx) > 100.0 || fabs(wz) > 100.0) {
+    ctx->err = "rr_set_particle_wind: each component of the mean wind is a finite number of m/s of magnitude <= 100";
+    return RR_E_ARG;
+  }
+  if (wx != ctx->wind_x || wz != ctx->wind_z) {               // the chains of a noisy run start from pristine records made under the old wind
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = noise_states_drop(ctx))) return rc;
+  }
+  ctx->wind_x = wx;
+  ctx->wind_z = wz;
   return RR_OK;
 }
 
@@ -8300,6 +8361,7 @@ int rr_set_option(rr_ctx* ctx, int32_t option, int32_t value) {
     case RR_OPT_FOV_ORDER: ctx->fov_order = value != 0 ? 1 : 0; return RR_OK;
     case RR_OPT_PIPELINE_F32: ctx->pipe_f32 = value != 0; return RR_OK;
     case RR_OPT_WILD_PIXELS: ctx->wild_pixels = value != 0; return RR_OK;
+    case RR_OPT_STREAK_LEAN: ctx->streak_lean = value != 0 ? 1 : 0; return RR_OK;
     case RR_OPT_PNG_DEFLATE: ctx->png_deflate = value != 0; return RR_OK;
     case RR_OPT_COLOUR_STREAM:
       if (value < 0 || value > 2) break;

@@ -1358,19 +1358,35 @@ struct ExtGeom {
   bool has;
   int tw, th, min_x, min_y;
 };
+// `lean` (RR_OPT_STREAK_LEAN; last, defaulted: 0 is the reference's rule).  The reference decides a rotated tile's lean by the
+// half of the image its streak ends in (flip = end.x > W // 2, generator.py:165) and puts the tile's corner at the streak's
+// START (generator.py:171): both are right for streaks that radiate from the image centre, as a forward-moving camera gives
+// them, and for no others.  With lean = 1 a rotated (Medium or Small) tile takes both from the streak itself:
+// flip = x1 > x0, and the corner (min x, min y) of the two end points, as Big drops have it already.  Nothing else moves.
+// Why x1 > x0 and not the sign of (x1 - x0) (y1 - y0): the rotation is by -(theta), theta = acos((y1 - y0) / n) in [0, 180]
+// degrees, so the UNFLIPPED tile of a streak that runs up the image (theta > 90) already leans the other way from that of
+// one that runs down; measured on the oracle's tiles (tests/test_streak_lean_host.py), the flipped tile's mass has the x-y
+// covariance sign(y1 - y0).  The tile leans like the streak -- covariance sign((x1 - x0) (y1 - y0)) -- exactly when the
+// flip is taken for x1 > x0, whichever way the streak runs; for the radial streaks of a forward-moving camera that is the
+// reference's `end.x > W // 2`.  RR_PLAN_LEAN_DEFAULT: what a call without the
+// argument gets (a test build of the unchanged callers may name a variable here).
+#ifndef RR_PLAN_LEAN_DEFAULT
+#define RR_PLAN_LEAN_DEFAULT 0
+#endif
 template <bool DEFER_BIG = false>     // true: a Big drop's mi[] is left zero (the caller runs plan_big_homography later)
 RR_HD void plan_drop(const rr_drop& d, const rr_camera& cam, const Dims& dm, const int32_t* tex_h, const int32_t* tex_w,
-                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const ExtGeom xg);
+                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const ExtGeom xg, int lean = RR_PLAN_LEAN_DEFAULT);
 template <bool DEFER_BIG = false>
 RR_HD void plan_drop(const rr_drop& d, const rr_camera& cam, const Dims& dm, const int32_t* tex_h, const int32_t* tex_w,
-                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const rr_ext_tile* ext = nullptr) {
+                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const rr_ext_tile* ext = nullptr,
+                     int lean = RR_PLAN_LEAN_DEFAULT) {
   const bool has = ext && ext->alpha;
   plan_drop<DEFER_BIG>(d, cam, dm, tex_h, tex_w, opacity_attenuation, strategy, p, size_out,
-                       ExtGeom{has, has ? ext->tw : 0, has ? ext->th : 0, has ? ext->min_x : 0, has ? ext->min_y : 0});
+                       ExtGeom{has, has ? ext->tw : 0, has ? ext->th : 0, has ? ext->min_x : 0, has ? ext->min_y : 0}, lean);
 }
 template <bool DEFER_BIG>
 RR_HD void plan_drop(const rr_drop& d, const rr_camera& cam, const Dims& dm, const int32_t* tex_h, const int32_t* tex_w,
-                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const ExtGeom xg) {
+                     double opacity_attenuation, int strategy, DropPlan& p, int64_t& size_out, const ExtGeom xg, int lean) {
   size_out = 0;
   p.status = RR_DROP_OK;
   p.tex = d.tex_index;
@@ -1417,7 +1433,7 @@ RR_HD void plan_drop(const rr_drop& d, const rr_camera& cam, const Dims& dm, con
     minCy = miny;
   } else {
     p.kind = KIND_ROT;
-    p.flip = (d.x1 > W / 2) ? 1 : 0;
+    p.flip = lean ? ((d.x1 > d.x0) ? 1 : 0) : ((d.x1 > W / 2) ? 1 : 0);
     p.th = imax(iabs(d.y1 - d.y0), 2);
     p.tw = imax(iabs(d.x1 - d.x0), d.max_width + 2);
     // imutils.rotate_bound geometry
@@ -1462,8 +1478,8 @@ RR_HD void plan_drop(const rr_drop& d, const rr_camera& cam, const Dims& dm, con
     } else {
       p.rs_mode = RS_LINEAR;
     }
-    minCx = d.x0;
-    minCy = d.y0;
+    minCx = lean ? imin(d.x0, d.x1) : d.x0;
+    minCy = lean ? imin(d.y0, d.y1) : d.y0;
   }
 
   if (strategy == 1) {

@@ -75,9 +75,18 @@ RR_HD void project(const rr_sim_frame& sf, double X, double Y, double depth, dou
   iw = (wd * sf.fpx) / depth;
 }
 
+// ---- the MEAN WIND (rr_set_particle_wind, tools/particles.py wind=): the air's mean horizontal velocity (wx, wz), m/s ----
+// In the axes of the particle world: x right, z toward the viewer -- the camera frame of the i.i.d. and field models, the rig
+// frame of the rig model, the lattice's world frame under a trajectory.  WIND is a compile-time switch of every generator
+// below, the way TRAJ is one of k_rig_particles: with WIND the drop's horizontal velocity is vx = wind_life + wx and
+// vz = speed_mps + wz, each evaluated once, and those two take the place of the life's wind and of speed_mps wherever they
+// enter.  WIND = false is the function as it was: wx and wz are not read (x + 0.0 is not x for x = -0.0, which block_wind
+// gives at wind_sigma = 0, so the sums are not formed at all).  Slot counts, boxes, lives and tables do not depend on it.
+
 // particle i of frame sf: three Philox blocks, counter = (i, frame, block, 0); *pick_word = the pick's word (b[2])
+template <bool WIND = false>
 RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const double* cdf, int n_grid, uint32_t i, Particle& p,
-                         uint32_t* pick_word = nullptr) {
+                         uint32_t* pick_word = nullptr, double wx = 0.0, double wz = 0.0) {
   uint32_t a[4] = {i, sf.frame, 0u, 0u}, b[4] = {i, sf.frame, 1u, 0u}, c[4] = {i, sf.frame, 2u, 0u};
   philox4x32_10(a, sf.key0, sf.key1);
   philox4x32_10(b, sf.key0, sf.key1);
@@ -98,9 +107,11 @@ RR_HD void make_particle(const rr_sim_frame& sf, const double* dgrid, const doub
   const double Z = -depth;
   const double wind = block_wind(c, sf.wind_sigma);
   const double t = sf.exposure_s;
-  const double X2 = X + wind * t;
+  double vx = wind, vz = sf.speed_mps;
+  if constexpr (WIND) { vx = wind + wx; vz = sf.speed_mps + wz; }
+  const double X2 = X + vx * t;
   const double Y2 = Y - terminal_velocity(D) * t;
-  const double Z2 = Z + sf.speed_mps * t;
+  const double Z2 = Z + vz * t;
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
   p.wp2[0] = X2; p.wp2[1] = Y2; p.wp2[2] = Z2;
   p.wd = wd;
@@ -167,16 +178,19 @@ RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, doub
 }
 
 // Returns whether the particle is inside the frustum; `life` = g; *pick_word = word 2 of the life's block 1 (texture_pick).
+template <bool WIND = false>
 RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
-                               Particle& p, double& life, uint32_t* pick_word = nullptr) {
+                               Particle& p, double& life, uint32_t* pick_word = nullptr, double wind_x = 0.0, double wind_z = 0.0) {
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
   const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;   // frustum half-widths at unit depth
   const double bx = hx * s.z_max, by = hy * s.z_max;
   const double wx = 2.0 * bx, wy = 2.0 * by;
   const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
-  const double qx = unit32(f.b[0]) + (f.wind * f.tau) / wx;   // box coordinates in units of the box: wrapped into [0, 1)
-  const double qz = unit32(f.b[1]) - (sf.speed_mps * f.tau) / s.z_max;
+  double vx = f.wind, vz = sf.speed_mps;
+  if constexpr (WIND) { vx = f.wind + wind_x; vz = sf.speed_mps + wind_z; }
+  const double qx = unit32(f.b[0]) + (vx * f.tau) / wx;   // box coordinates in units of the box: wrapped into [0, 1)
+  const double qz = unit32(f.b[1]) - (vz * f.tau) / s.z_max;
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   const double X = fx * wx - bx;
   const double Y = by - f.age * wy;
@@ -186,9 +200,9 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   const double depth = rr::dmax(zr, 0.05);
   const double Z = -depth;
   const double e = sf.exposure_s;
-  const double X2 = X + f.wind * e;
+  const double X2 = X + vx * e;
   const double Y2 = Y - f.v * e;
-  const double Z2 = Z + sf.speed_mps * e;
+  const double Z2 = Z + vz * e;
   life = f.life;
   if (pick_word) *pick_word = f.b[2];
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
@@ -211,17 +225,21 @@ struct RigSlot {
   double wd, z_max;               // diameter (m), farthest depth shown (the box's half side in x and z is box[0] z_max)
   double life;
   uint32_t pick_word;             // word 2 of the life's block 1 (texture_pick): one pick for every view and frame of the life
+  double vx, vz;                  // WIND only (else not written, not read): rig-frame velocity (vx, -v, vz) under the mean wind
 };
 
+template <bool WIND = false>
 RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
-                         uint32_t j, RigSlot& q) {
+                         uint32_t j, RigSlot& q, double wx = 0.0, double wz = 0.0) {
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double b = box[0] * s.z_max;
   const double by = box[1] * s.z_max + box[2];
   const double w = 2.0 * b, wy = 2.0 * by;
   const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
-  const double qx = unit32(f.b[0]) + (f.wind * f.tau) / w;
-  const double qz = unit32(f.b[1]) + (sf.speed_mps * f.tau) / w;   // the vehicle's motion: drops gain +speed in z
+  double vx = f.wind, vz = sf.speed_mps;
+  if constexpr (WIND) { q.vx = vx = f.wind + wx; q.vz = vz = sf.speed_mps + wz; }
+  const double qx = unit32(f.b[0]) + (vx * f.tau) / w;
+  const double qz = unit32(f.b[1]) + (vz * f.tau) / w;             // the vehicle's motion: drops gain +speed in z
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   q.X = fx * w - b;
   q.Y = by - f.age * wy;
@@ -269,11 +287,14 @@ RR_HD void rig_view_end(const rr_sim_frame& sf, const RigSlot& q, double ex, dou
 }
 // slot q through a view at rest: the start moved by the drop's velocity x exposure.  (NOT traj_view_end with c1 == c0: the bits
 // would agree, but the subtraction cannot be folded away and this is the path of every run without a trajectory.)
+// WIND: the slot's (vx, vz) in place of (wind, speed_mps).
+template <bool WIND = false>
 RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const double box[3], const double* R, const double* c, Particle& p) {
   double d[3];
   const bool inside = traj_view_start(sf, q, box, R, c, d, p);
   const double e = sf.exposure_s;
-  rig_view_end(sf, q, d[0] + q.wind * e, d[1] + (-q.v) * e, d[2] + sf.speed_mps * e, R, p);
+  if constexpr (WIND) rig_view_end(sf, q, d[0] + q.vx * e, d[1] + (-q.v) * e, d[2] + q.vz * e, R, p);
+  else rig_view_end(sf, q, d[0] + q.wind * e, d[1] + (-q.v) * e, d[2] + sf.speed_mps * e, R, p);
   return inside;
 }
 
@@ -284,11 +305,14 @@ RR_HD bool rig_view_particle(const rr_sim_frame& sf, const RigSlot& q, const dou
 // image as the start, never wrapped again -- and turns it by R1.  With R1 == R0 and c1 == c0 the subtraction is - 0.0 and the
 // pair gives rig_view_particle's bits.  Two calls, so that a kernel makes the second for the lanes the cull left only and R1, c1
 // are not live across it.
+template <bool WIND = false>
 RR_HD void traj_view_end(const rr_sim_frame& sf, const RigSlot& q, const double d[3], const double* c0, const double* R1, const double* c1,
                          Particle& p) {
   const double e = sf.exposure_s;
-  rig_view_end(sf, q, (d[0] + q.wind * e) - (c1[0] - c0[0]), (d[1] + (-q.v) * e) - (c1[1] - c0[1]),
-               (d[2] + sf.speed_mps * e) - (c1[2] - c0[2]), R1, p);
+  double vx = q.wind, vz = sf.speed_mps;
+  if constexpr (WIND) { vx = q.vx; vz = q.vz; }
+  rig_view_end(sf, q, (d[0] + vx * e) - (c1[0] - c0[0]), (d[1] + (-q.v) * e) - (c1[1] - c0[1]),
+               (d[2] + vz * e) - (c1[2] - c0[2]), R1, p);
 }
 
 // ceil(sqrt(n)) of a non-negative integer, exactly (np.ceil(np.sqrt(.)) of the loader gives the same: a non-integer root

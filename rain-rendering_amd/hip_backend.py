@@ -38,6 +38,7 @@ RR_OPT_TILE_ROWS = 22
 RR_OPT_ROWS_SHARES = 23
 RR_OPT_FIELD_CHUNKS = 24
 RR_OPT_FOV_ORDER = 25
+RR_OPT_STREAK_LEAN = 26
 RR_PARTICLES_IID, RR_PARTICLES_FIELD, RR_PARTICLES_RIG = 0, 1, 2      # rr_set_particle_model
 PARTICLE_MODELS = {'iid': RR_PARTICLES_IID, 'field': RR_PARTICLES_FIELD, 'rig': RR_PARTICLES_RIG}
 RR_DRAWS_STREAM, RR_DRAWS_COUNTER = 0, 1                              # rr_set_particle_draws
@@ -158,7 +159,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_trajectory',
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose']
 
 _lib = None
@@ -258,6 +259,7 @@ def load_library(path=None):
     lib.rr_set_particle_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
     lib.rr_set_particle_draws.argtypes = [ctypes.c_void_p, ctypes.c_int32]
     lib.rr_set_particle_jitter.argtypes = [ctypes.c_void_p, ctypes.c_double]
+    lib.rr_set_particle_wind.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
@@ -878,6 +880,13 @@ class RainHip:
         the particle kernels themselves.  0 (default): off.  Every model, both draws; not together with angular noise."""
         self._check(self.lib.rr_set_particle_jitter(self.h, float(deg)), 'rr_set_particle_jitter')
 
+    def set_particle_wind(self, wx=0.0, wz=0.0):
+        """rr_set_particle_wind: the air's mean horizontal velocity in m/s (x right, z toward the viewer, in the particle world's
+        axes) added to every drop's own (tools/particles.py wind=), by the particle kernels themselves.  (0, 0) (default): off.
+        Every model, both draws, with jitter, rigs and trajectories.  Streaks then slant the same way all over the image:
+        render them with set_option(RR_OPT_STREAK_LEAN, 1)."""
+        self._check(self.lib.rr_set_particle_wind(self.h, float(wx), float(wz)), 'rr_set_particle_wind')
+
     def set_particle_rig(self, views, box, active=None):
         """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =
         the views a batch renders, in batch order (default: all).  Select the model with set_particle_model('rig', cam_hz)."""
@@ -923,7 +932,8 @@ class RainHip:
         return [out[k, :min(int(cnt[k]), cap)] for k in range(n)], cnt
 
     def set_option(self, option, value):
-        """rr_set_option: tuning / A-B switches that never change a result bit (include/rainhip.h)."""
+        """rr_set_option: tuning / A-B switches that never change a result bit, and the opt-in modes that do -- RR_OPT_DEPTH_OCCLUSION,
+        RR_OPT_WILD_PIXELS, RR_OPT_STREAK_LEAN (include/rainhip.h)."""
         self._check(self.lib.rr_set_option(self.h, int(option), int(value)), 'rr_set_option')
 
     def set_camera(self, cam):

@@ -70,6 +70,15 @@ _FLAGS = [
                                 help="with --device_particles: turn every streak by DEG degrees times a standard normal deviate of the "
                                      "drop's own (from its random counter: a drop keeps its tilt over its life and across the views of a "
                                      "rig); any --particle_model and --particle_draws; 0: off (not with --noise_std)")),
+    (('--wind',), dict(type=str, default=None,
+                       help="with --device_particles: WX,WZ, the air's mean horizontal velocity in m/s (x right, z toward the viewer; the "
+                            "rig's axes under --particle_model rig, the world's under --trajectory): 5,0 makes the rain fall at 40 degrees to "
+                            "the vertical, small drops leaning more than large ones; any --particle_model, --particle_draws and "
+                            "--streak_jitter")),
+    (('--streak_lean',), dict(type=str, default='auto', choices=['auto', 'on', 'off'],
+                              help="'on': a streak tile's lean and corner come from the streak's own end points; 'off': the reference's rule "
+                                   "(lean by the image half the streak ends in, corner at its start: right for streaks that radiate from the "
+                                   "image centre); 'auto' (default): on exactly when a non-zero --wind is given")),
     (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'mono' (one camera), 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
                                                    "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
     (('--trajectory',), dict(type=str, default=None,
@@ -89,6 +98,25 @@ def _parse(argv):
     for names, kw in _FLAGS:
         ap.add_argument(*names, **kw)
     return ap.parse_args(argv)
+
+
+def _wind_and_lean(ns):
+    """--wind WX,WZ as a pair of floats (default (0, 0)) and --streak_lean as ns.lean: 'auto' is on exactly when a non-zero wind is
+    given, so that no command line without --wind changes its output."""
+    wind = getattr(ns, 'wind', None)
+    if wind is not None and not isinstance(wind, tuple):
+        try:
+            wind = tuple(float(v) for v in str(wind).split(','))
+        except ValueError:
+            wind = ()
+        if len(wind) != 2 or not all(math.isfinite(v) and abs(v) <= 100.0 for v in wind):
+            raise SystemExit("--wind %r: expected WX,WZ, two finite numbers of m/s of magnitude <= 100" % (ns.wind,))
+        if any(wind) and not ns.device_particles:
+            raise SystemExit("--wind needs --device_particles (the wind moves the particles the GPU's generator makes)")
+    ns.wind = wind if wind is not None else (0.0, 0.0)
+    mode = getattr(ns, 'streak_lean', 'auto') or 'auto'
+    ns.lean = any(ns.wind) if mode == 'auto' else mode == 'on'
+    return ns
 
 
 def _derive(ns):
@@ -121,6 +149,7 @@ def _derive(ns):
         if ns.noise_std:
             raise SystemExit("--streak_jitter cannot be combined with --noise_std: the jitter is a function of the drop, the angular "
                              "noise of the order of the run")
+    _wind_and_lean(ns)
     ns.verbose = not ns.noverbose
     light_db = _J(ns.streaks_db, 'env_light_database')
     ns.texture = _J(light_db, 'size32')

@@ -93,6 +93,16 @@ angular noise turns one (``noise_rotation``: rotation terms by the angle sum, en
 kept set, sizes, texture and world positions do not depend on it.  Under the field and rig models g is a function of
 (seed, slot, life): a drop keeps its tilt in every frame of its life and in every view.  It is not ``--noise_std`` (whose
 deviates come from the run's sequential stream) and is refused together with it.
+
+Mean wind (``wind=(wx, wz)``, ``rr_set_particle_wind`` in the library): the air's mean horizontal velocity in m/s, in the axes
+of the particle world -- x right, z toward the viewer: the camera frame of the i.i.d. and field models, the rig frame of the
+rig model, the lattice's world frame under a trajectory.  ``_drift`` adds it to a drop's horizontal velocity once,
+``vx = wind_life + wx`` and ``vz = speed + wz``, and those two take the place of the life's wind and of the speed wherever they
+enter: the end of the streak in every model, and the position inside a life of the field and rig models (a translation modulo
+the box: the law at one instant does not change).  Slot counts, boxes, lives and tables do not depend on it.  ``(0, 0)``
+(default) is off and forms no sum at all (``x + 0.0`` is not ``x`` for ``x = -0.0``, which ``_block_wind`` gives at
+``wind_sigma = 0``): the records are those without the keyword, byte for byte.  A uniform slant needs the renderer's
+``RR_OPT_STREAK_LEAN``.  The host XML writer's default path (``simulate``) has no wind.
 """
 import os
 
@@ -483,6 +493,26 @@ def _block_wind(c, wind_sigma):
     return (s4 * 1.7320508075688772) * wind_sigma
 
 
+def _check_wind(wind):
+    """(wx, wz) as two floats; rr_set_particle_wind's refusals."""
+    try:
+        wx, wz = (float(v) for v in wind)
+    except (TypeError, ValueError):
+        raise ValueError("mean wind %r: expected two numbers (wx, wz) in m/s" % (wind,))
+    if not (np.isfinite(wx) and np.isfinite(wz)) or abs(wx) > 100.0 or abs(wz) > 100.0:
+        raise ValueError("mean wind %r: each component is a finite number of m/s of magnitude <= 100" % (wind,))
+    return wx, wz
+
+
+def _drift(wind_life, speed, wind):
+    """A drop's horizontal velocity (vx, vz) under the mean wind `wind` (rr_particles.h WIND): the life's own wind plus wx, the
+    vehicle's speed plus wz -- one addition each.  wind == (0, 0): the two inputs themselves, no addition (module docstring)."""
+    wx, wz = _check_wind(wind)
+    if wx == 0.0 and wz == 0.0:
+        return wind_life, speed
+    return wind_life + wx, float(speed) + wz
+
+
 def _project(cam, X, Y, depth, wd):
     """rr_particles.h project: (sensor position (n, 2), image width) of one streak end at camera-frame (X, Y), `depth` away."""
     W, H = float(cam.W), float(cam.H)
@@ -499,7 +529,7 @@ def _records(n, wp1, wp2, wd, ip1, iw1, ip2, iw2):
     return rec
 
 
-def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0):
+def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0, wind=(0.0, 0.0)):
     """The n particles of simulated frame `frame` as PARTICLE_DTYPE records: the numpy statement of
     rr_particles.h make_particle (same operations, same order)."""
     if n == 0:
@@ -521,11 +551,11 @@ def make_particles(cam, dgrid, cdf, n, frame, seed, wind_sigma=1.0, margin=0.05,
     X = ((px - W / 2.0) * depth) / cam.fpx
     Y = ((py - H / 2.0) * depth) / cam.fpx
     Z = -depth
-    wind = _block_wind(c, wind_sigma)
+    vx, vz = _drift(_block_wind(c, wind_sigma), cam.speed, wind)
     t = cam.exposure
-    X2 = X + wind * t
+    X2 = X + vx * t
     Y2 = Y - terminal_velocity(D) * t
-    Z2 = Z + cam.speed * t
+    Z2 = Z + vz * t
     ip2, iw2 = _project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd)
     return _records(n, [X, Y, Z], [X2, Y2, Z2], wd, np.stack([px, py], axis=1), (wd * cam.fpx) / depth, ip2, iw2)
 
@@ -587,7 +617,7 @@ def _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma):
 
 
 def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                         cull=True):
+                         cull=True, wind=(0.0, 0.0)):
     """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
     of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
     life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
@@ -600,9 +630,10 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
     bx, by = hx * z_max, hy * z_max
     wx, wy = 2.0 * bx, 2.0 * by
-    v, g, age, tau, b, wind = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
-    qx = unit32(b[0]) + (wind * tau) / wx
-    qz = unit32(b[1]) - (cam.speed * tau) / z_max
+    v, g, age, tau, b, wind_life = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
+    vx, vz = _drift(wind_life, cam.speed, wind)
+    qx = unit32(b[0]) + (vx * tau) / wx
+    qz = unit32(b[1]) - (vz * tau) / z_max
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
     X = fx * wx - bx
     Y = by - age * wy
@@ -612,29 +643,29 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     depth = np.maximum(zr, 0.05)
     Z = -depth
     e = cam.exposure
-    X2 = X + wind * e
+    X2 = X + vx * e
     Y2 = Y - v * e
-    Z2 = Z + cam.speed * e
+    Z2 = Z + vz * e
     rec = _records(n_slots, [X, Y, Z], [X2, Y2, Z2], wd, *_project(cam, X, Y, depth, wd), *_project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd))
     if cull:
         return rec[inside], g[inside]
     return rec, g
 
 
-def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0):
+def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0, wind=(0.0, 0.0)):
     """Velocity (n, 3) in m/s (x right, y up, z towards the camera) of the given slots in the given lives, and the slots'
     boxes (n, 3): full width, full height, depth -- what tests compare a track's displacement with."""
     j = np.asarray(slots, np.uint64)
     key = _key(seed)
     D, _, _, z_max = _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far)
     hx, hy = ((0.5 + margin) * float(cam.W)) / cam.fpx, ((0.5 + margin) * float(cam.H)) / cam.fpx
-    wind = _block_wind(philox4x32(*_life_counter(j, lives, 2), *key), wind_sigma)
-    vel = np.stack([wind, -terminal_velocity(D), np.full(len(j), float(cam.speed))], axis=1)
+    vx, vz = _drift(_block_wind(philox4x32(*_life_counter(j, lives, 2), *key), wind_sigma), cam.speed, wind)
+    vel = np.stack([vx, -terminal_velocity(D), np.full(len(j), float(vz))], axis=1)
     return vel, np.stack([2.0 * (hx * z_max), 2.0 * (hy * z_max), z_max], axis=1)
 
 
 def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-                cull=True):
+                cull=True, wind=(0.0, 0.0)):
     """Frame `k` of a field-model run ALONE: (PARTICLE_DTYPE records with pid = slot id, life per record) of the particles
     inside the frustum -- the identity of a frame's particles.  Time index k, settings of simulated frame k % n_sim
     (n_sim: n_sim_frames(options) by default).  `generate(..., model='field')` is these frames one after the other."""
@@ -643,7 +674,7 @@ def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.0
     cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
     _, dgrid, cdf, _ = expected_count(cam, rate, min_px, z_far, margin)
     n_slots = int(field_slot_counts(options, fallrate, ks + 1, seed, min_px, z_far, margin, count)[ks])
-    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull)
+    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind)
 
 
 # ---- the RIG model: one field, several cameras (module docstring) --------------------------------------------------
@@ -697,7 +728,7 @@ def rig_tables(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=
                    lambda cam, rate: rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far))
 
 
-def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0):
+def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0, wind=(0.0, 0.0)):
     """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters (rr_particles.h
     make_rig_slot): dict(D, z_max, b (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
     r, r_y, o_y = (float(v) for v in box)
@@ -707,19 +738,20 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
     b = r * z_max
     by = r_y * z_max + o_y
     w, wy = 2.0 * b, 2.0 * by
-    v, g, age, tau, bb, wind = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
-    qx = unit32(bb[0]) + (wind * tau) / w
-    qz = unit32(bb[1]) + (cam.speed * tau) / w
+    v, g, age, tau, bb, wind_life = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
+    vx, vz = _drift(wind_life, cam.speed, wind)
+    qx = unit32(bb[0]) + (vx * tau) / w
+    qz = unit32(bb[1]) + (vz * tau) / w
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
     X = fx * w - b
     Y = by - age * wy
     Z = fz * w - b
     return dict(D=D, wd=wd, z_max=z_max, b=b, by=by, life=g, pos=np.stack([X, Y, Z], axis=1),
-                vel=np.stack([wind, -v, np.full(n_slots, float(cam.speed))], axis=1))
+                vel=np.stack([vx, -v, np.full(n_slots, float(vz))], axis=1))
 
 
 def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                       cull=True, image=(0, 0), view_end=None):
+                       cull=True, image=(0, 0), view_end=None, wind=(0.0, 0.0)):
     """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
     statement of rr_particles.h make_rig_slot + rig_view_particle (traj_view_start, rig_view_end; same operations, same order).  `box` = (r, r_y, o_y).
     Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
@@ -733,7 +765,7 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
         return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
     R = [float(v) for v in np.asarray(view[0], np.float64).reshape(9)]
     c = [float(v) for v in np.asarray(view[1], np.float64).reshape(3)]
-    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far)
+    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind)
     W, H = float(cam.W), float(cam.H)
     hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
     b, z_max, wd = st['b'], st['z_max'], st['wd']
@@ -782,7 +814,7 @@ def _traj_cam(cam):
 
 
 def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-              cull=True, image=(0, 0), trajectory=None, box=None):
+              cull=True, image=(0, 0), trajectory=None, box=None, wind=(0.0, 0.0)):
     """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame.  With
     `trajectory` (trajectory.Trajectory): the view's composed poses of time index k, the trajectory's box and slot counts, speed 0.
     `box`: another box than the run's (tests)."""
@@ -799,7 +831,7 @@ def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, m
         po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
         cam, pose, view_end = _traj_cam(cam), (po['R0'], po['c0']), (po['R1'], po['c1'])
     return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, pose, box, wind_sigma, margin, min_px, z_far, cull, image,
-                              view_end=view_end)
+                              view_end=view_end, wind=wind)
 
 
 def rig_run_sims(sims, k_idx, n_active):
@@ -808,7 +840,8 @@ def rig_run_sims(sims, k_idx, n_active):
     return field_run_sims(sims, np.repeat(np.asarray(k_idx, np.int64), int(n_active)))
 
 
-def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid'):
+def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid',
+             wind=(0.0, 0.0)):
     """(frames, drops) record arrays of `n_frames` camera frames.  `count`: force that many drops per frame instead
     of the Poisson-distributed physical count.  model='field': the persistent field (module docstring), frame k at time
     k / cam_hz under the settings of simulated frame k; pid is then the slot id.  (The rig model has no particle file: its
@@ -832,10 +865,10 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
         _, dgrid, cdf, _ = tables[tk]
         n = int(counts[k])
         if model == 'field':
-            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far)
+            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, wind=wind)
             n = len(rec)
         else:
-            rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far)
+            rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far, wind=wind)
         frames[k] = (k, int(round(cam.exposure * 1e6)), int(round(k * 1e6 / cam.hz)), n, first, n)
         chunks.append(rec)
         first += n
@@ -897,7 +930,8 @@ def field_run_sims(sims, f_idx):
     return out
 
 
-def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0, trajectory=None):
+def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0, trajectory=None,
+                  wind=(0.0, 0.0)):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
     texture pick of every row (counter_picks of the row's particle); with `jitter`, `jitter_g`: the row's counter_jitter."""
@@ -908,7 +942,7 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
     life = None
     k, margin = int(s['frame']), float(s['margin'])
     tab, n = cdf[int(s['table'])], int(s['n_particles'])
-    kw = dict(wind_sigma=float(s['wind_sigma']), margin=margin, min_px=float(s['min_px']), z_far=float(s['z_far']))
+    kw = dict(wind_sigma=float(s['wind_sigma']), margin=margin, min_px=float(s['min_px']), z_far=float(s['z_far']), wind=wind)
     if model == 'rig':
         pose, box, view_end = rig.views[int(view)] if trajectory is None else None, rig, None
         if trajectory is not None:
@@ -940,7 +974,7 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
 
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
-                     rig=None, view=None, draws='stream', jitter=0.0, trajectory=None):
+                     rig=None, view=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0)):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -967,9 +1001,13 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
 
     jitter=DEG (rr_set_particle_jitter; every model, both draws): the records above, then every kept non-Big one turned by
     DEG * counter_jitter of its drop (jitter_records).  jitter=0: the records above.  Not with noise_std / noise_scale / run, and
-    run_pos must be 0."""
+    run_pos must be 0.
+
+    wind=(wx, wz) (rr_set_particle_wind; every model, both draws, with jitter, rig and trajectory): the records of the particles
+    made under that mean wind (module docstring).  (0, 0): the records above."""
     from .. import hip_backend
     _check_model(model)
+    wind = _check_wind(wind)
     noisy = bool(noise_std) and bool(noise_scale)
     jitter = _check_jitter(jitter, noisy, run)
     _check_draws(draws, noisy)
@@ -986,7 +1024,7 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory, wind)
         p = int(s['run_pos'])
         if jitter or draws == 'counter':
             if p != 0:

@@ -1,0 +1,305 @@
+"""GPU tier: the mean wind on the device (rr_set_particle_wind; the WIND instantiations of k_particles, k_field_particles and
+k_rig_particles, count passes included).
+
+  1. device records == the host statement (tools/particles.py expected_records(wind=)), bit for bit, counts included: i.i.d. (and a
+     capacity below the count), field (one chunk: store pass alone; three chunks: count pass + store pass; also with jitter 5), rig
+     (both stereo views with one and two chunks, then view 1 alone) and a rig under a yawing trajectory, each under counter and stream
+     draws;
+  2. set_particle_wind(0, 0) on the same context: today's records;
+  3. the kernel profile: the launch counts with the wind on are those with it off;
+  4. every RR_E_ARG; angular noise with a wind under the i.i.d. model;
+  6. RainAugment(particle_model='field', draws='counter', wind=(6, 0)) == rr_pipeline_submit fed the host statement's records with the
+     lean on, and differs from the wind = (0, 0) batch;
+  7. the driver: `main.py --device_particles --wind 6,0` writes the files whose pixels RainAugment(wind=(6, 0)) gives, --streak_lean
+     off other ones."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import helpers as h
+from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
+from test_gpu_particle_draws import H, KITTI_STEREO, W, _field_run, _iid_run, _kitti, _set_rig
+from test_gpu_particle_field import _rh
+from test_gpu_particle_jitter import _same
+from test_gpu_particle_noise import _entries
+from test_gpu_particle_trajectory import MONO, _arc_poses, _set
+
+pytestmark = pytest.mark.gpu
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+trajmod = importlib.import_module('rain-rendering_amd.trajectory')
+augment = importlib.import_module('rain-rendering_amd.augment')
+imgops = importlib.import_module('rain-rendering_amd.common.imgops')
+envmod = importlib.import_module('rain-rendering_amd.common.envmap')
+
+WIND = (-7.5, 2.0)
+DRAWS = ['counter', 'stream']
+
+
+def _check(rh, sims, want, what):
+    got, cnt = rh.generate_drops(sims, H, W)
+    for k in range(len(sims)):
+        assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
+        _same(got[k], want[k], '%s: frame %d' % (what, k))
+    return cnt
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+def test_iid_records_equal_host_statement(tmp_path, built, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
+    sims, dgrid, cdf, kw = _iid_run(_kitti())
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_draws(draws)
+        rh.set_particle_wind(*WIND)
+        cnt = _check(rh, sims, want, 'i.i.d., %s' % draws)
+        # a capacity below the drop count: the count still tells, the records that fit are the first ones
+        small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[0]) // 2, 1))
+        assert np.array_equal(cnt_small, cnt)
+        _same(small[0], want[0][:len(want[0]) // 2], 'i.i.d., half the capacity')
+        rh.set_particle_wind(0, 0)                           # back to today's records on the same context
+        _check(rh, sims, plain, 'i.i.d., %s, wind off again' % draws)
+    finally:
+        rh.close()
+    assert want[0].tobytes() != plain[0].tobytes()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("jitter", [0.0, 5.0])
+@pytest.mark.parametrize("chunks", [1, 3])
+def test_field_records_equal_host_statement(tmp_path, built, chunks, jitter, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    sims, dgrid, cdf, kw = _field_run(_kitti())
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=WIND, **kw)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, **kw)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_model('field', kw['cam_hz'])
+        rh.set_particle_draws(draws)
+        rh.set_particle_jitter(jitter)
+        rh.set_particle_wind(*WIND)
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+        _check(rh, sims, want, 'field, %d chunks, %s, jitter %g' % (chunks, draws, jitter))
+        rh.set_particle_wind(0, 0)
+        _check(rh, sims, plain, 'field, %d chunks, %s, jitter %g, wind off again' % (chunks, draws, jitter))
+    finally:
+        rh.close()
+    assert want[1].tobytes() != plain[1].tobytes()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+def test_rig_records_equal_host_statement(tmp_path, built, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=KITTI_STEREO)
+    inst = [1, 2 ** 31 + 5]
+    sims = particles.rig_run_sims(sims1, inst, 2)
+    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)          # frame 2 i + v
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set_rig(rh, opt)
+        rh.set_particle_draws(draws)
+        rh.set_particle_wind(*WIND)
+        for chunks in (1, 2):
+            rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+            _check(rh, sims, want, 'rig, %d chunks, %s' % (chunks, draws))
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+        # view 1 alone: the same bits per view
+        _set_rig(rh, opt, active=[1])
+        got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
+        for i in range(len(inst)):
+            _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+        _set_rig(rh, opt)
+        rh.set_particle_wind(0, 0)
+        _check(rh, sims, plain, 'rig, %s, wind off again' % draws)
+    finally:
+        rh.close()
+    assert want[0].tobytes() != plain[0].tobytes()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+def test_trajectory_records_equal_host_statement(tmp_path, built, draws):
+    """A single camera on an arc (10 m/s, 20 degrees a second): at instant 7 it has yawed 14 degrees; the wind stays a world vector."""
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    rig = MONO
+    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=rig, trajectory=traj)
+    inst = [0, 7, 3]
+    sims = particles.rig_run_sims(sims1, inst, 1)
+    kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set(rh, rig, traj, opt, hz)
+        rh.set_particle_draws(draws)
+        rh.set_particle_wind(*WIND)
+        for chunks in (1, 2):
+            rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+            _check(rh, sims, want, 'trajectory, %d chunks, %s' % (chunks, draws))
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+        rh.set_particle_wind(0, 0)
+        _check(rh, sims, plain, 'trajectory, %s, wind off again' % draws)
+    finally:
+        rh.close()
+    assert want[1].tobytes() != plain[1].tobytes()
+
+
+def test_the_wind_adds_no_launch(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    sims1, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    rig_run = (particles.rig_run_sims(sims1, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
+    rh = _rh(sc)
+    try:
+        rh.profile(True)
+        for name, (sims, dgrid, cdf, kw) in (('k_particles', _iid_run(opt)), ('k_field_particles', _field_run(opt)), ('k_rig_particles', rig_run)):
+            rh.set_particle_tables(dgrid, cdf)
+            if kw['model'] == 'rig':
+                _set_rig(rh, opt)
+            else:
+                rh.set_particle_model(kw['model'], kw.get('cam_hz', 0.0))
+            for chunks in ((0,) if name == 'k_particles' else (1, 2)):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                for draws in DRAWS:
+                    rh.set_particle_draws(draws)
+                    counts = {}
+                    for wind in ((0.0, 0.0), WIND):
+                        rh.set_particle_wind(*wind)
+                        rh.profile_reset()
+                        rh.generate_drops(sims, H, W)
+                        stats = rh.profile_read()
+                        counts[wind] = {k: v[0] for k, v in stats.items()}
+                        assert stats[name][0] >= 1, (name, draws, wind, stats)
+                    assert counts[(0.0, 0.0)] == counts[WIND], (name, chunks, draws, counts)
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+def test_refusals_and_noise_with_a_wind(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    sims, dgrid, cdf, kw = _iid_run(_kitti())
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        for bad in ((float('nan'), 0.0), (0.0, float('nan')), (float('inf'), 0.0), (0.0, -float('inf')), (100.5, 0.0), (0.0, -101.0)):
+            with pytest.raises(RuntimeError, match='wind'):
+                rh.set_particle_wind(*bad)
+        rh.set_particle_wind(100.0, -100.0)                      # the limit itself is allowed
+        rh.set_particle_wind(3.0, 0.0)
+        got, cnt = rh.generate_drops(sims, H, W)                 # a refusal leaves the context working, with the last good wind
+        want = particles.expected_records(sims, dgrid, cdf, sc.db, wind=(3.0, 0.0), **kw)
+        _same(got[0], want[0], 'after the refusals')
+        # angular noise stays allowed where it is today: the i.i.d. model -- the chains start from the windy pristine records
+        f_idx = [0, 1, 2, 3]                                     # entry p: simulated frame p % 3, seed p
+        run = particles.run_table(sims, len(sims), f_idx)
+        noisy = _entries(sims, f_idx, [0, 3])                    # histories of 0 entries and of 1 (frame 0 again)
+        rh.set_particle_noise(2.0, 1.0, *run)
+        got, cnt = rh.generate_drops(noisy, H, W)
+        want = particles.expected_records(noisy, dgrid, cdf, sc.db, noise_std=2.0, noise_scale=1.0, run=run, wind=(3.0, 0.0))
+        for k in range(2):
+            assert int(cnt[k]) == len(want[k]) > 100
+            _same(got[k], want[k], 'noise with a wind: frame %d' % k)
+    finally:
+        rh.close()
+
+
+def test_rain_augment_renders_the_host_statements_records(built, streaks_db):
+    """RainAugment(particle_model='field', draws='counter', wind=(6, 0)), B = 2, bytes, KITTI, 25 mm/hr, against rr_pipeline_submit fed
+    expected_records(wind=(6, 0)) as host tables with RR_OPT_STREAK_LEAN on: image bytes and mask equal; the calm batch has other pixels,
+    and so has the windy batch rendered with the reference's lean rule."""
+    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='field', draws='counter')
+    wind = (6.0, 0.0)
+    aug = augment.RainAugment('kitti', wind=(6, 0), **kw)
+    others = []
+    try:
+        assert aug.frame_size() == (H, W)
+        bgr, depth = _scene(2, H, W, seed=40)
+        idx = [4, 5]
+        p = aug.plan(25, idx)
+        assert p['wind'] == wind and p['lean'] is True
+        want = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws='counter', wind=wind)
+        rainy, mask = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        rainy, mask = rainy.cpu().numpy(), mask.cpu().numpy()
+        rh = h.hb.RainHip(0)
+        try:
+            rh.set_streak_db(aug.db.streaks_light)
+            rh.set_camera(h.hb.make_camera(aug.focal, aug.f_number, aug.exposure))
+            rh.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            we = rh.set_envmap_geometry(H, W, *envmod.EnvironmentMapGenerator(aug.focal, W, H).device_tables(H, W))
+            rh.set_solid_angles(h.solid_angle.get_solid_angles(np.empty((H, we, 0))))
+            rh.set_option(h.hb.RR_OPT_STREAK_LEAN, 1)
+            frames = [dict(bg_u8=np.ascontiguousarray(bgr[i]), depth=np.ascontiguousarray(depth[i]), fog=tuple(p['fog'][i]), omega=None,
+                           drops=want[i]) for i in range(2)]
+            outs = [dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W))) for _ in range(2)]
+            rh.pipeline_submit(0, frames, outs)
+            while not rh.pipeline_wait(0):
+                rh.pipeline_submit(0, frames, outs)
+        finally:
+            rh.close()
+        for i in range(2):
+            assert len(want[i]) > 100
+            assert np.array_equal(rainy[i].transpose(1, 2, 0), outs[i]['image_u8']), i
+            assert np.array_equal(mask[i, 0], outs[i]['mask'].astype(np.float32)), i
+            assert outs[i]['mask'].max() > 0, i
+        for other_kw in (dict(), dict(wind=(6, 0), lean=False)):
+            others.append(augment.RainAugment('kitti', **other_kw, **kw))
+            rainy_0, _ = others[-1](_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+            assert not np.array_equal(rainy_0.cpu().numpy(), rainy), other_kw
+    finally:
+        aug.close()
+        for a in others:
+            a.close()
+
+
+def test_the_driver_writes_what_the_augmenter_renders(tmp_path, built, monkeypatch):
+    """Two KITTI-sized frames: `main.py --device_particles --particle_model field --particle_draws counter --wind 6,0` (--streak_lean
+    auto: on) writes the bytes RainAugment(particle_model='field', draws='counter', wind=(6, 0)) gives for the clip from uint8 images;
+    the same run with --streak_lean off, and the run without --wind, write other files."""
+    tmp = str(tmp_path)
+    n = 2
+    src = os.path.join(tmp, 'source')
+    h.synthetic.write_dataset(src, 'kitti', os.path.join('data_object', 'training'), n, H, W, depth_m=None)
+    db_dir = os.path.join(tmp, 'rainstreakdb')
+    h.synthetic.write_streak_db(db_dir)
+    main = importlib.import_module('rain-rendering_amd.main')
+    common = ['--dataset', 'kitti', '-k', src, '-d', src, '-r', os.path.join(tmp, 'particles'), '-sd', db_dir, '-i', '25', '--noverbose',
+              '--device_particles', '--particle_model', 'field', '--particle_draws', 'counter']
+    monkeypatch.setenv('RAIN_BATCH', '2')
+    gen = main.main(common + ['--wind', '6,0', '--output', os.path.join(tmp, 'windy')])
+    assert len(gen.stats) == n and all(s_['drops'] > 100 for s_ in gen.stats)
+    main.main(common + ['--wind', '6,0', '--streak_lean', 'off', '--output', os.path.join(tmp, 'windy_ref_rule')])
+    main.main(common + ['--output', os.path.join(tmp, 'calm')])
+    sub = os.path.join('kitti', 'data_object', 'training', 'rain', '25mm', 'rainy_image')
+    names = ['%06d.png' % i for i in range(n)]
+
+    def files(run):
+        return np.stack([np.array(Image.open(os.path.join(tmp, run, sub, f)))[..., :3] for f in names])
+    windy = files('windy')
+    assert not np.array_equal(windy, files('windy_ref_rule')) and not np.array_equal(windy, files('calm'))
+    img_dir = os.path.join(src, 'kitti', 'data_object', 'training', 'image_2')
+    rgb = np.stack([np.array(Image.open(os.path.join(img_dir, f)).convert('RGB')) for f in names])
+    depth = np.stack([np.array(Image.open(os.path.join(img_dir, 'depth', f))).astype(np.float32) / 256. for f in names])
+    aug = augment.RainAugment('kitti', streaks_db=db_dir, sequence='data_object/training', particle_model='field', draws='counter', wind=(6, 0))
+    try:
+        rainy, mask = aug(torch.from_numpy(rgb.transpose(0, 3, 1, 2).copy()).to(DEV), torch.from_numpy(depth).to(DEV), 25, np.arange(n))
+        assert np.array_equal(rainy.cpu().numpy().transpose(0, 2, 3, 1), windy)
+        assert all(float(mask[i].max()) > 0 for i in range(n))
+    finally:
+        aug.close()
