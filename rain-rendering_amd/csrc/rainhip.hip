@@ -2087,7 +2087,7 @@ __global__ __launch_bounds__(256) void k_tile_big(const FrameDesc* frames, int m
 __global__ __launch_bounds__(256) void k_tile(const FrameDesc* frames, int max_drops, const uint8_t* texels,
                                               const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off,
                                               Scratch sc) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   __shared__ DropPlan sp;
   __shared__ double s_lut[256];
   __shared__ __attribute__((aligned(16))) uint8_t s_tex[TEX_LDS];
@@ -3350,7 +3350,8 @@ struct SmallItem {                  // what k_blur_small needs of a drop, all wa
   long long a0, a1;
 };
 __global__ __launch_bounds__(256, 4) void k_blur_small(const FrameDesc* frames, int max_drops, Scratch sc) {
-  const int f = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f = blockIdx.y, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (wave-uniform by construction; the compiler wants the proof)
   __shared__ __attribute__((aligned(16))) double Xs[4][BS_X], Ys[4][BS_Y];
   double* X = Xs[wave];
   double* Y = Ys[wave];
