@@ -493,11 +493,32 @@ int rr_set_particle_jitter(rr_ctx* ctx, double jitter_deg);
  * The particle kernels take the two numbers as arguments: no further launch.  tools/particles.py expected_records(wind=)
  * states the records bit for bit.  (0, 0) (default): off -- the records and the kernels are those without it (the sums are
  * not formed: x + 0.0 is not x for x = -0.0).  Angular noise stays where it is allowed today (RR_PARTICLES_IID).
- * Not simulated: a streak that starts outside the margin-enlarged field and ends inside it (as for speed_mps); gusts; a
- * vertical wind.  One wind per context.
+ * Not simulated: a streak that starts outside the margin-enlarged field and ends inside it (as for speed_mps); a vertical
+ * wind.  One mean wind per context; a wind that changes over time is rr_set_particle_gusts.
  * RR_E_ARG: a component that is not finite or whose magnitude exceeds 100 m/s.  Call it between runs, with no call of the
  * generator in flight. */
 int rr_set_particle_wind(rr_ctx* ctx, double wx, double wz);
+
+/* Gusts: a wind that changes over time, under RR_PARTICLES_FIELD and RR_PARTICLES_RIG (with or without a trajectory, both draw
+ * modes, with or without jitter), on top of the mean wind.  disp = G[0 .. n]: (n + 1) x 2 doubles, row i the air's horizontal
+ * DISPLACEMENT (x, z) in metres at time index frame0 + i, in the mean wind's axes; the air moves linearly between samples.  The
+ * table is the caller's (tools/particles.py gust_series makes an Ornstein-Uhlenbeck one); the device looks up, interpolates and
+ * adds -- no transcendental, no state.  With m = rr_sim_frame.frame - frame0 and back = tau cam_hz (tau: seconds since the
+ * drop's life began), every step one IEEE double operation, no contraction:
+ *     sb = m - back;  i = max(floor(sb), 0);  Gb = G[i] + (sb - i) (G[i + 1] - G[i])
+ *     dG = G[m] - Gb;  ge = (G[m + 1] - G[m]) cam_hz
+ * (before the series starts the first interval's velocity is held).  dG joins the mean wind's term in the position of a life,
+ * (vx tau + dGx) / w_box, and ge its velocity in the streak's end, vx + gex; with a series set both mean-wind additions are
+ * formed, also for a mean of (0, 0).  Under the rig model the term is evaluated once per slot, for every view; under a
+ * trajectory it is a world-frame vector.  Slot counts, boxes, lives, tables, the pick and the jitter do not depend on it, and a
+ * single frame keeps the i.i.d. law.  Drops follow the air with no inertia.  tools/particles.py expected_records(gusts=) states
+ * the records bit for bit.  The table is uploaded here, once; the particle kernels read it and take no further launch.
+ * Call it after rr_set_particle_model (it needs cam_hz; a later rr_set_particle_model drops the series), between runs, with no
+ * call of the generator in flight.  n = 0 turns gusts off: the context is what it was.  One series per context.
+ * RR_E_ARG when setting: n < 0 or n > 2^20; frame0 + n > 2^32; a number that is not finite; |G| > 1e6 m; an interval whose
+ * |step| cam_hz exceeds 100 m/s; the model is RR_PARTICLES_IID (rr_set_particle_model to RR_PARTICLES_IID while a series is set
+ * is refused likewise).  RR_E_ARG when generating: a record whose frame lies outside [frame0, frame0 + n); run_pos != 0. */
+int rr_set_particle_gusts(rr_ctx* ctx, int32_t n, uint32_t frame0, const double* disp /* (n + 1) x 2, metres */);
 
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,

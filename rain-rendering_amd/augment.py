@@ -42,6 +42,12 @@ world's axes (the camera for 'iid' and 'field', the rig for 'rig', the world und
 `lean=None` (default) follows the wind: with a non-zero wind the renderer takes a streak tile's lean and corner from the streak
 itself (RR_OPT_STREAK_LEAN), without one it keeps the reference's rule; True / False force either.
 
+`gusts=GustSeries` (default None: off; 'field' and 'rig' only) is a wind that changes over time: the air's horizontal displacement
+sampled at the frame indices frame0 .. frame0 + n (tools/particles.py gust_series makes one; `main.py --gusts SIGMA[,TAU[,SEED]]`;
+DESIGN 5k).  `frame_index` then also selects the wind: a clip k0 + arange(T) sways coherently, random indices into a long series give
+every image of a batch its own slant.  A frame_index outside the series is a ValueError.  `lean=None` is on with a series too.
+`set_gusts()` takes another series between batches.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -99,7 +105,7 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None):
+                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
@@ -117,7 +123,7 @@ class RainAugment:
             raise ValueError("wind %r: expected two numbers (wx, wz) in m/s" % (wind,))
         if lean is not None and not isinstance(lean, bool):
             raise ValueError("lean %r: expected None (follow the wind), True or False" % (lean,))
-        self.lean = bool(self.wind[0] or self.wind[1]) if lean is None else lean
+        self._lean_arg = lean
         if (particle_model == 'rig') != (rig is not None):
             raise ValueError("particle_model='rig' and rig= go together (rig.Rig)")
         if rig is None and views is not None:
@@ -136,6 +142,8 @@ class RainAugment:
         self.f_number, self.exposure, self.camera_gain = st['cam_f_number'], st['cam_exposure'], st['cam_gain']
         self.n_sim = particles.n_sim_frames(self.options)
         self.trajectory = self._check_trajectory(trajectory)
+        self.gusts = particles._check_gusts(gusts, self.options["cam_hz"], particle_model)
+        self.lean = bool(self.wind[0] or self.wind[1] or self.gusts is not None) if lean is None else lean
         light_db = os.path.join(streaks_db, 'env_light_database')
         self.db = DBManager(streaks_path=os.path.join(light_db, 'size32'),
                             norm_coeff_path=os.path.join(light_db, 'txt', 'normalized_env_max.txt'))
@@ -153,6 +161,7 @@ class RainAugment:
         self._tables_key = None                  # the union the context holds
         self._geom = None                        # (H, W) whose envmap geometry and solid angles the context holds
         self._traj_set = trajectory is None      # whether the context holds the current trajectory's box and table
+        self._gusts_set = gusts is None          # whether the context holds the current gust series
 
     def _check_trajectory(self, trajectory):
         if trajectory is None:
@@ -169,6 +178,14 @@ class RainAugment:
         self.trajectory = self._check_trajectory(trajectory)
         self._rates, self._unions, self._tables_key = {}, {}, None
         self._traj_set = False
+
+    def set_gusts(self, gusts):
+        """Another gust series (or None: the mean wind alone) from the next call on: between batches, with no call in flight.  With
+        lean=None the renderer's lean follows: on with a series or a non-zero wind."""
+        self.gusts = particles._check_gusts(gusts, self.options["cam_hz"], self.particle_model)
+        if self._lean_arg is None:
+            self.lean = bool(self.wind[0] or self.wind[1] or self.gusts is not None)
+        self._gusts_set = False
 
     # ---- host side: what a call sends (no GPU needed) ----------------------------------------------------------------
     def frame_size(self):
@@ -206,7 +223,7 @@ class RainAugment:
     def plan(self, intensity, frame_index, B=None):
         """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
         union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key, particle_model,
-        cam_hz, draws, jitter, wind: what expected_records needs; lean: the renderer's RR_OPT_STREAK_LEAN to state the call's drop tables).  Under the
+        cam_hz, draws, jitter, wind, gusts: what expected_records needs; lean: the renderer's RR_OPT_STREAK_LEAN to state the call's drop tables).  Under the
         rig model B counts instants: sims and fog hold V = len(views) consecutive entries per instant (view views[i % V] of
         instant i // V), plus views, rig_views and rig_box (what rr_set_particle_rig gets)."""
         if B is None:
@@ -217,6 +234,9 @@ class RainAugment:
             raise ValueError("intensity must be positive (mm/hr), got %r" % (rates,))
         if any(f < 0 or f >= 2 ** 32 for f in idx):
             raise ValueError("frame_index must hold integers in [0, 2^32), got %r" % (idx,))
+        if self.gusts is not None and not self.gusts.covers(idx).all():
+            raise ValueError("frame_index %r is outside the gust series' frames %d .. %d" % (
+                [f for f in idx if not self.gusts.covers(f)], self.gusts.frame0, self.gusts.frame0 + self.gusts.n - 1))
         key, (dgrid, cdf, offs) = self._union(rates)
         sims = np.zeros(B, hip_backend.SIM_FRAME_DTYPE)
         fog = np.zeros((B, 4), np.float64)
@@ -236,7 +256,7 @@ class RainAugment:
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
         out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter,
-                   wind=self.wind, lean=self.lean)
+                   wind=self.wind, lean=self.lean, gusts=self.gusts)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
             box_rig = self.rig if self.trajectory is None else self.trajectory.bind(self.rig)
@@ -301,6 +321,10 @@ class RainAugment:
             self._hip.set_particle_rig(p['rig_views'], p['rig_box'], active=p['views'])      # the box is the trajectory's
             self._hip.set_particle_trajectory(p.get('traj_poses'))
             self._traj_set = True
+        if not self._gusts_set:                  # (the previous call has finished: no kernel reads the old series)
+            self._hip.set_particle_gusts(self.gusts)
+            self._hip.set_option(hip_backend.RR_OPT_STREAK_LEAN, int(self.lean))
+            self._gusts_set = True
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)
             self._tables_key = key

@@ -114,8 +114,22 @@ class Generator:
             raise ValueError("--wind %r: expected WX,WZ, two finite numbers of m/s of magnitude <= 100" % (self.wind,))
         if any(self.wind) and not self.device_particles:
             raise ValueError("--wind needs --device_particles")
+        # --gusts SIGMA[,TAU[,SEED]] (main.py _wind_and_lean has parsed it into (sigma, tau, seed)): a wind that changes over time, as a
+        # series over the run's frame indices (tools/particles.gust_series); the field and rig models only
+        self.gusts = getattr(args, 'gusts', None)
+        if self.gusts is not None:
+            try:
+                sigma, tau_s, gseed = self.gusts
+                self.gusts = (float(sigma), float(tau_s), int(gseed))
+            except (TypeError, ValueError):
+                raise ValueError("--gusts %r: expected (SIGMA, TAU, SEED)" % (self.gusts,))
+            if not (np.isfinite(self.gusts[0]) and 0 < self.gusts[0] <= 20.0) or not (np.isfinite(self.gusts[1]) and self.gusts[1] > 0) or \
+                    not 0 <= self.gusts[2] < 2 ** 32:
+                raise ValueError("--gusts %r: expected 0 < SIGMA <= 20 m/s, TAU > 0 seconds, SEED in [0, 2^32)" % (self.gusts,))
+            if not self.device_particles or self.particle_model not in ('field', 'rig'):
+                raise ValueError("--gusts needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
         lean = getattr(args, 'lean', None)                       # main.py _wind_and_lean has resolved 'auto'
-        self.streak_lean = any(self.wind) if lean is None else bool(lean)
+        self.streak_lean = (any(self.wind) or self.gusts is not None) if lean is None else bool(lean)
         if self.streak_jitter and not self.device_particles:
             raise ValueError("--streak_jitter needs --device_particles")
         if self.streak_jitter and bool(self.noise_std):
@@ -482,6 +496,10 @@ class Generator:
                         hip.set_particle_noise(0.0, 0.0)
                     hip.set_particle_jitter(self.streak_jitter)
                     hip.set_particle_wind(*self.wind)
+                    if self.gusts is not None:                   # one series over every time index the run can name (f_name_idx)
+                        hip.set_particle_gusts(particles.gust_series(max(len(files), n_sim) + 1, opts["cam_hz"], *self.gusts))
+                    else:
+                        hip.set_particle_gusts(None)
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)

@@ -4699,6 +4699,48 @@ __device__ inline double wind_z(const WindArgs<WIND>& w) {
   if constexpr (WIND) return w.z; else return 0.0;
 }
 
+// GUST (rr_set_particle_gusts; a parameter of k_field_particles and k_rig_particles, count passes included -- the cull reads the
+// position; only with WIND): the series' table [n + 1][2] doubles, uploaded once by the setter and never written by a kernel.
+// G[m], G[m + 1] of the workgroup's frame are wave-uniform: four doubles through the constant address space, on the scalar path
+// like a trajectory's pose, once per 512-slot round (gust_frame_of says why not once per workgroup).  G[i], G[i + 1] around a life's birth differ per lane: two 16-byte vector loads that
+// rrsim::slot_fall issues before the life's Philox blocks.  GUST = false is the kernel as it was: an empty struct behind every
+// other argument.
+typedef double __attribute__((address_space(4))) const_f64;
+template <bool GUST>
+struct GustArgs {};
+template <>
+struct GustArgs<true> {
+  const double* tab;                          // [n + 1][2] metres
+  int32_t n;                                  // intervals
+  uint32_t frame0;                            // the time index of row 0
+};
+// m = frame - frame0 of the workgroup's frame, on the scalar side.  The host has checked frame0 <= frame < frame0 + n; the
+// comparison keeps any other index inside the table.
+template <bool GUST>
+__device__ inline uint32_t gust_index(const GustArgs<GUST>& ga, uint32_t frame) {
+  if constexpr (GUST) {
+    const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(frame - ga.frame0));
+    return d < (uint32_t)ga.n ? d : (uint32_t)(ga.n - 1);
+  } else {
+    return 0u;
+  }
+}
+// The frame's part of the series for one round of slots.  A kernel calls it INSIDE its loop over the rounds: the empty asm makes
+// the index opaque, so the four doubles are loaded again per round (scalar loads, a cache hit) and hold no register across the
+// rest of the round -- the store passes have none to spare.
+template <bool GUST>
+__device__ inline void gust_frame_of(const GustArgs<GUST>& ga, uint32_t mi, rrsim::GustFrame& g) {
+  if constexpr (GUST) {
+    asm volatile("" : "+s"(mi));
+    const const_f64* r = (const const_f64*)(ga.tab + 2 * (size_t)mi);
+    g.tab = reinterpret_cast<const rrsim::GustRow*>(ga.tab);
+    g.n = ga.n;
+    g.m = (double)mi;
+    g.gm.x = r[0]; g.gm.z = r[1];
+    g.gm1.x = r[2]; g.gm1.z = r[3];
+  }
+}
+
 // ---- the tail the three particle kernels share: finish the record, compact the kept ones, store whole lines.  No helper holds a
 // barrier: where a kernel synchronises, and why, is written in its own body. ----
 // Finish the record of a candidate that reached derive_drop: the first texture of its ratio bucket, CTR: plus the drop's pick,
@@ -4793,12 +4835,13 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
 // pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
 // twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
 // batches fill the chip by themselves) there is no count pass.
-template <bool COUNT, bool CTR, bool JIT, bool WIND = false>
+template <bool COUNT, bool CTR, bool JIT, bool WIND = false, bool GUST = false>
 __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
                                                           const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
                                                           int32_t* n_out, int32_t* chunk_cnt, int chunk_slots, double jitter_deg,
-                                                          const WindArgs<WIND> wa) {
+                                                          const WindArgs<WIND> wa, const GustArgs<GUST> ga) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
+  static_assert(WIND || !GUST, "the gust path forms the mean-wind additions");
   const int f = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   __shared__ rr_sim_frame s_sf;
   __shared__ int s_cnt[8];
@@ -4817,16 +4860,20 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
 #pragma unroll
   for (int k = 0; k < 4; k++) rdb[k] = ratio_db[k];
   const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
+  const uint32_t gmi = gust_index(ga, sf.frame);
   int base_out = s_base;
   for (int base = first; base < last; base += 512) {
     const int j = base + t;
+    rrsim::GustFrame gfr;
+    gust_frame_of(ga, gmi, gfr);
     bool keep = false;
     rr_drop d;
     if (j < last) {
       rrsim::Particle p;
       double life;
       uint32_t pw = 0;
-      if (rrsim::make_field_particle<WIND>(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr, wind_x(wa), wind_z(wa))) {
+      if (rrsim::make_field_particle<WIND, GUST>(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr, wind_x(wa), wind_z(wa),
+                                                 GUST ? &gfr : nullptr)) {
         double ratio;
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
         finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::life_jitter(sf, (uint32_t)j, life); });
@@ -4876,7 +4923,6 @@ struct RigViews {                    // the ACTIVE views in batch order, and the
 // addresses are wave-uniform and the table is never written by a kernel (constant address space): scalar loads.  The count pass
 // and the store pass read the same row and the count pass needs R0 and c0 only.  TRAJ = false is the kernel as it was: the
 // argument is an empty struct behind every other one.
-typedef double __attribute__((address_space(4))) const_f64;
 template <bool TRAJ>
 struct TrajArgs {};
 template <>
@@ -4886,12 +4932,14 @@ struct TrajArgs<true> {
   int32_t active[RR_MAX_VIEWS];               // the rig's number of the batch's view a
   int32_t n_views;
 };
-template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false, bool WIND = false>
+template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false, bool WIND = false, bool GUST = false>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
                                                         rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots,
-                                                        double jitter_deg, const TrajArgs<TRAJ> tj, const WindArgs<WIND> wa) {
+                                                        double jitter_deg, const TrajArgs<TRAJ> tj, const WindArgs<WIND> wa,
+                                                        const GustArgs<GUST> ga) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
+  static_assert(WIND || !GUST, "the gust path forms the mean-wind additions");
   const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int na = rv.n_active;
@@ -4916,12 +4964,15 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
   const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
   int row = 0;
   if constexpr (TRAJ) row = tj.rows[inst];
+  const uint32_t gmi = gust_index(ga, sf.frame);
   int step = 0;
   for (int base = first; base < last; base += 512) {
     const int j = base + t;
     const bool valid = j < last;
+    rrsim::GustFrame gfr;
+    gust_frame_of(ga, gmi, gfr);
     rrsim::RigSlot q;
-    if (valid) rrsim::make_rig_slot<WIND>(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q, wind_x(wa), wind_z(wa));
+    if (valid) rrsim::make_rig_slot<WIND, GUST>(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q, wind_x(wa), wind_z(wa), GUST ? &gfr : nullptr);
     // CTR: the slot's pick (0 .. 9) is live across the view loop, where the stream kernel has no register to spare.  It
     // takes the place of z_max, which every view step forms again from the diameter (the same expression as make_rig_slot's:
     // the same bits); the empty asm keeps the compiler from hoisting that back out of the loop.
@@ -5315,6 +5366,9 @@ struct rr_ctx {
   int particle_draws = RR_DRAWS_STREAM;   // rr_set_particle_draws: the texture pick from numpy's stream, or from the drop's own counter
   double jitter_deg = 0.0;                // rr_set_particle_jitter: degrees per unit of the drop's own normal deviate; 0: none
   double wind_x = 0.0, wind_z = 0.0;      // rr_set_particle_wind: the air's mean horizontal velocity, m/s; (0, 0): none
+  int32_t gust_n = 0;                     // rr_set_particle_gusts: intervals of the series; 0: none
+  uint32_t gust_frame0 = 0;
+  double* d_gust = nullptr;               // [gust_n + 1][2] metres
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
@@ -6293,6 +6347,24 @@ void with_wind(const rr_ctx* ctx, F fn) {
   }
 }
 
+// fn(WIND, WindArgs<WIND>, GUST, GustArgs<GUST>) for the field and rig kernels: with a gust series (rr_set_particle_gusts) the mean
+// wind's additions are formed whatever the mean; without one, with_wind's choice and the kernels as they were
+template <class F>
+void with_air(const rr_ctx* ctx, F fn) {
+  if (ctx->gust_n > 0) {
+    WindArgs<true> wa;
+    wa.x = ctx->wind_x;
+    wa.z = ctx->wind_z;
+    GustArgs<true> ga;
+    ga.tab = ctx->d_gust;
+    ga.n = ctx->gust_n;
+    ga.frame0 = ctx->gust_frame0;
+    fn(std::true_type{}, wa, std::true_type{}, ga);
+  } else {
+    with_wind(ctx, [&](auto wnd, auto wa) { fn(wnd, wa, std::false_type{}, GustArgs<false>{}); });
+  }
+}
+
 // The frames of a call with angular noise (run_pos >= 1): plan, per simulated frame, the steps from its held state (or its
 // pristine streaks) to each of its frames -- in run order, one chain per simulated frame -- and enqueue them (k_noise_chains).
 // The plan is made here, in call order, so the held states follow the order of the calls whatever the streams.
@@ -6478,6 +6550,20 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       ctx->traj_rows[(size_t)i] = (int32_t)(it - ctx->traj_frame.begin());
     }
   }
+  if (ctx->gust_n > 0) {                                       // (the series is only ever set under the field and rig models)
+    for (int f = 0; f < n; f++) {
+      const int64_t m = (int64_t)sims[f].frame - (int64_t)ctx->gust_frame0;
+      if (m < 0 || m >= ctx->gust_n) {
+        ctx->err = "rr_sim_frame.frame " + std::to_string(sims[f].frame) + " (frame " + std::to_string(f) + ") is outside the gust series' frames " +
+                   std::to_string(ctx->gust_frame0) + " .. " + std::to_string((int64_t)ctx->gust_frame0 + ctx->gust_n - 1) + " (rr_set_particle_gusts)";
+        return RR_E_ARG;
+      }
+      if (sims[f].run_pos != 0) {
+        ctx->err = "rr_sim_frame.run_pos " + std::to_string(sims[f].run_pos) + " (frame " + std::to_string(f) + "): run_pos must be 0 under a gust series";
+        return RR_E_ARG;
+      }
+    }
+  }
   const bool ctr = ctx->particle_draws == RR_DRAWS_COUNTER;
   const bool jit = ctx->jitter_deg != 0.0;
   int n_noisy = 0;
@@ -6560,8 +6646,8 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
       memcpy(rv.box, ctx->rig_box, sizeof rv.box);
       ProfScope ps(ctx, s, "k_rig_particles");
-      auto passes = [&](auto with_traj, auto with_wnd, auto wa) {   // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
-        constexpr bool TRAJ = decltype(with_traj)::value, WIND = decltype(with_wnd)::value;
+      auto passes = [&](auto with_traj, auto with_wnd, auto wa, auto with_gst, auto ga) {   // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
+        constexpr bool TRAJ = decltype(with_traj)::value, WIND = decltype(with_wnd)::value, GUST = decltype(with_gst)::value;
         TrajArgs<TRAJ> tj;
         if constexpr (TRAJ) {
           tj.poses = ctx->d_traj;
@@ -6571,25 +6657,25 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
         }
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa);
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa, ga);
         };
-        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND>);   // (a count depends neither on the draws nor on the jitter)
-        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND>); });
+        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND, GUST>);   // (a count depends neither on the draws nor on the jitter)
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND, GUST>); });
       };
-      with_wind(ctx, [&](auto wnd, auto wa) {
-        if (traj) passes(std::true_type{}, wnd, wa);
-        else passes(std::false_type{}, wnd, wa);
+      with_air(ctx, [&](auto wnd, auto wa, auto gst, auto ga) {
+        if (traj) passes(std::true_type{}, wnd, wa, gst, ga);
+        else passes(std::false_type{}, wnd, wa, gst, ga);
       });
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
-      with_wind(ctx, [&](auto wnd, auto wa) {
-        constexpr bool WIND = decltype(wnd)::value;
+      with_air(ctx, [&](auto wnd, auto wa, auto gst, auto ga) {
+        constexpr bool WIND = decltype(wnd)::value, GUST = decltype(gst)::value;
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa);
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa, ga);
         };
-        if (chunks > 1) launch(k_field_particles<true, false, false, WIND>);
-        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND>); });
+        if (chunks > 1) launch(k_field_particles<true, false, false, WIND, GUST>);
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND, GUST>); });
       });
     }
     if (!ctr) {
@@ -6752,6 +6838,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_ratio_db);
   hipFree(ctx->d_sims);
   hipFree(ctx->d_traj);
+  hipFree(ctx->d_gust);
   hipFree(ctx->d_gen_drops);
   hipFree(ctx->d_gen_counts);
   hipFree(ctx->d_field_cnt);
@@ -7251,6 +7338,11 @@ int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz) {
       return RR_E_ARG;
     }
   }
+  if (ctx->gust_n > 0 && model == RR_PARTICLES_IID) {
+    ctx->err = "rr_set_particle_model: a gust series is set and the i.i.d. model has no time; turn it off first (rr_set_particle_gusts with n 0)";
+    return RR_E_ARG;
+  }
+  ctx->gust_n = 0;                                            // a series is checked against cam_hz: a new model drops it
   ctx->particle_model = model;
   ctx->cam_hz = model != RR_PARTICLES_IID ? cam_hz : 0.0;
   return RR_OK;
@@ -7299,6 +7391,57 @@ int rr_set_particle_wind(rr_ctx* ctx, double wx, double wz) {
   }
   ctx->wind_x = wx;
   ctx->wind_z = wz;
+  return RR_OK;
+}
+
+int rr_set_particle_gusts(rr_ctx* ctx, int32_t n, uint32_t frame0, const double* disp) {
+  if (!ctx) return RR_E_ARG;
+  if (n < 0 || n > (1 << 20)) {
+    ctx->err = "rr_set_particle_gusts: n must be 0 .. 2^20, got " + std::to_string(n);
+    return RR_E_ARG;
+  }
+  if (n == 0) {
+    ctx->gust_n = 0;
+    return RR_OK;
+  }
+  if (ctx->particle_model != RR_PARTICLES_FIELD && ctx->particle_model != RR_PARTICLES_RIG) {
+    ctx->err = "rr_set_particle_gusts: a gust series needs the field or rig model (rr_set_particle_model first): the i.i.d. model has no time";
+    return RR_E_ARG;
+  }
+  if (!disp) {
+    ctx->err = "rr_set_particle_gusts: disp must be given";
+    return RR_E_ARG;
+  }
+  if ((uint64_t)frame0 + (uint64_t)n > (1ull << 32)) {
+    ctx->err = "rr_set_particle_gusts: frame0 + n is beyond 2^32";
+    return RR_E_ARG;
+  }
+  for (int32_t i = 0; i <= n; i++) {
+    const double x = disp[2 * (size_t)i], z = disp[2 * (size_t)i + 1];
+    if (!std::isfinite(x) || !std::isfinite(z)) {
+      ctx->err = "rr_set_particle_gusts: row " + std::to_string(i) + " is not finite";
+      return RR_E_ARG;
+    }
+    if (sqrt(x * x + z * z) > 1e6) {
+      ctx->err = "rr_set_particle_gusts: row " + std::to_string(i) + ": |G| is beyond 1e6 m";
+      return RR_E_ARG;
+    }
+    if (i > 0) {
+      const double sx = x - disp[2 * (size_t)i - 2], sz = z - disp[2 * (size_t)i - 1];
+      if (sqrt(sx * sx + sz * sz) * ctx->cam_hz > 100.0) {
+        ctx->err = "rr_set_particle_gusts: interval " + std::to_string(i - 1) + ": |step| * cam_hz is beyond 100 m/s";
+        return RR_E_ARG;
+      }
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipDeviceSynchronize());                            // (between runs: nothing of the context is in flight)
+  ctx->gust_n = 0;
+  int rc;
+  if ((rc = dev_alloc(ctx, ctx->d_gust, 2 * ((size_t)n + 1)))) return rc;
+  HIPCHK(hipMemcpy(ctx->d_gust, disp, sizeof(double) * 2 * ((size_t)n + 1), hipMemcpyHostToDevice));
+  ctx->gust_n = n;
+  ctx->gust_frame0 = frame0;
   return RR_OK;
 }
 

@@ -153,13 +153,68 @@ RR_HD SlotDraw slot_draw(const rr_sim_frame& sf, const double* dgrid, const doub
   return s;
 }
 
+// ---- GUSTS (rr_set_particle_gusts, tools/particles.py gusts=): a wind that changes over time, field and rig models ----
+// The series is a table G[0 .. n] of (x, z) metres: row i is the air's horizontal displacement at time index frame0 + i, linear
+// in between; the host makes it, the statements look up, interpolate and add.  GUST is a compile-time switch of the field and rig
+// generators, instantiated with WIND = true only (the gust path forms both mean-wind additions, also for a mean of (0, 0)).  With
+// m = frame - frame0 (0 <= m < n, the host's check) and back = tau cam_hz the frames since the life's birth:
+//   sb = m - back;  i = max(floor(sb), 0);  Gb = G[i] + (sb - i) (G[i + 1] - G[i])      the air at the drop's birth
+//   dG = G[m] - Gb                                   the air's displacement over the drop's life so far
+//   ge = (G[m + 1] - G[m]) cam_hz                    the air's velocity during this frame's interval
+// (sb < 0: the first interval's velocity is held).  dG joins v tau in the position of a life, ge joins v in the streak's end.
+// GUST = false is every function as it was: no GustFrame is read, no field of it exists in a caller's registers.
+struct alignas(16) GustRow { double x, z; };   // one row of the table: 16 bytes, one load
+struct GustFrame {                // what a frame's generators get of the series: wave-uniform
+  const GustRow* tab;             // G[0 .. n]; never written by a kernel
+  int32_t n;                      // intervals
+  double m;                       // frame - frame0: an exact integer, 0 <= m < n
+  GustRow gm, gm1;                // G[m], G[m + 1]
+};
+// the frame's part, from the table itself (the host build; a kernel fills the same fields through its scalar path)
+RR_HD GustFrame gust_frame(const double* tab, int32_t n, uint32_t frame0, uint32_t frame) {
+  GustFrame g;
+  g.tab = reinterpret_cast<const GustRow*>(tab);
+  g.n = n;
+  const uint32_t mi = frame - frame0;
+  g.m = (double)mi;
+  g.gm = g.tab[mi];
+  g.gm1 = g.tab[mi + 1];
+  return g;
+}
+struct GustBirth {                // the two rows around a life's birth and the fraction between them: per lane
+  GustRow g0, g1;
+  double fr;
+};
+// the look-up: issued as soon as tau is known, before the life's Philox blocks, so that those cover its latency.  The index is an
+// exact integer in 0 .. m <= n - 1; the comparison keeps any other value (a NaN from settings nobody checked) inside the table.
+RR_HD void gust_birth(const GustFrame& gf, double cam_hz, double tau, GustBirth& gb) {
+  const double back = tau * cam_hz;
+  const double sb = gf.m - back;
+  const double i = rr::dmax(floor(sb), 0.0);
+  const int32_t ii = i < (double)gf.n ? (int32_t)i : gf.n - 1;
+  gb.fr = sb - i;
+  gb.g0 = gf.tab[ii];
+  gb.g1 = gf.tab[ii + 1];
+}
+// (dGx, dGz) and (gex, gez)
+RR_HD void gust_terms(const GustFrame& gf, double cam_hz, const GustBirth& gb, double dG[2], double ge[2]) {
+  const double bx = gb.g0.x + gb.fr * (gb.g1.x - gb.g0.x);
+  const double bz = gb.g0.z + gb.fr * (gb.g1.z - gb.g0.z);
+  dG[0] = gf.gm.x - bx;
+  dG[1] = gf.gm.z - bz;
+  ge[0] = (gf.gm1.x - gf.gm.x) * cam_hz;
+  ge[1] = (gf.gm1.z - gf.gm.z) * cam_hz;
+}
+
 struct SlotFall {                 // where slot j is in its fall through a box of height wy at time index sf.frame
   double v;                       // terminal velocity, m/s
   double life, age, tau;          // completed falls g, the fraction of the current one, seconds since it began
   double wind;                    // the life's wind (block 2)
   uint32_t b[4];                  // the life's block 1: lateral start, start depth, the texture pick's word
 };
-RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, double D, double wy, double phase) {
+template <bool GUST = false>
+RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, double D, double wy, double phase, const GustFrame* gf = nullptr,
+                         GustBirth* gb = nullptr) {
   SlotFall f;
   f.v = terminal_velocity(D);
   const double T = wy / f.v;
@@ -168,6 +223,7 @@ RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, doub
   f.life = floor(s);
   f.age = s - f.life;
   f.tau = f.age * T;
+  if constexpr (GUST) gust_birth(*gf, cam_hz, f.tau, *gb);
   uint32_t c[4];
   life_counter(j, f.life, 1u, f.b);
   life_counter(j, f.life, 2u, c);
@@ -178,19 +234,33 @@ RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, doub
 }
 
 // Returns whether the particle is inside the frustum; `life` = g; *pick_word = word 2 of the life's block 1 (texture_pick).
-template <bool WIND = false>
+template <bool WIND = false, bool GUST = false>
 RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
-                               Particle& p, double& life, uint32_t* pick_word = nullptr, double wind_x = 0.0, double wind_z = 0.0) {
+                               Particle& p, double& life, uint32_t* pick_word = nullptr, double wind_x = 0.0, double wind_z = 0.0,
+                               const GustFrame* gf = nullptr) {
+  static_assert(WIND || !GUST, "the gust path forms the mean-wind additions: GUST needs WIND");
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
   const double hx = ((0.5 + sf.margin) * W) / sf.fpx, hy = ((0.5 + sf.margin) * H) / sf.fpx;   // frustum half-widths at unit depth
   const double bx = hx * s.z_max, by = hy * s.z_max;
   const double wx = 2.0 * bx, wy = 2.0 * by;
-  const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
+  GustBirth gb;
+  const SlotFall f = slot_fall<GUST>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb);
   double vx = f.wind, vz = sf.speed_mps;
   if constexpr (WIND) { vx = f.wind + wind_x; vz = sf.speed_mps + wind_z; }
-  const double qx = unit32(f.b[0]) + (vx * f.tau) / wx;   // box coordinates in units of the box: wrapped into [0, 1)
-  const double qz = unit32(f.b[1]) - (vz * f.tau) / s.z_max;
+  double qx, qz;                                            // box coordinates in units of the box: wrapped into [0, 1)
+  double ux = vx, uz = vz;                                  // the velocity of the streak's end
+  if constexpr (GUST) {
+    double dG[2], ge[2];
+    gust_terms(*gf, cam_hz, gb, dG, ge);
+    qx = unit32(f.b[0]) + (vx * f.tau + dG[0]) / wx;
+    qz = unit32(f.b[1]) - (vz * f.tau + dG[1]) / s.z_max;
+    ux = vx + ge[0];
+    uz = vz + ge[1];
+  } else {
+    qx = unit32(f.b[0]) + (vx * f.tau) / wx;
+    qz = unit32(f.b[1]) - (vz * f.tau) / s.z_max;
+  }
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   const double X = fx * wx - bx;
   const double Y = by - f.age * wy;
@@ -200,9 +270,9 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   const double depth = rr::dmax(zr, 0.05);
   const double Z = -depth;
   const double e = sf.exposure_s;
-  const double X2 = X + vx * e;
+  const double X2 = X + ux * e;
   const double Y2 = Y - f.v * e;
-  const double Z2 = Z + vz * e;
+  const double Z2 = Z + uz * e;
   life = f.life;
   if (pick_word) *pick_word = f.b[2];
   p.wp1[0] = X; p.wp1[1] = Y; p.wp1[2] = Z;
@@ -225,21 +295,34 @@ struct RigSlot {
   double wd, z_max;               // diameter (m), farthest depth shown (the box's half side in x and z is box[0] z_max)
   double life;
   uint32_t pick_word;             // word 2 of the life's block 1 (texture_pick): one pick for every view and frame of the life
-  double vx, vz;                  // WIND only (else not written, not read): rig-frame velocity (vx, -v, vz) under the mean wind
+  double vx, vz;                  // WIND only (else not written, not read): rig-frame velocity (vx, -v, vz) under the mean wind;
+                                  // GUST: plus the frame's gust velocity (gex, gez) -- every view and a trajectory's end use it unchanged
 };
 
-template <bool WIND = false>
+template <bool WIND = false, bool GUST = false>
 RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
-                         uint32_t j, RigSlot& q, double wx = 0.0, double wz = 0.0) {
+                         uint32_t j, RigSlot& q, double wx = 0.0, double wz = 0.0, const GustFrame* gf = nullptr) {
+  static_assert(WIND || !GUST, "the gust path forms the mean-wind additions: GUST needs WIND");
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double b = box[0] * s.z_max;
   const double by = box[1] * s.z_max + box[2];
   const double w = 2.0 * b, wy = 2.0 * by;
-  const SlotFall f = slot_fall(sf, cam_hz, j, s.D, wy, s.phase);
+  GustBirth gb;
+  const SlotFall f = slot_fall<GUST>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb);
   double vx = f.wind, vz = sf.speed_mps;
   if constexpr (WIND) { q.vx = vx = f.wind + wx; q.vz = vz = sf.speed_mps + wz; }
-  const double qx = unit32(f.b[0]) + (vx * f.tau) / w;
-  const double qz = unit32(f.b[1]) + (vz * f.tau) / w;             // the vehicle's motion: drops gain +speed in z
+  double qx, qz;
+  if constexpr (GUST) {                                             // once per slot, not per view
+    double dG[2], ge[2];
+    gust_terms(*gf, cam_hz, gb, dG, ge);
+    qx = unit32(f.b[0]) + (vx * f.tau + dG[0]) / w;
+    qz = unit32(f.b[1]) + (vz * f.tau + dG[1]) / w;
+    q.vx = vx + ge[0];
+    q.vz = vz + ge[1];
+  } else {
+    qx = unit32(f.b[0]) + (vx * f.tau) / w;
+    qz = unit32(f.b[1]) + (vz * f.tau) / w;                         // the vehicle's motion: drops gain +speed in z
+  }
   const double fx = qx - floor(qx), fz = qz - floor(qz);
   q.X = fx * w - b;
   q.Y = by - f.age * wy;

@@ -159,7 +159,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_trajectory',
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose']
 
 _lib = None
@@ -260,6 +260,7 @@ def load_library(path=None):
     lib.rr_set_particle_draws.argtypes = [ctypes.c_void_p, ctypes.c_int32]
     lib.rr_set_particle_jitter.argtypes = [ctypes.c_void_p, ctypes.c_double]
     lib.rr_set_particle_wind.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
+    lib.rr_set_particle_gusts.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
@@ -886,6 +887,20 @@ class RainHip:
         Every model, both draws, with jitter, rigs and trajectories.  Streaks then slant the same way all over the image:
         render them with set_option(RR_OPT_STREAK_LEAN, 1)."""
         self._check(self.lib.rr_set_particle_wind(self.h, float(wx), float(wz)), 'rr_set_particle_wind')
+
+    def set_particle_gusts(self, gusts=None):
+        """rr_set_particle_gusts: a wind that changes over time under the field and rig models -- `gusts` = a
+        tools/particles.GustSeries (frame0, disp [(n + 1), 2] metres: the air's displacement at time indices frame0 .. frame0 + n), or
+        None: off.  After set_particle_model (a later one drops the series); every generated record's frame must lie inside it."""
+        if gusts is None:
+            self._check(self.lib.rr_set_particle_gusts(self.h, 0, 0, None), 'rr_set_particle_gusts')
+            return
+        d = np.ascontiguousarray(gusts.disp, np.float64)
+        if d.ndim != 2 or d.shape[1] != 2 or len(d) < 2:
+            raise ValueError("gust series: disp must be (n + 1) x 2 with n >= 1, got shape %r" % (d.shape,))
+        if not 0 <= int(gusts.frame0) < 2 ** 32:
+            raise ValueError("gust series: frame0 %d is outside 0 .. 2^32 - 1" % int(gusts.frame0))
+        self._check(self.lib.rr_set_particle_gusts(self.h, len(d) - 1, int(gusts.frame0), _ptr(d)), 'rr_set_particle_gusts')
 
     def set_particle_rig(self, views, box, active=None):
         """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =

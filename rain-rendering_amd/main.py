@@ -75,10 +75,15 @@ _FLAGS = [
                             "rig's axes under --particle_model rig, the world's under --trajectory): 5,0 makes the rain fall at 40 degrees to "
                             "the vertical, small drops leaning more than large ones; any --particle_model, --particle_draws and "
                             "--streak_jitter")),
+    (('--gusts',), dict(type=str, default=None,
+                        help="with --device_particles --particle_model field|rig: SIGMA[,TAU[,SEED]], a wind that changes over time on top "
+                             "of --wind: per component an Ornstein-Uhlenbeck velocity of standard deviation SIGMA m/s (0 < SIGMA <= 20) and "
+                             "correlation time TAU seconds (default 2), from SEED (default 0), over the run's frame indices: the slant "
+                             "sways over seconds, coherently for every drop and every view")),
     (('--streak_lean',), dict(type=str, default='auto', choices=['auto', 'on', 'off'],
                               help="'on': a streak tile's lean and corner come from the streak's own end points; 'off': the reference's rule "
                                    "(lean by the image half the streak ends in, corner at its start: right for streaks that radiate from the "
-                                   "image centre); 'auto' (default): on exactly when a non-zero --wind is given")),
+                                   "image centre); 'auto' (default): on exactly when a non-zero --wind or --gusts is given")),
     (('--rig',), dict(type=str, default=None, help="with --particle_model rig: 'mono' (one camera), 'stereo:<baseline in metres>' (KITTI: stereo:0.54; view 0 "
                                                    "left, view 1 right) or a JSON file {\"views\": [{\"R\": [...9], \"c\": [...3]}, ...]}")),
     (('--trajectory',), dict(type=str, default=None,
@@ -101,8 +106,9 @@ def _parse(argv):
 
 
 def _wind_and_lean(ns):
-    """--wind WX,WZ as a pair of floats (default (0, 0)) and --streak_lean as ns.lean: 'auto' is on exactly when a non-zero wind is
-    given, so that no command line without --wind changes its output."""
+    """--wind WX,WZ as a pair of floats (default (0, 0)), --gusts SIGMA[,TAU[,SEED]] as (sigma, tau, seed) or None, and --streak_lean as
+    ns.lean: 'auto' is on exactly when a non-zero wind or a gust series is given, so that no command line without --wind or --gusts
+    changes its output."""
     wind = getattr(ns, 'wind', None)
     if wind is not None and not isinstance(wind, tuple):
         try:
@@ -114,8 +120,22 @@ def _wind_and_lean(ns):
         if any(wind) and not ns.device_particles:
             raise SystemExit("--wind needs --device_particles (the wind moves the particles the GPU's generator makes)")
     ns.wind = wind if wind is not None else (0.0, 0.0)
+    gusts = getattr(ns, 'gusts', None)
+    if gusts is not None and not isinstance(gusts, tuple):     # --gusts SIGMA[,TAU[,SEED]] as (sigma, tau, seed)
+        parts = str(gusts).split(',')
+        try:
+            gusts = (float(parts[0]), float(parts[1]) if len(parts) > 1 else 2.0, int(parts[2]) if len(parts) > 2 else 0)
+        except ValueError:
+            gusts = ()
+        if not 1 <= len(parts) <= 3 or len(gusts) != 3 or not (math.isfinite(gusts[0]) and 0 < gusts[0] <= 20.0) or \
+                not (math.isfinite(gusts[1]) and gusts[1] > 0) or not 0 <= gusts[2] < 2 ** 32:
+            raise SystemExit("--gusts %r: expected SIGMA[,TAU[,SEED]] with 0 < SIGMA <= 20 m/s, TAU > 0 seconds, SEED an integer in "
+                             "[0, 2^32)" % (ns.gusts,))
+        if not ns.device_particles or getattr(ns, 'particle_model', 'iid') not in ('field', 'rig'):
+            raise SystemExit("--gusts needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
+    ns.gusts = gusts
     mode = getattr(ns, 'streak_lean', 'auto') or 'auto'
-    ns.lean = any(ns.wind) if mode == 'auto' else mode == 'on'
+    ns.lean = (any(ns.wind) or ns.gusts is not None) if mode == 'auto' else mode == 'on'
     return ns
 
 

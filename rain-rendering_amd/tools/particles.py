@@ -103,6 +103,22 @@ the box: the law at one instant does not change).  Slot counts, boxes, lives and
 (default) is off and forms no sum at all (``x + 0.0`` is not ``x`` for ``x = -0.0``, which ``_block_wind`` gives at
 ``wind_sigma = 0``): the records are those without the keyword, byte for byte.  A uniform slant needs the renderer's
 ``RR_OPT_STREAK_LEAN``.  The host XML writer's default path (``simulate``) has no wind.
+
+Gusts (``gusts=GustSeries``, ``rr_set_particle_gusts`` in the library; field and rig models): a wind that changes over time, as
+the air's horizontal DISPLACEMENT sampled at frame times.  ``disp[(n + 1), 2]`` holds (x, z) metres, row i at time index
+``frame0 + i``; the air moves linearly between samples.  The table is data: the host makes it any way it likes
+(``gust_series``: an Ornstein-Uhlenbeck velocity), the statements only look up, interpolate and add (``_gust_terms``).  With
+m = frame - frame0 (0 <= m < n) and back = tau cam_hz the frames since the life's birth:
+    sb = m - back;  i = max(floor(sb), 0);  Gb = G[i] + (sb - i) (G[i + 1] - G[i])     -- the air at the drop's birth
+    dG = G[m] - Gb                                                  -- the air's displacement over the drop's life so far
+    ge = (G[m + 1] - G[m]) cam_hz                                   -- the air's velocity during this frame's interval
+(before the series starts the first interval's velocity is held: a constant-velocity series is a mean wind).  They enter where
+the mean wind enters: ``(vx tau + dGx) / box`` in the position of a life, ``vx + gex`` in the streak's end (the rig slot's
+velocity carries it: every view and a trajectory's end pose use it unchanged); vx, vz are ``_drift``'s, and with a series both
+mean-wind additions are formed, also for a mean of (0, 0).  Nothing else depends on the series: slot counts, boxes, lives,
+Philox blocks, tables, the pick, the jitter.  Inside a life the term is a translation modulo the box that does not depend on the
+uniform start: one frame keeps the i.i.d. law.  Drops follow the air with no inertia.  ``gusts=None`` (default) is off and forms
+no addition.  The i.i.d. model has no time and refuses a series.
 """
 import os
 
@@ -504,13 +520,109 @@ def _check_wind(wind):
     return wx, wz
 
 
-def _drift(wind_life, speed, wind):
+def _drift(wind_life, speed, wind, gusts=None):
     """A drop's horizontal velocity (vx, vz) under the mean wind `wind` (rr_particles.h WIND): the life's own wind plus wx, the
-    vehicle's speed plus wz -- one addition each.  wind == (0, 0): the two inputs themselves, no addition (module docstring)."""
+    vehicle's speed plus wz -- one addition each.  wind == (0, 0): the two inputs themselves, no addition (module docstring) --
+    unless a gust series is given: the gust path forms both additions whatever the mean."""
     wx, wz = _check_wind(wind)
-    if wx == 0.0 and wz == 0.0:
+    if wx == 0.0 and wz == 0.0 and gusts is None:
         return wind_life, speed
     return wind_life + wx, float(speed) + wz
+
+
+# ---- gusts: the air's displacement sampled at frame times (module docstring; rr_set_particle_gusts) -------------------
+GUST_MAX_N = 1 << 20                 # intervals of a series
+GUST_MAX_DISP = 1e6                  # metres
+GUST_MAX_SPEED = 100.0               # m/s over any interval
+
+
+class GustSeries:
+    """frame0: the time index of row 0; disp [(n + 1), 2]: the air's horizontal displacement (x, z) in metres at time indices
+    frame0 .. frame0 + n.  Covers the frames frame0 <= k < frame0 + n."""
+
+    def __init__(self, frame0, disp):
+        self.frame0 = int(frame0)
+        self.disp = np.ascontiguousarray(disp, np.float64)
+
+    @property
+    def n(self):
+        return len(self.disp) - 1
+
+    def covers(self, k):
+        k = np.asarray(k, np.int64)
+        return (k >= self.frame0) & (k < self.frame0 + self.n)
+
+
+def _check_gusts(gusts, cam_hz, model='field', frames=None):
+    """rr_set_particle_gusts' refusals (and the generator's, for the time indices `frames`) as ValueError.  Returns `gusts`."""
+    if gusts is None:
+        return None
+    if not isinstance(gusts, GustSeries):
+        raise ValueError("gusts %r: expected a particles.GustSeries or None" % (gusts,))
+    if model not in ('field', 'rig'):
+        raise ValueError("a gust series needs particle model 'field' or 'rig': the i.i.d. model has no time")
+    if cam_hz is None or not np.isfinite(float(cam_hz)) or not float(cam_hz) > 0:
+        raise ValueError("a gust series needs cam_hz > 0")
+    G = gusts.disp
+    if G.ndim != 2 or G.shape[1] != 2 or len(G) < 2:
+        raise ValueError("gust series: disp must be (n + 1) x 2 with n >= 1, got shape %r" % (G.shape,))
+    n = len(G) - 1
+    if n > GUST_MAX_N:
+        raise ValueError("gust series: n = %d is beyond 2^20 intervals" % n)
+    if gusts.frame0 < 0 or gusts.frame0 + n > 2 ** 32:
+        raise ValueError("gust series: frame0 %d + n %d must lie in 0 .. 2^32" % (gusts.frame0, n))
+    if not np.isfinite(G).all():
+        raise ValueError("gust series: every displacement must be finite")
+    if (np.sqrt(G[:, 0] * G[:, 0] + G[:, 1] * G[:, 1]) > GUST_MAX_DISP).any():
+        raise ValueError("gust series: a displacement is beyond 1e6 m")
+    st = G[1:] - G[:-1]
+    if (np.sqrt(st[:, 0] * st[:, 0] + st[:, 1] * st[:, 1]) * float(cam_hz) > GUST_MAX_SPEED).any():
+        raise ValueError("gust series: an interval's |step| * cam_hz is beyond 100 m/s")
+    if frames is not None and not gusts.covers(np.asarray(frames, np.int64) & 0xFFFFFFFF).all():
+        raise ValueError("time index outside the gust series' frames %d .. %d" % (gusts.frame0, gusts.frame0 + n - 1))
+    return gusts
+
+
+def gust_series(n, cam_hz, sigma, tau_s, seed, frame0=0):
+    """A GustSeries of n intervals at cam_hz frames per second: per component an Ornstein-Uhlenbeck velocity with stationary
+    standard deviation `sigma` (m/s) and correlation time `tau_s` (seconds), one value per interval (exact discretisation:
+    u[i + 1] = a u[i] + sigma sqrt(1 - a^2) N(0, 1), a = exp(-1 / (cam_hz tau_s)), u[0] = sigma N(0, 1)), from
+    np.random.RandomState(seed).  The displacement is the sequential sum of velocity / cam_hz from 0 (np.add.accumulate)."""
+    n, cam_hz, sigma, tau_s = int(n), float(cam_hz), float(sigma), float(tau_s)
+    if n < 1 or n > GUST_MAX_N:
+        raise ValueError("gust_series: n must be 1 .. 2^20, got %d" % n)
+    if not (np.isfinite(cam_hz) and cam_hz > 0 and np.isfinite(sigma) and sigma >= 0 and np.isfinite(tau_s) and tau_s > 0):
+        raise ValueError("gust_series: cam_hz > 0, sigma >= 0 and tau_s > 0 must be finite")
+    rs = np.random.RandomState(int(seed) % (2 ** 32))
+    z = rs.standard_normal((n, 2))
+    a = float(np.exp(-1.0 / (cam_hz * tau_s)))
+    b = sigma * float(np.sqrt(1.0 - a * a))
+    u = np.zeros((n, 2), np.float64)
+    u[0] = sigma * z[0]
+    for i in range(1, n):
+        u[i] = a * u[i - 1] + b * z[i]
+    disp = np.zeros((n + 1, 2), np.float64)
+    disp[1:] = np.add.accumulate(u / cam_hz, axis=0)
+    return _check_gusts(GustSeries(frame0, disp), cam_hz)
+
+
+def _gust_terms(gusts, k, tau, cam_hz):
+    """rr_particles.h gust_birth / gust_terms: (dG (n, 2), ge (2,)) of the slots whose lives began `tau` seconds before time
+    index k (module docstring): look up, interpolate, add -- one operation per step."""
+    G = gusts.disp
+    m = (int(k) & 0xFFFFFFFF) - gusts.frame0
+    if not 0 <= m < gusts.n:
+        raise ValueError("time index %d is outside the gust series' frames %d .. %d" % (int(k), gusts.frame0, gusts.frame0 + gusts.n - 1))
+    back = tau * float(cam_hz)
+    sb = float(m) - back
+    i = np.maximum(np.floor(sb), 0.0)
+    ii = i.astype(np.int64)
+    fr = sb - i
+    g0, g1 = G[ii], G[ii + 1]
+    Gb = g0 + fr[:, None] * (g1 - g0)
+    dG = G[m][None, :] - Gb
+    ge = (G[m + 1] - G[m]) * float(cam_hz)
+    return dG, ge
 
 
 def _project(cam, X, Y, depth, wd):
@@ -617,7 +729,7 @@ def _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma):
 
 
 def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                         cull=True, wind=(0.0, 0.0)):
+                         cull=True, wind=(0.0, 0.0), gusts=None):
     """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
     of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
     life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
@@ -631,9 +743,16 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     bx, by = hx * z_max, hy * z_max
     wx, wy = 2.0 * bx, 2.0 * by
     v, g, age, tau, b, wind_life = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
-    vx, vz = _drift(wind_life, cam.speed, wind)
-    qx = unit32(b[0]) + (vx * tau) / wx
-    qz = unit32(b[1]) - (vz * tau) / z_max
+    vx, vz = _drift(wind_life, cam.speed, wind, gusts)
+    ex, ez = vx, vz                                            # the velocity of the streak's end
+    if gusts is None:
+        qx = unit32(b[0]) + (vx * tau) / wx
+        qz = unit32(b[1]) - (vz * tau) / z_max
+    else:
+        dG, ge = _gust_terms(_check_gusts(gusts, cam_hz), k, tau, cam_hz)
+        qx = unit32(b[0]) + (vx * tau + dG[:, 0]) / wx
+        qz = unit32(b[1]) - (vz * tau + dG[:, 1]) / z_max
+        ex, ez = vx + ge[0], vz + ge[1]
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
     X = fx * wx - bx
     Y = by - age * wy
@@ -643,29 +762,32 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     depth = np.maximum(zr, 0.05)
     Z = -depth
     e = cam.exposure
-    X2 = X + vx * e
+    X2 = X + ex * e
     Y2 = Y - v * e
-    Z2 = Z + vz * e
+    Z2 = Z + ez * e
     rec = _records(n_slots, [X, Y, Z], [X2, Y2, Z2], wd, *_project(cam, X, Y, depth, wd), *_project(cam, X2, Y2, np.maximum(-Z2, 0.05), wd))
     if cull:
         return rec[inside], g[inside]
     return rec, g
 
 
-def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0, wind=(0.0, 0.0)):
+def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0, wind=(0.0, 0.0),
+                     gusts=None):
     """Velocity (n, 3) in m/s (x right, y up, z towards the camera) of the given slots in the given lives, and the slots'
-    boxes (n, 3): full width, full height, depth -- what tests compare a track's displacement with."""
+    boxes (n, 3): full width, full height, depth -- what tests compare a track's displacement with.  With `gusts` the velocity
+    is the drop's own against the air, (vx, -v, vz) with both mean-wind additions formed: a frame's gust velocity ge and the
+    air's step G[m + 1] - G[m] depend on the time index and are added by the caller."""
     j = np.asarray(slots, np.uint64)
     key = _key(seed)
     D, _, _, z_max = _slot_draw(cam, dgrid, cdf, j, key, min_px, z_far)
     hx, hy = ((0.5 + margin) * float(cam.W)) / cam.fpx, ((0.5 + margin) * float(cam.H)) / cam.fpx
-    vx, vz = _drift(_block_wind(philox4x32(*_life_counter(j, lives, 2), *key), wind_sigma), cam.speed, wind)
+    vx, vz = _drift(_block_wind(philox4x32(*_life_counter(j, lives, 2), *key), wind_sigma), cam.speed, wind, gusts)
     vel = np.stack([vx, -terminal_velocity(D), np.full(len(j), float(vz))], axis=1)
     return vel, np.stack([2.0 * (hx * z_max), 2.0 * (hy * z_max), z_max], axis=1)
 
 
 def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-                cull=True, wind=(0.0, 0.0)):
+                cull=True, wind=(0.0, 0.0), gusts=None):
     """Frame `k` of a field-model run ALONE: (PARTICLE_DTYPE records with pid = slot id, life per record) of the particles
     inside the frustum -- the identity of a frame's particles.  Time index k, settings of simulated frame k % n_sim
     (n_sim: n_sim_frames(options) by default).  `generate(..., model='field')` is these frames one after the other."""
@@ -674,7 +796,7 @@ def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.0
     cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
     _, dgrid, cdf, _ = expected_count(cam, rate, min_px, z_far, margin)
     n_slots = int(field_slot_counts(options, fallrate, ks + 1, seed, min_px, z_far, margin, count)[ks])
-    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind)
+    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind, gusts=gusts)
 
 
 # ---- the RIG model: one field, several cameras (module docstring) --------------------------------------------------
@@ -728,7 +850,7 @@ def rig_tables(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=
                    lambda cam, rate: rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far))
 
 
-def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0, wind=(0.0, 0.0)):
+def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0, wind=(0.0, 0.0), gusts=None):
     """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters (rr_particles.h
     make_rig_slot): dict(D, z_max, b (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
     r, r_y, o_y = (float(v) for v in box)
@@ -739,9 +861,15 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
     by = r_y * z_max + o_y
     w, wy = 2.0 * b, 2.0 * by
     v, g, age, tau, bb, wind_life = _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma)
-    vx, vz = _drift(wind_life, cam.speed, wind)
-    qx = unit32(bb[0]) + (vx * tau) / w
-    qz = unit32(bb[1]) + (vz * tau) / w
+    vx, vz = _drift(wind_life, cam.speed, wind, gusts)
+    if gusts is None:
+        qx = unit32(bb[0]) + (vx * tau) / w
+        qz = unit32(bb[1]) + (vz * tau) / w
+    else:                                                      # the slot's velocity carries the frame's gust: once per slot, for every view
+        dG, ge = _gust_terms(_check_gusts(gusts, cam_hz, 'rig'), k, tau, cam_hz)
+        qx = unit32(bb[0]) + (vx * tau + dG[:, 0]) / w
+        qz = unit32(bb[1]) + (vz * tau + dG[:, 1]) / w
+        vx, vz = vx + ge[0], float(vz) + ge[1]
     fx, fz = qx - np.floor(qx), qz - np.floor(qz)
     X = fx * w - b
     Y = by - age * wy
@@ -751,7 +879,7 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
 
 
 def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                       cull=True, image=(0, 0), view_end=None, wind=(0.0, 0.0)):
+                       cull=True, image=(0, 0), view_end=None, wind=(0.0, 0.0), gusts=None):
     """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
     statement of rr_particles.h make_rig_slot + rig_view_particle (traj_view_start, rig_view_end; same operations, same order).  `box` = (r, r_y, o_y).
     Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
@@ -765,7 +893,7 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
         return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
     R = [float(v) for v in np.asarray(view[0], np.float64).reshape(9)]
     c = [float(v) for v in np.asarray(view[1], np.float64).reshape(3)]
-    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind)
+    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind, gusts=gusts)
     W, H = float(cam.W), float(cam.H)
     hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
     b, z_max, wd = st['b'], st['z_max'], st['wd']
@@ -814,7 +942,7 @@ def _traj_cam(cam):
 
 
 def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-              cull=True, image=(0, 0), trajectory=None, box=None, wind=(0.0, 0.0)):
+              cull=True, image=(0, 0), trajectory=None, box=None, wind=(0.0, 0.0), gusts=None):
     """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame.  With
     `trajectory` (trajectory.Trajectory): the view's composed poses of time index k, the trajectory's box and slot counts, speed 0.
     `box`: another box than the run's (tests)."""
@@ -831,7 +959,7 @@ def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, m
         po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
         cam, pose, view_end = _traj_cam(cam), (po['R0'], po['c0']), (po['R1'], po['c1'])
     return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, pose, box, wind_sigma, margin, min_px, z_far, cull, image,
-                              view_end=view_end, wind=wind)
+                              view_end=view_end, wind=wind, gusts=gusts)
 
 
 def rig_run_sims(sims, k_idx, n_active):
@@ -841,13 +969,15 @@ def rig_run_sims(sims, k_idx, n_active):
 
 
 def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid',
-             wind=(0.0, 0.0)):
+             wind=(0.0, 0.0), gusts=None):
     """(frames, drops) record arrays of `n_frames` camera frames.  `count`: force that many drops per frame instead
     of the Poisson-distributed physical count.  model='field': the persistent field (module docstring), frame k at time
     k / cam_hz under the settings of simulated frame k; pid is then the slot id.  (The rig model has no particle file: its
     frames are made per view, rig_frame.)"""
     frames = np.zeros(n_frames, PARTICLE_FRAME_DTYPE)
     _check_model(model)
+    if gusts is not None and model == 'iid':
+        raise ValueError("a gust series needs particle model 'field' or 'rig': the i.i.d. model has no time")
     if model == 'rig':
         raise ValueError("particle model 'rig' writes no particle file: use rig_frame / expected_records (one table per view)")
     if model == 'field':
@@ -865,7 +995,7 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
         _, dgrid, cdf, _ = tables[tk]
         n = int(counts[k])
         if model == 'field':
-            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, wind=wind)
+            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, wind=wind, gusts=gusts)
             n = len(rec)
         else:
             rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far, wind=wind)
@@ -931,7 +1061,7 @@ def field_run_sims(sims, f_idx):
 
 
 def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0, trajectory=None,
-                  wind=(0.0, 0.0)):
+                  wind=(0.0, 0.0), gusts=None):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
     texture pick of every row (counter_picks of the row's particle); with `jitter`, `jitter_g`: the row's counter_jitter."""
@@ -951,9 +1081,9 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
                 raise ValueError("time index %d is outside the trajectory's %d poses" % (k, len(po)))
             po = po[k, int(view)]
             pose, box, view_end = (po['R0'], po['c0']), trajectory.bind(rig), (po['R1'], po['c1'])
-        rec, life = make_rig_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), pose, _rig_box(box, cam, margin), view_end=view_end, **kw)
+        rec, life = make_rig_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), pose, _rig_box(box, cam, margin), view_end=view_end, gusts=gusts, **kw)
     elif model == 'field':
-        rec, life = make_field_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), **kw)
+        rec, life = make_field_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), gusts=gusts, **kw)
     else:
         rec = make_particles(cam, dgrid, tab, n, k, seed, **kw)
     fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
@@ -974,7 +1104,8 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
 
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
-                     rig=None, view=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0)):
+                     rig=None, view=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0),
+                     gusts=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -1004,10 +1135,17 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     run_pos must be 0.
 
     wind=(wx, wz) (rr_set_particle_wind; every model, both draws, with jitter, rig and trajectory): the records of the particles
-    made under that mean wind (module docstring).  (0, 0): the records above."""
+    made under that mean wind (module docstring).  (0, 0): the records above.
+
+    gusts=GustSeries (rr_set_particle_gusts; field and rig models, both draws, with jitter, wind and trajectory): the records of the
+    particles made under that gust series; every record's frame must lie inside it and run_pos must be 0.  None: the records above."""
     from .. import hip_backend
     _check_model(model)
     wind = _check_wind(wind)
+    if gusts is not None:
+        _check_gusts(gusts, cam_hz, model, frames=[int(s['frame']) for s in sims])
+        if any(int(s['run_pos']) != 0 for s in sims):
+            raise ValueError("a gust series: run_pos must be 0")
     noisy = bool(noise_std) and bool(noise_scale)
     jitter = _check_jitter(jitter, noisy, run)
     _check_draws(draws, noisy)
@@ -1024,7 +1162,7 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory, wind)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory, wind, gusts)
         p = int(s['run_pos'])
         if jitter or draws == 'counter':
             if p != 0:

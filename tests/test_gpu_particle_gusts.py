@@ -1,0 +1,371 @@
+"""GPU tier: gusts on the device (rr_set_particle_gusts; the GUST instantiations of k_field_particles and k_rig_particles, count passes
+included).
+
+  1. device records == the host statement (tools/particles.py expected_records(gusts=)), bit for bit, counts included: field (one
+     chunk: store pass alone; three chunks: count pass + store pass; jitter 0 and 5), rig (both stereo views with one and two chunks,
+     then view 1 alone), a rig on an arc; both draws, the mean wind on and off; under the series of the CPU tier (n = 1, a frame at
+     m = 0, frame0 = 2^31 + 3, a frame at m = n - 1);
+  2. set_particle_gusts(None) on the same context: the mean wind's records, then today's;
+  3. the kernel profile: the launch counts with a series are those without;
+  4. every RR_E_ARG, a frame outside the series, the i.i.d. model, a model change dropping the series;
+  5. RainAugment('field', draws='counter', gusts=...) == rr_pipeline_submit fed the host statement's records with the lean on; two
+     images of one batch with different frame_index lean differently;
+  6. the driver: `main.py ... --gusts 3,2` writes the files whose pixels that augmenter gives."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import helpers as h
+from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
+from test_gpu_particle_draws import H, KITTI_STEREO, W, _kitti, _set_rig
+from test_gpu_particle_field import _rh
+from test_gpu_particle_jitter import _same
+from test_gpu_particle_trajectory import MONO, _arc_poses, _set
+from test_particle_gusts_host import HZ, gust_cases
+
+pytestmark = pytest.mark.gpu
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+trajmod = importlib.import_module('rain-rendering_amd.trajectory')
+augment = importlib.import_module('rain-rendering_amd.augment')
+imgops = importlib.import_module('rain-rendering_amd.common.imgops')
+envmod = importlib.import_module('rain-rendering_amd.common.envmap')
+
+WIND = (-7.5, 2.0)
+DRAWS = ['counter', 'stream']
+SEED = 1234 + 2 ** 40
+RR_E_ARG = -1                                             # include/rainhip.h
+
+
+def _check(rh, sims, want, what):
+    got, cnt = rh.generate_drops(sims, H, W)
+    for k in range(len(sims)):
+        assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
+        _same(got[k], want[k], '%s: frame %d' % (what, k))
+    return cnt
+
+
+# ---- 1. device == host statement -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("jitter", [0.0, 5.0])
+def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
+    opt = _kitti()
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    kw = dict(model='field', cam_hz=opt['cam_hz'])
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_model('field', kw['cam_hz'])
+        rh.set_particle_draws(draws)
+        rh.set_particle_jitter(jitter)
+        for wind in ((0.0, 0.0), WIND):
+            rh.set_particle_wind(*wind)
+            for gusts, frames in gust_cases():
+                sims = particles.field_run_sims(sims1, frames)
+                want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=wind, gusts=gusts, **kw)
+                rh.set_particle_gusts(gusts)
+                for chunks in (1, 3):
+                    rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                    _check(rh, sims, want, 'field, %d chunks, %s, jitter %g, wind %s, frames %s' % (chunks, draws, jitter, wind, frames))
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("wind", [(0.0, 0.0), WIND], ids=['calm', 'wind'])
+def test_rig_records_equal_host_statement(tmp_path, built, wind, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=KITTI_STEREO)
+    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set_rig(rh, opt)
+        rh.set_particle_draws(draws)
+        rh.set_particle_wind(*wind)
+        for gusts, inst in gust_cases():
+            sims = particles.rig_run_sims(sims1, inst, 2)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=wind, gusts=gusts, **kw)          # frame 2 i + v
+            _set_rig(rh, opt)                                     # (a model change drops the series: set it after)
+            rh.set_particle_gusts(gusts)
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                _check(rh, sims, want, 'rig, %d chunks, %s, wind %s, instants %s' % (chunks, draws, wind, inst))
+            rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+            # view 1 alone: the same bits per view
+            _set_rig(rh, opt, active=[1])
+            rh.set_particle_gusts(gusts)
+            got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
+            for i in range(len(inst)):
+                _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+    finally:
+        rh.close()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+def test_arc_records_equal_host_statement(tmp_path, built, draws):
+    """A single camera on an arc (10 m/s, 20 degrees a second): the gust is a world-frame vector like the mean wind; a jitter of 5
+    degrees on top.  A series over the arc's nine instants at m = 0, inside and at m = n - 1, and one of a single interval."""
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    rig = MONO
+    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=rig, trajectory=traj)
+    kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set(rh, rig, traj, opt, hz)
+        rh.set_particle_draws(draws)
+        rh.set_particle_jitter(5.0)
+        rh.set_particle_wind(*WIND)
+        for gusts, inst in ((particles.gust_series(8, HZ, 4.0, 2.0, seed=9), [0, 7, 3]),
+                            (particles.GustSeries(3, np.array([[0.5, -0.25], [0.81, -0.37]])), [3])):
+            sims = particles.rig_run_sims(sims1, inst, 1)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=WIND, gusts=gusts, **kw)
+            rh.set_particle_gusts(gusts)
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                _check(rh, sims, want, 'arc, %d chunks, %s, instants %s' % (chunks, draws, inst))
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+# ---- 2. off again --------------------------------------------------------------------------------------------------
+def test_gusts_off_again_on_the_same_context(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    gusts, frames = gust_cases()[1]
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    sims = particles.field_run_sims(sims1, frames)
+    kw = dict(model='field', cam_hz=opt['cam_hz'], draws='counter')
+    gusty = particles.expected_records(sims, dgrid, cdf, sc.db, wind=WIND, gusts=gusts, **kw)
+    windy = particles.expected_records(sims, dgrid, cdf, sc.db, wind=WIND, **kw)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)
+    assert gusty[0].tobytes() != windy[0].tobytes() != plain[0].tobytes()
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_model('field', kw['cam_hz'])
+        rh.set_particle_draws('counter')
+        rh.set_particle_wind(*WIND)
+        rh.set_particle_gusts(gusts)
+        _check(rh, sims, gusty, 'field with the series')
+        rh.set_particle_gusts(None)
+        _check(rh, sims, windy, 'series off: the mean wind')
+        rh.set_particle_wind(0, 0)
+        _check(rh, sims, plain, 'wind off: as before')
+        rh.set_particle_gusts(gusts)                             # and on again, over a calm mean
+        _check(rh, sims, particles.expected_records(sims, dgrid, cdf, sc.db, gusts=gusts, **kw), 'series over a calm mean')
+    finally:
+        rh.close()
+
+
+# ---- 3. launch counts ----------------------------------------------------------------------------------------------
+def test_a_series_adds_no_launch(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    gusts = particles.gust_series(4, HZ, 4.0, 2.0, seed=3)
+    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    rig_run = (particles.rig_run_sims(sims_r, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
+    sims_f, dgrid_f, cdf_f = particles.sim_frames(opt, 25, 1, seed=7, model='field')
+    field_run = (particles.field_run_sims(sims_f, [0, 1, 3]), dgrid_f, cdf_f, dict(model='field', cam_hz=opt['cam_hz']))
+    rh = _rh(sc)
+    try:
+        rh.profile(True)
+        for name, (sims, dgrid, cdf, kw) in (('k_field_particles', field_run), ('k_rig_particles', rig_run)):
+            rh.set_particle_tables(dgrid, cdf)
+            if kw['model'] == 'rig':
+                _set_rig(rh, opt)
+            else:
+                rh.set_particle_model('field', kw['cam_hz'])
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                for draws in DRAWS:
+                    rh.set_particle_draws(draws)
+                    counts = {}
+                    for on in (False, True):
+                        rh.set_particle_gusts(gusts if on else None)
+                        rh.profile_reset()
+                        rh.generate_drops(sims, H, W)
+                        stats = rh.profile_read()
+                        counts[on] = {k: v[0] for k, v in stats.items()}
+                        assert stats[name][0] >= 1, (name, draws, on, stats)
+                    assert counts[False] == counts[True], (name, chunks, draws, counts)
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+# ---- 4. refusals ---------------------------------------------------------------------------------------------------
+def test_refusals(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    G = particles.GustSeries
+    ok = np.array([[0.0, 0.0], [0.1, 0.0], [0.2, 0.1]])
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    kw = dict(model='field', cam_hz=opt['cam_hz'])
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        with pytest.raises(RuntimeError, match='gust'):          # the i.i.d. model has no time
+            rh.set_particle_gusts(G(0, ok))
+        rh.set_particle_gusts(None)                              # off is always allowed
+        rh.set_particle_model('field', kw['cam_hz'])
+        lib, hnd = rh.lib, rh.h
+        nan = np.array([[0.0, 0.0], [np.nan, 0.0]])
+        for n, frame0, disp in ((-1, 0, ok), (2 ** 20 + 1, 0, np.zeros((2 ** 20 + 2, 2))), (2, 2 ** 32 - 1, ok), (1, 0, nan),
+                                (1, 0, np.array([[0.0, 0.0], [0.0, np.inf]])), (1, 0, np.array([[1e6, 1.0], [1e6, 1.0]])),
+                                (1, 0, np.array([[0.0, 0.0], [8.0, 8.0]])), (2, 0, None)):
+            d = None if disp is None else np.ascontiguousarray(disp, np.float64)
+            rc = lib.rr_set_particle_gusts(hnd, n, frame0, None if d is None else d.ctypes.data)
+            assert rc == RR_E_ARG, (n, frame0, rc)
+        rh.set_particle_gusts(G(2 ** 32 - 2, ok))                # frame0 + n = 2^32 is allowed
+        rh.set_particle_gusts(G(0, np.array([[0.0, 0.0], [10.0, 0.0]])))     # 100 m/s itself is allowed
+        # a refusal leaves the last good series: frames 1, 2 of G(1, ok)
+        rh.set_particle_gusts(G(1, ok))
+        assert lib.rr_set_particle_gusts(hnd, 1, 0, np.ascontiguousarray(nan).ctypes.data) == RR_E_ARG
+        sims = particles.field_run_sims(sims1, [1, 2])
+        _check(rh, sims, particles.expected_records(sims, dgrid, cdf, sc.db, gusts=G(1, ok), **kw), 'after the refusals')
+        # generating: a frame outside the series, before and behind it; run_pos
+        for f in (0, 3, 2 ** 31):
+            with pytest.raises(RuntimeError, match='outside the gust series'):
+                rh.generate_drops(particles.field_run_sims(sims1, [1, f]), H, W)
+        runp = sims.copy()
+        runp['run_pos'] = 1
+        with pytest.raises(RuntimeError, match='run_pos'):
+            rh.generate_drops(runp, H, W)
+        # the model: i.i.d. is refused while a series is set and leaves it; a new field / rig model drops it
+        with pytest.raises(RuntimeError, match='gust'):
+            rh.set_particle_model('iid')
+        _check(rh, sims, particles.expected_records(sims, dgrid, cdf, sc.db, gusts=G(1, ok), **kw), 'after the refused model')
+        rh.set_particle_model('field', kw['cam_hz'])
+        plain = particles.expected_records(particles.field_run_sims(sims1, [1, 7]), dgrid, cdf, sc.db, **kw)
+        _check(rh, particles.field_run_sims(sims1, [1, 7]), plain, 'the model set again: no series')     # (frame 7 lies outside the old series)
+        rh.set_particle_model('iid')                             # and with no series the i.i.d. model is allowed again
+    finally:
+        rh.close()
+
+
+# ---- 5. RainAugment end to end -------------------------------------------------------------------------------------
+def _mean_slant(rec):
+    nb = rec['type'] != 0
+    return float((rec['x1'] - rec['x0'])[nb].astype(np.float64).sum() / (rec['y1'] - rec['y0'])[nb].astype(np.float64).sum())
+
+
+def test_rain_augment_renders_the_host_statements_records(built, streaks_db):
+    """RainAugment(particle_model='field', draws='counter', gusts=...), B = 2, bytes, KITTI, 25 mm/hr, against rr_pipeline_submit fed
+    expected_records(gusts=) as host tables with RR_OPT_STREAK_LEAN on: image bytes and mask equal.  The series blows +6 m/s over frame
+    4's interval and -6 m/s over frame 5's: the two images of the batch lean opposite ways."""
+    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='field', draws='counter')
+    disp = np.zeros((9, 2))
+    disp[5, 0] = 0.6                                             # G[4] = 0, G[5] = 0.6, G[6] = 0 at 10 Hz
+    gusts = particles.GustSeries(0, disp)
+    aug = augment.RainAugment('kitti', gusts=gusts, **kw)
+    calm = None
+    try:
+        assert aug.frame_size() == (H, W) and aug.lean is True
+        bgr, depth = _scene(2, H, W, seed=40)
+        idx = [4, 5]
+        p = aug.plan(25, idx)
+        assert p['gusts'] is gusts and p['lean'] is True and p['wind'] == (0.0, 0.0)
+        want = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws='counter',
+                                          gusts=gusts)
+        s4, s5 = _mean_slant(want[0]), _mean_slant(want[1])
+        print('mean dx / dy: frame 4 %+.3f, frame 5 %+.3f' % (s4, s5))
+        assert s4 > 0.3 and s5 < -0.3
+        rainy, mask = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        rainy, mask = rainy.cpu().numpy(), mask.cpu().numpy()
+        rh = h.hb.RainHip(0)
+        try:
+            rh.set_streak_db(aug.db.streaks_light)
+            rh.set_camera(h.hb.make_camera(aug.focal, aug.f_number, aug.exposure))
+            rh.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            we = rh.set_envmap_geometry(H, W, *envmod.EnvironmentMapGenerator(aug.focal, W, H).device_tables(H, W))
+            rh.set_solid_angles(h.solid_angle.get_solid_angles(np.empty((H, we, 0))))
+            rh.set_option(h.hb.RR_OPT_STREAK_LEAN, 1)
+            frames = [dict(bg_u8=np.ascontiguousarray(bgr[i]), depth=np.ascontiguousarray(depth[i]), fog=tuple(p['fog'][i]), omega=None,
+                           drops=want[i]) for i in range(2)]
+            outs = [dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W))) for _ in range(2)]
+            rh.pipeline_submit(0, frames, outs)
+            while not rh.pipeline_wait(0):
+                rh.pipeline_submit(0, frames, outs)
+        finally:
+            rh.close()
+        for i in range(2):
+            assert len(want[i]) > 100
+            assert np.array_equal(rainy[i].transpose(1, 2, 0), outs[i]['image_u8']), i
+            assert np.array_equal(mask[i, 0], outs[i]['mask'].astype(np.float32)), i
+            assert outs[i]['mask'].max() > 0, i
+        # a frame outside the series; another series between batches; none: the calm augmenter's pixels
+        with pytest.raises(ValueError, match='outside the gust series'):
+            aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, [4, 8])
+        aug.set_gusts(None)
+        assert aug.lean is False
+        rainy_0, _ = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        calm = augment.RainAugment('kitti', **kw)
+        rainy_c, _ = calm(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        assert np.array_equal(rainy_0.cpu().numpy(), rainy_c.cpu().numpy()) and not np.array_equal(rainy_0.cpu().numpy(), rainy)
+        aug.set_gusts(gusts)
+        rainy_1, _ = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        assert np.array_equal(rainy_1.cpu().numpy(), rainy)
+        with pytest.raises(ValueError, match='no time'):
+            augment.RainAugment('kitti', streaks_db=streaks_db, sequence='data_object/training', gusts=gusts)
+    finally:
+        aug.close()
+        if calm is not None:
+            calm.close()
+
+
+# ---- 6. the driver -------------------------------------------------------------------------------------------------
+def test_the_driver_writes_what_the_augmenter_renders(tmp_path, built, monkeypatch):
+    """Two KITTI-sized frames: `main.py --device_particles --particle_model field --particle_draws counter --gusts 3,2` (--streak_lean
+    auto: on) writes the bytes RainAugment(particle_model='field', draws='counter', gusts=gust_series(n, 10, 3, 2, 0)) gives for the clip
+    (the series is made sequentially: its first rows do not depend on n); the run without --gusts writes other files."""
+    tmp = str(tmp_path)
+    n = 2
+    src = os.path.join(tmp, 'source')
+    h.synthetic.write_dataset(src, 'kitti', os.path.join('data_object', 'training'), n, H, W, depth_m=None)
+    db_dir = os.path.join(tmp, 'rainstreakdb')
+    h.synthetic.write_streak_db(db_dir)
+    main = importlib.import_module('rain-rendering_amd.main')
+    common = ['--dataset', 'kitti', '-k', src, '-d', src, '-r', os.path.join(tmp, 'particles'), '-sd', db_dir, '-i', '25', '--noverbose',
+              '--device_particles', '--particle_model', 'field', '--particle_draws', 'counter']
+    for bad in (['--gusts', '3,2'], ['--device_particles', '--gusts', '3,2'], ['--device_particles', '--particle_model', 'field', '--gusts', '0'],
+                ['--device_particles', '--particle_model', 'field', '--gusts', '3,0'],
+                ['--device_particles', '--particle_model', 'field', '--gusts', '3,2,1,4'],
+                ['--device_particles', '--particle_model', 'field', '--gusts', 'a']):
+        with pytest.raises(SystemExit, match='--gusts'):
+            main._derive(main._parse(['--dataset', 'kitti', '-k', src, '-i', '25'] + bad))
+    monkeypatch.setenv('RAIN_BATCH', '2')
+    gen = main.main(common + ['--gusts', '3,2', '--output', os.path.join(tmp, 'gusty')])
+    assert len(gen.stats) == n and all(s_['drops'] > 100 for s_ in gen.stats)
+    main.main(common + ['--output', os.path.join(tmp, 'calm')])
+    sub = os.path.join('kitti', 'data_object', 'training', 'rain', '25mm', 'rainy_image')
+    names = ['%06d.png' % i for i in range(n)]
+
+    def files(run):
+        return np.stack([np.array(Image.open(os.path.join(tmp, run, sub, f)))[..., :3] for f in names])
+    gusty = files('gusty')
+    assert not np.array_equal(gusty, files('calm'))
+    img_dir = os.path.join(src, 'kitti', 'data_object', 'training', 'image_2')
+    rgb = np.stack([np.array(Image.open(os.path.join(img_dir, f)).convert('RGB')) for f in names])
+    depth = np.stack([np.array(Image.open(os.path.join(img_dir, 'depth', f))).astype(np.float32) / 256. for f in names])
+    aug = augment.RainAugment('kitti', streaks_db=db_dir, sequence='data_object/training', particle_model='field', draws='counter',
+                              gusts=particles.gust_series(16, HZ, 3.0, 2.0, seed=0))
+    try:
+        rainy, mask = aug(torch.from_numpy(rgb.transpose(0, 3, 1, 2).copy()).to(DEV), torch.from_numpy(depth).to(DEV), 25, np.arange(n))
+        assert np.array_equal(rainy.cpu().numpy().transpose(0, 2, 3, 1), gusty)
+        assert all(float(mask[i].max()) > 0 for i in range(n))
+    finally:
+        aug.close()
