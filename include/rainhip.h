@@ -520,6 +520,29 @@ int rr_set_particle_wind(rr_ctx* ctx, double wx, double wz);
  * is refused likewise).  RR_E_ARG when generating: a record whose frame lies outside [frame0, frame0 + n); run_pos != 0. */
 int rr_set_particle_gusts(rr_ctx* ctx, int32_t n, uint32_t frame0, const double* disp /* (n + 1) x 2, metres */);
 
+/* Showers: a rain rate that changes over time, under RR_PARTICLES_FIELD and RR_PARTICLES_RIG (with or without a trajectory, both
+ * draw modes, with or without jitter, wind and gusts).  The slots, tables and capacities of the run are those of the series' PEAK
+ * rate; a life of a slot is kept with the probability N(D; R) / N(D; R_peak) = exp(-(Lambda(R) - Lambda(R_peak)) D) of the rate R at
+ * the life's BIRTH (Marshall-Palmer, Lambda = 4.1 R^-0.21 mm^-1): the peak's field thinned to the lower rate, in law the field at
+ * rate R, and a drop that has started to fall keeps falling.  dlam = L[0 .. n]: n + 1 doubles, L[i] = min(Lambda(rate at time index
+ * frame0 + i) - Lambda(peak), 100) mm^-1 (a rate of 0: 100), linear between samples.  The table is the caller's
+ * (tools/particles.py RateSeries.dlam; shower_series makes a series); the device looks up, interpolates and compares -- no state.
+ * With m = rr_sim_frame.frame - frame0, tau the seconds since the life began and D its diameter in mm, every step one IEEE
+ * double operation, no contraction:
+ *     sb = max(m - tau cam_hz, 0);  i = floor(sb);  Lb = L[i] + (sb - i) (L[i + 1] - L[i]);  p = det_exp(-(Lb D))
+ *     alive = unit32(w) < p            w: word 3 of the life's Philox block 1, which nothing else reads
+ * (before the series starts its first value is held).  A life that is not alive is culled as a slot outside the frustum is; under
+ * the rig model the decision is made once per slot, for every view.  L = 0 gives p = 1 exactly: a series at its peak leaves the
+ * records of no series, byte for byte.  L = 100 gives p < 2^-33, unit32's smallest value: no new drop.  Slot counts, boxes, lives,
+ * tables, positions, the pick, the jitter, wind and gusts do not depend on it.  tools/particles.py expected_records(rate_series=)
+ * states the records bit for bit.  The table is uploaded here, once; the particle kernels read it and take no further launch.
+ * Call it after rr_set_particle_model (a later rr_set_particle_model drops the series), between runs, with no call of the generator
+ * in flight.  n = 0 turns it off: the context is what it was.  One series per context.
+ * RR_E_ARG when setting: n < 0 or n > 2^20; frame0 + n > 2^32; a value that is not finite, below 0 or above 100; the model is
+ * RR_PARTICLES_IID (rr_set_particle_model to RR_PARTICLES_IID while a series is set is refused likewise).  RR_E_ARG when
+ * generating: a record whose frame lies outside [frame0, frame0 + n); run_pos != 0. */
+int rr_set_particle_rate_series(rr_ctx* ctx, int32_t n, uint32_t frame0, const double* dlam /* n + 1, mm^-1 */);
+
 /* ---------------------------------------------------------------------------------------
  * Rain on a batch of images that already lives on the GPU in a deep-learning framework's layout (PyTorch: planar RGB,
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`

@@ -48,6 +48,14 @@ DESIGN 5k).  `frame_index` then also selects the wind: a clip k0 + arange(T) swa
 every image of a batch its own slant.  A frame_index outside the series is a ValueError.  `lean=None` is on with a series too.
 `set_gusts()` takes another series between batches.
 
+`showers=RateSeries` (default None: off; 'field' and 'rig' only) is a rain rate that changes over time: mm/hr sampled at the frame
+indices frame0 .. frame0 + n (tools/particles.py RateSeries; shower_series makes one that builds, peaks and fades;
+`main.py --showers LOW,PERIOD_S[,PHASE]`).  The slots, tables and `drops_cap` are those of the series' peak and never
+change; `frame_index` then also selects the rate: a clip k0 + arange(T) shows ONE field whose drops thin out and come back -- a
+drop that has started to fall keeps falling -- and image i's fog constants are those of the rate at frame_index[i].  `intensity`
+is then None or the series' peak (anything else is a ValueError, as is None without a series), and a frame_index outside the
+series is a ValueError.  `set_showers()` takes another series between batches.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -105,7 +113,7 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None):
+                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None, showers=None):
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
@@ -144,6 +152,7 @@ class RainAugment:
         self.trajectory = self._check_trajectory(trajectory)
         self.gusts = particles._check_gusts(gusts, self.options["cam_hz"], particle_model)
         self.lean = bool(self.wind[0] or self.wind[1] or self.gusts is not None) if lean is None else lean
+        self.showers = particles._check_rate_series(showers, particle_model)
         light_db = os.path.join(streaks_db, 'env_light_database')
         self.db = DBManager(streaks_path=os.path.join(light_db, 'size32'),
                             norm_coeff_path=os.path.join(light_db, 'txt', 'normalized_env_max.txt'))
@@ -162,6 +171,8 @@ class RainAugment:
         self._geom = None                        # (H, W) whose envmap geometry and solid angles the context holds
         self._traj_set = trajectory is None      # whether the context holds the current trajectory's box and table
         self._gusts_set = gusts is None          # whether the context holds the current gust series
+        self._showers_set = showers is None      # whether the context holds the current rate series
+        self._fogs = {}                          # rate -> fog constants (a rate series: one rate per frame index)
 
     def _check_trajectory(self, trajectory):
         if trajectory is None:
@@ -187,6 +198,12 @@ class RainAugment:
             self.lean = bool(self.wind[0] or self.wind[1] or self.gusts is not None)
         self._gusts_set = False
 
+    def set_showers(self, showers):
+        """Another rate series (or None: one intensity per image again) from the next call on: between batches, with no call in
+        flight.  The slots and tables follow the series' peak."""
+        self.showers = particles._check_rate_series(showers, self.particle_model)
+        self._showers_set = False
+
     # ---- host side: what a call sends (no GPU needed) ----------------------------------------------------------------
     def frame_size(self):
         """(H, W) of the frames this dataset's simulation renders (sensor size / render_scale)."""
@@ -194,7 +211,18 @@ class RainAugment:
         return int(sims[0]['sensor_h']) // self.render_scale, int(sims[0]['sensor_w']) // self.render_scale
 
     def _first_rate(self):
+        if self.showers is not None and not self._rates:
+            return self.showers.peak
         return next(iter(self._rates)) if self._rates else 25.0
+
+    def _fog(self, rate):
+        """FogRain.constants at `rate` mm/hr (a rate series: image i's rate is the series' at frame_index[i])."""
+        rate = float(rate)
+        if rate not in self._fogs:
+            fog = add_attenuation.FogRain(rain_intensity=rate, focal=self.focal, f_number=self.f_number, angle=90,
+                                          exposure=self.exposure, camera_gain=self.camera_gain).constants()
+            self._fogs[rate] = tuple(float(v) for v in fog)
+        return self._fogs[rate]
 
     def _rate(self, rate):
         """The driver's run set-up at one intensity (common/generator.py: sim_frames at seed `seed`, FogRain.constants)."""
@@ -223,13 +251,21 @@ class RainAugment:
     def plan(self, intensity, frame_index, B=None):
         """What a call sends for these intensities and frame indices: dict(sims = SIM_FRAME_DTYPE records, d_grid, cdf = the
         union of the intensities' diameter tables the records index, fog = [B, 4] pre-pass constants, drops_cap, key, particle_model,
-        cam_hz, draws, jitter, wind, gusts: what expected_records needs; lean: the renderer's RR_OPT_STREAK_LEAN to state the call's drop tables).  Under the
+        cam_hz, draws, jitter, wind, gusts, showers (expected_records' rate_series): what expected_records needs; lean: the renderer's RR_OPT_STREAK_LEAN to state the call's drop tables).  Under the
         rig model B counts instants: sims and fog hold V = len(views) consecutive entries per instant (view views[i % V] of
         instant i // V), plus views, rig_views and rig_box (what rr_set_particle_rig gets)."""
         if B is None:
             B = len(np.atleast_1d(np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index)))
-        rates = [float(r) for r in _as_list(intensity, B, 'intensity', 'rate')]
         idx = [int(f) for f in _as_list(frame_index, B, 'frame_index', 'index')]
+        if self.showers is not None:                         # the series says the rate; the slots and tables are its peak's
+            peak = self.showers.peak
+            if intensity is not None and any(float(r) != peak for r in _as_list(intensity, B, 'intensity', 'rate')):
+                raise ValueError("intensity %r: with showers= the rate comes from the series; pass None or its peak %r" % (intensity, peak))
+            rates = [peak] * B
+        elif intensity is None:
+            raise ValueError("intensity=None needs showers= (a rate series)")
+        else:
+            rates = [float(r) for r in _as_list(intensity, B, 'intensity', 'rate')]
         if any(not (r > 0) or not np.isfinite(r) for r in rates):
             raise ValueError("intensity must be positive (mm/hr), got %r" % (rates,))
         if any(f < 0 or f >= 2 ** 32 for f in idx):
@@ -237,6 +273,9 @@ class RainAugment:
         if self.gusts is not None and not self.gusts.covers(idx).all():
             raise ValueError("frame_index %r is outside the gust series' frames %d .. %d" % (
                 [f for f in idx if not self.gusts.covers(f)], self.gusts.frame0, self.gusts.frame0 + self.gusts.n - 1))
+        if self.showers is not None and not self.showers.covers(idx).all():
+            raise ValueError("frame_index %r is outside the rate series' frames %d .. %d" % (
+                [f for f in idx if not self.showers.covers(f)], self.showers.frame0, self.showers.frame0 + self.showers.n - 1))
         key, (dgrid, cdf, offs) = self._union(rates)
         sims = np.zeros(B, hip_backend.SIM_FRAME_DTYPE)
         fog = np.zeros((B, 4), np.float64)
@@ -249,14 +288,14 @@ class RainAugment:
                 sims[i]['frame'] = f
             sims[i]['table'] = int(rs[f % self.n_sim]['table']) + offs[r]
             sims[i]['run_pos'] = 0
-            fog[i] = fc
+            fog[i] = fc if self.showers is None else self._fog(self.showers.rate_at(f))
         for r in key:
             n_max = max(n_max, int(self._rate(r)[0]['n_particles'].max()))
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
         out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter,
-                   wind=self.wind, lean=self.lean, gusts=self.gusts)
+                   wind=self.wind, lean=self.lean, gusts=self.gusts, showers=self.showers)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
             V = len(self.views)
             box_rig = self.rig if self.trajectory is None else self.trajectory.bind(self.rig)
@@ -325,6 +364,9 @@ class RainAugment:
             self._hip.set_particle_gusts(self.gusts)
             self._hip.set_option(hip_backend.RR_OPT_STREAK_LEAN, int(self.lean))
             self._gusts_set = True
+        if not self._showers_set:                # (likewise)
+            self._hip.set_particle_rate_series(self.showers)
+            self._showers_set = True
         if self._tables_key != key:              # (the previous call has finished: no kernel reads the old tables)
             self._hip.set_particle_tables(dgrid, cdf)
             self._tables_key = key

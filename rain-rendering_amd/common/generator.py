@@ -128,6 +128,21 @@ class Generator:
                 raise ValueError("--gusts %r: expected 0 < SIGMA <= 20 m/s, TAU > 0 seconds, SEED in [0, 2^32)" % (self.gusts,))
             if not self.device_particles or self.particle_model not in ('field', 'rig'):
                 raise ValueError("--gusts needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
+        # --showers LOW,PERIOD_S[,PHASE] (main.py _wind_and_lean has parsed it into (low, period_s, phase)): a rain rate that changes over
+        # time, as a series over the run's frame indices whose peak is the run's intensity (tools/particles.shower_series)
+        self.showers = getattr(args, 'showers', None)
+        if self.showers is not None:
+            try:
+                low, period_s, phase = self.showers
+                self.showers = (float(low), float(period_s), float(phase))
+            except (TypeError, ValueError):
+                raise ValueError("--showers %r: expected (LOW, PERIOD_S, PHASE)" % (self.showers,))
+            if not (np.isfinite(self.showers[0]) and self.showers[0] >= 0) or not (np.isfinite(self.showers[1]) and self.showers[1] > 0) or \
+                    not np.isfinite(self.showers[2]):
+                raise ValueError("--showers %r: expected LOW >= 0 mm/hr, PERIOD_S > 0 seconds, PHASE finite" % (self.showers,))
+            if not self.device_particles or self.particle_model not in ('field', 'rig'):
+                raise ValueError("--showers needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
+        self._shower_series = None                               # the current run's RateSeries (run())
         lean = getattr(args, 'lean', None)                       # main.py _wind_and_lean has resolved 'auto'
         self.streak_lean = (any(self.wind) or self.gusts is not None) if lean is None else bool(lean)
         if self.streak_jitter and not self.device_particles:
@@ -500,6 +515,14 @@ class Generator:
                         hip.set_particle_gusts(particles.gust_series(max(len(files), n_sim) + 1, opts["cam_hz"], *self.gusts))
                     else:
                         hip.set_particle_gusts(None)
+                    self._shower_series = None
+                    if self.showers is not None:                 # likewise; the tables and slots above are the peak's: the run's intensity
+                        low, period_s, phase = self.showers
+                        self._shower_series = particles.shower_series(max(len(files), n_sim) + 1, opts["cam_hz"], float(fallrate), low,
+                                                                      period_s, phase=phase)
+                        self._shower_fog = {}                    # rate -> fog constants: each frame's fog comes from its own rate
+                        self._shower_fog_params = fog_params
+                    hip.set_particle_rate_series(self._shower_series)
                     frame_render_dict = []
                 else:
                     self.db.load_streaks_from_xml(self.dataset, self.settings, [imW, imH], use_pickle=False, verbose=self.verbose)
@@ -536,6 +559,13 @@ class Generator:
                 if frames_exist_nb > 0:
                     print("Skipped {}/{} already existing renderings".format(frames_exist_nb, len(idx)))
             print("\n\nEnd of the simulation")
+
+    def _shower_fog_of(self, f_idx):
+        """--showers: FogRain.constants at the rate of time index f_idx."""
+        rate = self._shower_series.rate_at(f_idx)
+        if rate not in self._shower_fog:
+            self._shower_fog[rate] = tuple(float(v) for v in add_attenuation.FogRain(**dict(self._shower_fog_params, rain_intensity=rate)).constants())
+        return self._shower_fog[rate]
 
     def _cap_batch(self, B, imH, imW, frame_render_dict, sims):
         """Frames per library call, bounded by the page-locked memory a rank may hold: three slots of B frames, each frame
@@ -796,6 +826,8 @@ class Generator:
                         if self.particle_model in ('field', 'rig'):    # the field's time is the frame's own index (it does not wrap)
                             sl.sim_recs[k]['frame'] = f_idx
                         sl.sim_recs[k]['run_pos'] = items[k]['run_pos']    # angular noise: its entry in the run (0: none)
+                        if getattr(self, '_shower_series', None) is not None:    # --showers: the frame's fog is that of its own rate
+                            sl.prep.set_fog(k, self._shower_fog_of(f_idx))
                     else:
                         sl.prep.set_drop_count(k, nd)
                 sl.t_submit = time.time()

@@ -4741,6 +4741,41 @@ __device__ inline void gust_frame_of(const GustArgs<GUST>& ga, uint32_t mi, rrsi
   }
 }
 
+// RATE (rr_set_particle_rate_series; a parameter of k_field_particles and k_rig_particles, count passes included -- the cull reads
+// the decision; orthogonal to WIND, GUST, TRAJ, CTR, JIT): the series' table as n rows (L[i], L[i + 1]) of doubles, uploaded once
+// by the setter and never written by a kernel.  A lane needs the one row around its life's birth: a 16-byte vector load that
+// rrsim::slot_fall issues before the life's Philox blocks.  m = frame - frame0 is wave-uniform and the only thing a frame adds.
+// RATE = false is the kernel as it was: an empty struct behind every other argument.
+template <bool RATE>
+struct RateArgs {};
+template <>
+struct RateArgs<true> {
+  const double* tab;                          // [n][2] mm^-1
+  int32_t n;                                  // intervals
+  uint32_t frame0;                            // the time index of row 0
+};
+// m of the workgroup's frame, on the scalar side; the comparison keeps an index the host did not check inside the table
+template <bool RATE>
+__device__ inline uint32_t rate_index(const RateArgs<RATE>& ra, uint32_t frame) {
+  if constexpr (RATE) {
+    const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(frame - ra.frame0));
+    return d < (uint32_t)ra.n ? d : (uint32_t)(ra.n - 1);
+  } else {
+    return 0u;
+  }
+}
+// The frame's part of the series for one round of slots: formed INSIDE the loop over the rounds from the opaque index, like
+// gust_frame_of, so that the pointer, n and m hold no scalar register across the rest of the round.
+template <bool RATE>
+__device__ inline void rate_frame_of(const RateArgs<RATE>& ra, uint32_t mi, rrsim::RateFrame& r) {
+  if constexpr (RATE) {
+    asm volatile("" : "+s"(mi));
+    r.tab = reinterpret_cast<const rrsim::RateRow*>(ra.tab);
+    r.n = ra.n;
+    r.m = (double)mi;
+  }
+}
+
 // ---- the tail the three particle kernels share: finish the record, compact the kept ones, store whole lines.  No helper holds a
 // barrier: where a kernel synchronises, and why, is written in its own body. ----
 // Finish the record of a candidate that reached derive_drop: the first texture of its ratio bucket, CTR: plus the drop's pick,
@@ -4835,11 +4870,14 @@ __global__ __launch_bounds__(512) void k_particles(const rr_sim_frame* sims, int
 // pass then starts chunk c behind the records of chunks 0 .. c - 1 and makes its records once more.  Making the records
 // twice costs less than leaving most of the chip idle when the batch has few frames; with one chunk per frame (large
 // batches fill the chip by themselves) there is no count pass.
-template <bool COUNT, bool CTR, bool JIT, bool WIND = false, bool GUST = false>
-__global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
+// RATE: the store passes need the bound that LDS sets anyway (two workgroups per CU: four waves per SIMD, 128 VGPRs) spelled out:
+// without it the compiler takes 131 to 153 VGPRs and a workgroup no longer finds room beside another.  RATE = false keeps the
+// attribute's default (one workgroup) and the code it had.
+template <bool COUNT, bool CTR, bool JIT, bool WIND = false, bool GUST = false, bool RATE = false>
+__global__ __launch_bounds__(512, RATE ? 4 : 1) void k_field_particles(const rr_sim_frame* sims, double cam_hz, int H, int W, const double* dgrid,
                                                           const double* cdf_tabs, int n_grid, const double* ratio_db, rr_drop* out, int cap,
                                                           int32_t* n_out, int32_t* chunk_cnt, int chunk_slots, double jitter_deg,
-                                                          const WindArgs<WIND> wa, const GustArgs<GUST> ga) {
+                                                          const WindArgs<WIND> wa, const GustArgs<GUST> ga, const RateArgs<RATE> ra) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   static_assert(WIND || !GUST, "the gust path forms the mean-wind additions");
   const int f = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -4861,19 +4899,23 @@ __global__ __launch_bounds__(512) void k_field_particles(const rr_sim_frame* sim
   for (int k = 0; k < 4; k++) rdb[k] = ratio_db[k];
   const int first = imin(c * chunk_slots, sf.n_particles), last = imin(first + chunk_slots, sf.n_particles);
   const uint32_t gmi = gust_index(ga, sf.frame);
+  const uint32_t rmi = rate_index(ra, sf.frame);
   int base_out = s_base;
   for (int base = first; base < last; base += 512) {
     const int j = base + t;
     rrsim::GustFrame gfr;
     gust_frame_of(ga, gmi, gfr);
+    rrsim::RateFrame rfr;
+    rate_frame_of(ra, rmi, rfr);
     bool keep = false;
     rr_drop d;
     if (j < last) {
       rrsim::Particle p;
       double life;
       uint32_t pw = 0;
-      if (rrsim::make_field_particle<WIND, GUST>(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr, wind_x(wa), wind_z(wa),
-                                                 GUST ? &gfr : nullptr)) {
+      // RATE: a life the series rejects is outside: it skips derive_drop, and a wave of rejected lives the rest of its round
+      if (rrsim::make_field_particle<WIND, GUST, RATE>(sf, cam_hz, dgrid, cdf, n_grid, (uint32_t)j, p, life, CTR ? &pw : nullptr, wind_x(wa),
+                                                       wind_z(wa), GUST ? &gfr : nullptr, RATE ? &rfr : nullptr)) {
         double ratio;
         keep = rrsim::derive_drop(p, sf.render_scale, W, H, d, ratio);
         finish_record<CTR, JIT>(d, keep, ratio, rdb, rrsim::texture_pick(pw), jitter_deg, [&] { return rrsim::life_jitter(sf, (uint32_t)j, life); });
@@ -4932,12 +4974,12 @@ struct TrajArgs<true> {
   int32_t active[RR_MAX_VIEWS];               // the rig's number of the batch's view a
   int32_t n_views;
 };
-template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false, bool WIND = false, bool GUST = false>
+template <bool COUNT, bool CTR, bool JIT, bool TRAJ = false, bool WIND = false, bool GUST = false, bool RATE = false>
 __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* sims, double cam_hz, const RigViews rv, int H, int W,
                                                         const double* dgrid, const double* cdf_tabs, int n_grid, const double* ratio_db,
                                                         rr_drop* out, int cap, int32_t* n_out, int32_t* chunk_cnt, int chunk_slots,
                                                         double jitter_deg, const TrajArgs<TRAJ> tj, const WindArgs<WIND> wa,
-                                                        const GustArgs<GUST> ga) {
+                                                        const GustArgs<GUST> ga, const RateArgs<RATE> ra) {
   static_assert(!(COUNT && JIT), "the count does not depend on the jitter: the count pass exists once");
   static_assert(WIND || !GUST, "the gust path forms the mean-wind additions");
   const int inst = blockIdx.y, c = blockIdx.x, nchunk = gridDim.x, t = threadIdx.x, lane = t & 63;
@@ -4965,14 +5007,22 @@ __global__ __launch_bounds__(512, 4) void k_rig_particles(const rr_sim_frame* si
   int row = 0;
   if constexpr (TRAJ) row = tj.rows[inst];
   const uint32_t gmi = gust_index(ga, sf.frame);
+  const uint32_t rmi = rate_index(ra, sf.frame);
   int step = 0;
   for (int base = first; base < last; base += 512) {
     const int j = base + t;
-    const bool valid = j < last;
+    bool valid = j < last;
     rrsim::GustFrame gfr;
     gust_frame_of(ga, gmi, gfr);
+    rrsim::RateFrame rfr;
+    rate_frame_of(ra, rmi, rfr);
     rrsim::RigSlot q;
-    if (valid) rrsim::make_rig_slot<WIND, GUST>(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q, wind_x(wa), wind_z(wa), GUST ? &gfr : nullptr);
+    if (valid) {
+      // RATE: the slot's life is decided once, here; a rejected slot is invalid for every view (the view steps keep their barriers)
+      const bool alive = rrsim::make_rig_slot<WIND, GUST, RATE>(sf, cam_hz, rv.box, dgrid, cdf, n_grid, (uint32_t)j, q, wind_x(wa), wind_z(wa),
+                                                                GUST ? &gfr : nullptr, RATE ? &rfr : nullptr);
+      if constexpr (RATE) valid = alive;
+    }
     // CTR: the slot's pick (0 .. 9) is live across the view loop, where the stream kernel has no register to spare.  It
     // takes the place of z_max, which every view step forms again from the diameter (the same expression as make_rig_slot's:
     // the same bits); the empty asm keeps the compiler from hoisting that back out of the loop.
@@ -5369,6 +5419,9 @@ struct rr_ctx {
   int32_t gust_n = 0;                     // rr_set_particle_gusts: intervals of the series; 0: none
   uint32_t gust_frame0 = 0;
   double* d_gust = nullptr;               // [gust_n + 1][2] metres
+  int32_t rate_n = 0;                     // rr_set_particle_rate_series: intervals of the series; 0: none
+  uint32_t rate_frame0 = 0;
+  double* d_rate = nullptr;               // [rate_n][2] mm^-1: rows (L[i], L[i + 1])
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
   int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
@@ -6365,6 +6418,21 @@ void with_air(const rr_ctx* ctx, F fn) {
   }
 }
 
+// fn(RATE, RateArgs<RATE>) for the field and rig kernels: with a rate series (rr_set_particle_rate_series) the kernels that thin
+// the lives; without one the kernels as they were
+template <class F>
+void with_rate(const rr_ctx* ctx, F fn) {
+  if (ctx->rate_n > 0) {
+    RateArgs<true> ra;
+    ra.tab = ctx->d_rate;
+    ra.n = ctx->rate_n;
+    ra.frame0 = ctx->rate_frame0;
+    fn(std::true_type{}, ra);
+  } else {
+    fn(std::false_type{}, RateArgs<false>{});
+  }
+}
+
 // The frames of a call with angular noise (run_pos >= 1): plan, per simulated frame, the steps from its held state (or its
 // pristine streaks) to each of its frames -- in run order, one chain per simulated frame -- and enqueue them (k_noise_chains).
 // The plan is made here, in call order, so the held states follow the order of the calls whatever the streams.
@@ -6564,6 +6632,21 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
     }
   }
+  if (ctx->rate_n > 0) {                                       // (likewise)
+    for (int f = 0; f < n; f++) {
+      const int64_t m = (int64_t)sims[f].frame - (int64_t)ctx->rate_frame0;
+      if (m < 0 || m >= ctx->rate_n) {
+        ctx->err = "rr_sim_frame.frame " + std::to_string(sims[f].frame) + " (frame " + std::to_string(f) + ") is outside the rate series' frames " +
+                   std::to_string(ctx->rate_frame0) + " .. " + std::to_string((int64_t)ctx->rate_frame0 + ctx->rate_n - 1) +
+                   " (rr_set_particle_rate_series)";
+        return RR_E_ARG;
+      }
+      if (sims[f].run_pos != 0) {
+        ctx->err = "rr_sim_frame.run_pos " + std::to_string(sims[f].run_pos) + " (frame " + std::to_string(f) + "): run_pos must be 0 under a rate series";
+        return RR_E_ARG;
+      }
+    }
+  }
   const bool ctr = ctx->particle_draws == RR_DRAWS_COUNTER;
   const bool jit = ctx->jitter_deg != 0.0;
   int n_noisy = 0;
@@ -6646,8 +6729,9 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       }
       memcpy(rv.box, ctx->rig_box, sizeof rv.box);
       ProfScope ps(ctx, s, "k_rig_particles");
-      auto passes = [&](auto with_traj, auto with_wnd, auto wa, auto with_gst, auto ga) {   // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
+      auto passes = [&](auto with_traj, auto with_wnd, auto wa, auto with_gst, auto ga, auto with_rt, auto ra) {   // TRAJ: the same passes, the poses from the table (rv.R, rv.c unread)
         constexpr bool TRAJ = decltype(with_traj)::value, WIND = decltype(with_wnd)::value, GUST = decltype(with_gst)::value;
+        constexpr bool RATE = decltype(with_rt)::value;
         TrajArgs<TRAJ> tj;
         if constexpr (TRAJ) {
           tj.poses = ctx->d_traj;
@@ -6657,25 +6741,29 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
         }
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa, ga);
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa, ga, ra);
         };
-        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND, GUST>);   // (a count depends neither on the draws nor on the jitter)
-        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND, GUST>); });
+        if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND, GUST, RATE>);   // (a count depends neither on the draws nor on the jitter)
+        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND, GUST, RATE>); });
       };
       with_air(ctx, [&](auto wnd, auto wa, auto gst, auto ga) {
-        if (traj) passes(std::true_type{}, wnd, wa, gst, ga);
-        else passes(std::false_type{}, wnd, wa, gst, ga);
+        with_rate(ctx, [&](auto rt, auto ra) {
+          if (traj) passes(std::true_type{}, wnd, wa, gst, ga, rt, ra);
+          else passes(std::false_type{}, wnd, wa, gst, ga, rt, ra);
+        });
       });
     } else {
       ProfScope ps(ctx, s, "k_field_particles");
       with_air(ctx, [&](auto wnd, auto wa, auto gst, auto ga) {
-        constexpr bool WIND = decltype(wnd)::value, GUST = decltype(gst)::value;
-        auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa, ga);
-        };
-        if (chunks > 1) launch(k_field_particles<true, false, false, WIND, GUST>);
-        with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND, GUST>); });
+        with_rate(ctx, [&](auto rt, auto ra) {
+          constexpr bool WIND = decltype(wnd)::value, GUST = decltype(gst)::value, RATE = decltype(rt)::value;
+          auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                               ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa, ga, ra);
+          };
+          if (chunks > 1) launch(k_field_particles<true, false, false, WIND, GUST, RATE>);
+          with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND, GUST, RATE>); });
+        });
       });
     }
     if (!ctr) {
@@ -6839,6 +6927,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_sims);
   hipFree(ctx->d_traj);
   hipFree(ctx->d_gust);
+  hipFree(ctx->d_rate);
   hipFree(ctx->d_gen_drops);
   hipFree(ctx->d_gen_counts);
   hipFree(ctx->d_field_cnt);
@@ -7342,7 +7431,12 @@ int rr_set_particle_model(rr_ctx* ctx, int32_t model, double cam_hz) {
     ctx->err = "rr_set_particle_model: a gust series is set and the i.i.d. model has no time; turn it off first (rr_set_particle_gusts with n 0)";
     return RR_E_ARG;
   }
+  if (ctx->rate_n > 0 && model == RR_PARTICLES_IID) {
+    ctx->err = "rr_set_particle_model: a rate series is set and the i.i.d. model has no time; turn it off first (rr_set_particle_rate_series with n 0)";
+    return RR_E_ARG;
+  }
   ctx->gust_n = 0;                                            // a series is checked against cam_hz: a new model drops it
+  ctx->rate_n = 0;                                            // (a rate series goes with the model it was set under)
   ctx->particle_model = model;
   ctx->cam_hz = model != RR_PARTICLES_IID ? cam_hz : 0.0;
   return RR_OK;
@@ -7442,6 +7536,50 @@ int rr_set_particle_gusts(rr_ctx* ctx, int32_t n, uint32_t frame0, const double*
   HIPCHK(hipMemcpy(ctx->d_gust, disp, sizeof(double) * 2 * ((size_t)n + 1), hipMemcpyHostToDevice));
   ctx->gust_n = n;
   ctx->gust_frame0 = frame0;
+  return RR_OK;
+}
+
+int rr_set_particle_rate_series(rr_ctx* ctx, int32_t n, uint32_t frame0, const double* dlam) {
+  if (!ctx) return RR_E_ARG;
+  if (n < 0 || n > (1 << 20)) {
+    ctx->err = "rr_set_particle_rate_series: n must be 0 .. 2^20, got " + std::to_string(n);
+    return RR_E_ARG;
+  }
+  if (n == 0) {
+    ctx->rate_n = 0;
+    return RR_OK;
+  }
+  if (ctx->particle_model != RR_PARTICLES_FIELD && ctx->particle_model != RR_PARTICLES_RIG) {
+    ctx->err = "rr_set_particle_rate_series: a rate series needs the field or rig model (rr_set_particle_model first): the i.i.d. model has no time";
+    return RR_E_ARG;
+  }
+  if (!dlam) {
+    ctx->err = "rr_set_particle_rate_series: dlam must be given";
+    return RR_E_ARG;
+  }
+  if ((uint64_t)frame0 + (uint64_t)n > (1ull << 32)) {
+    ctx->err = "rr_set_particle_rate_series: frame0 + n is beyond 2^32";
+    return RR_E_ARG;
+  }
+  for (int32_t i = 0; i <= n; i++) {
+    if (!std::isfinite(dlam[i]) || dlam[i] < 0.0 || dlam[i] > 100.0) {
+      ctx->err = "rr_set_particle_rate_series: dlam[" + std::to_string(i) + "] must be a finite number in 0 .. 100 mm^-1";
+      return RR_E_ARG;
+    }
+  }
+  std::vector<double> rows(2 * (size_t)n);                   // (L[i], L[i + 1]): what a lane reads with one 16-byte load
+  for (int32_t i = 0; i < n; i++) {
+    rows[2 * (size_t)i] = dlam[i];
+    rows[2 * (size_t)i + 1] = dlam[i + 1];
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipDeviceSynchronize());                            // (between runs: nothing of the context is in flight)
+  ctx->rate_n = 0;
+  int rc;
+  if ((rc = dev_alloc(ctx, ctx->d_rate, rows.size()))) return rc;
+  HIPCHK(hipMemcpy(ctx->d_rate, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+  ctx->rate_n = n;
+  ctx->rate_frame0 = frame0;
   return RR_OK;
 }
 

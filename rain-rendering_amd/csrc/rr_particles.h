@@ -206,15 +206,60 @@ RR_HD void gust_terms(const GustFrame& gf, double cam_hz, const GustBirth& gb, d
   ge[1] = (gf.gm1.z - gf.gm.z) * cam_hz;
 }
 
+// ---- SHOWERS (rr_set_particle_rate_series, tools/particles.py rate_series=): a rain rate that changes over time, field and rig ----
+// Slots and tables are drawn once for the series' PEAK rate; a life is kept with the probability N(D; R) / N(D; R_peak) =
+// exp(-(Lambda(R) - Lambda(R_peak)) D) of the rate R at the life's BIRTH: Marshall-Palmer thinned to the lower rate, and a drop
+// that has started to fall keeps falling.  The host makes the table L[0 .. n] = min(Lambda(rate[i]) - Lambda(peak), 100) mm^-1
+// (row i at time index frame0 + i, linear in between) and lays it out as n rows (L[i], L[i + 1]): 16 bytes, one load per lane.
+// With m = frame - frame0 (0 <= m < n, the host's check), every step one IEEE double operation:
+//   sb = max(m - tau cam_hz, 0);  i = floor(sb);  Lb = L[i] + (sb - i) (L[i + 1] - L[i]);  p = det_exp(-(Lb D))
+//   alive = unit32(b[3]) < p                         b[3]: word 3 of the life's block 1, which nothing else reads
+// (before the series starts its first value is held).  Lb = 0 gives p = 1.0 exactly and every life alive: a series at its peak
+// leaves the records of no series.  Lb = 100 gives p <= 1.9e-22 < unit32's smallest value: no new drop.  A life that is not alive
+// is culled like a slot outside the frustum.  RATE = false is every function as it was: no RateFrame is read.
+struct alignas(16) RateRow { double l0, l1; };  // (L[i], L[i + 1]): 16 bytes, one load
+struct RateFrame {                // what a frame's generators get of the series: wave-uniform
+  const RateRow* tab;             // rows 0 .. n - 1; never written by a kernel
+  int32_t n;                      // intervals
+  double m;                       // frame - frame0: an exact integer, 0 <= m < n
+};
+RR_HD RateFrame rate_frame(const RateRow* tab, int32_t n, uint32_t frame0, uint32_t frame) {
+  RateFrame r;
+  r.tab = tab;
+  r.n = n;
+  r.m = (double)(frame - frame0);
+  return r;
+}
+struct RateBirth {                // the row around a life's birth and the fraction inside it: per lane
+  RateRow r;
+  double fr;
+};
+// the look-up: issued as soon as tau is known, before the life's Philox blocks, so that those cover its latency.  The index is an
+// exact integer in 0 .. m <= n - 1; the comparison keeps any other value (a NaN from settings nobody checked) inside the table.
+RR_HD void rate_birth(const RateFrame& rf, double cam_hz, double tau, RateBirth& rb) {
+  const double back = tau * cam_hz;
+  const double sb = rr::dmax(rf.m - back, 0.0);
+  const double i = floor(sb);
+  const int32_t ii = i < (double)rf.n ? (int32_t)i : rf.n - 1;
+  rb.fr = sb - i;
+  rb.r = rf.tab[ii];
+}
+// whether the life is kept: D in mm, w = word 3 of the life's block 1
+RR_HD bool rate_alive(const RateBirth& rb, double D, uint32_t w) {
+  const double Lb = rb.r.l0 + rb.fr * (rb.r.l1 - rb.r.l0);
+  return unit32(w) < det_exp(-(Lb * D));
+}
+
 struct SlotFall {                 // where slot j is in its fall through a box of height wy at time index sf.frame
   double v;                       // terminal velocity, m/s
   double life, age, tau;          // completed falls g, the fraction of the current one, seconds since it began
   double wind;                    // the life's wind (block 2)
-  uint32_t b[4];                  // the life's block 1: lateral start, start depth, the texture pick's word
+  uint32_t b[4];                  // the life's block 1: lateral start, start depth, the texture pick's word, RATE: the acceptance deviate
+  bool alive;                     // RATE: whether the rate series keeps the life (true without RATE: nothing reads it)
 };
-template <bool GUST = false>
+template <bool GUST = false, bool RATE = false>
 RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, double D, double wy, double phase, const GustFrame* gf = nullptr,
-                         GustBirth* gb = nullptr) {
+                         GustBirth* gb = nullptr, const RateFrame* rf = nullptr) {
   SlotFall f;
   f.v = terminal_velocity(D);
   const double T = wy / f.v;
@@ -224,20 +269,27 @@ RR_HD SlotFall slot_fall(const rr_sim_frame& sf, double cam_hz, uint32_t j, doub
   f.age = s - f.life;
   f.tau = f.age * T;
   if constexpr (GUST) gust_birth(*gf, cam_hz, f.tau, *gb);
+  RateBirth rb;
+  if constexpr (RATE) rate_birth(*rf, cam_hz, f.tau, rb);
   uint32_t c[4];
   life_counter(j, f.life, 1u, f.b);
-  life_counter(j, f.life, 2u, c);
   philox4x32_10(f.b, sf.key0, sf.key1);
+  // RATE: decided as soon as block 1 is there -- it covers the look-up's latency; the row, the fraction and D are dead after it
+  if constexpr (RATE) f.alive = rate_alive(rb, D, f.b[3]); else f.alive = true;
+  life_counter(j, f.life, 2u, c);
   philox4x32_10(c, sf.key0, sf.key1);
   f.wind = block_wind(c, sf.wind_sigma);
   return f;
 }
 
 // Returns whether the particle is inside the frustum; `life` = g; *pick_word = word 2 of the life's block 1 (texture_pick).
-template <bool WIND = false, bool GUST = false>
+// RATE: a life the rate series rejects is outside: one bit joins the cull, so that a kernel skips derive_drop for it as for a slot
+// outside the frustum.  (No return before the position: in k_field_particles' store passes such a branch cost 32 to 116 bytes of
+// scratch per lane at four waves per SIMD)
+template <bool WIND = false, bool GUST = false, bool RATE = false>
 RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const double* dgrid, const double* cdf, int n_grid, uint32_t j,
                                Particle& p, double& life, uint32_t* pick_word = nullptr, double wind_x = 0.0, double wind_z = 0.0,
-                               const GustFrame* gf = nullptr) {
+                               const GustFrame* gf = nullptr, const RateFrame* rf = nullptr) {
   static_assert(WIND || !GUST, "the gust path forms the mean-wind additions: GUST needs WIND");
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double W = (double)sf.sensor_w, H = (double)sf.sensor_h;
@@ -245,7 +297,7 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   const double bx = hx * s.z_max, by = hy * s.z_max;
   const double wx = 2.0 * bx, wy = 2.0 * by;
   GustBirth gb;
-  const SlotFall f = slot_fall<GUST>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb);
+  const SlotFall f = slot_fall<GUST, RATE>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb, rf);
   double vx = f.wind, vz = sf.speed_mps;
   if constexpr (WIND) { vx = f.wind + wind_x; vz = sf.speed_mps + wind_z; }
   double qx, qz;                                            // box coordinates in units of the box: wrapped into [0, 1)
@@ -266,7 +318,8 @@ RR_HD bool make_field_particle(const rr_sim_frame& sf, double cam_hz, const doub
   const double Y = by - f.age * wy;
   const double zr = fz * s.z_max;                           // depth in the box
   const double ax = hx * zr, ay = hy * zr;
-  const bool inside = -ax <= X && X <= ax && -ay <= Y && Y <= ay;
+  bool inside = -ax <= X && X <= ax && -ay <= Y && Y <= ay;
+  if constexpr (RATE) inside = inside && f.alive;
   const double depth = rr::dmax(zr, 0.05);
   const double Z = -depth;
   const double e = sf.exposure_s;
@@ -299,16 +352,20 @@ struct RigSlot {
                                   // GUST: plus the frame's gust velocity (gex, gez) -- every view and a trajectory's end use it unchanged
 };
 
-template <bool WIND = false, bool GUST = false>
-RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
-                         uint32_t j, RigSlot& q, double wx = 0.0, double wz = 0.0, const GustFrame* gf = nullptr) {
+// RATE: returns whether the slot's life is alive -- decided here, once per slot, so that every view and a trajectory agree; a
+// rejected slot is kept by no view (k_rig_particles treats it as a slot beyond the chunk: no view step works on it).  Without
+// RATE: true.
+template <bool WIND = false, bool GUST = false, bool RATE = false>
+RR_HD bool make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box[3], const double* dgrid, const double* cdf, int n_grid,
+                         uint32_t j, RigSlot& q, double wx = 0.0, double wz = 0.0, const GustFrame* gf = nullptr,
+                         const RateFrame* rf = nullptr) {
   static_assert(WIND || !GUST, "the gust path forms the mean-wind additions: GUST needs WIND");
   const SlotDraw s = slot_draw(sf, dgrid, cdf, n_grid, j);
   const double b = box[0] * s.z_max;
   const double by = box[1] * s.z_max + box[2];
   const double w = 2.0 * b, wy = 2.0 * by;
   GustBirth gb;
-  const SlotFall f = slot_fall<GUST>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb);
+  const SlotFall f = slot_fall<GUST, RATE>(sf, cam_hz, j, s.D, wy, s.phase, gf, &gb, rf);
   double vx = f.wind, vz = sf.speed_mps;
   if constexpr (WIND) { q.vx = vx = f.wind + wx; q.vz = vz = sf.speed_mps + wz; }
   double qx, qz;
@@ -333,6 +390,8 @@ RR_HD void make_rig_slot(const rr_sim_frame& sf, double cam_hz, const double box
   q.z_max = s.z_max;
   q.life = f.life;
   q.pick_word = f.b[2];
+  if constexpr (RATE) return f.alive;
+  return true;
 }
 
 // The START of slot q's streak as the view (R row-major rig -> camera, c the camera's centre) sees it: the lattice image nearest

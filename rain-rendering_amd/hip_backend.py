@@ -159,7 +159,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
-           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_trajectory',
+           'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose']
 
 _lib = None
@@ -261,6 +261,7 @@ def load_library(path=None):
     lib.rr_set_particle_jitter.argtypes = [ctypes.c_void_p, ctypes.c_double]
     lib.rr_set_particle_wind.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
     lib.rr_set_particle_gusts.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p]
+    lib.rr_set_particle_rate_series.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p]
     lib.rr_augment_frames_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_batch), ctypes.c_void_p]
     lib.rr_set_particle_rig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     assert lib.rr_sizeof_rig_view() == RIG_VIEW_DTYPE.itemsize == 96, (lib.rr_sizeof_rig_view(), RIG_VIEW_DTYPE.itemsize)
@@ -642,6 +643,11 @@ class Prepared:
         """Frame k renders the first n_drops records of the drop array it was prepared with."""
         self.fin[k].n_drops = int(n_drops)
 
+    def set_fog(self, k, fog):
+        """Frame k's pre-pass takes these fog constants (beta_ext, beta_hg, irr_num, irr_den) instead of those it was prepared with."""
+        p = self.pin[k]
+        p.beta_ext, p.beta_hg, p.irr_num, p.irr_den = [float(v) for v in fog]
+
 
 class RainHip:
     """One rendering context on one GPU (one per process / per GPU)."""
@@ -901,6 +907,24 @@ class RainHip:
         if not 0 <= int(gusts.frame0) < 2 ** 32:
             raise ValueError("gust series: frame0 %d is outside 0 .. 2^32 - 1" % int(gusts.frame0))
         self._check(self.lib.rr_set_particle_gusts(self.h, len(d) - 1, int(gusts.frame0), _ptr(d)), 'rr_set_particle_gusts')
+
+    def set_particle_rate_series(self, rate_series=None):
+        """rr_set_particle_rate_series: a rain rate that changes over time under the field and rig models -- `rate_series` = a
+        tools/particles.RateSeries (frame0, rate [n + 1] mm/hr at time indices frame0 .. frame0 + n, peak), or None: off.  The
+        table the library gets is RateSeries.dlam(); the particle tables and sim records of the run are the PEAK rate's.  After
+        set_particle_model (a later one drops the series); every generated record's frame must lie inside it."""
+        if rate_series is None:
+            self._check(self.lib.rr_set_particle_rate_series(self.h, 0, 0, None), 'rr_set_particle_rate_series')
+            return
+        r = np.asarray(rate_series.rate, np.float64)
+        if r.ndim != 1 or len(r) < 2:
+            raise ValueError("rate series: rate must hold n + 1 values with n >= 1, got shape %r" % (r.shape,))
+        if not 0 <= int(rate_series.frame0) < 2 ** 32:
+            raise ValueError("rate series: frame0 %d is outside 0 .. 2^32 - 1" % int(rate_series.frame0))
+        if not (np.isfinite(r).all() and (r >= 0).all() and np.isfinite(rate_series.peak) and rate_series.peak > 0):
+            raise ValueError("rate series: every rate must be finite and >= 0, the peak > 0")
+        d = np.ascontiguousarray(rate_series.dlam(), np.float64)
+        self._check(self.lib.rr_set_particle_rate_series(self.h, len(d) - 1, int(rate_series.frame0), _ptr(d)), 'rr_set_particle_rate_series')
 
     def set_particle_rig(self, views, box, active=None):
         """rr_set_particle_rig: `views` = RIG_VIEW_DTYPE records (rig.Rig.as_records()), `box` = (r, r_y, o_y) (Rig.box), `active` =

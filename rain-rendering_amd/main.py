@@ -80,6 +80,12 @@ _FLAGS = [
                              "of --wind: per component an Ornstein-Uhlenbeck velocity of standard deviation SIGMA m/s (0 < SIGMA <= 20) and "
                              "correlation time TAU seconds (default 2), from SEED (default 0), over the run's frame indices: the slant "
                              "sways over seconds, coherently for every drop and every view")),
+    (('--showers',), dict(type=str, default=None,
+                          help="with --device_particles --particle_model field|rig: LOW,PERIOD_S[,PHASE], a rain rate that changes over "
+                               "time: it swings between LOW mm/hr (0 <= LOW <= --intensity) and the run's --intensity, its peak, once every "
+                               "PERIOD_S seconds (PHASE radians, default 0: the run starts at LOW), over the run's frame indices.  One rain "
+                               "field builds, peaks and fades: drops that fall keep falling, each frame's fog follows its own rate; works "
+                               "with --wind, --gusts, --trajectory, --rig, both --particle_draws and --streak_jitter")),
     (('--streak_lean',), dict(type=str, default='auto', choices=['auto', 'on', 'off'],
                               help="'on': a streak tile's lean and corner come from the streak's own end points; 'off': the reference's rule "
                                    "(lean by the image half the streak ends in, corner at its start: right for streaks that radiate from the "
@@ -106,9 +112,9 @@ def _parse(argv):
 
 
 def _wind_and_lean(ns):
-    """--wind WX,WZ as a pair of floats (default (0, 0)), --gusts SIGMA[,TAU[,SEED]] as (sigma, tau, seed) or None, and --streak_lean as
-    ns.lean: 'auto' is on exactly when a non-zero wind or a gust series is given, so that no command line without --wind or --gusts
-    changes its output."""
+    """--wind WX,WZ as a pair of floats (default (0, 0)), --gusts SIGMA[,TAU[,SEED]] as (sigma, tau, seed) or None, --showers
+    LOW,PERIOD_S[,PHASE] as (low, period_s, phase) or None, and --streak_lean as ns.lean: 'auto' is on exactly when a non-zero wind or
+    a gust series is given, so that no command line without --wind or --gusts changes its output."""
     wind = getattr(ns, 'wind', None)
     if wind is not None and not isinstance(wind, tuple):
         try:
@@ -134,6 +140,24 @@ def _wind_and_lean(ns):
         if not ns.device_particles or getattr(ns, 'particle_model', 'iid') not in ('field', 'rig'):
             raise SystemExit("--gusts needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
     ns.gusts = gusts
+    showers = getattr(ns, 'showers', None)
+    if showers is not None and not isinstance(showers, tuple):  # --showers LOW,PERIOD_S[,PHASE] as (low, period_s, phase)
+        parts = str(showers).split(',')
+        try:
+            showers = (float(parts[0]), float(parts[1]), float(parts[2]) if len(parts) > 2 else 0.0)
+        except (ValueError, IndexError):
+            showers = ()
+        try:                                                    # the peak is the run's --intensity: every one of them
+            peaks = [float(v) for v in (ns.intensity.split(',') if isinstance(ns.intensity, str) else ns.intensity)]
+        except (ValueError, TypeError, AttributeError):
+            peaks = []
+        if not 2 <= len(parts) <= 3 or len(showers) != 3 or not (math.isfinite(showers[0]) and showers[0] >= 0) or \
+                not (math.isfinite(showers[1]) and showers[1] > 0) or not math.isfinite(showers[2]) or any(showers[0] > p for p in peaks):
+            raise SystemExit("--showers %r: expected LOW,PERIOD_S[,PHASE] with 0 <= LOW <= --intensity mm/hr, PERIOD_S > 0 seconds, PHASE a "
+                             "finite number of radians" % (ns.showers,))
+        if not ns.device_particles or getattr(ns, 'particle_model', 'iid') not in ('field', 'rig'):
+            raise SystemExit("--showers needs --device_particles --particle_model field|rig (the i.i.d. model has no time)")
+    ns.showers = showers
     mode = getattr(ns, 'streak_lean', 'auto') or 'auto'
     ns.lean = (any(ns.wind) or ns.gusts is not None) if mode == 'auto' else mode == 'on'
     return ns

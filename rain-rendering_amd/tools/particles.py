@@ -54,7 +54,7 @@ in the library) is a persistent, stateless particle field for video:
   * the TIME is the rendered frame's index f itself (it does not wrap); the SETTINGS of frame f are those of simulated frame
     f % n_sim.  Motion is continuous across frames whose settings agree; where the settings of two consecutive frames
     differ (``sim_mode == "steps"``: speed, focal length, exposure or fall rate per step) the boxes, periods and tables
-    differ and the field may jump;
+    differ and the field may jump (a fall rate that changes WITHOUT a jump is a rate series: Showers, below);
   * particle (slot j, frame k) is a pure function of (seed, j, k) and the settings: any frame can be made alone, in any
     batch, on any rank, with the same bits.  The kept records of a frame are in ascending slot order.  Angular noise
     (``--noise_std``) is not defined for the field model.
@@ -119,6 +119,23 @@ mean-wind additions are formed, also for a mean of (0, 0).  Nothing else depends
 Philox blocks, tables, the pick, the jitter.  Inside a life the term is a translation modulo the box that does not depend on the
 uniform start: one frame keeps the i.i.d. law.  Drops follow the air with no inertia.  ``gusts=None`` (default) is off and forms
 no addition.  The i.i.d. model has no time and refuses a series.
+
+Showers (``rate_series=RateSeries``, ``rr_set_particle_rate_series`` in the library; field and rig models): a rain rate that
+changes over time.  ``rate[n + 1]`` holds mm/hr, row i at time index ``frame0 + i``.  The run's slots, slot counts, boxes and
+tables are those of the series' PEAK rate and never change; a life of a slot is kept with the probability
+``N(D; R) / N(D; R_peak) = exp(-(Lambda(R) - Lambda(R_peak)) D)`` (at most 1 for R <= R_peak) of the rate R at the life's BIRTH
+time: the peak's field thinned to the field at rate R, in law, and a drop that has started to fall keeps falling.  The host turns
+the series into the table ``L[i] = min(mp_lambda(rate[i]) - mp_lambda(peak), RATE_DLAM_MAX)`` (``RateSeries.dlam``; a rate of 0
+gives RATE_DLAM_MAX), the statements look up, interpolate and compare (``_rate_alive``).  With m = frame - frame0 (0 <= m < n):
+    sb = max(m - tau cam_hz, 0);  i = floor(sb);  Lb = L[i] + (sb - i) (L[i + 1] - L[i])   -- Lambda's excess at the drop's birth
+    p = det_exp(-(Lb D));  alive = unit32(b[3]) < p                        -- b[3]: word 3 of the life's block 1, read by nothing else
+(before the series starts its first value is held -- no extrapolation).  A life that is not alive is culled exactly as a slot
+outside the frustum is; under the rig model the decision belongs to the slot (``rig_state``), so every view and a trajectory
+agree.  Lb = 0 gives p = 1.0 exactly: a series that sits at its peak gives the records of no series, byte for byte.  Lb = 100
+gives p < 2^-33, the smallest ``unit32``: a rate of 0 admits no new drop.  Nothing else depends on the series: slot counts, boxes,
+lives, periods, tables, positions, the pick, the jitter, wind and gusts.  So where the rate changes during a clip the field no
+longer jumps.  The rate seen at time t is the rate at the drops' birth times: large near drops lag by up to one fall period.
+``rate_series=None`` (default) is off and forms none of the above.  The i.i.d. model has no time and refuses a series.
 """
 import os
 
@@ -625,6 +642,104 @@ def _gust_terms(gusts, k, tau, cam_hz):
     return dG, ge
 
 
+# ---- showers: the rain rate sampled at frame times (module docstring; rr_set_particle_rate_series) -------------------
+RATE_MAX_N = 1 << 20                 # intervals of a series
+RATE_DLAM_MAX = 100.0                # mm^-1: det_exp(-(100 D)) is below every unit32 for D >= 0.5 mm
+
+
+class RateSeries:
+    """frame0: the time index of row 0; rate [n + 1]: the rain rate in mm/hr at time indices frame0 .. frame0 + n; peak: the
+    rate the run's slots and tables are drawn for (default: max(rate)).  Covers the frames frame0 <= k < frame0 + n."""
+
+    def __init__(self, frame0, rate, peak=None):
+        self.frame0 = int(frame0)
+        self.rate = np.ascontiguousarray(rate, np.float64)
+        self._peak = None if peak is None else float(peak)
+
+    @property
+    def n(self):
+        return len(self.rate) - 1
+
+    @property
+    def peak(self):
+        return float(self.rate.max()) if self._peak is None else self._peak
+
+    def covers(self, k):
+        k = np.asarray(k, np.int64)
+        return (k >= self.frame0) & (k < self.frame0 + self.n)
+
+    def rate_at(self, k):
+        """The rate at time index k (frame0 <= k <= frame0 + n)."""
+        return float(self.rate[int(k) - self.frame0])
+
+    def dlam(self):
+        """rr_set_particle_rate_series' table: L[i] = min(mp_lambda(rate[i]) - mp_lambda(peak), RATE_DLAM_MAX), [n + 1] mm^-1."""
+        lp = mp_lambda(self.peak)
+        return np.asarray([min(mp_lambda(r) - lp, RATE_DLAM_MAX) if r > 0.0 else RATE_DLAM_MAX for r in self.rate.tolist()], np.float64)
+
+
+def _check_rate_series(rate_series, model='field', frames=None):
+    """rr_set_particle_rate_series' refusals (and the generator's, for the time indices `frames`) as ValueError.  Returns
+    `rate_series`."""
+    if rate_series is None:
+        return None
+    if not isinstance(rate_series, RateSeries):
+        raise ValueError("rate_series %r: expected a particles.RateSeries or None" % (rate_series,))
+    if model not in ('field', 'rig'):
+        raise ValueError("a rate series needs particle model 'field' or 'rig': the i.i.d. model has no time")
+    R = rate_series.rate
+    if R.ndim != 1 or len(R) < 2:
+        raise ValueError("rate series: rate must hold n + 1 values with n >= 1, got shape %r" % (R.shape,))
+    n = len(R) - 1
+    if n > RATE_MAX_N:
+        raise ValueError("rate series: n = %d is beyond 2^20 intervals" % n)
+    if rate_series.frame0 < 0 or rate_series.frame0 + n > 2 ** 32:
+        raise ValueError("rate series: frame0 %d + n %d must lie in 0 .. 2^32" % (rate_series.frame0, n))
+    if not np.isfinite(R).all() or (R < 0).any():
+        raise ValueError("rate series: every rate must be finite and >= 0 (mm/hr)")
+    peak = rate_series.peak
+    if not np.isfinite(peak) or not peak > 0 or peak < R.max():
+        raise ValueError("rate series: peak %r must be finite, > 0 and >= max(rate) = %r" % (peak, float(R.max())))
+    if frames is not None and not rate_series.covers(np.asarray(frames, np.int64) & 0xFFFFFFFF).all():
+        raise ValueError("time index outside the rate series' frames %d .. %d" % (rate_series.frame0, rate_series.frame0 + n - 1))
+    return rate_series
+
+
+def shower_series(n, cam_hz, peak, low, period_s, frame0=0, phase=0.0):
+    """A RateSeries of n intervals at cam_hz frames per second: a shower that swings between `low` and `peak` mm/hr once every
+    `period_s` seconds, rate[i] = low + (peak - low) (1 - cos(2 pi (i / cam_hz) / period_s + phase)) / 2 (never above peak), with
+    `peak` the series' peak.  A helper that makes data, like gust_series: the statements take any series."""
+    n, cam_hz, peak, low, period_s, phase = int(n), float(cam_hz), float(peak), float(low), float(period_s), float(phase)
+    if n < 1 or n > RATE_MAX_N:
+        raise ValueError("shower_series: n must be 1 .. 2^20, got %d" % n)
+    if not (np.isfinite(cam_hz) and cam_hz > 0 and np.isfinite(period_s) and period_s > 0 and np.isfinite(phase)):
+        raise ValueError("shower_series: cam_hz > 0, period_s > 0 and phase must be finite")
+    if not (np.isfinite(peak) and np.isfinite(low) and peak > 0 and 0 <= low <= peak):
+        raise ValueError("shower_series: 0 <= low <= peak, peak > 0 (mm/hr)")
+    i = np.arange(n + 1, dtype=np.float64)
+    rate = low + (peak - low) * (1.0 - np.cos(2.0 * np.pi * (i / cam_hz) / period_s + phase)) / 2.0
+    return _check_rate_series(RateSeries(frame0, np.minimum(np.maximum(rate, 0.0), peak), peak=peak))
+
+
+def _rate_alive(rate_series, k, tau, cam_hz, D, w):
+    """rr_particles.h rate_birth / rate_alive: whether the lives that began `tau` seconds before time index k, of drops of
+    diameter D (mm) with the acceptance word w (word 3 of the life's block 1), are kept (module docstring): look up, interpolate,
+    det_exp, compare -- one operation per step."""
+    L = rate_series.dlam()
+    m = (int(k) & 0xFFFFFFFF) - rate_series.frame0
+    if not 0 <= m < rate_series.n:
+        raise ValueError("time index %d is outside the rate series' frames %d .. %d" % (
+            int(k), rate_series.frame0, rate_series.frame0 + rate_series.n - 1))
+    back = tau * float(cam_hz)
+    sb = np.maximum(float(m) - back, 0.0)
+    i = np.floor(sb)
+    ii = i.astype(np.int64)
+    fr = sb - i
+    l0, l1 = L[ii], L[ii + 1]
+    Lb = l0 + fr * (l1 - l0)
+    return unit32(w) < det_exp(-(Lb * D))
+
+
 def _project(cam, X, Y, depth, wd):
     """rr_particles.h project: (sensor position (n, 2), image width) of one streak end at camera-frame (X, Y), `depth` away."""
     W, H = float(cam.W), float(cam.H)
@@ -729,10 +844,11 @@ def _slot_fall(cam, cam_hz, k, j, key, D, wy, phase, wind_sigma):
 
 
 def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                         cull=True, wind=(0.0, 0.0), gusts=None):
+                         cull=True, wind=(0.0, 0.0), gusts=None, rate_series=None):
     """The field model's particles of time index `k` (t = k / cam_hz) under the settings `cam` / `cdf`: the numpy statement
     of rr_particles.h make_field_particle (same operations, same order).  Returns (PARTICLE_DTYPE records with pid = slot,
-    life per record); with `cull` only the slots inside the frustum, in ascending slot order."""
+    life per record); with `cull` only the slots inside the frustum, in ascending slot order.  `rate_series`: `cdf` and
+    n_slots are the peak's, and a life the series rejects is culled like a slot outside the frustum."""
     if n_slots == 0:
         return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
     j = np.arange(n_slots, dtype=np.uint64)
@@ -759,6 +875,8 @@ def make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, wind_sigma=1
     zr = fz * z_max
     ax, ay = hx * zr, hy * zr
     inside = (-ax <= X) & (X <= ax) & (-ay <= Y) & (Y <= ay)
+    if rate_series is not None:
+        inside = inside & _rate_alive(_check_rate_series(rate_series), k, tau, cam_hz, D, b[3])
     depth = np.maximum(zr, 0.05)
     Z = -depth
     e = cam.exposure
@@ -787,16 +905,20 @@ def field_kinematics(cam, dgrid, cdf, slots, lives, seed, wind_sigma=1.0, margin
 
 
 def field_frame(options, fallrate, k, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-                cull=True, wind=(0.0, 0.0), gusts=None):
+                cull=True, wind=(0.0, 0.0), gusts=None, rate_series=None):
     """Frame `k` of a field-model run ALONE: (PARTICLE_DTYPE records with pid = slot id, life per record) of the particles
     inside the frustum -- the identity of a frame's particles.  Time index k, settings of simulated frame k % n_sim
-    (n_sim: n_sim_frames(options) by default).  `generate(..., model='field')` is these frames one after the other."""
+    (n_sim: n_sim_frames(options) by default).  `generate(..., model='field')` is these frames one after the other.
+    `rate_series`: `fallrate` is the series' peak."""
     n_sim = n_sim_frames(options) if n_sim is None else int(n_sim)
     ks = int(k) % n_sim
     cam, rate = _frame_settings(options, fallrate, ks, min_px, z_far, margin)
     _, dgrid, cdf, _ = expected_count(cam, rate, min_px, z_far, margin)
     n_slots = int(field_slot_counts(options, fallrate, ks + 1, seed, min_px, z_far, margin, count)[ks])
-    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind, gusts=gusts)
+    if rate_series is None:
+        return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind, gusts=gusts)
+    return make_field_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, cull, wind=wind, gusts=gusts,
+                                rate_series=rate_series)
 
 
 # ---- the RIG model: one field, several cameras (module docstring) --------------------------------------------------
@@ -850,9 +972,11 @@ def rig_tables(options, fallrate, n_frames, rig, min_px=1.0, z_far=15.0, margin=
                    lambda cam, rate: rig_expected_count(cam, rate, _rig_box(rig, cam, margin), min_px, z_far))
 
 
-def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0, wind=(0.0, 0.0), gusts=None):
+def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, min_px=1.0, z_far=15.0, wind=(0.0, 0.0), gusts=None,
+              rate_series=None):
     """The rig-frame state of every slot at time index k -- the part of make_rig_particles no view enters (rr_particles.h
-    make_rig_slot): dict(D, z_max, b (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life)."""
+    make_rig_slot): dict(D, z_max, b (half side in x and z), by, pos (n, 3), vel (n, 3) in m/s, life).  With `rate_series` also
+    `alive`: whether the series keeps the slot's life -- one decision per slot, for every view."""
     r, r_y, o_y = (float(v) for v in box)
     j = np.arange(n_slots, dtype=np.uint64)
     key = _key(seed)
@@ -874,12 +998,15 @@ def rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma=1.0, mi
     X = fx * w - b
     Y = by - age * wy
     Z = fz * w - b
-    return dict(D=D, wd=wd, z_max=z_max, b=b, by=by, life=g, pos=np.stack([X, Y, Z], axis=1),
-                vel=np.stack([vx, -v, np.full(n_slots, float(vz))], axis=1))
+    st = dict(D=D, wd=wd, z_max=z_max, b=b, by=by, life=g, pos=np.stack([X, Y, Z], axis=1),
+              vel=np.stack([vx, -v, np.full(n_slots, float(vz))], axis=1))
+    if rate_series is not None:
+        st['alive'] = _rate_alive(_check_rate_series(rate_series, 'rig'), k, tau, cam_hz, D, bb[3])
+    return st
 
 
 def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, wind_sigma=1.0, margin=0.05, min_px=1.0, z_far=15.0,
-                       cull=True, image=(0, 0), view_end=None, wind=(0.0, 0.0), gusts=None):
+                       cull=True, image=(0, 0), view_end=None, wind=(0.0, 0.0), gusts=None, rate_series=None):
     """The rig model's particles of time index `k` as view `view` = (R [9] row-major rig -> camera, c [3]) sees them: the numpy
     statement of rr_particles.h make_rig_slot + rig_view_particle (traj_view_start, rig_view_end; same operations, same order).  `box` = (r, r_y, o_y).
     Returns (PARTICLE_DTYPE records in the CAMERA's frame with pid = slot, life per record); with `cull` only the slots the
@@ -893,7 +1020,10 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
         return np.zeros(0, PARTICLE_DTYPE), np.zeros(0, np.float64)
     R = [float(v) for v in np.asarray(view[0], np.float64).reshape(9)]
     c = [float(v) for v in np.asarray(view[1], np.float64).reshape(3)]
-    st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind, gusts=gusts)
+    if rate_series is None:
+        st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind, gusts=gusts)
+    else:
+        st = rig_state(cam, dgrid, cdf, n_slots, k, seed, cam_hz, box, wind_sigma, min_px, z_far, wind=wind, gusts=gusts, rate_series=rate_series)
     W, H = float(cam.W), float(cam.H)
     hx, hy = ((0.5 + margin) * W) / cam.fpx, ((0.5 + margin) * H) / cam.fpx
     b, z_max, wd = st['b'], st['z_max'], st['wd']
@@ -912,6 +1042,8 @@ def make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam_hz, view, box, win
     zr = -zc                                                    # depth along the view's axis
     ax, ay = hx * zr, hy * zr
     inside = (zr > 0.0) & (zr <= z_max) & (-ax <= xc) & (xc <= ax) & (-ay <= yc) & (yc <= ay)
+    if rate_series is not None:                                 # a rejected slot is kept by no view
+        inside = inside & st['alive']
     depth = np.maximum(zr, 0.05)
     e = cam.exposure
     ex = dx + st['vel'][:, 0] * e
@@ -942,7 +1074,7 @@ def _traj_cam(cam):
 
 
 def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, n_sim=None,
-              cull=True, image=(0, 0), trajectory=None, box=None, wind=(0.0, 0.0), gusts=None):
+              cull=True, image=(0, 0), trajectory=None, box=None, wind=(0.0, 0.0), gusts=None, rate_series=None):
     """Frame (k, view) of a rig-model run ALONE: (records with pid = slot, life per record), like field_frame.  With
     `trajectory` (trajectory.Trajectory): the view's composed poses of time index k, the trajectory's box and slot counts, speed 0.
     `box`: another box than the run's (tests)."""
@@ -959,7 +1091,7 @@ def rig_frame(options, fallrate, k, rig, view, seed=0, min_px=1.0, z_far=15.0, m
         po = trajectory.compose(rig, cam.exposure)[int(k), int(view)]
         cam, pose, view_end = _traj_cam(cam), (po['R0'], po['c0']), (po['R1'], po['c1'])
     return make_rig_particles(cam, dgrid, cdf, n_slots, k, seed, cam.hz, pose, box, wind_sigma, margin, min_px, z_far, cull, image,
-                              view_end=view_end, wind=wind, gusts=gusts)
+                              view_end=view_end, wind=wind, gusts=gusts, rate_series=rate_series)
 
 
 def rig_run_sims(sims, k_idx, n_active):
@@ -969,7 +1101,7 @@ def rig_run_sims(sims, k_idx, n_active):
 
 
 def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin=0.05, wind_sigma=1.0, count=None, model='iid',
-             wind=(0.0, 0.0), gusts=None):
+             wind=(0.0, 0.0), gusts=None, rate_series=None):
     """(frames, drops) record arrays of `n_frames` camera frames.  `count`: force that many drops per frame instead
     of the Poisson-distributed physical count.  model='field': the persistent field (module docstring), frame k at time
     k / cam_hz under the settings of simulated frame k; pid is then the slot id.  (The rig model has no particle file: its
@@ -978,6 +1110,8 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
     _check_model(model)
     if gusts is not None and model == 'iid':
         raise ValueError("a gust series needs particle model 'field' or 'rig': the i.i.d. model has no time")
+    if rate_series is not None:                                # (`fallrate` is the series' peak: the slots and tables are the peak's)
+        _check_rate_series(rate_series, model, frames=range(n_frames) if model == 'field' else None)
     if model == 'rig':
         raise ValueError("particle model 'rig' writes no particle file: use rig_frame / expected_records (one table per view)")
     if model == 'field':
@@ -995,7 +1129,8 @@ def generate(options, fallrate, n_frames, seed=0, min_px=1.0, z_far=15.0, margin
         _, dgrid, cdf, _ = tables[tk]
         n = int(counts[k])
         if model == 'field':
-            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, wind=wind, gusts=gusts)
+            rec, _ = make_field_particles(cam, dgrid, cdf, n, k, seed, cam.hz, wind_sigma, margin, min_px, z_far, wind=wind, gusts=gusts,
+                                          rate_series=rate_series)
             n = len(rec)
         else:
             rec = make_particles(cam, dgrid, cdf, n, k, seed, wind_sigma, margin, min_px, z_far, wind=wind)
@@ -1061,7 +1196,7 @@ def field_run_sims(sims, f_idx):
 
 
 def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None, view=0, draws='stream', jitter=0.0, trajectory=None,
-                  wind=(0.0, 0.0), gusts=None):
+                  wind=(0.0, 0.0), gusts=None, rate_series=None):
     """(streak table, W, H) of one rr_sim_frame record the host's way: make_particles -> DBManager.load_streaks_from_records
     (the loader's derived fields) on the rendered frame.  draws='counter': the table also carries `pick`, the counter-based
     texture pick of every row (counter_picks of the row's particle); with `jitter`, `jitter_g`: the row's counter_jitter."""
@@ -1081,9 +1216,10 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
                 raise ValueError("time index %d is outside the trajectory's %d poses" % (k, len(po)))
             po = po[k, int(view)]
             pose, box, view_end = (po['R0'], po['c0']), trajectory.bind(rig), (po['R1'], po['c1'])
-        rec, life = make_rig_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), pose, _rig_box(box, cam, margin), view_end=view_end, gusts=gusts, **kw)
+        rec, life = make_rig_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), pose, _rig_box(box, cam, margin), view_end=view_end, gusts=gusts,
+                                       rate_series=rate_series, **kw)
     elif model == 'field':
-        rec, life = make_field_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), gusts=gusts, **kw)
+        rec, life = make_field_particles(cam, dgrid, tab, n, k, seed, float(cam_hz), gusts=gusts, rate_series=rate_series, **kw)
     else:
         rec = make_particles(cam, dgrid, tab, n, k, seed, **kw)
     fr = np.zeros(1, PARTICLE_FRAME_DTYPE)
@@ -1105,7 +1241,7 @@ def _loaded_table(s, dgrid, cdf, db, dataset, model='iid', cam_hz=None, rig=None
 
 def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise_scale=0.0, run=None, model='iid', cam_hz=None,
                      rig=None, view=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0),
-                     gusts=None):
+                     gusts=None, rate_series=None):
     """What rr_generate_drops_device must leave in HBM for these frames: per frame the rr_drop records (DROP_DTYPE) made the
     host's way -- make_particles -> DBManager.load_streaks_from_records (the loader's derived fields) ->
     hip_backend.pack_frame (frame filter + the frame's random draws) with the exact rotation terms.  `db`: a DBManager
@@ -1138,7 +1274,11 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
     made under that mean wind (module docstring).  (0, 0): the records above.
 
     gusts=GustSeries (rr_set_particle_gusts; field and rig models, both draws, with jitter, wind and trajectory): the records of the
-    particles made under that gust series; every record's frame must lie inside it and run_pos must be 0.  None: the records above."""
+    particles made under that gust series; every record's frame must lie inside it and run_pos must be 0.  None: the records above.
+
+    rate_series=RateSeries (rr_set_particle_rate_series; field and rig models, both draws, with jitter, wind, gusts and trajectory):
+    the records of the lives that series keeps -- `sims` and `cdf` are the peak rate's; every record's frame must lie inside the
+    series and run_pos must be 0.  None: the records above."""
     from .. import hip_backend
     _check_model(model)
     wind = _check_wind(wind)
@@ -1146,6 +1286,10 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
         _check_gusts(gusts, cam_hz, model, frames=[int(s['frame']) for s in sims])
         if any(int(s['run_pos']) != 0 for s in sims):
             raise ValueError("a gust series: run_pos must be 0")
+    if rate_series is not None:
+        _check_rate_series(rate_series, model, frames=[int(s['frame']) for s in sims])
+        if any(int(s['run_pos']) != 0 for s in sims):
+            raise ValueError("a rate series: run_pos must be 0")
     noisy = bool(noise_std) and bool(noise_scale)
     jitter = _check_jitter(jitter, noisy, run)
     _check_draws(draws, noisy)
@@ -1162,7 +1306,8 @@ def expected_records(sims, dgrid, cdf, db, dataset='kitti', noise_std=0.0, noise
             raise ValueError("%d records are not a multiple of the %d active views" % (len(sims), len(views)))
     out = []
     for i, s in enumerate(sims):
-        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory, wind, gusts)
+        table, m, W, H = _loaded_table(s, dgrid, cdf, db, dataset, model, cam_hz, rig, views[i % len(views)], draws, jitter, trajectory, wind, gusts,
+                                       rate_series)
         p = int(s['run_pos'])
         if jitter or draws == 'counter':
             if p != 0:

@@ -19,12 +19,12 @@ for b in re.split(r'remark: [^\n]*Function Name: ', txt)[1:]:
     g = lambda k: int(re.search(k + r': (\d+)', b).group(1)) if re.search(k + r': (\d+)', b) else -1
     rows.append((name, g('VGPRs'), g('AGPRs'), g('SGPRs'), g(r'ScratchSize \[bytes/lane\]'), g(r'Occupancy \[waves/SIMD\]'), g(r'LDS Size \[bytes/block\]')))
 dem = subprocess.run(['c++filt'] + [r[0] for r in rows], capture_output=True, text=True).stdout.split('\n')
-lines = ['%-60s %5s %5s %5s %8s %10s %9s' % ('kernel', 'VGPR', 'AGPR', 'SGPR', 'scratch', 'waves/SIMD', 'LDS bytes')]
+lines = ['%-72s %5s %5s %5s %8s %10s %9s' % ('kernel', 'VGPR', 'AGPR', 'SGPR', 'scratch', 'waves/SIMD', 'LDS bytes')]
 for r, d in sorted(zip(rows, dem), key=lambda x: x[1]):
     d = re.sub(r'\(anonymous namespace\)::', '', d)
     d = re.sub(r'^void ', '', d)
     d = re.sub(r'\(.*', '', d)
-    lines.append('%-60s %5d %5d %5d %8d %10d %9d' % ((d[:60],) + r[1:]))
+    lines.append('%-72s %5d %5d %5d %8d %10d %9d' % ((d[:72],) + r[1:]))
 out = '\n'.join(lines) + '\n(static LDS only: dynamic shared memory is sized at launch)\n'
 if len(sys.argv) > 1:
     open(sys.argv[1], 'w').write(out)

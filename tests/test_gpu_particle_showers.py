@@ -1,0 +1,397 @@
+"""GPU tier: showers on the device (rr_set_particle_rate_series; the RATE instantiations of k_field_particles and k_rig_particles, count
+passes included).
+
+  1. device records == the host statement (tools/particles.py expected_records(rate_series=)), bit for bit, counts included: field (one
+     chunk: store pass alone; three chunks: count pass + store pass; jitter 0 and 5), rig (both stereo views with one and two chunks,
+     then view 1 alone), a rig on an arc; both draws; the mean wind and a gust series on and off; under the series of the CPU tier
+     (n = 1, a frame at m = 0, frame0 = 2^31 + 3, a frame at m = n - 1, a series that touches 0) -- every compared frame keeps more
+     than 100 records -- and under a dry series, which must keep none;
+  2. set_particle_rate_series(None) on the same context: today's records;
+  3. the kernel profile: the launch counts with a series are those without;
+  4. every RR_E_ARG, a frame outside the series, the i.i.d. model, a model change dropping the series;
+  5. RainAugment('field', draws='counter', showers=...) == rr_pipeline_submit fed the host statement's records and the per-image fog
+     constants; a wet and a dry frame_index of one batch differ in mask sum the way their rates order them;
+  6. the driver: `main.py ... --showers 2,4` writes the files whose pixels that augmenter gives."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import helpers as h
+from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
+from test_gpu_particle_draws import H, KITTI_STEREO, W, _kitti, _set_rig
+from test_gpu_particle_field import _rh
+from test_gpu_particle_jitter import _same
+from test_gpu_particle_trajectory import MONO, _arc_poses, _set
+from test_particle_showers_host import HZ, PEAK, _gusts_over, rate_cases
+
+pytestmark = pytest.mark.gpu
+
+particles = importlib.import_module('rain-rendering_amd.tools.particles')
+trajmod = importlib.import_module('rain-rendering_amd.trajectory')
+augment = importlib.import_module('rain-rendering_amd.augment')
+imgops = importlib.import_module('rain-rendering_amd.common.imgops')
+envmod = importlib.import_module('rain-rendering_amd.common.envmap')
+
+WIND = (-7.5, 2.0)
+DRAWS = ['counter', 'stream']
+SEED = 1234 + 2 ** 40
+RR_E_ARG = -1                                             # include/rainhip.h
+R = particles.RateSeries
+# the deliberately dry one: the rate is 0 from the start, and a birth before the series takes its first value
+DRY = (R(0, [0.0] * 7, peak=PEAK), [0, 5])
+# (mean wind, with a gust series): on and off, all four
+AIRS = [((0.0, 0.0), False), (WIND, False), ((0.0, 0.0), True), (WIND, True)]
+AIR_IDS = ['calm', 'wind', 'gusts', 'wind+gusts']
+
+
+def _check(rh, sims, want, what, dry=False):
+    got, cnt = rh.generate_drops(sims, H, W)
+    for k in range(len(sims)):
+        if dry:
+            assert int(cnt[k]) == len(want[k]) == 0, (what, k, int(cnt[k]), len(want[k]))
+            continue
+        assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
+        _same(got[k], want[k], '%s: frame %d' % (what, k))
+    return cnt
+
+
+def _cases():
+    return [(rs, frames, False) for rs, frames in rate_cases()] + [DRY + (True,)]
+
+
+# ---- 1. device == host statement -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("jitter", [0.0, 5.0])
+def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
+    opt = _kitti()
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    kw = dict(model='field', cam_hz=opt['cam_hz'])
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_model('field', kw['cam_hz'])
+        rh.set_particle_draws(draws)
+        rh.set_particle_jitter(jitter)
+        for wind, gusty in AIRS:
+            rh.set_particle_wind(*wind)
+            for rs, frames, dry in _cases():
+                gusts = _gusts_over(rs) if gusty else None
+                sims = particles.field_run_sims(sims1, frames)
+                want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=wind, gusts=gusts, rate_series=rs, **kw)
+                rh.set_particle_gusts(gusts)
+                rh.set_particle_rate_series(rs)
+                for chunks in (1, 3):
+                    rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                    _check(rh, sims, want, 'field, %d chunks, %s, jitter %g, wind %s, gusts %s, frames %s' % (chunks, draws, jitter, wind, gusty, frames),
+                           dry)
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("wind,gusty", AIRS, ids=AIR_IDS)
+def test_rig_records_equal_host_statement(tmp_path, built, wind, gusty, draws):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=KITTI_STEREO)
+    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set_rig(rh, opt)
+        rh.set_particle_draws(draws)
+        rh.set_particle_wind(*wind)
+        for rs, inst, dry in _cases():
+            gusts = _gusts_over(rs) if gusty else None
+            sims = particles.rig_run_sims(sims1, inst, 2)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=wind, gusts=gusts, rate_series=rs, **kw)    # frame 2 i + v
+            _set_rig(rh, opt)                                     # (a model change drops the series: set them after)
+            rh.set_particle_gusts(gusts)
+            rh.set_particle_rate_series(rs)
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                _check(rh, sims, want, 'rig, %d chunks, %s, wind %s, gusts %s, instants %s' % (chunks, draws, wind, gusty, inst), dry)
+            rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+            # view 1 alone: the same bits per view
+            _set_rig(rh, opt, active=[1])
+            rh.set_particle_gusts(gusts)
+            rh.set_particle_rate_series(rs)
+            got, cnt = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
+            for i in range(len(inst)):
+                assert int(cnt[i]) == len(want[2 * i + 1])
+                if not dry:
+                    _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+    finally:
+        rh.close()
+
+
+@pytest.mark.parametrize("draws", DRAWS)
+def test_arc_records_equal_host_statement(tmp_path, built, draws):
+    """A single camera on an arc (10 m/s, 20 degrees a second) under the mean wind, a gust series and a jitter of 5 degrees: the
+    decision is the slot's, made before any pose enters.  A series over the arc's nine instants that touches 0, at m = 0, inside and
+    at m = n - 1, and one of a single interval."""
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    hz = opt['cam_hz']
+    rig = MONO
+    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=rig, trajectory=traj)
+    kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        _set(rh, rig, traj, opt, hz)
+        rh.set_particle_draws(draws)
+        rh.set_particle_jitter(5.0)
+        rh.set_particle_wind(*WIND)
+        for rs, inst in ((R(0, [10.0, 18.0, 25.0, 12.0, 0.0, 6.0, 14.0, 20.0, 9.0]), [0, 7, 3]), (R(3, [12.0, 20.0], peak=PEAK), [3])):
+            gusts = _gusts_over(rs)
+            sims = particles.rig_run_sims(sims1, inst, 1)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=WIND, gusts=gusts, rate_series=rs, **kw)
+            rh.set_particle_gusts(gusts)
+            rh.set_particle_rate_series(rs)
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                _check(rh, sims, want, 'arc, %d chunks, %s, instants %s' % (chunks, draws, inst))
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+# ---- 2. off again --------------------------------------------------------------------------------------------------
+def test_the_series_off_again_on_the_same_context(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    rs, frames = rate_cases()[1]
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    sims = particles.field_run_sims(sims1, frames)
+    kw = dict(model='field', cam_hz=opt['cam_hz'], draws='counter')
+    thin = particles.expected_records(sims, dgrid, cdf, sc.db, rate_series=rs, **kw)
+    plain = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)
+    assert all(len(a) < len(b) for a, b in zip(thin, plain))
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        rh.set_particle_model('field', kw['cam_hz'])
+        rh.set_particle_draws('counter')
+        _check(rh, sims, plain, 'before any series')
+        rh.set_particle_rate_series(rs)
+        _check(rh, sims, thin, 'field with the series')
+        rh.set_particle_rate_series(None)
+        _check(rh, sims, plain, 'series off: as before')
+        rh.set_particle_rate_series(R(0, [PEAK] * 7))           # a series at its peak: the records of no series
+        _check(rh, sims, plain, 'a series at its peak')
+        rh.set_particle_rate_series(rs)                          # and on again
+        _check(rh, sims, thin, 'the series again')
+    finally:
+        rh.close()
+
+
+# ---- 3. launch counts ----------------------------------------------------------------------------------------------
+def test_a_series_adds_no_launch(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    rs = R(0, [20.0, 10.0, 5.0, 15.0, 25.0])
+    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    rig_run = (particles.rig_run_sims(sims_r, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
+    sims_f, dgrid_f, cdf_f = particles.sim_frames(opt, 25, 1, seed=7, model='field')
+    field_run = (particles.field_run_sims(sims_f, [0, 1, 3]), dgrid_f, cdf_f, dict(model='field', cam_hz=opt['cam_hz']))
+    rh = _rh(sc)
+    try:
+        rh.profile(True)
+        for name, (sims, dgrid, cdf, kw) in (('k_field_particles', field_run), ('k_rig_particles', rig_run)):
+            rh.set_particle_tables(dgrid, cdf)
+            if kw['model'] == 'rig':
+                _set_rig(rh, opt)
+            else:
+                rh.set_particle_model('field', kw['cam_hz'])
+            for chunks in (1, 2):
+                rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
+                for draws in DRAWS:
+                    rh.set_particle_draws(draws)
+                    counts = {}
+                    for on in (False, True):
+                        rh.set_particle_rate_series(rs if on else None)
+                        rh.profile_reset()
+                        rh.generate_drops(sims, H, W)
+                        stats = rh.profile_read()
+                        counts[on] = {k: v[0] for k, v in stats.items()}
+                        assert stats[name][0] >= 1, (name, draws, on, stats)
+                    assert counts[False] == counts[True], (name, chunks, draws, counts)
+        rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
+    finally:
+        rh.close()
+
+
+# ---- 4. refusals ---------------------------------------------------------------------------------------------------
+def test_refusals(tmp_path, built):
+    sc = h.Scene(tmp_path, 64, 96, 10)
+    opt = _kitti()
+    ok = [25.0, 10.0, 16.0]
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    kw = dict(model='field', cam_hz=opt['cam_hz'])
+    rh = _rh(sc)
+    try:
+        rh.set_particle_tables(dgrid, cdf)
+        with pytest.raises(RuntimeError, match='rate series'):   # the i.i.d. model has no time
+            rh.set_particle_rate_series(R(0, ok))
+        rh.set_particle_rate_series(None)                        # off is always allowed
+        rh.set_particle_model('field', kw['cam_hz'])
+        lib, hnd = rh.lib, rh.h
+        good = np.array([0.0, 0.5, 0.2])
+        for n, frame0, dlam in ((-1, 0, good), (2 ** 20 + 1, 0, np.zeros(2 ** 20 + 2)), (2, 2 ** 32 - 1, good), (1, 0, np.array([0.0, np.nan])),
+                                (1, 0, np.array([0.0, np.inf])), (1, 0, np.array([-1e-9, 0.0])), (1, 0, np.array([0.0, 100.5])), (2, 0, None)):
+            d = None if dlam is None else np.ascontiguousarray(dlam, np.float64)
+            rc = lib.rr_set_particle_rate_series(hnd, n, frame0, None if d is None else d.ctypes.data)
+            assert rc == RR_E_ARG, (n, frame0, rc)
+        rh.set_particle_rate_series(R(2 ** 32 - 2, ok))          # frame0 + n = 2^32 is allowed
+        assert lib.rr_set_particle_rate_series(hnd, 1, 0, np.array([0.0, 100.0]).ctypes.data) == 0     # 100 itself is allowed
+        with pytest.raises(ValueError, match='rate series'):     # the binding's own: a negative rate, a peak of 0
+            rh.set_particle_rate_series(R(0, [25.0, -1.0]))
+        with pytest.raises(ValueError, match='rate series'):
+            rh.set_particle_rate_series(R(0, [0.0, 0.0]))
+        # a refusal leaves the last good series: frames 1, 2 of R(1, ok)
+        rh.set_particle_rate_series(R(1, ok))
+        assert lib.rr_set_particle_rate_series(hnd, 1, 0, np.array([0.0, np.nan]).ctypes.data) == RR_E_ARG
+        sims = particles.field_run_sims(sims1, [1, 2])
+        _check(rh, sims, particles.expected_records(sims, dgrid, cdf, sc.db, rate_series=R(1, ok), **kw), 'after the refusals')
+        # generating: a frame outside the series, before and behind it; run_pos
+        for f in (0, 3, 2 ** 31):
+            with pytest.raises(RuntimeError, match='outside the rate series'):
+                rh.generate_drops(particles.field_run_sims(sims1, [1, f]), H, W)
+        runp = sims.copy()
+        runp['run_pos'] = 1
+        with pytest.raises(RuntimeError, match='run_pos'):
+            rh.generate_drops(runp, H, W)
+        # the model: i.i.d. is refused while a series is set and leaves it; a new field / rig model drops it
+        with pytest.raises(RuntimeError, match='rate series'):
+            rh.set_particle_model('iid')
+        _check(rh, sims, particles.expected_records(sims, dgrid, cdf, sc.db, rate_series=R(1, ok), **kw), 'after the refused model')
+        rh.set_particle_model('field', kw['cam_hz'])
+        plain = particles.expected_records(particles.field_run_sims(sims1, [1, 7]), dgrid, cdf, sc.db, **kw)
+        _check(rh, particles.field_run_sims(sims1, [1, 7]), plain, 'the model set again: no series')     # (frame 7 lies outside the old series)
+        rh.set_particle_model('iid')                             # and with no series the i.i.d. model is allowed again
+    finally:
+        rh.close()
+
+
+# ---- 5. RainAugment end to end -------------------------------------------------------------------------------------
+def test_rain_augment_renders_the_host_statements_records(built, streaks_db):
+    """RainAugment(particle_model='field', draws='counter', showers=...), B = 2, bytes, KITTI, peak 25 mm/hr, against rr_pipeline_submit fed
+    expected_records(rate_series=) as host tables and each image's own fog constants: image bytes and mask equal.  The series stands
+    at 25 mm/hr up to frame 4 and at 3 mm/hr from frame 5 on: frame 2 is wet, frame 9 nearly dry, and the masks say so."""
+    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='field', draws='counter')
+    rs = R(0, [25.0] * 5 + [3.0] * 6)
+    aug = augment.RainAugment('kitti', showers=rs, **kw)
+    plain = None
+    try:
+        assert aug.frame_size() == (H, W) and aug.lean is False
+        bgr, depth = _scene(2, H, W, seed=40)
+        idx = [2, 9]
+        p = aug.plan(None, idx)
+        assert p['showers'] is rs and p['key'] == (25.0,) and p['fog'][0, 0] > p['fog'][1, 0] > 0
+        want = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws='counter',
+                                          rate_series=rs)
+        assert len(want[0]) > 3 * len(want[1]) > 0
+        rainy, mask = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), None, idx)
+        rainy, mask = rainy.cpu().numpy(), mask.cpu().numpy()
+        rh = h.hb.RainHip(0)
+        try:
+            rh.set_streak_db(aug.db.streaks_light)
+            rh.set_camera(h.hb.make_camera(aug.focal, aug.f_number, aug.exposure))
+            rh.set_prepass_kernels(imgops.gaussian_kernel(25, 25), imgops.gaussian_kernel(15, 0))
+            we = rh.set_envmap_geometry(H, W, *envmod.EnvironmentMapGenerator(aug.focal, W, H).device_tables(H, W))
+            rh.set_solid_angles(h.solid_angle.get_solid_angles(np.empty((H, we, 0))))
+            frames = [dict(bg_u8=np.ascontiguousarray(bgr[i]), depth=np.ascontiguousarray(depth[i]), fog=tuple(p['fog'][i]), omega=None,
+                           drops=want[i]) for i in range(2)]
+            outs = [dict(image_u8=np.zeros((H, W, 3), np.uint8), mask=np.zeros((H, W))) for _ in range(2)]
+            rh.pipeline_submit(0, frames, outs)
+            while not rh.pipeline_wait(0):
+                rh.pipeline_submit(0, frames, outs)
+        finally:
+            rh.close()
+        for i in range(2):
+            assert np.array_equal(rainy[i].transpose(1, 2, 0), outs[i]['image_u8']), i
+            assert np.array_equal(mask[i, 0], outs[i]['mask'].astype(np.float32)), i
+            assert outs[i]['mask'].max() > 0, i
+        wet, dry = float(mask[0].sum()), float(mask[1].sum())
+        print('mask sum: frame 2 (25 mm/hr) %.1f, frame 9 (3 mm/hr) %.1f' % (wet, dry))
+        assert wet > dry > 0
+        # the peak may be named; anything else, and a frame outside the series, is refused before any GPU work
+        rainy_p, _ = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        assert np.array_equal(rainy_p.cpu().numpy(), rainy)
+        with pytest.raises(ValueError, match='intensity'):
+            aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 10, idx)
+        with pytest.raises(ValueError, match='outside the rate series'):
+            aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), None, [2, 10])
+        # no series between batches: the plain augmenter's pixels; and the series again
+        aug.set_showers(None)
+        rainy_0, _ = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        plain = augment.RainAugment('kitti', **kw)
+        rainy_c, _ = plain(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), 25, idx)
+        assert np.array_equal(rainy_0.cpu().numpy(), rainy_c.cpu().numpy()) and not np.array_equal(rainy_0.cpu().numpy(), rainy)
+        assert np.array_equal(rainy_0.cpu().numpy()[0], rainy[0])          # frame 2 stands at the peak: the plain frame
+        aug.set_showers(rs)
+        rainy_1, _ = aug(_planar(bgr).to(DEV), torch.from_numpy(depth).to(DEV), None, idx)
+        assert np.array_equal(rainy_1.cpu().numpy(), rainy)
+        with pytest.raises(ValueError, match='no time'):
+            augment.RainAugment('kitti', streaks_db=streaks_db, sequence='data_object/training', showers=rs)
+    finally:
+        aug.close()
+        if plain is not None:
+            plain.close()
+
+
+# ---- 6. the driver -------------------------------------------------------------------------------------------------
+def test_the_driver_writes_what_the_augmenter_renders(tmp_path, built, monkeypatch):
+    """Three KITTI-sized frames: `main.py --device_particles --particle_model field --particle_draws counter --showers 2,4` writes the
+    bytes RainAugment(particle_model='field', draws='counter', showers=shower_series(n, 10, 25, 2, 4)) gives for the clip (a sample of
+    the series depends on its index alone, not on n) -- every frame with the fog of its own rate; the run without --showers writes
+    other files."""
+    tmp = str(tmp_path)
+    n = 3
+    src = os.path.join(tmp, 'source')
+    h.synthetic.write_dataset(src, 'kitti', os.path.join('data_object', 'training'), n, H, W, depth_m=None)
+    db_dir = os.path.join(tmp, 'rainstreakdb')
+    h.synthetic.write_streak_db(db_dir)
+    main = importlib.import_module('rain-rendering_amd.main')
+    common = ['--dataset', 'kitti', '-k', src, '-d', src, '-r', os.path.join(tmp, 'particles'), '-sd', db_dir, '-i', '25', '--noverbose',
+              '--device_particles', '--particle_model', 'field', '--particle_draws', 'counter']
+    for bad in (['--showers', '2,4'], ['--device_particles', '--showers', '2,4'], ['--device_particles', '--particle_model', 'field', '--showers', '2'],
+                ['--device_particles', '--particle_model', 'field', '--showers', '2,0'],
+                ['--device_particles', '--particle_model', 'field', '--showers', '26,4'],
+                ['--device_particles', '--particle_model', 'field', '--showers', 'a,4']):
+        with pytest.raises(SystemExit, match='--showers'):
+            main._derive(main._parse(['--dataset', 'kitti', '-k', src, '-i', '25'] + bad))
+    series = particles.shower_series(16, HZ, 25.0, 2.0, 4.0)
+    aug = augment.RainAugment('kitti', streaks_db=db_dir, sequence='data_object/training', particle_model='field', draws='counter', showers=series)
+    try:
+        p = aug.plan(None, np.arange(n))
+        want = particles.expected_records(p['sims'], p['d_grid'], p['cdf'], aug.db, model='field', cam_hz=p['cam_hz'], draws='counter',
+                                          rate_series=series)
+        monkeypatch.setenv('RAIN_BATCH', '2')
+        gen = main.main(common + ['--showers', '2,4', '--output', os.path.join(tmp, 'showers')])
+        assert len(gen.stats) == n and sorted(s_['drops'] for s_ in gen.stats) == sorted(len(w) for w in want) and min(len(w) for w in want) > 0
+        main.main(common + ['--output', os.path.join(tmp, 'steady')])
+        sub = os.path.join('kitti', 'data_object', 'training', 'rain', '25mm', 'rainy_image')
+        names = ['%06d.png' % i for i in range(n)]
+
+        def files(run):
+            return np.stack([np.array(Image.open(os.path.join(tmp, run, sub, f)))[..., :3] for f in names])
+        showers = files('showers')
+        assert not np.array_equal(showers, files('steady'))
+        img_dir = os.path.join(src, 'kitti', 'data_object', 'training', 'image_2')
+        rgb = np.stack([np.array(Image.open(os.path.join(img_dir, f)).convert('RGB')) for f in names])
+        depth = np.stack([np.array(Image.open(os.path.join(img_dir, 'depth', f))).astype(np.float32) / 256. for f in names])
+        rainy, mask = aug(torch.from_numpy(rgb.transpose(0, 3, 1, 2).copy()).to(DEV), torch.from_numpy(depth).to(DEV), None, np.arange(n))
+        assert np.array_equal(rainy.cpu().numpy().transpose(0, 2, 3, 1), showers)
+        assert all(float(mask[i].max()) > 0 for i in range(n))
+    finally:
+        aug.close()
