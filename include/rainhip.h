@@ -575,6 +575,58 @@ typedef struct {
 int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream);
 int rr_sizeof_tensor_batch(void);
 
+/* ---------------------------------------------------------------------------------------
+ * Drops on the lens: adherent raindrops on the camera's lens or windshield, on a batch of planar images that lives on the GPU
+ * (rain-rendering_amd/augment.py RainAugment(lens=) and LensAugment).  The reference has nothing of the kind: the
+ * model is this library's own, stated bit for bit by rain-rendering_amd/tools/lens.py apply_numpy, its arithmetic by
+ * csrc/rr_lens.h.  Every drop is a small inverted, minified, defocused view of the INPUT image with a soft edge and a dark rim.
+ * For pixel (x, y) of a drop's bounding box floor(cx - rx) .. floor(cx + rx) + 1 (likewise y), clipped to the frame, in double:
+ *     u = (x - cx) / rx, v = (y - cy) / ry, rho2 = u u + v v
+ *     t = clamp((1 - rho2) / edge, 0, 1), A = float(t t (3 - 2 t))               coverage; A == 0: the input value, bit for bit
+ *     g = 1 / sqrt(1 - 0.75 min(rho2, 1)), sx = cx - (mag (x - cx)) g, sy alike    clamped to the frame; upside down and mirrored
+ * and in float, every step one IEEE operation, no contraction:
+ *     V(q)   bilinear sample of the input at (sx, sy) between floor(s) and min(floor(s) + 1, size - 1), fractions float(s - floor(s))
+ *     B      the separable blur of V with the 2 R + 1 weights of the drop's class, rows then columns, taps added in ascending
+ *            offset order, V evaluated at q clamped to the frame
+ *     out = (1 - A) in + A (float(1 - (rim rho2) rho2) B)
+ * Pixel values enter as float(value): 0 .. 255 for bytes, which store clamp(rint(out), 0, 255) (half to even); float32 stores out.
+ * Every drop refracts `images`, never `out`, and the bounding boxes of one frame's drops must be pairwise disjoint, so the result
+ * does not depend on any order.  alpha_out (may be NULL) receives A inside the boxes and 0 elsewhere.
+ *
+ * rr_lens_drops_device enqueues on `stream` (NULL = the ctx stream): the device-to-device copy images -> out (and the clearing of
+ * alpha_out), the upload of the records, the blur table and the work list (one workgroup per 32 x 32 piece of a box) through the
+ * context's pinned ring, and ONE kernel, k_lens_drops.  counts, drops, class_radius and weights are read before the call returns.
+ * With a stream of the caller's it returns without waiting; with NULL it waits for the context's stream (the caller has no handle
+ * to order later work behind it).  The caller's current device is restored.
+ * RR_E_ARG, with nothing enqueued: a null pointer, sizes or dtype out of range; out or alpha_out overlapping images or each other;
+ * a count above cap or RR_MAX_LENS_DROPS; a field that is not finite; rx or ry <= 0; mag < 1; edge outside (0, 1]; rim outside
+ * [0, 1]; sigma_class not an integer in 0 .. n_classes - 1; n_classes outside 1 .. 16, a class radius outside 0 .. 15 or a
+ * weight that is not finite; two overlapping bounding boxes in one frame. */
+#define RR_MAX_LENS_DROPS 128
+typedef struct {
+  float cx, cy;                          /* centre, pixels */
+  float rx, ry;                          /* semi-axes, pixels, > 0 */
+  float mag;                             /* how many times wider the field seen through the drop is, >= 1 */
+  float edge;                            /* soft-edge width, (0, 1] */
+  float rim;                             /* rim darkening, [0, 1] */
+  float sigma_class;                     /* blur class: a float holding an integer in 0 .. n_classes - 1 */
+} rr_lens_drop;                          /* 32 bytes */
+typedef struct {
+  int32_t n, H, W, dtype;                /* dtype: RR_TENSOR_*; images and out share it */
+  const void* images;                    /* DEVICE, [n,3,H,W] planar, contiguous */
+  void* out;                             /* DEVICE, [n,3,H,W]; must not overlap images */
+  float* alpha_out;                      /* DEVICE, [n,H,W], or NULL */
+  const int32_t* counts;                 /* HOST, n drop counts */
+  const rr_lens_drop* drops;             /* HOST, n x cap records: frame f's are drops[f * cap .. f * cap + counts[f]) */
+  int32_t cap;
+  int32_t n_classes;                     /* 1 .. 16 */
+  const int32_t* class_radius;           /* HOST, n_classes radii R in 0 .. 15 */
+  const float* weights;                  /* HOST, 16 x 31 float32: class c's 2 R + 1 taps are weights[31 c .. 31 c + 2 R] */
+} rr_lens_batch;
+int rr_lens_drops_device(rr_ctx* ctx, const rr_lens_batch* b, void* stream);
+int rr_sizeof_lens_drop(void);
+int rr_sizeof_lens_batch(void);
+
 /* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
  * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does
  * nothing).  Unknown options or values are RR_E_ARG.  The library reads no environment variables. */

@@ -56,6 +56,14 @@ drop that has started to fall keeps falling -- and image i's fog constants are t
 is then None or the series' peak (anything else is a ValueError, as is None without a series), and a frame_index outside the
 series is a ValueError.  `set_showers()` takes another series between batches.
 
+`lens=LensDrops` (default None: off; tools/lens.py) puts adherent drops on the camera's lens: after the rain, the rainy
+images go through the lens pass (rr_lens_drops_device: one more kernel, k_lens_drops) on the same stream.  Each drop is a small
+inverted, minified, defocused view of the rainy image with a soft edge and a dark rim, and sits still for seconds: `frame_index[i]`
+selects the table, `lens.table(frame_index[i])`; under the rig model view v wears `lens.for_view(views[v])`.  The LensDrops' H, W
+must be the augmenter's frame size (ValueError).  The streak mask comes back unchanged; `return_lens_alpha=True` returns a third
+tensor, float32 [B, 1, H, W] ([B, V, 1, H, W] for a rig): the drops' coverage, 0 outside them -- the label raindrop-removal work trains
+on.  `LensAugment(lens)` is the lens pass alone, for drops without streak rain: `(images, frame_index) -> images`.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -75,6 +83,7 @@ from .common import db as dbmod
 from .common.bad_weather import DBManager
 from . import rig as rigmod
 from .trajectory import Trajectory
+from .tools import lens as lensmod
 from .tools import particles
 
 
@@ -113,7 +122,14 @@ class RainAugment:
     """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
-                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None, showers=None):
+                 rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None, showers=None,
+                 lens=None, return_lens_alpha=False):
+        if lens is not None and not isinstance(lens, lensmod.LensDrops):
+            raise TypeError("lens must be a tools.lens.LensDrops, got %r" % (type(lens).__name__,))
+        if not isinstance(return_lens_alpha, bool) or (return_lens_alpha and lens is None):
+            raise ValueError("return_lens_alpha=%r: True or False, and True needs lens=" % (return_lens_alpha,))
+        self.lens, self.return_lens_alpha = lens, return_lens_alpha
+        self._lens_views = {}                    # view number -> lens.for_view(view)
         if particle_model not in particles.MODELS:
             raise ValueError("particle_model %r: expected one of %s" % (particle_model, ', '.join(particles.MODELS)))
         self.particle_model = particle_model
@@ -173,6 +189,9 @@ class RainAugment:
         self._gusts_set = gusts is None          # whether the context holds the current gust series
         self._showers_set = showers is None      # whether the context holds the current rate series
         self._fogs = {}                          # rate -> fog constants (a rate series: one rate per frame index)
+        if lens is not None and (lens.H, lens.W) != self.frame_size():
+            raise ValueError("lens: the LensDrops are for %d x %d frames (H x W), %s renders %d x %d" %
+                             ((lens.H, lens.W, dataset) + self.frame_size()))
 
     def _check_trajectory(self, trajectory):
         if trajectory is None:
@@ -408,9 +427,86 @@ class RainAugment:
                 # queued on it (the inputs) is finished first, and the call's own wait covers the outputs
                 stream.synchronize()
             hip.augment_frames_device(b, stream.cuda_stream)
+            alpha = None
+            if self.lens is not None:            # the drops on the lens refract the rainy image: one more kernel on the same stream
+                idx = [int(f) for f in _as_list(frame_index, B if V is None else B // V, 'frame_index', 'index')]
+                rainy, alpha = _lens_pass(hip, self._lens_tables(idx), self.lens.weights(), rainy, self.return_lens_alpha, stream)
         if V is not None:
-            return rainy.reshape(B // V, V, 3, H, W), mask.reshape(B // V, V, 1, H, W)
-        return rainy, mask
+            rainy, mask = rainy.reshape(B // V, V, 3, H, W), mask.reshape(B // V, V, 1, H, W)
+            alpha = None if alpha is None else alpha.reshape(B // V, V, 1, H, W)
+        return (rainy, mask, alpha) if self.return_lens_alpha else (rainy, mask)
+
+    def _lens_tables(self, idx):
+        """The drop tables of a call, one per image of the library's batch: frame_index[i]'s; under a rig, V per instant, view v's own."""
+        if self.rig is None:
+            return [self.lens.table(f) for f in idx]
+        for v in self.views:
+            if v not in self._lens_views:
+                self._lens_views[v] = self.lens.for_view(v)
+        return [self._lens_views[v].table(f) for f in idx for v in self.views]
+
+    def close(self):
+        if self._hip is not None:
+            self._hip.close()
+            self._hip = None
+
+
+def _lens_pass(hip, tables, weights, images, want_alpha, stream):
+    """rr_lens_drops_device on the contiguous [n, 3, H, W] tensor `images`, on `stream`: (images with the drops, alpha or None)."""
+    n, _, H, W = images.shape
+    out = torch.empty_like(images)
+    alpha = torch.empty((n, 1, H, W), dtype=torch.float32, device=images.device) if want_alpha else None
+    hip.lens_drops_device(images.data_ptr(), out.data_ptr(), n, H, W, images.dtype == torch.float32, tables, weights,
+                          alpha_ptr=None if alpha is None else alpha.data_ptr(), stream=stream.cuda_stream)
+    return out, alpha
+
+
+class LensAugment:
+    """Callable: (images, frame_index) -> images with the drops of `lens` (tools/lens.py LensDrops) on them -- the lens pass of
+    RainAugment(lens=) alone, for drops without streak rain.  `images` is [B, 3, H, W] planar on the GPU, uint8 or float32, H x W the
+    LensDrops'; image i wears `lens.table(frame_index[i])`.  return_alpha=True: (images, alpha), alpha float32 [B, 1, H, W], the
+    drops' coverage.  Enqueued on the caller's current stream; on the legacy default stream the call waits for the result."""
+
+    def __init__(self, lens, device=None, return_alpha=False):
+        if not isinstance(lens, lensmod.LensDrops):
+            raise TypeError("lens must be a tools.lens.LensDrops, got %r" % (type(lens).__name__,))
+        self.lens, self.return_alpha = lens, bool(return_alpha)
+        if device is not None:
+            device = torch.device(device) if not isinstance(device, int) else torch.device('cuda', device)
+            if device.type != 'cuda':
+                raise ValueError("LensAugment renders on a GPU: device must be a CUDA (HIP) device, got %s" % device)
+            if device.index is None:
+                device = torch.device('cuda', torch.cuda.current_device())
+        self.device = device                     # None: the current device at the first call
+        self._hip = None
+
+    def __call__(self, images, frame_index):
+        if not isinstance(images, torch.Tensor):
+            raise TypeError("images must be a torch tensor")
+        if images.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("images must be uint8 or float32, got %s" % images.dtype)
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+            raise ValueError("images must be [B, 3, H, W] (planar), got %s" % (tuple(images.shape),))
+        B, _, H, W = images.shape
+        if (H, W) != (self.lens.H, self.lens.W):
+            raise ValueError("the LensDrops are for %d x %d frames (H x W), the images are %d x %d" % (self.lens.H, self.lens.W, H, W))
+        idx = [int(f) for f in _as_list(frame_index, B, 'frame_index', 'index')]
+        if any(f < 0 for f in idx):
+            raise ValueError("frame_index must hold integers >= 0, got %r" % (idx,))
+        if images.device.type != 'cuda':
+            raise ValueError("images must be on the GPU (a CUDA / HIP tensor), got a %s tensor" % images.device.type)
+        dev = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        if images.device != dev:
+            raise ValueError("images is on %s, the augmenter's context on %s" % (images.device, dev))
+        tables = [self.lens.table(f) for f in idx]
+        with torch.cuda.device(dev):
+            if self._hip is None:
+                self._hip, self.device = hip_backend.RainHip(dev.index), dev
+            stream = torch.cuda.current_stream(dev)
+            if not stream.cuda_stream:           # handle 0 is "the context's own stream" to the library: finish the inputs first
+                stream.synchronize()
+            out, alpha = _lens_pass(self._hip, tables, self.lens.weights(), images.contiguous(), self.return_alpha, stream)
+        return (out, alpha) if self.return_alpha else out
 
     def close(self):
         if self._hip is not None:

@@ -55,6 +55,7 @@
 #include "rr_deflate.h"
 #include "rr_pngrows.h"
 #include "rr_particles.h"
+#include "rr_lens.h"
 
 using namespace rr;
 
@@ -5353,6 +5354,97 @@ __global__ void k_patch_counts(FrameDesc* frames, int n) {
   frames[f].n_drops = imax(imin(c, frames[f].n_drops), 0);
 }
 
+// ---- drops on the lens (rr_lens_drops_device; the arithmetic is rr_lens.h's) --------------------------------------
+struct LensTable {                   // head of a call's uploaded block: its blur table
+  float w[rrlens::MAX_CLASSES * rrlens::TAPS];
+  int32_t radius[rrlens::MAX_CLASSES];
+};
+constexpr int LENS_VW = rrlens::TILE + 2 * rrlens::MAX_RADIUS;     // a sub-tile with its halo: at most 62 x 62 samples
+
+// One workgroup per work item = one sub-tile (at most 32 x 32 outputs) of one drop's bounding box.  It evaluates the refracted
+// samples V of the sub-tile plus a halo of R once, all three channels, into LDS (46 KB); then, channel by channel, the row pass LDS ->
+// LDS (8 KB) and the column pass from LDS straight into the composite.  54 KB of LDS: two workgroups per compute unit.  The work
+// item, the drop's record and the class's weights are wave-uniform and read through the constant address space (an earlier kernel,
+// k_copy_small, wrote them): scalar loads.  Planes of odd width are misaligned: plain element loads and stores.  Reads `images`,
+// writes `out` (which holds a copy of `images`): pixels with A == 0 are skipped.
+template <bool F32>
+__global__ __launch_bounds__(256) void k_lens_drops(const void* images, void* out, float* alpha_out, const LensTable* table,
+                                                    const rr_lens_drop* drops, const rrlens::WorkItem* work, int H, int W) {
+  using T = std::conditional_t<F32, float, uint8_t>;
+  constexpr int TL = rrlens::TILE;
+  __shared__ float s_v[3][LENS_VW * LENS_VW];
+  __shared__ float s_r[LENS_VW * TL];
+  const const_ptr<rrlens::WorkItem> wp = as_constant(work) + blockIdx.x;
+  const int frame = wp->frame, tx = wp->tx, ty = wp->ty;
+  const const_ptr<rr_lens_drop> dp = as_constant(drops) + wp->drop;
+  rr_lens_drop d;
+  d.cx = dp->cx; d.cy = dp->cy; d.rx = dp->rx; d.ry = dp->ry;
+  d.mag = dp->mag; d.edge = dp->edge; d.rim = dp->rim; d.sigma_class = dp->sigma_class;
+  int bx0, bx1, by0, by1;
+  if (!rrlens::lens_box(d, W, H, bx0, bx1, by0, by1)) return;
+  const int ox = bx0 + tx * TL, oy = by0 + ty * TL;
+  const int tw = imin(TL, bx1 + 1 - ox), th = imin(TL, by1 + 1 - oy);
+  if (tx < 0 || ty < 0 || tw <= 0 || th <= 0) return;
+  const const_ptr<LensTable> tp = as_constant(table);
+  const int cls = imin(imax((int)d.sigma_class, 0), rrlens::MAX_CLASSES - 1);
+  const int R = imin(imax(tp->radius[cls], 0), rrlens::MAX_RADIUS);
+  const const_ptr<float> wt = tp->w + cls * rrlens::TAPS;
+  const int vw = tw + 2 * R, vh = th + 2 * R;
+  const double cx = d.cx, cy = d.cy, rx = d.rx, ry = d.ry, mag = d.mag;
+  const int64_t plane = (int64_t)H * W;
+  const global_ptr<const T> img = as_global(static_cast<const T*>(images)) + (int64_t)frame * 3 * plane;
+  const global_ptr<T> dst = as_global(static_cast<T*>(out)) + (int64_t)frame * 3 * plane;
+
+  for (int i = threadIdx.x; i < vw * vh; i += 256) {
+    const int hy = i / vw, hx = i - hy * vw;
+    const int qx = imin(imax(ox - R + hx, 0), W - 1), qy = imin(imax(oy - R + hy, 0), H - 1);     // the halo: q clamped to the frame
+    const double dx = (double)qx - cx, dy = (double)qy - cy;
+    const double g = rrlens::lens_gain(rrlens::lens_rho2(dx, dy, rx, ry));
+    int x0, x1, y0, y1;
+    float fx, fy;
+    rrlens::lens_sample_axis(cx, mag, dx, g, W, x0, x1, fx);
+    rrlens::lens_sample_axis(cy, mag, dy, g, H, y0, y1, fy);
+#pragma unroll
+    for (int c = 0; c < 3; c++) s_v[c][hy * LENS_VW + hx] = rrlens::lens_refract(img + c * plane, W, y0, y1, x0, x1, fx, fy);
+  }
+
+  // this thread's outputs: pixel threadIdx.x + 256 p of the sub-tile, two rows of 32 per wave
+  float A[4], rimf[4];
+  int64_t pix[4];
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    const int idx = (int)threadIdx.x + 256 * p, x = idx & (TL - 1), y = idx >> 5;
+    A[p] = 0.0f;
+    rimf[p] = 0.0f;
+    pix[p] = -1;
+    if (x < tw && y < th) {
+      const double r2 = rrlens::lens_rho2((double)(ox + x) - cx, (double)(oy + y) - cy, rx, ry);
+      A[p] = rrlens::lens_coverage(r2, (double)d.edge);
+      rimf[p] = rrlens::lens_rim((double)d.rim, r2);
+      pix[p] = (int64_t)(oy + y) * W + (ox + x);
+      if (alpha_out) as_global(alpha_out)[(int64_t)frame * plane + pix[p]] = A[p];
+    }
+  }
+  __syncthreads();
+
+  for (int c = 0; c < 3; c++) {
+    for (int i = threadIdx.x; i < vh * TL; i += 256) {
+      const int row = i >> 5, x = i & (TL - 1);
+      if (x < tw) s_r[row * TL + x] = rrlens::lens_blur_taps(&s_v[c][row * LENS_VW + x], 1, wt, R);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+      if (pix[p] < 0 || A[p] == 0.0f) continue;
+      const int idx = (int)threadIdx.x + 256 * p, x = idx & (TL - 1), y = idx >> 5;
+      const float B = rrlens::lens_blur_taps(&s_r[y * TL + x], TL, wt, R);
+      const float v = rrlens::lens_composite(A[p], rimf[p], B, (float)img[c * plane + pix[p]]);
+      dst[c * plane + pix[p]] = rrlens::lens_store(v, static_cast<T*>(nullptr));
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -5476,7 +5568,7 @@ struct rr_ctx {
     hipEvent_t ev[N] = {};
     bool used[N] = {};
     int next = 0;
-  } ring_frames, ring_pre, ring_sims, ring_noise;
+  } ring_frames, ring_pre, ring_sims, ring_noise, ring_lens;
   // last launch (for rr_synchronize bookkeeping)
   int last_n = 0;
   // host-pointer entry points: device staging per pipeline slot (slot 0 serves the synchronous calls)
@@ -5546,6 +5638,9 @@ struct rr_ctx {
   // grown to the largest batch seen, never shrunk
   char* d_aug = nullptr;
   size_t aug_bytes = 0;
+  // rr_lens_drops_device: the block a call uploads (blur table, drop records, work list), grown to the largest call seen
+  char* d_lens = nullptr;
+  size_t lens_bytes = 0;
 };
 
 namespace {
@@ -6921,6 +7016,7 @@ int rr_destroy(rr_ctx* ctx) {
   hipFree(ctx->d_omega);
   hipFree(ctx->d_omega32);
   hipFree(ctx->d_aug);
+  hipFree(ctx->d_lens);
   hipFree(ctx->d_dgrid);
   hipFree(ctx->d_cdf);
   hipFree(ctx->d_ratio_db);
@@ -6934,7 +7030,7 @@ int rr_destroy(rr_ctx* ctx) {
   for (void* b : ctx->noise_blocks) hipFree(b);
   hipFree(ctx->d_noise_desc);
   if (ctx->ev_noise) hipEventDestroy(ctx->ev_noise);
-  for (auto* r : {&ctx->ring_frames, &ctx->ring_pre, &ctx->ring_sims, &ctx->ring_noise})
+  for (auto* r : {&ctx->ring_frames, &ctx->ring_pre, &ctx->ring_sims, &ctx->ring_noise, &ctx->ring_lens})
     for (int k = 0; k < rr_ctx::DescRing::N; k++) {
       if (r->host[k]) hipHostFree(r->host[k]);
       if (r->ev[k]) hipEventDestroy(r->ev[k]);
@@ -8393,11 +8489,119 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   }
 }
 
+// images -> out, the upload, k_lens_drops, on `s` (see include/rainhip.h); every check comes before the first enqueue
+int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
+  const int n = b->n, H = b->H, W = b->W;
+  if (n <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32) || !b->images ||
+      !b->out || !b->counts || b->cap < 0 || (b->cap > 0 && !b->drops)) {
+    ctx->err = "rr_lens_drops_device: bad argument (sizes, dtype or a null pointer)";
+    return RR_E_ARG;
+  }
+  const size_t px = (size_t)H * W, el = b->dtype == RR_TENSOR_F32 ? 4 : 1;
+  const size_t img_bytes = (size_t)n * 3 * px * el, alpha_bytes = (size_t)n * px * sizeof(float);
+  auto overlap = [](const void* a, size_t na, const void* c, size_t nc) {
+    const uintptr_t a0 = (uintptr_t)a, c0 = (uintptr_t)c;
+    return a0 < c0 + nc && c0 < a0 + na;
+  };
+  if (overlap(b->images, img_bytes, b->out, img_bytes) ||
+      (b->alpha_out && (overlap(b->alpha_out, alpha_bytes, b->images, img_bytes) || overlap(b->alpha_out, alpha_bytes, b->out, img_bytes)))) {
+    ctx->err = "rr_lens_drops_device: out and alpha_out must not overlap images or each other (every drop refracts the input)";
+    return RR_E_ARG;
+  }
+  std::string why = rrlens::check_classes(b->n_classes, b->class_radius, b->weights);
+  if (!why.empty()) {
+    ctx->err = "rr_lens_drops_device: blur table: " + why;
+    return RR_E_ARG;
+  }
+  std::vector<rr_lens_drop> recs;
+  std::vector<rrlens::WorkItem> work;
+  std::vector<rrlens::Box> boxes;
+  for (int f = 0; f < n; f++) {
+    boxes.clear();
+    const rr_lens_drop* fd = b->cap > 0 ? b->drops + (size_t)f * b->cap : nullptr;
+    why = rrlens::check_frame(fd, b->counts[f], b->cap, b->n_classes, W, H, boxes);
+    if (!why.empty()) {
+      ctx->err = "rr_lens_drops_device: frame " + std::to_string(f) + ": " + why;
+      return RR_E_ARG;
+    }
+    for (const rrlens::Box& bx : boxes) {
+      rrlens::box_work(bx, f, (int32_t)recs.size(), work);
+      recs.push_back(fd[bx.drop]);
+    }
+  }
+  {
+    ProfScope ps(ctx, s, "lens_copy");
+    HIPCHK(hipMemcpyAsync(b->out, b->images, img_bytes, hipMemcpyDeviceToDevice, s));
+    if (b->alpha_out) HIPCHK(hipMemsetAsync(b->alpha_out, 0, alpha_bytes, s));
+  }
+  if (work.empty()) return RR_OK;
+  const size_t off_recs = sizeof(LensTable), off_work = off_recs + recs.size() * sizeof(rr_lens_drop);
+  const size_t bytes = off_work + work.size() * sizeof(rrlens::WorkItem);
+  if (bytes > ctx->lens_bytes) {
+    HIPCHK(hipDeviceSynchronize());
+    if (ctx->d_lens) HIPCHK(hipFree(ctx->d_lens));
+    ctx->d_lens = nullptr;
+    ctx->lens_bytes = 0;
+    const size_t want = bytes + bytes / 2;
+    HIPCHK(hipMalloc((void**)&ctx->d_lens, want));
+    ctx->lens_bytes = want;
+  }
+  int rc, ring_idx;
+  void* host;
+  if ((rc = ring_acquire(ctx, ctx->ring_lens, bytes, ring_idx, host))) return rc;
+  LensTable* tab = static_cast<LensTable*>(host);
+  memset(tab, 0, sizeof(LensTable));
+  for (int c = 0; c < b->n_classes; c++) {
+    tab->radius[c] = b->class_radius[c];
+    memcpy(tab->w + c * rrlens::TAPS, b->weights + c * rrlens::TAPS, sizeof(float) * (size_t)(2 * b->class_radius[c] + 1));
+  }
+  memcpy(static_cast<char*>(host) + off_recs, recs.data(), recs.size() * sizeof(rr_lens_drop));
+  memcpy(static_cast<char*>(host) + off_work, work.data(), work.size() * sizeof(rrlens::WorkItem));
+  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_lens),
+                     (int)(bytes / 4));
+  if ((rc = ring_commit(ctx, ctx->ring_lens, ring_idx, s))) return rc;
+  {
+    ProfScope ps(ctx, s, "k_lens_drops");
+    const LensTable* d_tab = reinterpret_cast<const LensTable*>(ctx->d_lens);
+    const rr_lens_drop* d_recs = reinterpret_cast<const rr_lens_drop*>(ctx->d_lens + off_recs);
+    const rrlens::WorkItem* d_work = reinterpret_cast<const rrlens::WorkItem*>(ctx->d_lens + off_work);
+    if (el == 4)
+      hipLaunchKernelGGL(k_lens_drops<true>, dim3((unsigned)work.size()), dim3(256), 0, s, b->images, b->out, b->alpha_out, d_tab, d_recs, d_work, H, W);
+    else
+      hipLaunchKernelGGL(k_lens_drops<false>, dim3((unsigned)work.size()), dim3(256), 0, s, b->images, b->out, b->alpha_out, d_tab, d_recs, d_work, H, W);
+  }
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int rr_sizeof_tensor_batch(void) { return (int)sizeof(rr_tensor_batch); }
+int rr_sizeof_lens_drop(void) { return (int)sizeof(rr_lens_drop); }
+int rr_sizeof_lens_batch(void) { return (int)sizeof(rr_lens_batch); }
+
+int rr_lens_drops_device(rr_ctx* ctx, const rr_lens_batch* b, void* stream) {
+  if (!ctx) return RR_E_ARG;
+  if (!b) {
+    ctx->err = "rr_lens_drops_device: null batch";
+    return RR_E_ARG;
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  struct Restore {                     // the caller's current device, whatever way the call ends
+    int d;
+    ~Restore() {
+      if (d >= 0) (void)hipSetDevice(d);
+    }
+  } restore{prev};
+  HIPCHK(hipSetDevice(ctx->device));
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const int rc = lens_drops(ctx, b, s);
+  if (rc || !stream) (void)hipStreamSynchronize(s);      // (NULL: the caller has no handle to order later work behind the context's stream)
+  return rc;
+}
 
 int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream) {
   if (!ctx) return RR_E_ARG;

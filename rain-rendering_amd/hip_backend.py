@@ -148,6 +148,18 @@ class rr_tensor_batch(ctypes.Structure):
                 ('mask_out', ctypes.c_void_p)]
 
 
+RR_MAX_LENS_DROPS = 128
+LENS_DROP_DTYPE = np.dtype([('cx', '<f4'), ('cy', '<f4'), ('rx', '<f4'), ('ry', '<f4'), ('mag', '<f4'), ('edge', '<f4'), ('rim', '<f4'),
+                            ('sigma_class', '<f4')])                     # rr_lens_drop
+
+
+class rr_lens_batch(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                ('images', ctypes.c_void_p), ('out', ctypes.c_void_p), ('alpha_out', ctypes.c_void_p), ('counts', ctypes.c_void_p),
+                ('drops', ctypes.c_void_p), ('cap', ctypes.c_int32), ('n_classes', ctypes.c_int32), ('class_radius', ctypes.c_void_p),
+                ('weights', ctypes.c_void_p)]
+
+
 EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_streak_db', 'rr_set_streak_db_device',
            'rr_set_camera', 'rr_render_frames', 'rr_render_frames_device', 'rr_synchronize', 'rr_profile_enable',
            'rr_profile_reset', 'rr_profile_read', 'rr_sizeof_drop', 'rr_sizeof_camera', 'rr_sizeof_frame_in',
@@ -160,7 +172,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
-           'rr_sizeof_traj_pose']
+           'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch']
 
 _lib = None
 
@@ -269,6 +281,9 @@ def load_library(path=None):
     assert lib.rr_sizeof_traj_pose() == TRAJ_POSE_DTYPE.itemsize == 192, (lib.rr_sizeof_traj_pose(), TRAJ_POSE_DTYPE.itemsize)
     assert lib.rr_sizeof_sim_frame() == SIM_FRAME_DTYPE.itemsize, (lib.rr_sizeof_sim_frame(), SIM_FRAME_DTYPE.itemsize)
     assert lib.rr_sizeof_tensor_batch() == ctypes.sizeof(rr_tensor_batch), (lib.rr_sizeof_tensor_batch(), ctypes.sizeof(rr_tensor_batch))
+    lib.rr_lens_drops_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_lens_batch), ctypes.c_void_p]
+    assert lib.rr_sizeof_lens_drop() == LENS_DROP_DTYPE.itemsize == 32, (lib.rr_sizeof_lens_drop(), LENS_DROP_DTYPE.itemsize)
+    assert lib.rr_sizeof_lens_batch() == ctypes.sizeof(rr_lens_batch), (lib.rr_sizeof_lens_batch(), ctypes.sizeof(rr_lens_batch))
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
     assert lib.rr_sizeof_prepass_out() == ctypes.sizeof(rr_prepass_out)
     assert lib.rr_sizeof_prepass_kernels() == ctypes.sizeof(rr_prepass_kernels)
@@ -1222,6 +1237,31 @@ class RainHip:
         and the fog constants).  Returns once the batch is complete on `stream` (augment.RainAugment is the user-facing form)."""
         self._check(self.lib.rr_augment_frames_device(self.h, ctypes.byref(batch), ctypes.c_void_p(stream) if stream else None),
                     'rr_augment_frames_device')
+
+    def lens_drops_device(self, images_ptr, out_ptr, n, H, W, f32, tables, weights, alpha_ptr=None, stream=None):
+        """rr_lens_drops_device: drops on the lens of the n planar [3, H, W] images at DEVICE pointer images_ptr (float32 when f32, else
+        bytes) into out_ptr, and their coverage into alpha_ptr ([n, H, W] float32) when given.  `tables`: n arrays of LENS_DROP_DTYPE
+        records (tools/lens.py LensDrops.table), `weights`: the blur table (class_radius, float32 [16, 31]; LensDrops.weights()).
+        Enqueued on `stream`; without one the call waits for the context's own stream."""
+        if len(tables) != n:
+            raise ValueError("%d drop tables for %d images" % (len(tables), n))
+        radius = np.ascontiguousarray(weights[0], np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights[1], np.float32)
+        if w.shape != (16, 31):
+            raise ValueError("the blur table's weights must be float32 [16, 31], got %s" % (w.shape,))
+        tabs = [np.ascontiguousarray(t, LENS_DROP_DTYPE).reshape(-1) for t in tables]
+        counts = np.array([len(t) for t in tabs], np.int32)
+        cap = max(1, int(counts.max()))
+        drops = np.zeros((n, cap), LENS_DROP_DTYPE)
+        for f, t in enumerate(tabs):
+            drops[f, :len(t)] = t
+        b = rr_lens_batch()
+        b.n, b.H, b.W, b.dtype = n, H, W, RR_TENSOR_F32 if f32 else RR_TENSOR_U8
+        b.images, b.out, b.alpha_out = images_ptr, out_ptr, alpha_ptr
+        b.counts, b.drops, b.cap = counts.ctypes.data, drops.ctypes.data, cap
+        b.n_classes, b.class_radius, b.weights = len(radius), radius.ctypes.data, w.ctypes.data
+        self._check(self.lib.rr_lens_drops_device(self.h, ctypes.byref(b), ctypes.c_void_p(stream) if stream else None),
+                    'rr_lens_drops_device')
 
     def synchronize(self):
         """Returns True if the batch completed, False if the tile arena had to be regrown
