@@ -560,7 +560,9 @@ int rr_set_particle_rate_series(rr_ctx* ctx, int32_t n, uint32_t frame0, const d
  * Scratch in the context, grown to the largest batch seen and never shrunk, per frame about
  *     3 H W (bytes; 12 H W for float32) + 12 H W (fog layer) + 12 H We (map) + 8 H W (mask) + 112 drops_cap  bytes
  * (KITTI 1242 x 375 with bytes: about 23 MB per frame) on top of the hot path's own per-batch scratch. */
-enum { RR_TENSOR_U8 = 0, RR_TENSOR_F32 = 1 };
+enum { RR_TENSOR_U8 = 0, RR_TENSOR_F32 = 1,
+       RR_TENSOR_U8_HWC = 3 };           /* interleaved bytes [n,H,W,3]: rr_lens_batch.dtype only (rr_augment_frames_device refuses it).
+                                          * 2 names no layout and stays refused everywhere, as it was before this layout existed */
 typedef struct {
   int32_t n, H, W, dtype;                /* dtype: RR_TENSOR_*; images and rainy_out share it */
   const void* images;                    /* DEVICE, [n,3,H,W] planar RGB, contiguous: bytes, or float32 in [0,1] */
@@ -626,6 +628,38 @@ typedef struct {
 int rr_lens_drops_device(rr_ctx* ctx, const rr_lens_batch* b, void* stream);
 int rr_sizeof_lens_drop(void);
 int rr_sizeof_lens_batch(void);
+/* rr_lens_batch.dtype == RR_TENSOR_U8_HWC: images and out are [n,H,W,3] interleaved bytes (pixel p's channel c at byte 3 p + c, the
+ * layout of rr_frame_out.rainy_rgb); alpha_out stays float32 [n,H,W].  The same arithmetic, byte for byte what RR_TENSOR_U8 gives on
+ * the transposed planes.
+ *
+ * Drops on the lens inside the frame pipeline.  rr_pipeline_set_lens ARMS a pipeline slot: every batch submitted on it
+ * afterwards (rr_pipeline_submit; slot 0 also serves rr_pipeline_frames and rr_render_frames) runs the lens pass between the
+ * finalize kernel and the PNG rows, so rainy_rgb and rainy_png carry the drops of frame f's table.  rainy_bg_out, mask_f64, mask_i32,
+ * mask_png, drop_status and drop_colour are what they are without it: the streak mask knows nothing of the lens.  The armed state stays
+ * on the slot until it is replaced or disarmed (lens == NULL), and EVERY submit on the slot applies it once -- the re-submit after
+ * RR_E_ARENA included, so the batch that is submitted again gets its drops once, not twice.
+ *   counts, drops, class_radius, weights   HOST pointers with the meaning and the checks of rr_lens_batch; copied before the call returns
+ *   alpha_png     NULL, or n HOST pointers, each NULL or a buffer of H * (1 + 4 W) bytes that receives the frame's LABEL file the way
+ *                 mask_png receives the mask file: PNG scanlines (filter Sub) of RGBA pixels R = G = B = v, alpha 255, with
+ *                 v = clamp(rint(A * 255.0f)) (half to even; A the coverage, 0 outside the drops) -- or, under RR_OPT_PNG_DEFLATE, the
+ *                 finished zlib stream behind the 16-byte header (same rule, same fallback).  The buffers must stay valid until
+ *                 rr_pipeline_wait of every batch submitted while the slot is armed with them.
+ * Device memory of an armed slot, allocated by the call and kept: n H W 4 bytes (the un-dropped copy of the frames and the label
+ * plane) plus n H (1 + 4 W) for the label's scanlines when alpha_png asks for them.
+ * RR_E_ARG, with nothing changed: a bad slot, n, H or W <= 0, a null table, or any table error of rr_lens_drops_device's list.
+ * RR_E_STATE: the slot is in flight.  rr_pipeline_submit on an armed slot returns RR_E_ARG with nothing enqueued when the batch's n, H
+ * or W are not the armed ones or when the batch renders nothing (in == NULL; rr_prepass_frames runs on slot 0). */
+typedef struct {
+  int32_t n, H, W, cap;
+  const int32_t* counts;                 /* HOST, n drop counts */
+  const rr_lens_drop* drops;             /* HOST, n x cap records */
+  int32_t n_classes, reserved;
+  const int32_t* class_radius;           /* HOST */
+  const float* weights;                  /* HOST, 16 x 31 float32 */
+  uint8_t* const* alpha_png;             /* NULL, or n HOST pointers (each may be NULL) */
+} rr_pipeline_lens;
+int rr_pipeline_set_lens(rr_ctx* ctx, int32_t slot, const rr_pipeline_lens* lens);
+int rr_sizeof_pipeline_lens(void);
 
 /* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
  * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does

@@ -39,6 +39,8 @@ def _cpu_budget():
 
 
 class Generator:
+    lens_spec, lens_alpha, _lens = None, False, None             # --lens_drops / --lens_alpha: off unless __init__ / run() say otherwise
+
     def __init__(self, args):
         self.conflict_strategy = args.conflict_strategy
         self.rendering_strategy = args.rendering_strategy
@@ -150,6 +152,13 @@ class Generator:
         if self.streak_jitter and bool(self.noise_std):
             raise ValueError("--streak_jitter cannot be combined with --noise_std: the jitter is a function of the drop, the angular "
                              "noise of the order of the run")
+        # --lens_drops SPEC: adherent drops on the lens (tools/lens.py LensDrops.from_spec), made per run at the rendered
+        # frame size; --lens_alpha: their per-pixel label as a third file per frame
+        self.lens_spec = getattr(args, 'lens_drops', None)
+        self.lens_alpha = bool(getattr(args, 'lens_alpha', False))
+        if self.lens_alpha and self.lens_spec is None:
+            raise ValueError("--lens_alpha needs --lens_drops")
+        self._lens = None                                        # the current run's LensDrops (run())
         self.sim_options = getattr(args, 'sim_options', {})
         self.batch = int(os.environ.get('RAIN_BATCH', '128'))     # frames per library call (three calls in flight); bench.py's host-inclusive leg uses the same
         self.rank, self.world = sharding.rank_world()
@@ -256,9 +265,9 @@ class Generator:
         Every array is one page-locked block with the frames back to back, each on a 16-byte boundary (RainHip.host_rows):
         the library then moves an array of the whole batch with ONE copy instead of one DMA request per frame."""
 
-        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False):
+        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False):
             """png_rows: the image / depth blocks hold the files' filtered scanlines (rr_io_read_frames_rows: H rows of 1 + 3 W /
-            1 + 2 W bytes per frame) instead of pixels."""
+            1 + 2 W bytes per frame) instead of pixels.  lens_alpha: a third scanline block, the label file of --lens_alpha."""
             self.B, self.H, self.W = B, H, W
             self._raw = []
 
@@ -277,6 +286,9 @@ class Generator:
             # the blocks themselves ((B, stride) bytes): what the library's batch I/O calls address
             self.raw_bg, self.raw_depth, self.raw_drops, _, self.raw_png_i, self.raw_png_m = self._raw[:6]
             self.env = rows((H, We, 3), np.uint8) if save_envmap else None
+            self.png_a = rows((row,), np.uint8) if lens_alpha else None
+            self.raw_png_a = self._raw[-1] if lens_alpha else None
+            self.lens_alpha = bool(lens_alpha)
             self.drops_cap = drops_cap
             self.key = (B, H, W, We, 'png rows' if png_rows else np.dtype(bg_dtype), 'png rows' if png_rows else np.dtype(depth_dtype), bool(save_envmap))
             self.items, self.encodes, self.busy = [], [], False
@@ -286,8 +298,8 @@ class Generator:
             """Page-locked memory is only returned by rr_host_free (dropping the numpy views frees nothing): called when
             a slot is replaced by a larger / differently shaped one, after its batch has been collected and encoded."""
             assert not self.busy and not self.encodes
-            self.bg = self.depth = self.drops = self.status = self.png_i = self.png_m = self.env = None
-            self.raw_bg = self.raw_depth = self.raw_drops = self.raw_png_i = self.raw_png_m = None
+            self.bg = self.depth = self.drops = self.status = self.png_i = self.png_m = self.env = self.png_a = None
+            self.raw_bg = self.raw_depth = self.raw_drops = self.raw_png_i = self.raw_png_m = self.raw_png_a = None
             self.prep = None
             for raw in self._raw:
                 hip.host_free(raw)
@@ -309,6 +321,9 @@ class Generator:
         os.makedirs(os.path.dirname(item['out_rainy_mask_path']), exist_ok=True)
         imgops.png_from_scanlines(item['out_rainy_path'], slot.png_i[k], W, H)        # generator.py:466
         imgops.png_from_scanlines(item['out_rainy_mask_path'], slot.png_m[k], W, H)   # generator.py:467
+        if self.lens_alpha:
+            os.makedirs(os.path.dirname(item['out_lens_alpha_path']), exist_ok=True)
+            imgops.png_from_scanlines(item['out_lens_alpha_path'], slot.png_a[k], W, H)
         if self.save_envmap:
             os.makedirs(os.path.dirname(item['out_env_path']), exist_ok=True)
             env_bgr = slot.env[k] / 255.0                                              # generator.py:469 (plt.imsave of a float map)
@@ -401,6 +416,8 @@ class Generator:
                         out_rainy_path=os.path.join(out_dir, 'rainy_image', '{}.png'.format(file_name[:-4])),
                         out_rainy_mask_path=os.path.join(out_dir, 'rain_mask', '{}.png'.format(file_name[:-4])),
                         out_env_path=os.path.join(out_seq_dir, 'envmap', '{}.png'.format(file_name[:-4])))
+            if self.lens_alpha:                                  # (the skip rule below stays the reference's: rainy or mask file)
+                item['out_lens_alpha_path'] = os.path.join(out_dir, 'lens_alpha', '{}.png'.format(file_name[:-4]))
             if os.path.exists(item['out_rainy_path']) or os.path.exists(item['out_rainy_mask_path']):
                 if self.conflict_strategy == "skip":
                     frames_exist_nb += 1
@@ -428,6 +445,29 @@ class Generator:
         if self.dataset == 'nuscenes':
             return int(np.linspace(0, n_sim, n_files, endpoint=False, dtype=int)[i])
         return i
+
+    def _make_lens(self, imH, imW):
+        """--lens_drops: the run's LensDrops at the rendered frame size and the dataset's frame rate; under --particle_model rig the
+        drops on the lens of the run's own view.  None without the flag."""
+        if self.lens_spec is None:
+            return None
+        from ..tools.lens import LensDrops
+        L = self.lens_spec if isinstance(self.lens_spec, LensDrops) else \
+            LensDrops.from_spec(self.lens_spec, int(imH), int(imW), float(self.settings["cam_hz"]))
+        if (L.H, L.W) != (int(imH), int(imW)):
+            raise ValueError("--lens_drops: drops made for %d x %d frames, the run renders %d x %d" % (L.H, L.W, imH, imW))
+        return L.for_view(self.rig_view) if self.particle_model == 'rig' else L
+
+    def _lens_tables(self, items):
+        """The drop tables of a batch's frames in slot order: frame i of the sequence (the work item's i) wears L.table(i)."""
+        return [self._lens.table(int(it['i'])) for it in items]
+
+    def _arm_lens(self, hip, si, sl, tables):
+        """Before a batch is submitted on slot si: its frames' drop tables (rr_pipeline_set_lens), the label buffers with --lens_alpha."""
+        if self._lens is None:
+            return
+        hip.pipeline_set_lens(si, tables, self._lens.weights(), sl.H, sl.W,
+                              alpha_png=[sl.png_a[k] for k in range(len(tables))] if self.lens_alpha else None)
 
     def _mark(self, name):
         """set-up clock: seconds since run() began at which a stage of the set-up was finished (timing[...]['setup'])"""
@@ -460,6 +500,7 @@ class Generator:
                     raise Exception("Invalid extension", im)
                 rs = self.settings["render_scale"]
                 imH, imW = imH // rs, imW // rs
+                self._lens = self._make_lens(imH, imW)
 
                 print('Simulation: rain {}mm/hr'.format(fallrate))
                 self.db = DBManager(streaks_path_xml=sim_file, streaks_path=self.texture, norm_coeff_path=self.norm_coeff)
@@ -661,8 +702,9 @@ class Generator:
         # are reversed on the device (k_png_unfilter), 40 % of the host's decode time.  RAIN_PNG_ROWS=0: pixels decoded by the host.
         rows_in = u8 and os.environ.get('RAIN_PNG_ROWS', '1') != '0'
         key = (B, H, W, env_w, 'png rows' if rows_in else np.dtype(bg_dtype), 'png rows' if rows_in else np.dtype(depth_dtype), False)
+        lens_alpha = self._lens is not None and self.lens_alpha
         pkey = (tuple(float(v) for v in fog_const), float(self.opacity_attenuation), self.rendering_strategy, sims is not None)
-        for d in {os.path.dirname(it[k]) for it in work for k in ('out_rainy_path', 'out_rainy_mask_path')}:
+        for d in {os.path.dirname(it[k]) for it in work for k in ('out_rainy_path', 'out_rainy_mask_path') + (('out_lens_alpha_path',) if lens_alpha else ())}:
             os.makedirs(d, exist_ok=True)
         encodes = [None] * nslot                                 # the slot's encode job (future) and its frames
         done = [0]
@@ -670,13 +712,13 @@ class Generator:
         pending = {}                                             # slots being page-locked by the helper thread (see below)
 
         def new_slot():
-            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in)
+            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha)
 
         def slot_for(si):
             if si in pending:
                 slots[si] = pending.pop(si).result()
             sl = slots[si]
-            if sl is None or sl.key != key or sl.drops_cap < drops_cap:
+            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha):
                 if sl is not None:
                     sl.free(hip)
                 sl = slots[si] = new_slot()
@@ -751,6 +793,8 @@ class Generator:
             # (rr_host_pack_frames stores at most drops_cap records and reports the full count)
             assert int(counts.max(initial=0)) <= sl.drops_cap, \
                 "Assert that the number of drops doesn't overpass the uint16 rain_mask capacity"       # generator.py:424
+            if self._lens is not None:                          # the frames' lens drops, in slot order (gaps closed like the inputs)
+                sl.lens_tables = self._lens_tables([items[k] for k in order])
             return [items[k] for k in order], [int(counts[k]) for k in order]
 
         def encode_job(sl, items, nds, gpu_ms):
@@ -759,6 +803,11 @@ class Generator:
             if st.any():
                 bad = int(np.nonzero(st)[0][0])
                 raise IOError("could not write %s / %s (%d)" % (items[bad]['out_rainy_path'], items[bad]['out_rainy_mask_path'], st[bad]))
+            if lens_alpha:                                      # the label files: the same call, one file per frame
+                st = hip_backend.io_write_frames([it['out_lens_alpha_path'] for it in items], None, sl.raw_png_a, None, W, H, threads)
+                if st.any():
+                    bad = int(np.nonzero(st)[0][0])
+                    raise IOError("could not write %s (%d)" % (items[bad]['out_lens_alpha_path'], st[bad]))
             return [dict(file=it['out_rainy_path'], drops=nd, skipped=int(np.count_nonzero(sl.status[k][:nd])), gpu_ms=gpu_ms)
                     for k, (it, nd) in enumerate(zip(items, nds))]
 
@@ -799,7 +848,7 @@ class Generator:
         maker = None
         for si in range(1, min(nslot, len(batches))):
             sl = slots[si]
-            if sl is None or sl.key != key or sl.drops_cap < drops_cap:
+            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha):
                 if sl is not None:
                     sl.free(hip)
                     slots[si] = None
@@ -831,6 +880,7 @@ class Generator:
                     else:
                         sl.prep.set_drop_count(k, nd)
                 sl.t_submit = time.time()
+                self._arm_lens(hip, si, sl, getattr(sl, 'lens_tables', None))
                 hip.pipeline_submit_prepared(si, sl.prep, sl.n_valid)
                 if bi == 0:
                     self._mark('first batch submitted')
@@ -842,7 +892,7 @@ class Generator:
             if bi + 1 < len(batches):                            # and decode the next one into the slot that is idle now
                 sn = (bi + 1) % nslot
                 finish(sn)
-                if slots[sn] is not None and (slots[sn].key != key or slots[sn].drops_cap < drops_cap):
+                if slots[sn] is not None and (slots[sn].key != key or slots[sn].drops_cap < drops_cap or (lens_alpha and not slots[sn].lens_alpha)):
                     drain(sn)                                    # (a slot of another shape is replaced: its encoders first)
                 decoding = stage.submit(decode_job, slot_for(sn), batches[bi + 1])
             if self.verbose:
@@ -940,11 +990,12 @@ class Generator:
             need_drops = max(len(ld[2]) for _, ld in valid)
             key = (B, H, W, state['env_w'], bg0.dtype, dep0.dtype, bool(self.save_envmap))
             sl = slots[si]
-            if sl is None or sl.key != key or sl.drops_cap < need_drops:
+            lens_alpha = self._lens is not None and self.lens_alpha
+            if sl is None or sl.key != key or sl.drops_cap < need_drops or (lens_alpha and not sl.lens_alpha):
                 if sl is not None:                               # (finish / drain above left it idle)
                     sl.free(hip)
                 sl = slots[si] = Generator._Slot(hip, B, H, W, state['env_w'], bg0.dtype, dep0.dtype, self.save_envmap,
-                                                 max(need_drops + need_drops // 4, 1024))
+                                                 max(need_drops + need_drops // 4, 1024), lens_alpha=lens_alpha)
             # the batch's descriptors are made once per slot (the buffers do not move) and for the run's constants
             pkey = (tuple(float(v) for v in fog_const), float(self.opacity_attenuation), self.rendering_strategy)
             if getattr(sl, 'prep', None) is None or sl.pkey != pkey:
@@ -970,6 +1021,8 @@ class Generator:
                 sl.items.append((it, nd))
             sl.n_valid = len(valid)
             sl.t_submit = time.time()
+            if self._lens is not None:                           # the frames' lens drops, in slot order (skipped frames leave no gap)
+                self._arm_lens(hip, si, sl, self._lens_tables([it for it, _ in valid]))
             hip.pipeline_submit_prepared(si, sl.prep, sl.n_valid)
             if t_first is None:
                 t_first = time.time()                            # set-up (pinned buffers, first decodes) ends here

@@ -29,8 +29,10 @@
 //     k_bin_rows (k_bin: frames wider than 4096 px), [k_pad_visits], k_composite32 (k_composite: float64 colours)
 //                      ordered per-tile drop lists (ballot compaction, no atomics); float64 mask in drop order, float
 //                      (or float64) colours, tile sums
-//     k_means, k_finalize16 (k_finalize: a float or float64 composite), [k_png_image, k_png_mask, k_pngz_blocks, k_pngz_pack]
-//                      mean-contrast shift, clip, truncating u8 quantisation; optional PNG scanlines / zlib streams
+//     k_means, k_finalize16 (k_finalize: a float or float64 composite), [k_lens_drops_hwc], [k_png_image, k_png_mask, k_png_alpha,
+//     k_pngz_blocks, k_pngz_pack]
+//                      mean-contrast shift, clip, truncating u8 quantisation; optional drops on the lens (a pipeline slot armed with
+//                      rr_pipeline_set_lens); optional PNG scanlines / zlib streams
 //   elsewhere: k_particles / k_field_particles / k_particle_draws (drop tables born on the device), k_png_unfilter (input files' scanlines),
 //   k_pad_textures, k_pair_textures, k_copy_pieces / k_copy_small (batched copies, descriptors)
 // rr_prepass.h holds the fog / environment-map pre-pass kernels, rr_host.cpp the host-only helpers.
@@ -4523,13 +4525,34 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t* rows_base, i
 // k_pngz_blocks: one workgroup of 512 threads per 32 KB block of a file's scanlines (grid: blocks x files; file = 2 * frame +
 // {image, mask}); its working set (the block, its compressed form, the code tables: 76 KB) is dynamic LDS.  The compressed block goes to the
 // block's slot in the scratch, its size and Adler-32 sums to its record.
-__global__ __launch_bounds__(512) void k_pngz_blocks(const FrameDesc* frames, int64_t n_bytes, int nb, uint8_t* slots, rrz::BlockMeta* meta) {
+// KINDS (a slot armed with rr_pipeline_set_lens that writes the label): 3 = file = 3 * frame + {image, mask, label}, the
+// label's scanlines (k_png_alpha) at label.rows + frame * label.stride.  KINDS = 2 is the kernel as it was: the argument is an empty
+// struct behind every other one, like WindArgs<false>.
+template <int KINDS>
+struct PngzLabel {};
+template <>
+struct PngzLabel<3> {
+  uint8_t* rows;
+  int64_t stride;
+};
+template <int KINDS>
+__device__ inline uint8_t* pngz_rows(const FrameDesc* frames, int file, const PngzLabel<KINDS>& label) {
+  if constexpr (KINDS == 3) {
+    const int f = file / 3, kind = file - 3 * f;
+    return kind == 2 ? label.rows + (int64_t)f * label.stride : (kind == 1 ? frames[f].png_mask : frames[f].png_image);
+  } else {
+    const FrameDesc& fr = frames[file >> 1];
+    return (file & 1) ? fr.png_mask : fr.png_image;
+  }
+}
+template <int KINDS>
+__global__ __launch_bounds__(512) void k_pngz_blocks(const FrameDesc* frames, int64_t n_bytes, int nb, uint8_t* slots, rrz::BlockMeta* meta,
+                                                     PngzLabel<KINDS> label) {
   using namespace rrz;
   extern __shared__ __attribute__((aligned(16))) uint8_t pngz_lds[];
   BlockState& S = *reinterpret_cast<BlockState*>(pngz_lds);
   const int file = blockIdx.y, k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const FrameDesc& fr = frames[file >> 1];
-  const uint8_t* rows = (file & 1) ? fr.png_mask : fr.png_image;
+  const uint8_t* rows = pngz_rows<KINDS>(frames, file, label);
   if (!rows) return;
   const int64_t at = (int64_t)k * BLOCK;
   const int len = (int)(n_bytes - at < BLOCK ? n_bytes - at : BLOCK), last = k == nb - 1;
@@ -4643,11 +4666,12 @@ __global__ __launch_bounds__(512) void k_pngz_blocks(const FrameDesc* frames, in
 // k_pngz_pack: the blocks of a file behind each other in the file's scanline buffer, in front of them the 16-byte header and
 // the zlib header, behind them the Adler-32 -- if all of it fits the buffer; else the scanlines stay (every workgroup of the
 // file reaches the same verdict from the same records).
-__global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int64_t n_bytes, int nb, const uint8_t* slots, const rrz::BlockMeta* meta) {
+template <int KINDS>
+__global__ __launch_bounds__(256) void k_pngz_pack(const FrameDesc* frames, int64_t n_bytes, int nb, const uint8_t* slots, const rrz::BlockMeta* meta,
+                                                   PngzLabel<KINDS> label) {
   using namespace rrz;
   const int file = blockIdx.y, k = blockIdx.x, tid = threadIdx.x;
-  const FrameDesc& fr = frames[file >> 1];
-  uint8_t* rows = (file & 1) ? fr.png_mask : fr.png_image;
+  uint8_t* rows = pngz_rows<KINDS>(frames, file, label);
   if (!rows) return;
   const BlockMeta* fm = meta + (int64_t)file * nb;
   __shared__ int64_t s_total, s_off;
@@ -5445,6 +5469,120 @@ __global__ __launch_bounds__(256) void k_lens_drops(const void* images, void* ou
   }
 }
 
+// k_lens_drops for interleaved bytes: frame f's pixel p, channel c at byte 3 p + c of images + f * img_stride, the
+// layout of the frame pipeline's rainy_rgb and of RR_TENSOR_U8_HWC.  The same chain as above, step for step -- rr_lens.h's functions in
+// the same order, the same LDS (54 064 bytes static), the same scalar reads -- only the addressing differs: a refracted sample reads the
+// three bytes of each of its four neighbours, and a thread keeps its pixel's three channel results and stores them as three adjacent
+// bytes once the last channel's column pass is done (the channel loop is split by barriers; one visit of the pixel's line instead of
+// three).  LABEL: `alpha` is a byte plane [n][H][W] that receives lens_round_u8(A * 255.0f) inside the boxes (the pipeline's label,
+// cleared before); else it is the float32 plane of rr_lens_batch.alpha_out or NULL.
+template <bool LABEL>
+__global__ __launch_bounds__(256) void k_lens_drops_hwc(const uint8_t* images, int64_t img_stride, uint8_t* out, int64_t out_stride, void* alpha,
+                                                        const LensTable* table, const rr_lens_drop* drops, const rrlens::WorkItem* work, int H, int W) {
+  constexpr int TL = rrlens::TILE;
+  __shared__ float s_v[3][LENS_VW * LENS_VW];
+  __shared__ float s_r[LENS_VW * TL];
+  const const_ptr<rrlens::WorkItem> wp = as_constant(work) + blockIdx.x;
+  const int frame = wp->frame, tx = wp->tx, ty = wp->ty;
+  const const_ptr<rr_lens_drop> dp = as_constant(drops) + wp->drop;
+  rr_lens_drop d;
+  d.cx = dp->cx; d.cy = dp->cy; d.rx = dp->rx; d.ry = dp->ry;
+  d.mag = dp->mag; d.edge = dp->edge; d.rim = dp->rim; d.sigma_class = dp->sigma_class;
+  int bx0, bx1, by0, by1;
+  if (!rrlens::lens_box(d, W, H, bx0, bx1, by0, by1)) return;
+  const int ox = bx0 + tx * TL, oy = by0 + ty * TL;
+  const int tw = imin(TL, bx1 + 1 - ox), th = imin(TL, by1 + 1 - oy);
+  if (tx < 0 || ty < 0 || tw <= 0 || th <= 0) return;
+  const const_ptr<LensTable> tp = as_constant(table);
+  const int cls = imin(imax((int)d.sigma_class, 0), rrlens::MAX_CLASSES - 1);
+  const int R = imin(imax(tp->radius[cls], 0), rrlens::MAX_RADIUS);
+  const const_ptr<float> wt = tp->w + cls * rrlens::TAPS;
+  const int vw = tw + 2 * R, vh = th + 2 * R;
+  const double cx = d.cx, cy = d.cy, rx = d.rx, ry = d.ry, mag = d.mag;
+  const int64_t plane = (int64_t)H * W;
+  const global_ptr<const uint8_t> img = as_global(images) + (int64_t)frame * img_stride;
+  const global_ptr<uint8_t> dst = as_global(out) + (int64_t)frame * out_stride;
+
+  for (int i = threadIdx.x; i < vw * vh; i += 256) {
+    const int hy = i / vw, hx = i - hy * vw;
+    const int qx = imin(imax(ox - R + hx, 0), W - 1), qy = imin(imax(oy - R + hy, 0), H - 1);     // the halo: q clamped to the frame
+    const double dx = (double)qx - cx, dy = (double)qy - cy;
+    const double g = rrlens::lens_gain(rrlens::lens_rho2(dx, dy, rx, ry));
+    int x0, x1, y0, y1;
+    float fx, fy;
+    rrlens::lens_sample_axis(cx, mag, dx, g, W, x0, x1, fx);
+    rrlens::lens_sample_axis(cy, mag, dy, g, H, y0, y1, fy);
+    const int64_t a00 = ((int64_t)y0 * W + x0) * 3, a01 = ((int64_t)y0 * W + x1) * 3, a10 = ((int64_t)y1 * W + x0) * 3, a11 = ((int64_t)y1 * W + x1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      s_v[c][hy * LENS_VW + hx] = rrlens::lens_bilinear((float)img[a00 + c], (float)img[a01 + c], (float)img[a10 + c], (float)img[a11 + c], fx, fy);
+  }
+
+  // this thread's outputs: pixel threadIdx.x + 256 p of the sub-tile, two rows of 32 per wave
+  float A[4], rimf[4];
+  int64_t pix[4];
+  uint8_t res[4][3];
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    const int idx = (int)threadIdx.x + 256 * p, x = idx & (TL - 1), y = idx >> 5;
+    A[p] = 0.0f;
+    rimf[p] = 0.0f;
+    pix[p] = -1;
+    if (x < tw && y < th) {
+      const double r2 = rrlens::lens_rho2((double)(ox + x) - cx, (double)(oy + y) - cy, rx, ry);
+      A[p] = rrlens::lens_coverage(r2, (double)d.edge);
+      rimf[p] = rrlens::lens_rim((double)d.rim, r2);
+      pix[p] = (int64_t)(oy + y) * W + (ox + x);
+      if (alpha) {
+        if constexpr (LABEL) as_global(static_cast<uint8_t*>(alpha))[(int64_t)frame * plane + pix[p]] = rrlens::lens_label(A[p]);
+        else as_global(static_cast<float*>(alpha))[(int64_t)frame * plane + pix[p]] = A[p];
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int c = 0; c < 3; c++) {
+    for (int i = threadIdx.x; i < vh * TL; i += 256) {
+      const int row = i >> 5, x = i & (TL - 1);
+      if (x < tw) s_r[row * TL + x] = rrlens::lens_blur_taps(&s_v[c][row * LENS_VW + x], 1, wt, R);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+      if (pix[p] < 0 || A[p] == 0.0f) continue;
+      const int idx = (int)threadIdx.x + 256 * p, x = idx & (TL - 1), y = idx >> 5;
+      const float B = rrlens::lens_blur_taps(&s_r[y * TL + x], TL, wt, R);
+      res[p][c] = rrlens::lens_round_u8(rrlens::lens_composite(A[p], rimf[p], B, (float)img[pix[p] * 3 + c]));
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    if (pix[p] < 0 || A[p] == 0.0f) continue;
+    const global_ptr<uint8_t> o = dst + pix[p] * 3;
+    o[0] = res[p][0]; o[1] = res[p][1]; o[2] = res[p][2];
+  }
+}
+
+// The label file of a frame (rr_pipeline_lens.alpha_png), ready for deflate: what k_png_image makes of an image, of the label plane --
+// H rows of 1 + 4 W bytes, filter type 1 (Sub), RGBA pixels R = G = B = v, alpha 255.
+__global__ __launch_bounds__(256) void k_png_alpha(const uint8_t* label, uint8_t* rows, int64_t rows_stride, Dims dm) {
+  const int f = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (int64_t)dm.H * dm.W) return;
+  const int y = (int)(pix / dm.W), x = (int)(pix - (int64_t)y * dm.W);
+  const global_ptr<const uint8_t> s = as_global(label) + (int64_t)f * dm.H * dm.W + pix;
+  const global_ptr<uint8_t> o = as_global(rows) + (int64_t)f * rows_stride + (int64_t)y * (1 + 4 * dm.W) + 1 + 4 * x;
+  if (x == 0) {
+    o[-1] = 1;                                        // filter type: Sub
+    o[0] = s[0]; o[1] = s[0]; o[2] = s[0]; o[3] = 255;
+  } else {
+    const uint8_t v = (uint8_t)(s[0] - s[-1]);
+    o[0] = v; o[1] = v; o[2] = v;
+    o[3] = 0;                                         // alpha 255 - 255
+  }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -5596,6 +5734,20 @@ struct rr_ctx {
     int64_t* h_flags = nullptr;      // pinned: [0] arena-overflow flag as seen after this batch
     bool busy = false, rendered = false;
     std::vector<void*> ext_blobs;     // device copies of caller-made tiles (rr_ext_tile), freed when the slot is reused
+    // rr_pipeline_set_lens: the slot's OWN upload block -- blur table, records of the drops that touch a frame, work
+    // list -- pinned on the host and mirrored on the device.  Only rr_pipeline_set_lens writes the host block, and it refuses a slot in
+    // flight, so no batch's block is overwritten before its kernel has run however many batches are queued.  Device staging
+    // (allocated by the first arming call, grown, never shrunk): the un-dropped bytes of the batch's rainy_rgb, the label plane,
+    // and the label's scanlines when alpha_png asks for them.
+    struct Lens {
+      bool armed = false, want_alpha = false;
+      int n = 0, H = 0, W = 0, n_work = 0;
+      char *h_block = nullptr, *d_block = nullptr;
+      size_t block_cap = 0, bytes = 0, off_recs = 0, off_work = 0;
+      uint8_t *d_copy = nullptr, *d_label = nullptr, *d_png = nullptr;
+      size_t copy_cap = 0, label_cap = 0, png_cap = 0;
+      std::vector<uint8_t*> alpha_png;                   // the caller's n host buffers (NULL entries allowed), or empty
+    } lens;
   } slots[RR_PIPE_SLOTS];
   hipStream_t s_up = nullptr, s_down = nullptr;
   // pre-pass (fog + environment map)
@@ -5881,8 +6033,17 @@ struct PlanarOut {
   int f32;
 };
 
+// The lens stage of a batch on an armed pipeline slot (rr_pipeline_set_lens): between the finalize kernel and the PNG rows.
+// rgb: the batch's interleaved frames rgb_stride bytes apart (the slot's st.rgb); they are copied to `copy` and the kernel reads the
+// copy (every drop refracts the un-dropped frame) and writes rgb.
+struct LensStage {
+  const rr_ctx::Slot::Lens* lens;
+  uint8_t* rgb;
+  int64_t rgb_stride, png_stride;
+};
+
 int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, hipStream_t s, int ovf_idx = 0,
-            const PlanarOut* planar = nullptr) {
+            const PlanarOut* planar = nullptr, const LensStage* lens = nullptr) {
   if (!ctx->have_cam || !ctx->have_db) {
     ctx->err = "streak DB and camera must be set before rendering";
     return RR_E_STATE;
@@ -6290,16 +6451,39 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     else
       hipLaunchKernelGGL(k_finalize, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, ctx->d_frames, dm, sc);
   }
+  const bool lens_png = lens && lens->lens->want_alpha;
+  if (lens) {
+    const rr_ctx::Slot::Lens& L = *lens->lens;
+    {
+      ProfScope ps(ctx, s, "lens_copy");
+      HIPCHK(hipMemcpyAsync(L.d_copy, lens->rgb, (size_t)n * (size_t)lens->rgb_stride, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemsetAsync(L.d_label, 0, (size_t)n * dm.H * dm.W, s));
+    }
+    if (L.n_work > 0) {
+      hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(L.h_block), reinterpret_cast<uint32_t*>(L.d_block),
+                         (int)(L.bytes / 4));
+      ProfScope ps(ctx, s, "k_lens_drops_hwc");
+      hipLaunchKernelGGL(k_lens_drops_hwc<true>, dim3((unsigned)L.n_work), dim3(256), 0, s, L.d_copy, lens->rgb_stride, lens->rgb, lens->rgb_stride,
+                         (void*)L.d_label, reinterpret_cast<const LensTable*>(L.d_block), reinterpret_cast<const rr_lens_drop*>(L.d_block + L.off_recs),
+                         reinterpret_cast<const rrlens::WorkItem*>(L.d_block + L.off_work), dm.H, dm.W);
+    }
+    want_png = want_png || lens_png;
+  }
   if (want_png) {
     ProfScope ps(ctx, s, "k_png_rows");
     const dim3 grid((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n);
     hipLaunchKernelGGL(k_png_image, grid, dim3(256), 0, s, ctx->d_frames, dm);
     if (ctx->have_lut) hipLaunchKernelGGL(k_png_mask, grid, dim3(256), 0, s, ctx->d_frames, dm, ctx->d_lut, sc);
   }
+  if (lens_png) {
+    ProfScope ps(ctx, s, "k_png_alpha");
+    hipLaunchKernelGGL(k_png_alpha, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, lens->lens->d_label, lens->lens->d_png,
+                       lens->png_stride, dm);
+  }
   if (want_png && ctx->png_deflate) {
     const int64_t n_bytes = (int64_t)dm.H * (1 + 4 * (int64_t)dm.W);
     const int nb = (int)rrz::blocks_of(n_bytes);
-    const size_t need = (size_t)2 * n * nb;
+    const size_t need = (size_t)(lens_png ? 3 : 2) * n * nb;
     if (need > ctx->pngz_cap) {
       HIPCHK(hipDeviceSynchronize());
       int rc;
@@ -6308,12 +6492,21 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
       ctx->pngz_cap = need;
     }
     if (!ctx->pngz_attr) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
       ctx->pngz_attr = true;
     }
     ProfScope ps(ctx, s, "k_pngz");
-    hipLaunchKernelGGL(k_pngz_blocks, dim3(nb, 2 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta);
-    hipLaunchKernelGGL(k_pngz_pack, dim3(nb, 2 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta);
+    if (lens_png) {                                      // image, mask and the label: three streams per frame
+      const PngzLabel<3> label{lens->lens->d_png, lens->png_stride};
+      hipLaunchKernelGGL(k_pngz_blocks<3>, dim3(nb, 3 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots,
+                         ctx->d_pngz_meta, label);
+      hipLaunchKernelGGL(k_pngz_pack<3>, dim3(nb, 3 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta, label);
+    } else {
+      hipLaunchKernelGGL(k_pngz_blocks<2>, dim3(nb, 2 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots,
+                         ctx->d_pngz_meta, PngzLabel<2>{});
+      hipLaunchKernelGGL(k_pngz_pack<2>, dim3(nb, 2 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta, PngzLabel<2>{});
+    }
   }
   HIPCHK(hipGetLastError());
   ctx->last_n = n;
@@ -7064,6 +7257,11 @@ int rr_destroy(rr_ctx* ctx) {
     if (sl.h_up) hipHostFree(sl.h_up);
     if (sl.h_down) hipHostFree(sl.h_down);
     for (void* b : sl.ext_blobs) hipFree(b);
+    if (sl.lens.h_block) hipHostFree(sl.lens.h_block);
+    hipFree(sl.lens.d_block);
+    hipFree(sl.lens.d_copy);
+    hipFree(sl.lens.d_label);
+    hipFree(sl.lens.d_png);
   }
   if (ctx->s_col) hipStreamDestroy(ctx->s_col);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
@@ -8085,6 +8283,12 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
   Dims dm{0, 0, 0, 0};
   int max_drops = 1, rc;
   if ((rc = validate_host_batch(ctx, n, pre, in, out, pre_out, dm, max_drops))) return rc;
+  if (sl.lens.armed && (!in || sl.lens.n != n || sl.lens.H != dm.H || sl.lens.W != dm.W)) {
+    ctx->err = !in ? "pipeline slot armed with rr_pipeline_set_lens: the batch renders nothing (in == NULL)"
+                   : "pipeline slot armed with rr_pipeline_set_lens for " + std::to_string(sl.lens.n) + " frames of " + std::to_string(sl.lens.H) + " x " +
+                         std::to_string(sl.lens.W) + ": the batch has " + std::to_string(n) + " of " + std::to_string(dm.H) + " x " + std::to_string(dm.W);
+    return RR_E_ARG;
+  }
   if ((rc = slot_init(ctx, sl))) return rc;
   for (void* b : sl.ext_blobs) hipFree(b);             // the slot's previous batch is complete (not busy)
   sl.ext_blobs.clear();
@@ -8290,7 +8494,8 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
   if (!sims.empty() && (rc = enqueue_particles(ctx, n, sims.data(), dm.H, dm.W, st.drops, drop_stride, st.ndrops, s))) return drained(rc);
   if (in) {                           // the slot's own overflow flag, cleared in stream order before the batch's k_scan may set it
     hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, ctx->sc.overflow + 1 + slot, 0);
-    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot))) return drained(rc);
+    const LensStage stage{&sl.lens, st.rgb, (int64_t)T.px3b, (int64_t)T.pngb};
+    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot, nullptr, sl.lens.armed ? &stage : nullptr))) return drained(rc);
   }
   if (hipEventRecord(sl.ev_comp, s) != hipSuccess) {
     ctx->err = "pipeline: hipEventRecord failed";
@@ -8309,6 +8514,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if (out[f].n_drops_out && in[f].sim) down.add(out[f].n_drops_out, st.ndrops + f, sizeof(int32_t));
     if (out[f].rainy_png) down.add(out[f].rainy_png, dout[f].rainy_png, png_bytes);
     if (out[f].mask_png) down.add(out[f].mask_png, dout[f].mask_png, png_bytes);
+    if (sl.lens.armed && sl.lens.want_alpha && sl.lens.alpha_png[(size_t)f]) down.add(sl.lens.alpha_png[(size_t)f], sl.lens.d_png + (size_t)f * T.pngb, png_bytes);
   }
   for (int f = 0; pre && pre_out && f < n; f++) {
     if (pre_out[f].rainy_bg && pre[f].mode != RR_PRE_ENV_ONLY) down.add(pre_out[f].rainy_bg, pout[f].rainy_bg, px * 3 * rainy_el);
@@ -8492,8 +8698,8 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
 // images -> out, the upload, k_lens_drops, on `s` (see include/rainhip.h); every check comes before the first enqueue
 int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
   const int n = b->n, H = b->H, W = b->W;
-  if (n <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32) || !b->images ||
-      !b->out || !b->counts || b->cap < 0 || (b->cap > 0 && !b->drops)) {
+  if (n <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32 && b->dtype != RR_TENSOR_U8_HWC) ||
+      !b->images || !b->out || !b->counts || b->cap < 0 || (b->cap > 0 && !b->drops)) {
     ctx->err = "rr_lens_drops_device: bad argument (sizes, dtype or a null pointer)";
     return RR_E_ARG;
   }
@@ -8560,11 +8766,15 @@ int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
   hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_lens),
                      (int)(bytes / 4));
   if ((rc = ring_commit(ctx, ctx->ring_lens, ring_idx, s))) return rc;
-  {
+  const LensTable* d_tab = reinterpret_cast<const LensTable*>(ctx->d_lens);
+  const rr_lens_drop* d_recs = reinterpret_cast<const rr_lens_drop*>(ctx->d_lens + off_recs);
+  const rrlens::WorkItem* d_work = reinterpret_cast<const rrlens::WorkItem*>(ctx->d_lens + off_work);
+  if (b->dtype == RR_TENSOR_U8_HWC) {
+    ProfScope ps(ctx, s, "k_lens_drops_hwc");
+    hipLaunchKernelGGL(k_lens_drops_hwc<false>, dim3((unsigned)work.size()), dim3(256), 0, s, static_cast<const uint8_t*>(b->images), (int64_t)(3 * px),
+                       static_cast<uint8_t*>(b->out), (int64_t)(3 * px), (void*)b->alpha_out, d_tab, d_recs, d_work, H, W);
+  } else {
     ProfScope ps(ctx, s, "k_lens_drops");
-    const LensTable* d_tab = reinterpret_cast<const LensTable*>(ctx->d_lens);
-    const rr_lens_drop* d_recs = reinterpret_cast<const rr_lens_drop*>(ctx->d_lens + off_recs);
-    const rrlens::WorkItem* d_work = reinterpret_cast<const rrlens::WorkItem*>(ctx->d_lens + off_work);
     if (el == 4)
       hipLaunchKernelGGL(k_lens_drops<true>, dim3((unsigned)work.size()), dim3(256), 0, s, b->images, b->out, b->alpha_out, d_tab, d_recs, d_work, H, W);
     else
@@ -8574,9 +8784,113 @@ int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
   return RR_OK;
 }
 
+// rr_pipeline_set_lens: every check, then the slot's block and staging; nothing of the slot changes before the last check has passed
+int set_lens(rr_ctx* ctx, int slot, const rr_pipeline_lens* b) {
+  if (slot < 0 || slot >= RR_PIPE_SLOTS) {
+    ctx->err = "rr_pipeline_set_lens: bad pipeline slot";
+    return RR_E_ARG;
+  }
+  rr_ctx::Slot& sl = ctx->slots[slot];
+  if (sl.busy) {
+    ctx->err = "rr_pipeline_set_lens: pipeline slot still in flight: call rr_pipeline_wait first";
+    return RR_E_STATE;
+  }
+  rr_ctx::Slot::Lens& L = sl.lens;
+  if (!b) {
+    L.armed = false;
+    L.alpha_png.clear();
+    return RR_OK;
+  }
+  const int n = b->n, H = b->H, W = b->W;
+  if (n <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || !b->counts || b->cap < 0 || (b->cap > 0 && !b->drops)) {
+    ctx->err = "rr_pipeline_set_lens: bad argument (sizes or a null pointer)";
+    return RR_E_ARG;
+  }
+  std::string why = rrlens::check_classes(b->n_classes, b->class_radius, b->weights);
+  if (!why.empty()) {
+    ctx->err = "rr_pipeline_set_lens: blur table: " + why;
+    return RR_E_ARG;
+  }
+  std::vector<rr_lens_drop> recs;
+  std::vector<rrlens::WorkItem> work;
+  std::vector<rrlens::Box> boxes;
+  for (int f = 0; f < n; f++) {
+    boxes.clear();
+    const rr_lens_drop* fd = b->cap > 0 ? b->drops + (size_t)f * b->cap : nullptr;
+    why = rrlens::check_frame(fd, b->counts[f], b->cap, b->n_classes, W, H, boxes);
+    if (!why.empty()) {
+      ctx->err = "rr_pipeline_set_lens: frame " + std::to_string(f) + ": " + why;
+      return RR_E_ARG;
+    }
+    for (const rrlens::Box& bx : boxes) {
+      rrlens::box_work(bx, f, (int32_t)recs.size(), work);
+      recs.push_back(fd[bx.drop]);
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t off_recs = sizeof(LensTable), off_work = off_recs + recs.size() * sizeof(rr_lens_drop);
+  const size_t bytes = off_work + work.size() * sizeof(rrlens::WorkItem);
+  const Dims dm{H, W, 0, 0};
+  const Strides T = strides_of(dm);
+  bool want_alpha = false;
+  for (int f = 0; b->alpha_png && f < n; f++) want_alpha = want_alpha || b->alpha_png[f];
+  // (the slot is not in flight: nothing reads its blocks.  A failed allocation leaves the slot disarmed.)
+  L.armed = false;
+  L.alpha_png.clear();
+  if (bytes > L.block_cap) {
+    if (L.h_block) HIPCHK(hipHostFree(L.h_block));
+    if (L.d_block) HIPCHK(hipFree(L.d_block));
+    L.h_block = L.d_block = nullptr;
+    L.block_cap = 0;
+    const size_t want = bytes + bytes / 2;
+    HIPCHK(hipHostMalloc((void**)&L.h_block, want, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&L.d_block, want));
+    L.block_cap = want;
+  }
+  auto grow = [&](uint8_t*& p, size_t& cap, size_t need) -> int {
+    if (need <= cap) return RR_OK;
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipMalloc((void**)&p, need));
+    cap = need;
+    return RR_OK;
+  };
+  int rc;
+  if ((rc = grow(L.d_copy, L.copy_cap, (size_t)n * T.px3b))) return rc;
+  if ((rc = grow(L.d_label, L.label_cap, (size_t)n * H * W))) return rc;
+  if (want_alpha && (rc = grow(L.d_png, L.png_cap, (size_t)n * T.pngb))) return rc;
+  LensTable* tab = reinterpret_cast<LensTable*>(L.h_block);
+  memset(tab, 0, sizeof(LensTable));
+  for (int c = 0; c < b->n_classes; c++) {
+    tab->radius[c] = b->class_radius[c];
+    memcpy(tab->w + c * rrlens::TAPS, b->weights + c * rrlens::TAPS, sizeof(float) * (size_t)(2 * b->class_radius[c] + 1));
+  }
+  memcpy(L.h_block + off_recs, recs.data(), recs.size() * sizeof(rr_lens_drop));
+  memcpy(L.h_block + off_work, work.data(), work.size() * sizeof(rrlens::WorkItem));
+  L.bytes = bytes;
+  L.off_recs = off_recs;
+  L.off_work = off_work;
+  L.n_work = (int)work.size();
+  L.n = n;
+  L.H = H;
+  L.W = W;
+  L.want_alpha = want_alpha;
+  if (want_alpha) L.alpha_png.assign(b->alpha_png, b->alpha_png + n);
+  L.armed = true;
+  return RR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rr_sizeof_pipeline_lens(void) { return (int)sizeof(rr_pipeline_lens); }
+
+int rr_pipeline_set_lens(rr_ctx* ctx, int32_t slot, const rr_pipeline_lens* lens) {
+  if (!ctx) return RR_E_ARG;
+  return set_lens(ctx, slot, lens);
+}
 
 int rr_sizeof_tensor_batch(void) { return (int)sizeof(rr_tensor_batch); }
 int rr_sizeof_lens_drop(void) { return (int)sizeof(rr_lens_drop); }

@@ -78,6 +78,9 @@ RR_HD float lens_composite(float A, float rimf, float B, float in) { return (1.0
 // a byte tensor stores clamp(rint(out), 0, 255), half to even
 RR_HD uint8_t lens_round_u8(float v) { return (uint8_t)(int)fminf(fmaxf(rintf(v), 0.0f), 255.0f); }
 
+// the frame pipeline's per-pixel drop label (rr_pipeline_lens.alpha_png): one float multiply, then half to even
+RR_HD uint8_t lens_label(float A) { return lens_round_u8(A * 255.0f); }
+
 RR_HD float lens_store(float v, float*) { return v; }
 RR_HD uint8_t lens_store(float v, uint8_t*) { return lens_round_u8(v); }
 

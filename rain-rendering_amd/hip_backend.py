@@ -139,6 +139,7 @@ class rr_prepass_out(ctypes.Structure):
 
 
 RR_TENSOR_U8, RR_TENSOR_F32 = 0, 1                       # rr_tensor_batch.dtype
+RR_TENSOR_U8_HWC = 3                                     # rr_lens_batch.dtype only: interleaved bytes [n, H, W, 3] (2 stays refused)
 
 
 class rr_tensor_batch(ctypes.Structure):
@@ -160,6 +161,12 @@ class rr_lens_batch(ctypes.Structure):
                 ('weights', ctypes.c_void_p)]
 
 
+class rr_pipeline_lens(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('cap', ctypes.c_int32), ('counts', ctypes.c_void_p),
+                ('drops', ctypes.c_void_p), ('n_classes', ctypes.c_int32), ('reserved', ctypes.c_int32), ('class_radius', ctypes.c_void_p),
+                ('weights', ctypes.c_void_p), ('alpha_png', ctypes.c_void_p)]
+
+
 EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_streak_db', 'rr_set_streak_db_device',
            'rr_set_camera', 'rr_render_frames', 'rr_render_frames_device', 'rr_synchronize', 'rr_profile_enable',
            'rr_profile_reset', 'rr_profile_read', 'rr_sizeof_drop', 'rr_sizeof_camera', 'rr_sizeof_frame_in',
@@ -172,7 +179,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
-           'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch']
+           'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
+           'rr_sizeof_pipeline_lens']
 
 _lib = None
 
@@ -284,6 +292,8 @@ def load_library(path=None):
     lib.rr_lens_drops_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_lens_batch), ctypes.c_void_p]
     assert lib.rr_sizeof_lens_drop() == LENS_DROP_DTYPE.itemsize == 32, (lib.rr_sizeof_lens_drop(), LENS_DROP_DTYPE.itemsize)
     assert lib.rr_sizeof_lens_batch() == ctypes.sizeof(rr_lens_batch), (lib.rr_sizeof_lens_batch(), ctypes.sizeof(rr_lens_batch))
+    lib.rr_pipeline_set_lens.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(rr_pipeline_lens)]
+    assert lib.rr_sizeof_pipeline_lens() == ctypes.sizeof(rr_pipeline_lens), (lib.rr_sizeof_pipeline_lens(), ctypes.sizeof(rr_pipeline_lens))
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
     assert lib.rr_sizeof_prepass_out() == ctypes.sizeof(rr_prepass_out)
     assert lib.rr_sizeof_prepass_kernels() == ctypes.sizeof(rr_prepass_kernels)
@@ -604,13 +614,14 @@ def io_read_frames_scaled(image_paths, depth_paths, H, W, render_scale, depth_sc
 
 
 def io_write_frames(image_paths, mask_paths, rows_image_block, rows_mask_block, W, H, threads=0):
-    """rr_io_write_frames from the scanline blocks of a pipeline slot ((n, stride) uint8 arrays).  Per-frame status."""
+    """rr_io_write_frames from the scanline blocks of a pipeline slot ((n, stride) uint8 arrays).  Per-frame status.
+    mask_paths None (then rows_mask_block is not read and may be None): one file per frame, the label files of --lens_alpha."""
     lib = load_library()
     n = len(image_paths)
     ip, k1 = _c_paths(image_paths)
-    mp, k2 = _c_paths(mask_paths)
+    mp, k2 = _c_paths(mask_paths) if mask_paths is not None else (None, None)
     status = np.zeros(n, np.int32)
-    assert rows_image_block.strides[0] == rows_mask_block.strides[0]
+    assert mask_paths is None or rows_image_block.strides[0] == rows_mask_block.strides[0]
     rc = lib.rr_io_write_frames(n, ip, mp, _ptr(rows_image_block), _ptr(rows_mask_block), int(rows_image_block.strides[0]), int(W), int(H),
                                 int(threads), _ptr(status))
     if rc != 0:
@@ -1238,13 +1249,9 @@ class RainHip:
         self._check(self.lib.rr_augment_frames_device(self.h, ctypes.byref(batch), ctypes.c_void_p(stream) if stream else None),
                     'rr_augment_frames_device')
 
-    def lens_drops_device(self, images_ptr, out_ptr, n, H, W, f32, tables, weights, alpha_ptr=None, stream=None):
-        """rr_lens_drops_device: drops on the lens of the n planar [3, H, W] images at DEVICE pointer images_ptr (float32 when f32, else
-        bytes) into out_ptr, and their coverage into alpha_ptr ([n, H, W] float32) when given.  `tables`: n arrays of LENS_DROP_DTYPE
-        records (tools/lens.py LensDrops.table), `weights`: the blur table (class_radius, float32 [16, 31]; LensDrops.weights()).
-        Enqueued on `stream`; without one the call waits for the context's own stream."""
-        if len(tables) != n:
-            raise ValueError("%d drop tables for %d images" % (len(tables), n))
+    @staticmethod
+    def _lens_tables(tables, weights):
+        """(counts int32[n], drops [n, cap] records, cap, class_radius int32[], weights float32[16, 31]) of n drop tables and a blur table."""
         radius = np.ascontiguousarray(weights[0], np.int32).reshape(-1)
         w = np.ascontiguousarray(weights[1], np.float32)
         if w.shape != (16, 31):
@@ -1252,11 +1259,55 @@ class RainHip:
         tabs = [np.ascontiguousarray(t, LENS_DROP_DTYPE).reshape(-1) for t in tables]
         counts = np.array([len(t) for t in tabs], np.int32)
         cap = max(1, int(counts.max()))
-        drops = np.zeros((n, cap), LENS_DROP_DTYPE)
+        drops = np.zeros((len(tabs), cap), LENS_DROP_DTYPE)
         for f, t in enumerate(tabs):
             drops[f, :len(t)] = t
+        return counts, drops, cap, radius, w
+
+    def pipeline_set_lens(self, slot, tables, weights=None, H=0, W=0, alpha_png=None):
+        """rr_pipeline_set_lens: arm pipeline slot `slot` with the drop tables of its next batches' frames (`tables`: one array of
+        LENS_DROP_DTYPE records per frame, in batch order; `weights`: the blur table, LensDrops.weights()) for H x W frames, or disarm
+        it with tables=None.  alpha_png: None, or one entry per frame, each None or a C-contiguous uint8 array of H * (1 + 4 W) bytes
+        (ideally from host_array) that receives the frame's label file like mask_png; the arrays must stay alive and untouched until
+        pipeline_wait.  The tables are copied by the call.  Every submit on the slot applies the armed tables once, until the slot is
+        armed again or disarmed."""
+        if tables is None:
+            self._check(self.lib.rr_pipeline_set_lens(self.h, int(slot), None), 'rr_pipeline_set_lens')
+            getattr(self, '_lens_keep', {}).pop(int(slot), None)
+            return
+        n = len(tables)
+        counts, drops, cap, radius, w = self._lens_tables(tables, weights)
+        b = rr_pipeline_lens()
+        b.n, b.H, b.W, b.cap = n, int(H), int(W), cap
+        b.counts, b.drops = counts.ctypes.data, drops.ctypes.data
+        b.n_classes, b.class_radius, b.weights = len(radius), radius.ctypes.data, w.ctypes.data
+        ptrs = None
+        if alpha_png is not None:
+            if len(alpha_png) != n:
+                raise ValueError("%d alpha_png buffers for %d drop tables" % (len(alpha_png), n))
+            for a in alpha_png:
+                if a is not None and not (a.dtype == np.uint8 and a.flags['C_CONTIGUOUS'] and a.size >= int(H) * (1 + 4 * int(W))):
+                    raise ValueError("an alpha_png buffer is a C-contiguous uint8 array of H * (1 + 4 W) bytes")
+            ptrs = (ctypes.c_void_p * n)(*[None if a is None else a.ctypes.data for a in alpha_png])
+            b.alpha_png = ctypes.cast(ptrs, ctypes.c_void_p)
+        self._check(self.lib.rr_pipeline_set_lens(self.h, int(slot), ctypes.byref(b)), 'rr_pipeline_set_lens')
+        if not hasattr(self, '_lens_keep'):
+            self._lens_keep = {}
+        self._lens_keep[int(slot)] = alpha_png           # (the library copied everything else)
+
+    def lens_drops_device(self, images_ptr, out_ptr, n, H, W, f32, tables, weights, alpha_ptr=None, stream=None, layout='chw'):
+        """rr_lens_drops_device: drops on the lens of the n planar [3, H, W] images at DEVICE pointer images_ptr (float32 when f32, else
+        bytes) into out_ptr, and their coverage into alpha_ptr ([n, H, W] float32) when given.  `tables`: n arrays of LENS_DROP_DTYPE
+        records (tools/lens.py LensDrops.table), `weights`: the blur table (class_radius, float32 [16, 31]; LensDrops.weights()).
+        layout='hwc': the images are interleaved [H, W, 3] bytes (RR_TENSOR_U8_HWC; not with f32).
+        Enqueued on `stream`; without one the call waits for the context's own stream."""
+        if len(tables) != n:
+            raise ValueError("%d drop tables for %d images" % (len(tables), n))
+        if layout not in ('chw', 'hwc') or (layout == 'hwc' and f32):
+            raise ValueError("layout %r: expected 'chw', or 'hwc' with bytes" % (layout,))
+        counts, drops, cap, radius, w = self._lens_tables(tables, weights)
         b = rr_lens_batch()
-        b.n, b.H, b.W, b.dtype = n, H, W, RR_TENSOR_F32 if f32 else RR_TENSOR_U8
+        b.n, b.H, b.W, b.dtype = n, H, W, RR_TENSOR_U8_HWC if layout == 'hwc' else (RR_TENSOR_F32 if f32 else RR_TENSOR_U8)
         b.images, b.out, b.alpha_out = images_ptr, out_ptr, alpha_ptr
         b.counts, b.drops, b.cap = counts.ctypes.data, drops.ctypes.data, cap
         b.n_classes, b.class_radius, b.weights = len(radius), radius.ctypes.data, w.ctypes.data

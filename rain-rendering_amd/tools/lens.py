@@ -217,6 +217,13 @@ def apply_numpy(images, tables, weights, alpha=False):
     return (out, al) if alpha else out
 
 
+def alpha_label(alpha):
+    """The byte label the frame pipeline writes for a coverage A (rr_pipeline_lens.alpha_png; rr_lens.h lens_label):
+    v = clamp(rint(float32(A) * float32(255)), 0, 255), one float32 multiply, then half to even.  uint8, the shape of `alpha`."""
+    a = np.asarray(alpha, np.float32)
+    return np.minimum(np.maximum(np.rint(a * np.float32(255.0)), np.float32(0.0)), np.float32(255.0)).astype(np.uint8)
+
+
 # ---- the generator -------------------------------------------------------------------------------------------------
 def _range(name, v, lo=None, hi=None, lo_open=False):
     try:
@@ -269,6 +276,31 @@ class LensDrops:
     def _args(self):
         return dict(count=self.count, radius=self.radius, aspect=self.aspect, mag=self.mag, blur=self.blur, edge=self.edge, rim=self.rim,
                     life_s=self.life_s, hz=self.hz)
+
+    _SPEC_KEYS = ('count', 'radius', 'aspect', 'mag', 'blur', 'edge', 'rim', 'life_s', 'hz', 'seed')
+
+    @classmethod
+    def from_spec(cls, spec, H, W, hz):
+        """The drops of a command line (main.py --lens_drops): COUNT[,SEED], or the path of a JSON file holding an object of LensDrops
+        keywords (count, radius, aspect, mag, blur, edge, rim, life_s, hz, seed).  H, W and -- unless the file names one -- hz come
+        from the caller."""
+        import json
+        import os
+        spec = str(spec).strip()
+        parts = spec.split(',')
+        if 1 <= len(parts) <= 2 and all(p.strip().lstrip('+-').isdigit() for p in parts):
+            return cls(H, W, count=int(parts[0]), seed=int(parts[1]) if len(parts) > 1 else 0, hz=hz)
+        if not os.path.isfile(spec):
+            raise ValueError("lens drops %r: expected COUNT[,SEED] or the path of a JSON file of LensDrops keywords" % (spec,))
+        try:
+            with open(spec) as f:
+                kw = json.load(f)
+        except (OSError, ValueError) as e:
+            raise ValueError("lens drops %r: expected a JSON file of LensDrops keywords (%s)" % (spec, e))
+        if not isinstance(kw, dict) or any(k not in cls._SPEC_KEYS for k in kw):
+            raise ValueError("lens drops %r: expected a JSON object with keys among %s" % (spec, ', '.join(cls._SPEC_KEYS)))
+        kw.setdefault('hz', hz)
+        return cls(H, W, **kw)
 
     def weights(self):
         """The blur table of every call with this instance's tables."""
