@@ -119,12 +119,17 @@ def test_fov_options_and_retired_options(setup):
             alt.set_streak_db(sc.db.streaks_light)
             alt.set_camera(sc.cam)
             out = alt.render_frames([fr])[0]
+            # the float route (no float64 composite asked for): k_fov_sums32 at the same drops per thread
+            out32 = alt.render_frames([fr], want_composite=False)[0]
         finally:
             alt.close()
         assert np.array_equal(out['status'], base['status']), opts
         assert np.array_equal(out['mask'], base['mask']) and np.array_equal(out['mask_i32'], base['mask_i32']), opts
         assert np.abs(out['image_u8'].astype(int) - base['image_u8'].astype(int)).max() <= 1, opts
         assert np.abs(out['rainy_bg'] - base['rainy_bg']).max() < 1e-9, opts
+        assert np.array_equal(out32['status'], base['status']), opts
+        assert np.array_equal(out32['mask'], base['mask']) and np.array_equal(out32['mask_i32'], base['mask_i32']), opts
+        assert np.abs(out32['image_u8'].astype(int) - base['image_u8'].astype(int)).max() <= 1, opts
     # retired options: (option, the accepted value, another value)
     retired = ((h.hb.RR_OPT_FOV_THREADS, 1024, 512), (h.hb.RR_OPT_BLUR_WORKGROUPS, 4, 5),
                (h.hb.RR_OPT_PADDED_TEXTURES, 1, 0), (h.hb.RR_OPT_COMPOSITE_WAVES, 0, 6),
