@@ -9,7 +9,6 @@
   4. invalid combinations are RR_E_ARG with a message."""
 import importlib
 import os
-import socket
 import subprocess
 import sys
 
@@ -19,48 +18,28 @@ import torch
 from PIL import Image
 
 import helpers as h
+import particle_cases as cases
 
 pytestmark = pytest.mark.gpu
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-db = importlib.import_module('rain-rendering_amd.common.db')
 augment = importlib.import_module('rain-rendering_amd.augment')
 
 DEV = torch.device('cuda', 0)
 CAMS = {'kitti': None, 'cityscapes': None, 'nuscenes': h.NUSCENES}
 
 
-def _options(dataset, **kw):
-    o = dict(db.settings(dataset))
-    o.pop('sequences', None)
-    o.update(kw)
-    return o
-
-
-def _rh(sc):
-    rh = h.hb.RainHip(0)
-    rh.set_streak_db(sc.db.streaks_light)
-    rh.set_camera(sc.cam)
-    return rh
-
-
-def _same(got, want, what):
-    assert len(got) == len(want), '%s: %d records on the device, %d on the host' % (what, len(got), len(want))
-    for name in h.hb.DROP_DTYPE.names:
-        assert got[name].tobytes() == want[name].tobytes(), '%s: %s' % (what, name)
-
-
 @pytest.mark.parametrize("dataset,rs", [('kitti', 1), ('cityscapes', 2), ('nuscenes', 1)])
 @pytest.mark.parametrize("rate", [25, 100])
 def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0, 0.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0, 0.0])})
     sims, dgrid, cdf = particles.sim_frames(opt, rate, 3, render_scale=rs, seed=1234 + 2 ** 40, model='field')
     sims = particles.field_run_sims(sims, [0, 1, 17, 2 ** 31 + 5, 4000000000])
     hz = opt['cam_hz']
     want = particles.expected_records(sims, dgrid, cdf, sc.db, model='field', cam_hz=hz)
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', hz)
@@ -69,14 +48,14 @@ def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate)
             got, cnt = rh.generate_drops(sims, H, W)
             for k in range(len(sims)):
                 assert int(cnt[k]) == len(want[k]) > 100
-                _same(got[k], want[k], 'frame %d, %d chunks' % (k, chunks))
+                cases.same_bytes(got[k], want[k], 'frame %d, %d chunks' % (k, chunks))
             # a frame alone, and in another order: the same bits (no state, no dependence on the batch)
             alone, _ = rh.generate_drops(sims[3:4], H, W)
-            _same(alone[0], want[3], 'frame 3 alone, %d chunks' % chunks)
+            cases.same_bytes(alone[0], want[3], 'frame 3 alone, %d chunks' % chunks)
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
         back, _ = rh.generate_drops(sims[::-1], H, W)
         for k in range(len(sims)):
-            _same(back[len(sims) - 1 - k], want[k], 'frame %d, reversed batch' % k)
+            cases.same_bytes(back[len(sims) - 1 - k], want[k], 'frame %d, reversed batch' % k)
         # a capacity below the drop count: the count still tells, the records that fit are the first ones
         small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[0]) // 2, 1))
         assert np.array_equal(cnt_small, cnt)
@@ -90,14 +69,14 @@ def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate)
 def test_frame_path_renders_the_host_statements_records(tmp_path, built, dataset, rs, rate):
     """rr_render_frames with rr_frame_in.sim under the field model against the same call fed expected_records: count, drop
     status, mask and image identical."""
-    opt = _options(dataset)
+    opt = cases.options(dataset)
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
     sc = h.Scene(tmp_path, H, W, 10, **({'cam': CAMS[dataset]} if CAMS[dataset] is not None else {}))
     sims, dgrid, cdf = particles.sim_frames(opt, rate, 1, render_scale=rs, seed=77, model='field')
     sims = particles.field_run_sims(sims, [5, 6])
     want = particles.expected_records(sims, dgrid, cdf, sc.db, model='field', cam_hz=opt['cam_hz'])
     bg, env = sc.frame_inputs(0)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', opt['cam_hz'])
@@ -116,10 +95,10 @@ def test_frame_path_renders_the_host_statements_records(tmp_path, built, dataset
 
 def test_default_models_bits_do_not_move(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         for dataset, rs in (('kitti', 1), ('cityscapes', 2), ('nuscenes', 1)):
-            opt = _options(dataset)
+            opt = cases.options(dataset)
             sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, render_scale=rs, seed=9)
             want = particles.expected_records(sims, dgrid, cdf, sc.db)
             W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
@@ -137,9 +116,9 @@ def test_default_models_bits_do_not_move(tmp_path, built):
 
 def test_invalid_combinations_are_refused(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, model='field')
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         for hz in (0.0, -10.0, float('nan'), float('inf')):
@@ -194,12 +173,6 @@ def _pipeline_f32(aug, p, bgr, depth):
     return np.stack([o['image_u8'] for o in outs])
 
 
-def _free_port():
-    with socket.socket() as s_:
-        s_.bind(('127.0.0.1', 0))
-        return s_.getsockname()[1]
-
-
 def test_driver_one_rank_two_ranks_and_the_augmenter_agree(tmp_path, built, monkeypatch):
     """A short KITTI-sized sequence: the field-model run as one rank and as two ranks on GPU 0 writes byte-identical folders
     (every rank makes its own frames from the frame index alone); RainAugment(particle_model='field') on the clip gives the
@@ -228,7 +201,7 @@ def test_driver_one_rank_two_ranks_and_the_augmenter_agree(tmp_path, built, monk
         main.main(common + ['--particle_model', 'field', '--noise_std', '2', '--output', os.path.join(tmp, 'outn')])
     env = dict(os.environ, RAIN_DEVICE='0', RAIN_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', RAIN_BATCH='2')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(_free_port()), os.path.join(h.ROOT, 'rain-rendering_amd', 'main.py')] + common +
+                        '--master-port', str(cases.free_port()), os.path.join(h.ROOT, 'rain-rendering_amd', 'main.py')] + common +
                        ['--particle_model', 'field', '--output', os.path.join(tmp, 'out2'), '--conflict_strategy', 'rename_folder'],
                        env=env, cwd=h.ROOT, capture_output=True, timeout=600)
     assert r.returncode == 0, (r.stdout.decode()[-3000:], r.stderr.decode()[-3000:])

@@ -20,14 +20,11 @@ import torch
 from PIL import Image
 
 import helpers as h
+import particle_cases as cases
 from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
-from test_gpu_particle_draws import H, KITTI_STEREO, W, _kitti, _set_rig
-from test_gpu_particle_field import _rh
-from test_gpu_particle_jitter import _same
-from test_gpu_particle_trajectory import MONO, _arc_poses, _set
-from test_particle_gusts_host import HZ, gust_cases
 
 pytestmark = pytest.mark.gpu
+W, H = cases.W, cases.H
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 trajmod = importlib.import_module('rain-rendering_amd.trajectory')
@@ -35,9 +32,6 @@ augment = importlib.import_module('rain-rendering_amd.augment')
 imgops = importlib.import_module('rain-rendering_amd.common.imgops')
 envmod = importlib.import_module('rain-rendering_amd.common.envmap')
 
-WIND = (-7.5, 2.0)
-DRAWS = ['counter', 'stream']
-SEED = 1234 + 2 ** 40
 RR_E_ARG = -1                                             # include/rainhip.h
 
 
@@ -45,27 +39,27 @@ def _check(rh, sims, want, what):
     got, cnt = rh.generate_drops(sims, H, W)
     for k in range(len(sims)):
         assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
-        _same(got[k], want[k], '%s: frame %d' % (what, k))
+        cases.same_nan_rotation(got[k], want[k], '%s: frame %d' % (what, k))
     return cnt
 
 
 # ---- 1. device == host statement -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 @pytest.mark.parametrize("jitter", [0.0, 5.0])
 def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _kitti()
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    opt = cases.kitti()
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     kw = dict(model='field', cam_hz=opt['cam_hz'])
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
         rh.set_particle_draws(draws)
         rh.set_particle_jitter(jitter)
-        for wind in ((0.0, 0.0), WIND):
+        for wind in ((0.0, 0.0), cases.WIND):
             rh.set_particle_wind(*wind)
-            for gusts, frames in gust_cases():
+            for gusts, frames in cases.gust_cases():
                 sims = particles.field_run_sims(sims1, frames)
                 want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=wind, gusts=gusts, **kw)
                 rh.set_particle_gusts(gusts)
@@ -77,61 +71,61 @@ def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
         rh.close()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
-@pytest.mark.parametrize("wind", [(0.0, 0.0), WIND], ids=['calm', 'wind'])
+@pytest.mark.parametrize("draws", cases.DRAWS)
+@pytest.mark.parametrize("wind", [(0.0, 0.0), cases.WIND], ids=['calm', 'wind'])
 def test_rig_records_equal_host_statement(tmp_path, built, wind, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=KITTI_STEREO)
-    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
-    rh = _rh(sc)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='rig', rig=cases.KITTI_STEREO)
+    kw = dict(model='rig', cam_hz=hz, rig=cases.KITTI_STEREO)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, opt)
+        cases.set_rig(rh, opt)
         rh.set_particle_draws(draws)
         rh.set_particle_wind(*wind)
-        for gusts, inst in gust_cases():
+        for gusts, inst in cases.gust_cases():
             sims = particles.rig_run_sims(sims1, inst, 2)
             want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=wind, gusts=gusts, **kw)          # frame 2 i + v
-            _set_rig(rh, opt)                                     # (a model change drops the series: set it after)
+            cases.set_rig(rh, opt)                                     # (a model change drops the series: set it after)
             rh.set_particle_gusts(gusts)
             for chunks in (1, 2):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
                 _check(rh, sims, want, 'rig, %d chunks, %s, wind %s, instants %s' % (chunks, draws, wind, inst))
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
             # view 1 alone: the same bits per view
-            _set_rig(rh, opt, active=[1])
+            cases.set_rig(rh, opt, active=[1])
             rh.set_particle_gusts(gusts)
             got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
             for i in range(len(inst)):
-                _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+                cases.same_nan_rotation(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
     finally:
         rh.close()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_arc_records_equal_host_statement(tmp_path, built, draws):
     """A single camera on an arc (10 m/s, 20 degrees a second): the gust is a world-frame vector like the mean wind; a jitter of 5
     degrees on top.  A series over the arc's nine instants at m = 0, inside and at m = n - 1, and one of a single interval."""
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    rig = MONO
-    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=rig, trajectory=traj)
+    rig = cases.MONO
+    traj = trajmod.Trajectory(np.array(cases.arc_poses(9)), 10.0)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='rig', rig=rig, trajectory=traj)
     kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set(rh, rig, traj, opt, hz)
+        cases.set_trajectory(rh, rig, traj, opt, hz)
         rh.set_particle_draws(draws)
         rh.set_particle_jitter(5.0)
-        rh.set_particle_wind(*WIND)
-        for gusts, inst in ((particles.gust_series(8, HZ, 4.0, 2.0, seed=9), [0, 7, 3]),
+        rh.set_particle_wind(*cases.WIND)
+        for gusts, inst in ((particles.gust_series(8, cases.HZ, 4.0, 2.0, seed=9), [0, 7, 3]),
                             (particles.GustSeries(3, np.array([[0.5, -0.25], [0.81, -0.37]])), [3])):
             sims = particles.rig_run_sims(sims1, inst, 1)
-            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=WIND, gusts=gusts, **kw)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=cases.WIND, gusts=gusts, **kw)
             rh.set_particle_gusts(gusts)
             for chunks in (1, 2):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
@@ -144,21 +138,21 @@ def test_arc_records_equal_host_statement(tmp_path, built, draws):
 # ---- 2. off again --------------------------------------------------------------------------------------------------
 def test_gusts_off_again_on_the_same_context(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
-    gusts, frames = gust_cases()[1]
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    opt = cases.kitti()
+    gusts, frames = cases.gust_cases()[1]
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     sims = particles.field_run_sims(sims1, frames)
     kw = dict(model='field', cam_hz=opt['cam_hz'], draws='counter')
-    gusty = particles.expected_records(sims, dgrid, cdf, sc.db, wind=WIND, gusts=gusts, **kw)
-    windy = particles.expected_records(sims, dgrid, cdf, sc.db, wind=WIND, **kw)
+    gusty = particles.expected_records(sims, dgrid, cdf, sc.db, wind=cases.WIND, gusts=gusts, **kw)
+    windy = particles.expected_records(sims, dgrid, cdf, sc.db, wind=cases.WIND, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)
     assert gusty[0].tobytes() != windy[0].tobytes() != plain[0].tobytes()
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
         rh.set_particle_draws('counter')
-        rh.set_particle_wind(*WIND)
+        rh.set_particle_wind(*cases.WIND)
         rh.set_particle_gusts(gusts)
         _check(rh, sims, gusty, 'field with the series')
         rh.set_particle_gusts(None)
@@ -174,24 +168,24 @@ def test_gusts_off_again_on_the_same_context(tmp_path, built):
 # ---- 3. launch counts ----------------------------------------------------------------------------------------------
 def test_a_series_adds_no_launch(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
-    gusts = particles.gust_series(4, HZ, 4.0, 2.0, seed=3)
-    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    opt = cases.kitti()
+    gusts = particles.gust_series(4, cases.HZ, 4.0, 2.0, seed=3)
+    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=cases.KITTI_STEREO)
     rig_run = (particles.rig_run_sims(sims_r, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
     sims_f, dgrid_f, cdf_f = particles.sim_frames(opt, 25, 1, seed=7, model='field')
     field_run = (particles.field_run_sims(sims_f, [0, 1, 3]), dgrid_f, cdf_f, dict(model='field', cam_hz=opt['cam_hz']))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.profile(True)
         for name, (sims, dgrid, cdf, kw) in (('k_field_particles', field_run), ('k_rig_particles', rig_run)):
             rh.set_particle_tables(dgrid, cdf)
             if kw['model'] == 'rig':
-                _set_rig(rh, opt)
+                cases.set_rig(rh, opt)
             else:
                 rh.set_particle_model('field', kw['cam_hz'])
             for chunks in (1, 2):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
-                for draws in DRAWS:
+                for draws in cases.DRAWS:
                     rh.set_particle_draws(draws)
                     counts = {}
                     for on in (False, True):
@@ -210,12 +204,12 @@ def test_a_series_adds_no_launch(tmp_path, built):
 # ---- 4. refusals ---------------------------------------------------------------------------------------------------
 def test_refusals(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     G = particles.GustSeries
     ok = np.array([[0.0, 0.0], [0.1, 0.0], [0.2, 0.1]])
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     kw = dict(model='field', cam_hz=opt['cam_hz'])
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         with pytest.raises(RuntimeError, match='gust'):          # the i.i.d. model has no time
@@ -362,7 +356,7 @@ def test_the_driver_writes_what_the_augmenter_renders(tmp_path, built, monkeypat
     rgb = np.stack([np.array(Image.open(os.path.join(img_dir, f)).convert('RGB')) for f in names])
     depth = np.stack([np.array(Image.open(os.path.join(img_dir, 'depth', f))).astype(np.float32) / 256. for f in names])
     aug = augment.RainAugment('kitti', streaks_db=db_dir, sequence='data_object/training', particle_model='field', draws='counter',
-                              gusts=particles.gust_series(16, HZ, 3.0, 2.0, seed=0))
+                              gusts=particles.gust_series(16, cases.HZ, 3.0, 2.0, seed=0))
     try:
         rainy, mask = aug(torch.from_numpy(rgb.transpose(0, 3, 1, 2).copy()).to(DEV), torch.from_numpy(depth).to(DEV), 25, np.arange(n))
         assert np.array_equal(rainy.cpu().numpy().transpose(0, 2, 3, 1), gusty)

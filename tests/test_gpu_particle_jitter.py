@@ -15,11 +15,11 @@ import pytest
 import torch
 
 import helpers as h
+import particle_cases as cases
 from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
-from test_gpu_particle_draws import H, KITTI_STEREO, W, _field_run, _iid_run, _kitti, _set_rig
-from test_gpu_particle_field import _rh
 
 pytestmark = pytest.mark.gpu
+W, H = cases.W, cases.H
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 augment = importlib.import_module('rain-rendering_amd.augment')
@@ -27,36 +27,23 @@ imgops = importlib.import_module('rain-rendering_amd.common.imgops')
 envmod = importlib.import_module('rain-rendering_amd.common.envmap')
 
 JITTER = 5.0
-DRAWS = ['counter', 'stream']
-
-
-def _same(got, want, what):
-    """Every field's bytes; NaN rotation terms are compared as NaN (sign and payload are the machine's)."""
-    assert len(got) == len(want), '%s: %d records on the device, %d on the host' % (what, len(got), len(want))
-    for name in h.hb.DROP_DTYPE.names:
-        a, b = got[name], want[name]
-        if name in ('rot_cos', 'rot_sin'):
-            nan = np.isnan(b)
-            assert np.array_equal(np.isnan(a), nan) and a[~nan].tobytes() == b[~nan].tobytes(), '%s: %s' % (what, name)
-        else:
-            assert a.tobytes() == b.tobytes(), '%s: %s' % (what, name)
 
 
 def _check(rh, sims, want, what):
     got, cnt = rh.generate_drops(sims, H, W)
     for k in range(len(sims)):
         assert int(cnt[k]) == len(want[k]) > 100, (what, k)
-        _same(got[k], want[k], '%s: frame %d' % (what, k))
+        cases.same_nan_rotation(got[k], want[k], '%s: frame %d' % (what, k))
     return cnt
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_iid_records_equal_host_statement(tmp_path, built, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    sims, dgrid, cdf, kw = _iid_run(_kitti())
+    sims, dgrid, cdf, kw = cases.iid_run(cases.kitti())
     want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=JITTER, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_draws(draws)
@@ -65,7 +52,7 @@ def test_iid_records_equal_host_statement(tmp_path, built, draws):
         # a capacity below the drop count: the count still tells, the records that fit are the first ones
         small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[0]) // 2, 1))
         assert np.array_equal(cnt_small, cnt)
-        _same(small[0], want[0][:len(want[0]) // 2], 'i.i.d., half the capacity')
+        cases.same_nan_rotation(small[0], want[0][:len(want[0]) // 2], 'i.i.d., half the capacity')
         rh.set_particle_jitter(0)                            # back to today's records on the same context
         _check(rh, sims, plain, 'i.i.d., %s, jitter off again' % draws)
     finally:
@@ -73,14 +60,14 @@ def test_iid_records_equal_host_statement(tmp_path, built, draws):
     assert want[0].tobytes() != plain[0].tobytes()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 @pytest.mark.parametrize("chunks", [1, 3])
 def test_field_records_equal_host_statement(tmp_path, built, chunks, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    sims, dgrid, cdf, kw = _field_run(_kitti())
+    sims, dgrid, cdf, kw = cases.field_run(cases.kitti())
     want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=JITTER, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
@@ -95,21 +82,21 @@ def test_field_records_equal_host_statement(tmp_path, built, chunks, draws):
     assert want[1].tobytes() != plain[1].tobytes()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_rig_records_equal_host_statement(tmp_path, built, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=KITTI_STEREO)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=cases.KITTI_STEREO)
     inst = [1, 2 ** 31 + 5]
     sims = particles.rig_run_sims(sims1, inst, 2)
-    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
+    kw = dict(model='rig', cam_hz=hz, rig=cases.KITTI_STEREO)
     want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=JITTER, **kw)          # frame 2 i + v
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, opt)
+        cases.set_rig(rh, opt)
         rh.set_particle_draws(draws)
         rh.set_particle_jitter(JITTER)
         for chunks in (1, 2):
@@ -117,11 +104,11 @@ def test_rig_records_equal_host_statement(tmp_path, built, draws):
             _check(rh, sims, want, 'rig, %d chunks, %s' % (chunks, draws))
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
         # view 1 alone: the same bits per view
-        _set_rig(rh, opt, active=[1])
+        cases.set_rig(rh, opt, active=[1])
         got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
         for i in range(len(inst)):
-            _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
-        _set_rig(rh, opt)
+            cases.same_nan_rotation(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+        cases.set_rig(rh, opt)
         rh.set_particle_jitter(0)
         _check(rh, sims, plain, 'rig, %s, jitter off again' % draws)
     finally:
@@ -131,21 +118,21 @@ def test_rig_records_equal_host_statement(tmp_path, built, draws):
 
 def test_the_jitter_adds_no_launch(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
-    sims1, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    opt = cases.kitti()
+    sims1, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=cases.KITTI_STEREO)
     rig_run = (particles.rig_run_sims(sims1, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.profile(True)
-        for name, (sims, dgrid, cdf, kw) in (('k_particles', _iid_run(opt)), ('k_field_particles', _field_run(opt)), ('k_rig_particles', rig_run)):
+        for name, (sims, dgrid, cdf, kw) in (('k_particles', cases.iid_run(opt)), ('k_field_particles', cases.field_run(opt)), ('k_rig_particles', rig_run)):
             rh.set_particle_tables(dgrid, cdf)
             if kw['model'] == 'rig':
-                _set_rig(rh, opt)
+                cases.set_rig(rh, opt)
             else:
                 rh.set_particle_model(kw['model'], kw.get('cam_hz', 0.0))
             for chunks in ((0,) if name == 'k_particles' else (1, 2)):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
-                for draws in DRAWS:
+                for draws in cases.DRAWS:
                     rh.set_particle_draws(draws)
                     counts = {}
                     for deg in (0.0, JITTER):
@@ -163,8 +150,8 @@ def test_the_jitter_adds_no_launch(tmp_path, built):
 
 def test_invalid_combinations_are_refused(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    sims, dgrid, cdf, _ = _iid_run(_kitti())
-    rh = _rh(sc)
+    sims, dgrid, cdf, _ = cases.iid_run(cases.kitti())
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         for bad in (-1.0, float('nan'), float('inf')):

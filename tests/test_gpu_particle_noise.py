@@ -18,6 +18,7 @@ import pytest
 from PIL import Image
 
 import helpers as h
+import particle_cases as cases
 
 pytestmark = pytest.mark.gpu
 
@@ -25,56 +26,18 @@ particles = importlib.import_module('rain-rendering_amd.tools.particles')
 db = importlib.import_module('rain-rendering_amd.common.db')
 
 
-def _options(dataset, **kw):
-    o = dict(db.settings(dataset))
-    o.pop('sequences', None)
-    o.update(kw)
-    return o
-
-
-def _rh(sc):
-    rh = h.hb.RainHip(0)
-    rh.set_streak_db(sc.db.streaks_light)
-    rh.set_camera(sc.cam)
-    return rh
-
-
-def _entries(sims, f_idx, entries):
-    """records of the run entries `entries` of a run whose entry p is frame f_idx[p]"""
-    n_sim = len(sims)
-    fr = sims[np.asarray(f_idx)[entries] % n_sim].copy()
-    fr['draw_seed'] = np.asarray(f_idx)[entries]
-    fr['run_pos'] = np.asarray(entries) + 1
-    return fr
-
-
-def _canon(a):
-    """a field with every NaN as the one quiet NaN: a streak turned to zero length has NaN rotation terms (0 / 0, as in the
-    reference), whose sign bit is the machine's (x86 and gfx950 differ); every other bit must agree"""
-    a = np.array(a)
-    if a.dtype.kind == 'f':
-        a[np.isnan(a)] = np.nan
-    return a.tobytes()
-
-
-def _same(got, want, what):
-    assert len(got) == len(want), '%s: %d drops on the device, %d on the host' % (what, len(got), len(want))
-    for name in h.hb.DROP_DTYPE.names:
-        assert _canon(got[name]) == _canon(want[name]), '%s: %s' % (what, name)
-
-
 @pytest.mark.parametrize("noise_std,noise_scale", [(3.0, 1.0), (10.0, 0.5)])
 @pytest.mark.parametrize("dataset,rs,rate", [('nuscenes', 1, 100), ('nuscenes', 1, 200), ('kitti', 1, 100), ('cityscapes', 2, 50)])
 def test_device_records_equal_host_statement_with_noise(tmp_path, built, dataset, rs, rate, noise_std, noise_scale):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0])})
     sims, dgrid, cdf = particles.sim_frames(opt, rate, 2, render_scale=rs, seed=99)
     f_idx = list(range(12))                                   # entry p: simulated frame p % 2, seed p
     run = particles.run_table(sims, 2, f_idx)
-    fr = _entries(sims, f_idx, [0, 2, 10, 1])                 # histories of 0, 1 and 5 entries (and 0 for the other frame)
+    fr = cases.entries(sims, f_idx, [0, 2, 10, 1])                 # histories of 0, 1 and 5 entries (and 0 for the other frame)
     want = particles.expected_records(fr, dgrid, cdf, sc.db, noise_std=noise_std, noise_scale=noise_scale, run=run)
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_noise(noise_std, noise_scale, *run)
@@ -86,39 +49,39 @@ def test_device_records_equal_host_statement_with_noise(tmp_path, built, dataset
         rh.close()
     for k, p in enumerate((0, 2, 10, 1)):
         assert int(cnt[k]) == len(want[k]) > 20
-        _same(got[k], want[k], 'entry %d' % p)
+        cases.same_nan_anywhere(got[k], want[k], 'entry %d' % p)
         assert (want[k]['type'] != 0).sum() > 10
     plain = fr.copy()
     plain['run_pos'] = 0
     for k, w in enumerate(particles.expected_records(plain, dgrid, cdf, sc.db)):
-        _same(quiet[k], w, 'noise off, frame %d' % k)
+        cases.same_nan_anywhere(quiet[k], w, 'noise off, frame %d' % k)
     assert got[2].tobytes() != quiet[2].tobytes()
 
 
 def test_held_state_in_order_out_of_order_and_per_rank(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 100, 3, seed=5, count=3000)
     f_idx = list(range(10))
     run = particles.run_table(sims, 3, f_idx)
-    want = particles.expected_records(_entries(sims, f_idx, list(range(10))), dgrid, cdf, sc.db, noise_std=4.0, noise_scale=1.0, run=run)
+    want = particles.expected_records(cases.entries(sims, f_idx, list(range(10))), dgrid, cdf, sc.db, noise_std=4.0, noise_scale=1.0, run=run)
     W, H = opt["cam_CCD_WH"]
-    a, b = _rh(sc), _rh(sc)
+    a, b = cases.rain_hip(sc), cases.rain_hip(sc)
     try:
         for rh in (a, b):
             rh.set_particle_tables(dgrid, cdf)
             rh.set_particle_noise(4.0, 1.0, *run)
         # in order, several entries per call, simulated frame 0 twice in the first call (entries 0 and 3)
         for call in ([0, 1, 2, 3], [4, 5, 6, 7, 8, 9], [2, 7], [9, 0, 6]):       # then out of order: resets
-            got, _ = a.generate_drops(_entries(sims, f_idx, call), H, W)
+            got, _ = a.generate_drops(cases.entries(sims, f_idx, call), H, W)
             for k, p in enumerate(call):
-                _same(got[k], want[p], 'context A, entry %d of call %s' % (p, call))
+                cases.same_nan_anywhere(got[k], want[p], 'context A, entry %d of call %s' % (p, call))
         for call in ([1, 3], [5, 7, 9]):                      # rank 1 of 2: the other entries are replayed, not rendered
-            got, _ = b.generate_drops(_entries(sims, f_idx, call), H, W)
+            got, _ = b.generate_drops(cases.entries(sims, f_idx, call), H, W)
             for k, p in enumerate(call):
-                _same(got[k], want[p], 'context B, entry %d' % p)
+                cases.same_nan_anywhere(got[k], want[p], 'context B, entry %d' % p)
         # a run_pos the run does not have, or one that names another frame / seed
-        bad = _entries(sims, f_idx, [3])
+        bad = cases.entries(sims, f_idx, [3])
         bad['run_pos'] = 11
         with pytest.raises(RuntimeError, match='run_pos'):
             a.generate_drops(bad, H, W)
@@ -136,16 +99,16 @@ def test_noisy_generated_tables_through_the_async_pipeline(tmp_path, built):
     imgops = importlib.import_module('rain-rendering_amd.common.imgops')
     H, W = 225, 400
     sc = h.Scene(tmp_path, H, W, 10, cam=h.NUSCENES)
-    opt = _options('nuscenes', cam_CCD_WH=[W, H])
+    opt = cases.options('nuscenes', cam_CCD_WH=[W, H])
     sims, dgrid, cdf = particles.sim_frames(opt, 100, 2, seed=3, count=900)
     f_idx = list(range(6))
     run = particles.run_table(sims, 2, f_idx)
-    fr = _entries(sims, f_idx, f_idx)
+    fr = cases.entries(sims, f_idx, f_idx)
     want = particles.expected_records(fr, dgrid, cdf, sc.db, noise_std=5.0, noise_scale=1.0, run=run)
     cs = sc.cam_settings
     consts = fogmod.FogRain(rain_intensity=100, focal=cs['focal_mm'] / 1000., f_number=cs['f_number'], angle=90, exposure=cs['exposure_ms'],
                             camera_gain=1.0).constants()
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_noise(5.0, 1.0, *run)
@@ -220,7 +183,7 @@ def test_main_device_particles_with_angular_noise(tmp_path, built):
     run = particles.run_table(sims, 3, list(range(n)))
     streaks = h.bw.DBManager(streaks_path=tex_dir, norm_coeff_path=norm)
     streaks.load_streak_database()
-    want = particles.expected_records(_entries(sims, list(range(n)), list(range(n))), dgrid, cdf, streaks, noise_std=3.0, noise_scale=1.0,
+    want = particles.expected_records(cases.entries(sims, list(range(n)), list(range(n))), dgrid, cdf, streaks, noise_std=3.0, noise_scale=1.0,
                                       run=run)
     focal = st['cam_focal'] / 1000.
     consts = fogmod.FogRain(rain_intensity=100, focal=focal, f_number=st['cam_f_number'], angle=90, exposure=st['cam_exposure'],

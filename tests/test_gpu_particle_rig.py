@@ -19,31 +19,20 @@ import torch
 from PIL import Image
 
 import helpers as h
-from test_gpu_particle_field import _free_port, _options, _rh, _same
+import particle_cases as cases
 
 pytestmark = pytest.mark.gpu
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-rigmod = importlib.import_module('rain-rendering_amd.rig')
 augment = importlib.import_module('rain-rendering_amd.augment')
 
 DEV = torch.device('cuda', 0)
-KITTI_STEREO = rigmod.Rig.stereo(0.54)
-RING6 = rigmod.Rig.yaw_ring([0, 55, 110, 180, -110, -55], 0.8)
-CONFIGS = [('kitti', 1, 25, KITTI_STEREO), ('kitti', 1, 100, KITTI_STEREO), ('cityscapes', 2, 25, rigmod.Rig.stereo(0.22)),
-           ('nuscenes', 1, 100, RING6)]
-IDS = ['kitti25-stereo', 'kitti100-stereo', 'cityscapes-rs2-stereo', 'nuscenes100-ring6']
 
 
-def _set_rig(rh, rig, opt, hz, active=None):
-    rh.set_particle_rig(rig.as_records(), rig.box(particles.FrameCamera(opt, 0)), active=active)
-    rh.set_particle_model('rig', hz)
-
-
-@pytest.mark.parametrize("dataset,rs,rate,rig", CONFIGS, ids=IDS)
+@pytest.mark.parametrize("dataset,rs,rate,rig", cases.CONFIGS, ids=cases.IDS)
 def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate, rig):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([30.0])})
     hz = opt['cam_hz']
     V = len(rig)
     sims1, dgrid, cdf = particles.sim_frames(opt, rate, 1, render_scale=rs, seed=1234 + 2 ** 40, model='rig', rig=rig)
@@ -51,35 +40,35 @@ def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate,
     sims = particles.rig_run_sims(sims1, inst, V)
     want = particles.expected_records(sims, dgrid, cdf, sc.db, model='rig', cam_hz=hz, rig=rig)          # frame i * V + v
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, rig, opt, hz)
+        cases.set_rig(rh, opt, rig)
         for chunks in (0, 1, 2, 64):
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
             got, cnt = rh.generate_drops(sims, H, W)
             for k in range(len(sims)):
                 assert int(cnt[k]) == len(want[k]) > 100
-                _same(got[k], want[k], 'instant %d view %d, %d chunks' % (k // V, k % V, chunks))
+                cases.same_bytes(got[k], want[k], 'instant %d view %d, %d chunks' % (k // V, k % V, chunks))
             alone, _ = rh.generate_drops(sims[V:2 * V], H, W)                  # a batch of one instant
             for v in range(V):
-                _same(alone[v], want[V + v], 'instant 1 alone, view %d, %d chunks' % (v, chunks))
+                cases.same_bytes(alone[v], want[V + v], 'instant 1 alone, view %d, %d chunks' % (v, chunks))
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
         # a subset of the views, and a permutation: the same tables per (instant, view), nothing else moves
         sub = [V - 1] if V == 2 else [4, 1, 2]
-        _set_rig(rh, rig, opt, hz, active=sub)
+        cases.set_rig(rh, opt, rig, active=sub)
         got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, len(sub)), H, W)
         for i in range(len(inst)):
             for a, v in enumerate(sub):
-                _same(got[i * len(sub) + a], want[i * V + v], 'active %r: instant %d view %d' % (sub, i, v))
+                cases.same_bytes(got[i * len(sub) + a], want[i * V + v], 'active %r: instant %d view %d' % (sub, i, v))
         perm = list(range(V))[::-1]
-        _set_rig(rh, rig, opt, hz, active=perm)
+        cases.set_rig(rh, opt, rig, active=perm)
         got, _ = rh.generate_drops(sims, H, W)
         for i in range(len(inst)):
             for a, v in enumerate(perm):
-                _same(got[i * V + a], want[i * V + v], 'active %r: instant %d view %d' % (perm, i, v))
+                cases.same_bytes(got[i * V + a], want[i * V + v], 'active %r: instant %d view %d' % (perm, i, v))
         # a capacity below the drop count: the count still tells, the records that fit are the first ones
-        _set_rig(rh, rig, opt, hz)
+        cases.set_rig(rh, opt, rig)
         small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[1]) // 2, 1))
         assert np.array_equal(cnt_small, cnt)
         assert small[1].tobytes() == want[1][:len(small[1])].tobytes()
@@ -89,7 +78,7 @@ def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate,
             got, cnt64 = rh.generate_drops(many, H, W)
             for k in range(len(many)):
                 assert int(cnt64[k]) == len(want64[k])
-                _same(got[k], want64[k], 'batch of 64 instants: frame %d' % k)
+                cases.same_bytes(got[k], want64[k], 'batch of 64 instants: frame %d' % k)
     finally:
         rh.close()
 
@@ -97,18 +86,18 @@ def test_device_records_equal_host_statement(tmp_path, built, dataset, rs, rate,
 def test_frame_path_renders_the_host_statements_records(tmp_path, built):
     """rr_render_frames with rr_frame_in.sim under the rig model (KITTI stereo) against the same call fed expected_records:
     count, drop status, mask and image identical."""
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     W, H = opt["cam_CCD_WH"]
-    rig = KITTI_STEREO
+    rig = cases.KITTI_STEREO
     sc = h.Scene(tmp_path, H, W, 10)
     sims, dgrid, cdf = particles.sim_frames(opt, 100, 1, seed=77, model='rig', rig=rig)
     sims = particles.rig_run_sims(sims, [5, 6], 2)
     want = particles.expected_records(sims, dgrid, cdf, sc.db, model='rig', cam_hz=opt['cam_hz'], rig=rig)
     bg, env = sc.frame_inputs(0)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, rig, opt, opt['cam_hz'])
+        cases.set_rig(rh, opt, rig)
         outs = rh.render_frames([dict(bg=bg, rainy_bg=bg, env_xyY=env, omega=sc.omega, sim=sims[k]) for k in range(4)])
         refs = rh.render_frames([dict(bg=bg, rainy_bg=bg, env_xyY=env, omega=sc.omega, drops=want[k]) for k in range(4)])
         with pytest.raises(RuntimeError, match='multiple'):
@@ -126,11 +115,11 @@ def test_frame_path_renders_the_host_statements_records(tmp_path, built):
 
 def test_other_models_bits_do_not_move(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     hz = opt['cam_hz']
     W, H = opt["cam_CCD_WH"]
-    rig = KITTI_STEREO
-    rh = _rh(sc)
+    rig = cases.KITTI_STEREO
+    rh = cases.rain_hip(sc)
     try:
         for model in ('iid', 'field'):
             sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=9, model=model)
@@ -140,7 +129,7 @@ def test_other_models_bits_do_not_move(tmp_path, built):
             rh.set_particle_tables(dgrid, cdf)
             rh.set_particle_model(model, hz)
             before, cb = rh.generate_drops(sims, H, W)
-            _set_rig(rh, rig, opt, hz)
+            cases.set_rig(rh, opt, rig)
             through, _ = rh.generate_drops(sims, H, W)           # (the other model's table under the rig model: other rain)
             rh.set_particle_model(model, hz)
             after, ca = rh.generate_drops(sims, H, W)
@@ -154,12 +143,12 @@ def test_other_models_bits_do_not_move(tmp_path, built):
 
 def test_invalid_combinations_are_refused(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
-    rig = KITTI_STEREO
+    opt = cases.options('kitti')
+    rig = cases.KITTI_STEREO
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, model='rig', rig=rig)
     sims = particles.rig_run_sims(sims, [0, 1], 2)
     views, box = rig.as_records(), rig.box(particles.FrameCamera(opt, 0))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         with pytest.raises(RuntimeError, match='needs a rig first'):
@@ -232,7 +221,7 @@ def test_driver_runs_per_view_and_the_augmenter_agree(tmp_path, built, monkeypat
         main.main(common[:-2] + ['--output', os.path.join(tmp, 'outx')])
     env = dict(os.environ, RAIN_DEVICE='0', RAIN_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', RAIN_BATCH='2')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(_free_port()), os.path.join(h.ROOT, 'rain-rendering_amd', 'main.py')] + common +
+                        '--master-port', str(cases.free_port()), os.path.join(h.ROOT, 'rain-rendering_amd', 'main.py')] + common +
                        ['--rig_view', '1', '--output', os.path.join(tmp, 'view1_2ranks'), '--conflict_strategy', 'rename_folder'],
                        env=env, cwd=h.ROOT, capture_output=True, timeout=600)
     assert r.returncode == 0, (r.stdout.decode()[-3000:], r.stderr.decode()[-3000:])
@@ -249,7 +238,7 @@ def test_driver_runs_per_view_and_the_augmenter_agree(tmp_path, built, monkeypat
     depth = np.stack([np.array(Image.open(os.path.join(img_dir, 'depth', f))).astype(np.float32) / 256. for f in names])
     files = np.stack([np.stack([np.array(Image.open(os.path.join(tmp, 'view%d' % v, sub, 'rainy_image', f)))[..., :3] for v in (0, 1)])
                       for f in names])                                  # [n, V, H, W, 3]
-    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='rig', rig=KITTI_STEREO)
+    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='rig', rig=cases.KITTI_STEREO)
     aug = augment.RainAugment('kitti', **kw)
     right = augment.RainAugment('kitti', views=[1], **kw)
     try:

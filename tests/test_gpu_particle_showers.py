@@ -21,14 +21,11 @@ import torch
 from PIL import Image
 
 import helpers as h
+import particle_cases as cases
 from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
-from test_gpu_particle_draws import H, KITTI_STEREO, W, _kitti, _set_rig
-from test_gpu_particle_field import _rh
-from test_gpu_particle_jitter import _same
-from test_gpu_particle_trajectory import MONO, _arc_poses, _set
-from test_particle_showers_host import HZ, PEAK, _gusts_over, rate_cases
 
 pytestmark = pytest.mark.gpu
+W, H = cases.W, cases.H
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 trajmod = importlib.import_module('rain-rendering_amd.trajectory')
@@ -36,15 +33,12 @@ augment = importlib.import_module('rain-rendering_amd.augment')
 imgops = importlib.import_module('rain-rendering_amd.common.imgops')
 envmod = importlib.import_module('rain-rendering_amd.common.envmap')
 
-WIND = (-7.5, 2.0)
-DRAWS = ['counter', 'stream']
-SEED = 1234 + 2 ** 40
 RR_E_ARG = -1                                             # include/rainhip.h
 R = particles.RateSeries
 # the deliberately dry one: the rate is 0 from the start, and a birth before the series takes its first value
-DRY = (R(0, [0.0] * 7, peak=PEAK), [0, 5])
+DRY = (R(0, [0.0] * 7, peak=cases.PEAK), [0, 5])
 # (mean wind, with a gust series): on and off, all four
-AIRS = [((0.0, 0.0), False), (WIND, False), ((0.0, 0.0), True), (WIND, True)]
+AIRS = [((0.0, 0.0), False), (cases.WIND, False), ((0.0, 0.0), True), (cases.WIND, True)]
 AIR_IDS = ['calm', 'wind', 'gusts', 'wind+gusts']
 
 
@@ -55,23 +49,23 @@ def _check(rh, sims, want, what, dry=False):
             assert int(cnt[k]) == len(want[k]) == 0, (what, k, int(cnt[k]), len(want[k]))
             continue
         assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
-        _same(got[k], want[k], '%s: frame %d' % (what, k))
+        cases.same_nan_rotation(got[k], want[k], '%s: frame %d' % (what, k))
     return cnt
 
 
 def _cases():
-    return [(rs, frames, False) for rs, frames in rate_cases()] + [DRY + (True,)]
+    return [(rs, frames, False) for rs, frames in cases.rate_cases()] + [DRY + (True,)]
 
 
 # ---- 1. device == host statement -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 @pytest.mark.parametrize("jitter", [0.0, 5.0])
 def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _kitti()
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    opt = cases.kitti()
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     kw = dict(model='field', cam_hz=opt['cam_hz'])
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
@@ -80,7 +74,7 @@ def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
         for wind, gusty in AIRS:
             rh.set_particle_wind(*wind)
             for rs, frames, dry in _cases():
-                gusts = _gusts_over(rs) if gusty else None
+                gusts = cases.gusts_over(rs) if gusty else None
                 sims = particles.field_run_sims(sims1, frames)
                 want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=wind, gusts=gusts, rate_series=rs, **kw)
                 rh.set_particle_gusts(gusts)
@@ -94,25 +88,25 @@ def test_field_records_equal_host_statement(tmp_path, built, jitter, draws):
         rh.close()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 @pytest.mark.parametrize("wind,gusty", AIRS, ids=AIR_IDS)
 def test_rig_records_equal_host_statement(tmp_path, built, wind, gusty, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=KITTI_STEREO)
-    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
-    rh = _rh(sc)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='rig', rig=cases.KITTI_STEREO)
+    kw = dict(model='rig', cam_hz=hz, rig=cases.KITTI_STEREO)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, opt)
+        cases.set_rig(rh, opt)
         rh.set_particle_draws(draws)
         rh.set_particle_wind(*wind)
         for rs, inst, dry in _cases():
-            gusts = _gusts_over(rs) if gusty else None
+            gusts = cases.gusts_over(rs) if gusty else None
             sims = particles.rig_run_sims(sims1, inst, 2)
             want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=wind, gusts=gusts, rate_series=rs, **kw)    # frame 2 i + v
-            _set_rig(rh, opt)                                     # (a model change drops the series: set them after)
+            cases.set_rig(rh, opt)                                     # (a model change drops the series: set them after)
             rh.set_particle_gusts(gusts)
             rh.set_particle_rate_series(rs)
             for chunks in (1, 2):
@@ -120,41 +114,41 @@ def test_rig_records_equal_host_statement(tmp_path, built, wind, gusty, draws):
                 _check(rh, sims, want, 'rig, %d chunks, %s, wind %s, gusts %s, instants %s' % (chunks, draws, wind, gusty, inst), dry)
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
             # view 1 alone: the same bits per view
-            _set_rig(rh, opt, active=[1])
+            cases.set_rig(rh, opt, active=[1])
             rh.set_particle_gusts(gusts)
             rh.set_particle_rate_series(rs)
             got, cnt = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
             for i in range(len(inst)):
                 assert int(cnt[i]) == len(want[2 * i + 1])
                 if not dry:
-                    _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+                    cases.same_nan_rotation(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
     finally:
         rh.close()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_arc_records_equal_host_statement(tmp_path, built, draws):
     """A single camera on an arc (10 m/s, 20 degrees a second) under the mean wind, a gust series and a jitter of 5 degrees: the
     decision is the slot's, made before any pose enters.  A series over the arc's nine instants that touches 0, at m = 0, inside and
     at m = n - 1, and one of a single interval."""
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    rig = MONO
-    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='rig', rig=rig, trajectory=traj)
+    rig = cases.MONO
+    traj = trajmod.Trajectory(np.array(cases.arc_poses(9)), 10.0)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='rig', rig=rig, trajectory=traj)
     kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set(rh, rig, traj, opt, hz)
+        cases.set_trajectory(rh, rig, traj, opt, hz)
         rh.set_particle_draws(draws)
         rh.set_particle_jitter(5.0)
-        rh.set_particle_wind(*WIND)
-        for rs, inst in ((R(0, [10.0, 18.0, 25.0, 12.0, 0.0, 6.0, 14.0, 20.0, 9.0]), [0, 7, 3]), (R(3, [12.0, 20.0], peak=PEAK), [3])):
-            gusts = _gusts_over(rs)
+        rh.set_particle_wind(*cases.WIND)
+        for rs, inst in ((R(0, [10.0, 18.0, 25.0, 12.0, 0.0, 6.0, 14.0, 20.0, 9.0]), [0, 7, 3]), (R(3, [12.0, 20.0], peak=cases.PEAK), [3])):
+            gusts = cases.gusts_over(rs)
             sims = particles.rig_run_sims(sims1, inst, 1)
-            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=WIND, gusts=gusts, rate_series=rs, **kw)
+            want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=5.0, wind=cases.WIND, gusts=gusts, rate_series=rs, **kw)
             rh.set_particle_gusts(gusts)
             rh.set_particle_rate_series(rs)
             for chunks in (1, 2):
@@ -168,15 +162,15 @@ def test_arc_records_equal_host_statement(tmp_path, built, draws):
 # ---- 2. off again --------------------------------------------------------------------------------------------------
 def test_the_series_off_again_on_the_same_context(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
-    rs, frames = rate_cases()[1]
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    opt = cases.kitti()
+    rs, frames = cases.rate_cases()[1]
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     sims = particles.field_run_sims(sims1, frames)
     kw = dict(model='field', cam_hz=opt['cam_hz'], draws='counter')
     thin = particles.expected_records(sims, dgrid, cdf, sc.db, rate_series=rs, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)
     assert all(len(a) < len(b) for a, b in zip(thin, plain))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
@@ -186,7 +180,7 @@ def test_the_series_off_again_on_the_same_context(tmp_path, built):
         _check(rh, sims, thin, 'field with the series')
         rh.set_particle_rate_series(None)
         _check(rh, sims, plain, 'series off: as before')
-        rh.set_particle_rate_series(R(0, [PEAK] * 7))           # a series at its peak: the records of no series
+        rh.set_particle_rate_series(R(0, [cases.PEAK] * 7))           # a series at its peak: the records of no series
         _check(rh, sims, plain, 'a series at its peak')
         rh.set_particle_rate_series(rs)                          # and on again
         _check(rh, sims, thin, 'the series again')
@@ -197,24 +191,24 @@ def test_the_series_off_again_on_the_same_context(tmp_path, built):
 # ---- 3. launch counts ----------------------------------------------------------------------------------------------
 def test_a_series_adds_no_launch(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     rs = R(0, [20.0, 10.0, 5.0, 15.0, 25.0])
-    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    sims_r, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=cases.KITTI_STEREO)
     rig_run = (particles.rig_run_sims(sims_r, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
     sims_f, dgrid_f, cdf_f = particles.sim_frames(opt, 25, 1, seed=7, model='field')
     field_run = (particles.field_run_sims(sims_f, [0, 1, 3]), dgrid_f, cdf_f, dict(model='field', cam_hz=opt['cam_hz']))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.profile(True)
         for name, (sims, dgrid, cdf, kw) in (('k_field_particles', field_run), ('k_rig_particles', rig_run)):
             rh.set_particle_tables(dgrid, cdf)
             if kw['model'] == 'rig':
-                _set_rig(rh, opt)
+                cases.set_rig(rh, opt)
             else:
                 rh.set_particle_model('field', kw['cam_hz'])
             for chunks in (1, 2):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
-                for draws in DRAWS:
+                for draws in cases.DRAWS:
                     rh.set_particle_draws(draws)
                     counts = {}
                     for on in (False, True):
@@ -233,11 +227,11 @@ def test_a_series_adds_no_launch(tmp_path, built):
 # ---- 4. refusals ---------------------------------------------------------------------------------------------------
 def test_refusals(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     ok = [25.0, 10.0, 16.0]
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=SEED, model='field')
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=cases.SEED, model='field')
     kw = dict(model='field', cam_hz=opt['cam_hz'])
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         with pytest.raises(RuntimeError, match='rate series'):   # the i.i.d. model has no time
@@ -370,7 +364,7 @@ def test_the_driver_writes_what_the_augmenter_renders(tmp_path, built, monkeypat
                 ['--device_particles', '--particle_model', 'field', '--showers', 'a,4']):
         with pytest.raises(SystemExit, match='--showers'):
             main._derive(main._parse(['--dataset', 'kitti', '-k', src, '-i', '25'] + bad))
-    series = particles.shower_series(16, HZ, 25.0, 2.0, 4.0)
+    series = particles.shower_series(16, cases.HZ, 25.0, 2.0, 4.0)
     aug = augment.RainAugment('kitti', streaks_db=db_dir, sequence='data_object/training', particle_model='field', draws='counter', showers=series)
     try:
         p = aug.plan(None, np.arange(n))

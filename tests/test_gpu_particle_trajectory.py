@@ -19,7 +19,7 @@ import torch
 from PIL import Image
 
 import helpers as h
-from test_gpu_particle_field import _options, _rh, _same
+import particle_cases as cases
 
 pytestmark = pytest.mark.gpu
 
@@ -29,42 +29,18 @@ trajmod = importlib.import_module('rain-rendering_amd.trajectory')
 augment = importlib.import_module('rain-rendering_amd.augment')
 
 DEV = torch.device('cuda', 0)
-KITTI_STEREO = rigmod.Rig.stereo(0.54)
-MONO = rigmod.Rig.from_spec('mono')
-
-
-def _pose(yaw_deg, pitch_deg=0.0, t=(0.0, 0.0, 0.0)):
-    P = np.zeros((3, 4))
-    P[:, :3] = rigmod._rot_y(yaw_deg) @ rigmod._rot_x(pitch_deg)
-    P[:, 3] = t
-    return P
-
-
-def _arc_poses(n, speed=10.0, yaw_rate_deg=20.0, hz=10.0):
-    om = np.deg2rad(yaw_rate_deg)
-    rad = speed / om
-    return [_pose(np.rad2deg(om * k / hz), 0.0, (-rad + rad * np.cos(om * k / hz), 0.0, -rad * np.sin(om * k / hz))) for k in range(n)]
 
 
 def _arc_with_a_far_pose():
     """Poses 0 .. 8: the arc (10 m/s, 20 deg/s, 10 Hz); poses 9 and 10: 1e5 m away, a metre apart, pitched."""
     far = np.array([6e4, 0.0, -8e4])
-    return trajmod.Trajectory(np.array(_arc_poses(9) + [_pose(140.0, 6.0, far), _pose(142.0, 6.5, far + np.array([0.4, 0.02, 0.9]))]), 10.0)
+    return trajmod.Trajectory(np.array(cases.arc_poses(9) + [cases.pose(140.0, 6.0, far), cases.pose(142.0, 6.5, far + np.array([0.4, 0.02, 0.9]))]), 10.0)
 
 
-def _set(rh, rig, traj, opt, hz, active=None, rows=None):
-    cam = particles._traj_cam(particles.FrameCamera(opt, 0))
-    rh.set_particle_rig(rig.as_records(), traj.box(rig, cam), active=active)
-    rh.set_particle_model('rig', hz)
-    po = traj.compose(rig, cam.exposure)
-    rows = np.arange(len(po)) if rows is None else np.asarray(rows)
-    rh.set_particle_trajectory(po[rows], frame=rows)
-
-
-@pytest.mark.parametrize("rig", [KITTI_STEREO, MONO], ids=['kitti25-stereo', 'kitti25-mono'])
+@pytest.mark.parametrize("rig", [cases.KITTI_STEREO, cases.MONO], ids=['kitti25-stereo', 'kitti25-mono'])
 def test_device_records_equal_host_statement(tmp_path, built, rig):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     hz = opt['cam_hz']
     V = len(rig)
     traj = _arc_with_a_far_pose()
@@ -76,31 +52,31 @@ def test_device_records_equal_host_statement(tmp_path, built, rig):
     want = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)          # frame i * V + v
     assert all(want[V + v].tobytes() == want[3 * V + v].tobytes() for v in range(V)) and want[0].tobytes() != want[V].tobytes()
     W, H = opt["cam_CCD_WH"]
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set(rh, rig, traj, opt, hz, rows=rows)
+        cases.set_trajectory(rh, rig, traj, opt, hz, rows=rows)
         for chunks in (0, 1, 2, 64):
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
             got, cnt = rh.generate_drops(sims, H, W)
             for k in range(len(sims)):
                 assert int(cnt[k]) == len(want[k]) > 100, (k, chunks, int(cnt[k]), len(want[k]))
-                _same(got[k], want[k], 'instant %d view %d, %d chunks' % (inst[k // V], k % V, chunks))
+                cases.same_bytes(got[k], want[k], 'instant %d view %d, %d chunks' % (inst[k // V], k % V, chunks))
             alone, _ = rh.generate_drops(sims[2 * V:3 * V], H, W)                # a batch of one instant: row 3 of the table
             for v in range(V):
-                _same(alone[v], want[2 * V + v], 'instant 7 alone, view %d, %d chunks' % (v, chunks))
+                cases.same_bytes(alone[v], want[2 * V + v], 'instant 7 alone, view %d, %d chunks' % (v, chunks))
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
         if V == 2:                                               # a subset of the views, and a permutation
-            _set(rh, rig, traj, opt, hz, active=[1], rows=rows)
+            cases.set_trajectory(rh, rig, traj, opt, hz, active=[1], rows=rows)
             got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
             for i in range(len(inst)):
-                _same(got[i], want[i * V + 1], 'active [1]: instant %d' % inst[i])
-            _set(rh, rig, traj, opt, hz, active=[1, 0], rows=rows)
+                cases.same_bytes(got[i], want[i * V + 1], 'active [1]: instant %d' % inst[i])
+            cases.set_trajectory(rh, rig, traj, opt, hz, active=[1, 0], rows=rows)
             got, _ = rh.generate_drops(sims, H, W)
             for i in range(len(inst)):
                 for a, v in enumerate([1, 0]):
-                    _same(got[i * V + a], want[i * V + v], 'active [1, 0]: instant %d view %d' % (inst[i], v))
-            _set(rh, rig, traj, opt, hz, rows=rows)
+                    cases.same_bytes(got[i * V + a], want[i * V + v], 'active [1, 0]: instant %d view %d' % (inst[i], v))
+            cases.set_trajectory(rh, rig, traj, opt, hz, rows=rows)
         # a capacity below the drop count: the count still tells, the records that fit are the first ones
         small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[1]) // 2, 1))
         assert np.array_equal(cnt_small, cnt)
@@ -111,12 +87,12 @@ def test_device_records_equal_host_statement(tmp_path, built, rig):
 
 def test_coincident_ends_and_turning_it_off(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})     # speed_mps stays in the formula: a drift of the world
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})     # speed_mps stays in the formula: a drift of the world
     hz = opt['cam_hz']
     W, H = opt["cam_CCD_WH"]
-    rig = KITTI_STEREO
+    rig = cases.KITTI_STEREO
     cam = particles.FrameCamera(opt, 0)
-    still = trajmod.Trajectory(np.array([_pose(37.0, 5.0, (1e3, 0.4, -2e3))] * 3), 10.0)
+    still = trajmod.Trajectory(np.array([cases.pose(37.0, 5.0, (1e3, 0.4, -2e3))] * 3), 10.0)
     po = still.compose(rig, cam.exposure)
     assert po['R0'].tobytes() == po['R1'].tobytes() and po['c0'].tobytes() == po['c1'].tobytes()
     box = still.box(rig, cam)
@@ -124,7 +100,7 @@ def test_coincident_ends_and_turning_it_off(tmp_path, built):
     sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=5, model='rig', rig=still.bind(rig))
     assert float(sims1['speed_mps'][0]) > 8.0
     sims = particles.rig_run_sims(sims1, [1, 2], 2)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_rig(seen.as_records(), box)
@@ -175,21 +151,21 @@ def _slots_of_records(s, dgrid, cdf, sc, hz, rig, view, traj):
 
 def test_counter_draws_and_jitter_are_coherent(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     hz = opt['cam_hz']
     W, H = opt["cam_CCD_WH"]
-    rig = KITTI_STEREO
-    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
+    rig = cases.KITTI_STEREO
+    traj = trajmod.Trajectory(np.array(cases.arc_poses(9)), 10.0)
     JIT = 3.0
     sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=21, model='rig', rig=rig, trajectory=traj)
     sims = particles.rig_run_sims(sims1, [4, 5], 2)
     kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj, draws='counter')
     want = particles.expected_records(sims, dgrid, cdf, sc.db, jitter=JIT, **kw)
     straight = particles.expected_records(sims, dgrid, cdf, sc.db, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set(rh, rig, traj, opt, hz)
+        cases.set_trajectory(rh, rig, traj, opt, hz)
         rh.set_particle_draws('counter')
         rh.set_particle_jitter(JIT)
         got, cnt = rh.generate_drops(sims, H, W)
@@ -199,8 +175,8 @@ def test_counter_draws_and_jitter_are_coherent(tmp_path, built):
         rh.close()
     for k in range(4):
         assert int(cnt[k]) == len(want[k]) > 100
-        _same(got[k], want[k], 'counter draws + jitter, frame %d' % k)
-        _same(got0[k], straight[k], 'counter draws, frame %d' % k)
+        cases.same_bytes(got[k], want[k], 'counter draws + jitter, frame %d' % k)
+        cases.same_bytes(got0[k], straight[k], 'counter draws, frame %d' % k)
     cam = particles._traj_cam(particles.FrameCamera(opt, 0))
     seed = int(sims[0]['key0']) | (int(sims[0]['key1']) << 32)
     ids, lives = [], []
@@ -270,7 +246,7 @@ def test_driver_runs_per_view_and_the_augmenter_agree(tmp_path, built, monkeypat
     files = np.stack([np.stack([np.array(Image.open(os.path.join(tmp, 'view%d' % v, sub, 'rainy_image', f)))[..., :3] for v in (0, 1)])
                       for f in names])                                  # [n, V, H, W, 3]
     traj = trajmod.Trajectory.from_file(poses, hz=10.0)
-    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='rig', rig=KITTI_STEREO)
+    kw = dict(streaks_db=streaks_db, sequence='data_object/training', particle_model='rig', rig=cases.KITTI_STEREO)
     with pytest.raises(ValueError, match="needs particle_model='rig'"):
         augment.RainAugment('kitti', streaks_db=streaks_db, sequence='data_object/training', particle_model='field', trajectory=traj)
     aug = augment.RainAugment('kitti', trajectory=traj, **kw)
@@ -297,13 +273,13 @@ def test_driver_runs_per_view_and_the_augmenter_agree(tmp_path, built, monkeypat
 
 def test_invalid_arguments_are_refused(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
-    rig = KITTI_STEREO
+    opt = cases.options('kitti')
+    rig = cases.KITTI_STEREO
     cam = particles._traj_cam(particles.FrameCamera(opt, 0))
-    traj = trajmod.Trajectory(np.array(_arc_poses(4)), 10.0)
+    traj = trajmod.Trajectory(np.array(cases.arc_poses(4)), 10.0)
     po = np.array(traj.compose(rig, cam.exposure))
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, model='rig', rig=rig, trajectory=traj)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         with pytest.raises(RuntimeError, match='no rig set'):
@@ -344,7 +320,7 @@ def test_invalid_arguments_are_refused(tmp_path, built):
         with pytest.raises(RuntimeError, match='angular noise'):
             rh.set_particle_noise(2.0, 1.0, [0], [0])
         # a rig with another number of views drops the table: the one-view rig runs as the plain rig model
-        rh.set_particle_rig(MONO.as_records(), MONO.box(cam))
+        rh.set_particle_rig(cases.MONO.as_records(), cases.MONO.box(cam))
         got, cnt = rh.generate_drops(particles.rig_run_sims(sims, [2], 1), 375, 1242)
         assert int(cnt[0]) > 100
     finally:

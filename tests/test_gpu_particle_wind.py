@@ -1,4 +1,4 @@
-"""GPU tier: the mean wind on the device (rr_set_particle_wind; the WIND instantiations of k_particles, k_field_particles and
+"""GPU tier: the mean wind on the device (rr_set_particle_wind; the cases.WIND instantiations of k_particles, k_field_particles and
 k_rig_particles, count passes included).
 
   1. device records == the host statement (tools/particles.py expected_records(wind=)), bit for bit, counts included: i.i.d. (and a
@@ -21,14 +21,11 @@ import torch
 from PIL import Image
 
 import helpers as h
+import particle_cases as cases
 from test_gpu_augment import DEV, _planar, _scene, streaks_db          # noqa: F401  (streaks_db: a fixture)
-from test_gpu_particle_draws import H, KITTI_STEREO, W, _field_run, _iid_run, _kitti, _set_rig
-from test_gpu_particle_field import _rh
-from test_gpu_particle_jitter import _same
-from test_gpu_particle_noise import _entries
-from test_gpu_particle_trajectory import MONO, _arc_poses, _set
 
 pytestmark = pytest.mark.gpu
+W, H = cases.W, cases.H
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 trajmod = importlib.import_module('rain-rendering_amd.trajectory')
@@ -36,34 +33,31 @@ augment = importlib.import_module('rain-rendering_amd.augment')
 imgops = importlib.import_module('rain-rendering_amd.common.imgops')
 envmod = importlib.import_module('rain-rendering_amd.common.envmap')
 
-WIND = (-7.5, 2.0)
-DRAWS = ['counter', 'stream']
-
 
 def _check(rh, sims, want, what):
     got, cnt = rh.generate_drops(sims, H, W)
     for k in range(len(sims)):
         assert int(cnt[k]) == len(want[k]) > 100, (what, k, int(cnt[k]), len(want[k]))
-        _same(got[k], want[k], '%s: frame %d' % (what, k))
+        cases.same_nan_rotation(got[k], want[k], '%s: frame %d' % (what, k))
     return cnt
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_iid_records_equal_host_statement(tmp_path, built, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    sims, dgrid, cdf, kw = _iid_run(_kitti())
-    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)
+    sims, dgrid, cdf, kw = cases.iid_run(cases.kitti())
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=cases.WIND, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_draws(draws)
-        rh.set_particle_wind(*WIND)
+        rh.set_particle_wind(*cases.WIND)
         cnt = _check(rh, sims, want, 'i.i.d., %s' % draws)
         # a capacity below the drop count: the count still tells, the records that fit are the first ones
         small, cnt_small = rh.generate_drops(sims, H, W, cap=max(len(want[0]) // 2, 1))
         assert np.array_equal(cnt_small, cnt)
-        _same(small[0], want[0][:len(want[0]) // 2], 'i.i.d., half the capacity')
+        cases.same_nan_rotation(small[0], want[0][:len(want[0]) // 2], 'i.i.d., half the capacity')
         rh.set_particle_wind(0, 0)                           # back to today's records on the same context
         _check(rh, sims, plain, 'i.i.d., %s, wind off again' % draws)
     finally:
@@ -71,21 +65,21 @@ def test_iid_records_equal_host_statement(tmp_path, built, draws):
     assert want[0].tobytes() != plain[0].tobytes()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 @pytest.mark.parametrize("jitter", [0.0, 5.0])
 @pytest.mark.parametrize("chunks", [1, 3])
 def test_field_records_equal_host_statement(tmp_path, built, chunks, jitter, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    sims, dgrid, cdf, kw = _field_run(_kitti())
-    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=WIND, **kw)
+    sims, dgrid, cdf, kw = cases.field_run(cases.kitti())
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, wind=cases.WIND, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=jitter, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         rh.set_particle_model('field', kw['cam_hz'])
         rh.set_particle_draws(draws)
         rh.set_particle_jitter(jitter)
-        rh.set_particle_wind(*WIND)
+        rh.set_particle_wind(*cases.WIND)
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
         _check(rh, sims, want, 'field, %d chunks, %s, jitter %g' % (chunks, draws, jitter))
         rh.set_particle_wind(0, 0)
@@ -95,33 +89,33 @@ def test_field_records_equal_host_statement(tmp_path, built, chunks, jitter, dra
     assert want[1].tobytes() != plain[1].tobytes()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_rig_records_equal_host_statement(tmp_path, built, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=KITTI_STEREO)
+    sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=cases.KITTI_STEREO)
     inst = [1, 2 ** 31 + 5]
     sims = particles.rig_run_sims(sims1, inst, 2)
-    kw = dict(model='rig', cam_hz=hz, rig=KITTI_STEREO)
-    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)          # frame 2 i + v
+    kw = dict(model='rig', cam_hz=hz, rig=cases.KITTI_STEREO)
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=cases.WIND, **kw)          # frame 2 i + v
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set_rig(rh, opt)
+        cases.set_rig(rh, opt)
         rh.set_particle_draws(draws)
-        rh.set_particle_wind(*WIND)
+        rh.set_particle_wind(*cases.WIND)
         for chunks in (1, 2):
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
             _check(rh, sims, want, 'rig, %d chunks, %s' % (chunks, draws))
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
         # view 1 alone: the same bits per view
-        _set_rig(rh, opt, active=[1])
+        cases.set_rig(rh, opt, active=[1])
         got, _ = rh.generate_drops(particles.rig_run_sims(sims1, inst, 1), H, W)
         for i in range(len(inst)):
-            _same(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
-        _set_rig(rh, opt)
+            cases.same_nan_rotation(got[i], want[2 * i + 1], 'active [1]: instant %d' % i)
+        cases.set_rig(rh, opt)
         rh.set_particle_wind(0, 0)
         _check(rh, sims, plain, 'rig, %s, wind off again' % draws)
     finally:
@@ -129,26 +123,26 @@ def test_rig_records_equal_host_statement(tmp_path, built, draws):
     assert want[0].tobytes() != plain[0].tobytes()
 
 
-@pytest.mark.parametrize("draws", DRAWS)
+@pytest.mark.parametrize("draws", cases.DRAWS)
 def test_trajectory_records_equal_host_statement(tmp_path, built, draws):
     """A single camera on an arc (10 m/s, 20 degrees a second): at instant 7 it has yawed 14 degrees; the wind stays a world vector."""
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
+    opt = cases.kitti()
     hz = opt['cam_hz']
-    rig = MONO
-    traj = trajmod.Trajectory(np.array(_arc_poses(9)), 10.0)
+    rig = cases.MONO
+    traj = trajmod.Trajectory(np.array(cases.arc_poses(9)), 10.0)
     sims1, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=rig, trajectory=traj)
     inst = [0, 7, 3]
     sims = particles.rig_run_sims(sims1, inst, 1)
     kw = dict(model='rig', cam_hz=hz, rig=rig, trajectory=traj)
-    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=WIND, **kw)
+    want = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, wind=cases.WIND, **kw)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
-        _set(rh, rig, traj, opt, hz)
+        cases.set_trajectory(rh, rig, traj, opt, hz)
         rh.set_particle_draws(draws)
-        rh.set_particle_wind(*WIND)
+        rh.set_particle_wind(*cases.WIND)
         for chunks in (1, 2):
             rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
             _check(rh, sims, want, 'trajectory, %d chunks, %s' % (chunks, draws))
@@ -162,31 +156,31 @@ def test_trajectory_records_equal_host_statement(tmp_path, built, draws):
 
 def test_the_wind_adds_no_launch(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _kitti()
-    sims1, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=KITTI_STEREO)
+    opt = cases.kitti()
+    sims1, dgrid_r, cdf_r = particles.sim_frames(opt, 25, 1, seed=7, model='rig', rig=cases.KITTI_STEREO)
     rig_run = (particles.rig_run_sims(sims1, [1, 2], 2), dgrid_r, cdf_r, dict(model='rig', cam_hz=opt['cam_hz']))
-    rh = _rh(sc)
+    rh = cases.rain_hip(sc)
     try:
         rh.profile(True)
-        for name, (sims, dgrid, cdf, kw) in (('k_particles', _iid_run(opt)), ('k_field_particles', _field_run(opt)), ('k_rig_particles', rig_run)):
+        for name, (sims, dgrid, cdf, kw) in (('k_particles', cases.iid_run(opt)), ('k_field_particles', cases.field_run(opt)), ('k_rig_particles', rig_run)):
             rh.set_particle_tables(dgrid, cdf)
             if kw['model'] == 'rig':
-                _set_rig(rh, opt)
+                cases.set_rig(rh, opt)
             else:
                 rh.set_particle_model(kw['model'], kw.get('cam_hz', 0.0))
             for chunks in ((0,) if name == 'k_particles' else (1, 2)):
                 rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, chunks)
-                for draws in DRAWS:
+                for draws in cases.DRAWS:
                     rh.set_particle_draws(draws)
                     counts = {}
-                    for wind in ((0.0, 0.0), WIND):
+                    for wind in ((0.0, 0.0), cases.WIND):
                         rh.set_particle_wind(*wind)
                         rh.profile_reset()
                         rh.generate_drops(sims, H, W)
                         stats = rh.profile_read()
                         counts[wind] = {k: v[0] for k, v in stats.items()}
                         assert stats[name][0] >= 1, (name, draws, wind, stats)
-                    assert counts[(0.0, 0.0)] == counts[WIND], (name, chunks, draws, counts)
+                    assert counts[(0.0, 0.0)] == counts[cases.WIND], (name, chunks, draws, counts)
         rh.set_option(h.hb.RR_OPT_FIELD_CHUNKS, 0)
     finally:
         rh.close()
@@ -194,8 +188,8 @@ def test_the_wind_adds_no_launch(tmp_path, built):
 
 def test_refusals_and_noise_with_a_wind(tmp_path, built):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    sims, dgrid, cdf, kw = _iid_run(_kitti())
-    rh = _rh(sc)
+    sims, dgrid, cdf, kw = cases.iid_run(cases.kitti())
+    rh = cases.rain_hip(sc)
     try:
         rh.set_particle_tables(dgrid, cdf)
         for bad in ((float('nan'), 0.0), (0.0, float('nan')), (float('inf'), 0.0), (0.0, -float('inf')), (100.5, 0.0), (0.0, -101.0)):
@@ -205,17 +199,17 @@ def test_refusals_and_noise_with_a_wind(tmp_path, built):
         rh.set_particle_wind(3.0, 0.0)
         got, cnt = rh.generate_drops(sims, H, W)                 # a refusal leaves the context working, with the last good wind
         want = particles.expected_records(sims, dgrid, cdf, sc.db, wind=(3.0, 0.0), **kw)
-        _same(got[0], want[0], 'after the refusals')
+        cases.same_nan_rotation(got[0], want[0], 'after the refusals')
         # angular noise stays allowed where it is today: the i.i.d. model -- the chains start from the windy pristine records
         f_idx = [0, 1, 2, 3]                                     # entry p: simulated frame p % 3, seed p
         run = particles.run_table(sims, len(sims), f_idx)
-        noisy = _entries(sims, f_idx, [0, 3])                    # histories of 0 entries and of 1 (frame 0 again)
+        noisy = cases.entries(sims, f_idx, [0, 3])                    # histories of 0 entries and of 1 (frame 0 again)
         rh.set_particle_noise(2.0, 1.0, *run)
         got, cnt = rh.generate_drops(noisy, H, W)
         want = particles.expected_records(noisy, dgrid, cdf, sc.db, noise_std=2.0, noise_scale=1.0, run=run, wind=(3.0, 0.0))
         for k in range(2):
             assert int(cnt[k]) == len(want[k]) > 100
-            _same(got[k], want[k], 'noise with a wind: frame %d' % k)
+            cases.same_nan_rotation(got[k], want[k], 'noise with a wind: frame %d' % k)
     finally:
         rh.close()
 

@@ -1,103 +1,42 @@
 """CPU tier: counter-based per-drop draws (tools/particles.py counter_picks / expected_records(draws='counter'), rr_particles.h
 texture_pick, rr_set_particle_draws) -- the texture pick from the drop's own Philox counter instead of numpy's stream.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/draws_emu.cpp: the code the counter-mode kernels run) == numpy, bit
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code the counter-mode kernels run) == numpy, bit
      for bit, for the i.i.d., field and rig models;
   2. coherence: a field slot keeps its pick from frame k to k + 1 inside one life, a rig slot in both stereo views of an instant;
      the stream mode's picks of the same pairs agree about one time in ten (the control);
   3. law: the ten picks are equally likely (chi-square, both modes through the same threshold);
   4. the counter mode changes tex_index only, and only its last decimal digit;
   5. every refusal of the Python layer and of the driver's argument handling."""
-import ctypes
 import importlib
-import os
 
 import numpy as np
 import pytest
 
 import helpers as h
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-rigmod = importlib.import_module('rain-rendering_amd.rig')
-db = importlib.import_module('rain-rendering_amd.common.db')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-KITTI_STEREO = rigmod.Rig.stereo(0.54)                    # KITTI's documented baseline
-MODEL_ID = {'iid': 0, 'field': 1, 'rig': 2}               # RR_PARTICLES_*
 CHI2_9_999 = 27.88                                        # chi-square, 9 degrees of freedom: P(X > 27.88) = 0.001
-
-
-def _options(dataset='kitti', **kw):
-    o = dict(db.settings(dataset))
-    o.pop('sequences', None)
-    o.update(kw)
-    return o
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libdrawsemu.so'))
-    V = ctypes.c_void_p
-    lib.rr_emu_iid_picks.argtypes = [V, V, V, ctypes.c_int32, V]
-    lib.rr_emu_field_picks.argtypes = [V, ctypes.c_double, V, V, ctypes.c_int32, V, V]
-    lib.rr_emu_rig_picks.argtypes = [V, ctypes.c_double, V, V, V, ctypes.c_int32, V, V]
-    lib.rr_emu_counter_records.argtypes = [ctypes.c_int32, V, ctypes.c_double, V, V, V, V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, V, V,
-                                           ctypes.c_int32]
-    return lib
-
-
-def _run(model, opt, rate, frames, seed, rig=None, rs=1, count=None):
-    """(sims of the rendered frames `frames`, d_grid, cdf, keyword arguments of expected_records) of a run under `model`; the rig
-    model's records come V per instant."""
-    n_sim = 1
-    sims, dgrid, cdf = particles.sim_frames(opt, rate, n_sim, render_scale=rs, seed=seed, model=model, rig=rig, count=count)
-    kw = dict(model=model)
-    if model == 'iid':
-        sims = np.ascontiguousarray(sims[np.zeros(len(frames), np.int64)])
-        sims['frame'] = np.asarray(frames, np.uint32)     # (a simulated frame per entry: the i.i.d. pick is a function of it)
-        sims['draw_seed'] = np.asarray(frames, np.uint32)
-    elif model == 'field':
-        sims = particles.field_run_sims(sims, frames)
-        kw.update(cam_hz=opt['cam_hz'])
-    else:
-        sims = particles.rig_run_sims(sims, frames, len(rig))
-        kw.update(cam_hz=opt['cam_hz'], rig=rig)
-    return sims, dgrid, cdf, kw
-
-
-def _kept(s, dgrid, cdf, sdb, model, cam_hz=None, rig=None, view=0):
-    """(particle / slot number, life) of the records expected_records makes of the one record `s`, in their order."""
-    hb = importlib.import_module('rain-rendering_amd.hip_backend')
-    table, _, W, H = particles._loaded_table(s, dgrid, cdf, sdb, 'kitti', model, cam_hz, rig, view)
-    pid = table.pid[hb.filter_streaks(table, W, H)]
-    if model == 'iid':
-        return pid, np.zeros(len(pid))
-    cam = type('Cam', (), dict(W=int(s['sensor_w']), H=int(s['sensor_h']), fpx=float(s['fpx']), exposure=float(s['exposure_s']),
-                               speed=float(s['speed_mps'])))()
-    seed = int(s['key0']) | (int(s['key1']) << 32)
-    tab, n = cdf[int(s['table'])], int(s['n_particles'])
-    if model == 'field':
-        _, life = particles.make_field_particles(cam, dgrid, tab, n, int(s['frame']), seed, float(cam_hz), cull=False)
-    else:
-        _, life = particles.make_rig_particles(cam, dgrid, tab, n, int(s['frame']), seed, float(cam_hz), rig.views[view],
-                                               particles._rig_box(rig, cam, float(s['margin'])), cull=False)
-    return pid, life[pid]
+    return pe.load()
 
 
 # ---- 1. g++ == numpy -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", ['iid', 'field', 'rig'])
 def test_gxx_build_equals_numpy(tmp_path, emu, model):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     hz = float(opt['cam_hz'])
-    rig = KITTI_STEREO if model == 'rig' else None
+    rig = cases.KITTI_STEREO if model == 'rig' else None
     V = len(rig) if rig is not None else 1
     seed = 1234 + 2 ** 40
-    sims, dgrid, cdf, kw = _run(model, opt, 25, [0, 1, 2 ** 31 + 5], seed, rig)
+    sims, dgrid, cdf, kw = cases.run(model, opt, 25, [0, 1, 2 ** 31 + 5], seed, rig)
     want = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', **kw)
     assert len(want) == 3 * V
     W, H = opt["cam_CCD_WH"]
@@ -106,33 +45,31 @@ def test_gxx_build_equals_numpy(tmp_path, emu, model):
     cam = particles.FrameCamera(opt, 0)
     box = np.array(rig.box(cam), np.float64) if rig is not None else np.zeros(3)
     views = rig.as_records() if rig is not None else None
+    total = 0
     for i, s in enumerate(sims):
-        one = np.ascontiguousarray(sims[i:i + 1])
         n = int(s['n_particles'])
+        view = views[i % V:i % V + 1] if views is not None else None
+        run = pe.run(model=model, sim=sims[i:i + 1], cam_hz=hz, view=view, box=box, dgrid=dgrid, cdf=tab, counter=True)
         # the pick of every particle / slot, kept or not
-        pick, life = np.full(n, -1, np.int32), np.zeros(n)
+        _, _, life, pick = pe.all_slots(run)
         if model == 'iid':
-            emu.rr_emu_iid_picks(_p(one), _p(dgrid), _p(tab), len(dgrid), _p(pick))
             ref = particles.counter_picks(seed, np.arange(n), frame=int(s['frame']))
         elif model == 'field':
-            emu.rr_emu_field_picks(_p(one), hz, _p(dgrid), _p(tab), len(dgrid), _p(pick), _p(life))
             _, g = particles.make_field_particles(cam, dgrid, tab, n, int(s['frame']), seed, hz, cull=False)
             assert np.array_equal(life, g)
             ref = particles.counter_picks(seed, np.arange(n), life=g)
         else:
-            emu.rr_emu_rig_picks(_p(one), hz, _p(box), _p(dgrid), _p(tab), len(dgrid), _p(pick), _p(life))
             g = particles.rig_state(cam, dgrid, tab, n, int(s['frame']), seed, hz, box)['life']
             assert np.array_equal(life, g)
             ref = particles.counter_picks(seed, np.arange(n), life=g)
         assert np.array_equal(pick, ref) and 0 <= pick.min() and pick.max() <= 9 and len(set(pick.tolist())) == 10
         # the finished records
-        out = np.zeros(n, h.hb.DROP_DTYPE)
-        view = views[i % V:i % V + 1] if views is not None else None
-        k = emu.rr_emu_counter_records(MODEL_ID[model], _p(one), hz, _p(view) if view is not None else None, _p(box), _p(dgrid), _p(tab),
-                                       len(dgrid), H, W, _p(ratio_db), _p(out), n)
+        out, _ = pe.records(run, H, W, ratio_db)
+        k = len(out)
         assert k == len(want[i]) > 100, (i, k, len(want[i]))
-        for name in h.hb.DROP_DTYPE.names:
-            assert out[:k][name].tobytes() == want[i][name].tobytes(), (i, name)
+        pe.assert_records_equal(out, want[i], 'counter', i)
+        total += k
+    print('%s: %d records compared' % (model, total))
 
 
 def test_texture_pick_is_the_scaled_word():
@@ -148,13 +85,13 @@ N_CLIP = 40
 def clips(tmp_path_factory):
     """Per mode the picks of (a) a 40-frame field clip and (b) 40 stereo instants: lists of {slot: (life, pick)} per frame."""
     sc = h.Scene(tmp_path_factory.mktemp('draws'), 64, 96, 10)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     frames = 50 + np.arange(N_CLIP)
     out = {}
-    for model, rig in (('field', None), ('rig', KITTI_STEREO)):
-        sims, dgrid, cdf, kw = _run(model, opt, 25, frames, 77, rig)
+    for model, rig in (('field', None), ('rig', cases.KITTI_STEREO)):
+        sims, dgrid, cdf, kw = cases.run(model, opt, 25, frames, 77, rig)
         V = 2 if rig is not None else 1
-        ids = [_kept(s, dgrid, cdf, sc.db, model, opt['cam_hz'], rig, i % V) for i, s in enumerate(sims)]
+        ids = [cases.kept(s, dgrid, cdf, sc.db, model, opt['cam_hz'], rig, i % V) for i, s in enumerate(sims)]
         for draws in ('stream', 'counter'):
             recs = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
             per = []
@@ -216,12 +153,12 @@ def _chi2(picks):
 @pytest.mark.parametrize("model", ['iid', 'field'])
 def test_the_ten_picks_are_equally_likely(tmp_path, model):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('nuscenes')
+    opt = cases.options('nuscenes')
     # chi-square asks for independent samples: under the field model a drop shows in every frame of its life with the one pick
     # (that is the point of the mode), so the field's frames are taken 1000 apart -- no life lasts that long (the tallest box
     # is crossed in about a second), every record is then a drop of its own
     frames = [3, 4, 5, 6, 7] if model == 'iid' else [3, 1003, 2003, 3003, 4003]
-    sims, dgrid, cdf, kw = _run(model, opt, 100, frames, 2024)
+    sims, dgrid, cdf, kw = cases.run(model, opt, 100, frames, 2024)
     for draws in ('counter', 'stream'):                      # (the stream mode goes through the same threshold: the control)
         recs = particles.expected_records(sims, dgrid, cdf, sc.db, dataset='nuscenes', draws=draws, **kw)
         x2, n = _chi2(np.concatenate([r['tex_index'] % 10 for r in recs]))
@@ -234,9 +171,9 @@ def test_the_ten_picks_are_equally_likely(tmp_path, model):
 @pytest.mark.parametrize("model", ['iid', 'field', 'rig'])
 def test_only_the_last_digit_of_tex_index_differs(tmp_path, model):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
-    rig = KITTI_STEREO if model == 'rig' else None
-    sims, dgrid, cdf, kw = _run(model, opt, 100, [7, 8], 11, rig)
+    opt = cases.options('kitti')
+    rig = cases.KITTI_STEREO if model == 'rig' else None
+    sims, dgrid, cdf, kw = cases.run(model, opt, 100, [7, 8], 11, rig)
     a = particles.expected_records(sims, dgrid, cdf, sc.db, draws='stream', **kw)
     b = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', **kw)
     other = sims.copy()
@@ -255,7 +192,7 @@ def test_only_the_last_digit_of_tex_index_differs(tmp_path, model):
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------
 def test_refusals(tmp_path):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
     with pytest.raises(ValueError, match='particle draws'):
         particles.expected_records(sims, dgrid, cdf, sc.db, draws='philox')

@@ -5,10 +5,9 @@ persistent, stateless particle field: frame k + 1 shows the drops of frame k mov
   2. random access: frame k alone == frame k of a run 0 .. k == frame k under another batch split, bit for bit;
   3. same law as the i.i.d. model frame by frame: kept count and the marginals of diameter, depth and image position;
   4. no recurrence: consecutive lives of a slot start at different lateral positions, with another wind;
-  5. the g++ build of the RR_HD statement (tests/hostemu/field_emu.cpp: the code k_field_particles runs) == numpy, bit for
+  5. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code k_field_particles runs) == numpy, bit for
      bit: particles and the rr_drop records of whole frames;
   6. RainAugment(particle_model='field').plan: what a clip sends."""
-import ctypes
 import importlib
 import os
 
@@ -16,65 +15,26 @@ import numpy as np
 import pytest
 
 import helpers as h
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 db = importlib.import_module('rain-rendering_amd.common.db')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53                                            # unit roundoff of IEEE double
-
-
-def _options(dataset='kitti', **kw):
-    o = dict(db.settings(dataset))
-    o.pop('sequences', None)
-    o.update(kw)
-    return o
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libfieldemu.so'))
-    lib.rr_emu_field_particles.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.rr_emu_field_records.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
-    return lib
+    return pe.load()
 
 
 # ---- 1. tracks -----------------------------------------------------------------------------------------------------
-def _track_bounds(vel, box, life, dt):
-    """Largest |displacement - velocity dt| (modulo the box) rounding can cause, per axis, from the operation count of
-    make_field_particle.  u = 2^-53; every operation has a relative error of at most u; S = life + 2 bounds |t / T + phase|
-    in both frames.
-      age = frac(t / T + phase): T = wy / v, t = k / cam_hz, t / T are three roundings of a value of size <= S and the sum
-        is a fourth: |d age| <= 4 u S (the subtraction of the integer part is exact).
-      y = by - age wy: d age wy, the product (age < 1) and the difference (|.| <= wy): (4 S + 2) u wy per frame.
-      x = frac(u_x + wind tau / wx) wx - bx with tau = age T: tau carries d age T and two roundings (T, the product), wind tau
-        and / wx two more: (4 S + 4) u R with R = |wind| T / wx; the sum with u_x one of size <= 1 + R; the fractional part
-        is exact; the product with wx and the difference one each: ((4 S + 5) R + 3) u wx per frame.
-      z likewise with the box depth for wx and the vehicle's speed for the wind (one operation fewer: no difference).
-    Two frames double it; the expected displacement v dt formed here in double adds 2 u |v dt|, the test's own difference
-    and its reduction modulo the box 2 u of the box."""
-    S = life + 2.0
-    T = box[:, 1] / np.abs(vel[:, 1])
-    out = np.zeros_like(vel)
-    for ax in (0, 2):
-        R = np.abs(vel[:, ax]) * T / box[:, ax]
-        out[:, ax] = (2.0 * ((4.0 * S + 5.0) * R + 3.0) + 2.0) * U * box[:, ax] + 2.0 * U * np.abs(vel[:, ax] * dt)
-    out[:, 1] = (2.0 * (4.0 * S + 2.0) + 2.0) * U * box[:, 1] + 2.0 * U * np.abs(vel[:, 1] * dt)
-    return out
-
-
 @pytest.mark.parametrize("speed_kmh,k0", [(0.0, 0), (50.0, 0), (50.0, 1000)])
 def test_tracks_move_by_velocity_over_cam_hz(speed_kmh, k0):
     """KITTI at 25 mm/hr, constant settings: every particle of frame k that is kept again in frame k + 1 in the same life
     has wp1(k + 1) - wp1(k) = velocity / cam_hz, component by component, modulo the box on the wrapped axes, within the
     rounding bound of _track_bounds.  (The depth of a drop nearer than 5 cm is clamped for the projection: such a drop is
     left out, its z is not its position.)"""
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([speed_kmh])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([speed_kmh])})
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     dt = 1.0 / cam.hz
@@ -93,7 +53,7 @@ def test_tracks_move_by_velocity_over_cam_hz(speed_kmh, k0):
         r = (rb['wp1'][ib] - ra['wp1'][ia]) - vel * dt
         r[:, 0] -= box[:, 0] * np.rint(r[:, 0] / box[:, 0])
         r[:, 2] -= box[:, 2] * np.rint(r[:, 2] / box[:, 2])
-        bound = _track_bounds(vel, box, la[ia], dt)
+        bound = cases._track_bounds(vel, box, la[ia], dt)
         print('frame %d -> %d: %d of %d kept again (%.1f %%), worst |residual| / bound per axis %s'
               % (k, k + 1, len(ia), len(ra), 100 * shares[-1], (np.abs(r) / bound).max(axis=0)))
         assert np.all(np.abs(r) <= bound), np.abs(r / bound).max(axis=0)
@@ -105,7 +65,7 @@ def test_tracks_move_by_velocity_over_cam_hz(speed_kmh, k0):
 
 # ---- 2. random access ----------------------------------------------------------------------------------------------
 def test_a_frame_alone_equals_the_frame_in_a_run(tmp_path):
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     k = 5
     frames, drops = particles.generate(opt, 25, k + 1, seed=3, model='field')
     a, n = int(frames['first_drop'][k]), int(frames['n_drops'][k])
@@ -127,69 +87,29 @@ def test_a_frame_alone_equals_the_frame_in_a_run(tmp_path):
 
 
 # ---- 3. same law as the i.i.d. model ---------------------------------------------------------------------------------
-N_LAW = 60                                                # frames per sample
-
-
-def _sample(model, seed0):
-    """N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own: frames of different seeds share no random number, so
-    they are independent whatever the model (frames of one field run are correlated for as long as the slowest slot's
-    period; spacing them would need that bound, seeds need nothing)."""
-    opt = _options('kitti')
-    cam = particles.FrameCamera(opt, 0)
-    counts, D, depth, px, py = [], [], [], [], []
-    for i in range(N_LAW):
-        if model == 'field':
-            rec, _ = particles.field_frame(opt, 25, 7 * i + 3, seed=seed0 + i)
-        else:
-            _, rec = particles.generate(opt, 25, 1, seed=seed0 + i)
-        counts.append(len(rec))
-        D.append(rec['wd1'] * 1e3)
-        depth.append(-rec['wp1'][:, 2])
-        px.append(rec['ip1'][:, 0])
-        py.append(rec['ip1'][:, 1])
-    return dict(cam=cam, counts=np.array(counts), D=np.concatenate(D), depth=np.concatenate(depth), px=np.concatenate(px), py=np.concatenate(py))
-
-
-def _same_law(a, b):
-    """Two samples of N_LAW independent frames each.  Count: the frames' counts are Poisson(mean); the difference of the two
-    sample means has the standard error sqrt(2 mean / N_LAW); four of them, as tests/test_particles.py takes for the count.
-    Marginals: the two-sample Kolmogorov-Smirnov statistic D against its large-sample law, P(sqrt(n m / (n + m)) D > c) =
-    2 sum (-1)^(j-1) exp(-2 j^2 c^2): c = 1.95 is exceeded with probability 1e-3 per marginal by two samples of one law
-    (the particles of a frame are independent given the count in both models, so the pooled particles are a sample)."""
-    mean = particles.expected_count(a['cam'], 25)[0]
-    se = np.sqrt(2.0 * mean / N_LAW)
-    out = {'count': abs(a['counts'].mean() - b['counts'].mean()) / (4.0 * se)}
-    for name in ('D', 'depth', 'px', 'py'):
-        x, y = np.sort(a[name]), np.sort(b[name])
-        grid = np.concatenate([x, y])
-        d = np.abs(np.searchsorted(x, grid, side='right') / len(x) - np.searchsorted(y, grid, side='right') / len(y)).max()
-        out[name] = d * np.sqrt(len(x) * len(y) / (len(x) + len(y))) / 1.95
-    return out
-
-
 def test_field_frames_have_the_iid_models_law():
-    iid_a, iid_b, field = _sample('iid', 1000), _sample('iid', 5000), _sample('field', 9000)
+    iid_a, iid_b, field = cases._sample('iid', 1000), cases._sample('iid', 5000), cases._sample('field', 9000)
     mean = particles.expected_count(field['cam'], 25)[0]
-    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / N_LAW)       # the model's own expected count
-    margin_check = _same_law(iid_a, iid_b)                    # the i.i.d. model against itself: the margin is not too tight
-    got = _same_law(field, iid_a)
-    got_b = _same_law(field, iid_b)
+    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)       # the model's own expected count
+    margin_check = cases._same_law(iid_a, iid_b)                    # the i.i.d. model against itself: the margin is not too tight
+    got = cases._same_law(field, iid_a)
+    got_b = cases._same_law(field, iid_b)
     print('statistic / threshold -- iid vs iid: %s\n  field vs iid: %s\n  field vs iid (other seeds): %s' % (margin_check, got, got_b))
     assert all(v < 1 for v in margin_check.values()), margin_check
     assert all(v < 1 for v in got.values()), got
     assert all(v < 1 for v in got_b.values()), got_b
     # the test can tell: the slots BEFORE the cull (uniform in the box, not in the frustum) fail it by a wide margin
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     box = dict(field)
-    rec = np.concatenate([particles.field_frame(opt, 25, 3, seed=20000 + i, cull=False)[0][::3] for i in range(N_LAW)])
+    rec = np.concatenate([particles.field_frame(opt, 25, 3, seed=20000 + i, cull=False)[0][::3] for i in range(cases.N_LAW)])
     box['depth'] = -rec['wp1'][:, 2]
-    assert _same_law(box, iid_a)['depth'] > 3
+    assert cases._same_law(box, iid_a)['depth'] > 3
 
 
 # ---- 4. no recurrence ------------------------------------------------------------------------------------------------
 def test_consecutive_lives_of_a_slot_start_elsewhere():
     """Slots followed over their first lives: each life has its own lateral start, start depth and wind (property 4)."""
-    opt = _options('kitti', cam_hz=1000.0, cam_exposure=0.5)  # fine time steps: every life of a slot is seen many times
+    opt = cases.options('kitti', cam_hz=1000.0, cam_exposure=0.5)  # fine time steps: every life of a slot is seen many times
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     n = 64
@@ -235,44 +155,37 @@ def terminal(cam, dgrid, cdf, j, seed):
 @pytest.mark.parametrize("dataset,rs,rate", [('kitti', 1, 25), ('kitti', 1, 100), ('cityscapes', 2, 25), ('nuscenes', 1, 100)])
 def test_gxx_build_equals_numpy(tmp_path, emu, dataset, rs, rate):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0, 0.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([30.0, 50.0, 0.0])})
     sims, dgrid, cdf = particles.sim_frames(opt, rate, 3, render_scale=rs, seed=1234 + 2 ** 40, model='field')
     sims = particles.field_run_sims(sims, [0, 17, 2 ** 31 + 5, 4000000000])      # (records 0, 2, 2, 1 of the three settings)
     hz = float(opt['cam_hz'])
     want = particles.expected_records(sims, dgrid, cdf, sc.db, model='field', cam_hz=hz)
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
     ratio_db = np.ascontiguousarray(np.asarray(sc.db.ratio, np.float64)[:4])
+    total = 0
     for i, s in enumerate(sims):
         n = int(s['n_particles'])
         cam = particles.FrameCamera(opt, int(s['frame']) % 3)
         seed = int(s['key0']) | (int(s['key1']) << 32)
         rec, life = particles.make_field_particles(cam, dgrid, cdf[int(s['table'])], n, int(s['frame']), seed, hz, cull=False)
         kept, _ = particles.make_field_particles(cam, dgrid, cdf[int(s['table'])], n, int(s['frame']), seed, hz)
-        one = np.ascontiguousarray(sims[i:i + 1])
-        out, ins, lf = np.zeros((n, 15)), np.zeros(n, np.uint8), np.zeros(n)
         tab = np.ascontiguousarray(cdf[int(s['table'])])
-        emu.rr_emu_field_particles(_p(one), hz, _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
-        for name, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-            assert out[:, cols].tobytes() == np.ascontiguousarray(rec[name]).tobytes(), (name, i)
-        assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-        assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == life.tobytes()
+        run = pe.run(model='field', sim=sims[i:i + 1], cam_hz=hz, dgrid=dgrid, cdf=tab)
+        out, ins, lf, _ = pe.all_slots(run)
+        pe.assert_slots_equal(out, lf, rec, life, i)
         assert np.array_equal(np.nonzero(ins)[0], kept['pid'])
         assert 0.30 < ins.mean() < 0.37                           # a pyramid fills a third of its bounding box
         # whole frames of rr_drop records, as the kernel leaves them in front of the draws
-        got = np.zeros(n, h.hb.DROP_DTYPE)
-        m = emu.rr_emu_field_records(_p(one), hz, _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(got), n)
-        assert m == len(want[i]) > 100
-        got = got[:m]
-        for name in h.hb.DROP_DTYPE.names:
-            if name == 'tex_index':                               # the draws pick one of the block of ten
-                assert np.array_equal(got[name], want[i][name] // 10 * 10)
-            else:
-                assert got[name].tobytes() == want[i][name].tobytes(), (name, i)
+        got, _ = pe.records(run, H, W, ratio_db)
+        assert len(got) == len(want[i]) > 100
+        pe.assert_records_equal(got, want[i], 'stream', i)        # the draws pick one of the block of ten
+        total += len(got)
+    print('%s rs %d %d mm/hr: %d records compared' % (dataset, rs, rate, total))
     assert sims['n_particles'][0] == sims['n_particles'][1] == sims['n_particles'][2]     # one slot count per settings of a run
 
 
 def test_model_argument_is_checked():
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     with pytest.raises(ValueError, match='particle model'):
         particles.generate(opt, 25, 1, model='brownian')
     with pytest.raises(ValueError, match='particle model'):

@@ -2,7 +2,7 @@
 rr_set_particle_gusts).  The series is the air's displacement G[0 .. n] sampled at frame times; a drop born `back` frames ago has
 been carried by dG = G[m] - G(m - back) and its streak ends with the frame's air velocity ge = (G[m + 1] - G[m]) cam_hz.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/gust_emu.cpp: the code the GUST kernels run) == numpy, bit for bit, for
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code the GUST kernels run) == numpy, bit for bit, for
      every slot kept or culled and for the finished records: field, rig (stereo, a yaw ring), a trajectory that yaws and pitches;
      both draws, jitter 0 / 5, mean wind (0, 0) / (-7.5, 2); series with n = 1, a frame at m = 0, frame0 = 2^31 + 3, a frame at m = n - 1;
   2. gusts=None gives the bytes of the functions called without the keyword, also at wind_sigma = 0;
@@ -12,7 +12,6 @@ been carried by dG = G[m] - G(m - back) and its streak ends with the frame's air
   6. a field frame under a sigma = 4 m/s series follows the i.i.d. model's law;
   7. gust_series: reproducible, the right variance, a sequential sum;
   8. every refusal."""
-import ctypes
 import importlib
 import os
 
@@ -20,46 +19,21 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_particle_field_host as tf                     # _track_bounds / _same_law / _sample / N_LAW
-import test_particle_rig_host as tr                       # the rigs
-import test_particle_wind_host as tw                      # _case_run, _windy_bounds, the rigs and the trajectory of the wind's tests
-from test_particle_draws_host import MODEL_ID, _options, _p
-from test_particle_jitter_host import _same_field
-from test_particle_trajectory_host import MONO
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
-HZ = 10.0                                                 # KITTI's cam_hz
-BIG0 = 2 ** 31 + 3
+U = cases.U
+HZ, BIG0 = cases.HZ, cases.BIG0
 WINDS = [(0.0, 0.0), (-7.5, 2.0)]
-
-
-def gust_cases(traj=False):
-    """[(GustSeries, frames)]: the series of item 1 (and of the GPU tier) and the time indices generated under each.  n = 1 (its
-    only frame is m = 0 = n - 1); a six-interval series at m = 0 -- where nearly every birth lies before the series: the held first
-    interval -- and at m = n - 1; frame0 = 2^31 + 3 at m = 0 and inside.  Under the three-pose trajectory the indices are 0 .. 2."""
-    if traj:
-        return [(particles.GustSeries(1, np.array([[0.5, -0.25], [0.81, -0.37]])), [1]),
-                (particles.gust_series(3, HZ, 4.0, 2.0, seed=5), [0, 2])]
-    return [(particles.GustSeries(3, np.array([[0.5, -0.25], [0.81, -0.37]])), [3]),
-            (particles.gust_series(6, HZ, 4.0, 2.0, seed=5), [0, 5]),
-            (particles.gust_series(4, HZ, 4.0, 2.0, seed=6, frame0=BIG0), [BIG0, BIG0 + 2])]
-
-
 # (name, model, rig, trajectory)
-CASES = [c for c in tw.CASES if c[1] != 'iid']
+CASES = [c for c in cases.CASES if c[1] != 'iid']
 CASE_IDS = [c[0] for c in CASES]
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libgustemu.so'))
-    V, I, D, U32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_uint32
-    lib.rr_emu_gust_particles.argtypes = [I, D, D, I, U32, V, V, D, V, V, V, V, V, I, V, V, V]
-    lib.rr_emu_gust_records.argtypes = [I, I, D, D, D, I, U32, V, V, D, V, V, V, V, V, I, I, I, V, V, I]
-    lib.rr_emu_gust_records.restype = I
-    return lib
+    return pe.load()
 
 
 @pytest.fixture(scope='module')
@@ -84,8 +58,8 @@ def _all_slots(model, cam, dgrid, tab, s, hz, rig, traj, view, box, **kw):
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
     total = n_before = 0
-    for gusts, frames in gust_cases(traj is not None):
-        opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, traj, frames)
+    for gusts, frames in cases.gust_cases(traj is not None):
+        opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, frames)
         hz = float(opt['cam_hz'])
         assert hz == HZ
         V = len(rig) if rig is not None else 1
@@ -94,37 +68,23 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
         tab = np.ascontiguousarray(cdf[0])
         views = rig.as_records() if rig is not None else None
         poses = traj.compose(rig, cam.exposure) if traj is not None else None
-        disp = np.ascontiguousarray(gusts.disp)
         for wind in WINDS:
             mean_only = particles.expected_records(sims, dgrid, cdf, sdb, wind=wind, **kw)
             want = {(d, j): particles.expected_records(sims, dgrid, cdf, sdb, draws=d, jitter=j, wind=wind, gusts=gusts, **kw)
                     for d in ('counter', 'stream') for j in (0.0, 5.0)}
             for i, s in enumerate(sims):
-                one = np.ascontiguousarray(sims[i:i + 1])
-                n, v = int(s['n_particles']), i % V
-                view_rec = np.ascontiguousarray(views[v:v + 1]) if views is not None and traj is None else None
-                view = _p(view_rec) if view_rec is not None else None
-                po = np.ascontiguousarray(poses[int(s['frame']), v:v + 1]) if traj is not None else None
+                v = i % V
+                view = views[v:v + 1] if views is not None and traj is None else None
+                po = poses[int(s['frame']), v:v + 1] if traj is not None else None
+                air = dict(model=model, sim=sims[i:i + 1], cam_hz=hz, view=view, pose=po, box=box, dgrid=dgrid, cdf=tab, wind=wind, gusts=gusts)
                 rec, life = _all_slots(model, cam, dgrid, tab, s, hz, rig, traj, v, box, wind=wind, gusts=gusts)
-                out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
-                emu.rr_emu_gust_particles(MODEL_ID[model], wind[0], wind[1], gusts.n, gusts.frame0, _p(disp), _p(one), hz, view,
-                                          _p(po) if po is not None else None, _p(box), _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
-                for nm, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-                    assert out[:, cols].tobytes() == np.ascontiguousarray(rec[nm]).tobytes(), (nm, i, wind, frames)
-                assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-                assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == np.ascontiguousarray(life).tobytes()
+                out, ins, lf, _ = pe.all_slots(pe.run(**air))
+                pe.assert_slots_equal(out, lf, rec, life, (i, wind, frames))
                 for (draws, jit), recs in want.items():
-                    got = np.zeros(n, h.hb.DROP_DTYPE)
-                    m = emu.rr_emu_gust_records(MODEL_ID[model], int(draws == 'counter'), jit, wind[0], wind[1], gusts.n, gusts.frame0, _p(disp),
-                                                _p(one), hz, view, _p(po) if po is not None else None, _p(box), _p(dgrid), _p(tab), len(dgrid),
-                                                H, W, _p(ratio_db), _p(got), n)
-                    w = recs[i]
+                    got, _ = pe.records(pe.run(counter=draws == 'counter', jitter=jit, **air), H, W, ratio_db)
+                    m, w = len(got), recs[i]
                     assert m == len(w) > 100, (i, wind, draws, jit, m, len(w))
-                    for nm in h.hb.DROP_DTYPE.names:
-                        if nm == 'tex_index' and draws == 'stream':    # (the particle kernel leaves the block's first texture to k_particle_draws)
-                            assert np.array_equal(got[:m][nm], w[nm] // 10 * 10), (i, wind, draws, jit)
-                        else:
-                            assert _same_field(got[:m][nm], w[nm]), (i, wind, draws, jit, nm)
+                    pe.assert_records_equal(got, w, draws, (i, wind, draws, jit), cases._same_field)
                     total += m
                 assert want[('stream', 0.0)][i].tobytes() != mean_only[i].tobytes()     # the series does something
         # the branch sb < 0 is reached where the frame is the series' first
@@ -144,7 +104,7 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 @pytest.mark.parametrize("wind_sigma", [1.0, 0.0])
 def test_no_series_gives_the_bytes_without_the_keyword(sdb, name, model, rig, traj, wind_sigma):
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, traj, [0, 1])
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, [0, 1])
     sims['wind_sigma'] = wind_sigma
     hz = float(opt['cam_hz'])
     for wind in WINDS:
@@ -164,7 +124,7 @@ def test_no_series_gives_the_bytes_without_the_keyword(sdb, name, model, rig, tr
                 sa = particles.rig_state(cam, dgrid, tab, n, k, seed, hz, tuple(box), wind_sigma=wind_sigma, wind=wind)
                 sb = particles.rig_state(cam, dgrid, tab, n, k, seed, hz, tuple(box), wind_sigma=wind_sigma, wind=wind, gusts=None)
                 assert all(sa[key].tobytes() == sb[key].tobytes() for key in sa)
-    opt2 = _options('kitti')
+    opt2 = cases.options('kitti')
     if model == 'field':
         a, b = particles.generate(opt2, 25, 2, seed=3, model='field'), particles.generate(opt2, 25, 2, seed=3, model='field', gusts=None)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
@@ -183,7 +143,7 @@ def test_no_series_gives_the_bytes_without_the_keyword(sdb, name, model, rig, tr
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 def test_a_zero_series_is_the_mean_wind(sdb, name, model, rig, traj):
     """dG = 0 - (0 + fr (0 - 0)) and ge = (0 - 0) cam_hz are zeros: x + 0 == x in value (only a zero's sign may differ)."""
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, traj, [0, 2])
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, [0, 2])
     zero = particles.GustSeries(0, np.zeros((4, 2)))
     for wind in [(-7.5, 2.0), (3.0, 0.0)]:
         for draws, jit in (('stream', 0.0), ('counter', 5.0)):
@@ -232,11 +192,11 @@ def _const_bounds(vx, vxm, tau, m, w, q, X, e):
 @pytest.mark.parametrize("wind", WINDS)
 def test_a_constant_velocity_series_is_a_mean_wind(model, wind):
     gusts = _const_series()
-    rig = tr.KITTI_STEREO if model == 'rig' else None
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, None, [0])
+    rig = cases.KITTI_STEREO if model == 'rig' else None
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, None, [0])
     tab = np.ascontiguousarray(cdf[0])
     n = int(sims[0]['n_particles'])
-    seed = tw.SEED
+    seed = cases.SEED
     key = particles._key(seed)
     j = np.arange(n, dtype=np.uint64)
     windm = (wind[0] + 2.5, wind[1])
@@ -296,12 +256,12 @@ def _gust_err(gusts, back, m):
 
 def test_field_tracks_move_with_the_air():
     """A slot kept at k and k + 1 in one life: wp1(k + 1) - wp1(k) = (vx, -v, vz) / cam_hz + (G[m + 1] - G[m]) modulo the box.  The
-    birth instant is the same in both frames, so Gb cancels in exact arithmetic.  Bound: the wind's own (tw._windy_bounds over
-    tf._track_bounds) taken with |velocity| + max |step| cam_hz on x and z -- the error of tau moves the birth, and the air is never
+    birth instant is the same in both frames, so Gb cancels in exact arithmetic.  Bound: the wind's own (cases._windy_bounds over
+    cases._track_bounds) taken with |velocity| + max |step| cam_hz on x and z -- the error of tau moves the birth, and the air is never
     faster than that --, plus _gust_err for each of the two frames, plus 2 u |G[m + 1] - G[m]| for the difference formed here."""
     wind = (-7.5, 2.0)
     gusts = particles.gust_series(12, HZ, 4.0, 2.0, seed=21, frame0=1000)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([50.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([50.0])})
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     dt = 1.0 / cam.hz
@@ -327,7 +287,7 @@ def test_field_tracks_move_with_the_air():
         veff = vel.copy()
         veff[:, 0] = np.abs(vel[:, 0]) + smax * HZ
         veff[:, 2] = np.abs(vel[:, 2]) + smax * HZ
-        bound = tw._windy_bounds(tf._track_bounds(veff, box, la[ia], dt), veff, box, la[ia], dt)
+        bound = cases._windy_bounds(cases._track_bounds(veff, box, la[ia], dt), veff, box, la[ia], dt)
         T = box[:, 1] / np.abs(vel[:, 1])
         ge = 2.0 * _gust_err(gusts, T * HZ + 1.0, float(m + 1)) + 2.0 * U * np.abs(step).max()
         bound[:, 0] += ge
@@ -343,14 +303,14 @@ def test_field_tracks_move_with_the_air():
     assert total >= 60, total
 
 
-@pytest.mark.parametrize("name,model,rig", [('field', 'field', None), ('rig-ring', 'rig', tw.RING3)])
+@pytest.mark.parametrize("name,model,rig", [('field', 'field', None), ('rig-ring', 'rig', cases.RING3)])
 def test_a_streak_is_the_velocity_with_the_gust_times_the_exposure(sdb, name, model, rig):
     """Every kept record: wpe - wps = R (vx + gex, -v(D), vz + gez) exposure in the view's axes, within the mean wind's bound
     (tests/test_particle_wind_host.py) with one more rounding of the velocity: vx + gex is a rounded sum, formed here with the same
     bits, and ge itself -- a difference of two table entries times cam_hz -- is formed here with the same two operations."""
     wind = (-7.5, 2.0)
-    gusts, frames = gust_cases()[1]
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, None, frames)
+    gusts, frames = cases.gust_cases()[1]
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, None, frames)
     hz = float(opt['cam_hz'])
     tab = np.ascontiguousarray(cdf[0])
     recs = particles.expected_records(sims, dgrid, cdf, sdb, wind=wind, gusts=gusts, **kw)
@@ -394,7 +354,7 @@ def test_the_slant_follows_the_gust_and_flips_in_a_view_yawed_180_degrees(sdb):
     end points' rounding to pixels (half a pixel each: |dx - r dy| <= 1 + |r|).  Frame 0 leans right, frame 1 left; the view that
     looks backwards sees the opposite in both."""
     gusts = _slant_series()
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run('rig', tw.BACK_TO_BACK, None, [0, 1], speed_kmh=0.0)
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run('rig', cases.BACK_TO_BACK, None, [0, 1], speed_kmh=0.0)
     sims['wind_sigma'] = 0.0
     recs = particles.expected_records(sims, dgrid, cdf, sdb, gusts=gusts, **kw)
     hz = float(opt['cam_hz'])
@@ -402,9 +362,9 @@ def test_the_slant_follows_the_gust_and_flips_in_a_view_yawed_180_degrees(sdb):
         frame, view = i // 2, i % 2
         gex = (gusts.disp[frame + 1, 0] - gusts.disp[frame, 0]) * hz
         sign = (1.0 if view == 0 else -1.0) * np.sign(gex)
-        table, _, W, H = particles._loaded_table(sims[i], dgrid, cdf, sdb, 'kitti', 'rig', hz, tw.BACK_TO_BACK, view, gusts=gusts)
+        table, _, W, H = particles._loaded_table(sims[i], dgrid, cdf, sdb, 'kitti', 'rig', hz, cases.BACK_TO_BACK, view, gusts=gusts)
         pid = table.pid[h.hb.filter_streaks(table, W, H)]
-        D = particles._slot_draw(cam, dgrid, cdf[0], pid.astype(np.uint64), particles._key(tw.SEED), 1.0, 15.0)[0]
+        D = particles._slot_draw(cam, dgrid, cdf[0], pid.astype(np.uint64), particles._key(cases.SEED), 1.0, 15.0)[0]
         r = sign * abs(gex) / particles.terminal_velocity(D)
         dx, dy = (rec['x1'] - rec['x0']).astype(np.float64), (rec['y1'] - rec['y0']).astype(np.float64)
         nb = rec['type'] != 0
@@ -414,11 +374,11 @@ def test_the_slant_follows_the_gust_and_flips_in_a_view_yawed_180_degrees(sdb):
 
 # ---- 6. the law ----------------------------------------------------------------------------------------------------
 def test_a_gusty_field_frame_has_the_iid_models_law():
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
-    gusts = particles.gust_series(7 * tf.N_LAW + 4, HZ, 4.0, 2.0, seed=77)
+    gusts = particles.gust_series(7 * cases.N_LAW + 4, HZ, 4.0, 2.0, seed=77)
     counts, D, depth, px, py = [], [], [], [], []
-    for i in range(tf.N_LAW):                                  # tf._sample('field', 9000) under the series
+    for i in range(cases.N_LAW):                                  # cases._sample('field', 9000) under the series
         rec, _ = particles.field_frame(opt, 25, 7 * i + 3, seed=9000 + i, gusts=gusts)
         counts.append(len(rec))
         D.append(rec['wd1'] * 1e3)
@@ -426,12 +386,12 @@ def test_a_gusty_field_frame_has_the_iid_models_law():
         px.append(rec['ip1'][:, 0])
         py.append(rec['ip1'][:, 1])
     field = dict(cam=cam, counts=np.array(counts), D=np.concatenate(D), depth=np.concatenate(depth), px=np.concatenate(px), py=np.concatenate(py))
-    iid_a, iid_b = tf._sample('iid', 1000), tf._sample('iid', 5000)
-    control = tf._same_law(iid_a, iid_b)
+    iid_a, iid_b = cases._sample('iid', 1000), cases._sample('iid', 5000)
+    control = cases._same_law(iid_a, iid_b)
     assert all(v < 1 for v in control.values()), control
     mean = particles.expected_count(cam, 25)[0]
-    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
-    got, got_b = tf._same_law(field, iid_a), tf._same_law(field, iid_b)
+    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)
+    got, got_b = cases._same_law(field, iid_a), cases._same_law(field, iid_b)
     print('statistic / threshold -- iid vs iid: %s\n  gusty field vs iid: %s\n  gusty field vs iid (other seeds): %s' % (control, got, got_b))
     assert all(v < 1 for v in got.values()), got
     assert all(v < 1 for v in got_b.values()), got_b
@@ -503,13 +463,13 @@ def test_refusals(sdb):
     with pytest.raises(ValueError, match='no time'):
         particles._check_gusts(G(0, ok), HZ, 'iid')
     # the generator's: the i.i.d. model, a frame outside the series, run_pos
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
     with pytest.raises(ValueError, match='no time'):
         particles.expected_records(sims, dgrid, cdf, sdb, gusts=G(0, ok))
     with pytest.raises(ValueError, match='no time'):
         particles.generate(opt, 25, 1, gusts=G(0, ok))
-    opt, fs, dgrid, cdf, kw, cam, box = tw._case_run('field', None, None, [2])
+    opt, fs, dgrid, cdf, kw, cam, box = cases.case_run('field', None, None, [2])
     with pytest.raises(ValueError, match='outside the gust series'):
         particles.expected_records(fs, dgrid, cdf, sdb, gusts=G(0, ok), **kw)
     with pytest.raises(ValueError, match='outside the gust series'):
@@ -518,7 +478,7 @@ def test_refusals(sdb):
     with pytest.raises(ValueError, match='outside the gust series'):
         particles.field_frame(opt, 25, 2, gusts=G(0, ok))
     with pytest.raises(ValueError, match='outside the gust series'):
-        particles.rig_frame(opt, 25, 2, MONO, 0, gusts=G(0, ok))
+        particles.rig_frame(opt, 25, 2, cases.MONO, 0, gusts=G(0, ok))
     runp = fs.copy()
     runp['run_pos'] = 1
     with pytest.raises(ValueError, match='run_pos'):

@@ -1,14 +1,13 @@
 """CPU tier: per-drop streak jitter (tools/particles.py counter_jitter / expected_records(jitter=), rr_particles.h jitter_deviate /
 particle_jitter / life_jitter, rr_set_particle_jitter) -- every drop is turned by jitter x a normal deviate of its own counter.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/jitter_emu.cpp: the code the JIT kernels run) == numpy, bit for bit, for
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code the JIT kernels run) == numpy, bit for bit, for
      the i.i.d., field and rig models and both draws;
   2. what the jitter does not touch: the kept set, every field but the end points and the rotation terms, Big records;
   3. coherence: a field slot keeps its deviate from frame k to k + 1 inside one life, a rig slot in both stereo views; other lives
      and other slots have other deviates; the stream noise turns one drop differently in two frames (the control);
   4. law: Kolmogorov-Smirnov against N(0, 1), |g| <= 8.6, det_log / det_sincos on the deviate's domain;
   5. every refusal of the Python layer and of the driver's argument handling;  6. RainAugment.plan carries the jitter."""
-import ctypes
 import importlib
 import math
 import os
@@ -17,12 +16,10 @@ import numpy as np
 import pytest
 
 import helpers as h
-from test_particle_draws_host import KITTI_STEREO, MODEL_ID, _kept, _options, _p, _run
-from test_particle_noise_host import _ulp
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-db = importlib.import_module('rain-rendering_amd.common.db')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 JITTER = 5.0
 KS_C = 1.95                 # tests/test_particle_field_host.py _same_law: P(sqrt(n) D > 1.95) = 1e-3 for a sample of the law
@@ -31,19 +28,7 @@ TURNED = ('x0', 'y0', 'x1', 'y1', 'rot_cos', 'rot_sin')
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libjitteremu.so'))
-    V, I, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
-    lib.rr_emu_jitter_deviates.argtypes = [V, I, V, V, V]
-    lib.rr_emu_jitter_records.argtypes = [I, I, D, V, D, V, V, V, V, I, I, I, V, V, V, I]
-    lib.rr_emu_jitter_records.restype = I
-    return lib
-
-
-def _same_field(a, b):
-    """Bytes equal; NaN rotation terms are compared as NaN (their sign and payload are the machine's)."""
-    if a.dtype.kind == 'f':
-        return a.shape == b.shape and bool(np.all((_ulp(a, b) == 0) | (np.isnan(a) & np.isnan(b))))
-    return a.tobytes() == b.tobytes()
+    return pe.load()
 
 
 def _turn_deg(rec, plain):
@@ -58,12 +43,12 @@ def _turn_deg(rec, plain):
 @pytest.mark.parametrize("model", ['iid', 'field', 'rig'])
 def test_gxx_build_equals_numpy(tmp_path, emu, model):
     sc = h.Scene(tmp_path, 64, 96, 10)                       # (only its streak database is used: the texture ratios)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     hz = float(opt['cam_hz'])
-    rig = KITTI_STEREO if model == 'rig' else None
+    rig = cases.KITTI_STEREO if model == 'rig' else None
     V = len(rig) if rig is not None else 1
     seed = 1234 + 2 ** 40
-    sims, dgrid, cdf, kw = _run(model, opt, 25, [0, 1, 2 ** 31 + 5], seed, rig)
+    sims, dgrid, cdf, kw = cases.run(model, opt, 25, [0, 1, 2 ** 31 + 5], seed, rig)
     want = {d: particles.expected_records(sims, dgrid, cdf, sc.db, draws=d, jitter=JITTER, **kw) for d in ('counter', 'stream')}
     assert len(want['counter']) == 3 * V
     W, H = opt["cam_CCD_WH"]
@@ -72,6 +57,7 @@ def test_gxx_build_equals_numpy(tmp_path, emu, model):
     cam = particles.FrameCamera(opt, 0)
     box = np.array(rig.box(cam), np.float64) if rig is not None else np.zeros(3)
     views = rig.as_records() if rig is not None else None
+    total = 0
     for i, s in enumerate(sims):
         one = np.ascontiguousarray(sims[i:i + 1])
         n = int(s['n_particles'])
@@ -79,7 +65,7 @@ def test_gxx_build_equals_numpy(tmp_path, emu, model):
         pid = np.arange(n, dtype=np.uint32)
         g = np.zeros(n)
         if model == 'iid':
-            emu.rr_emu_jitter_deviates(_p(one), n, _p(pid), None, _p(g))
+            emu.rr_emu_jitter_deviates(cases.p(one), n, pid, None, g)
             ref = particles.counter_jitter(seed, pid, frame=int(s['frame']))
         else:
             if model == 'field':
@@ -87,22 +73,19 @@ def test_gxx_build_equals_numpy(tmp_path, emu, model):
             else:
                 life = particles.rig_state(cam, dgrid, tab, n, int(s['frame']), seed, hz, box)['life']
             life = np.ascontiguousarray(life, np.float64)
-            emu.rr_emu_jitter_deviates(_p(one), n, _p(pid), _p(life), _p(g))
+            emu.rr_emu_jitter_deviates(cases.p(one), n, pid, cases.p(life), g)
             ref = particles.counter_jitter(seed, pid, life=life)
         assert g.tobytes() == ref.tobytes() and np.abs(g).max() <= 8.6 and g.std() > 0.9
         # the finished records
         view = views[i % V:i % V + 1] if views is not None else None
         for draws in ('counter', 'stream'):
-            out, g_out = np.zeros(n, h.hb.DROP_DTYPE), np.zeros(n)
-            k = emu.rr_emu_jitter_records(MODEL_ID[model], int(draws == 'counter'), JITTER, _p(one), hz, _p(view) if view is not None else None,
-                                          _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(out), _p(g_out), n)
-            w = want[draws][i]
+            run = pe.run(model=model, sim=one, cam_hz=hz, view=view, box=box, dgrid=dgrid, cdf=tab, counter=draws == 'counter', jitter=JITTER)
+            out, _ = pe.records(run, H, W, ratio_db)
+            k, w = len(out), want[draws][i]
             assert k == len(w) > 100, (i, draws, k, len(w))
-            for name in h.hb.DROP_DTYPE.names:
-                if name == 'tex_index' and draws == 'stream':      # (the particle kernel leaves the block's first texture to k_particle_draws)
-                    assert np.array_equal(out[:k][name], w[name] // 10 * 10), (i, draws, name)
-                else:
-                    assert _same_field(out[:k][name], w[name]), (i, draws, name)
+            pe.assert_records_equal(out, w, draws, (i, draws), cases._same_field)
+            total += k
+    print('%s: %d records compared' % (model, total))
 
 
 # ---- 2. what the jitter does not touch -----------------------------------------------------------------------------
@@ -110,9 +93,9 @@ def test_gxx_build_equals_numpy(tmp_path, emu, model):
 @pytest.mark.parametrize("draws", ['stream', 'counter'])
 def test_only_end_points_and_rotation_terms_move(tmp_path, model, draws):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
-    rig = KITTI_STEREO if model == 'rig' else None
-    sims, dgrid, cdf, kw = _run(model, opt, 100, [7, 8], 11, rig)
+    opt = cases.options('kitti')
+    rig = cases.KITTI_STEREO if model == 'rig' else None
+    sims, dgrid, cdf, kw = cases.run(model, opt, 100, [7, 8], 11, rig)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, **kw)
     zero = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=0, **kw)
     turned = particles.expected_records(sims, dgrid, cdf, sc.db, draws=draws, jitter=JITTER, **kw)
@@ -142,17 +125,17 @@ def clips(tmp_path_factory):
     """(a) a 12-frame field clip and (b) 12 stereo instants with the jitter on: per frame {slot: (life, turn in degrees)}, the turn
     read back from the records' rotation terms."""
     sc = h.Scene(tmp_path_factory.mktemp('jitter'), 64, 96, 10)
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     frames = 50 + np.arange(N_CLIP)
     out = {}
-    for model, rig in (('field', None), ('rig', KITTI_STEREO)):
-        sims, dgrid, cdf, kw = _run(model, opt, 25, frames, 77, rig)
+    for model, rig in (('field', None), ('rig', cases.KITTI_STEREO)):
+        sims, dgrid, cdf, kw = cases.run(model, opt, 25, frames, 77, rig)
         V = 2 if rig is not None else 1
         plain = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', **kw)
         turned = particles.expected_records(sims, dgrid, cdf, sc.db, draws='counter', jitter=JITTER, **kw)
         per = []
         for i, s in enumerate(sims):
-            pid, life = _kept(s, dgrid, cdf, sc.db, model, opt['cam_hz'], rig, i % V)
+            pid, life = cases.kept(s, dgrid, cdf, sc.db, model, opt['cam_hz'], rig, i % V)
             deg, nb = _turn_deg(turned[i], plain[i])
             assert len(pid) == len(plain[i])
             per.append({int(j): (float(g), float(d)) for j, g, d in zip(pid[nb], life[nb], deg)})
@@ -200,7 +183,7 @@ def test_the_stream_noise_has_no_such_coherence(tmp_path):
     """The control: the reference's angular noise turns the SAME streak (one simulated frame, pristine end points) by another
     angle in another rendered frame -- its deviate belongs to the frame's stream, not to the drop."""
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=77)
     plain = particles.expected_records(sims, dgrid, cdf, sc.db)[0]
     turns = []
@@ -261,16 +244,16 @@ def test_the_deviate_at_the_ends_of_its_domain():
     u1 = np.concatenate([[2.0 ** -53, 2.0 ** -52, 0.5, 1.0 - 2.0 ** -53, 1.0], (rs.randint(0, 2 ** 53, 200000) + 1.0) * 2.0 ** -53,
                          2.0 ** -rs.uniform(0, 53, 100000)])
     assert u1.min() > 0 and u1.max() <= 1
-    assert _ulp(particles.det_log(u1), np.log(u1)).max() <= 2
+    assert cases._ulp(particles.det_log(u1), np.log(u1)).max() <= 2
     x = 6.283185307179586 * particles.unit32(np.concatenate([[0, full], rs.randint(0, 2 ** 32, 300000)]).astype(np.uint32))
     sn, cn = particles.det_sincos(x)
-    assert _ulp(cn, np.cos(x)).max() <= 2 and _ulp(sn, np.sin(x)).max() <= 2
+    assert cases._ulp(cn, np.cos(x)).max() <= 2 and cases._ulp(sn, np.sin(x)).max() <= 2
 
 
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------
 def test_refusals(tmp_path):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
     with pytest.raises(ValueError, match='jitter'):
         particles.expected_records(sims, dgrid, cdf, sc.db, jitter=2.0, noise_std=2.0, noise_scale=1.0, run=([0], [0]))

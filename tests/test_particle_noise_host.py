@@ -1,51 +1,28 @@
 """CPU tier: angular noise (--noise_std) on device-generated drop tables -- the arithmetic and the host statement.
 
   1. det_log / det_sincos (tools/particles.py, rr_device.h): within 2 ulp of numpy's libm over sweeps;
-  2. the g++ build of the RR_HD statement (tests/hostemu/noise_emu.cpp: the code k_noise_chains runs) equals the numpy
+  2. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code k_noise_chains runs) equals the numpy
      statement bit for bit: logs, sines and cosines, polar factors, rotation terms and turned end points;
   3. legacy_draws walks numpy's legacy stream word for word: every texture index of np.random.seed(s) + randint / normal,
      deviates within 2 ulp (log is det_log instead of libm's);
   4. expected_records with noise against the reference's way of running six frames over two simulated frames (sequential,
      the shared tables turned in place, pack_drops with the global RNG and numpy's libm)."""
-import ctypes
 import importlib
-import os
 
 import numpy as np
 import pytest
 
 import helpers as h
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 db = importlib.import_module('rain-rendering_amd.common.db')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _ulp(a, b):
-    """distance in units in the last place of float64 arrays (equal NaNs: 0)"""
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    ia = a.view(np.int64).astype(object)
-    ib = b.view(np.int64).astype(object)
-    ia = np.where(ia < 0, -2 ** 63 - ia, ia)
-    ib = np.where(ib < 0, -2 ** 63 - ib, ib)
-    d = np.abs(ia - ib)
-    d[np.isnan(a) & np.isnan(b)] = 0
-    return d.astype(np.float64)
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libnoiseemu.so'))
-    for name in ('rr_emu_det_log', 'rr_emu_polar_factor'):
-        getattr(lib, name).argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-    lib.rr_emu_det_sincos.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.rr_emu_noise_rotate.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
-    return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
+    return pe.load()
 
 
 def _log_inputs():
@@ -64,14 +41,14 @@ def _angle_inputs():
 
 def test_det_log_within_2ulp_of_libm():
     x = _log_inputs()
-    assert _ulp(particles.det_log(x), np.log(x)).max() <= 2
+    assert cases._ulp(particles.det_log(x), np.log(x)).max() <= 2
 
 
 def test_det_sincos_within_2ulp_of_libm():
     nu = _angle_inputs()
     s, c = particles.det_sincos(nu)
-    assert _ulp(s, np.sin(nu)).max() <= 2
-    assert _ulp(c, np.cos(nu)).max() <= 2
+    assert cases._ulp(s, np.sin(nu)).max() <= 2
+    assert cases._ulp(c, np.cos(nu)).max() <= 2
     s, c = particles.det_sincos(np.array([np.inf, -np.inf, np.nan]))
     assert np.isnan(s).all() and np.isnan(c).all()
 
@@ -79,13 +56,13 @@ def test_det_sincos_within_2ulp_of_libm():
 def test_gxx_statement_equals_numpy_statement(emu):
     x = _log_inputs()
     out = np.empty_like(x)
-    emu.rr_emu_det_log(len(x), _p(x), _p(out))
+    emu.rr_emu_det_log(len(x), x, out)
     assert out.tobytes() == particles.det_log(x).tobytes()
-    emu.rr_emu_polar_factor(len(x), _p(x), _p(out))
+    emu.rr_emu_polar_factor(len(x), x, out)
     assert out.tobytes() == particles.polar_factor(x).tobytes()
     nu = _angle_inputs()
     s, c = np.empty_like(nu), np.empty_like(nu)
-    emu.rr_emu_det_sincos(len(nu), _p(nu), _p(s), _p(c))
+    emu.rr_emu_det_sincos(len(nu), nu, s, c)
     ws, wc = particles.det_sincos(nu)
     assert s.tobytes() == ws.tobytes() and c.tobytes() == wc.tobytes()
     # rotation terms and turned end points of streaks of every direction and length
@@ -101,7 +78,7 @@ def test_gxx_statement_equals_numpy_statement(emu):
     g = rs.normal(0, 1, len(rec))
     for std, scale in ((3.0, 1.0), (10.0, 0.5), (200.0, 7.0)):
         got = rec.copy()
-        emu.rr_emu_noise_rotate(len(got), _p(got), _p(g), std, scale)
+        emu.rr_emu_noise_rotate(len(got), got, g, std, scale)
         s_ = np.stack([rec['x0'], rec['y0']], 1)
         e_ = np.stack([rec['x1'], rec['y1']], 1)
         rc, rsn, s2, e2 = particles.noise_rotation(s_, e_, particles.noise_degrees(g, std, scale))
@@ -129,7 +106,7 @@ def test_legacy_draws_follow_numpys_stream(seed):
         if not big[k]:
             want_g[k] = np.random.normal(0.0, 1.0)
     assert np.array_equal(tex, want_tex)                      # the stream stays aligned to the last drop
-    assert _ulp(g, want_g).max() <= 2 and (g[big] == 0).all()
+    assert cases._ulp(g, want_g).max() <= 2 and (g[big] == 0).all()
 
 
 def _kitti(n_sim, count, draw_seeds=None):

@@ -1,14 +1,13 @@
 """CPU tier: the RIG particle model (tools/particles.py make_rig_particles, rr_particles.h make_rig_slot / rig_view_particle,
 rig.py) -- one persistent, stateless particle field in the rig's frame, seen by several cameras.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/rig_emu.cpp: the code k_rig_particles runs) == numpy, bit for bit;
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code k_rig_particles runs) == numpy, bit for bit;
   2. cross-view geometry: a slot kept by two views at one instant is ONE point of the lattice world; stereo disparity;
   3. every view has the i.i.d. model's law (the thresholds and the control of tests/test_particle_field_host.py);
   4. motion: a slot kept at k and k + 1 in one life has moved by its velocity / cam_hz;
   5. random access: an instant alone, a subset or a permutation of the active views: the same bits per (instant, view);
   6. no double vision: with the host's r the nearest lattice image is the only one a view can see; 1 % less and another is;
   7. every refusal of the Python layer; 8. RainAugment.plan of a [B, V] clip."""
-import ctypes
 import importlib
 import json
 import os
@@ -17,48 +16,26 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_particle_field_host as tf                     # _sample / _same_law / N_LAW: the law test's thresholds and control
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 rigmod = importlib.import_module('rain-rendering_amd.rig')
 db = importlib.import_module('rain-rendering_amd.common.db')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53                                            # unit roundoff of IEEE double
-
-KITTI_STEREO = rigmod.Rig.stereo(0.54)                    # KITTI's documented baseline
-RING6 = rigmod.Rig.yaw_ring([0, 55, 110, 180, -110, -55], 0.8)         # a nuScenes-like surround ring (made-up calibration)
-PITCHED = rigmod.Rig.yaw_ring([0, 40, -40], 0.5, pitches_deg=[0, 10, -5])
-CONFIGS = [('kitti', 1, 25, KITTI_STEREO), ('kitti', 1, 100, KITTI_STEREO), ('cityscapes', 2, 25, rigmod.Rig.stereo(0.22)),
-           ('nuscenes', 1, 100, RING6)]
-IDS = ['kitti25-stereo', 'kitti100-stereo', 'cityscapes-rs2-stereo', 'nuscenes100-ring6']
-
-
-def _options(dataset='kitti', **kw):
-    o = dict(db.settings(dataset))
-    o.pop('sequences', None)
-    o.update(kw)
-    return o
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data)
+U = cases.U
+CONFIGS, IDS = cases.CONFIGS, cases.IDS
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'librigemu.so'))
-    lib.rr_emu_rig_particles.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.rr_emu_rig_records.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
-    return lib
+    return pe.load()
 
 
 # ---- 1. g++ == numpy -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dataset,rs,rate,rig", CONFIGS, ids=IDS)
 def test_gxx_build_equals_numpy(tmp_path, emu, dataset, rs, rate, rig):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([30.0])})
     hz = float(opt['cam_hz'])
     V = len(rig)
     sims, dgrid, cdf = particles.sim_frames(opt, rate, 1, render_scale=rs, seed=1234 + 2 ** 40, model='rig', rig=rig)
@@ -70,68 +47,38 @@ def test_gxx_build_equals_numpy(tmp_path, emu, dataset, rs, rate, rig):
     W, H = opt["cam_CCD_WH"][0] // rs, opt["cam_CCD_WH"][1] // rs
     ratio_db = np.ascontiguousarray(np.asarray(sc.db.ratio, np.float64)[:4])
     tab = np.ascontiguousarray(cdf[0])
+    total = 0
     for i, s in enumerate(sims):
         v = i % V
         n = int(s['n_particles'])
         seed = int(s['key0']) | (int(s['key1']) << 32)
         rec, life = particles.make_rig_particles(cam, dgrid, tab, n, int(s['frame']), seed, hz, rig.views[v], box, cull=False)
         kept, _ = particles.make_rig_particles(cam, dgrid, tab, n, int(s['frame']), seed, hz, rig.views[v], box)
-        one = np.ascontiguousarray(sims[i:i + 1])
-        out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
-        emu.rr_emu_rig_particles(_p(one), hz, _p(views[v:v + 1]), _p(box), _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
-        for name, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-            assert out[:, cols].tobytes() == np.ascontiguousarray(rec[name]).tobytes(), (name, i)
-        assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-        assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == life.tobytes()
+        run = pe.run(model='rig', sim=sims[i:i + 1], cam_hz=hz, view=views[v:v + 1], box=box, dgrid=dgrid, cdf=tab)
+        out, ins, lf, _ = pe.all_slots(run)
+        pe.assert_slots_equal(out, lf, rec, life, i)
         assert np.array_equal(np.nonzero(ins)[0], kept['pid']) and len(kept) > 100
-        got = np.zeros(n, h.hb.DROP_DTYPE)
-        m = emu.rr_emu_rig_records(_p(one), hz, _p(views[v:v + 1]), _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(got), n)
-        assert m == len(want[i]) > 100
-        got = got[:m]
-        for name in h.hb.DROP_DTYPE.names:
-            if name == 'tex_index':                               # the draws pick one of the block of ten
-                assert np.array_equal(got[name], want[i][name] // 10 * 10)
-            else:
-                assert got[name].tobytes() == want[i][name].tobytes(), (name, i)
+        got, _ = pe.records(run, H, W, ratio_db)
+        assert len(got) == len(want[i]) > 100
+        pe.assert_records_equal(got, want[i], 'stream', i)        # the draws pick one of the block of ten
+        total += len(got)
+    print('%s rs %d %d mm/hr, %d views: %d records compared' % (dataset, rs, rate, V, total))
     assert want[0].tobytes() != want[V].tobytes()                 # the field moves from instant to instant
 
 
 # ---- 2. cross-view geometry ------------------------------------------------------------------------------------------
-def _ortho_defect(R):
-    return float(np.abs(R.T @ R - np.eye(3)).max())
-
-
-def _world(rec, view):
-    """R^T p + c of the records' start points, in the operation order the bound below counts."""
-    R, c = view
-    p = rec['wp1']
-    return np.stack([(R[0, i] * p[:, 0] + R[1, i] * p[:, 1]) + R[2, i] * p[:, 2] for i in range(3)], axis=1) + c
-
-
-def _world_bound(rec, view, w):
-    """Largest |R^T p + c - (the slot's lattice point)| rounding can cause, per slot, from the operation count.  u = 2^-53.
-    S bounds every intermediate value on the way: |X| <= w / 2, the offsets from the camera |d| <= |p|_1 (a rotation keeps
-    the length, the 1-norm bounds it), |c|_1, and one period w for the wrap's product.  Roundings on the path of one
-    component: X - c (1), floor(.) w and its subtraction (2), the rotation's three products and two sums (5), the test's own
-    un-rotation (5) and + c (1): 14, each at most u S; the un-rotation multiplies what was there by at most sum_j |R_ji| < 2.
-    R^T R = I + E with |E_ij| <= e (measured on the input matrix, not on the code under test) adds 3 e S."""
-    R, c = view
-    S = np.abs(rec['wp1']).sum(axis=1) + np.abs(c).sum() + 1.5 * w
-    return (2.0 * 14.0 * U + 3.0 * _ortho_defect(R)) * S
-
-
 def _period(cam, dgrid, cdf, slots, seed, box):
     D = particles.sample_diameter(dgrid, cdf, particles.unit32(particles.philox4x32(np.asarray(slots, np.uint64), 0, 0, 1, *particles._key(seed))[0]))
     z_max = np.minimum(((D * 1e-3) * cam.fpx) / 1.0, 15.0)
     return 2.0 * (box[0] * z_max), 2.0 * (box[1] * z_max + box[2])
 
 
-@pytest.mark.parametrize("dataset,rate,rig,n_inst", [('kitti', 25, KITTI_STEREO, 2), ('nuscenes', 100, RING6, 2)], ids=['stereo', 'ring6'])
+@pytest.mark.parametrize("dataset,rate,rig,n_inst", [('kitti', 25, cases.KITTI_STEREO, 2), ('nuscenes', 100, cases.RING6, 2)], ids=['stereo', 'ring6'])
 def test_two_views_see_one_world(dataset, rate, rig, n_inst):
     """Every slot kept by two views at one instant: R_a^T p_a + c_a and R_b^T p_b + c_b agree modulo the lattice period 2 b(D) in
     x and z and without any period in y, within _world_bound.  Stereo, pairs on the same lattice image: ip1.x differs by
     fpx baseline / depth.  (Slots nearer than 5 cm are left out: their depth is clamped for the projection.)"""
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([50.0])})
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([50.0])})
     cam = particles.FrameCamera(opt, 0)
     box = rig.box(cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, rate, box)
@@ -146,16 +93,16 @@ def test_two_views_see_one_world(dataset, rate, rig, n_inst):
                 if len(ra) == 0:
                     continue
                 w, _ = _period(cam, dgrid, cdf, ra['pid'], 21, box)
-                r = _world(ra, rig.views[a]) - _world(rb, rig.views[b])
+                r = cases._world(ra, rig.views[a]) - cases._world(rb, rig.views[b])
                 m = np.rint(r[:, [0, 2]] / w[:, None])
                 r[:, 0] -= m[:, 0] * w
                 r[:, 2] -= m[:, 1] * w
-                bound = _world_bound(ra, rig.views[a], w) + _world_bound(rb, rig.views[b], w) + 2.0 * U * w * (1.0 + np.abs(m).max(axis=1))
+                bound = cases._world_bound(ra, rig.views[a], w) + cases._world_bound(rb, rig.views[b], w) + 2.0 * U * w * (1.0 + np.abs(m).max(axis=1))
                 print('instant %d views %d, %d: %d shared slots, worst |residual| / bound %.3f, %d on another lattice image'
                       % (7 + k, a, b, len(ra), (np.abs(r).max(axis=1) / bound).max(), int((m != 0).any(axis=1).sum())))
                 assert np.all(np.abs(r) <= bound[:, None]), (np.abs(r).max(axis=1) / bound).max()
                 shared += len(ra)
-                if rig is KITTI_STEREO:
+                if rig is cases.KITTI_STEREO:
                     base = rig.views[b][1][0] - rig.views[a][1][0]
                     on = ~(m != 0).any(axis=1)
                     depth = -ra['wp1'][on, 2]
@@ -175,17 +122,17 @@ def test_two_views_see_one_world(dataset, rate, rig, n_inst):
                     same_image += int(on.sum())
     print('%d shared slots compared' % shared)
     assert shared >= 200
-    if rig is KITTI_STEREO:
+    if rig is cases.KITTI_STEREO:
         assert same_image >= 200
 
 
 # ---- 3. the law of every view ------------------------------------------------------------------------------------------
 def _rig_sample(rig, view, seed0):
-    """tf._sample for one view of a rig: N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own."""
-    opt = _options('kitti')
+    """cases._sample for one view of a rig: cases.N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own."""
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
     counts, D, depth, px, py = [], [], [], [], []
-    for i in range(tf.N_LAW):
+    for i in range(cases.N_LAW):
         rec, _ = particles.rig_frame(opt, 25, 7 * i + 3, rig, view, seed=seed0 + i)
         counts.append(len(rec))
         D.append(rec['wd1'] * 1e3)
@@ -197,42 +144,30 @@ def _rig_sample(rig, view, seed0):
 
 def test_every_view_has_the_iid_models_law():
     """Each view of the stereo rig and of a ring with pitched cameras against the i.i.d. model: the count within four Poisson
-    standard errors, Kolmogorov-Smirnov on diameter, depth and image position -- tf._same_law with tf's thresholds and its
+    standard errors, Kolmogorov-Smirnov on diameter, depth and image position -- cases._same_law with tf's thresholds and its
     i.i.d.-against-itself control."""
-    iid_a, iid_b = tf._sample('iid', 1000), tf._sample('iid', 5000)
-    control = tf._same_law(iid_a, iid_b)
+    iid_a, iid_b = cases._sample('iid', 1000), cases._sample('iid', 5000)
+    control = cases._same_law(iid_a, iid_b)
     assert all(v < 1 for v in control.values()), control
     mean = particles.expected_count(iid_a['cam'], 25)[0]
-    for name, rig in (('stereo', KITTI_STEREO), ('pitched ring', PITCHED)):
+    for name, rig in (('stereo', cases.KITTI_STEREO), ('pitched ring', cases.PITCHED)):
         for v in range(len(rig)):
             s = _rig_sample(rig, v, 9000 + 1000 * v)
-            got, got_b = tf._same_law(s, iid_a), tf._same_law(s, iid_b)
+            got, got_b = cases._same_law(s, iid_a), cases._same_law(s, iid_b)
             print('%s view %d: mean count %.1f (model %.1f); statistic / threshold vs iid: %s; vs iid (other seeds): %s'
                   % (name, v, s['counts'].mean(), mean, got, got_b))
-            assert abs(s['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
+            assert abs(s['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)
             assert all(x < 1 for x in got.values()), (name, v, got)
             assert all(x < 1 for x in got_b.values()), (name, v, got_b)
 
 
 # ---- 4. motion ---------------------------------------------------------------------------------------------------------
-def _state_bounds(vel, w, wy, life, dt):
-    """tf._track_bounds for the rig's box: x and z both wrap modulo w and both end in `f w - b` (the field's z has one operation
-    fewer; the x count covers it), y falls through wy."""
-    box = np.stack([w, wy, w], axis=1)
-    out = tf._track_bounds(vel, box, life, dt)
-    S = life + 2.0
-    T = wy / np.abs(vel[:, 1])
-    R = np.abs(vel[:, 2]) * T / w
-    out[:, 2] = (2.0 * ((4.0 * S + 5.0) * R + 3.0) + 2.0) * U * w + 2.0 * U * np.abs(vel[:, 2] * dt)
-    return out
-
-
-@pytest.mark.parametrize("rig,dataset,rate", [(KITTI_STEREO, 'kitti', 25), (PITCHED, 'kitti', 25)], ids=['stereo', 'pitched-ring'])
+@pytest.mark.parametrize("rig,dataset,rate", [(cases.KITTI_STEREO, 'kitti', 25), (cases.PITCHED, 'kitti', 25)], ids=['stereo', 'pitched-ring'])
 def test_tracks_move_by_velocity_over_cam_hz(rig, dataset, rate):
     """A slot kept by view v at k and k + 1 in one life: p(k + 1) - p(k) = R_v velocity / cam_hz up to whole lattice periods --
     checked on the residual turned back into the rig frame, within the rounding of the two positions (_world_bound), of the
-    rig-frame state (tf._track_bounds with the rig's box) and of the expected displacement."""
-    opt = _options(dataset, sim_steps={"cam_motion": np.array([50.0])})
+    rig-frame state (cases._track_bounds with the rig's box) and of the expected displacement."""
+    opt = cases.options(dataset, sim_steps={"cam_motion": np.array([50.0])})
     cam = particles.FrameCamera(opt, 0)
     box = rig.box(cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, rate, box)
@@ -251,11 +186,11 @@ def test_tracks_move_by_velocity_over_cam_hz(rig, dataset, rate):
                 continue
             vel = st['vel'][ra['pid']]
             w, wy = 2.0 * st['b'][ra['pid']], 2.0 * st['by'][ra['pid']]
-            r = (_world(rb, rig.views[v]) - _world(ra, rig.views[v])) - vel * dt
+            r = (cases._world(rb, rig.views[v]) - cases._world(ra, rig.views[v])) - vel * dt
             m = np.rint(r[:, [0, 2]] / w[:, None])
             r[:, 0] -= m[:, 0] * w
             r[:, 2] -= m[:, 1] * w
-            bound = _state_bounds(vel, w, wy, life, dt) + (_world_bound(ra, rig.views[v], w) + _world_bound(rb, rig.views[v], w))[:, None]
+            bound = cases._state_bounds(vel, w, wy, life, dt) + (cases._world_bound(ra, rig.views[v], w) + cases._world_bound(rb, rig.views[v], w))[:, None]
             print('view %d, %d -> %d: %d kept again, worst |residual| / bound per axis %s' % (v, k, k + 1, len(ra), (np.abs(r) / bound).max(axis=0)))
             assert np.all(np.abs(r) <= bound), (np.abs(r) / bound).max(axis=0)
             total += len(ra)
@@ -266,9 +201,9 @@ def test_tracks_move_by_velocity_over_cam_hz(rig, dataset, rate):
 # ---- 5. random access ------------------------------------------------------------------------------------------------
 def test_an_instant_and_a_view_alone_have_the_runs_bits(tmp_path):
     sc = h.Scene(tmp_path, 64, 96, 10)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     hz = opt['cam_hz']
-    rig = KITTI_STEREO
+    rig = cases.KITTI_STEREO
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=3, model='rig', rig=rig)
     run = particles.rig_run_sims(sims, np.arange(6), 2)
     kw = dict(model='rig', cam_hz=hz, rig=rig)
@@ -295,9 +230,9 @@ def test_the_nearest_image_is_the_only_visible_one():
     nearest is visible there -- in the periodic world that slot would be seen by an image the statement does not look at.
     (A realistic camera cannot see two images of one slot at once: its frustum is narrower than a period in every direction;
     what a too small r breaks is the nearest-image cull, and that is what is shown.)"""
-    opt = _options('nuscenes')
+    opt = cases.options('nuscenes')
     cam = particles.FrameCamera(opt, 0)
-    rig = RING6
+    rig = cases.RING6
     box = rig.box(cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, 100, box)
     n = 400000
@@ -339,20 +274,20 @@ def test_refusals_of_the_python_layer(tmp_path):
     with pytest.raises(ValueError, match='intrinsics'):
         rigmod.Rig.from_spec(spec)                                           # per-view intrinsics are out of scope
     with open(spec, 'w') as fh:
-        json.dump({"views": [{"R": v[0].reshape(9).tolist(), "c": v[1].tolist()} for v in RING6.views]}, fh)
-    assert rigmod.Rig.from_spec(spec).as_records().tobytes() == RING6.as_records().tobytes()
-    assert rigmod.Rig.from_spec('stereo:0.54').as_records().tobytes() == KITTI_STEREO.as_records().tobytes()
+        json.dump({"views": [{"R": v[0].reshape(9).tolist(), "c": v[1].tolist()} for v in cases.RING6.views]}, fh)
+    assert rigmod.Rig.from_spec(spec).as_records().tobytes() == cases.RING6.as_records().tobytes()
+    assert rigmod.Rig.from_spec('stereo:0.54').as_records().tobytes() == cases.KITTI_STEREO.as_records().tobytes()
     for bad in ([], [0, 0], [2], [-1], [0.5]):
         with pytest.raises(ValueError, match='distinct'):
             rigmod.check_active(bad, 2)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     with pytest.raises(ValueError, match='rig='):
         particles.sim_frames(opt, 25, 1, model='rig')
     with pytest.raises(ValueError, match='one camera'):
-        particles.sim_frames(_options('kitti', sim_mode='steps', sim_steps={"cam_focal": np.array([4.0, 6.0])}), 25, 2, model='rig', rig=KITTI_STEREO)
-    sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, model='rig', rig=KITTI_STEREO)
+        particles.sim_frames(cases.options('kitti', sim_mode='steps', sim_steps={"cam_focal": np.array([4.0, 6.0])}), 25, 2, model='rig', rig=cases.KITTI_STEREO)
+    sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, model='rig', rig=cases.KITTI_STEREO)
     with pytest.raises(ValueError, match='angular noise'):
-        particles.expected_records(sims, dgrid, cdf, None, model='rig', cam_hz=10.0, rig=KITTI_STEREO, noise_std=2.0, noise_scale=1.0)
+        particles.expected_records(sims, dgrid, cdf, None, model='rig', cam_hz=10.0, rig=cases.KITTI_STEREO, noise_std=2.0, noise_scale=1.0)
     # RainAugment
     root = str(tmp_path)
     h.synthetic.write_streak_db(os.path.join(root, 'rainstreakdb'))
@@ -360,14 +295,14 @@ def test_refusals_of_the_python_layer(tmp_path):
     with pytest.raises(ValueError, match='go together'):
         augment.RainAugment('kitti', particle_model='rig', **kw)
     with pytest.raises(ValueError, match='go together'):
-        augment.RainAugment('kitti', particle_model='field', rig=KITTI_STEREO, **kw)
+        augment.RainAugment('kitti', particle_model='field', rig=cases.KITTI_STEREO, **kw)
     with pytest.raises(ValueError, match='views='):
         augment.RainAugment('kitti', views=[0], **kw)
     with pytest.raises(TypeError, match='rig.Rig'):
         augment.RainAugment('kitti', particle_model='rig', rig=[(eye, [0, 0, 0])], **kw)
     with pytest.raises(ValueError, match='distinct'):
-        augment.RainAugment('kitti', particle_model='rig', rig=KITTI_STEREO, views=[0, 2], **kw)
-    aug = augment.RainAugment('kitti', particle_model='rig', rig=KITTI_STEREO, **kw)
+        augment.RainAugment('kitti', particle_model='rig', rig=cases.KITTI_STEREO, views=[0, 2], **kw)
+    aug = augment.RainAugment('kitti', particle_model='rig', rig=cases.KITTI_STEREO, **kw)
     import torch
     H, W = aug.frame_size()
     with pytest.raises(ValueError, match=r'\[B, V = 2, 3, H, W\]'):
@@ -387,13 +322,13 @@ def test_augment_plan_of_a_rig_clip(tmp_path):
     SEQ = 'data_object/training'
     root = str(tmp_path)
     h.synthetic.write_streak_db(os.path.join(root, 'rainstreakdb'))
-    kw = dict(streaks_db=os.path.join(root, 'rainstreakdb'), sequence=SEQ, particle_model='rig', rig=KITTI_STEREO)
+    kw = dict(streaks_db=os.path.join(root, 'rainstreakdb'), sequence=SEQ, particle_model='rig', rig=cases.KITTI_STEREO)
     aug = augment.RainAugment('kitti', **kw)
     right = augment.RainAugment('kitti', views=[1], **kw)
     st = db.settings('kitti')
     opts = db.sim('kitti', SEQ, os.path.join('particles', 'kitti'))['options']
     n_sim = particles.n_sim_frames(opts)
-    sims, dgrid, cdf = particles.sim_frames(opts, 25, n_sim, render_scale=st['render_scale'], seed=0, model='rig', rig=KITTI_STEREO)
+    sims, dgrid, cdf = particles.sim_frames(opts, 25, n_sim, render_scale=st['render_scale'], seed=0, model='rig', rig=cases.KITTI_STEREO)
     idx = n_sim - 2 + np.arange(5)                                # a clip across the end of the simulated frames: time goes on
     p = aug.plan(25, idx)
     assert p['particle_model'] == 'rig' and p['cam_hz'] == float(opts['cam_hz']) and p['views'] == [0, 1]
@@ -401,8 +336,8 @@ def test_augment_plan_of_a_rig_clip(tmp_path):
     assert p['sims'].tobytes() == want.tobytes() and len(p['sims']) == 10 and p['fog'].shape == (10, 4)
     assert np.array_equal(p['sims']['frame'], np.repeat(idx, 2)) and np.array_equal(p['sims']['draw_seed'], np.repeat(idx, 2))
     assert np.array_equal(p['d_grid'], dgrid) and np.array_equal(p['cdf'], np.atleast_2d(cdf))
-    assert p['rig_views'].tobytes() == KITTI_STEREO.as_records().tobytes()
-    assert tuple(p['rig_box']) == tuple(KITTI_STEREO.box(particles.FrameCamera(opts, 0)))
+    assert p['rig_views'].tobytes() == cases.KITTI_STEREO.as_records().tobytes()
+    assert tuple(p['rig_box']) == tuple(cases.KITTI_STEREO.box(particles.FrameCamera(opts, 0)))
     n_slots = int(p['sims']['n_particles'][0])
     assert set(p['sims']['n_particles'].tolist()) == {n_slots}
     assert p['drops_cap'] == (min(max(1024, n_slots), 2 ** 16) + 3) // 4 * 4

@@ -2,7 +2,7 @@
 rr_particles.h RATE, rr_set_particle_rate_series).  Slots and tables are the PEAK rate's; a life is kept with the probability
 exp(-(Lambda(R) - Lambda(R_peak)) D) of the rate R at its birth, decided by word 3 of the life's Philox block 1.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/rate_emu.cpp: the code the RATE kernels run) == numpy, bit for bit, for
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code the RATE kernels run) == numpy, bit for bit, for
      every slot kept or culled and for the finished records: field, rig (stereo, a yaw ring), a trajectory; both draws, jitter 0 / 5,
      mean wind (0, 0) / (-7.5, 2), with and without a gust series; series with n = 1, a frame at m = 0, frame0 = 2^31 + 3, a frame
      at m = n - 1, a series that touches rate 0;
@@ -13,7 +13,6 @@ exp(-(Lambda(R) - Lambda(R_peak)) D) of the rate R at its birth, decided by word
   5. a dry spell empties the field after the longest fall period, and what is left before is older than the spell;
   6. both stereo views keep the same (slot, life) among the slots both see;
   7. shower_series' values, every refusal, the driver's flag and RainAugment.plan."""
-import ctypes
 import importlib
 import os
 
@@ -21,54 +20,21 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_particle_field_host as tf                     # _track_bounds / _same_law / _sample / N_LAW
-import test_particle_rig_host as tr                       # the rigs
-import test_particle_wind_host as tw                      # _case_run, the rigs and the trajectory of the wind's tests
-from test_particle_draws_host import MODEL_ID, _options, _p
-from test_particle_jitter_host import _same_field
-from test_particle_trajectory_host import MONO
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HZ = 10.0                                                 # KITTI's cam_hz
-PEAK = 25.0                                               # tw._case_run's tables
-BIG0 = 2 ** 31 + 3
+HZ, PEAK, BIG0 = cases.HZ, cases.PEAK, cases.BIG0
 WINDS = [(0.0, 0.0), (-7.5, 2.0)]
 R = particles.RateSeries
-
-
-def rate_cases(traj=False):
-    """[(RateSeries, frames)]: the series of item 1 (and of the GPU tier) under KITTI's 25 mm/hr tables, and the time indices
-    generated under each.  n = 1 (its only frame is m = 0 = n - 1); a six-interval series that touches 0, at m = 0 -- where nearly
-    every birth lies before the series: the held first value -- and at m = n - 1; frame0 = 2^31 + 3 at m = 0 and inside.  Under the
-    three-pose trajectory the indices are 0 .. 2 (its box is low: a fall takes two to four frames, so the zero sits where the
-    compared frame's youngest drops are born, not its oldest)."""
-    if traj:
-        return [(R(1, [12.0, 20.0], peak=PEAK), [1]),
-                (R(0, [8.0, 16.0, 0.0, 25.0]), [0, 2])]
-    return [(R(3, [12.0, 20.0], peak=PEAK), [3]),
-            (R(0, [8.0, 14.0, 25.0, 0.0, 5.0, 16.0, 22.0]), [0, 5]),
-            (particles.shower_series(4, HZ, PEAK, 5.0, 0.8, frame0=BIG0, phase=1.0), [BIG0, BIG0 + 2])]
-
-
-def _gusts_over(rs):
-    """A gust series over the frames of the rate series `rs`."""
-    return particles.gust_series(rs.n, HZ, 4.0, 2.0, seed=5, frame0=rs.frame0)
-
-
 # (name, model, rig, trajectory)
-CASES = [c for c in tw.CASES if c[1] != 'iid']
+CASES = [c for c in cases.CASES if c[1] != 'iid']
 CASE_IDS = [c[0] for c in CASES]
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'librateemu.so'))
-    V, I, D, U32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_uint32
-    lib.rr_emu_rate_particles.argtypes = [I, I, D, D, I, U32, V, I, U32, V, V, D, V, V, V, V, V, I, V, V, V]
-    lib.rr_emu_rate_records.argtypes = [I, I, D, I, D, D, I, U32, V, I, U32, V, V, D, V, V, V, V, V, I, I, I, V, V, I]
-    lib.rr_emu_rate_records.restype = I
-    return lib
+    return pe.load()
 
 
 @pytest.fixture(scope='module')
@@ -98,8 +64,8 @@ def _all_slots(model, cam, dgrid, tab, s, hz, rig, traj, view, box, **kw):
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
     total = n_before = n_rejected = 0
-    for rs, frames in rate_cases(traj is not None):
-        opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, traj, frames)
+    for rs, frames in cases.rate_cases(traj is not None):
+        opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, frames)
         hz = float(opt['cam_hz'])
         assert hz == HZ
         V = len(rig) if rig is not None else 1
@@ -111,45 +77,28 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
         dlam = np.ascontiguousarray(rs.dlam())
         assert dlam.min() >= 0.0 and dlam.max() <= particles.RATE_DLAM_MAX
         for wind in WINDS:
-            for gusts in (None, _gusts_over(rs)):
+            for gusts in (None, cases.gusts_over(rs)):
                 air = dict(wind=wind, gusts=gusts)
-                gn, g0, disp = (0, 0, None) if gusts is None else (gusts.n, gusts.frame0, np.ascontiguousarray(gusts.disp))
-                windy = int(bool(wind[0] or wind[1]) or gusts is not None)
-                dp = _p(disp) if disp is not None else None
                 no_series = particles.expected_records(sims, dgrid, cdf, sdb, **air, **kw)
                 want = {(d, j): particles.expected_records(sims, dgrid, cdf, sdb, draws=d, jitter=j, rate_series=rs, **air, **kw)
                         for d in ('counter', 'stream') for j in (0.0, 5.0)}
                 for i, s in enumerate(sims):
-                    one = np.ascontiguousarray(sims[i:i + 1])
-                    n, v = int(s['n_particles']), i % V
-                    view_rec = np.ascontiguousarray(views[v:v + 1]) if views is not None and traj is None else None
-                    view = _p(view_rec) if view_rec is not None else None
-                    po = np.ascontiguousarray(poses[int(s['frame']), v:v + 1]) if traj is not None else None
+                    v = i % V
+                    view = views[v:v + 1] if views is not None and traj is None else None
+                    po = poses[int(s['frame']), v:v + 1] if traj is not None else None
+                    under = dict(model=model, sim=sims[i:i + 1], cam_hz=hz, view=view, pose=po, box=box, dgrid=dgrid, cdf=tab, rate_series=rs, **air)
                     rec, life, kept = _all_slots(model, cam, dgrid, tab, s, hz, rig, traj, v, box, rate_series=rs, **air)
                     _, _, kept_plain = _all_slots(model, cam, dgrid, tab, s, hz, rig, traj, v, box, **air)
-                    out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
-                    emu.rr_emu_rate_particles(MODEL_ID[model], windy, wind[0], wind[1], gn, g0, dp, rs.n, rs.frame0, _p(dlam), _p(one), hz,
-                                              view, _p(po) if po is not None else None, _p(box), _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins),
-                                              _p(lf))
+                    out, ins, lf, _ = pe.all_slots(pe.run(**under))
                     assert ins.tobytes() == kept.tobytes(), (i, wind, gusts is not None, frames)     # every slot: kept or culled
                     assert np.all(kept <= kept_plain)                                               # the series only removes
                     n_rejected += int((kept_plain & ~kept & 1).sum())
-                    for nm, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-                        assert out[:, cols].tobytes() == np.ascontiguousarray(rec[nm]).tobytes(), (nm, i, wind, frames)
-                    assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-                    assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == np.ascontiguousarray(life).tobytes()
+                    pe.assert_slots_equal(out, lf, rec, life, (i, wind, frames))
                     for (draws, jit), recs in want.items():
-                        got = np.zeros(n, h.hb.DROP_DTYPE)
-                        m = emu.rr_emu_rate_records(MODEL_ID[model], int(draws == 'counter'), jit, windy, wind[0], wind[1], gn, g0, dp, rs.n,
-                                                    rs.frame0, _p(dlam), _p(one), hz, view, _p(po) if po is not None else None, _p(box),
-                                                    _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(got), n)
-                        w = recs[i]
+                        got, _ = pe.records(pe.run(counter=draws == 'counter', jitter=jit, **under), H, W, ratio_db)
+                        m, w = len(got), recs[i]
                         assert m == len(w) > 100, (i, wind, draws, jit, m, len(w))
-                        for nm in h.hb.DROP_DTYPE.names:
-                            if nm == 'tex_index' and draws == 'stream':    # (the particle kernel leaves the block's first texture to k_particle_draws)
-                                assert np.array_equal(got[:m][nm], w[nm] // 10 * 10), (i, wind, draws, jit)
-                            else:
-                                assert _same_field(got[:m][nm], w[nm]), (i, wind, draws, jit, nm)
+                        pe.assert_records_equal(got, w, draws, (i, wind, draws, jit), cases._same_field)
                         total += m
                     assert len(want[('stream', 0.0)][i]) < len(no_series[i])                  # the series does something
         # the held first value is reached where the frame is the series' first
@@ -169,7 +118,7 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 def test_no_series_and_a_series_at_its_peak_give_todays_bytes(sdb, name, model, rig, traj):
     frames = [0, 2]
-    opt, sims, dgrid, cdf, kw, cam, box = tw._case_run(model, rig, traj, frames)
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, frames)
     hz = float(opt['cam_hz'])
     at_peak = R(0, [PEAK] * 4)
     assert at_peak.peak == PEAK and at_peak.dlam().tobytes() == np.zeros(4).tobytes()
@@ -197,7 +146,7 @@ def test_no_series_and_a_series_at_its_peak_give_todays_bytes(sdb, name, model, 
                 sc = particles.rig_state(cam, dgrid, tab, n, k, seed, hz, tuple(box), rate_series=at_peak, **air)
                 assert set(sa) == set(sb) and all(sa[key].tobytes() == sb[key].tobytes() == sc[key].tobytes() for key in sa)
                 assert sc['alive'].all()
-    opt2 = _options('kitti')
+    opt2 = cases.options('kitti')
     if model == 'field':
         a = particles.generate(opt2, 25, 2, seed=3, model='field')
         for series in (None, at_peak):
@@ -214,14 +163,14 @@ def test_no_series_and_a_series_at_its_peak_give_todays_bytes(sdb, name, model, 
 
 # ---- 3. the law ----------------------------------------------------------------------------------------------------
 def test_a_thinned_field_has_the_law_of_the_field_at_the_lower_rate():
-    """Slots and tables at 100 mm/hr, thinned by a series constant at 25 mm/hr: over tf.N_LAW independent frames (a seed each, as
-    tf._sample takes them) the kept count is within four standard errors of expected_count(cam, 25), and diameter, depth and image
-    position pass tf._same_law -- its bounds, unchanged -- against plain 25 mm/hr fields of other seeds."""
-    opt = _options('kitti')
+    """Slots and tables at 100 mm/hr, thinned by a series constant at 25 mm/hr: over cases.N_LAW independent frames (a seed each, as
+    cases._sample takes them) the kept count is within four standard errors of expected_count(cam, 25), and diameter, depth and image
+    position pass cases._same_law -- its bounds, unchanged -- against plain 25 mm/hr fields of other seeds."""
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
-    rs = R(0, [25.0] * (7 * tf.N_LAW + 5), peak=100.0)
+    rs = R(0, [25.0] * (7 * cases.N_LAW + 5), peak=100.0)
     counts, D, depth, px, py = [], [], [], [], []
-    for i in range(tf.N_LAW):                                  # tf._sample('field', 9000) at the peak, under the series
+    for i in range(cases.N_LAW):                                  # cases._sample('field', 9000) at the peak, under the series
         rec, _ = particles.field_frame(opt, 100, 7 * i + 3, seed=9000 + i, rate_series=rs)
         counts.append(len(rec))
         D.append(rec['wd1'] * 1e3)
@@ -229,22 +178,22 @@ def test_a_thinned_field_has_the_law_of_the_field_at_the_lower_rate():
         px.append(rec['ip1'][:, 0])
         py.append(rec['ip1'][:, 1])
     thin = dict(cam=cam, counts=np.array(counts), D=np.concatenate(D), depth=np.concatenate(depth), px=np.concatenate(px), py=np.concatenate(py))
-    plain_a, plain_b = tf._sample('field', 3000), tf._sample('field', 5000)
-    control = tf._same_law(plain_a, plain_b)
+    plain_a, plain_b = cases._sample('field', 3000), cases._sample('field', 5000)
+    control = cases._same_law(plain_a, plain_b)
     assert all(v < 1 for v in control.values()), control
     mean = particles.expected_count(cam, 25)[0]
-    print('kept count: mean %.1f against expected_count %.1f, four standard errors %.1f' % (thin['counts'].mean(), mean, 4 * np.sqrt(mean / tf.N_LAW)))
-    assert abs(thin['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
-    got, got_b = tf._same_law(thin, plain_a), tf._same_law(thin, plain_b)
+    print('kept count: mean %.1f against expected_count %.1f, four standard errors %.1f' % (thin['counts'].mean(), mean, 4 * np.sqrt(mean / cases.N_LAW)))
+    assert abs(thin['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)
+    got, got_b = cases._same_law(thin, plain_a), cases._same_law(thin, plain_b)
     print('statistic / threshold -- field vs field: %s\n  thinned vs field: %s\n  thinned vs field (other seeds): %s' % (control, got, got_b))
     assert all(v < 1 for v in got.values()), got
     assert all(v < 1 for v in got_b.values()), got_b
     # the test can tell: the peak's field itself has four times the count and larger drops
     peak = dict(thin)
-    rec = [particles.field_frame(opt, 100, 7 * i + 3, seed=9000 + i)[0] for i in range(tf.N_LAW)]
+    rec = [particles.field_frame(opt, 100, 7 * i + 3, seed=9000 + i)[0] for i in range(cases.N_LAW)]
     peak['counts'] = np.array([len(r) for r in rec])
     peak['D'] = np.concatenate([r['wd1'] * 1e3 for r in rec])
-    bad = tf._same_law(peak, plain_a)
+    bad = cases._same_law(peak, plain_a)
     assert bad['count'] > 1 and bad['D'] > 1, bad
 
 
@@ -261,9 +210,9 @@ def _ramp():
 def test_a_ramp_keeps_or_drops_a_life_for_good_and_kept_tracks_move_by_the_velocity():
     """25 -> 5 mm/hr over 40 frames.  The decision belongs to the (slot, life): its birth time m - tau cam_hz is the same number in
     every frame of the life up to the rounding of tau, so a life kept in frames k and k + 1 without the series is kept in both or
-    in neither with it.  The tracks that stay move by tf._track_bounds' displacement: the series touches no position.  (FAST_HZ.)"""
+    in neither with it.  The tracks that stay move by cases._track_bounds' displacement: the series touches no position.  (FAST_HZ.)"""
     rs = _ramp()
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([50.0])}, cam_hz=FAST_HZ)
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([50.0])}, cam_hz=FAST_HZ)
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     dt = 1.0 / cam.hz
@@ -292,7 +241,7 @@ def test_a_ramp_keeps_or_drops_a_life_for_good_and_kept_tracks_move_by_the_veloc
         r = (tb['wp1'][jb] - ta['wp1'][ja]) - vel * dt
         r[:, 0] -= box[:, 0] * np.rint(r[:, 0] / box[:, 0])
         r[:, 2] -= box[:, 2] * np.rint(r[:, 2] / box[:, 2])
-        bound = tf._track_bounds(vel, box, tla[ja], dt)
+        bound = cases._track_bounds(vel, box, tla[ja], dt)
         assert np.all(np.abs(r) <= bound), (k, (np.abs(r) / bound).max(axis=0))
         tracked += len(ja)
     print('ramp: %d (slot, life) pairs kept in both frames, %d in neither, %d tracks checked' % (both, neither, tracked))
@@ -325,7 +274,7 @@ def test_the_count_follows_the_rate():
     the statement's expectation and against expected_count at the frames' own rates alike (at KITTI's 10 frames/s a fall lasts one
     to three frames, and the lag moves the expectation by 6 to 8 drops of 220 to 560)."""
     rs = _ramp()
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
     means, wants = [], []
     for frames in (range(0, 10), range(N_RAMP - 10, N_RAMP)):
@@ -351,7 +300,7 @@ def test_a_dry_spell_empties_the_field_after_the_longest_fall_period():
     """The rate is 25 up to time index 2 and 0 from index 3 on.  A life born at or after index 3 is never admitted (L = 100), so a
     frame k > 3 holds only drops at least (k - 3) / cam_hz old, and none once that exceeds the longest fall period of the settings
     -- computed here from field_kinematics' boxes and velocities.  (FAST_HZ.)"""
-    opt = _options('kitti', cam_hz=FAST_HZ)
+    opt = cases.options('kitti', cam_hz=FAST_HZ)
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     n_slots = int(particles.field_slot_counts(opt, 25, 1, 11)[0])
@@ -379,9 +328,9 @@ def test_a_dry_spell_empties_the_field_after_the_longest_fall_period():
 
 # ---- 6. the rig ----------------------------------------------------------------------------------------------------
 def test_both_stereo_views_keep_the_same_lives():
-    rs = rate_cases()[1][0]
-    rig = tr.KITTI_STEREO
-    opt = _options('kitti')
+    rs = cases.rate_cases()[1][0]
+    rig = cases.KITTI_STEREO
+    opt = cases.options('kitti')
     seen = rejected = 0
     for k in (0, 5):
         a = [particles.rig_frame(opt, 25, k, rig, v, seed=3) for v in (0, 1)]
@@ -440,13 +389,13 @@ def test_refusals(sdb):
     with pytest.raises(ValueError, match='no time'):
         particles._check_rate_series(R(0, ok), 'iid')
     # the generator's: the i.i.d. model, a frame outside the series, run_pos
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
     with pytest.raises(ValueError, match='no time'):
         particles.expected_records(sims, dgrid, cdf, sdb, rate_series=R(0, ok))
     with pytest.raises(ValueError, match='no time'):
         particles.generate(opt, 25, 1, rate_series=R(0, ok))
-    opt, fs, dgrid, cdf, kw, cam, box = tw._case_run('field', None, None, [2])
+    opt, fs, dgrid, cdf, kw, cam, box = cases.case_run('field', None, None, [2])
     with pytest.raises(ValueError, match='outside the rate series'):
         particles.expected_records(fs, dgrid, cdf, sdb, rate_series=R(0, ok), **kw)
     with pytest.raises(ValueError, match='outside the rate series'):
@@ -457,7 +406,7 @@ def test_refusals(sdb):
     with pytest.raises(ValueError, match='outside the rate series'):
         particles.generate(opt, 25, 3, model='field', rate_series=R(0, ok))
     with pytest.raises(ValueError, match='outside the rate series'):
-        particles.rig_frame(opt, 25, 2, MONO, 0, rate_series=R(0, ok))
+        particles.rig_frame(opt, 25, 2, cases.MONO, 0, rate_series=R(0, ok))
     runp = fs.copy()
     runp['run_pos'] = 1
     with pytest.raises(ValueError, match='run_pos'):
@@ -520,7 +469,7 @@ def test_the_driver_and_the_augmenter_carry_the_series(tmp_path):
         aug.plan(None, [4, 5])
     aug.set_showers(rs)
     assert aug.plan(None, [4])['showers'] is rs
-    rig_aug = augment.RainAugment('kitti', particle_model='rig', rig=tr.KITTI_STEREO, showers=rs, **kw)
+    rig_aug = augment.RainAugment('kitti', particle_model='rig', rig=cases.KITTI_STEREO, showers=rs, **kw)
     pr = rig_aug.plan(None, [6, 0])
     assert pr['showers'] is rs and pr['fog'].shape == (4, 4) and pr['fog'][0].tobytes() == pr['fog'][1].tobytes() == p['fog'][0].tobytes()
     for bad in ('showers', (0, rs.rate), particles.RateSeries(0, [25.0, -1.0]), particles.RateSeries(0, [25.0, 5.0], peak=20.0)):

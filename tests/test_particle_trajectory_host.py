@@ -1,14 +1,13 @@
 """CPU tier: the rig particle model under a camera TRAJECTORY (tools/particles.py make_rig_particles view_end=, rr_particles.h
 traj_view_start / traj_view_end, trajectory.py) -- the rig's lattice world seen from a rig that moves and turns.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/traj_emu.cpp: the code k_rig_particles<.., TRAJ> runs) == numpy, bit for bit;
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code k_rig_particles<.., TRAJ> runs) == numpy, bit for bit;
   2. a trajectory whose two ends coincide == the rig model with those composed views; an identity trajectory == the rig model;
   3. coherence: on an arc a slot kept in frames k and k + 1 in one life has moved in the WORLD by (wind, -v, 0) / cam_hz;
   4. every frame of the arc has the i.i.d. model's law (the thresholds and the control of tests/test_particle_field_host.py);
   5. no double vision over the whole arc with Trajectory.box's r; 1 % less and another lattice image is visible;
   6. a camera yawing in place: streaks displaced horizontally by fpx yaw_rate exposure at the image centre, sign included;
   7. every refusal of trajectory.py, the file reader, both conventions;  8. the ABI layout of rr_traj_pose."""
-import ctypes
 import importlib
 import os
 
@@ -16,50 +15,20 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_particle_field_host as tf                     # _sample / _same_law / N_LAW: the law test's thresholds and control
-import test_particle_rig_host as tr                       # _world / _world_bound / _state_bounds: the rounding bounds of the rig's world
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
 rigmod = importlib.import_module('rain-rendering_amd.rig')
 trajmod = importlib.import_module('rain-rendering_amd.trajectory')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
-_options, _p = tr._options, tr._p
-MONO = rigmod.Rig.from_spec('mono')
-RIGS = [('stereo', tr.KITTI_STEREO), ('ring6', tr.RING6), ('mono', MONO)]
-
-
-def _pose(yaw_deg, pitch_deg=0.0, t=(0.0, 0.0, 0.0)):
-    """rig -> world, native frame: yaw counter-clockwise seen from above, then pitch (positive looks up)."""
-    P = np.zeros((3, 4))
-    P[:, :3] = rigmod._rot_y(yaw_deg) @ rigmod._rot_x(pitch_deg)
-    P[:, 3] = t
-    return P
-
-
-def arc(n, speed=10.0, yaw_rate_deg=20.0, hz=10.0, origin=(0.0, 0.0, 0.0)):
-    """A left-hand bend at constant speed: heading psi_k = yaw_rate k / hz, on a circle of radius speed / yaw_rate."""
-    om = np.deg2rad(yaw_rate_deg)
-    rad = speed / om
-    poses = []
-    for k in range(n):
-        psi = om * k / hz
-        # forward is rot_y(psi) (0, 0, -1) = (-sin psi, 0, -cos psi); the centre of the circle lies to the left, at (-rad, 0, 0)
-        poses.append(_pose(np.rad2deg(psi), 0.0, (origin[0] - rad + rad * np.cos(psi), origin[1], origin[2] - rad * np.sin(psi))))
-    return trajmod.Trajectory(np.array(poses), hz, 'native')
-
-
-ARC = arc(24)
+RIGS = [('stereo', cases.KITTI_STEREO), ('ring6', cases.RING6), ('mono', cases.MONO)]
+ARC = cases.arc(24)
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libtrajemu.so'))
-    lib.rr_emu_traj_particles.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.rr_emu_traj_records.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
-    return lib
+    return pe.load()
 
 
 # ---- 1. g++ == numpy -----------------------------------------------------------------------------------------------
@@ -70,8 +39,8 @@ def _pinned_trajectory():
     poses = []
     for yaw, pitch, dist in pins:
         d = np.array([0.6, 0.0, -0.8]) * dist
-        poses.append(_pose(yaw, pitch, d))
-        poses.append(_pose(yaw + 2.0, pitch + 0.5, d + np.array([0.3, 0.02, -0.9])))
+        poses.append(cases.pose(yaw, pitch, d))
+        poses.append(cases.pose(yaw + 2.0, pitch + 0.5, d + np.array([0.3, 0.02, -0.9])))
     return trajmod.Trajectory(np.array(poses), 10.0, 'native')
 
 
@@ -79,7 +48,7 @@ def _pinned_trajectory():
 def test_gxx_build_equals_numpy(tmp_path, emu, name, rig):
     sc = h.Scene(tmp_path, 64, 96, 10)
     traj = _pinned_trajectory()
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     hz = float(opt['cam_hz'])
     V = len(rig)
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=1234 + 2 ** 40, model='rig', rig=rig, trajectory=traj)
@@ -102,23 +71,14 @@ def test_gxx_build_equals_numpy(tmp_path, emu, name, rig):
         kw = dict(view_end=(po['R1'][0], po['c1'][0]))
         rec, life = particles.make_rig_particles(cam, dgrid, tab, n, k, seed, hz, (po['R0'][0], po['c0'][0]), box, cull=False, **kw)
         kept, _ = particles.make_rig_particles(cam, dgrid, tab, n, k, seed, hz, (po['R0'][0], po['c0'][0]), box, **kw)
-        one = np.ascontiguousarray(sims[i:i + 1])
-        out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
-        emu.rr_emu_traj_particles(_p(one), hz, _p(po), _p(box), _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
-        for nm, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-            assert out[:, cols].tobytes() == np.ascontiguousarray(rec[nm]).tobytes(), (nm, i)
-        assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-        assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == life.tobytes()
+        run = pe.run(model='rig', sim=sims[i:i + 1], cam_hz=hz, pose=po, box=box, dgrid=dgrid, cdf=tab)
+        out, ins, lf, _ = pe.all_slots(run)
+        pe.assert_slots_equal(out, lf, rec, life, i)
         assert np.array_equal(np.nonzero(ins)[0], kept['pid']) and len(kept) > 100
-        got = np.zeros(n, h.hb.DROP_DTYPE)
-        m = emu.rr_emu_traj_records(_p(one), hz, _p(po), _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db), _p(got), n)
+        got, _ = pe.records(run, H, W, ratio_db)
+        m = len(got)
         assert m == len(want[i]) > 50
-        got = got[:m]
-        for nm in h.hb.DROP_DTYPE.names:
-            if nm == 'tex_index':                                 # the draws pick one of the block of ten
-                assert np.array_equal(got[nm], want[i][nm] // 10 * 10)
-            else:
-                assert got[nm].tobytes() == want[i][nm].tobytes(), (nm, i)
+        pe.assert_records_equal(got, want[i], 'stream', i)        # the draws pick one of the block of ten
         total += m
     print('%s: %d records compared' % (name, total))
 
@@ -126,13 +86,13 @@ def test_gxx_build_equals_numpy(tmp_path, emu, name, rig):
 # ---- 2. coincident ends == the rig model -------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,rig", RIGS, ids=[n for n, _ in RIGS])
 def test_coincident_ends_give_the_rig_models_bits(name, rig):
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([30.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([30.0])})
     cam = particles.FrameCamera(opt, 0)                           # speed 30 km/h stays in the formula as a drift of the world
     box = rig.box(cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
     n = 5000
     # the same pose twice: compose hands out the start pose as the end pose, bit for bit
-    still = trajmod.Trajectory(np.array([_pose(37.0, 5.0, (1e3, 0.4, -2e3))] * 2), 10.0)
+    still = trajmod.Trajectory(np.array([cases.pose(37.0, 5.0, (1e3, 0.4, -2e3))] * 2), 10.0)
     po = still.compose(rig, cam.exposure)
     assert po['R0'].tobytes() == po['R1'].tobytes() and po['c0'].tobytes() == po['c1'].tobytes()
     big = tuple(np.maximum(still.box(rig, cam), box))
@@ -142,13 +102,13 @@ def test_coincident_ends_give_the_rig_models_bits(name, rig):
         b, lb = particles.make_rig_particles(cam, dgrid, cdf, n, 9, 5, cam.hz, view, big, cull=False, view_end=(po['R1'][0, v], po['c1'][0, v]))
         assert a.tobytes() == b.tobytes() and la.tobytes() == lb.tobytes()
     # the identity trajectory is the rig model itself: the rig's own views, the rig's own box
-    ident = trajmod.Trajectory(np.array([_pose(0.0)] * 3), 10.0)
+    ident = trajmod.Trajectory(np.array([cases.pose(0.0)] * 3), 10.0)
     assert tuple(ident.box(rig, cam)) == tuple(box)
     pi = ident.compose(rig, cam.exposure)
     for v in range(len(rig)):
         assert pi['R0'][1, v].tobytes() == rig.views[v][0].tobytes() and pi['c0'][1, v].tobytes() == rig.views[v][1].tobytes()
         a, _ = particles.rig_frame(opt, 25, 1, rig, v, seed=4, count=300)
-        o0 = _options('kitti')                                    # rig_frame(trajectory=) takes speed 0
+        o0 = cases.options('kitti')                                    # rig_frame(trajectory=) takes speed 0
         b, _ = particles.rig_frame(o0, 25, 1, rig, v, seed=4, count=300, trajectory=ident)
         c, _ = particles.rig_frame(o0, 25, 1, rig, v, seed=4, count=300)
         assert len(b) > 100 and b.tobytes() == c.tobytes() and a.tobytes() != b.tobytes()
@@ -159,13 +119,13 @@ def test_coincident_ends_give_the_rig_models_bits(name, rig):
 def test_world_positions_move_by_velocity_over_cam_hz(origin):
     """KITTI stereo on the arc (10 m/s, 20 deg/s, 10 Hz).  A slot kept by a view in frames k and k + 1 in one life: its world
     position R0^T p_cam + c0 has moved by (wind, -v, 0) / cam_hz modulo the lattice period in x and z.  The tolerance is the
-    rounding bound of the rig's own motion test -- the rig-frame state (tr._state_bounds, from tf._track_bounds' operation
-    count) plus the two recovered positions (tr._world_bound: 14 roundings of values bounded by |p|_1 + |c|_1 + 1.5 w, and 3 x
+    rounding bound of the rig's own motion test -- the rig-frame state (cases._state_bounds, from cases._track_bounds' operation
+    count) plus the two recovered positions (cases._world_bound: 14 roundings of values bounded by |p|_1 + |c|_1 + 1.5 w, and 3 x
     the orthonormality defect of the composed R0, measured on the input matrix) -- with |c| the camera's distance from the
     world's origin, which enters through |c|_1."""
-    rig = tr.KITTI_STEREO
-    traj = arc(40, origin=origin)
-    opt = _options('kitti')
+    rig = cases.KITTI_STEREO
+    traj = cases.arc(40, origin=origin)
+    opt = cases.options('kitti')
     cam = particles._traj_cam(particles.FrameCamera(opt, 0))
     box = traj.box(rig, cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
@@ -189,11 +149,11 @@ def test_world_positions_move_by_velocity_over_cam_hz(origin):
             vb = (po['R0'][k + 1, v].reshape(3, 3), po['c0'][k + 1, v])
             vel = st['vel'][ra['pid']]
             w, wy = 2.0 * st['b'][ra['pid']], 2.0 * st['by'][ra['pid']]
-            r = (tr._world(rb, vb) - tr._world(ra, va)) - vel * dt
+            r = (cases._world(rb, vb) - cases._world(ra, va)) - vel * dt
             m = np.rint(r[:, [0, 2]] / w[:, None])
             r[:, 0] -= m[:, 0] * w
             r[:, 2] -= m[:, 1] * w
-            bound = tr._state_bounds(vel, w, wy, life, dt) + (tr._world_bound(ra, va, w) + tr._world_bound(rb, vb, w))[:, None] \
+            bound = cases._state_bounds(vel, w, wy, life, dt) + (cases._world_bound(ra, va, w) + cases._world_bound(rb, vb, w))[:, None] \
                 + (2.0 * U * w * (1.0 + np.abs(m).max(axis=1)))[:, None]
             worst = max(worst, float((np.abs(r) / bound).max()))
             assert np.all(np.abs(r) <= bound), (k, v, (np.abs(r) / bound).max(axis=0))
@@ -204,11 +164,11 @@ def test_world_positions_move_by_velocity_over_cam_hz(origin):
 
 # ---- 4. the law of every frame of the arc ----------------------------------------------------------------------------------
 def _arc_sample(rig, view, seed0):
-    """tf._sample on the arc: N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own, frame i at pose i % len(ARC)."""
-    opt = _options('kitti')
+    """cases._sample on the arc: cases.N_LAW frames of KITTI at 25 mm/hr, each under a seed of its own, frame i at pose i % len(ARC)."""
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
     counts, D, depth, px, py = [], [], [], [], []
-    for i in range(tf.N_LAW):
+    for i in range(cases.N_LAW):
         rec, _ = particles.rig_frame(opt, 25, i % len(ARC), rig, view, seed=seed0 + i, trajectory=ARC)
         counts.append(len(rec))
         D.append(rec['wd1'] * 1e3)
@@ -219,17 +179,17 @@ def _arc_sample(rig, view, seed0):
 
 
 def test_every_frame_of_the_arc_has_the_iid_models_law():
-    iid_a, iid_b = tf._sample('iid', 1000), tf._sample('iid', 5000)
-    control = tf._same_law(iid_a, iid_b)
+    iid_a, iid_b = cases._sample('iid', 1000), cases._sample('iid', 5000)
+    control = cases._same_law(iid_a, iid_b)
     assert all(v < 1 for v in control.values()), control
     mean = particles.expected_count(iid_a['cam'], 25)[0]
-    for name, rig, views in (('stereo', tr.KITTI_STEREO, (0, 1)), ('mono', MONO, (0,))):
+    for name, rig, views in (('stereo', cases.KITTI_STEREO, (0, 1)), ('mono', cases.MONO, (0,))):
         for v in views:
-            s = _arc_sample(rig, v, 13000 + 1000 * v + (500 if rig is MONO else 0))
-            got, got_b = tf._same_law(s, iid_a), tf._same_law(s, iid_b)
+            s = _arc_sample(rig, v, 13000 + 1000 * v + (500 if rig is cases.MONO else 0))
+            got, got_b = cases._same_law(s, iid_a), cases._same_law(s, iid_b)
             print('%s view %d on the arc: mean count %.1f (model %.1f); statistic / threshold vs iid: %s; vs iid (other seeds): %s'
                   % (name, v, s['counts'].mean(), mean, got, got_b))
-            assert abs(s['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
+            assert abs(s['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)
             assert all(x < 1 for x in got.values()), (name, v, got)
             assert all(x < 1 for x in got_b.values()), (name, v, got_b)
 
@@ -238,9 +198,9 @@ def test_every_frame_of_the_arc_has_the_iid_models_law():
 def test_the_nearest_image_is_the_only_visible_one_over_the_arc():
     """With r from Trajectory.box every frustum of the arc lies inside the lattice cell centred on its camera.  With r 1 % smaller
     a far corner of the frustum of the pose that attains r sticks out: a lattice image other than the nearest passes the cull."""
-    rig = tr.KITTI_STEREO
-    traj = arc(24)                                                # headings 0 .. 46 degrees: r is attained where a far corner
-    opt = _options('kitti')                                       # points along an axis of the lattice
+    rig = cases.KITTI_STEREO
+    traj = cases.arc(24)                                                # headings 0 .. 46 degrees: r is attained where a far corner
+    opt = cases.options('kitti')                                       # points along an axis of the lattice
     cam = particles._traj_cam(particles.FrameCamera(opt, 0))
     box = traj.box(rig, cam)
     assert box[0] > rig.box(cam)[0]                               # the reach of all headings, not of the rig alone
@@ -278,12 +238,12 @@ def test_a_camera_yawing_in_place_displaces_streaks_horizontally(yaw_rate):
     height.  ip2.x - ip1.x = fpx (tan(theta + psi) - tan(theta)) = fpx psi (1 + tan^2 theta) + fpx psi^2 tan theta (1 + tan^2 theta)
     + O(psi^3); at the image centre (|tan theta| <= T = 0.02) it is fpx psi within fpx |psi| (2 T^2 + 2 |psi| T + psi^2): twice the
     first neglected terms."""
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     cam = particles._traj_cam(particles.FrameCamera(opt, 0))
     hz = float(cam.hz)
-    traj = trajmod.Trajectory(np.array([_pose(yaw_rate * k / hz) for k in range(3)]), hz)
+    traj = trajmod.Trajectory(np.array([cases.pose(yaw_rate * k / hz) for k in range(3)]), hz)
     psi = np.deg2rad(yaw_rate) * cam.exposure
-    rec, _ = particles.rig_frame(opt, 25, 1, MONO, 0, seed=8, count=30000, wind_sigma=0.0, trajectory=traj)
+    rec, _ = particles.rig_frame(opt, 25, 1, cases.MONO, 0, seed=8, count=30000, wind_sigma=0.0, trajectory=traj)
     T = 0.02
     tan_theta = (rec['ip1'][:, 0] - cam.W / 2.0) / cam.fpx
     sel = (np.abs(tan_theta) <= T) & (rec['wp1'][:, 2] < -0.05) & (rec['wp2'][:, 2] < -0.05)
@@ -299,7 +259,7 @@ def test_a_camera_yawing_in_place_displaces_streaks_horizontally(yaw_rate):
 # ---- 7. trajectory.py: refusals, the reader, conventions ------------------------------------------------------------------
 def test_refusals_reader_and_conventions(tmp_path):
     T = trajmod.Trajectory
-    good = np.array([_pose(0.0), _pose(2.0, 0.0, (0.0, 0.0, -1.0))])
+    good = np.array([cases.pose(0.0), cases.pose(2.0, 0.0, (0.0, 0.0, -1.0))])
     for bad, match in ((np.zeros((2, 3, 3)), 'N, 3, 4'), (np.zeros((0, 3, 4)), 'N >= 1'), ('abc', 'poses'), (np.zeros((3, 4)), 'N, 3, 4')):
         with pytest.raises(ValueError, match=match):
             T(bad, 10.0)
@@ -321,36 +281,36 @@ def test_refusals_reader_and_conventions(tmp_path):
     with pytest.raises(ValueError, match='1e\\+06 m'):
         T(b, 10.0)
     b4 = np.zeros((2, 4, 4)); b4[:, :3] = good; b4[:, 3, 3] = 1.0
-    assert T(b4, 10.0).compose(MONO, 0.002).tobytes() == T(good, 10.0).compose(MONO, 0.002).tobytes()
+    assert T(b4, 10.0).compose(cases.MONO, 0.002).tobytes() == T(good, 10.0).compose(cases.MONO, 0.002).tobytes()
     b4[1, 3, 0] = 0.5
     with pytest.raises(ValueError, match='bottom row'):
         T(b4, 10.0)
     with pytest.raises(ValueError, match='170 degrees'):
-        T(np.array([_pose(0.0), _pose(175.0)]), 10.0).compose(MONO, 0.002)
+        T(np.array([cases.pose(0.0), cases.pose(175.0)]), 10.0).compose(cases.MONO, 0.002)
     with pytest.raises(ValueError, match='exposure'):
-        T(good, 10.0).compose(MONO, -1.0)
+        T(good, 10.0).compose(cases.MONO, -1.0)
     # a composed centre beyond 1e6 m although the rig's origin is inside; a view that is no rotation is the rig's own refusal
-    far = T(np.array([_pose(0.0, 0.0, (999999.5, 0.0, 0.0))]), 10.0)
+    far = T(np.array([cases.pose(0.0, 0.0, (999999.5, 0.0, 0.0))]), 10.0)
     with pytest.raises(ValueError, match='beyond'):
         far.compose(rigmod.Rig([(np.eye(3), [1.0, 0.0, 0.0])]), 0.002)
     with pytest.raises(ValueError, match='POSE_DTYPE'):
         trajmod.check_poses(np.zeros(3))
-    po = np.array(T(good, 10.0).compose(tr.KITTI_STEREO, 0.002))
+    po = np.array(T(good, 10.0).compose(cases.KITTI_STEREO, 0.002))
     po['R1'][1, 1, 4] = np.nan
     with pytest.raises(ValueError, match=r'pose \(1, 1\), R1.*finite'):
         trajmod.check_poses(po)
-    po = np.array(T(good, 10.0).compose(tr.KITTI_STEREO, 0.002))
+    po = np.array(T(good, 10.0).compose(cases.KITTI_STEREO, 0.002))
     po['R0'][0, 1] *= 1.0 + 1e-8
     with pytest.raises(ValueError, match=r'pose \(0, 1\), R0.*orthonormal'):
         trajmod.check_poses(po)
     with pytest.raises(ValueError, match="model 'rig'"):
-        particles.sim_frames(_options('kitti'), 25, 1, model='field', trajectory=T(good, 10.0))
+        particles.sim_frames(cases.options('kitti'), 25, 1, model='field', trajectory=T(good, 10.0))
     with pytest.raises(ValueError, match="model 'rig'"):
         particles.expected_records([], None, None, None, model='iid', trajectory=T(good, 10.0))
     # a single pose stands still; the last pose extrapolates from the one before
-    one = T(good[:1], 10.0).compose(MONO, 0.002)
+    one = T(good[:1], 10.0).compose(cases.MONO, 0.002)
     assert one['R0'].tobytes() == one['R1'].tobytes() and one['c0'].tobytes() == one['c1'].tobytes()
-    two = T(good, 10.0).compose(MONO, 0.01)                       # a tenth of the way
+    two = T(good, 10.0).compose(cases.MONO, 0.01)                       # a tenth of the way
     assert np.allclose(two['c1'][0, 0], (0.0, 0.0, -0.1), atol=1e-15) and np.allclose(two['c1'][1, 0], (0.0, 0.0, -1.1), atol=1e-15)
     assert np.allclose(two['R1'][0, 0].reshape(3, 3), rigmod._rot_y(0.2).T, atol=1e-15)
     assert np.allclose(two['R1'][1, 0].reshape(3, 3), rigmod._rot_y(2.2).T, atol=1e-15)
@@ -359,7 +319,7 @@ def test_refusals_reader_and_conventions(tmp_path):
     kitti = np.zeros((2, 3, 4)); kitti[0, :, :3] = np.eye(3)
     kitti[1, :, :3] = [[np.cos(a), 0.0, -np.sin(a)], [0.0, 1.0, 0.0], [np.sin(a), 0.0, np.cos(a)]]    # heading towards -x: left
     kitti[1, :, 3] = (0.0, 0.3, 1.0)                             # one metre forward, 0.3 m DOWN
-    tk, tn = T(kitti, 10.0, 'kitti'), T(np.array([_pose(0.0), _pose(2.0, 0.0, (0.0, -0.3, -1.0))]), 10.0)
+    tk, tn = T(kitti, 10.0, 'kitti'), T(np.array([cases.pose(0.0), cases.pose(2.0, 0.0, (0.0, -0.3, -1.0))]), 10.0)
     assert np.allclose(tk.R, tn.R, atol=1e-15) and np.array_equal(tk.t, tn.t)
     # the reader: 12 numbers per line, blank lines and comments skipped, few digits re-orthonormalised
     path = os.path.join(str(tmp_path), 'poses.txt')
@@ -386,16 +346,16 @@ def test_refusals_reader_and_conventions(tmp_path):
     with pytest.raises(ValueError, match='no pose'):
         T.from_file(path)
     # levelled: the start altitude leaves both ends; the box no longer grows with the climb
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
-    hill = T(np.array([_pose(0.0, 0.0, (0.0, 3.0 * k, -1.0 * k)) for k in range(4)]), 10.0)
+    hill = T(np.array([cases.pose(0.0, 0.0, (0.0, 3.0 * k, -1.0 * k)) for k in range(4)]), 10.0)
     lv = hill.levelled()
-    ph, pl = hill.compose(MONO, cam.exposure), lv.compose(MONO, cam.exposure)
+    ph, pl = hill.compose(cases.MONO, cam.exposure), lv.compose(cases.MONO, cam.exposure)
     assert np.all(pl['c0'][:, 0, 1] == 0.0) and np.allclose(pl['c1'][:, 0, 1], 3.0 * cam.exposure * 10.0, rtol=1e-12)
     assert np.array_equal(pl['c0'][:, 0, [0, 2]], ph['c0'][:, 0, [0, 2]]) and pl['R0'].tobytes() == ph['R0'].tobytes()
-    assert hill.box(MONO, cam)[2] >= 9.0 and lv.box(MONO, cam)[2] < 0.1
+    assert hill.box(cases.MONO, cam)[2] >= 9.0 and lv.box(cases.MONO, cam)[2] < 0.1
     assert 'BETWEEN frames' in T.levelled.__doc__
-    assert len(rigmod.Rig.from_spec('mono')) == 1 and MONO.as_records().tobytes() == rigmod.Rig([(np.eye(3), [0, 0, 0])]).as_records().tobytes()
+    assert len(rigmod.Rig.from_spec('mono')) == 1 and cases.MONO.as_records().tobytes() == rigmod.Rig([(np.eye(3), [0, 0, 0])]).as_records().tobytes()
 
 
 # ---- 8. ABI ----------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """CPU tier: the mean wind of the particle generators (tools/particles.py wind=, rr_particles.h WIND, rr_set_particle_wind) -- the air's
 mean horizontal velocity (wx, wz) joins every drop's own: vx = wind_life + wx, vz = speed + wz.
 
-  1. the g++ build of the RR_HD statement (tests/hostemu/wind_emu.cpp: the code the WIND kernels run) == numpy, bit for bit: i.i.d.,
+  1. the g++ build of the RR_HD statement (tests/hostemu/particles_emu.cpp: the code the WIND kernels run) == numpy, bit for bit: i.i.d.,
      field, rig (stereo, a yaw ring) and a rig under a trajectory yawed 37 degrees and pitched; three winds, both draws, jitter 0 / 5;
   2. wind=(0, 0) gives the bytes of the functions called without the keyword, for every model;
   3. kinematics: a slot seen again in its life has moved by (vx, -v, vz) / cam_hz; every kept record's streak is (vx, -v, vz) exposure
@@ -10,7 +10,6 @@ mean horizontal velocity (wx, wz) joins every drop's own: vx = wind_life + wx, v
   5. slant: with no scatter and no ego-motion every streak leans the wind's way, by wx / v(D); a view yawed 180 degrees sees the
      opposite; under a trajectory the wind is a world vector;
   8. every refusal of the Python layer and of the driver's argument handling; RainAugment.plan carries the wind."""
-import ctypes
 import importlib
 import os
 
@@ -18,67 +17,26 @@ import numpy as np
 import pytest
 
 import helpers as h
-import test_particle_field_host as tf                     # _track_bounds / _sample / _same_law / N_LAW
-import test_particle_rig_host as tr                       # _state_bounds, the rigs
-from test_particle_draws_host import MODEL_ID, _options, _p, _run
-from test_particle_jitter_host import _same_field
-from test_particle_trajectory_host import MONO, _pose
+import particle_cases as cases
+import particle_emu as pe
 
 particles = importlib.import_module('rain-rendering_amd.tools.particles')
-rigmod = importlib.import_module('rain-rendering_amd.rig')
 trajmod = importlib.import_module('rain-rendering_amd.trajectory')
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
-
+U = cases.U
+SEED = cases.SEED
 WINDS = [(3.0, 0.0), (-7.5, 2.0), (0.0, -4.0)]
-RING3 = rigmod.Rig.yaw_ring([0, 120, -120], 0.6)          # a yaw ring
-BACK_TO_BACK = rigmod.Rig.yaw_ring([0, 180], 0.0)         # view 1 looks the other way
-SEED = 1234 + 2 ** 40
-
-
-def _traj37():
-    """Three poses of a rig yawed 37 degrees and pitched -4, far from the origin, each a little further and further turned: both
-    ends of every exposure differ."""
-    d = np.array([0.6, 0.0, -0.8]) * 1e3
-    return trajmod.Trajectory(np.array([_pose(37.0 + 2.0 * i, -4.0 + 0.5 * i, d + i * np.array([0.3, 0.02, -0.9])) for i in range(3)]), 10.0,
-                              'native')
-
-
-# (name, model, rig, trajectory): what items 1 and 2 cover
-CASES = [('iid', 'iid', None, None), ('field', 'field', None, None), ('rig-stereo', 'rig', tr.KITTI_STEREO, None),
-         ('rig-ring', 'rig', RING3, None), ('trajectory', 'rig', MONO, _traj37())]
+CASES = cases.CASES                                       # (name, model, rig, trajectory): what items 1 and 2 cover
 CASE_IDS = [c[0] for c in CASES]
 
 
 @pytest.fixture(scope='module')
 def emu(built):
-    lib = ctypes.CDLL(os.path.join(ROOT, 'tests', 'hostemu', 'libwindemu.so'))
-    V, I, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
-    lib.rr_emu_wind_particles.argtypes = [I, D, D, V, D, V, V, V, V, V, I, V, V, V]
-    lib.rr_emu_wind_records.argtypes = [I, I, D, D, D, V, D, V, V, V, V, V, I, I, I, V, V, I]
-    lib.rr_emu_wind_records.restype = I
-    return lib
+    return pe.load()
 
 
 @pytest.fixture(scope='module')
 def sdb(tmp_path_factory):
     return h.Scene(tmp_path_factory.mktemp('wind'), 64, 96, 10).db     # (only the texture ratios are used)
-
-
-def _case_run(model, rig, traj, frames, seed=SEED, speed_kmh=30.0, **opt_kw):
-    """(opt, sims, d_grid, cdf, keyword arguments of expected_records, camera, box) of the rendered frames `frames`."""
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([speed_kmh])}, **opt_kw)
-    if traj is None:
-        sims, dgrid, cdf, kw = _run(model, opt, 25, frames, seed, rig)
-    else:
-        sims, dgrid, cdf = particles.sim_frames(opt, 25, 1, seed=seed, model='rig', rig=rig, trajectory=traj)
-        sims = particles.rig_run_sims(sims, frames, len(rig))
-        kw = dict(model='rig', cam_hz=opt['cam_hz'], rig=rig, trajectory=traj)
-    cam = particles.FrameCamera(opt, 0)
-    if traj is not None:
-        cam = particles._traj_cam(cam)
-    box = np.zeros(3) if rig is None else np.array((traj.box if traj is not None else rig.box)(*((rig, cam) if traj is not None else (cam,))))
-    return opt, sims, dgrid, cdf, kw, cam, box
 
 
 def _all_particles(model, cam, dgrid, tab, s, hz, rig, traj, view, box, wind=None):
@@ -102,7 +60,7 @@ def _all_particles(model, cam, dgrid, tab, s, hz, rig, traj, view, box, wind=Non
 @pytest.mark.parametrize("name,model,rig,traj", CASES, ids=CASE_IDS)
 def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
     frames = [0, 1] if traj is not None else [3, 2 ** 31 + 5]
-    opt, sims, dgrid, cdf, kw, cam, box = _case_run(model, rig, traj, frames)
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, frames)
     hz = float(opt['cam_hz'])
     V = len(rig) if rig is not None else 1
     W, H = opt["cam_CCD_WH"]
@@ -116,33 +74,20 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
         want = {(d, j): particles.expected_records(sims, dgrid, cdf, sdb, draws=d, jitter=j, wind=wind, **kw)
                 for d in ('counter', 'stream') for j in (0.0, 5.0)}
         for i, s in enumerate(sims):
-            one = np.ascontiguousarray(sims[i:i + 1])
-            n, v = int(s['n_particles']), i % V
-            view_rec = np.ascontiguousarray(views[v:v + 1]) if views is not None and traj is None else None
-            view = _p(view_rec) if view_rec is not None else None
-            po = np.ascontiguousarray(poses[int(s['frame']), v:v + 1]) if traj is not None else None
+            v = i % V
+            view = views[v:v + 1] if views is not None and traj is None else None
+            po = poses[int(s['frame']), v:v + 1] if traj is not None else None
+            air = dict(model=model, sim=sims[i:i + 1], cam_hz=hz, view=view, pose=po, box=box, dgrid=dgrid, cdf=tab, wind=wind)
             # every particle / slot, kept or not
             rec, life = _all_particles(model, cam, dgrid, tab, s, hz, rig, traj, v, box, wind)
-            out, ins, lf = np.zeros((n, 13)), np.zeros(n, np.uint8), np.zeros(n)
-            emu.rr_emu_wind_particles(MODEL_ID[model], wind[0], wind[1], _p(one), hz, view, _p(po) if po is not None else None, _p(box),
-                                      _p(dgrid), _p(tab), len(dgrid), _p(out), _p(ins), _p(lf))
-            for nm, cols in (('wp1', slice(0, 3)), ('wp2', slice(3, 6)), ('ip1', slice(7, 9)), ('ip2', slice(9, 11))):
-                assert out[:, cols].tobytes() == np.ascontiguousarray(rec[nm]).tobytes(), (nm, i, wind)
-            assert out[:, 6].tobytes() == rec['wd1'].tobytes() and out[:, 11].tobytes() == rec['iw1'].tobytes()
-            assert out[:, 12].tobytes() == rec['iw2'].tobytes() and lf.tobytes() == np.ascontiguousarray(life).tobytes()
+            out, ins, lf, _ = pe.all_slots(pe.run(**air))
+            pe.assert_slots_equal(out, lf, rec, life, (i, wind))
             # the finished records
             for (draws, jit), recs in want.items():
-                got = np.zeros(n, h.hb.DROP_DTYPE)
-                m = emu.rr_emu_wind_records(MODEL_ID[model], int(draws == 'counter'), jit, wind[0], wind[1], _p(one), hz, view,
-                                            _p(po) if po is not None else None, _p(box), _p(dgrid), _p(tab), len(dgrid), H, W, _p(ratio_db),
-                                            _p(got), n)
-                w = recs[i]
+                got, _ = pe.records(pe.run(counter=draws == 'counter', jitter=jit, **air), H, W, ratio_db)
+                m, w = len(got), recs[i]
                 assert m == len(w) > 100, (i, wind, draws, jit, m, len(w))
-                for nm in h.hb.DROP_DTYPE.names:
-                    if nm == 'tex_index' and draws == 'stream':    # (the particle kernel leaves the block's first texture to k_particle_draws)
-                        assert np.array_equal(got[:m][nm], w[nm] // 10 * 10), (i, wind, draws, jit)
-                    else:
-                        assert _same_field(got[:m][nm], w[nm]), (i, wind, draws, jit, nm)
+                pe.assert_records_equal(got, w, draws, (i, wind, draws, jit), cases._same_field)
                 total += m
             assert want[('stream', 0.0)][i].tobytes() != plain[i].tobytes()          # the wind does something
     print('%s: %d records compared' % (name, total))
@@ -153,7 +98,7 @@ def test_gxx_build_equals_numpy(emu, sdb, name, model, rig, traj):
 @pytest.mark.parametrize("wind_sigma", [1.0, 0.0])
 def test_zero_wind_gives_the_bytes_without_the_keyword(sdb, name, model, rig, traj, wind_sigma):
     """wind_sigma = 0 is the case an added zero would change: block_wind gives -0.0 for half of the drops."""
-    opt, sims, dgrid, cdf, kw, cam, box = _case_run(model, rig, traj, [0, 1])
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, [0, 1])
     sims['wind_sigma'] = wind_sigma
     hz = float(opt['cam_hz'])
     for draws, jit in (('stream', 0.0), ('counter', 5.0)):
@@ -185,7 +130,7 @@ def test_zero_wind_gives_the_bytes_without_the_keyword(sdb, name, model, rig, tr
     if model == 'rig' and wind_sigma == 0.0:
         assert n_neg > 0                                          # the -0.0 winds are there
     if model == 'field':
-        opt2 = _options('kitti')
+        opt2 = cases.options('kitti')
         a, b = particles.generate(opt2, 25, 2, seed=3, model='field'), particles.generate(opt2, 25, 2, seed=3, model='field', wind=(0, 0))
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
         fa, fb = particles.field_frame(opt2, 25, 4, seed=3), particles.field_frame(opt2, 25, 4, seed=3, wind=(0.0, 0.0))
@@ -194,35 +139,20 @@ def test_zero_wind_gives_the_bytes_without_the_keyword(sdb, name, model, rig, tr
         kb = particles.field_kinematics(cam, dgrid, tab, fa[0]['pid'], fa[1], 3, wind=(0.0, 0.0))
         assert ka[0].tobytes() == kb[0].tobytes() and ka[1].tobytes() == kb[1].tobytes()
     if model == 'iid':
-        opt2 = _options('kitti')
+        opt2 = cases.options('kitti')
         a, b = particles.generate(opt2, 25, 2, seed=3), particles.generate(opt2, 25, 2, seed=3, wind=(0, 0))
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
     if model == 'rig':
-        opt2 = _options('kitti')
+        opt2 = cases.options('kitti')
         a = particles.rig_frame(opt2, 25, 1, rig, 0, seed=3, trajectory=traj)
         b = particles.rig_frame(opt2, 25, 1, rig, 0, seed=3, trajectory=traj, wind=(0.0, 0.0))
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
 # ---- 3. kinematics -------------------------------------------------------------------------------------------------
-def _windy_bounds(bound, vel, box, life, dt):
-    """tf._track_bounds / tr._state_bounds with the wind's one more operation.  Those bounds take `vel` as the exact velocity of the
-    formula; under a wind the formula's vx = wind_life + wx (vz = speed + wz) is itself a rounded sum, of relative error u, formed
-    with the same bits here (field_kinematics / rig_state) and in the generator -- so it IS the velocity both sides use and the
-    expected displacement carries no further error.  What changes is nothing in the operation count of the position; the bound is
-    taken with one more rounding on the wrapped axes all the same ((4 S + 5) -> (4 S + 6) in R's factor, per frame), which covers
-    a generator that would form the sum twice."""
-    S = life + 2.0
-    T = box[:, 1] / np.abs(vel[:, 1])
-    out = bound.copy()
-    for ax in (0, 2):
-        out[:, ax] += 2.0 * (np.abs(vel[:, ax]) * T / box[:, ax]) * U * box[:, ax]
-    return out
-
-
 @pytest.mark.parametrize("wind", [(6.0, -2.0), (-7.5, 2.0)])
 def test_field_tracks_move_by_the_windy_velocity(wind):
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([50.0])})
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([50.0])})
     cam = particles.FrameCamera(opt, 0)
     _, dgrid, cdf, _ = particles.expected_count(cam, 25)
     dt = 1.0 / cam.hz
@@ -242,7 +172,7 @@ def test_field_tracks_move_by_the_windy_velocity(wind):
         r = (rb['wp1'][ib] - ra['wp1'][ia]) - vel * dt
         r[:, 0] -= box[:, 0] * np.rint(r[:, 0] / box[:, 0])
         r[:, 2] -= box[:, 2] * np.rint(r[:, 2] / box[:, 2])
-        bound = _windy_bounds(tf._track_bounds(vel, box, la[ia], dt), vel, box, la[ia], dt)
+        bound = cases._windy_bounds(cases._track_bounds(vel, box, la[ia], dt), vel, box, la[ia], dt)
         print('frame %d -> %d: %d kept again, worst |residual| / bound per axis %s' % (k, k + 1, len(ia), (np.abs(r) / bound).max(axis=0)))
         assert np.all(np.abs(r) <= bound), (np.abs(r) / bound).max(axis=0)
         total += len(ia)
@@ -252,8 +182,8 @@ def test_field_tracks_move_by_the_windy_velocity(wind):
 @pytest.mark.parametrize("wind", [(6.0, -2.0), (-7.5, 2.0)])
 def test_rig_slots_move_by_the_windy_velocity(wind):
     """The rig-frame state (rig_state: what make_rig_slot makes) of every slot a stereo view keeps at k and k + 1 in one life."""
-    rig = tr.KITTI_STEREO
-    opt = _options('kitti', sim_steps={"cam_motion": np.array([50.0])})
+    rig = cases.KITTI_STEREO
+    opt = cases.options('kitti', sim_steps={"cam_motion": np.array([50.0])})
     cam = particles.FrameCamera(opt, 0)
     box = rig.box(cam)
     _, dgrid, cdf, _ = particles.rig_expected_count(cam, 25, box)
@@ -277,14 +207,14 @@ def test_rig_slots_move_by_the_windy_velocity(wind):
             r = (sb['pos'][j] - sa['pos'][j]) - vel * dt
             r[:, 0] -= w * np.rint(r[:, 0] / w)
             r[:, 2] -= w * np.rint(r[:, 2] / w)
-            bound = _windy_bounds(tr._state_bounds(vel, w, wy, sa['life'][j], dt), vel, np.stack([w, wy, w], axis=1), sa['life'][j], dt)
+            bound = cases._windy_bounds(cases._state_bounds(vel, w, wy, sa['life'][j], dt), vel, np.stack([w, wy, w], axis=1), sa['life'][j], dt)
             assert np.all(np.abs(r) <= bound), (np.abs(r) / bound).max(axis=0)
             total += len(j)
     print('%d tracks compared' % total)
     assert total >= 50, total
 
 
-@pytest.mark.parametrize("name,model,rig", [('iid', 'iid', None), ('field', 'field', None), ('rig-ring', 'rig', RING3)])
+@pytest.mark.parametrize("name,model,rig", [('iid', 'iid', None), ('field', 'field', None), ('rig-ring', 'rig', cases.RING3)])
 @pytest.mark.parametrize("wind", WINDS)
 def test_a_streak_is_the_windy_velocity_times_the_exposure(sdb, name, model, rig, wind):
     """Every kept record: wpe - wps = R (vx, -v(D), vz) exposure in the view's axes (R = 1 for the i.i.d. and field models; the record
@@ -293,7 +223,7 @@ def test_a_streak_is_the_windy_velocity_times_the_exposure(sdb, name, model, rig
     2 u (|d_j| + |vel_j e|); each of the two rotations (three products, two sums) 3 u sum_j |R_ij| |.|_j <= 3 u |.|_2 (rows of unit
     length: Cauchy-Schwarz); the test's own R (vel e) another 3 u |vel e|_2 and its subtraction u: in all at most
     10 u (|wps|_2 + |vel e|_2) per axis.  (Records nearer than 5 cm are left out: their depth is clamped.)"""
-    opt, sims, dgrid, cdf, kw, cam, box = _case_run(model, rig, None, [5])
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, None, [5])
     hz = float(opt['cam_hz'])
     tab = np.ascontiguousarray(cdf[0])
     recs = particles.expected_records(sims, dgrid, cdf, sdb, wind=wind, **kw)
@@ -331,10 +261,10 @@ def test_a_streak_is_the_windy_velocity_times_the_exposure(sdb, name, model, rig
 # ---- 4. the law ----------------------------------------------------------------------------------------------------
 def test_a_windy_field_frame_has_the_iid_models_law():
     wind = (6.0, -2.0)
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     cam = particles.FrameCamera(opt, 0)
     counts, D, depth, px, py = [], [], [], [], []
-    for i in range(tf.N_LAW):                                  # tf._sample('field', 9000) with the wind
+    for i in range(cases.N_LAW):                                  # cases._sample('field', 9000) with the wind
         rec, _ = particles.field_frame(opt, 25, 7 * i + 3, seed=9000 + i, wind=wind)
         counts.append(len(rec))
         D.append(rec['wd1'] * 1e3)
@@ -342,12 +272,12 @@ def test_a_windy_field_frame_has_the_iid_models_law():
         px.append(rec['ip1'][:, 0])
         py.append(rec['ip1'][:, 1])
     field = dict(cam=cam, counts=np.array(counts), D=np.concatenate(D), depth=np.concatenate(depth), px=np.concatenate(px), py=np.concatenate(py))
-    iid_a, iid_b = tf._sample('iid', 1000), tf._sample('iid', 5000)
-    control = tf._same_law(iid_a, iid_b)
+    iid_a, iid_b = cases._sample('iid', 1000), cases._sample('iid', 5000)
+    control = cases._same_law(iid_a, iid_b)
     assert all(v < 1 for v in control.values()), control
     mean = particles.expected_count(cam, 25)[0]
-    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / tf.N_LAW)
-    got, got_b = tf._same_law(field, iid_a), tf._same_law(field, iid_b)
+    assert abs(field['counts'].mean() - mean) < 4 * np.sqrt(mean / cases.N_LAW)
+    got, got_b = cases._same_law(field, iid_a), cases._same_law(field, iid_b)
     print('statistic / threshold -- iid vs iid: %s\n  windy field vs iid: %s\n  windy field vs iid (other seeds): %s' % (control, got, got_b))
     assert all(v < 1 for v in got.values()), got
     assert all(v < 1 for v in got_b.values()), got_b
@@ -360,7 +290,7 @@ def test_a_windy_field_frame_has_the_iid_models_law():
 # ---- 5. slant ------------------------------------------------------------------------------------------------------
 def _calm_records(sdb, model, rig, traj, wind, frames=(4,)):
     """Records with no scatter (wind_sigma 0) and no ego-motion, and per record the terminal velocity of its drop."""
-    opt, sims, dgrid, cdf, kw, cam, box = _case_run(model, rig, traj, list(frames), speed_kmh=0.0)
+    opt, sims, dgrid, cdf, kw, cam, box = cases.case_run(model, rig, traj, list(frames), speed_kmh=0.0)
     sims['wind_sigma'] = 0.0
     hz = float(opt['cam_hz'])
     recs = particles.expected_records(sims, dgrid, cdf, sdb, wind=wind, **kw)
@@ -399,7 +329,7 @@ def test_streaks_lean_the_winds_way_by_wx_over_v(sdb, model, wx):
 
 
 def test_a_view_yawed_180_degrees_sees_the_opposite_lean(sdb):
-    recs, _, _, _ = _calm_records(sdb, 'rig', BACK_TO_BACK, None, (5.0, 0.0))
+    recs, _, _, _ = _calm_records(sdb, 'rig', cases.BACK_TO_BACK, None, (5.0, 0.0))
     front, back = recs[0], recs[1]
     assert np.all(front['x1'] >= front['x0']) and np.all(back['x1'] <= back['x0'])
     assert (front['x1'] > front['x0']).sum() > 100 and (back['x1'] < back['x0']).sum() > 100
@@ -409,8 +339,8 @@ def test_under_a_trajectory_the_wind_is_a_world_vector(sdb):
     """A rig that stands yawed by 90 degrees (it looks along the world's -x): the world's wind (wx, 0) blows along the rig's own +z,
     toward the viewer -- the streak's x extent in the camera is rounding only, its depth shrinks by wx e."""
     wx = 5.0
-    traj = trajmod.Trajectory(np.array([_pose(90.0), _pose(90.0)]), 10.0, 'native')
-    recs, vs, cam, _ = _calm_records(sdb, 'rig', MONO, traj, (wx, 0.0), frames=(0,))
+    traj = trajmod.Trajectory(np.array([cases.pose(90.0), cases.pose(90.0)]), 10.0, 'native')
+    recs, vs, cam, _ = _calm_records(sdb, 'rig', cases.MONO, traj, (wx, 0.0), frames=(0,))
     rec = recs[0]
     free = rec['wps'][:, 2] > 0.05
     d = (rec['wpe'] - rec['wps'])[free]
@@ -419,14 +349,14 @@ def test_under_a_trajectory_the_wind_is_a_world_vector(sdb):
     assert np.all(np.abs(d[:, 2] + wx * cam.exposure) <= 10.0 * U * scale)
     assert np.all(np.abs(d[:, 1] + vs[0][free] * cam.exposure) <= 10.0 * U * scale + 4.0 * U * vs[0][free] * cam.exposure)
     # the same wind on the rig at rest (no trajectory) blows along the rig's x
-    rest, _, _, _ = _calm_records(sdb, 'rig', MONO, None, (wx, 0.0))
+    rest, _, _, _ = _calm_records(sdb, 'rig', cases.MONO, None, (wx, 0.0))
     d0 = rest[0]['wpe'] - rest[0]['wps']
     assert np.all(np.abs(d0[:, 0] - wx * cam.exposure) <= 10.0 * U * (np.abs(rest[0]['wps']).sum(axis=1) + 1.0)) and np.all(d0[:, 2] == 0)
 
 
 # ---- 8. refusals, the public interface -----------------------------------------------------------------------------
 def test_refusals(tmp_path, sdb):
-    opt = _options('kitti')
+    opt = cases.options('kitti')
     sims, dgrid, cdf = particles.sim_frames(opt, 25, 1)
     for bad in ((float('nan'), 0.0), (0.0, float('inf')), (100.5, 0.0), (0.0, -101.0), (1.0,), (1.0, 2.0, 3.0), 'wind', None, ('a', 'b')):
         with pytest.raises(ValueError, match='wind'):
