@@ -381,7 +381,7 @@ constexpr int PLAN_DW = (int)(sizeof(DropPlan) / 4);
 // these from the 312-byte plan both times.
 //   x: tile class (bits 0-3) | blur class (bits 4-6) | texture << 8      y: tile cost (LC_ROWS, LC_BIG_LDS) / pixels (LC_BIG)
 //   z: fused blur layout wo | ho << 16                                   w: its number of sub-tiles
-enum { LC_NONE = 0, LC_BIG_LDS = 1, LC_BIG = 2, LC_ROWS = 3, LC_ROT_INT = 4, LC_ROT = 5, LC_GEN = 6 };
+//   (the tile classes LC_*: rr_device.h tile_class)
 enum { LB_NONE = 0, LB_SMALL = 1, LB_FUSED = 2, LB_SLOW = 3 };
 __device__ inline uint4 make_list_rec(const DropPlan& p, const int32_t* tex_h, const int32_t* tex_w, const Scratch& sc);
 __global__ __launch_bounds__(128) void k_plan(const FrameDesc* frames, Dims dm, rr_camera cam, const int32_t* tex_h,
@@ -1761,78 +1761,14 @@ __global__ __launch_bounds__(256) void k_colour(const FrameDesc* frames, Dims dm
 //       2   one lane per output pixel folds s_buf top to bottom.
 //     Every fold runs in the order resizeArea_ uses, so the tile is bit-identical to
 //     raw_tile_pixel (rr_device.h, the one-thread-per-pixel definition) / the oracle.
-constexpr int TEX_LDS = 11776;      // padded texels: (h+4)*(w+4) <= TEX_LDS (a multiple of 16: load_tex_copy)
-constexpr int NW_MAX = 384;
-constexpr int TW_MAX = 64;
-constexpr int BUF_MAX = 512;
+// (TEX_LDS, NW_MAX, TW_MAX, BUF_MAX, row_geom / row_interval / tile_pitch and the route predicates tile_is_fast / tile_is_rows /
+//  tile_is_big_lds / tile_class: rr_device.h "raw-tile routes", where the host build of the tests sees them too)
 constexpr int CAN_W = 480;        // doubles of sample staging per wave
 constexpr int ROWS_S = 32;        // canvas rows whose intervals a wave works out at a time (general path)
 constexpr int ROWS_W = 16;        // canvas rows a wave stages at most
 
-// Columns rx of canvas row `ry` (un-flipped row number) whose bilinear footprint can touch
-// the texture, conservatively (+-1 texel, +-1 column): [xa, xa+n).  Samples outside are
-// exactly 0.0.  The interval length is bounded by tile_pitch() for every row.
-struct RowGeom {                    // per-drop constants of row_interval
-  double inv[2];                    // 1 / (m0*1024), 1 / (m3*1024); 0 when the axis does not depend on rx
-  double U[2];
-};
-__device__ inline RowGeom row_geom(const DropPlan& p, int sh, int sw) {
-  RowGeom g;
-  const double A[2] = {p.ma[0] * 1024.0, p.ma[3] * 1024.0};
-  for (int k = 0; k < 2; k++) g.inv[k] = fabs(A[k]) < 1e-6 ? 0.0 : 1.0 / A[k];
-  g.U[0] = (double)(sw + 1) * 1024.0;
-  g.U[1] = (double)(sh + 1) * 1024.0;
-  return g;
-}
-// X0/Y0 are the row's fixed-point terms (rot_X0 / rot_Y0)
-__device__ inline void row_interval(const DropPlan& p, const RowGeom& g, int X0, int Y0, int& xa, int& n) {
-  double lo = 0.0, hi = (double)(p.nW - 1);
-  const double C[2] = {(double)X0, (double)Y0};
-  const double L = -2048.0;
-  bool empty = false;
-  for (int k = 0; k < 2; k++) {
-    if (g.inv[k] == 0.0) {
-      if (C[k] < L - 1024.0 || C[k] > g.U[k] + 1024.0) empty = true;
-    } else {
-      double t0 = (L - C[k]) * g.inv[k], t1 = (g.U[k] - C[k]) * g.inv[k];
-      if (t0 > t1) { double t = t0; t0 = t1; t1 = t; }
-      lo = fmax(lo, floor(t0) - 2.0);
-      hi = fmin(hi, ceil(t1) + 2.0);
-    }
-  }
-  if (empty || lo > hi) { xa = 0; n = 0; return; }
-  xa = (int)lo;
-  n = (int)hi - xa + 1;
-}
-// upper bound of row_interval's n over all rows
-__device__ inline int tile_pitch(const DropPlan& p, int sh, int sw) {
-  double w = (double)p.nW;
-  const double A[2] = {fabs(p.ma[0]) * 1024.0, fabs(p.ma[3]) * 1024.0};
-  const double span[2] = {(double)(sw + 1) * 1024.0 + 2048.0, (double)(sh + 1) * 1024.0 + 2048.0};
-  for (int k = 0; k < 2; k++)
-    if (A[k] >= 1e-6) w = fmin(w, span[k] / A[k] + 8.0);
-  return (int)w;
-}
-
-// which drops take the LDS-staged rotate+area-resize path (everything else: k_tile_generic)
-// fixed-point coordinates stay inside the int32 / short range the LDS sampler assumes
-__device__ inline bool tile_coords_safe(const DropPlan& p) {
-  const double cmax = (fabs(p.ma[1]) * p.nH + fabs(p.ma[2]) + fabs(p.ma[0]) * p.nW + fabs(p.ma[4]) * p.nH + fabs(p.ma[5]) +
-                       fabs(p.ma[3]) * p.nW) * 1024.0 + 64.0;
-  return cmax < 3.0e7;
-}
-__device__ inline bool tile_is_fast(const DropPlan& p, int sh, int sw) {
-  if (!((sh + 4) * (sw + 4) <= TEX_LDS && p.kind == KIND_ROT && p.nW <= NW_MAX && p.tw <= TW_MAX && tile_coords_safe(p))) return false;
-  if (p.rs_mode == RS_AREA_FAST) return true;                      // integer ratios: per-wave sequential chains
-  const int rows_per_dy = (int)ceil(p.scale_y) + 4;          // (floor(dy1 * s) + 1) - (floor(dy0 * s) - 1) + 1 <= floor(k * s) + 4 rows per group
-  return p.rs_mode == RS_AREA && rows_per_dy <= BUF_MAX;             // wide tiles are folded in column chunks
-}
-
 // ---- k_tile_rows (round 6): a WAVE per rotate + INTER_AREA tile, lanes = canvas rows (rr_device.h "row walks") ----
 constexpr int RW_WAVES = 16;          // waves of a workgroup (one workgroup per CU: the LDS holds one texture for all of them)
-constexpr int RW_NW = 324;            // canvas columns of a tile (sh = 320, sw = 32: nW <= 321)
-constexpr int RW_BUF = 344;           // doubles of cell sums per wave
-constexpr int RW_PAIR_BYTES = 24640;  // pair texture in LDS: (320 + 3) * 38 * 2 rounded up to 16
 constexpr int RW_TEX_MAX = 1024;      // textures of a database the batch-wide list is bucketed by
 constexpr int RW_SHARE_MAX = 4096;    // (>= compute units * RW_SHARES)
 struct RowsWave {                     // wave-private LDS of k_tile_rows
@@ -1842,27 +1778,6 @@ struct RowsWave {                     // wave-private LDS of k_tile_rows
   uint16_t cfirst[64], clast[64];     // first / last canvas column of every destination cell
 };
 static_assert(sizeof(RowsWave) == 8528 && sizeof(RowsWave) % 16 == 0, "RowsWave layout (col[] is read 16 bytes at a time)");
-// estimated cost of a tile of this texture (its samples ~ the padded texture's area, plus the per-tile set-up), for the
-// split of the sorted list among the workgroups
-// estimated cost of a tile in walk iterations (passes x columns a row can touch, + the per-pass and per-tile set-up)
-__device__ inline int rows_tile_cost(const DropPlan& p, int sh, int sw) {
-  int R, NS;
-  rows_pass_shape(p.tw, RW_BUF, R, NS);
-  const int passes = (p.nH + R - 1) / R;
-  return passes * ((imin(tile_pitch(p, sh, sw), p.nW) / NS + 3) / 2 + 6) + 24;
-}
-__device__ inline bool tile_is_rows(const DropPlan& p, int sh, int sw) {
-  return p.kind == KIND_ROT && p.rs_mode == RS_AREA && p.scale_x >= 2.0 && p.nW <= RW_NW && p.tw <= 64 && p.tw >= 1 && p.th >= 1 && p.th <= 64 &&
-         pair_bytes(sh, sw) <= RW_PAIR_BYTES && tile_coords_safe(p);
-}
-// Big (bicubic warp) tiles k_tile_rows takes: the padded texture (2-texel zero border, k_pad_textures) in the LDS region of the
-// pair texture.  A tile is ONE wave's work there, 64 pixels a pass: tiles of more than BIG_ROWS_MAX_PX pixels stay with
-// k_tile_big, whose threads take a pixel each across the whole device (nuScenes at f/1.8 has Big tiles of 10^5 pixels: as a
-// single wave's 1900 passes one of them was 0.75 ms, the whole kernel's time -- r06 A/B log).
-constexpr int BIG_ROWS_MAX_PX = 8192;
-__device__ inline bool tile_is_big_lds(const DropPlan& p, int sh, int sw) {
-  return p.kind == KIND_BIG && (int64_t)(sh + 4) * (sw + 4) + 48 <= RW_PAIR_BYTES && p.tw >= 1 && p.th >= 1 && (int64_t)p.tw * p.th <= BIG_ROWS_MAX_PX && p.bw0 >= 1;
-}
 __global__ __launch_bounds__(256) void k_pair_textures(const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w,
                                                        const int64_t* tex_off, const int64_t* tex_qoff, uint8_t* pairs) {
   const int i = blockIdx.x, sh = tex_h[i], sw = tex_w[i], P = pair_pitch(sw);
@@ -2347,7 +2262,10 @@ __global__ __launch_bounds__(256) void k_tile(const FrameDesc* frames, int max_d
 //   * cell sums -> LDS (one double per row and destination column) -> the vertical fold, a lane per output pixel.
 // Every sum folds in resizeArea_'s order: the tile is bit-identical to raw_tile_pixel (the CPU tier runs the same column table
 // and walk rule against it: tests/test_tile_rows_host.py; test_raw_tile_dedup_is_invisible, test_known_answers and the oracle
-// tests on the GPU).
+// tests on the GPU).  Which tile comes here, and both sides of every limit of that choice, by hand-built drops: tests/tile_routes.py
+// with tests/test_tile_routes_host.py (the census; row_interval / tile_pitch inside the walk's emulation; big_tile lane by lane
+// against warp_big_pixel) and tests/test_gpu_tile_routes.py (every route and share count against the oracle, the list shapes
+// -- no rows tile, one, three, forty in one bucket, only Big tiles, empty frames -- against the frames alone, k_dedup's counts).
 // The batch-wide list cut into n_shares pieces of equal estimated cost: bounds[q] = first tile of share q (k_tile_rows'
 // workgroups take shares off a counter).  Buckets are weighted by the summed cost of their tiles (k_lists), a bucket's
 // tiles count at their average.  One workgroup.
@@ -2798,13 +2716,11 @@ __device__ inline int blur_subtiles(const DropPlan& p, const BlurLayout& L) {
 __device__ inline uint4 make_list_rec(const DropPlan& p, const int32_t* tex_h, const int32_t* tex_w, const Scratch& sc) {
   if (p.status != RR_DROP_OK) return make_uint4(0u, 0u, 0u, 0u);
   const int sh = tex_h[p.tex], sw = tex_w[p.tex];
-  uint32_t cls, cost = 0u, bcls = LB_NONE, bwh = 0u, bns = 0u;
-  if (p.kind == KIND_BIG) {
-    if (sc.big_on && tile_is_big_lds(p, sh, sw)) { cls = LC_BIG_LDS; cost = (uint32_t)(RR_BIG_COST * ((p.tw * p.th + 63) / 64) + 4); }
-    else { cls = LC_BIG; cost = (uint32_t)(p.tw * p.th); }
-  } else if (sc.rows_on && p.kind != KIND_EXT && tile_is_rows(p, sh, sw)) { cls = LC_ROWS; cost = (uint32_t)rows_tile_cost(p, sh, sw); }
-  else if (p.kind != KIND_EXT && tile_is_fast(p, sh, sw)) cls = p.rs_mode == RS_AREA_FAST ? LC_ROT_INT : LC_ROT;
-  else cls = LC_GEN;
+  const uint32_t cls = (uint32_t)tile_class(p, sh, sw, sc.rows_on != 0, sc.big_on != 0);
+  uint32_t cost = 0u, bcls = LB_NONE, bwh = 0u, bns = 0u;
+  if (cls == LC_BIG_LDS) cost = (uint32_t)(RR_BIG_COST * ((p.tw * p.th + 63) / 64) + 4);
+  else if (cls == LC_BIG) cost = (uint32_t)(p.tw * p.th);
+  else if (cls == LC_ROWS) cost = (uint32_t)rows_tile_cost(p, sh, sw);
   if (p.r1 > 0) {
     if (blur_is_small(p)) bcls = LB_SMALL;
     else {

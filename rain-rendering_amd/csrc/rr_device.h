@@ -551,6 +551,110 @@ RR_HD int pair_pitch(int sw) { int q = sw + 4; while ((q & 3) != 2) q++; return 
 RR_HD int64_t pair_bytes(int sh, int sw) { return ((int64_t)(sh + 3) * pair_pitch(sw) * 2 + 15) & ~15LL; }
 
 // ---------------------------------------------------------------------------
+// raw-tile routes: which kernel of rainhip.hip renders a drop's raw tile (make_list_rec / k_lists), and the column
+// intervals k_tile / k_tile_rows walk.  Here, not in rainhip.hip, so that the host build of the tests classifies a drop
+// the way the library does (tests/tile_routes.py).
+// ---------------------------------------------------------------------------
+constexpr int TEX_LDS = 11776;      // padded texels: (h+4)*(w+4) <= TEX_LDS (a multiple of 16: load_tex_copy)
+constexpr int NW_MAX = 384;
+constexpr int TW_MAX = 64;
+constexpr int BUF_MAX = 512;
+
+// Columns rx of canvas row `ry` (un-flipped row number) whose bilinear footprint can touch
+// the texture, conservatively (+-1 texel, +-1 column): [xa, xa+n).  Samples outside are
+// exactly 0.0.  The interval length is bounded by tile_pitch() for every row.
+struct RowGeom {                    // per-drop constants of row_interval
+  double inv[2];                    // 1 / (m0*1024), 1 / (m3*1024); 0 when the axis does not depend on rx
+  double U[2];
+};
+RR_HD RowGeom row_geom(const DropPlan& p, int sh, int sw) {
+  RowGeom g;
+  const double A[2] = {p.ma[0] * 1024.0, p.ma[3] * 1024.0};
+  for (int k = 0; k < 2; k++) g.inv[k] = fabs(A[k]) < 1e-6 ? 0.0 : 1.0 / A[k];
+  g.U[0] = (double)(sw + 1) * 1024.0;
+  g.U[1] = (double)(sh + 1) * 1024.0;
+  return g;
+}
+// X0/Y0 are the row's fixed-point terms (rot_X0 / rot_Y0)
+RR_HD void row_interval(const DropPlan& p, const RowGeom& g, int X0, int Y0, int& xa, int& n) {
+  double lo = 0.0, hi = (double)(p.nW - 1);
+  const double C[2] = {(double)X0, (double)Y0};
+  const double L = -2048.0;
+  bool empty = false;
+  for (int k = 0; k < 2; k++) {
+    if (g.inv[k] == 0.0) {
+      if (C[k] < L - 1024.0 || C[k] > g.U[k] + 1024.0) empty = true;
+    } else {
+      double t0 = (L - C[k]) * g.inv[k], t1 = (g.U[k] - C[k]) * g.inv[k];
+      if (t0 > t1) { double t = t0; t0 = t1; t1 = t; }
+      lo = fmax(lo, floor(t0) - 2.0);
+      hi = fmin(hi, ceil(t1) + 2.0);
+    }
+  }
+  if (empty || lo > hi) { xa = 0; n = 0; return; }
+  xa = (int)lo;
+  n = (int)hi - xa + 1;
+}
+// upper bound of row_interval's n over all rows
+RR_HD int tile_pitch(const DropPlan& p, int sh, int sw) {
+  double w = (double)p.nW;
+  const double A[2] = {fabs(p.ma[0]) * 1024.0, fabs(p.ma[3]) * 1024.0};
+  const double span[2] = {(double)(sw + 1) * 1024.0 + 2048.0, (double)(sh + 1) * 1024.0 + 2048.0};
+  for (int k = 0; k < 2; k++)
+    if (A[k] >= 1e-6) w = fmin(w, span[k] / A[k] + 8.0);
+  return (int)w;
+}
+
+// which drops take the LDS-staged rotate+area-resize path (everything else: k_tile_generic)
+// fixed-point coordinates stay inside the int32 / short range the LDS sampler assumes
+RR_HD bool tile_coords_safe(const DropPlan& p) {
+  const double cmax = (fabs(p.ma[1]) * p.nH + fabs(p.ma[2]) + fabs(p.ma[0]) * p.nW + fabs(p.ma[4]) * p.nH + fabs(p.ma[5]) +
+                       fabs(p.ma[3]) * p.nW) * 1024.0 + 64.0;
+  return cmax < 3.0e7;
+}
+RR_HD bool tile_is_fast(const DropPlan& p, int sh, int sw) {
+  if (!((sh + 4) * (sw + 4) <= TEX_LDS && p.kind == KIND_ROT && p.nW <= NW_MAX && p.tw <= TW_MAX && tile_coords_safe(p))) return false;
+  if (p.rs_mode == RS_AREA_FAST) return true;                      // integer ratios: per-wave sequential chains
+  const int rows_per_dy = (int)ceil(p.scale_y) + 4;          // (floor(dy1 * s) + 1) - (floor(dy0 * s) - 1) + 1 <= floor(k * s) + 4 rows per group
+  return p.rs_mode == RS_AREA && rows_per_dy <= BUF_MAX;             // wide tiles are folded in column chunks
+}
+
+// k_tile_rows: a WAVE per rotate + INTER_AREA tile, lanes = canvas rows ("row walks" above)
+constexpr int RW_NW = 324;            // canvas columns of a tile (sh = 320, sw = 32: nW <= 321)
+constexpr int RW_BUF = 344;           // doubles of cell sums per wave
+constexpr int RW_PAIR_BYTES = 24640;  // pair texture in LDS: (320 + 3) * 38 * 2 rounded up to 16
+// estimated cost of a tile in walk iterations (passes x columns a row can touch, + the per-pass and per-tile set-up), for the
+// split of the sorted list among the workgroups
+RR_HD int rows_tile_cost(const DropPlan& p, int sh, int sw) {
+  int R, NS;
+  rows_pass_shape(p.tw, RW_BUF, R, NS);
+  const int passes = (p.nH + R - 1) / R;
+  return passes * ((imin(tile_pitch(p, sh, sw), p.nW) / NS + 3) / 2 + 6) + 24;
+}
+RR_HD bool tile_is_rows(const DropPlan& p, int sh, int sw) {
+  return p.kind == KIND_ROT && p.rs_mode == RS_AREA && p.scale_x >= 2.0 && p.nW <= RW_NW && p.tw <= 64 && p.tw >= 1 && p.th >= 1 && p.th <= 64 &&
+         pair_bytes(sh, sw) <= RW_PAIR_BYTES && tile_coords_safe(p);
+}
+// Big (bicubic warp) tiles k_tile_rows takes: the padded texture (2-texel zero border, k_pad_textures) in the LDS region of the
+// pair texture.  A tile is ONE wave's work there, 64 pixels a pass: tiles of more than BIG_ROWS_MAX_PX pixels stay with
+// k_tile_big, whose threads take a pixel each across the whole device (nuScenes at f/1.8 has Big tiles of 10^5 pixels: as a
+// single wave's 1900 passes one of them was 0.75 ms, the whole kernel's time -- r06 A/B log).
+constexpr int BIG_ROWS_MAX_PX = 8192;
+RR_HD bool tile_is_big_lds(const DropPlan& p, int sh, int sw) {
+  return p.kind == KIND_BIG && (int64_t)(sh + 4) * (sw + 4) + 48 <= RW_PAIR_BYTES && p.tw >= 1 && p.th >= 1 && (int64_t)p.tw * p.th <= BIG_ROWS_MAX_PX && p.bw0 >= 1;
+}
+// The kernel that renders the raw tile of a drop with status RR_DROP_OK whose texture is sh x sw (rows_on / big_on: RR_OPT_TILE_ROWS
+// >= 1 / 2 and a database small enough for the bucketed list): LC_ROWS and LC_BIG_LDS k_tile_rows, LC_ROT_INT and LC_ROT k_tile,
+// LC_GEN k_tile_generic, LC_BIG k_tile_big.
+enum { LC_NONE = 0, LC_BIG_LDS = 1, LC_BIG = 2, LC_ROWS = 3, LC_ROT_INT = 4, LC_ROT = 5, LC_GEN = 6 };
+RR_HD int tile_class(const DropPlan& p, int sh, int sw, bool rows_on, bool big_on) {
+  if (p.kind == KIND_BIG) return big_on && tile_is_big_lds(p, sh, sw) ? LC_BIG_LDS : LC_BIG;
+  if (rows_on && p.kind != KIND_EXT && tile_is_rows(p, sh, sw)) return LC_ROWS;
+  if (p.kind != KIND_EXT && tile_is_fast(p, sh, sw)) return p.rs_mode == RS_AREA_FAST ? LC_ROT_INT : LC_ROT;
+  return LC_GEN;
+}
+
+// ---------------------------------------------------------------------------
 // field-of-view polygon   (bad_weather.py:596-704)
 // ---------------------------------------------------------------------------
 RR_HD void rotmat(const double a[3], double c, double s, double R[9]) {   // bad_weather.py:532-538

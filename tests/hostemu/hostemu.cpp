@@ -185,8 +185,17 @@ int emu_tile(const DropPlan* p, const uint8_t* texels, const int32_t* tex_h, con
 // from a pair texture as the kernel; the lanes of a wave run one after the other.
 // out[th*tw] = the raw tile; also out_def[th*tw] = raw_tile_pixel (the definition).  Returns the number of pixels that
 // differ in any bit, or -1 when the plan is not one k_tile_rows takes.
+// emu_tile_rows_mode: interval 0 = the brute-force interval with ragged margins (above); 1 = the kernel's own row_interval
+// (rr_device.h), with two more return codes: -7 a column outside [xa, xa + n) has a non-zero sample (the kernel would drop
+// it), -8 n > tile_pitch (the bound rows_tile_cost and k_tile's staging rest on).
+int emu_tile_rows_mode(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off, int buf,
+                       double* out, double* out_def, int interval);
 int emu_tile_rows(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off, int buf,
                   double* out, double* out_def) {
+  return emu_tile_rows_mode(pp, texels, tex_h, tex_w, tex_off, buf, out, out_def, 0);
+}
+int emu_tile_rows_mode(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off, int buf,
+                       double* out, double* out_def, int interval) {
   const DropPlan& p = *pp;
   const int sh = tex_h[p.tex], sw = tex_w[p.tex];
   if (!(p.kind == KIND_ROT && p.rs_mode == RS_AREA && p.scale_x >= 2.0 && p.tw >= 1 && p.tw <= 64 && p.th >= 1)) return -1;
@@ -227,6 +236,8 @@ int emu_tile_rows(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_
   rows_pass_shape(tw, buf, R, NS);
   if ((R + 1) * tw > buf || R * NS > 64) return -2;
   const int colA = cfirst[0], colB = clast[tw - 1];
+  const RowGeom geom = row_geom(p, sh, sw);
+  const int pitch_bound = tile_pitch(p, sh, sw);
   double* const carry = B.data() + R * tw;
   for (int R0 = 0; R0 < nH; R0 += R) {
     const int R1 = imin(R0 + R, nH) - 1, nrows = R1 - R0 + 1;
@@ -241,8 +252,17 @@ int emu_tile_rows(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_
       int xa = nW, xe = -1;
       for (int x = 0; x < nW; x++)
         if (sample(X0 + col[x].ad, Y0 + col[x].bd) != 0.0) { xa = imin(xa, x); xe = imax(xe, x); }
-      xa = imax(xa - (c % 3), 0);                     // ragged margins: a walk may start and end anywhere outside the non-zero run
-      xe = imin(xe + (c % 2), nW - 1);
+      if (interval == 1) {                            // the kernel's interval: a superset of the non-zero run, no longer than the pitch
+        int ka, kn;
+        row_interval(p, geom, X0, Y0, ka, kn);
+        if (xe >= 0 && (kn <= 0 || xa < ka || xe > ka + kn - 1)) return -7;
+        if (kn > pitch_bound) return -8;
+        xa = ka;
+        xe = ka + kn - 1;
+      } else {
+        xa = imax(xa - (c % 3), 0);                   // ragged margins: a walk may start and end anywhere outside the non-zero run
+        xe = imin(xe + (c % 2), nW - 1);
+      }
       const int xs0 = imax(xa, colA), xe0 = imin(xe, colB);
       if (xs0 > xe0) continue;
       const int dlo = cell[xs0], dhi = imin(cell[xe0] + 1, tw - 1);
@@ -311,6 +331,187 @@ int emu_tile_rows(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_
     for (int x = 0; x < tw; x++) {
       out_def[y * tw + x] = raw_tile_pixel(p, tx, ctab, x, y);
       if (memcmp(&out_def[y * tw + x], &out[y * tw + x], 8) != 0) bad++;
+    }
+  return bad;
+}
+
+// row_interval / tile_pitch (rr_device.h) alone, for every canvas row of a rotate plan whatever kernel takes it (k_tile walks the
+// same intervals): 0, or -7 / -8 as emu_tile_rows_mode, or -1 when the plan is no rotate plan.  The samples are rot_sample's, the
+// definition's.
+int emu_row_interval_check(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off) {
+  const DropPlan& p = *pp;
+  if (p.kind != KIND_ROT || p.status != RR_DROP_OK) return -1;
+  const int sh = tex_h[p.tex], sw = tex_w[p.tex];
+  TexGlobal tx{texels + tex_off[p.tex], sh, sw};
+  const RowGeom geom = row_geom(p, sh, sw);
+  const int pitch_bound = tile_pitch(p, sh, sw);
+  for (int ry = 0; ry < p.nH; ry++) {
+    const int64_t X0 = rot_X0(p, ry), Y0 = rot_Y0(p, ry);
+    int xa = p.nW, xe = -1, ka, kn;
+    for (int x = 0; x < p.nW; x++)
+      if (rot_sample(tx, X0, Y0, rot_adelta(p, x), rot_bdelta(p, x)) != 0.0) { xa = imin(xa, x); xe = imax(xe, x); }
+    row_interval(p, geom, (int)X0, (int)Y0, ka, kn);
+    if (xe >= 0 && (kn <= 0 || xa < ka || xe > ka + kn - 1)) return -7;
+    if (kn > pitch_bound) return -8;
+  }
+  return 0;
+}
+
+// The kernel that takes each plan's raw tile (rr_device.h tile_class, what make_list_rec records): out[i] = LC_*, LC_NONE (0) for a
+// drop with a status.
+int emu_tile_class(const DropPlan* plans, int n, const int32_t* tex_h, const int32_t* tex_w, int rows_on, int big_on, int32_t* out) {
+  for (int i = 0; i < n; i++) {
+    const DropPlan& p = plans[i];
+    out[i] = p.status != RR_DROP_OK ? (int32_t)LC_NONE : (int32_t)tile_class(p, tex_h[p.tex], tex_w[p.tex], rows_on != 0, big_on != 0);
+  }
+  return 0;
+}
+
+// The limits the routes are decided on: out = {TEX_LDS, NW_MAX, TW_MAX, BUF_MAX, RW_NW, RW_BUF, RW_PAIR_BYTES, BIG_ROWS_MAX_PX}.
+void emu_tile_limits(int32_t* out) {
+  const int v[8] = {TEX_LDS, NW_MAX, TW_MAX, BUF_MAX, RW_NW, RW_BUF, RW_PAIR_BYTES, BIG_ROWS_MAX_PX};
+  for (int k = 0; k < 8; k++) out[k] = v[k];
+}
+
+// What tests/tile_routes.py flags a plan with.  A rotate plan: out[0..3] = k_tile_rows' pass shape R, S (rows_pass_shape with
+// RW_BUF), its number of passes, and whether some destination row's canvas rows lie in two passes (the carry).  A Big plan:
+// out[4] = the sides of the texture some pixel's 4 x 4 window crosses while it still holds texels (1 left, 2 right, 4 top, 8 bottom).
+int emu_tile_flags(const DropPlan* pp, const int32_t* tex_h, const int32_t* tex_w, int32_t* out) {
+  const DropPlan& p = *pp;
+  for (int k = 0; k < 5; k++) out[k] = 0;
+  if (p.status != RR_DROP_OK) return -1;
+  const int sh = tex_h[p.tex], sw = tex_w[p.tex];
+  if (p.kind == KIND_ROT && p.tw >= 1 && p.nH >= 1) {
+    int R, NS;
+    rows_pass_shape(p.tw, RW_BUF, R, NS);
+    out[0] = R; out[1] = NS; out[2] = (p.nH + R - 1) / R;
+    for (int dy = 0; dy < p.th; dy++) {
+      int fr, lr;
+      vfold_rows(area_span(p.nH, p.scale_y, dy), fr, lr);
+      if (fr / R != lr / R) out[3] = 1;
+    }
+  } else if (p.kind == KIND_BIG && p.bw0 >= 1) {
+    for (int y = 0; y < p.th; y++)
+      for (int x = 0; x < p.tw; x++) {
+        const BigCoord c = warp_big_coord(p, (x / p.bw0) * p.bw0, x, y);
+        const bool xin = c.sx + 3 >= 0 && c.sx <= sw - 1, yin = c.sy + 3 >= 0 && c.sy <= sh - 1;
+        if (!xin || !yin) continue;
+        if (c.sx < 0) out[4] |= 1;
+        if (c.sx + 3 > sw - 1) out[4] |= 2;
+        if (c.sy < 0) out[4] |= 4;
+        if (c.sy + 3 > sh - 1) out[4] |= 8;
+      }
+  }
+  return 0;
+}
+
+// ---- the Big path of k_tile_rows (big_tile, rainhip.hip), lane by lane ----
+// The texture as the kernel stages it: BIG_LDS_LEAD zero bytes, then n16 * 16 bytes of the database's padded copies from this
+// texture's offset on (rr_set_streak_db: every copy with its 2-texel zero border, pitch sw + 4, rounded up to 16 bytes, 16 zero
+// bytes behind the last), poison (0xA5) after that.  Restated from the kernel: the clamps of the window's column to [-4, sw] and
+// of its rows to [-2, sh + 1], the two aligned dwords around the four taps and the funnel shift, div_by_f (a float multiply with
+// an exact fix-up), the (x, y) of a lane's next pixel by steps of 64, the row-by-row / tap-by-tap sums.
+// out[th*tw] = the tile, out_def[th*tw] = warp_big_pixel (the definition).  Returns the number of pixels that differ in any bit;
+// -1 when the plan is not one big_tile takes, -2 when a byte that reaches a result lies outside the staged bytes, -3 when a
+// lane's incremental (x, y) is not its pixel's.
+static int emu_div_by_f(int n, int d, float inv_d) {
+  int q = (int)((float)n * inv_d);
+  const int r = n - q * d;
+  q += (r >= d) ? 1 : 0;
+  q -= (r < 0) ? 1 : 0;
+  return q;
+}
+int emu_big_lds(const DropPlan* pp, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off, int n_tex,
+                double* out, double* out_def) {
+  const DropPlan& p = *pp;
+  if (p.status != RR_DROP_OK || p.tex < 0 || p.tex >= n_tex) return -1;
+  const int sh = tex_h[p.tex], sw = tex_w[p.tex];
+  if (!tile_is_big_lds(p, sh, sw)) return -1;
+  constexpr int LEAD = 16;
+  // the database's padded copies (set_db_meta + k_pad_textures)
+  std::vector<int64_t> poff((size_t)n_tex);
+  int64_t total = 0;
+  for (int i = 0; i < n_tex; i++) {
+    poff[(size_t)i] = total;
+    total += (((int64_t)tex_h[i] + 4) * ((int64_t)tex_w[i] + 4) + 15) & ~15LL;
+  }
+  std::vector<uint8_t> pad((size_t)total + 16, 0);
+  for (int i = 0; i < n_tex; i++) {
+    const int h = tex_h[i], w = tex_w[i], P = w + 4;
+    const uint8_t* g = texels + tex_off[i];
+    for (int k = 0; k < (h + 4) * P; k++) {
+      const int y = k / P - 2, x = k - (y + 2) * P - 2;
+      pad[(size_t)(poff[(size_t)i] + k)] = (y >= 0 && y < h && x >= 0 && x < w) ? g[y * w + x] : (uint8_t)0;
+    }
+  }
+  const int n16 = ((sh + 4) * (sw + 4) + 2 + 15) >> 4;
+  const int staged = LEAD + n16 * 16;
+  if (staged > RW_PAIR_BYTES || poff[(size_t)p.tex] + (int64_t)n16 * 16 > total + 16) return -2;
+  std::vector<uint8_t> S((size_t)RW_PAIR_BYTES + 8, 0xA5);
+  memset(S.data(), 0, LEAD);
+  memcpy(S.data() + LEAD, pad.data() + poff[(size_t)p.tex], (size_t)n16 * 16);
+  float ctab[128];
+  build_cubic_tab(ctab);
+  double lut[256];
+  for (int k = 0; k < 256; k++) lut[k] = (double)k / 255.0;
+  auto med3 = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+  const int tw = p.tw, n = tw * p.th, bw0 = p.bw0, P = sw + 4;
+  const float inv_bw = 1.0f / (float)bw0;
+  const int tex00 = LEAD + 2 * P + 2;
+  const int width1 = imax(sw - 3, 0), height1 = imax(sh - 3, 0);
+  const int dq = 64 / tw, dr = 64 - dq * tw;
+  for (int lane = 0; lane < 64; lane++) {
+    int y = emu_div_by_f(lane, tw, 1.0f / (float)tw), x = lane - y * tw;
+    for (int it0 = 0; it0 < n; it0 += 64) {
+      const int it = it0 + lane;
+      if (it < n && (x < 0 || x >= tw || y * tw + x != it)) return -3;
+      const int bx = tw <= bw0 ? 0 : emu_div_by_f(x, bw0, inv_bw) * bw0;
+      const BigCoord c = warp_big_coord(p, bx, x, y);
+      x += dr;
+      y += dq;
+      if (x >= tw) { x -= tw; y += 1; }
+      if (it >= n) continue;                          // (the kernel's lanes past the end run on and store nothing)
+      const int col = tex00 + med3(c.sx, -4, sw);
+      uint32_t u[4];
+      for (int i = 0; i < 4; i++) {
+        const int a = col + med3(c.sy + i, -2, sh + 1) * P;
+        if (a < 0 || a + 4 > staged) return -2;
+        const int q = a & ~3;
+        uint32_t lo, hi;
+        memcpy(&lo, S.data() + q, 4);
+        memcpy(&hi, S.data() + q + 4, 4);
+        const uint32_t sft = (uint32_t)(a & 3) * 8u;
+        u[i] = (uint32_t)(((((uint64_t)hi) << 32) | (uint64_t)lo) >> sft);     // v_alignbit_b32
+      }
+      const float* cx = ctab + c.fx * 4;
+      const float* cy = ctab + c.fy * 4;
+      double pr[4][4];
+      for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+          const float w = cy[i] * cx[j];
+          pr[i][j] = lut[(u[i] >> (8 * j)) & 0xffu] * (double)w;
+        }
+      const bool interior = c.sx >= 0 && c.sx < width1 && c.sy >= 0 && c.sy < height1;
+      double sum = 0.0;
+      if (interior) {
+        for (int i = 0; i < 4; i++) {
+          double r = (pr[i][0] + pr[i][1]) + pr[i][2];
+          r = r + pr[i][3];
+          sum = (i == 0) ? r : sum + r;
+        }
+      } else {
+        for (int i = 0; i < 4; i++)
+          for (int j = 0; j < 4; j++) sum = sum + pr[i][j];
+      }
+      out[it] = clip01(sum);
+    }
+  }
+  TexGlobal tx{texels + tex_off[p.tex], sh, sw};
+  int bad = 0;
+  for (int yy = 0; yy < p.th; yy++)
+    for (int xx = 0; xx < tw; xx++) {
+      out_def[yy * tw + xx] = warp_big_pixel(p, tx, ctab, xx, yy);
+      if (memcmp(&out_def[yy * tw + xx], &out[yy * tw + xx], 8) != 0) bad++;
     }
   return bad;
 }
