@@ -633,7 +633,7 @@ int emu_render_frame(int H, int W, int He, int We, const double* bg, const doubl
 }
 
 // Pre-pass of one frame (fog + environment map) with the per-pixel bodies of rr_prepass.h.
-// rainy: H*W*3, env_xyY: H*We*3, env_u8: H*We*3 (We = cw + 2*(cw/2)); returns We or < 0.
+// rainy: H*W*3, env_xyY: H*We*3, env_u8: H*We*3 (We = cw + 2*(cw/2)); returns We or < 0.  cw == 0: the fog layer alone.
 // types: rrpre::PRE_* bits (element types of bg / rainy / env_xyY).  tiled: 0 = the three-kernel fog layer (k_fog_ext,
 // k_fog_h, k_fog_v), 1 = FogTile<12> the way k_fog_tile drives it (column strips x segments of seg_rows rows, 256 thread
 // roles per step, "barriers" = the ends of the loops over tid).
@@ -647,17 +647,18 @@ int emu_prepass(int H, int W, const void* bg, const void* depth, int depth_f64, 
   kn.env_k = env_k;
   for (int i = 0; i < fog_k; i++) kn.fog_w[i] = fog_w[i];
   for (int i = 0; i < env_k; i++) kn.env_w[i] = env_w[i];
+  const bool want_env = cw > 0;         // cw == 0: the fog layer alone (a frame too narrow for the map's geometry), returns 0
   std::vector<int32_t> src((size_t)H * cw), top(cw), bot(cw);
-  if (!build_env_tables(H, W, cw, n_uniq, uniq, first, src.data(), top.data(), bot.data())) return -1;
+  if (want_env && !build_env_tables(H, W, cw, n_uniq, uniq, first, src.data(), top.data(), bot.data())) return -1;
   std::vector<uint8_t> need((size_t)H * (cw + 2 * (cw / 2)));
-  build_env_need(H, cw, env_k / 2, src.data(), need.data());
+  if (want_env) build_env_need(H, cw, env_k / 2, src.data(), need.data());
   EnvGeom g{H, W, cw, cw / 2, cw + 2 * (cw / 2), src.data(), top.data(), bot.data(), tiled ? need.data() : nullptr};
   const size_t px = (size_t)H * W, ex = (size_t)H * g.We;
   std::vector<double> fext(px), tmpF(px), tmpL(px * 3), mean(3), etmp(ex * 3, -1.0e300);     // (a sum read without having been made would show)
   std::vector<uint32_t> epack(ex);
   std::vector<uint8_t> r8(px * 3);
   PreScratch sc{fext.data(), tmpF.data(), tmpL.data(), r8.data(), nullptr, mean.data(), epack.data(), etmp.data()};
-  PreFrame F{bg, depth, rainy, env_xyY, env_u8, r8.data(), beta_ext, beta_hg, irr_num, irr_den, depth_f64, types};
+  PreFrame F{bg, depth, rainy, env_xyY, env_u8, want_env ? r8.data() : nullptr, beta_ext, beta_hg, irr_num, irr_den, depth_f64, types};
   for (int c = 0; c < 3; c++) {         // k_fog_sum / k_fog_mean (sum order differs from the device's tree: ~1e-16)
     double s = 0;
     for (size_t p = 0; p < px; p++) s += (irr_num * load_unit(bg, types, (int64_t)(p * 3 + c))) / irr_den;
@@ -705,6 +706,7 @@ int emu_prepass(int H, int W, const void* bg, const void* depth, int depth_f64, 
     for (int y = 0; y < H; y++)
       for (int x = 0; x < W; x++) fog_v_px(F, 0, H, W, kn, sc, y, x);
   }
+  if (!want_env) return 0;
   for (int r = 0; r < H; r++)
     for (int x = 0; x < g.We; x++) env_build_px(F, 0, g, sc, r, x);
   for (int r = 0; r < H; r++)
@@ -844,10 +846,26 @@ int emu_generate_drops(const rr_sim_frame* sf, int H, int W, const double* dgrid
 }
 
 
+}  // extern "C"
+
+// What emu_pngz_trace reports of one block (tests/pngz_cases.py PNGZ_TRACE_DTYPE mirrors it): where a case of the catalogue landed.
+struct PngzTrace {
+  int32_t stored, bytes, len, nlit;
+  int32_t max_len;                   // the longest code length assigned (p6_assign)
+  int32_t kraft_changed;             // kraft_fix changed the counts per length
+  int32_t depth;                     // the deepest leaf of the unrestricted tree (before p4_depth's clamp)
+  int32_t cut_chunk, cut_eighth, cut_block;      // sequences of equal bytes that go on behind a chunk's / an eighth's / the block's end
+  int32_t chunks[8];                 // per wave: the chunks it walks
+  int32_t seqs[65];                  // sequences of equal bytes inside a chunk, by length
+  int32_t pad_;
+  int32_t runs[64][64];              // run tokens by [the lane that emits it][its length]
+};
+
 // The device's PNG entropy coder (rr_deflate.h: k_pngz_blocks + k_pngz_pack) on the host, thread roles in loops.  rows: n bytes of
 // filtered scanlines; dst: n bytes.  Returns the length of the zlib stream that now lies behind the 16-byte header in dst, or 0
 // if header + stream do not fit n bytes (dst is then a copy of rows, as the device leaves the scanlines in place).
-int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) {
+// trace: null, or one record per block.
+static int64_t pngz_run(const uint8_t* rows, int64_t n, uint8_t* dst, PngzTrace* trace) {
   using namespace rrz;
   const int nb = (int)blocks_of(n);
   std::vector<BlockMeta> meta(nb);
@@ -883,7 +901,24 @@ int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) {
       for (int c = 0; c < chunks_of(wave); c++) {
         chunk(wave, c, tok, bs, idx, valid);
         for (int lane = 0; lane < 64; lane++) p1_lane(S, wave, tok[lane], bs[lane], len - idx[lane], valid[lane], s1[lane], s2[lane]);
+        if (trace) {
+          PngzTrace& T = trace[k];
+          for (int lane = 0, j0 = 0; lane < 64 && valid[lane]; lane++) {
+            if (tok[lane].kind == 2) T.runs[lane][tok[lane].v]++;
+            const bool ends = lane == 63 || !valid[lane + 1] || bs[lane + 1] != bs[lane];
+            if (!ends) continue;
+            T.seqs[lane + 1 - j0]++;
+            j0 = lane + 1;
+            const int64_t at = (int64_t)k * BLOCK + idx[lane];              // the sequence's last byte, in the file
+            if (at + 1 < n && rows[at + 1] == rows[at]) {
+              if (idx[lane] + 1 == len) T.cut_block++;
+              else if ((idx[lane] + 1) % WAVE_BYTES == 0) T.cut_eighth++;
+              else if (lane == 63) T.cut_chunk++;
+            }
+          }
+        }
       }
+      if (trace) trace[k].chunks[wave] = chunks_of(wave);
       uint32_t a1 = 0, a2 = 0;                            // (the wave's sums: a DPP reduction on the device)
       for (int lane = 0; lane < 64; lane++) {
         a1 += s1[lane];
@@ -896,8 +931,20 @@ int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) {
     ALL(p2_rank(S, tid));
     ALL(p3_tree(S, tid));
     ALL(p4_depth(S, tid));
+    uint32_t cnt_before[MAXL + 1];
+    memcpy(cnt_before, S.cnt, sizeof(cnt_before));
     ALL(p5_limit(S, tid));
     ALL(p6_assign(S, tid));
+    if (trace) {
+      PngzTrace& T = trace[k];
+      T.kraft_changed = memcmp(cnt_before, S.cnt, sizeof(cnt_before)) != 0;
+      for (int i = 0; i < S.m; i++) {
+        int d = 0;
+        for (int v = i; v != 2 * S.m - 2; v = S.parent[v]) d++;
+        T.depth = d > T.depth ? d : T.depth;
+      }
+      for (int sym = 0; sym < NSYM; sym++) T.max_len = S.len[sym] > T.max_len ? S.len[sym] : T.max_len;
+    }
     ALL(p7_codes(S, tid));
     ALL(p8_header(S, tid));
     ALL(p9_wave_bits(S, tid));
@@ -921,6 +968,12 @@ int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) {
     ALL(p13_meta(S, tid, &meta[k]));
 #undef ALL
     memcpy(slots.data() + (size_t)k * SLOT_BYTES, S.out, S.bytes);
+    if (trace) {
+      trace[k].stored = S.stored;
+      trace[k].bytes = (int32_t)S.bytes;
+      trace[k].len = len;
+      trace[k].nlit = S.nlit;
+    }
   }
   memcpy(dst, rows, (size_t)n);
   const int64_t total = stream_bytes(meta.data(), nb);
@@ -928,6 +981,18 @@ int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) {
   for (int k = 0; k < nb; k++) memcpy(dst + block_offset(meta.data(), k), slots.data() + (size_t)k * SLOT_BYTES, meta[k].bytes);
   pack_ends(dst, meta.data(), nb);
   return total;
+}
+
+extern "C" {
+
+int64_t emu_pngz(const uint8_t* rows, int64_t n, uint8_t* dst) { return pngz_run(rows, n, dst, nullptr); }
+
+// emu_pngz with a record per block (blocks_of(n) records, `record_bytes` each as the caller sees them) of where the input landed:
+// returns -1 if the caller's record is not this build's.
+int64_t emu_pngz_trace(const uint8_t* rows, int64_t n, uint8_t* dst, void* trace, int32_t record_bytes) {
+  if (record_bytes != (int32_t)sizeof(PngzTrace)) return -1;
+  memset(trace, 0, sizeof(PngzTrace) * (size_t)rrz::blocks_of(n));
+  return pngz_run(rows, n, dst, static_cast<PngzTrace*>(trace));
 }
 
 
