@@ -295,6 +295,39 @@ int rr_pipeline_frames(rr_ctx* ctx, int32_t n, const rr_prepass_in* pre, const r
                        const rr_prepass_out* pre_out);
 
 /* ---------------------------------------------------------------------------------------
+ * Render-scale resize of the inputs on the device: full-size frames in.  The frame loader of the reference resizes
+ * image / 255 (float64) and the depth map (float32) with cv2.resize(INTER_LINEAR) when a plug-in renders at a fraction of the
+ * files' resolution (generator.py:352-381; Cityscapes: render_scale 2).  csrc/rr_resize.h states that resize once -- for
+ * rr_io_read_frames_scaled on the host and for the kernels k_resize_in / k_resize_depth -- bit for bit:
+ *     f = (k + 0.5) * (s / d) - 0.5;  weight f - floor(f), 0 where floor(f) < 0;  both indices clamped to [0, s - 1]
+ *     (a00 (1 - wx) + a01 wx) (1 - wy) + (a10 (1 - wx) + a11 wx) wy      in float64, in this order, not contracted
+ * on byte / 255.0 (or the widened float32 value) for the image and on float32(sample) / 256 (or the float32 metres) widened for
+ * the depth map, whose result is rounded once to float32.  Equal sizes are the identity.
+ *
+ * rr_set_input_resize arms the stage with the size of the images (src_H x src_W) and of the depth maps (depth_H x depth_W) the
+ * entry points below take from then on; all four 0 disarm it (the context is what it was).  RR_E_ARG for a side outside
+ * [1, 16384], RR_E_STATE while a pipeline slot is in flight.  While armed
+ *   rr_pipeline_submit / rr_pipeline_frames / rr_prepass_frames (host pointers) read rr_prepass_in.bg as a src_H x src_W image --
+ *       RR_IN_BG_U8, bg_u8 or RR_IN_BG_PNG_ROWS (src_H rows of 1 + 3 src_W bytes) -- and depth as a depth_H x depth_W map --
+ *       float32, RR_DEPTH_U16 or RR_DEPTH_PNG_ROWS, one kind per batch.  An interleaved float32 / float64 bg, a float64 depth
+ *       map and RR_PRE_ENV_ONLY are RR_E_ARG.
+ *   rr_augment_frames_device reads images as [n,3,src_H,src_W] and depth as [n,depth_H,depth_W]; rainy_out / mask_out keep H x W.
+ * H, W of every descriptor remain the render size.  The stage leaves a float64 B G R image and a float32 depth map of the render
+ * size on the device, and the rest of the call is the float64-image route (in_types 0, depth_f64 0) fed those arrays: the same
+ * outputs, bit for bit, as the unarmed call given the host-resized arrays.  RR_OPT_DEPTH_OCCLUSION is allowed with every kind of
+ * depth input (a float map exists behind the stage).  The source-size inputs wait in a block of the slot's own, sized by the
+ * source and allocated by the first armed batch. */
+int rr_set_input_resize(rr_ctx* ctx, int32_t src_H, int32_t src_W, int32_t depth_H, int32_t depth_W);
+/* The stage alone, on DEVICE arrays, with the sizes of the setter (RR_E_STATE when it is not armed): n images -> bg_out
+ * [n,H,W,3] float64 B G R, n depth maps -> depth_out [n,H,W] float32, enqueued on `stream` (NULL: the context's stream, and the
+ * call waits for it).  Either side may be NULL.  image_kind: RR_RESIZE_*; depth_kind: 0 (float32 metres) or RR_DEPTH_U16. */
+enum { RR_RESIZE_BGR_U8 = 0,             /* [n,src_H,src_W,3] interleaved B G R bytes (the un-filtered file) */
+       RR_RESIZE_RGB_U8_PLANAR = 1,      /* [n,3,src_H,src_W] planar R G B bytes */
+       RR_RESIZE_RGB_F32_PLANAR = 2 };   /* [n,3,src_H,src_W] planar R G B float32: widened, not divided */
+int rr_resize_inputs_device(rr_ctx* ctx, int32_t n, int32_t H, int32_t W, const void* images, int32_t image_kind, const void* depth,
+                            int32_t depth_kind, double* bg_out, float* depth_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Particle generator on the device (SURVEY 8f "next" #4, BASELINE.json configs[4]: "in-kernel particle simulation (no
  * XML)").  The reference drives a closed-source simulator binary through tools/simulation.py with the settings of
  * common/db.py:41-70 and reads its output back as XML (bad_weather.py:192-211); there is no source to follow, so the
@@ -893,6 +926,11 @@ int rr_io_read_frames(int32_t n, const char* const* image_paths, const char* con
 int rr_io_read_frames_rows(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
                            uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
                            int32_t* status);
+/*   rr_io_read_frames_rows_sized  the same with depth files of their own size depth_H x depth_W (rows of 1 + 2 depth_W bytes): the
+ *                       loader of a context armed with rr_set_input_resize, which resizes both on the device */
+int rr_io_read_frames_rows_sized(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
+                                 int32_t depth_H, int32_t depth_W, uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows,
+                                 int64_t depth_stride, int32_t threads, int32_t* status);
 int rr_io_read_frames_u16(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
                           uint8_t* bg_u8, int64_t bg_stride, uint16_t* depth_u16, int64_t depth_stride, int32_t threads, int32_t* status);
 /*   rr_io_read_frames_scaled  the same for a render scale other than 1 (generator.py:352-381, the Cityscapes plug-in's

@@ -64,6 +64,16 @@ must be the augmenter's frame size (ValueError).  The streak mask comes back unc
 tensor, float32 [B, 1, H, W] ([B, V, 1, H, W] for a rig): the drops' coverage, 0 outside them -- the label raindrop-removal work trains
 on.  `LensAugment(lens)` is the lens pass alone, for drops without streak rain: `(images, frame_index) -> images`.
 
+`source_size=(Hs, Ws)` (default None: the images have the render size `frame_size()`) takes full-size frames when the dataset renders
+at a fraction of its files' resolution (Cityscapes: render_scale 2): `images` is [B, 3, Hs, Ws] ([B, V, 3, Hs, Ws] under a rig) and
+the library resizes it on the device with the frame loader's own interpolation (rr_set_input_resize; csrc/rr_resize.h)
+before anything else.  `depth_size=(Hd, Wd)` (default None: the render size) is the size of `depth`, resized the same way.  `rainy`,
+`mask`, the lens pass and `return_lens_alpha` stay at the render size.  The contract: uint8 images of the source size give the RGB of
+the PNG a `main.py --device_particles` run at that render scale writes for files holding those pixels (and a depth file holding
+depth * 256); float32 images are widened, not re-quantised to bytes, so they match that run to the image contract only (+-1 LSB) --
+the mask is identical either way.  Shapes that do not match, or a `depth_size` other than the render size without `source_size`,
+are a ValueError.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -123,7 +133,7 @@ class RainAugment:
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
                  rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None, showers=None,
-                 lens=None, return_lens_alpha=False):
+                 lens=None, return_lens_alpha=False, source_size=None, depth_size=None):
         if lens is not None and not isinstance(lens, lensmod.LensDrops):
             raise TypeError("lens must be a tools.lens.LensDrops, got %r" % (type(lens).__name__,))
         if not isinstance(return_lens_alpha, bool) or (return_lens_alpha and lens is None):
@@ -192,6 +202,29 @@ class RainAugment:
         if lens is not None and (lens.H, lens.W) != self.frame_size():
             raise ValueError("lens: the LensDrops are for %d x %d frames (H x W), %s renders %d x %d" %
                              ((lens.H, lens.W, dataset) + self.frame_size()))
+        self.source_size, self.depth_size = self._check_sizes(source_size, depth_size)
+        self._resize_set = self.source_size is None          # whether the context holds the input sizes
+
+    def _check_sizes(self, source_size, depth_size):
+        """(source_size, depth_size) as pairs of ints, or (None, None): the images and depth maps have the render size."""
+        def pair(v, name):
+            if v is None:
+                return None
+            try:
+                a, b = v
+                ok = all(not isinstance(x, bool) and isinstance(x, numbers.Integral) and 1 <= x <= 16384 for x in (a, b))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("%s %r: expected (H, W), integers in [1, 16384]" % (name, v))
+            return int(a), int(b)
+        source_size, depth_size = pair(source_size, 'source_size'), pair(depth_size, 'depth_size')
+        if source_size is None:
+            if depth_size is not None and depth_size != self.frame_size():
+                raise ValueError("depth_size %r differs from the render size %r: it needs source_size= (the stage that resizes both)" %
+                                 (depth_size, self.frame_size()))
+            return None, None
+        return source_size, depth_size if depth_size is not None else self.frame_size()
 
     def _check_trajectory(self, trajectory):
         if trajectory is None:
@@ -312,7 +345,8 @@ class RainAugment:
             n_max = max(n_max, int(self._rate(r)[0]['n_particles'].max()))
         # the driver's capacity of a frame's drop table (generator.py _run_batches_native + _Slot)
         drops_cap = (min(max(1024, n_max), 2 ** 16) + 3) // 4 * 4
-        out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key,
+        out = dict(sims=sims, d_grid=dgrid, cdf=cdf, fog=fog, drops_cap=min(drops_cap, 2 ** 16), key=key, frame_size=self.frame_size(),
+                   source_size=self.source_size, depth_size=self.depth_size,     # (None, None: images and depth at the render size)
                    particle_model=self.particle_model, cam_hz=float(self.options["cam_hz"]), draws=self.draws, jitter=self.jitter,
                    wind=self.wind, lean=self.lean, gusts=self.gusts, showers=self.showers)
         if self.rig is not None:                             # V consecutive records per instant, equal up to draw_seed (equal too)
@@ -340,15 +374,17 @@ class RainAugment:
             if images.dim() != 5 or images.shape[1] != V or images.shape[2] != 3 or min(images.shape) < 1:
                 raise ValueError("images must be [B, V = %d, 3, H, W] (planar RGB per view), got %s" % (V, tuple(images.shape)))
             B, _, _, H, W = images.shape
-            if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, V, H, W), (B, V, 1, H, W)):
+            dH, dW = (H, W) if self.source_size is None else self.depth_size
+            if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, V, dH, dW), (B, V, 1, dH, dW)):
                 raise ValueError("depth must be float32 [B, V, H, W] or [B, V, 1, H, W] = %s, got %s %s" %
-                                 ((B, V, H, W), depth.dtype, tuple(depth.shape)))
+                                 ((B, V, dH, dW), depth.dtype, tuple(depth.shape)))
             return B, H, W
         if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1 or images.shape[2] < 1 or images.shape[3] < 1:
             raise ValueError("images must be [B, 3, H, W] (planar RGB), got %s" % (tuple(images.shape),))
         B, _, H, W = images.shape
-        if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, H, W), (B, 1, H, W)):
-            raise ValueError("depth must be float32 [B, H, W] or [B, 1, H, W] = %s, got %s %s" % ((B, H, W), depth.dtype, tuple(depth.shape)))
+        dH, dW = (H, W) if self.source_size is None else self.depth_size
+        if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, dH, dW), (B, 1, dH, dW)):
+            raise ValueError("depth must be float32 [B, H, W] or [B, 1, H, W] = %s, got %s %s" % ((B, dH, dW), depth.dtype, tuple(depth.shape)))
         return B, H, W
 
     def _check_device(self, images, depth):
@@ -393,21 +429,26 @@ class RainAugment:
             we = self._hip.set_envmap_geometry(H, W, *envmap.EnvironmentMapGenerator(self.focal, W, H).device_tables(H, W))
             self._hip.set_solid_angles(solid_angle.get_solid_angles(np.empty((H, we, 0))))
             self._geom = (H, W)
+        if not self._resize_set:                 # full-size frames in: the library resizes images and depth to H x W first
+            self._hip.set_input_resize(*(self.source_size + self.depth_size))
+            self._resize_set = True
         return self._hip
 
     def __call__(self, images, depth, intensity, frame_index):
         B, H, W = self._validate(images, depth)
         p = self.plan(intensity, frame_index, B)
         fh, fw = int(p['sims'][0]['sensor_h']) // self.render_scale, int(p['sims'][0]['sensor_w']) // self.render_scale
-        if (H, W) != (fh, fw):
-            raise ValueError("%s%s renders %d x %d frames (H x W), the images are %d x %d" %
-                             (self.dataset, '' if self.sequence is None else '/' + self.sequence, fh, fw, H, W))
+        if (H, W) != ((fh, fw) if self.source_size is None else self.source_size):
+            raise ValueError("%s%s renders %d x %d frames (H x W)%s, the images are %d x %d" %
+                             (self.dataset, '' if self.sequence is None else '/' + self.sequence, fh, fw,
+                              '' if self.source_size is None else ' from source_size = %d x %d' % self.source_size, H, W))
         dev = self._check_device(images, depth)
         V = None if self.rig is None else len(self.views)
         if V is not None:                                    # the library's batch: V consecutive frames per instant
             B = B * V
         images = images.reshape(B, 3, H, W).contiguous()
-        depth = depth.reshape(B, H, W).contiguous()
+        depth = depth.reshape((B,) + ((H, W) if self.source_size is None else self.depth_size)).contiguous()
+        H, W = fh, fw                                        # from here on: the render size
         with torch.cuda.device(dev):
             hip = self._context(dev, H, W, p['key'], p['d_grid'], p['cdf'], p)
             rainy = torch.empty((B, 3, H, W), dtype=images.dtype, device=dev)

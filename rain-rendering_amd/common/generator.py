@@ -78,6 +78,7 @@ class Generator:
         self.db = None
         self.renderer = None
         self.device_particles = bool(getattr(args, 'device_particles', False))     # drop tables generated on the GPU (no XML)
+        self.device_resize = bool(getattr(args, 'device_resize', False))           # full-size frames in: the library resizes them
         self.particle_model = getattr(args, 'particle_model', 'iid') or 'iid'       # 'field': persistent particles (tools/particles.py)
         if self.particle_model != 'iid' and not self.device_particles:
             raise ValueError("--particle_model %s needs --device_particles" % self.particle_model)
@@ -265,10 +266,13 @@ class Generator:
         Every array is one page-locked block with the frames back to back, each on a 16-byte boundary (RainHip.host_rows):
         the library then moves an array of the whole batch with ONE copy instead of one DMA request per frame."""
 
-        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False):
+        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False, resize=None):
             """png_rows: the image / depth blocks hold the files' filtered scanlines (rr_io_read_frames_rows: H rows of 1 + 3 W /
-            1 + 2 W bytes per frame) instead of pixels.  lens_alpha: a third scanline block, the label file of --lens_alpha."""
+            1 + 2 W bytes per frame) instead of pixels.  lens_alpha: a third scanline block, the label file of --lens_alpha.
+            resize = (sh, sw, dh, dw), with png_rows: the scanlines are those of sh x sw images and dh x dw depth files (the library
+            resizes them to H x W: --device_resize); the output blocks keep H x W."""
             self.B, self.H, self.W = B, H, W
+            sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
             self._raw = []
 
             def rows(shape, dtype):
@@ -276,8 +280,8 @@ class Generator:
                 self._raw.append(raw)
                 return views
             drops_cap = (drops_cap + 3) // 4 * 4
-            self.bg = rows((H * (1 + 3 * W),), np.uint8) if png_rows else rows((H, W, 3), bg_dtype)
-            self.depth = rows((H * (1 + 2 * W),), np.uint8) if png_rows else rows((H, W), depth_dtype)
+            self.bg = rows((sh * (1 + 3 * sw),), np.uint8) if png_rows else rows((H, W, 3), bg_dtype)
+            self.depth = rows((dh * (1 + 2 * dw),), np.uint8) if png_rows else rows((H, W), depth_dtype)
             self.drops = rows((drops_cap,), hip_backend.DROP_DTYPE)
             self.status = rows((drops_cap,), np.int32)
             row = H * (1 + 4 * W)
@@ -291,6 +295,8 @@ class Generator:
             self.lens_alpha = bool(lens_alpha)
             self.drops_cap = drops_cap
             self.key = (B, H, W, We, 'png rows' if png_rows else np.dtype(bg_dtype), 'png rows' if png_rows else np.dtype(depth_dtype), bool(save_envmap))
+            if resize is not None:
+                self.key += (tuple(resize),)
             self.items, self.encodes, self.busy = [], [], False
             self.prep, self.pkey, self.n_valid = None, None, 0
 
@@ -608,7 +614,7 @@ class Generator:
             self._shower_fog[rate] = tuple(float(v) for v in add_attenuation.FogRain(**dict(self._shower_fog_params, rain_intensity=rate)).constants())
         return self._shower_fog[rate]
 
-    def _cap_batch(self, B, imH, imW, frame_render_dict, sims):
+    def _cap_batch(self, B, imH, imW, frame_render_dict, sims, resize=None):
         """Frames per library call, bounded by the page-locked memory a rank may hold: three slots of B frames, each frame
         its input bytes (image, float32 depth), both PNG scanline blocks and the drop / status tables -- about 15 bytes per
         pixel + 116 per drop: 7.9 MB at KITTI size (3 GB for 3 x 128 frames), 32 MB at Cityscapes full size.  Budget:
@@ -621,6 +627,9 @@ class Generator:
         budget = float(os.environ.get('RAIN_PINNED_MB', 8192.0 / local)) * 2 ** 20
         n_max = int(sims['n_particles'].max()) if sims is not None else max((len(getattr(fr, 'table', ())) for fr in (frame_render_dict or ())), default=0)
         per_frame = imH * imW * 15 + 2 * imH + min(max(n_max, 1024), 2 ** 16) * 116
+        if resize is not None:                       # --device_resize: the inputs are the files' scanlines at their own sizes
+            sh, sw, dh, dw = resize
+            per_frame += sh * (1 + 3 * sw) + dh * (1 + 2 * dw) - imH * imW * 7
         return max(1, min(B, int(budget // (hip_backend.RR_PIPE_SLOTS * per_frame))))
 
     def _run_batches(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None):
@@ -630,6 +639,7 @@ class Generator:
         the batch-native route (one library call per batch and stage, nothing per frame under the interpreter lock);
         everything else the general one (per-frame Python on an I/O thread pool)."""
         ds = self.settings["depth_scale"]
+        B0, resize = B, None
         B = self._cap_batch(B, imH, imW, frame_render_dict, sims)
         native = (work and int(rs) == rs and rs >= 1 and int(ds) == ds and ds >= 1 and
                   (sims is not None or not (bool(self.noise_std) and bool(self.noise_scale))) and not self.save_envmap and
@@ -641,15 +651,21 @@ class Generator:
             i0, d0 = imgops._native_png(work[0]['image_file']), imgops._native_png(work[0]['depth_file'])
             native = (i0 is not None and d0 is not None and i0[4] == 8 and tuple(d0[3:5]) == (1, 16) and
                       (i0[1] // rs, i0[2] // rs) == (imW, imH) and ((d0[1] * ds) // rs, (d0[2] * ds) // rs) == (imW, imH) and
-                      (rs != 1 or (d0[1], d0[2]) == (imW, imH)))
+                      (rs != 1 or (d0[1], d0[2]) == (imW, imH) or self.device_resize))
+            # --device_resize: full-size files in, resized by the library -- where there is a resize to do (else the flag is a no-op)
+            if native and self.device_resize and ((i0[2], i0[1]) != (imH, imW) or (d0[2], d0[1]) != (imH, imW)):
+                resize = (int(i0[2]), int(i0[1]), int(d0[2]), int(d0[1]))
+                B = self._cap_batch(B0, imH, imW, frame_render_dict, sims, resize)
         if sims is not None:
             if work and not native:
                 raise NotImplementedError("--device_particles needs the batch-native route: PNG frames and depth maps of matching "
                                           "scaled sizes, no environment-map files (RAIN_NATIVE_IO not 0)")
             return self._run_batches_native(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num,
-                                            sim_t0, sims)
-        run = self._run_batches_native if native else self._run_batches_general
-        return run(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0)
+                                            sim_t0, sims, resize=resize)
+        if native:
+            return self._run_batches_native(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num,
+                                            sim_t0, resize=resize)
+        return self._run_batches_general(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0)
 
     @staticmethod
     def _set_png_deflate(hip):
@@ -661,12 +677,15 @@ class Generator:
             return
         hip.set_option(hip_backend.RR_OPT_PNG_DEFLATE, 0 if os.environ.get('RAIN_PNG_DEVICE', '1') == '0' else 1)
 
-    def _run_batches_native(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None):
+    def _run_batches_native(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None,
+                            resize=None):
         """Batch-native route.  Per batch, three whole-batch jobs, each one call (or two) into the library:
           decode  rr_io_read_frames (image bytes + depth metres straight into the slot's page-locked input blocks) and
                   rr_host_pack_frames (filter, draws, drop records into the slot's drop block) -- one batch ahead of the GPU;
           render  rr_pipeline_submit / rr_pipeline_wait on the prepared descriptors;
           encode  rr_io_write_frames (both files of every frame from the slot's scanline blocks) -- one batch behind.
+        resize = (sh, sw, dh, dw) (--device_resize): decode is rr_io_read_frames_rows at the files' own sizes, and the library, armed
+        with rr_set_input_resize, makes the H x W frames of them on the device; everything behind the inputs is unchanged.
         A slot's INPUT blocks are free again when its batch has been collected (the encoders only read the output
         blocks), so batch b+1 is decoded into slot (b+1) % 3 while batch b renders and batch b-1 is written."""
         stage = self._stage_pool()
@@ -690,7 +709,12 @@ class Generator:
         # never more than the 2 ** 16 the reference allows AFTER the filter (generator.py:424): a simulated frame with more
         # streaks than that is fine as long as fewer land inside the image -- checked on the filtered counts below
         drops_cap = min(max(1024, int(sims['n_particles'].max()) if sims is not None else max(len(fr.table) for fr in frame_render_dict)), 2 ** 16)
-        u8 = rs == 1                                              # at render scale 1 the bytes go to the GPU; a resized image is float64
+        u8 = rs == 1 or resize is not None                        # at render scale 1 the bytes go to the GPU; a resized image is float64
+        # the library resizes (or not) for the whole run: armed once, and left alone while the sizes stay what they are
+        if getattr(self, '_resize_armed', None) != (hip, resize):
+            if resize is not None or getattr(self, '_resize_armed', (None, None))[1] is not None:
+                hip.set_input_resize(*(resize or (0, 0, 0, 0)))
+            self._resize_armed = (hip, resize)
         bg_dtype = np.uint8 if u8 else np.float64
         ds = int(self.settings["depth_scale"])
         # at render scale 1 the depth file's uint16 samples travel as they are (rr_prepass_in.depth_f64 = RR_DEPTH_U16: metres =
@@ -700,8 +724,11 @@ class Generator:
         depth_dtype = np.uint16 if d16 else np.float32
         # ... and both files as the filtered scanlines their IDAT streams inflate to (rr_io_read_frames_rows): the scanline filters
         # are reversed on the device (k_png_unfilter), 40 % of the host's decode time.  RAIN_PNG_ROWS=0: pixels decoded by the host.
-        rows_in = u8 and os.environ.get('RAIN_PNG_ROWS', '1') != '0'
+        rows_in = resize is not None or (u8 and os.environ.get('RAIN_PNG_ROWS', '1') != '0')
         key = (B, H, W, env_w, 'png rows' if rows_in else np.dtype(bg_dtype), 'png rows' if rows_in else np.dtype(depth_dtype), False)
+        if resize is not None:
+            key += (tuple(resize),)
+        sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
         lens_alpha = self._lens is not None and self.lens_alpha
         pkey = (tuple(float(v) for v in fog_const), float(self.opacity_attenuation), self.rendering_strategy, sims is not None)
         for d in {os.path.dirname(it[k]) for it in work for k in ('out_rainy_path', 'out_rainy_mask_path') + (('out_lens_alpha_path',) if lens_alpha else ())}:
@@ -712,7 +739,7 @@ class Generator:
         pending = {}                                             # slots being page-locked by the helper thread (see below)
 
         def new_slot():
-            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha)
+            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha, resize=resize)
 
         def slot_for(si):
             if si in pending:
@@ -723,7 +750,9 @@ class Generator:
                     sl.free(hip)
                 sl = slots[si] = new_slot()
             if getattr(sl, 'prep', None) is None or sl.pkey != pkey:
-                inputs = ((lambda k: dict(bg_png_rows=sl.bg[k], shape=(H, W), depth_png_rows=sl.depth[k])) if rows_in else
+                inputs = ((lambda k: dict(bg_png_rows=sl.bg[k], shape=(sh, sw), depth_png_rows=sl.depth[k], depth_shape=(dh, dw), render_shape=(H, W)))
+                          if resize is not None else
+                          (lambda k: dict(bg_png_rows=sl.bg[k], shape=(H, W), depth_png_rows=sl.depth[k])) if rows_in else
                           (lambda k: dict(bg=None if u8 else sl.bg[k], bg_u8=sl.bg[k] if u8 else None, depth=sl.depth[k])))
                 frames = [dict(inputs(k), fog=fog_const, omega=None, drops=sl.drops[k],
                                opacity_attenuation=self.opacity_attenuation, strategy=1 if self.rendering_strategy == 'white' else 0)
@@ -741,7 +770,10 @@ class Generator:
 
         def decode_job(sl, items):
             """-> (frames of the batch in slot order, their drop counts): inputs of `sl` filled for the first len() frames."""
-            if rows_in:
+            if resize is not None:
+                st = hip_backend.io_read_frames_rows([it['image_file'] for it in items], [it['depth_file'] for it in items], sh, sw,
+                                                     sl.raw_bg, sl.raw_depth, threads, depth_shape=(dh, dw))
+            elif rows_in:
                 st = hip_backend.io_read_frames_rows([it['image_file'] for it in items], [it['depth_file'] for it in items], H, W,
                                                      sl.raw_bg, sl.raw_depth, threads)
             elif u8:
@@ -758,13 +790,18 @@ class Generator:
                                                  sl.drops_cap, sl.drops_cap, threads)
             ok = [True] * len(items)
             for k in np.nonzero(st)[0]:                          # not a file the fast readers take: the general loader
-                loaded = self._load_frame(items[k]['image_file'], items[k]['depth_file'], rs)
+                if resize is not None:                           # ... 's unscaled bytes and metres: the library resizes them
+                    bg = imgops.imread_bgr(items[k]['image_file'])
+                    depth = imgops.imread_unchanged(items[k]['depth_file'])
+                    loaded = None if depth is None else (bg, depth.astype(np.float32) / 256.)
+                else:
+                    loaded = self._load_frame(items[k]['image_file'], items[k]['depth_file'], rs)
                 if loaded is None:
                     print('Missing/Corrupted depth data (%s)' % items[k]['depth_file'])
                     ok[k] = False
                     continue
                 bg, depth = loaded
-                assert bg.shape[:2] == (H, W) and bg.dtype == bg_dtype and depth.shape == (H, W), "frames of one sequence share their size"
+                assert bg.shape[:2] == (sh, sw) and bg.dtype == bg_dtype and depth.shape == (dh, dw), "frames of one sequence share their size"
                 samples = None
                 if rows_in or d16:
                     # a 16-bit PNG depth map is sample / 256 in float32: the samples come back exactly -- anything else (an 8-bit

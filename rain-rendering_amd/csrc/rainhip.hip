@@ -58,6 +58,7 @@
 #include "rr_pngrows.h"
 #include "rr_particles.h"
 #include "rr_lens.h"
+#include "rr_resize.h"
 
 using namespace rr;
 
@@ -4437,6 +4438,158 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t* rows_base, i
   }
 }
 
+// The render-scale resize of the inputs (rr_set_input_resize; the arithmetic is csrc/rr_resize.h): full-size frames in,
+// the float64 B G R image / the float32 depth map of the render size out -- what the pre-pass and the hot path read as in_types = 0.
+//   k_resize_in<KIND>     RSZ_BGR8: the un-filtered file, interleaved B G R bytes; RSZ_RGB8P / RSZ_RGBF32P: a planar R G B tensor
+//   k_resize_depth<KIND>  RSZ_D16: uint16 samples (metres * 256); RSZ_DF32: float32 metres
+// A workgroup makes RSZ_SEG pixels of one output row of one frame (grid: segments x rows x frames), two pixels per lane.  The two
+// source rows it reads (six pieces for a planar tensor) are consecutive bytes: it stages them in LDS with aligned 16-byte loads
+// -- a piece starts wherever 3 Ws bytes per row put it, so the load window starts at the 16-byte boundary below the piece and the
+// piece's misalignment is added to every LDS index; windows that leave the caller's buffer [lo, hi) are read byte by byte -- and
+// every lane then picks its 2 x 2 neighbourhoods out of LDS.  A segment whose source span does not fit its share of the pool
+// (a scale above ~12 for bytes, ~3 for planar floats) reads global memory directly.  The image goes out as three 16-byte stores per
+// lane (48 bytes = two pixels), the odd last pixel of a row as three doubles.
+enum { RSZ_BGR8 = 0, RSZ_RGB8P = 1, RSZ_RGBF32P = 2, RSZ_D16 = 3, RSZ_DF32 = 4 };
+constexpr int RSZ_THREADS = 256, RSZ_SEG = 2 * RSZ_THREADS;
+constexpr int RSZ_POOL = 6 * 6656;                      // LDS bytes for the staged pieces: 1026 floats + the windows' ends, six times
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+
+struct ResizeArgs {
+  const uint8_t* src;               // frame 0; frames src_stride bytes apart
+  const uint8_t *lo, *hi;           // the buffer the frames lie in: nothing outside it is read
+  int64_t src_stride;
+  void* dst;                        // frame 0: H x W x 3 float64 / H x W float32; frames dst_stride bytes apart
+  int64_t dst_stride;
+  int32_t H, W, sH, sW;
+  double sx, sy;                    // rrresize::resize_scale(W, sW), (H, sH)
+};
+
+// global bytes [g0, g1) -> LDS: byte g0 + b lands at reg[(g0 & 15) + b]
+__device__ inline void resize_stage(const uint8_t* g0, const uint8_t* g1, const uint8_t* lo, const uint8_t* hi, uint8_t* reg) {
+  const uint8_t* al = g0 - (reinterpret_cast<uintptr_t>(g0) & 15u);
+  const int chunks = (int)((g1 - al + 15) >> 4);
+  for (int c = threadIdx.x; c < chunks; c += RSZ_THREADS) {
+    const uint8_t* a = al + 16 * (int64_t)c;
+    u32x4_t v;
+    if (a >= lo && a + 16 <= hi) {
+      v = *as_global(reinterpret_cast<const u32x4_t*>(a));
+    } else {
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+      for (int k = 0; k < 16; k++)
+        if (a + k >= lo && a + k < hi) w[k >> 2] |= (uint32_t)as_global(a)[k] << (8 * (k & 3));
+      v = u32x4_t{w[0], w[1], w[2], w[3]};
+    }
+    *reinterpret_cast<u32x4_t*>(reg + 16 * c) = v;
+  }
+}
+
+template <int KIND>
+__device__ inline void resize_rows(const ResizeArgs& a) {
+  constexpr bool IMAGE = KIND <= RSZ_RGBF32P;
+  constexpr int P = (KIND == RSZ_RGB8P || KIND == RSZ_RGBF32P) ? 3 : 1;                                  // pieces per source row
+  constexpr int EL = KIND == RSZ_BGR8 ? 3 : (KIND == RSZ_RGB8P ? 1 : (KIND == RSZ_D16 ? 2 : 4));      // bytes per pixel of a piece
+  constexpr int CAP = RSZ_POOL / (2 * P);
+  static_assert(CAP % 16 == 0, "every piece starts on a 16-byte boundary of the pool");
+  __shared__ double s_lut[256];
+  __shared__ u32x4_t s_pool[RSZ_POOL / 16];
+  const int t = threadIdx.x, f = blockIdx.z, y = blockIdx.y;
+  const int xs = blockIdx.x * RSZ_SEG, xe = rr::imin(xs + RSZ_SEG, a.W);
+  if (KIND == RSZ_BGR8 || KIND == RSZ_RGB8P) s_lut[t] = rrresize::image_unit((uint8_t)t);
+  const bool identity = a.sH == a.H && a.sW == a.W;
+  int32_t yy[2], xa, xb, spare;
+  double wy, wspare;
+  rrresize::resize_coord(y, a.sH, a.sy, yy[0], yy[1], wy);
+  rrresize::resize_coord(xs, a.sW, a.sx, xa, spare, wspare);               // the segment reads source columns xa .. xb
+  rrresize::resize_coord(xe - 1, a.sW, a.sx, spare, xb, wspare);
+  const int64_t row_bytes = (int64_t)a.sW * EL, plane_bytes = row_bytes * a.sH;
+  const uint8_t* fbase = a.src + (int64_t)f * a.src_stride;
+  const uint8_t* gp[P][2];          // piece p of row r: the address of source column 0 (plane 2 - p of a planar tensor: B G R order)
+  uint8_t* lp[P][2];                // ... and of source column xa in LDS
+  const bool staged = (int64_t)(xb - xa + 1) * EL + 30 <= CAP;
+#pragma unroll
+  for (int p = 0; p < P; p++)
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      gp[p][r] = fbase + (P == 3 ? (int64_t)(2 - p) * plane_bytes : 0) + (int64_t)yy[r] * row_bytes;
+      uint8_t* reg = reinterpret_cast<uint8_t*>(s_pool) + (p * 2 + r) * CAP;
+      const uint8_t* g0 = gp[p][r] + (int64_t)xa * EL;
+      lp[p][r] = reg + (reinterpret_cast<uintptr_t>(g0) & 15u);
+      if (staged) resize_stage(g0, gp[p][r] + (int64_t)(xb + 1) * EL, a.lo, a.hi, reg);
+    }
+  __syncthreads();
+  const int x = xs + 2 * t;
+  if (x >= xe) return;
+  const int cnt = x + 1 < xe ? 2 : 1;
+  // channel c (B G R) of source pixel (row r, column sx) as the loader's float64 sample
+  auto run = [&](auto&& sample) {
+    double v[2][IMAGE ? 3 : 1];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      if (k < cnt) {
+        int32_t x0, x1;
+        double wx;
+        rrresize::resize_coord(x + k, a.sW, a.sx, x0, x1, wx);
+#pragma unroll
+        for (int c = 0; c < (IMAGE ? 3 : 1); c++)
+          v[k][c] = identity ? sample(0, x0, c)
+                             : rrresize::resize_sample(sample(0, x0, c), sample(0, x1, c), sample(1, x0, c), sample(1, x1, c), wx, wy);
+      } else {
+#pragma unroll
+        for (int c = 0; c < (IMAGE ? 3 : 1); c++) v[k][c] = 0.0;
+      }
+    }
+    if (IMAGE) {
+      double* o = reinterpret_cast<double*>(static_cast<char*>(a.dst) + (int64_t)f * a.dst_stride) + ((int64_t)y * a.W + x) * 3;
+      const global_ptr<double> og = as_global(o);
+      if (cnt == 2 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
+        const global_ptr<f64x2_t> o2 = reinterpret_cast<global_ptr<f64x2_t>>(og);
+        o2[0] = f64x2_t{v[0][0], v[0][1]};
+        o2[1] = f64x2_t{v[0][IMAGE ? 2 : 0], v[1][0]};
+        o2[2] = f64x2_t{v[1][IMAGE ? 1 : 0], v[1][IMAGE ? 2 : 0]};
+      } else if (cnt == 2) {                              // a row that starts 8 bytes off: the two middle pairs are aligned
+        const global_ptr<f64x2_t> o2 = reinterpret_cast<global_ptr<f64x2_t>>(og + 1);
+        og[0] = v[0][0];
+        o2[0] = f64x2_t{v[0][IMAGE ? 1 : 0], v[0][IMAGE ? 2 : 0]};
+        o2[1] = f64x2_t{v[1][0], v[1][IMAGE ? 1 : 0]};
+        og[5] = v[1][IMAGE ? 2 : 0];
+      } else {
+        og[0] = v[0][0];
+        og[1] = v[0][IMAGE ? 1 : 0];
+        og[2] = v[0][IMAGE ? 2 : 0];
+      }
+    } else {                                              // cv2.resize keeps float32: one rounding of the float64 sample
+      float* o = reinterpret_cast<float*>(static_cast<char*>(a.dst) + (int64_t)f * a.dst_stride) + ((int64_t)y * a.W + x);
+      const global_ptr<float> og = as_global(o);
+      if (cnt == 2 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) {
+        *reinterpret_cast<global_ptr<u32x2_t>>(og) = u32x2_t{__float_as_uint((float)v[0][0]), __float_as_uint((float)v[1][0])};
+      } else {
+        og[0] = (float)v[0][0];
+        if (cnt == 2) og[1] = (float)v[1][0];
+      }
+    }
+  };
+  auto value = [&](const auto* q, int c) -> double {      // q: the pixel's first byte, in LDS or in global memory
+    if constexpr (KIND == RSZ_BGR8) return s_lut[q[c]];
+    else if constexpr (KIND == RSZ_RGB8P) return s_lut[q[0]];
+    else if constexpr (KIND == RSZ_RGBF32P) return (double)*reinterpret_cast<const float*>(q);
+    else if constexpr (KIND == RSZ_D16) return (double)rrresize::depth_metres(*reinterpret_cast<const uint16_t*>(q));
+    else return (double)*reinterpret_cast<const float*>(q);
+  };
+  if (staged)
+    run([&](int r, int sx, int c) { return value(lp[P == 3 ? c : 0][r] + (int64_t)(sx - xa) * EL, c); });
+  else
+    run([&](int r, int sx, int c) { return value(gp[P == 3 ? c : 0][r] + (int64_t)sx * EL, c); });
+}
+
+template <int KIND>
+__global__ __launch_bounds__(RSZ_THREADS) void k_resize_in(const ResizeArgs a) {
+  resize_rows<KIND>(a);
+}
+template <int KIND>
+__global__ __launch_bounds__(RSZ_THREADS) void k_resize_depth(const ResizeArgs a) {
+  resize_rows<KIND>(a);
+}
+
 // RR_OPT_PNG_DEFLATE: the scanlines of both files become the zlib streams of their IDAT chunks on the device (rr_deflate.h).
 // k_pngz_blocks: one workgroup of 512 threads per 32 KB block of a file's scanlines (grid: blocks x files; file = 2 * frame +
 // {image, mask}); its working set (the block, its compressed form, the code tables: 76 KB) is dynamic LDS.  The compressed block goes to the
@@ -5664,6 +5817,10 @@ struct rr_ctx {
       size_t copy_cap = 0, label_cap = 0, png_cap = 0;
       std::vector<uint8_t*> alpha_png;                   // the caller's n host buffers (NULL entries allowed), or empty
     } lens;
+    // rr_set_input_resize: the batch's source-size inputs (filtered rows, un-filtered bytes, samples), sized by the source and
+    // allocated by the first armed batch (grown, never shrunk)
+    uint8_t* d_src = nullptr;
+    size_t src_cap = 0;
   } slots[RR_PIPE_SLOTS];
   hipStream_t s_up = nullptr, s_down = nullptr;
   // pre-pass (fog + environment map)
@@ -5709,6 +5866,11 @@ struct rr_ctx {
   // rr_lens_drops_device: the block a call uploads (blur table, drop records, work list), grown to the largest call seen
   char* d_lens = nullptr;
   size_t lens_bytes = 0;
+  // rr_set_input_resize: the size of the images / depth maps the entry points take while armed
+  struct InputResize {
+    bool armed = false;
+    int sH = 0, sW = 0, dH = 0, dW = 0;
+  } rsz;
 };
 
 namespace {
@@ -7178,6 +7340,7 @@ int rr_destroy(rr_ctx* ctx) {
     hipFree(sl.lens.d_copy);
     hipFree(sl.lens.d_label);
     hipFree(sl.lens.d_png);
+    hipFree(sl.d_src);
   }
   if (ctx->s_col) hipStreamDestroy(ctx->s_col);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
@@ -8073,6 +8236,65 @@ int slot_init(rr_ctx* ctx, rr_ctx::Slot& sl) {
   return RR_OK;
 }
 
+// The input stage of rr_set_input_resize on `s`: n frames of the armed source size at `src` (src_stride bytes apart, inside the
+// buffer [lo, hi)) -> the render-size float64 image / float32 depth map at `dst`.  kind: RSZ_*.  Each kernel under its own scope.
+int enqueue_resize(rr_ctx* ctx, int n, int H, int W, int kind, const void* src, int64_t src_stride, const void* lo, const void* hi,
+                   void* dst, int64_t dst_stride, hipStream_t s) {
+  const bool image = kind <= RSZ_RGBF32P;
+  const int sH = image ? ctx->rsz.sH : ctx->rsz.dH, sW = image ? ctx->rsz.sW : ctx->rsz.dW;
+  if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || sH <= 0 || sW <= 0) {
+    ctx->err = "input resize: bad batch or frame size";
+    return RR_E_ARG;
+  }
+  const ResizeArgs a{static_cast<const uint8_t*>(src), static_cast<const uint8_t*>(lo), static_cast<const uint8_t*>(hi), src_stride, dst, dst_stride,
+                     H, W, sH, sW, rrresize::resize_scale(W, sW), rrresize::resize_scale(H, sH)};
+  const dim3 grid((unsigned)((W + RSZ_SEG - 1) / RSZ_SEG), (unsigned)H, (unsigned)n);
+  if (image) {
+    ProfScope ps(ctx, s, "k_resize_in");
+    if (kind == RSZ_BGR8) hipLaunchKernelGGL(k_resize_in<RSZ_BGR8>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGB8P) hipLaunchKernelGGL(k_resize_in<RSZ_RGB8P>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(k_resize_in<RSZ_RGBF32P>, grid, dim3(RSZ_THREADS), 0, s, a);
+  } else {
+    ProfScope ps(ctx, s, "k_resize_depth");
+    if (kind == RSZ_D16) hipLaunchKernelGGL(k_resize_depth<RSZ_D16>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(k_resize_depth<RSZ_DF32>, grid, dim3(RSZ_THREADS), 0, s, a);
+  }
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
+// rr_resize_inputs_device: the stage alone, on the caller's device arrays
+int resize_inputs(rr_ctx* ctx, int n, int H, int W, const void* images, int image_kind, const void* depth, int depth_kind, double* bg_out,
+                  float* depth_out, hipStream_t s) {
+  const rr_ctx::InputResize& R = ctx->rsz;
+  if (!R.armed) {
+    ctx->err = "rr_resize_inputs_device: rr_set_input_resize first";
+    return RR_E_STATE;
+  }
+  if (n <= 0 || (images && !bg_out) || (depth && !depth_out) || (images && (image_kind < RR_RESIZE_BGR_U8 || image_kind > RR_RESIZE_RGB_F32_PLANAR)) ||
+      (depth && depth_kind != 0 && depth_kind != RR_DEPTH_U16) ||
+      (images && image_kind == RR_RESIZE_RGB_F32_PLANAR && (reinterpret_cast<uintptr_t>(images) & 3u)) ||
+      (depth && (reinterpret_cast<uintptr_t>(depth) & (depth_kind == RR_DEPTH_U16 ? 1u : 3u)))) {
+    ctx->err = "rr_resize_inputs_device: bad argument (n, a kind, an output missing for its input, or a misaligned array)";
+    return RR_E_ARG;
+  }
+  int rc;
+  if (images) {
+    const int64_t fb = (int64_t)R.sH * R.sW * 3 * (image_kind == RR_RESIZE_RGB_F32_PLANAR ? 4 : 1);
+    const int kind = image_kind == RR_RESIZE_BGR_U8 ? RSZ_BGR8 : (image_kind == RR_RESIZE_RGB_U8_PLANAR ? RSZ_RGB8P : RSZ_RGBF32P);
+    if ((rc = enqueue_resize(ctx, n, H, W, kind, images, fb, images, static_cast<const char*>(images) + (int64_t)n * fb, bg_out,
+                             (int64_t)H * W * 24, s)))
+      return rc;
+  }
+  if (depth) {
+    const int64_t fb = (int64_t)R.dH * R.dW * (depth_kind == RR_DEPTH_U16 ? 2 : 4);
+    if ((rc = enqueue_resize(ctx, n, H, W, depth_kind == RR_DEPTH_U16 ? RSZ_D16 : RSZ_DF32, depth, fb, depth,
+                             static_cast<const char*>(depth) + (int64_t)n * fb, depth_out, (int64_t)H * W * 4, s)))
+      return rc;
+  }
+  return RR_OK;
+}
+
 // Validate the WHOLE batch before anything is copied or mutated (sizes, pointers, per-frame dimensions).
 int validate_host_batch(rr_ctx* ctx, int n, const rr_prepass_in* pre, const rr_frame_in* in, const rr_frame_out* out,
                         const rr_prepass_out* pre_out, Dims& dm, int& max_drops) {
@@ -8128,6 +8350,14 @@ int validate_host_batch(rr_ctx* ctx, int n, const rr_prepass_in* pre, const rr_f
           (env_only && ((pre[f].in_types & RR_IN_BG_PNG_ROWS) || pre[f].depth_f64 == RR_DEPTH_PNG_ROWS)) ||
           ((pre[f].in_types & RR_IN_BG_PNG_ROWS) && pre[f].bg_u8) || pre[f].depth_f64 < 0 || pre[f].depth_f64 > RR_DEPTH_PNG_ROWS) {
         ctx->err = "pre-pass: PNG scanlines (RR_IN_BG_PNG_ROWS / RR_DEPTH_PNG_ROWS) for every frame of a batch or for none, not with bg_u8 or RR_PRE_ENV_ONLY";
+        return RR_E_ARG;
+      }
+      // rr_set_input_resize: the image arrives as bytes (or as a file's scanlines) and the depth map as float32 or uint16 samples
+      // (or scanlines), one kind of depth for the whole batch (one launch of the resize kernel)
+      if (ctx->rsz.armed && (env_only || (!(bgk & (RR_IN_BG_U8 | RR_IN_BG_PNG_ROWS)) && !pre[f].bg_u8) || pre[f].depth_f64 == 1 ||
+                             (pre[f].depth_f64 == 0) != (pre[0].depth_f64 == 0))) {
+        ctx->err = "pre-pass, armed with rr_set_input_resize: the image is RR_IN_BG_U8 / bg_u8 / RR_IN_BG_PNG_ROWS (not an interleaved float image), "
+                   "the depth map float32 or uint16 samples for the whole batch, and not RR_PRE_ENV_ONLY";
         return RR_E_ARG;
       }
       if (!in && !env_only && !pre_out[f].rainy_bg) {
@@ -8265,8 +8495,47 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     }
   }
   const size_t rainy_el = (pre_types & RR_OUT_RAINY_F32) ? 4 : 8, penv_el = (pre_types & RR_OUT_ENV_F32) ? 4 : 8;
+  // rr_set_input_resize: a frame's source-size inputs in the slot's own block -- [image scanlines | image bytes | depth scanlines |
+  // depth samples or metres], every piece on a 16-byte boundary, the scanlines only where the batch brings them
+  const bool rsz = pre && ctx->rsz.armed;
+  const rr_ctx::InputResize R = ctx->rsz;
+  size_t rs_irows = 0, rs_img = 0, rs_drows = 0, rs_dep = 0, rs_frame = 0;
+  if (rsz) {
+    auto r16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    rs_img = rs_irows + ((pre[0].in_types & RR_IN_BG_PNG_ROWS) ? r16((size_t)R.sH * (1 + 3 * (size_t)R.sW)) : 0);
+    rs_drows = rs_img + r16((size_t)R.sH * R.sW * 3);
+    rs_dep = rs_drows + (pre[0].depth_f64 == RR_DEPTH_PNG_ROWS ? r16((size_t)R.dH * (1 + 2 * (size_t)R.dW)) : 0);
+    rs_frame = rs_dep + r16((size_t)R.dH * R.dW * 4);
+    if ((size_t)n * rs_frame > sl.src_cap) {
+      HIPCHK(hipDeviceSynchronize());
+      sl.src_cap = 0;
+      if ((rc = dev_alloc(ctx, sl.d_src, (size_t)n * rs_frame))) return rc;
+      sl.src_cap = (size_t)n * rs_frame;
+    }
+  }
   // ---- upload ----
-  for (int f = 0; pre && f < n; f++) {
+  for (int f = 0; rsz && f < n; f++) {
+    pin[f] = pre[f];
+    uint8_t* const fs = sl.d_src + (size_t)f * rs_frame;
+    const void* src = pre[f].bg_u8 ? (const void*)pre[f].bg_u8 : pre[f].bg;
+    if (pre[f].in_types & RR_IN_BG_PNG_ROWS) up.add(fs + rs_irows, src, (size_t)R.sH * (1 + 3 * (size_t)R.sW));
+    else up.add(fs + rs_img, src, (size_t)R.sH * R.sW * 3);
+    if (pre[f].depth_f64 == RR_DEPTH_PNG_ROWS) up.add(fs + rs_drows, pre[f].depth, (size_t)R.dH * (1 + 2 * (size_t)R.dW));
+    else up.add(fs + rs_dep, pre[f].depth, (size_t)R.dH * R.dW * (pre[f].depth_f64 == RR_DEPTH_U16 ? 2 : 4));
+    // behind the stage the frame is the float64-image route: float64 B G R image, float32 metres
+    pin[f].in_types = 0;
+    pin[f].bg = st.bg + f * T.px3d;
+    pin[f].bg_u8 = nullptr;
+    pin[f].depth = depth_at(f);
+    pin[f].depth_f64 = 0;
+    pout[f].out_types = pre_types;
+    pout[f].reserved = 0;
+    pout[f].rainy_bg = st.rainy + f * T.px3d;
+    const bool env = in || pre_out[f].env_xyY || pre_out[f].env_bgr_u8;
+    pout[f].env_xyY = env ? st.env + f * T.ex3d : nullptr;
+    pout[f].env_bgr_u8 = (pre_out && pre_out[f].env_bgr_u8) ? st.env_u8 + f * T.ex3b : nullptr;
+  }
+  for (int f = 0; pre && !rsz && f < n; f++) {
     pin[f] = pre[f];
     // the image in the caller's element type: bytes stay bytes (bg = bytes / 255.0 is formed where a kernel reads it)
     const void* src = pre[f].bg_u8 ? (const void*)pre[f].bg_u8 : pre[f].bg;
@@ -8305,12 +8574,13 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     din[f].omega = !in[f].omega ? nullptr : (same_omega ? din[0].omega : st.omega + f * T.exd);
     din[f].drops = st.drops + (size_t)f * drop_stride;
     if (pre) {                        // the pre-pass' depth buffer doubles as the occlusion depth
-      if (pre[f].depth_f64 >= RR_DEPTH_U16 && ctx->depth_occlusion) {
+      // (pin: behind rr_set_input_resize every kind of depth input has become a float32 map)
+      if (pin[f].depth_f64 >= RR_DEPTH_U16 && ctx->depth_occlusion) {
         ctx->err = "RR_OPT_DEPTH_OCCLUSION needs a float depth map (not RR_DEPTH_U16 / RR_DEPTH_PNG_ROWS)";
         return RR_E_ARG;
       }
-      din[f].depth = pre[f].depth_f64 >= RR_DEPTH_U16 ? nullptr : depth_at(f);
-      din[f].depth_f64 = pre[f].depth_f64 == 1 ? 1 : 0;
+      din[f].depth = pin[f].depth_f64 >= RR_DEPTH_U16 ? nullptr : depth_at(f);
+      din[f].depth_f64 = pin[f].depth_f64 == 1 ? 1 : 0;
     } else if (in[f].depth && ctx->depth_occlusion) {
       up.add((void*)depth_at(f), in[f].depth, px * (in[f].depth_f64 ? 8 : 4));
       din[f].depth = depth_at(f);
@@ -8397,7 +8667,23 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     return drained(RR_E_HIP);
   }
   // ---- compute ----
-  if (pre && ((pre[0].in_types & RR_IN_BG_PNG_ROWS) || pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)) {
+  if (rsz) {                          // the input stage at the source size: un-filter, then the resize to the render size
+    if ((pre[0].in_types & RR_IN_BG_PNG_ROWS) || pre[0].depth_f64 == RR_DEPTH_PNG_ROWS) {
+      ProfScope ps(ctx, s, "k_png_unfilter");
+      if (pre[0].in_types & RR_IN_BG_PNG_ROWS)
+        hipLaunchKernelGGL(k_png_unfilter<3>, dim3(n), dim3(64), 3 * (size_t)R.sW, s, sl.d_src + rs_irows, (int64_t)rs_frame, sl.d_src + rs_img,
+                           (int64_t)rs_frame, R.sH, R.sW);
+      if (pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)
+        hipLaunchKernelGGL(k_png_unfilter<2>, dim3(n), dim3(64), 2 * (size_t)R.dW, s, sl.d_src + rs_drows, (int64_t)rs_frame, sl.d_src + rs_dep,
+                           (int64_t)rs_frame, R.dH, R.dW);
+    }
+    const uint8_t* const hi = sl.d_src + (size_t)n * rs_frame;
+    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, RSZ_BGR8, sl.d_src + rs_img, (int64_t)rs_frame, sl.d_src, hi, st.bg, (int64_t)(T.px3d * 8), s)))
+      return drained(rc);
+    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, pre[0].depth_f64 == 0 ? RSZ_DF32 : RSZ_D16, sl.d_src + rs_dep, (int64_t)rs_frame, sl.d_src, hi,
+                             st.depth, (int64_t)depth_stride, s)))
+      return drained(rc);
+  } else if (pre && ((pre[0].in_types & RR_IN_BG_PNG_ROWS) || pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)) {
     ProfScope ps(ctx, s, "k_png_unfilter");
     if (pre[0].in_types & RR_IN_BG_PNG_ROWS)
       hipLaunchKernelGGL(k_png_unfilter<3>, dim3(n), dim3(64), 3 * (size_t)dm.W, s, reinterpret_cast<const uint8_t*>(st.rainy), (int64_t)(T.px3d * 8),
@@ -8516,9 +8802,17 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   }
   const size_t px = (size_t)H * W, el = b->dtype == RR_TENSOR_F32 ? 4 : 1;
   auto rnd = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t s_bg = rnd(px * 3 * el), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
-  const size_t b_drops = rnd((size_t)n * cap * sizeof(rr_drop)), b_counts = rnd((size_t)n * 4);
-  const size_t need = (size_t)n * (s_bg + s_rainy + s_env + s_mask) + b_drops + b_counts;
+  // rr_set_input_resize: images and depth arrive at the armed sizes; the stage makes the float64 image (and, where the depth map
+  // has another size than the frame, the float32 map) of the render size in the scratch
+  const rr_ctx::InputResize R = ctx->rsz;
+  const bool rsz = R.armed, rsz_depth = rsz && (R.dH != H || R.dW != W);
+  if (rsz && el == 4 && (reinterpret_cast<uintptr_t>(b->images) & 3u)) {
+    ctx->err = "rr_augment_frames_device: misaligned float32 images";
+    return RR_E_ARG;
+  }
+  const size_t s_bg = rnd(px * 3 * (rsz ? 8 : el)), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
+  const size_t b_drops = rnd((size_t)n * cap * sizeof(rr_drop)), b_counts = rnd((size_t)n * 4), s_dep = rsz_depth ? rnd(px * 4) : 0;
+  const size_t need = (size_t)n * (s_bg + s_rainy + s_env + s_mask + s_dep) + b_drops + b_counts;
   if (need > ctx->aug_bytes) {
     HIPCHK(hipDeviceSynchronize());
     if (ctx->d_aug) HIPCHK(hipFree(ctx->d_aug));
@@ -8533,7 +8827,8 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   char* const mask = env + (size_t)n * s_env;
   rr_drop* const drops = reinterpret_cast<rr_drop*>(mask + (size_t)n * s_mask);
   int32_t* const counts = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(drops) + b_drops);
-  const int bg_type = b->dtype == RR_TENSOR_F32 ? RR_IN_BG_F32 : RR_IN_BG_U8;
+  char* const dep = reinterpret_cast<char*>(counts) + b_counts;
+  const int bg_type = rsz ? 0 : (b->dtype == RR_TENSOR_F32 ? RR_IN_BG_F32 : RR_IN_BG_U8);
   // the descriptors rr_pipeline_frames builds for the same frames by default: float32 hand-over, resident solid angles
   std::vector<rr_prepass_in> pin(n);
   std::vector<rr_prepass_out> pout(n);
@@ -8545,7 +8840,7 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
     p.H = H;
     p.W = W;
     p.bg = bg + (size_t)f * s_bg;
-    p.depth = b->depth + (size_t)f * px;
+    p.depth = rsz_depth ? reinterpret_cast<const float*>(dep + (size_t)f * s_dep) : b->depth + (size_t)f * px;
     p.depth_f64 = 0;
     p.mode = 0;
     p.beta_ext = b->fog[4 * f + 0];
@@ -8584,7 +8879,15 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   for (int attempt = 0;; attempt++) {
     int rc;
     if ((rc = enqueue_particles(ctx, n, b->sims, H, W, drops, cap, counts, s))) return rc;
-    {
+    if (rsz) {
+      const int64_t fb = (int64_t)R.sH * R.sW * 3 * (int64_t)el, db = (int64_t)R.dH * R.dW * 4;
+      if ((rc = enqueue_resize(ctx, n, H, W, el == 4 ? RSZ_RGBF32P : RSZ_RGB8P, b->images, fb, b->images, static_cast<const char*>(b->images) + n * fb,
+                               bg, (int64_t)s_bg, s)))
+        return rc;
+      if (rsz_depth && (rc = enqueue_resize(ctx, n, H, W, RSZ_DF32, b->depth, db, b->depth, reinterpret_cast<const char*>(b->depth) + n * db, dep,
+                                            (int64_t)s_dep, s)))
+        return rc;
+    } else {
       ProfScope ps(ctx, s, "k_planar_in");
       if (el == 1) {
         const int64_t lanes = ((int64_t)px + 15) / 16;
@@ -8851,6 +9154,48 @@ int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   const int rc = augment(ctx, b, s);
   if (rc) (void)hipStreamSynchronize(s);        // (nothing of a failed call may keep writing the caller's tensors)
+  return rc;
+}
+
+int rr_set_input_resize(rr_ctx* ctx, int32_t src_H, int32_t src_W, int32_t depth_H, int32_t depth_W) {
+  if (!ctx) return RR_E_ARG;
+  for (const rr_ctx::Slot& sl : ctx->slots)
+    if (sl.busy) {
+      ctx->err = "rr_set_input_resize: a pipeline slot is still in flight: call rr_pipeline_wait first";
+      return RR_E_STATE;
+    }
+  if (src_H == 0 && src_W == 0 && depth_H == 0 && depth_W == 0) {
+    ctx->rsz = rr_ctx::InputResize{};
+    return RR_OK;
+  }
+  for (int32_t v : {src_H, src_W, depth_H, depth_W})
+    if (v <= 0 || v > rrresize::MAX_SIDE) {
+      ctx->err = "rr_set_input_resize: every side in [1, 16384], or all four 0 (off)";
+      return RR_E_ARG;
+    }
+  ctx->rsz.armed = true;
+  ctx->rsz.sH = src_H;
+  ctx->rsz.sW = src_W;
+  ctx->rsz.dH = depth_H;
+  ctx->rsz.dW = depth_W;
+  return RR_OK;
+}
+
+int rr_resize_inputs_device(rr_ctx* ctx, int32_t n, int32_t H, int32_t W, const void* images, int32_t image_kind, const void* depth,
+                            int32_t depth_kind, double* bg_out, float* depth_out, void* stream) {
+  if (!ctx) return RR_E_ARG;
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  struct Restore {
+    int d;
+    ~Restore() {
+      if (d >= 0) (void)hipSetDevice(d);
+    }
+  } restore{prev};
+  HIPCHK(hipSetDevice(ctx->device));
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const int rc = resize_inputs(ctx, n, H, W, images, image_kind, depth, depth_kind, bg_out, depth_out, s);
+  if (rc || !stream) (void)hipStreamSynchronize(s);      // (NULL: the caller has no handle to order later work behind the context's stream)
   return rc;
 }
 

@@ -24,6 +24,7 @@
 
 #include "rainhip.h"
 #include "rr_parallel.h"
+#include "rr_resize.h"
 
 namespace {
 
@@ -1389,7 +1390,7 @@ extern "C" int rr_io_read_frames(int32_t n, const char* const* image_paths, cons
           rc = rr_png_read_gray16_impl(depth_paths[k], d16.data(), H, W);
           if (rc == RR_OK) {
             float* o = reinterpret_cast<float*>(reinterpret_cast<char*>(depth_f32) + (size_t)k * (size_t)depth_stride);
-            for (size_t i = 0; i < (size_t)H * W; i++) o[i] = (float)d16[i] / 256.0f;
+            for (size_t i = 0; i < (size_t)H * W; i++) o[i] = rrresize::depth_metres(d16[i]);
           }
         }
       }
@@ -1473,17 +1474,18 @@ static int read_rows_impl(const char* path, uint8_t* rows, int32_t H, int32_t W,
   return RR_OK;
 }
 
-extern "C" int rr_io_read_frames_rows(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
-                                      uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
-                                      int32_t* status) {
-  if (n < 0 || H <= 0 || W <= 0 || !status || (n > 0 && (!image_paths || !image_rows)) || (depth_paths && !depth_rows) ||
-      image_stride < (int64_t)H * (1 + 3 * (int64_t)W) || (depth_paths && depth_stride < (int64_t)H * (1 + 2 * (int64_t)W)))
+// (the depth files dH x dW: their own size where the device resizes the inputs, rr_set_input_resize)
+static int read_frames_rows(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W, int32_t dH, int32_t dW,
+                            uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
+                            int32_t* status) {
+  if (n < 0 || H <= 0 || W <= 0 || dH <= 0 || dW <= 0 || !status || (n > 0 && (!image_paths || !image_rows)) || (depth_paths && !depth_rows) ||
+      image_stride < (int64_t)H * (1 + 3 * (int64_t)W) || (depth_paths && depth_stride < (int64_t)dH * (1 + 2 * (int64_t)dW)))
     return RR_E_ARG;
   rrpar::parallel_for(n, threads, [&](int k) {
     int rc;
     try {
       rc = image_paths[k] ? read_rows_impl(image_paths[k], image_rows + (size_t)k * (size_t)image_stride, H, W, 3) : RR_E_ARG;
-      if (rc == RR_OK && depth_paths) rc = depth_paths[k] ? read_rows_impl(depth_paths[k], depth_rows + (size_t)k * (size_t)depth_stride, H, W, 2) : RR_E_ARG;
+      if (rc == RR_OK && depth_paths) rc = depth_paths[k] ? read_rows_impl(depth_paths[k], depth_rows + (size_t)k * (size_t)depth_stride, dH, dW, 2) : RR_E_ARG;
     } catch (...) {
       rc = RR_E_PARSE;
     }
@@ -1492,32 +1494,33 @@ extern "C" int rr_io_read_frames_rows(int32_t n, const char* const* image_paths,
   return RR_OK;
 }
 
+extern "C" int rr_io_read_frames_rows(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
+                                      uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
+                                      int32_t* status) {
+  return read_frames_rows(n, image_paths, depth_paths, H, W, H, W, image_rows, image_stride, depth_rows, depth_stride, threads, status);
+}
+
+extern "C" int rr_io_read_frames_rows_sized(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
+                                            int32_t depth_H, int32_t depth_W, uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows,
+                                            int64_t depth_stride, int32_t threads, int32_t* status) {
+  return read_frames_rows(n, image_paths, depth_paths, H, W, depth_H, depth_W, image_rows, image_stride, depth_rows, depth_stride, threads, status);
+}
+
+// The resize tables of one axis and one output sample: csrc/rr_resize.h states both (the device's input stage reads the same header)
 static void linear_coords(int d, int s, std::vector<int32_t>& i0, std::vector<int32_t>& i1, std::vector<double>& w) {
   at_least(i0, (size_t)d);
   at_least(i1, (size_t)d);
   at_least(w, (size_t)d);
-  const double scale = (double)s / (double)d;
-  for (int k = 0; k < d; k++) {
-    const double f = ((double)k + 0.5) * scale - 0.5;
-    const double fl = std::floor(f);
-    const int64_t a = (int64_t)fl;
-    w[(size_t)k] = a < 0 ? 0.0 : f - fl;
-    const int64_t b = a + 1;
-    i0[(size_t)k] = (int32_t)(a < 0 ? 0 : (a > s - 1 ? s - 1 : a));
-    i1[(size_t)k] = (int32_t)(b < 0 ? 0 : (b > s - 1 ? s - 1 : b));
-  }
+  const double scale = rrresize::resize_scale(d, s);
+  for (int k = 0; k < d; k++) rrresize::resize_coord(k, s, scale, i0[(size_t)k], i1[(size_t)k], w[(size_t)k]);
 }
-// ... and one output sample: (a00 * (1 - wx) + a01 * wx) * (1 - wy) + (a10 * (1 - wx) + a11 * wx) * wy, the products and sums
-// in numpy's order
 static inline double bilinear(double a00, double a01, double a10, double a11, double wx, double wy) {
-  const double ux = 1 - wx, uy = 1 - wy;
-  const double top = a00 * ux + a01 * wx, bot = a10 * ux + a11 * wx;
-  return top * uy + bot * wy;
+  return rrresize::resize_sample(a00, a01, a10, a11, wx, wy);
 }
 struct UnitLut {                                       // byte / 255.0 (generator.py:352), as numpy divides
   double v[256];
   UnitLut() {
-    for (int i = 0; i < 256; i++) v[i] = (double)i / 255.0;
+    for (int i = 0; i < 256; i++) v[i] = rrresize::image_unit((uint8_t)i);
   }
 };
 
@@ -1589,11 +1592,11 @@ extern "C" int rr_io_read_frames_scaled(int32_t n, const char* const* image_path
         }
         float* o = reinterpret_cast<float*>(reinterpret_cast<char*>(depth_f32) + (size_t)k * (size_t)depth_stride);
         if (dh == H && dw == W) {
-          for (size_t i = 0; i < (size_t)H * W; i++) o[i] = (float)d16[i] / 256.0f;
+          for (size_t i = 0; i < (size_t)H * W; i++) o[i] = rrresize::depth_metres(d16[i]);
         } else {                                       // cv2.resize keeps float32: float64 inside resize_linear, rounded once
           linear_coords(H, dh, sc->y0, sc->y1, sc->wy);
           linear_coords(W, dw, sc->x0, sc->x1, sc->wx);
-          auto m = [&](size_t idx) { return (double)((float)d16[idx] / 256.0f); };
+          auto m = [&](size_t idx) { return (double)rrresize::depth_metres(d16[idx]); };
           for (int y = 0; y < H; y++) {
             const size_t r0 = (size_t)sc->y0[(size_t)y] * dw, r1 = (size_t)sc->y1[(size_t)y] * dw;
             const double wy = sc->wy[(size_t)y];

@@ -45,6 +45,7 @@ RR_DRAWS_STREAM, RR_DRAWS_COUNTER = 0, 1                              # rr_set_p
 PARTICLE_DRAWS = {'stream': RR_DRAWS_STREAM, 'counter': RR_DRAWS_COUNTER}
 RR_MAX_VIEWS = 8
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
+RR_RESIZE_BGR_U8, RR_RESIZE_RGB_U8_PLANAR, RR_RESIZE_RGB_F32_PLANAR = 0, 1, 2   # rr_resize_inputs_device: image_kind
 RR_IN_BG_PNG_ROWS, RR_DEPTH_PNG_ROWS = 32, 3              # a file's filtered scanlines (rr_io_read_frames_rows): un-filtered on the device
 RR_DEPTH_U16 = 2                                        # rr_prepass_in.depth_f64: the uint16 samples of the depth file (metres = sample / 256)
 RR_IN_BG_F32, RR_IN_BG_U8, RR_IN_ENV_F32, RR_IN_RAINY_F32, RR_IN_RAINY_U8 = 1, 2, 4, 8, 16      # rr_frame_in.in_types
@@ -176,11 +177,11 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_pipeline_submit', 'rr_pipeline_wait', 'rr_host_alloc', 'rr_host_last_error', 'rr_host_free', 'rr_bcast_streak_db', 'rr_bcast_selftest', 'rr_host_parse_particles',
            'rr_sizeof_particle', 'rr_sizeof_particle_frame', 'rr_set_colormap', 'rr_host_frame_draws', 'rr_host_assemble_drops',
            'rr_sizeof_streak_table', 'rr_png_info', 'rr_png_read_bgr8', 'rr_png_read_gray16', 'rr_png_write_scanlines',
-           'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
+           'rr_deflate_bound', 'rr_deflate_fast', 'rr_inflate_fast', 'rr_adler32', 'rr_crc32', 'rr_host_pack_frames', 'rr_io_read_frames', 'rr_io_read_frames_u16', 'rr_io_read_frames_rows', 'rr_io_read_frames_rows_sized', 'rr_io_read_frames_scaled', 'rr_io_write_frames', 'rr_set_particle_tables', 'rr_generate_drops_device', 'rr_generate_drops', 'rr_set_solid_angles',
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
-           'rr_sizeof_pipeline_lens']
+           'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device']
 
 _lib = None
 
@@ -256,6 +257,7 @@ def load_library(path=None):
                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_io_read_frames_u16.argtypes = lib.rr_io_read_frames.argtypes
     lib.rr_io_read_frames_rows.argtypes = lib.rr_io_read_frames.argtypes
+    lib.rr_io_read_frames_rows_sized.argtypes = lib.rr_io_read_frames.argtypes[:5] + [ctypes.c_int32, ctypes.c_int32] + lib.rr_io_read_frames.argtypes[5:]
     lib.rr_io_read_frames_scaled.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_void_p]
@@ -294,6 +296,9 @@ def load_library(path=None):
     assert lib.rr_sizeof_lens_batch() == ctypes.sizeof(rr_lens_batch), (lib.rr_sizeof_lens_batch(), ctypes.sizeof(rr_lens_batch))
     lib.rr_pipeline_set_lens.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(rr_pipeline_lens)]
     assert lib.rr_sizeof_pipeline_lens() == ctypes.sizeof(rr_pipeline_lens), (lib.rr_sizeof_pipeline_lens(), ctypes.sizeof(rr_pipeline_lens))
+    lib.rr_set_input_resize.argtypes = [ctypes.c_void_p] + [ctypes.c_int32] * 4
+    lib.rr_resize_inputs_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     assert lib.rr_sizeof_prepass_in() == ctypes.sizeof(rr_prepass_in)
     assert lib.rr_sizeof_prepass_out() == ctypes.sizeof(rr_prepass_out)
     assert lib.rr_sizeof_prepass_kernels() == ctypes.sizeof(rr_prepass_kernels)
@@ -568,18 +573,24 @@ def io_read_frames(image_paths, depth_paths, H, W, bg_block, depth_block, thread
     return status
 
 
-def io_read_frames_rows(image_paths, depth_paths, H, W, image_rows_block, depth_rows_block, threads=0):
+def io_read_frames_rows(image_paths, depth_paths, H, W, image_rows_block, depth_rows_block, threads=0, depth_shape=None):
     """rr_io_read_frames_rows: both files of every frame inflated only -- image_rows_block[k] receives the H rows of 1 + 3 W
     bytes (filter type + filtered R G B bytes) of frame k's image, depth_rows_block[k] the H rows of 1 + 2 W bytes of its
-    16-bit depth file (rr_prepass_in: RR_IN_BG_PNG_ROWS / RR_DEPTH_PNG_ROWS; the filters are reversed on the device)."""
+    16-bit depth file (rr_prepass_in: RR_IN_BG_PNG_ROWS / RR_DEPTH_PNG_ROWS; the filters are reversed on the device).
+    depth_shape = (dH, dW): depth files of their own size (rr_io_read_frames_rows_sized; a context armed with set_input_resize)."""
     lib = load_library()
     n = len(image_paths)
     ip, k1 = _c_paths(image_paths)
     dp, k2 = _c_paths(depth_paths)
     status = np.zeros(n, np.int32)
     assert image_rows_block.dtype == np.uint8 and depth_rows_block.dtype == np.uint8 and image_rows_block.shape[0] >= n and depth_rows_block.shape[0] >= n
-    rc = lib.rr_io_read_frames_rows(n, ip, dp, int(H), int(W), _ptr(image_rows_block), int(image_rows_block.strides[0]), _ptr(depth_rows_block),
-                                    int(depth_rows_block.strides[0]), int(threads), _ptr(status))
+    if depth_shape is not None:
+        rc = lib.rr_io_read_frames_rows_sized(n, ip, dp, int(H), int(W), int(depth_shape[0]), int(depth_shape[1]), _ptr(image_rows_block),
+                                              int(image_rows_block.strides[0]), _ptr(depth_rows_block), int(depth_rows_block.strides[0]),
+                                              int(threads), _ptr(status))
+    else:
+        rc = lib.rr_io_read_frames_rows(n, ip, dp, int(H), int(W), _ptr(image_rows_block), int(image_rows_block.strides[0]), _ptr(depth_rows_block),
+                                        int(depth_rows_block.strides[0]), int(threads), _ptr(status))
     if rc != 0:
         raise RuntimeError("rr_io_read_frames_rows failed (%d)" % rc)
     return status
@@ -1116,7 +1127,8 @@ class RainHip:
     @staticmethod
     def _fill_prepass(pin, fr, keep):
         """fr['bg']: the image / 255 as float64 (or float32: taken as it is, rr_prepass_in.in_types), or fr['bg_u8'] = the
-        uint8 BGR image (bg = bg_u8 / 255.0 is formed on the device)."""
+        uint8 BGR image (bg = bg_u8 / 255.0 is formed on the device).  fr['render_shape'] = (H, W), for a context armed with
+        set_input_resize: the descriptor's size; the arrays have the armed sizes (PNG rows: 'shape' / 'depth_shape' name theirs)."""
         if fr.get('bg_png_rows') is not None:              # H rows of 1 + 3 W bytes: an 8-bit RGB PNG inflated, not un-filtered; 'shape' = (H, W)
             rows = np.ascontiguousarray(fr['bg_png_rows'], np.uint8).reshape(-1)
             H, W = fr['shape']
@@ -1132,16 +1144,23 @@ class RainHip:
             bg = np.ascontiguousarray(bg, np.float32 if bg.dtype == np.float32 else np.float64)
             pin.bg, pin.bg_u8, pin.in_types = _ptr(bg), None, RR_IN_BG_F32 if bg.dtype == np.float32 else 0
         H, W = bg.shape[:2]
+        render = fr.get('render_shape')
+        dH, dW = (H, W) if render is None else fr.get('depth_shape', np.shape(fr['depth']) if fr.get('depth_png_rows') is None else (H, W))
         if fr.get('depth_png_rows') is not None:            # H rows of 1 + 2 W bytes: the 16-bit depth PNG inflated, not un-filtered
             depth = np.ascontiguousarray(fr['depth_png_rows'], np.uint8).reshape(-1)
-            assert depth.size == H * (1 + 2 * W), (depth.size, H, W)
-            pin.H, pin.W, pin.depth, pin.depth_f64 = H, W, _ptr(depth), RR_DEPTH_PNG_ROWS
+            assert depth.size == dH * (1 + 2 * dW), (depth.size, dH, dW)
+            pin.depth, pin.depth_f64 = _ptr(depth), RR_DEPTH_PNG_ROWS
         else:
             depth = np.asarray(fr['depth'])                    # float32 / float64 metres, or the uint16 samples of the depth file
             depth = np.ascontiguousarray(depth, depth.dtype if depth.dtype in (np.float32, np.uint16) else np.float64)
-            assert bg.shape == (H, W, 3) and depth.shape == (H, W), (bg.shape, depth.shape)
-            pin.H, pin.W, pin.depth = H, W, _ptr(depth)
+            assert bg.shape == (H, W, 3) and depth.shape == (dH, dW), (bg.shape, depth.shape)
+            pin.depth = _ptr(depth)
             pin.depth_f64 = 1 if depth.dtype == np.float64 else (RR_DEPTH_U16 if depth.dtype == np.uint16 else 0)
+        if render is not None:
+            keep.append(bg)
+            H, W = int(render[0]), int(render[1])
+            bg = np.empty((H, W, 3), np.uint8)               # (only its shape is used by the callers)
+        pin.H, pin.W = H, W
         pin.beta_ext, pin.beta_hg, pin.irr_num, pin.irr_den = [float(v) for v in fr['fog']]
         keep.append((bg, depth))
         return bg
@@ -1242,6 +1261,46 @@ class RainHip:
         """fin/fout: ctypes arrays of rr_frame_in/out holding DEVICE pointers."""
         rc = self.lib.rr_render_frames_device(self.h, n, fin, fout, ctypes.c_void_p(stream) if stream else None)
         self._check(rc, 'rr_render_frames_device')
+
+    def set_input_resize(self, src_h=0, src_w=0, depth_h=0, depth_w=0):
+        """rr_set_input_resize: from now on the pipeline / pre-pass entry points (host pointers) and augment_frames_device take
+        src_h x src_w images and depth_h x depth_w depth maps and resize them on the device to the descriptors' H x W (the render
+        size) -- the cv2.resize of the reference's frame loader, bit for bit (csrc/rr_resize.h).  All zero: off."""
+        self._check(self.lib.rr_set_input_resize(self.h, int(src_h), int(src_w), int(depth_h), int(depth_w)), 'rr_set_input_resize')
+
+    def resize_inputs(self, H, W, images=None, depth=None, planar=False):
+        """rr_resize_inputs_device on numpy arrays (uploaded and downloaded here; a caller with device arrays uses the C entry point):
+        images [n, sH, sW, 3] uint8 B G R -- or, planar, [n, 3, sH, sW] R G B uint8 / float32 -- and depth [n, dH, dW] uint16 samples or
+        float32 metres, at the sizes of set_input_resize.  The arrays travel through torch tensors (a process that uses this imports torch
+        before it loads the library, as augment.py does: torch brings its own HIP runtime).  Returns (bg [n, H, W, 3] float64 B G R | None, depth [n, H, W] float32 | None)."""
+        import torch
+        dev = torch.device('cuda', self.device)
+        n = len(images) if images is not None else len(depth)
+        t_img = t_dep = t_bg = t_out = None
+        ik = dk = 0
+        if images is not None:
+            images = np.array(images, order='C')          # (a copy: torch wants writable memory)
+            if planar and images.dtype == np.float32:
+                ik = RR_RESIZE_RGB_F32_PLANAR
+            elif images.dtype == np.uint8:
+                ik = RR_RESIZE_RGB_U8_PLANAR if planar else RR_RESIZE_BGR_U8
+            else:
+                raise ValueError("images: uint8 (interleaved B G R or planar R G B) or planar float32, got %s" % images.dtype)
+            t_img = torch.from_numpy(images.view(np.uint8).reshape(-1)).to(dev)
+            t_bg = torch.empty((n, H, W, 3), dtype=torch.float64, device=dev)
+        if depth is not None:
+            depth = np.array(depth, order='C')
+            if depth.dtype not in (np.uint16, np.float32):
+                raise ValueError("depth: uint16 samples or float32 metres, got %s" % depth.dtype)
+            dk = RR_DEPTH_U16 if depth.dtype == np.uint16 else 0
+            t_dep = torch.from_numpy(depth.view(np.uint8).reshape(-1)).to(dev)
+            t_out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        rc = self.lib.rr_resize_inputs_device(self.h, n, int(H), int(W), t_img.data_ptr() if t_img is not None else None, ik,
+                                              t_dep.data_ptr() if t_dep is not None else None, dk,
+                                              t_bg.data_ptr() if t_bg is not None else None, t_out.data_ptr() if t_out is not None else None, None)
+        self._check(rc, 'rr_resize_inputs_device')
+        return (t_bg.cpu().numpy() if t_bg is not None else None, t_out.cpu().numpy() if t_out is not None else None)
 
     def augment_frames_device(self, batch, stream=None):
         """rr_augment_frames_device: `batch` an rr_tensor_batch (device pointers for the tensors, host pointers for the records

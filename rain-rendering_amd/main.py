@@ -107,6 +107,11 @@ _FLAGS = [
                                   "--rig_view's own lens).  The rain mask does not show them")),
     (('--lens_alpha',), dict(action='store_true', help="with --lens_drops: also write <out_dir>/lens_alpha/<name>.png, the per-pixel "
                                                        "coverage of the drops on the lens as a grey level (0: no drop, 255: all drop)")),
+    (('--device_resize',), dict(action='store_true',
+                               help="resize full-size frames on the GPU: where a dataset renders at a fraction of its files' resolution "
+                                    "(render_scale / depth_scale other than 1) the batch-native route uploads the files' own scanlines and the "
+                                    "library resizes image and depth map on the device (rr_set_input_resize) instead of on the host; the "
+                                    "output files are the same, byte for byte.  Without a resize to do the flag changes nothing")),
     (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
                                                      "camera folder with the same seed gives a coherent set")),
 ]
