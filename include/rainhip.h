@@ -581,30 +581,44 @@ int rr_set_particle_rate_series(rr_ctx* ctx, int32_t n, uint32_t frame0, const d
  * [n][3][H][W], bytes or float32 in [0, 1]) -- rain-rendering_amd/augment.py RainAugment.  One call enqueues on `stream`
  * (NULL = the ctx stream)
  *     particles (rr_generate_drops_device semantics: tables and counts stay on the device)
- *  -> ingest (k_planar_in: planar RGB -> the interleaved BGR image, RR_IN_BG_U8 / RR_IN_BG_F32; values moved, not converted)
+ *  -> ingest (k_planar_in, or k_tensor_in for the formats behind planar bytes and float32: the caller's RGB -> the interleaved
+ *     BGR image, RR_IN_BG_U8 / RR_IN_BG_F32; values moved, a float16 / bfloat16 element widened to the float32 it equals exactly,
+ *     subnormals included)
  *  -> pre-pass (fog layer + xyY map handed over as float32, the resident solid angles: rr_pipeline_frames' defaults)
- *  -> hot path -> planar finalize (k_finalize_planar: rainy_out in the images' layout and dtype, mask_out = float(mask_f64))
+ *  -> hot path -> finalize (k_finalize_planar: rainy_out in the images' layout and dtype, mask_out = float(mask_f64))
  * and then waits on `stream` for the 4-byte arena-overflow flag: when the tile arena had to grow, the batch is enqueued once more.
  * So the call returns after the batch is complete -- a host wait on the caller's stream.  For the same records and input values
  * the result is bit for bit what rr_pipeline_frames gives: rainy_out bytes == rainy_rgb (planar), float32 rainy_out == those
- * bytes / 255.0f (what ToTensor makes of the PNG the driver writes).  Not offered: angular noise (run_pos must be 0; the streak
- * jitter of rr_set_particle_jitter is), the 'white' strategy, opacity attenuation.  Needs the streak database, camera, pre-pass kernels, particle tables, the envmap geometry of
+ * bytes / 255.0f (what ToTensor makes of the PNG the driver writes), float16 / bfloat16 rainy_out == that float32 rounded once to the
+ * half type, to nearest, ties to even (csrc/rr_convert.h).  layout (RR_LAYOUT_*) only moves values: the interleaved result of a
+ * batch is, element for element, the planar result of the same values, and mask_out depends on neither dtype nor layout.  All eight
+ * (dtype, layout) pairs work with and without an armed rr_set_input_resize (the half types feed (double)value, as float32 does).
+ * RR_E_ARG, with nothing enqueued: a dtype outside {RR_TENSOR_U8, RR_TENSOR_F32, RR_TENSOR_F16, RR_TENSOR_BF16}, a layout outside
+ * {RR_LAYOUT_PLANAR, RR_LAYOUT_INTERLEAVED}, images or rainy_out not aligned to the element size.
+ * Not offered: angular noise (run_pos must be 0; the streak jitter of rr_set_particle_jitter is), the 'white' strategy, opacity attenuation.  Needs the streak database, camera, pre-pass kernels, particle tables, the envmap geometry of
  * H x W and the solid angles of the H x rr_envmap_width() map (rr_set_solid_angles).  The caller's current device is restored.
  * Scratch in the context, grown to the largest batch seen and never shrunk, per frame about
- *     3 H W (bytes; 12 H W for float32) + 12 H W (fog layer) + 12 H We (map) + 8 H W (mask) + 112 drops_cap  bytes
+ *     3 H W (bytes; 12 H W for float32, float16 and bfloat16, which ingest into the float32 image; 24 H W for any dtype while
+ *     rr_set_input_resize is armed, plus 4 H W where the depth map is resized)
+ *     + 12 H W (fog layer) + 12 H We (map) + 8 H W (mask) + 112 drops_cap  bytes
  * (KITTI 1242 x 375 with bytes: about 23 MB per frame) on top of the hot path's own per-batch scratch. */
 enum { RR_TENSOR_U8 = 0, RR_TENSOR_F32 = 1,
-       RR_TENSOR_U8_HWC = 3 };           /* interleaved bytes [n,H,W,3]: rr_lens_batch.dtype only (rr_augment_frames_device refuses it).
+       RR_TENSOR_U8_HWC = 3,             /* interleaved bytes [n,H,W,3]: rr_lens_batch.dtype only (rr_augment_frames_device refuses it:
+                                          * there the layout is rr_tensor_batch.layout).
                                           * 2 names no layout and stays refused everywhere, as it was before this layout existed */
+       RR_TENSOR_F16 = 4,                /* IEEE binary16; rr_tensor_batch.dtype only */
+       RR_TENSOR_BF16 = 5 };             /* bfloat16; rr_tensor_batch.dtype only */
+enum { RR_LAYOUT_PLANAR = 0,             /* [n,3,H,W] */
+       RR_LAYOUT_INTERLEAVED = 1 };      /* [n,H,W,3] RGB: pixel p's channel c at element 3 p + c (a channels-last tensor) */
 typedef struct {
-  int32_t n, H, W, dtype;                /* dtype: RR_TENSOR_*; images and rainy_out share it */
-  const void* images;                    /* DEVICE, [n,3,H,W] planar RGB, contiguous: bytes, or float32 in [0,1] */
+  int32_t n, H, W, dtype;                /* dtype: RR_TENSOR_*; images and rainy_out share it and the layout */
+  const void* images;                    /* DEVICE, RGB in `layout`, contiguous: bytes, or float32 / float16 / bfloat16 in [0,1] */
   const float* depth;                    /* DEVICE, [n,H,W] metres */
   const struct rr_sim_frame* sims;       /* HOST, n records (frame, draw_seed, table, ...) */
   const double* fog;                     /* HOST, n x the four pre-pass constants (beta_ext, beta_hg, irr_num, irr_den) */
   int32_t drops_cap;                     /* drop-table capacity per frame */
-  int32_t reserved;
-  void* rainy_out;                       /* DEVICE, [n,3,H,W] planar RGB, same dtype as images */
+  int32_t layout;                        /* RR_LAYOUT_* (0, what a zeroed struct has always said: planar) */
+  void* rainy_out;                       /* DEVICE, RGB in `layout`, same dtype as images */
   float* mask_out;                       /* DEVICE, [n,H,W]: float32(rainy_mask) */
 } rr_tensor_batch;
 int rr_augment_frames_device(rr_ctx* ctx, const rr_tensor_batch* b, void* stream);

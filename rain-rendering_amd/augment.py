@@ -3,11 +3,14 @@
     aug = RainAugment(dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence='data_object/training')
     rainy, mask = aug(images, depth, intensity=25, frame_index=idx)
 
-`images` is [B, 3, H, W] planar RGB on the GPU, uint8 (torchvision.io.decode_png) or float32 in [0, 1] (ToTensor); `depth` is
+`images` is [B, 3, H, W] RGB on the GPU, uint8 (torchvision.io.decode_png) or float32 in [0, 1] (ToTensor); `depth` is
 [B, H, W] or [B, 1, H, W] float32 metres.  `rainy` comes back like `images` (same dtype and layout), `mask` as float32
-[B, 1, H, W] (rainy_mask).  Image i is rendered as frame frame_index[i] of a `main.py --device_particles` run on that dataset and
-sequence at its intensity: simulated frame f % n_sim, drawn with seed f (generator.py:304-321).  The uint8 result is the RGB of
-the PNG that run writes; the float32 result is that byte / 255, what ToTensor makes of the file.
+[B, 1, H, W] (rainy_mask).  float16 and bfloat16 batches are taken too: a value enters as the float32 it equals, and `rainy` is the
+float32 result rounded once to the batch's dtype.  A channels-last batch (`x.to(memory_format=torch.channels_last)`, or a decoder's
+[B, H, W, 3] frames seen as `.permute(0, 3, 1, 2)`) is read where it lies and `rainy` comes back with the same strides, the same values
+as the planar call; any other striding is made planar-contiguous first and comes back planar.
+Image i is rendered as frame frame_index[i] of a `main.py --device_particles` run on that dataset and sequence at its intensity:
+simulated frame f % n_sim, drawn with seed f (generator.py:304-321).  The uint8 result is the RGB of the PNG that run writes; the float32 result is that byte / 255, what ToTensor makes of the file.
 
 `particle_model='field'` (default 'iid') renders the frames of a `main.py --device_particles --particle_model field` run instead:
 a persistent particle field (tools/particles.py) in which frame f + 1 shows the drops of frame f a little lower and closer.
@@ -126,6 +129,38 @@ def _as_list(v, B, name, kind):
         if kind == 'index' and x != int(x):
             raise TypeError("%s must hold integers, got %r" % (name, x))
     return vals
+
+
+_DTYPES = {torch.uint8: hip_backend.RR_TENSOR_U8, torch.float32: hip_backend.RR_TENSOR_F32,
+           torch.float16: hip_backend.RR_TENSOR_F16, torch.bfloat16: hip_backend.RR_TENSOR_BF16}
+LENS_FORMATS = "uint8 batches (planar or channels-last) and planar float32 batches"
+
+
+def tensor_layout(images):
+    """How the frames [..., 3, H, W] of `images` lie in memory: 'planar' (contiguous), 'interleaved' (a dense NHWC view: channel
+    stride 1, W stride 3, H stride 3 W, the leading dims packed) or None (anything else: the caller makes it planar-contiguous).
+    The stride of a dim of size 1 says nothing and is not looked at."""
+    if images.is_contiguous():
+        return 'planar'
+    shape, stride = tuple(images.shape), tuple(images.stride())
+    H, W = shape[-2], shape[-1]
+    want = {-3: 1, -1: 3, -2: 3 * W}
+    step = 3 * H * W
+    for d in range(-4, -len(shape) - 1, -1):
+        want[d] = step
+        step *= shape[d]
+    if all(shape[d] == 1 or stride[d] == v for d, v in want.items()):
+        return 'interleaved'
+    return None
+
+
+def _empty_like_frames(shape, dtype, device, layout):
+    """An uninitialised [..., 3, H, W] tensor in `layout`."""
+    if layout != 'interleaved':
+        return torch.empty(shape, dtype=dtype, device=device)
+    lead, (H, W) = tuple(shape[:-3]), shape[-2:]
+    nd = len(lead)
+    return torch.empty(lead + (H, W, 3), dtype=dtype, device=device).permute(*range(nd), nd + 2, nd, nd + 1)
 
 
 class RainAugment:
@@ -367,12 +402,12 @@ class RainAugment:
     def _validate(self, images, depth):
         if not isinstance(images, torch.Tensor) or not isinstance(depth, torch.Tensor):
             raise TypeError("images and depth must be torch tensors")
-        if images.dtype not in (torch.uint8, torch.float32):
-            raise TypeError("images must be uint8 or float32, got %s" % images.dtype)
+        if images.dtype not in _DTYPES:
+            raise TypeError("images must be uint8 or float32 (or float16 / bfloat16), got %s" % images.dtype)
         if self.rig is not None:
             V = len(self.views)
             if images.dim() != 5 or images.shape[1] != V or images.shape[2] != 3 or min(images.shape) < 1:
-                raise ValueError("images must be [B, V = %d, 3, H, W] (planar RGB per view), got %s" % (V, tuple(images.shape)))
+                raise ValueError("images must be [B, V = %d, 3, H, W] (RGB per view; the shape, whatever the strides), got %s" % (V, tuple(images.shape)))
             B, _, _, H, W = images.shape
             dH, dW = (H, W) if self.source_size is None else self.depth_size
             if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, V, dH, dW), (B, V, 1, dH, dW)):
@@ -380,12 +415,21 @@ class RainAugment:
                                  ((B, V, dH, dW), depth.dtype, tuple(depth.shape)))
             return B, H, W
         if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1 or images.shape[2] < 1 or images.shape[3] < 1:
-            raise ValueError("images must be [B, 3, H, W] (planar RGB), got %s" % (tuple(images.shape),))
+            raise ValueError("images must be [B, 3, H, W] (RGB; the shape, whatever the strides), got %s" % (tuple(images.shape),))
         B, _, H, W = images.shape
         dH, dW = (H, W) if self.source_size is None else self.depth_size
         if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, dH, dW), (B, 1, dH, dW)):
             raise ValueError("depth must be float32 [B, H, W] or [B, 1, H, W] = %s, got %s %s" % ((B, dH, dW), depth.dtype, tuple(depth.shape)))
         return B, H, W
+
+    def _layout(self, images):
+        """The layout the call reads `images` in: 'interleaved' for a dense NHWC view, else 'planar' (contiguous, or made so).  With
+        lens=, a format the lens pass does not take is a ValueError here, before any GPU work."""
+        layout = tensor_layout(images) or 'planar'
+        if self.lens is not None and (images.dtype in (torch.float16, torch.bfloat16) or
+                                      (images.dtype == torch.float32 and layout == 'interleaved')):
+            raise ValueError("lens= takes %s, got a %s %s batch" % (LENS_FORMATS, layout, images.dtype))
+        return layout
 
     def _check_device(self, images, depth):
         for name, t in (('images', images), ('depth', depth)):
@@ -436,6 +480,7 @@ class RainAugment:
 
     def __call__(self, images, depth, intensity, frame_index):
         B, H, W = self._validate(images, depth)
+        layout = self._layout(images)
         p = self.plan(intensity, frame_index, B)
         fh, fw = int(p['sims'][0]['sensor_h']) // self.render_scale, int(p['sims'][0]['sensor_w']) // self.render_scale
         if (H, W) != ((fh, fw) if self.source_size is None else self.source_size):
@@ -446,18 +491,20 @@ class RainAugment:
         V = None if self.rig is None else len(self.views)
         if V is not None:                                    # the library's batch: V consecutive frames per instant
             B = B * V
-        images = images.reshape(B, 3, H, W).contiguous()
+        if layout == 'planar':                               # (an interleaved batch is read where it lies: B frames of [H, W, 3])
+            images = images.reshape(B, 3, H, W).contiguous()
         depth = depth.reshape((B,) + ((H, W) if self.source_size is None else self.depth_size)).contiguous()
         H, W = fh, fw                                        # from here on: the render size
         with torch.cuda.device(dev):
             hip = self._context(dev, H, W, p['key'], p['d_grid'], p['cdf'], p)
-            rainy = torch.empty((B, 3, H, W), dtype=images.dtype, device=dev)
+            rainy = _empty_like_frames((B, 3, H, W), images.dtype, dev, layout)
             mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
             sims = np.ascontiguousarray(p['sims'])
             fog = np.ascontiguousarray(p['fog'])
             b = hip_backend.rr_tensor_batch()
             b.n, b.H, b.W = B, H, W
-            b.dtype = hip_backend.RR_TENSOR_F32 if images.dtype == torch.float32 else hip_backend.RR_TENSOR_U8
+            b.dtype = _DTYPES[images.dtype]
+            b.layout = hip_backend.RR_LAYOUT_INTERLEAVED if layout == 'interleaved' else hip_backend.RR_LAYOUT_PLANAR
             b.images, b.depth = images.data_ptr(), depth.data_ptr()
             b.sims, b.fog = sims.ctypes.data, fog.ctypes.data
             b.drops_cap = p['drops_cap']
@@ -471,9 +518,10 @@ class RainAugment:
             alpha = None
             if self.lens is not None:            # the drops on the lens refract the rainy image: one more kernel on the same stream
                 idx = [int(f) for f in _as_list(frame_index, B if V is None else B // V, 'frame_index', 'index')]
-                rainy, alpha = _lens_pass(hip, self._lens_tables(idx), self.lens.weights(), rainy, self.return_lens_alpha, stream)
+                rainy, alpha = _lens_pass(hip, self._lens_tables(idx), self.lens.weights(), rainy, self.return_lens_alpha, stream,
+                                          'hwc' if layout == 'interleaved' else 'chw')
         if V is not None:
-            rainy, mask = rainy.reshape(B // V, V, 3, H, W), mask.reshape(B // V, V, 1, H, W)
+            rainy, mask = rainy.unflatten(0, (B // V, V)), mask.reshape(B // V, V, 1, H, W)      # (a view in either layout)
             alpha = None if alpha is None else alpha.reshape(B // V, V, 1, H, W)
         return (rainy, mask, alpha) if self.return_lens_alpha else (rainy, mask)
 
@@ -492,20 +540,22 @@ class RainAugment:
             self._hip = None
 
 
-def _lens_pass(hip, tables, weights, images, want_alpha, stream):
-    """rr_lens_drops_device on the contiguous [n, 3, H, W] tensor `images`, on `stream`: (images with the drops, alpha or None)."""
+def _lens_pass(hip, tables, weights, images, want_alpha, stream, layout='chw'):
+    """rr_lens_drops_device on the [n, 3, H, W] tensor `images` -- contiguous, or with layout='hwc' uint8 in a dense NHWC view -- on
+    `stream`: (images with the drops, in the same layout, alpha or None)."""
     n, _, H, W = images.shape
-    out = torch.empty_like(images)
+    out = _empty_like_frames(images.shape, images.dtype, images.device, 'interleaved' if layout == 'hwc' else 'planar')
     alpha = torch.empty((n, 1, H, W), dtype=torch.float32, device=images.device) if want_alpha else None
     hip.lens_drops_device(images.data_ptr(), out.data_ptr(), n, H, W, images.dtype == torch.float32, tables, weights,
-                          alpha_ptr=None if alpha is None else alpha.data_ptr(), stream=stream.cuda_stream)
+                          alpha_ptr=None if alpha is None else alpha.data_ptr(), stream=stream.cuda_stream, layout=layout)
     return out, alpha
 
 
 class LensAugment:
     """Callable: (images, frame_index) -> images with the drops of `lens` (tools/lens.py LensDrops) on them -- the lens pass of
-    RainAugment(lens=) alone, for drops without streak rain.  `images` is [B, 3, H, W] planar on the GPU, uint8 or float32, H x W the
-    LensDrops'; image i wears `lens.table(frame_index[i])`.  return_alpha=True: (images, alpha), alpha float32 [B, 1, H, W], the
+    RainAugment(lens=) alone, for drops without streak rain.  `images` is [B, 3, H, W] on the GPU, uint8 or float32, H x W the
+    LensDrops' (a uint8 channels-last batch is read where it lies and comes back channels-last; any other striding is made planar first);
+    image i wears `lens.table(frame_index[i])`.  return_alpha=True: (images, alpha), alpha float32 [B, 1, H, W], the
     drops' coverage.  Enqueued on the caller's current stream; on the legacy default stream the call waits for the result."""
 
     def __init__(self, lens, device=None, return_alpha=False):
@@ -527,7 +577,7 @@ class LensAugment:
         if images.dtype not in (torch.uint8, torch.float32):
             raise TypeError("images must be uint8 or float32, got %s" % images.dtype)
         if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
-            raise ValueError("images must be [B, 3, H, W] (planar), got %s" % (tuple(images.shape),))
+            raise ValueError("images must be [B, 3, H, W] (the shape, whatever the strides), got %s" % (tuple(images.shape),))
         B, _, H, W = images.shape
         if (H, W) != (self.lens.H, self.lens.W):
             raise ValueError("the LensDrops are for %d x %d frames (H x W), the images are %d x %d" % (self.lens.H, self.lens.W, H, W))
@@ -546,7 +596,10 @@ class LensAugment:
             stream = torch.cuda.current_stream(dev)
             if not stream.cuda_stream:           # handle 0 is "the context's own stream" to the library: finish the inputs first
                 stream.synchronize()
-            out, alpha = _lens_pass(self._hip, tables, self.lens.weights(), images.contiguous(), self.return_alpha, stream)
+            if images.dtype == torch.uint8 and tensor_layout(images) == 'interleaved':
+                out, alpha = _lens_pass(self._hip, tables, self.lens.weights(), images, self.return_alpha, stream, 'hwc')
+            else:
+                out, alpha = _lens_pass(self._hip, tables, self.lens.weights(), images.contiguous(), self.return_alpha, stream)
         return (out, alpha) if self.return_alpha else out
 
     def close(self):

@@ -59,6 +59,7 @@
 #include "rr_particles.h"
 #include "rr_lens.h"
 #include "rr_resize.h"
+#include "rr_convert.h"
 
 using namespace rr;
 
@@ -88,15 +89,18 @@ struct FrameDesc {
   const rr_ext_tile* ext;          // optional: caller-made tiles / FOV polygons per drop (device pointers inside)
   double* colour_out;              // optional: n_drops * 3 colour constants (rr_frame_out.drop_colour)
   const int32_t* n_drops_dev;      // optional: the drop count lives on the device (k_patch_counts)
-  void* planar;                    // rr_augment_frames_device: [3][H][W] RGB out (bytes, or floats with planar_f32) instead of rgb
+  void* planar;                    // rr_augment_frames_device: the caller's RGB frame out (its format: planar_fmt) instead of rgb
   float* mask_f32;                 // ... and float(mask_f64), H*W (k_finalize_planar)
   int32_t comp_f32, in_types;      // comp_out holds floats (the float-colour compositor wrote it); element types of the inputs
   int32_t depth_f64;
   int32_t n_drops;
   int32_t strategy;
-  int32_t planar_f32;
+  int32_t planar_fmt;              // TF_*: rr_tensor_batch.dtype, | TF_INTERLEAVED for [H][W][3]
   double opacity;
 };
+
+// the element type and layout of rr_augment_frames_device's tensors: RR_TENSOR_* (| TF_INTERLEAVED: RR_LAYOUT_INTERLEAVED)
+enum { TF_U8 = RR_TENSOR_U8, TF_F32 = RR_TENSOR_F32, TF_F16 = RR_TENSOR_F16, TF_BF16 = RR_TENSOR_BF16, TF_INTERLEAVED = 8 };
 
 // Pointers that arrive inside FrameDesc are loaded from memory, so the compiler has to treat them as generic
 // ("flat": every access also counts against the LDS counter).  They are all device-global: say so.
@@ -4440,7 +4444,9 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t* rows_base, i
 
 // The render-scale resize of the inputs (rr_set_input_resize; the arithmetic is csrc/rr_resize.h): full-size frames in,
 // the float64 B G R image / the float32 depth map of the render size out -- what the pre-pass and the hot path read as in_types = 0.
-//   k_resize_in<KIND>     RSZ_BGR8: the un-filtered file, interleaved B G R bytes; RSZ_RGB8P / RSZ_RGBF32P: a planar R G B tensor
+//   k_resize_in<KIND>     RSZ_BGR8: the un-filtered file, interleaved B G R bytes; RSZ_RGB8P / RSZ_RGBF32P: a planar R G B tensor;
+//                         RSZ_RGB8I .. RSZ_RGBBF16I: rr_tensor_batch's other formats -- interleaved R G B (I) and the half types,
+//                         which feed (double)value as float32 does (csrc/rr_convert.h); only the sample fetch differs
 //   k_resize_depth<KIND>  RSZ_D16: uint16 samples (metres * 256); RSZ_DF32: float32 metres
 // A workgroup makes RSZ_SEG pixels of one output row of one frame (grid: segments x rows x frames), two pixels per lane.  The two
 // source rows it reads (six pieces for a planar tensor) are consecutive bytes: it stages them in LDS with aligned 16-byte loads
@@ -4449,7 +4455,9 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t* rows_base, i
 // every lane then picks its 2 x 2 neighbourhoods out of LDS.  A segment whose source span does not fit its share of the pool
 // (a scale above ~12 for bytes, ~3 for planar floats) reads global memory directly.  The image goes out as three 16-byte stores per
 // lane (48 bytes = two pixels), the odd last pixel of a row as three doubles.
-enum { RSZ_BGR8 = 0, RSZ_RGB8P = 1, RSZ_RGBF32P = 2, RSZ_D16 = 3, RSZ_DF32 = 4 };
+enum { RSZ_BGR8 = 0, RSZ_RGB8P = 1, RSZ_RGBF32P = 2, RSZ_D16 = 3, RSZ_DF32 = 4,
+       RSZ_RGB8I = 5, RSZ_RGBF32I = 6, RSZ_RGBF16P = 7, RSZ_RGBBF16P = 8, RSZ_RGBF16I = 9, RSZ_RGBBF16I = 10 };
+constexpr bool rsz_is_image(int kind) { return kind != RSZ_D16 && kind != RSZ_DF32; }
 constexpr int RSZ_THREADS = 256, RSZ_SEG = 2 * RSZ_THREADS;
 constexpr int RSZ_POOL = 6 * 6656;                      // LDS bytes for the staged pieces: 1026 floats + the windows' ends, six times
 typedef double f64x2_t __attribute__((ext_vector_type(2)));
@@ -4485,16 +4493,18 @@ __device__ inline void resize_stage(const uint8_t* g0, const uint8_t* g1, const 
 
 template <int KIND>
 __device__ inline void resize_rows(const ResizeArgs& a) {
-  constexpr bool IMAGE = KIND <= RSZ_RGBF32P;
-  constexpr int P = (KIND == RSZ_RGB8P || KIND == RSZ_RGBF32P) ? 3 : 1;                                  // pieces per source row
-  constexpr int EL = KIND == RSZ_BGR8 ? 3 : (KIND == RSZ_RGB8P ? 1 : (KIND == RSZ_D16 ? 2 : 4));      // bytes per pixel of a piece
+  constexpr bool IMAGE = rsz_is_image(KIND);
+  constexpr bool HALF = KIND >= RSZ_RGBF16P && KIND <= RSZ_RGBBF16I, BF16 = KIND == RSZ_RGBBF16P || KIND == RSZ_RGBBF16I;
+  constexpr int P = (KIND == RSZ_RGB8P || KIND == RSZ_RGBF32P || KIND == RSZ_RGBF16P || KIND == RSZ_RGBBF16P) ? 3 : 1;      // pieces per source row
+  constexpr int EL = (KIND == RSZ_BGR8 || KIND == RSZ_RGB8I) ? 3 : (KIND == RSZ_RGB8P ? 1 : (KIND == RSZ_RGBF32I ? 12 :       // bytes per pixel of a piece
+                     (HALF ? (P == 3 ? 2 : 6) : (KIND == RSZ_D16 ? 2 : 4))));
   constexpr int CAP = RSZ_POOL / (2 * P);
   static_assert(CAP % 16 == 0, "every piece starts on a 16-byte boundary of the pool");
   __shared__ double s_lut[256];
   __shared__ u32x4_t s_pool[RSZ_POOL / 16];
   const int t = threadIdx.x, f = blockIdx.z, y = blockIdx.y;
   const int xs = blockIdx.x * RSZ_SEG, xe = rr::imin(xs + RSZ_SEG, a.W);
-  if (KIND == RSZ_BGR8 || KIND == RSZ_RGB8P) s_lut[t] = rrresize::image_unit((uint8_t)t);
+  if (KIND == RSZ_BGR8 || KIND == RSZ_RGB8P || KIND == RSZ_RGB8I) s_lut[t] = rrresize::image_unit((uint8_t)t);
   const bool identity = a.sH == a.H && a.sW == a.W;
   int32_t yy[2], xa, xb, spare;
   double wy, wspare;
@@ -4572,6 +4582,9 @@ __device__ inline void resize_rows(const ResizeArgs& a) {
     if constexpr (KIND == RSZ_BGR8) return s_lut[q[c]];
     else if constexpr (KIND == RSZ_RGB8P) return s_lut[q[0]];
     else if constexpr (KIND == RSZ_RGBF32P) return (double)*reinterpret_cast<const float*>(q);
+    else if constexpr (KIND == RSZ_RGB8I) return s_lut[q[2 - c]];
+    else if constexpr (KIND == RSZ_RGBF32I) return (double)reinterpret_cast<const float*>(q)[2 - c];
+    else if constexpr (HALF) return (double)rrconv::bits_f32(rrconv::widen_bits<BF16>(reinterpret_cast<const uint16_t*>(q)[P == 3 ? 0 : 2 - c]));
     else if constexpr (KIND == RSZ_D16) return (double)rrresize::depth_metres(*reinterpret_cast<const uint16_t*>(q));
     else return (double)*reinterpret_cast<const float*>(q);
   };
@@ -6102,13 +6115,13 @@ int grow_arena(rr_ctx* ctx) {
   return RR_OK;
 }
 
-// rr_augment_frames_device: frame f's image goes to rgb + f * rgb_stride as [3][H][W] planes (bytes, or float32 with f32) and its
-// mask to mask + f * H * W as float32, both written by k_finalize_planar instead of rr_frame_out.rainy_rgb
+// rr_augment_frames_device: frame f's image goes to rgb + f * rgb_stride in the caller's format (fmt: TF_*; [3][H][W] planes or
+// [H][W][3]) and its mask to mask + f * H * W as float32, both written by k_finalize_planar instead of rr_frame_out.rainy_rgb
 struct PlanarOut {
   char* rgb;
   float* mask;
   int64_t rgb_stride;
-  int f32;
+  int fmt;
 };
 
 // The lens stage of a batch on an armed pipeline slot (rr_pipeline_set_lens): between the finalize kernel and the PNG rows.
@@ -6207,7 +6220,7 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     fd.n_drops_dev = in[f].n_drops_dev;
     fd.planar = planar ? planar->rgb + (size_t)f * planar->rgb_stride : nullptr;
     fd.mask_f32 = planar ? planar->mask + (size_t)f * dm.H * dm.W : nullptr;
-    fd.planar_f32 = planar ? planar->f32 : 0;
+    fd.planar_fmt = planar ? planar->fmt : 0;
     fd.comp_f32 = use32 ? (ctx->wild_pixels ? 1 : 2) : 0;
     fd.in_types = in[f].in_types;
     any_dev_count = any_dev_count || in[f].n_drops_dev;
@@ -8240,7 +8253,7 @@ int slot_init(rr_ctx* ctx, rr_ctx::Slot& sl) {
 // buffer [lo, hi)) -> the render-size float64 image / float32 depth map at `dst`.  kind: RSZ_*.  Each kernel under its own scope.
 int enqueue_resize(rr_ctx* ctx, int n, int H, int W, int kind, const void* src, int64_t src_stride, const void* lo, const void* hi,
                    void* dst, int64_t dst_stride, hipStream_t s) {
-  const bool image = kind <= RSZ_RGBF32P;
+  const bool image = rsz_is_image(kind);
   const int sH = image ? ctx->rsz.sH : ctx->rsz.dH, sW = image ? ctx->rsz.sW : ctx->rsz.dW;
   if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || sH <= 0 || sW <= 0) {
     ctx->err = "input resize: bad batch or frame size";
@@ -8253,7 +8266,13 @@ int enqueue_resize(rr_ctx* ctx, int n, int H, int W, int kind, const void* src, 
     ProfScope ps(ctx, s, "k_resize_in");
     if (kind == RSZ_BGR8) hipLaunchKernelGGL(k_resize_in<RSZ_BGR8>, grid, dim3(RSZ_THREADS), 0, s, a);
     else if (kind == RSZ_RGB8P) hipLaunchKernelGGL(k_resize_in<RSZ_RGB8P>, grid, dim3(RSZ_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(k_resize_in<RSZ_RGBF32P>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGBF32P) hipLaunchKernelGGL(k_resize_in<RSZ_RGBF32P>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGB8I) hipLaunchKernelGGL(k_resize_in<RSZ_RGB8I>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGBF32I) hipLaunchKernelGGL(k_resize_in<RSZ_RGBF32I>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGBF16P) hipLaunchKernelGGL(k_resize_in<RSZ_RGBF16P>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGBBF16P) hipLaunchKernelGGL(k_resize_in<RSZ_RGBBF16P>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else if (kind == RSZ_RGBF16I) hipLaunchKernelGGL(k_resize_in<RSZ_RGBF16I>, grid, dim3(RSZ_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(k_resize_in<RSZ_RGBBF16I>, grid, dim3(RSZ_THREADS), 0, s, a);
   } else {
     ProfScope ps(ctx, s, "k_resize_depth");
     if (kind == RSZ_D16) hipLaunchKernelGGL(k_resize_depth<RSZ_D16>, grid, dim3(RSZ_THREADS), 0, s, a);
@@ -8781,9 +8800,18 @@ constexpr int AUG_FLAG = 1 + RR_PIPE_SLOTS;      // rr_augment_frames_device's o
 // particles -> ingest -> pre-pass -> hot path -> planar finalize, on `s`, then the overflow check (see include/rainhip.h)
 int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   const int n = b->n, H = b->H, W = b->W, cap = b->drops_cap;
-  if (n <= 0 || H <= 0 || W <= 0 || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32) || !b->images || !b->depth || !b->sims ||
+  const bool half = b->dtype == RR_TENSOR_F16 || b->dtype == RR_TENSOR_BF16;
+  if (n <= 0 || H <= 0 || W <= 0 || (b->dtype != RR_TENSOR_U8 && b->dtype != RR_TENSOR_F32 && !half) ||
+      (b->layout != RR_LAYOUT_PLANAR && b->layout != RR_LAYOUT_INTERLEAVED) || !b->images || !b->depth || !b->sims ||
       !b->fog || !b->rainy_out || !b->mask_out || cap <= 0 || cap > 65536) {
-    ctx->err = "rr_augment_frames_device: bad argument (sizes, dtype, a null pointer, or drops_cap outside [1, 2^16])";
+    ctx->err = "rr_augment_frames_device: bad argument (sizes, dtype, layout, a null pointer, or drops_cap outside [1, 2^16])";
+    return RR_E_ARG;
+  }
+  // el: bytes per element of the caller's tensors; bel: of the interleaved scratch image (the half types widen into float32)
+  const size_t el = b->dtype == RR_TENSOR_F32 ? 4 : (half ? 2 : 1), bel = el == 1 ? 1 : 4;
+  const bool il = b->layout == RR_LAYOUT_INTERLEAVED;
+  if (((reinterpret_cast<uintptr_t>(b->images) | reinterpret_cast<uintptr_t>(b->rainy_out)) & (el - 1)) != 0) {
+    ctx->err = "rr_augment_frames_device: images or rainy_out is not aligned to its element size";
     return RR_E_ARG;
   }
   for (int f = 0; f < n; f++)
@@ -8800,17 +8828,13 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
     ctx->err = "rr_augment_frames_device: rr_set_solid_angles must be called for the H x rr_envmap_width() map";
     return RR_E_STATE;
   }
-  const size_t px = (size_t)H * W, el = b->dtype == RR_TENSOR_F32 ? 4 : 1;
+  const size_t px = (size_t)H * W;
   auto rnd = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // rr_set_input_resize: images and depth arrive at the armed sizes; the stage makes the float64 image (and, where the depth map
   // has another size than the frame, the float32 map) of the render size in the scratch
   const rr_ctx::InputResize R = ctx->rsz;
   const bool rsz = R.armed, rsz_depth = rsz && (R.dH != H || R.dW != W);
-  if (rsz && el == 4 && (reinterpret_cast<uintptr_t>(b->images) & 3u)) {
-    ctx->err = "rr_augment_frames_device: misaligned float32 images";
-    return RR_E_ARG;
-  }
-  const size_t s_bg = rnd(px * 3 * (rsz ? 8 : el)), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
+  const size_t s_bg = rnd(px * 3 * (rsz ? 8 : bel)), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
   const size_t b_drops = rnd((size_t)n * cap * sizeof(rr_drop)), b_counts = rnd((size_t)n * 4), s_dep = rsz_depth ? rnd(px * 4) : 0;
   const size_t need = (size_t)n * (s_bg + s_rainy + s_env + s_mask + s_dep) + b_drops + b_counts;
   if (need > ctx->aug_bytes) {
@@ -8828,7 +8852,7 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   rr_drop* const drops = reinterpret_cast<rr_drop*>(mask + (size_t)n * s_mask);
   int32_t* const counts = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(drops) + b_drops);
   char* const dep = reinterpret_cast<char*>(counts) + b_counts;
-  const int bg_type = rsz ? 0 : (b->dtype == RR_TENSOR_F32 ? RR_IN_BG_F32 : RR_IN_BG_U8);
+  const int bg_type = rsz ? 0 : (bel == 4 ? RR_IN_BG_F32 : RR_IN_BG_U8);
   // the descriptors rr_pipeline_frames builds for the same frames by default: float32 hand-over, resident solid angles
   std::vector<rr_prepass_in> pin(n);
   std::vector<rr_prepass_out> pout(n);
@@ -8874,29 +8898,48 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
     memset(&fo, 0, sizeof fo);
     fo.mask_f64 = reinterpret_cast<double*>(mask + (size_t)f * s_mask);
   }
-  const PlanarOut pl{static_cast<char*>(b->rainy_out), b->mask_out, (int64_t)(px * 3 * el), b->dtype == RR_TENSOR_F32 ? 1 : 0};
+  const PlanarOut pl{static_cast<char*>(b->rainy_out), b->mask_out, (int64_t)(px * 3 * el), b->dtype | (il ? TF_INTERLEAVED : 0)};
   const int64_t total = (int64_t)n * 3 * (int64_t)px;
   for (int attempt = 0;; attempt++) {
     int rc;
     if ((rc = enqueue_particles(ctx, n, b->sims, H, W, drops, cap, counts, s))) return rc;
     if (rsz) {
       const int64_t fb = (int64_t)R.sH * R.sW * 3 * (int64_t)el, db = (int64_t)R.dH * R.dW * 4;
-      if ((rc = enqueue_resize(ctx, n, H, W, el == 4 ? RSZ_RGBF32P : RSZ_RGB8P, b->images, fb, b->images, static_cast<const char*>(b->images) + n * fb,
+      const int kind = b->dtype == RR_TENSOR_U8    ? (il ? RSZ_RGB8I : RSZ_RGB8P)
+                       : b->dtype == RR_TENSOR_F32 ? (il ? RSZ_RGBF32I : RSZ_RGBF32P)
+                       : b->dtype == RR_TENSOR_F16 ? (il ? RSZ_RGBF16I : RSZ_RGBF16P)
+                                                   : (il ? RSZ_RGBBF16I : RSZ_RGBBF16P);
+      if ((rc = enqueue_resize(ctx, n, H, W, kind, b->images, fb, b->images, static_cast<const char*>(b->images) + n * fb,
                                bg, (int64_t)s_bg, s)))
         return rc;
       if (rsz_depth && (rc = enqueue_resize(ctx, n, H, W, RSZ_DF32, b->depth, db, b->depth, reinterpret_cast<const char*>(b->depth) + n * db, dep,
                                             (int64_t)s_dep, s)))
         return rc;
     } else {
-      ProfScope ps(ctx, s, "k_planar_in");
-      if (el == 1) {
-        const int64_t lanes = ((int64_t)px + 15) / 16;
-        hipLaunchKernelGGL(k_planar_in<0>, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, b->images, (void*)bg, (int64_t)px,
-                           (int64_t)s_bg, total);
+      const int64_t per = 16 / (int64_t)el, lanes = ((int64_t)px + per - 1) / per;      // a lane's pixels: one 16-byte piece per plane
+      const dim3 grid((unsigned)((lanes + 255) / 256), n);
+      if (!il && !half) {
+        ProfScope ps(ctx, s, "k_planar_in");
+        if (el == 1)
+          hipLaunchKernelGGL(k_planar_in<0>, grid, dim3(256), 0, s, b->images, (void*)bg, (int64_t)px, (int64_t)s_bg, total);
+        else
+          hipLaunchKernelGGL(k_planar_in<1>, grid, dim3(256), 0, s, b->images, (void*)bg, (int64_t)px, (int64_t)(s_bg / 4), total);
       } else {
-        const int64_t lanes = ((int64_t)px + 3) / 4;
-        hipLaunchKernelGGL(k_planar_in<1>, dim3((unsigned)((lanes + 255) / 256), n), dim3(256), 0, s, b->images, (void*)bg, (int64_t)px,
-                           (int64_t)(s_bg / 4), total);
+        ProfScope ps(ctx, s, "k_tensor_in");
+        const uint8_t* img = static_cast<const uint8_t*>(b->images);
+        uint8_t* o = reinterpret_cast<uint8_t*>(bg);
+        const int64_t bytes = total * (int64_t)el;
+        if (el == 1) {
+          hipLaunchKernelGGL((k_tensor_in<TF_U8, 1>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+        } else if (el == 4) {
+          hipLaunchKernelGGL((k_tensor_in<TF_F32, 1>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+        } else if (b->dtype == RR_TENSOR_F16) {
+          if (il) hipLaunchKernelGGL((k_tensor_in<TF_F16, 1>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+          else hipLaunchKernelGGL((k_tensor_in<TF_F16, 0>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+        } else {
+          if (il) hipLaunchKernelGGL((k_tensor_in<TF_BF16, 1>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+          else hipLaunchKernelGGL((k_tensor_in<TF_BF16, 0>), grid, dim3(256), 0, s, img, o, (int64_t)px, (int64_t)s_bg, bytes);
+        }
       }
     }
     if ((rc = enqueue_prepass(ctx, n, pin.data(), pout.data(), s))) return rc;

@@ -1,8 +1,11 @@
-// rr_tensor.h -- the two kernels of rr_augment_frames_device (include/rainhip.h) that meet PyTorch's planar layout:
+// rr_tensor.h -- the kernels of rr_augment_frames_device (include/rainhip.h) that meet PyTorch's tensors:
 //   k_planar_in<0> / k_planar_in<1>    [n][3][H][W] RGB (bytes, or float32 in [0, 1]) -> the interleaved BGR image the pre-pass and
 //                                      the hot path read (RR_IN_BG_U8 / RR_IN_BG_F32): values moved, never converted
+//   k_tensor_in<DT, IL>                the same for the six other formats: [n][H][W][3] bytes and float32 (IL), float16 and bfloat16
+//                                      in either layout, widened into the float32 image (csrc/rr_convert.h)
 //   k_finalize_planar                  in place of k_finalize16 / k_finalize: the frame's bytes (finalize_rgb) straight into the caller's
-//                                      [3][H][W] planes -- as bytes, or as byte / 255 in float32 -- and float(mask_f64) into [H][W]
+//                                      frame -- [3][H][W] planes or [H][W][3]; as bytes, as byte / 255 in float32, or as that float
+//                                      rounded once to float16 / bfloat16 -- and float(mask_f64) into [H][W]
 // Included by rainhip.hip inside its anonymous namespace, behind FrameDesc, Scratch and finalize_rgb.
 #ifndef RR_TENSOR_H
 #define RR_TENSOR_H
@@ -119,6 +122,64 @@ __global__ __launch_bounds__(256) void k_planar_in(const void* img, void* out, i
     planar_in_u8(static_cast<const uint8_t*>(img), static_cast<uint8_t*>(out), npix, out_stride, total);
 }
 
+// The six formats k_planar_in does not take.  One lane per 16-byte piece of a plane (16 / EL pixels), or per the 48 bytes that hold as
+// many interleaved pixels: three load16 either way -- a frame starts 3 H W EL bytes behind the last one, so the misalignment is the
+// same for every lane of a wave -- and 48 (bytes) or 96 (half types, widened) or 48 (float32) bytes of B G R out, as whole 16-byte
+// stores (the frame's scratch image starts on a 16-byte boundary).  The last pixels of a frame element by element.
+// out_stride, total: BYTES between two frames of the scratch image / of the whole input batch.
+template <int DT, int IL>
+__global__ __launch_bounds__(256) void k_tensor_in(const uint8_t* img, uint8_t* out, int64_t npix, int64_t out_stride, int64_t total) {
+  static_assert(IL || DT == TF_F16 || DT == TF_BF16, "planar bytes and float32: k_planar_in");
+  constexpr int EL = DT == TF_U8 ? 1 : (DT == TF_F32 ? 4 : 2), OEL = DT == TF_U8 ? 1 : 4;      // bytes per element in / in the scratch image
+  constexpr int PX = 16 / EL, NW = PX * 3 * OEL / 4;                                         // a lane's pixels; the dwords it writes
+  constexpr int BF = DT == TF_BF16;
+  const int f = blockIdx.y;
+  const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * PX;
+  if (p0 >= npix) return;
+  const uint8_t* fb = img + (int64_t)f * 3 * npix * EL;
+  uint8_t* o = out + (int64_t)f * out_stride + p0 * 3 * OEL;
+  if (p0 + PX <= npix) {
+    const uint8_t* hi = img + total;
+    uint32_t w[12], ow[NW];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const u32x4_t v = load16(IL ? fb + rrconv::interleaved_index(p0, 0) * EL + 16 * k : fb + rrconv::planar_index(p0, k, npix) * EL, img, hi);
+      w[4 * k + 0] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+    }
+    if constexpr (DT == TF_U8) {
+      // R G B R | G B R G | B R G B -> B G R B | G R B G | R B G R, every 12 bytes: v_perm_b32 picks byte 0 .. 3 of its second
+      // operand and 4 .. 7 of its first; the middle dword takes bytes of all three
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t a = w[3 * j], b = w[3 * j + 1], c = w[3 * j + 2];
+        ow[3 * j + 0] = __builtin_amdgcn_perm(b, a, 0x05000102u);                                   // bytes 2 1 0 5
+        ow[3 * j + 1] = __builtin_amdgcn_perm(c, __builtin_amdgcn_perm(b, a, 0x07000304u), 0x03040100u);      // 4 3 8 7
+        ow[3 * j + 2] = __builtin_amdgcn_perm(c, b, 0x05060702u);                                   // 6 11 10 9
+      }
+    } else {
+#pragma unroll
+      for (int p = 0; p < PX; p++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          const int e = IL ? (int)rrconv::interleaved_index(p, c) : c * PX + p;                     // the element among the lane's 48 bytes
+          if constexpr (DT == TF_F32) ow[3 * p + 2 - c] = w[e];
+          else ow[3 * p + 2 - c] = rrconv::widen_bits<BF>((uint16_t)(w[e >> 1] >> (16 * (e & 1))));
+        }
+    }
+    const global_ptr<u32x4_t> o4 = reinterpret_cast<global_ptr<u32x4_t>>(as_global(o));
+#pragma unroll
+    for (int k = 0; k < NW / 4; k++) o4[k] = u32x4_t{ow[4 * k], ow[4 * k + 1], ow[4 * k + 2], ow[4 * k + 3]};
+  } else {
+    for (int64_t p = 0; p < npix - p0; p++)
+      for (int c = 0; c < 3; c++) {
+        const int64_t e = IL ? rrconv::interleaved_index(p0 + p, c) : rrconv::planar_index(p0 + p, c, npix);
+        if constexpr (DT == TF_U8) as_global(o)[3 * p + 2 - c] = as_global(fb)[e];
+        else if constexpr (DT == TF_F32) as_global(reinterpret_cast<uint32_t*>(o))[3 * p + 2 - c] = as_global(reinterpret_cast<const uint32_t*>(fb))[e];
+        else as_global(reinterpret_cast<uint32_t*>(o))[3 * p + 2 - c] = rrconv::widen_bits<BF>(as_global(reinterpret_cast<const uint16_t*>(fb))[e]);
+      }
+  }
+}
+
 // four floats to p: one 16-byte store where p allows it, two 8-byte ones at 8 bytes, else one by one (cnt < 4: the frame's tail)
 __device__ inline void store_f32x4(float* p, const float v[4], int cnt) {
   const uintptr_t a = reinterpret_cast<uintptr_t>(p);
@@ -148,6 +209,78 @@ __device__ inline void store_u8x4(uint8_t* p, uint32_t w, int cnt) {
   }
 }
 
+// N dwords holding a lane's elements of EL bytes, `bytes` of them to store, to p: whole stores of 16, 8 or 4 bytes where N, p and a
+// full count allow -- a lane's run is 4 N bytes behind its neighbour's, so the choice is the same across a wave -- bytes also in
+// pairs, else element by element (a frame's tail, or a frame that starts off a dword)
+template <int N, int EL>
+__device__ inline void store_packed(uint8_t* p, const uint32_t (&w)[N], int bytes) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const bool full = bytes == 4 * N;
+  if (N % 4 == 0 && full && (a & 15u) == 0) {
+    const global_ptr<u32x4_t> q = reinterpret_cast<global_ptr<u32x4_t>>(as_global(p));
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) q[k] = u32x4_t{w[4 * k], w[(4 * k + 1) % N], w[(4 * k + 2) % N], w[(4 * k + 3) % N]};
+  } else if (N % 2 == 0 && full && (a & 7u) == 0) {
+    const global_ptr<u32x2_t> q = reinterpret_cast<global_ptr<u32x2_t>>(as_global(p));
+#pragma unroll
+    for (int k = 0; k < N / 2; k++) q[k] = u32x2_t{w[2 * k], w[(2 * k + 1) % N]};
+  } else if (full && (a & 3u) == 0) {
+    const global_ptr<uint32_t> q = reinterpret_cast<global_ptr<uint32_t>>(as_global(p));
+#pragma unroll
+    for (int k = 0; k < N; k++) q[k] = w[k];
+  } else if (EL == 1 && full && (a & 1u) == 0) {
+    const global_ptr<uint16_t> q = reinterpret_cast<global_ptr<uint16_t>>(as_global(p));
+#pragma unroll
+    for (int k = 0; k < 2 * N; k++) q[k] = (uint16_t)(w[k >> 1] >> (16 * (k & 1)));
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4 * N / EL; e++)
+      if (e * EL < bytes) {
+        if (EL == 1) as_global(p)[e] = (uint8_t)(w[e >> 2] >> (8 * (e & 3)));
+        else if (EL == 2) reinterpret_cast<global_ptr<uint16_t>>(as_global(p))[e] = (uint16_t)(w[e >> 1] >> (16 * (e & 1)));
+        else reinterpret_cast<global_ptr<uint32_t>>(as_global(p))[e] = w[e];
+      }
+  }
+}
+
+// k_finalize_planar's stores for the formats behind its two own: a thread's four pixels (cnt of them: the frame's tail) as interleaved
+// elements -- 12 bytes, 48 (float32) or 24 (half types) per lane -- or as four halves, 8 bytes, per plane.  A float element is
+// float(byte) / 255.0f, a half that float rounded once (rr_convert.h).
+template <int DT, int IL>
+__device__ inline void finalize_store(void* frame, int64_t pix0, int64_t npix, const uint32_t (&rgb)[4][3], int cnt) {
+  constexpr int EL = DT == TF_U8 ? 1 : (DT == TF_F32 ? 4 : 2);
+  auto bits = [&](int px, int ch) -> uint32_t {
+    if constexpr (DT == TF_U8) {
+      return rgb[px][ch];
+    } else {
+      const uint32_t v = __float_as_uint((float)((double)rgb[px][ch] / 255.0));      // = float(byte) / 255.0f, correctly rounded
+      if constexpr (DT == TF_F32) return v;
+      else return rrconv::narrow_bits<DT == TF_BF16>(v);
+    }
+  };
+  uint8_t* base = static_cast<uint8_t*>(frame);
+  if constexpr (IL) {
+    constexpr int N = 3 * EL;
+    uint32_t w[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) w[k] = 0u;
+#pragma unroll
+    for (int px = 0; px < 4; px++)
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        const int e = (int)rrconv::interleaved_index(px, ch) * EL;
+        w[e >> 2] |= bits(px, ch) << (8 * (e & 3));
+      }
+    store_packed<N, EL>(base + rrconv::interleaved_index(pix0, 0) * EL, w, cnt * 3 * EL);
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const uint32_t w[2] = {bits(0, ch) | (bits(1, ch) << 16), bits(2, ch) | (bits(3, ch) << 16)};
+      store_packed<2, EL>(base + rrconv::planar_index(pix0, ch, npix) * EL, w, cnt * EL);
+    }
+  }
+}
+
 // Four pixels per thread: the composite (any form, comp_load) -> finalize_rgb -> the three planes; float output is the byte / 255
 // (what ToTensor makes of the PNG the driver writes).  The same pass turns the float64 mask into float32.
 __global__ __launch_bounds__(256) void k_finalize_planar(const FrameDesc* frames, Dims dm, Scratch sc) {
@@ -171,7 +304,8 @@ __global__ __launch_bounds__(256) void k_finalize_planar(const FrameDesc* frames
       mk[px] = (float)m64[px];
     }
   }
-  if (fr.planar_f32) {
+  const int fmt = fr.planar_fmt;             // the same for a frame's every workgroup: a wave-uniform branch
+  if (fmt == TF_F32) {
     float* base = static_cast<float*>(fr.planar) + pix0;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
@@ -180,11 +314,23 @@ __global__ __launch_bounds__(256) void k_finalize_planar(const FrameDesc* frames
       for (int px = 0; px < 4; px++) v[px] = (float)((double)rgb[px][ch] / 255.0);      // = float(byte) / 255.0f, correctly rounded
       store_f32x4(base + ch * npix, v, cnt);
     }
-  } else {
+  } else if (fmt == TF_U8) {
     uint8_t* base = static_cast<uint8_t*>(fr.planar) + pix0;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++)
       store_u8x4(base + ch * npix, rgb[0][ch] | (rgb[1][ch] << 8) | (rgb[2][ch] << 16) | (rgb[3][ch] << 24), cnt);
+  } else if (fmt == (TF_U8 | TF_INTERLEAVED)) {
+    finalize_store<TF_U8, 1>(fr.planar, pix0, npix, rgb, cnt);
+  } else if (fmt == (TF_F32 | TF_INTERLEAVED)) {
+    finalize_store<TF_F32, 1>(fr.planar, pix0, npix, rgb, cnt);
+  } else if (fmt == TF_F16) {
+    finalize_store<TF_F16, 0>(fr.planar, pix0, npix, rgb, cnt);
+  } else if (fmt == (TF_F16 | TF_INTERLEAVED)) {
+    finalize_store<TF_F16, 1>(fr.planar, pix0, npix, rgb, cnt);
+  } else if (fmt == TF_BF16) {
+    finalize_store<TF_BF16, 0>(fr.planar, pix0, npix, rgb, cnt);
+  } else {
+    finalize_store<TF_BF16, 1>(fr.planar, pix0, npix, rgb, cnt);
   }
   store_f32x4(fr.mask_f32 + pix0, mk, cnt);
 }

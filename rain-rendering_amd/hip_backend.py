@@ -141,12 +141,14 @@ class rr_prepass_out(ctypes.Structure):
 
 RR_TENSOR_U8, RR_TENSOR_F32 = 0, 1                       # rr_tensor_batch.dtype
 RR_TENSOR_U8_HWC = 3                                     # rr_lens_batch.dtype only: interleaved bytes [n, H, W, 3] (2 stays refused)
+RR_TENSOR_F16, RR_TENSOR_BF16 = 4, 5                     # rr_tensor_batch.dtype only
+RR_LAYOUT_PLANAR, RR_LAYOUT_INTERLEAVED = 0, 1           # rr_tensor_batch.layout: [n, 3, H, W] / [n, H, W, 3]
 
 
 class rr_tensor_batch(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('dtype', ctypes.c_int32),
                 ('images', ctypes.c_void_p), ('depth', ctypes.c_void_p), ('sims', ctypes.c_void_p), ('fog', ctypes.c_void_p),
-                ('drops_cap', ctypes.c_int32), ('reserved', ctypes.c_int32), ('rainy_out', ctypes.c_void_p),
+                ('drops_cap', ctypes.c_int32), ('layout', ctypes.c_int32), ('rainy_out', ctypes.c_void_p),
                 ('mask_out', ctypes.c_void_p)]
 
 
