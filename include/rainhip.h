@@ -844,6 +844,11 @@ int rr_profile_enable(rr_ctx* ctx, int32_t on);
 int rr_profile_reset(rr_ctx* ctx);
 int rr_profile_read(rr_ctx* ctx, rr_kernel_stat* out, int32_t cap);   /* returns #entries or <0 */
 
+/* What the context holds right now: out[0] device blocks and [1] their bytes, [2] pinned host blocks and [3] their bytes.
+ * Every allocation of the library on behalf of the context is counted; the caller's own rr_host_alloc blocks are not.  Reads
+ * host-side records only (no device call, no synchronisation). */
+int rr_debug_mem(rr_ctx* ctx, int64_t out[4]);
+
 /* Host-only helper (no device, no ctx): the random draws of one frame's drop loop, bit-identical to
  * numpy's legacy global RandomState after np.random.seed(seed) (generator.py:318): per drop one
  * randint(tex_lo[k], tex_lo[k]+10) (bad_weather.py:252-264) and, for non-Big drops, one

@@ -5670,15 +5670,28 @@ __global__ __launch_bounds__(256) void k_png_alpha(const uint8_t* label, uint8_t
 // ===========================================================================
 // host side
 // ===========================================================================
+#include "rr_mem.h"
+
 struct ProfEntry {
   const char* name;
   hipEvent_t a, b;
+};
+
+// the backend of a context's memory owner (rr_mem.h): the four HIP calls, their error codes as int
+struct HipMem {
+  int dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  int dev_free(void* p) { return (int)hipFree(p); }
+  int pin_alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  int pin_free(void* p) { return (int)hipHostFree(p); }
 };
 
 struct rr_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
+  // every device and pinned block below is allocated through `mem` (dev_alloc / pin_alloc / reserve) and freed by it: early by
+  // mem.free, at the latest by rr_destroy's release_all.  Only the caller's rr_host_alloc blocks (host_allocs) live outside it.
+  rrmem::Owner<HipMem> mem;
   // streak DB
   uint8_t* d_tex = nullptr;
   bool own_tex = false;
@@ -5694,14 +5707,12 @@ struct rr_ctx {
   int erec_nfov = 0;                 // n_fov the edge-record scratch was sized for
   int rows_shares = 2;               // RR_OPT_ROWS_SHARES: shares of the tile list per workgroup of k_tile_rows
   bool png_deflate = false;          // RR_OPT_PNG_DEFLATE: the PNG outputs hold zlib streams (rr_deflate.h)
-  uint8_t* d_pngz_slots = nullptr;
-  rrz::BlockMeta* d_pngz_meta = nullptr;
-  size_t pngz_cap = 0;               // blocks
+  rrmem::Buf<uint8_t> pngz_slots;    // rrz::SLOT_BYTES per block
+  rrmem::Buf<rrz::BlockMeta> pngz_meta;
   bool pngz_attr = false;
   int streak_lean = 0;               // RR_OPT_STREAK_LEAN: 1 a rotated tile's flip and corner come from the streak's own end points (plan_drop)
   bool wild_pixels = false;          // RR_OPT_WILD_PIXELS: rainy_bg may hold values outside [0, 1] (k_pad_visits)
-  int32_t *d_pad_first = nullptr, *d_eff_first = nullptr;
-  size_t pad_cap = 0;                // elements of each
+  rrmem::Buf<int32_t> pad_first, eff_first;
   bool pipe_f32 = true;              // RR_OPT_PIPELINE_F32: float32 hand-over from the pre-pass to the hot path inside rr_pipeline_*
   bool dda_attr = false;
   int fill_rule = 1;                 // RR_OPT_FOV_FILL_RULE: 1 (default since r06) OpenCV's fillConvexPoly; 0 the span rule of rounds 1-5
@@ -5718,9 +5729,8 @@ struct rr_ctx {
   // particle generator (rr_set_particle_tables / rr_generate_drops_device)
   double *d_dgrid = nullptr, *d_cdf = nullptr, *d_ratio_db = nullptr;
   int n_grid = 0, n_tables = 0, n_ratio = 0;
-  rr_sim_frame* d_sims = nullptr;
-  int cap_sims = 0;
-  rr_drop* d_gen_drops = nullptr;    // staging of rr_generate_drops (host-pointer variant)
+  rrmem::Buf<rr_sim_frame> sims;
+  rrmem::Buf<rr_drop> gen_drops;     // staging of rr_generate_drops (host-pointer variant)
   // angular noise on device-generated tables (rr_set_particle_noise, k_noise_chains)
   double noise_std = 0.0, noise_scale = 0.0;
   // the field model (rr_set_particle_model, k_field_particles)
@@ -5736,8 +5746,7 @@ struct rr_ctx {
   double* d_rate = nullptr;               // [rate_n][2] mm^-1: rows (L[i], L[i + 1])
   double cam_hz = 0.0;
   int field_chunks = 0;              // RR_OPT_FIELD_CHUNKS: workgroups per frame (0: sized by the batch)
-  int32_t* d_field_cnt = nullptr;    // [frames][chunks] records per chunk (the count pass)
-  size_t cap_field_cnt = 0;
+  rrmem::Buf<int32_t> field_cnt;     // [frames][chunks] records per chunk (the count pass)
   // the rig model (rr_set_particle_rig, k_rig_particles)
   int rig_n_views = 0, rig_n_active = 0;
   rr_rig_view rig_views[RR_MAX_VIEWS];
@@ -5760,12 +5769,10 @@ struct rr_ctx {
   };
   std::unordered_map<uint32_t, NoiseState> noise_states;
   std::vector<void*> noise_blocks;   // device memory of the states
-  uint8_t* d_noise_desc = nullptr;   // fresh states' rr_sim_frame records + NoiseChain + NoiseOp of a call
-  size_t cap_noise_desc = 0;
+  rrmem::Buf<uint8_t> noise_desc;    // fresh states' rr_sim_frame records + NoiseChain + NoiseOp of a call
   hipEvent_t ev_noise = nullptr;     // behind the last k_noise_chains: the next call's stream waits for it
   bool ev_noise_used = false;
-  int32_t* d_gen_counts = nullptr;
-  size_t cap_gen_drops = 0, cap_gen_counts = 0;
+  rrmem::Buf<int32_t> gen_counts;
   uint8_t* d_lut = nullptr;         // [256][4] RGBA colour map of the rain-mask PNG (rr_set_colormap)
   bool have_lut = false;
   rr_camera cam;
@@ -5783,8 +5790,7 @@ struct rr_ctx {
   // its copy, lets several batches be queued before the first copy has executed.
   struct DescRing {
     static constexpr int N = 2 * RR_PIPE_SLOTS + 2;
-    void* host[N] = {};
-    size_t cap[N] = {};
+    rrmem::PinnedBuf<char> host[N];
     hipEvent_t ev[N] = {};
     bool used[N] = {};
     int next = 0;
@@ -5810,9 +5816,7 @@ struct rr_ctx {
     Staging st;
     hipEvent_t ev_up = nullptr, ev_comp = nullptr, ev_down = nullptr;
     std::vector<HostCopy> down;                       // the batch's device-to-host copies, issued by rr_pipeline_wait
-    CopyPiece *d_up = nullptr, *d_down = nullptr;     // piece lists of the copy kernels
-    CopyPiece *h_up = nullptr, *h_down = nullptr;     // (pinned)
-    size_t cap_up = 0, cap_down = 0;
+    rrmem::MirrorBuf<CopyPiece> up_list, down_list;   // piece lists of the copy kernels, and their pinned sources
     int64_t* h_flags = nullptr;      // pinned: [0] arena-overflow flag as seen after this batch
     bool busy = false, rendered = false;
     std::vector<void*> ext_blobs;     // device copies of caller-made tiles (rr_ext_tile), freed when the slot is reused
@@ -5824,16 +5828,14 @@ struct rr_ctx {
     struct Lens {
       bool armed = false, want_alpha = false;
       int n = 0, H = 0, W = 0, n_work = 0;
-      char *h_block = nullptr, *d_block = nullptr;
-      size_t block_cap = 0, bytes = 0, off_recs = 0, off_work = 0;
-      uint8_t *d_copy = nullptr, *d_label = nullptr, *d_png = nullptr;
-      size_t copy_cap = 0, label_cap = 0, png_cap = 0;
+      rrmem::MirrorBuf<char> block;
+      size_t bytes = 0, off_recs = 0, off_work = 0;
+      rrmem::Buf<uint8_t> copy, label, png;
       std::vector<uint8_t*> alpha_png;                   // the caller's n host buffers (NULL entries allowed), or empty
     } lens;
     // rr_set_input_resize: the batch's source-size inputs (filtered rows, un-filtered bytes, samples), sized by the source and
     // allocated by the first armed batch (grown, never shrunk)
-    uint8_t* d_src = nullptr;
-    size_t src_cap = 0;
+    rrmem::Buf<uint8_t> src;
   } slots[RR_PIPE_SLOTS];
   hipStream_t s_up = nullptr, s_down = nullptr;
   // pre-pass (fog + environment map)
@@ -5874,11 +5876,9 @@ struct rr_ctx {
   std::vector<hipEvent_t> ev_pool;
   // rr_augment_frames_device: one block of scratch (interleaved image, fog layer, xyY map, float64 mask, drop tables, counts),
   // grown to the largest batch seen, never shrunk
-  char* d_aug = nullptr;
-  size_t aug_bytes = 0;
+  rrmem::Buf<char> aug;
   // rr_lens_drops_device: the block a call uploads (blur table, drop records, work list), grown to the largest call seen
-  char* d_lens = nullptr;
-  size_t lens_bytes = 0;
+  rrmem::Buf<char> lens;
   // rr_set_input_resize: the size of the images / depth maps the entry points take while armed
   struct InputResize {
     bool armed = false;
@@ -5905,15 +5905,30 @@ namespace {
     }                                                                                             \
   } while (0)
 
+int mem_error(rr_ctx* ctx, const char* what) {
+  ctx->err = std::string(what) + ": " + hipGetErrorString((hipError_t)ctx->mem.last_error);
+  return RR_E_HIP;
+}
+
+// p's old block freed, max(count, 1) elements of device (pin_alloc: pinned host) memory in its place; p is null after a failure
 template <typename T>
 int dev_alloc(rr_ctx* ctx, T*& p, size_t count) {
-  if (p) {
-    hipFree(p);
-    p = nullptr;
-  }
-  if (count == 0) count = 1;
-  HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
-  return RR_OK;
+  return ctx->mem.alloc(p, count) ? RR_OK : mem_error(ctx, "hipMalloc");
+}
+template <typename T>
+int pin_alloc(rr_ctx* ctx, T*& p, size_t count) {
+  return ctx->mem.alloc_pinned(p, count) ? RR_OK : mem_error(ctx, "hipHostMalloc");
+}
+
+// Room for `need` elements in a grow-only buffer (rr_mem.h): `want` elements (the site's slack; 0: exactly need) are allocated when
+// it is short, behind `sync` -- the wait for whatever may still read the old block.
+template <class B, class Sync>
+int reserve_after(rr_ctx* ctx, B& b, size_t need, size_t want, Sync sync) {
+  return ctx->mem.reserve(b, need, want, sync) ? RR_OK : mem_error(ctx, "reserve");
+}
+template <class B>
+int reserve(rr_ctx* ctx, B& b, size_t need, size_t want = 0, bool sync_first = true) {
+  return reserve_after(ctx, b, need, want, [sync_first] { return sync_first ? (int)hipDeviceSynchronize() : 0; });
 }
 
 hipEvent_t get_event(rr_ctx* ctx) {
@@ -5934,16 +5949,13 @@ int ring_acquire(rr_ctx* ctx, rr_ctx::DescRing& r, size_t bytes, int& idx, void*
   if (!r.ev[idx]) HIPCHK(hipEventCreateWithFlags(&r.ev[idx], hipEventDisableTiming));
   if (r.used[idx]) HIPCHK(hipEventSynchronize(r.ev[idx]));
   r.used[idx] = false;
-  if (bytes > r.cap[idx]) {
-    if (r.host[idx]) HIPCHK(hipHostFree(r.host[idx]));
-    r.host[idx] = nullptr;
-    r.cap[idx] = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    HIPCHK(hipHostMalloc(&r.host[idx], want, hipHostMallocDefault));
-    r.cap[idx] = want;
-  }
-  host = r.host[idx];
-  return RR_OK;
+  const size_t want = bytes + bytes / 2 + 4096;
+  int rc = reserve(ctx, r.host[idx], bytes, want, false);
+  // (the ring's buffers that do not exist yet come with it -- none of them can be in flight --, so that what a context holds is
+  // settled by its first batch of a kind, not by its N-th)
+  for (int k = 0; k < rr_ctx::DescRing::N && !rc; k++) rc = reserve(ctx, r.host[k], 1, want, false);
+  host = r.host[idx].p;
+  return rc;
 }
 int ring_commit(rr_ctx* ctx, rr_ctx::DescRing& r, int idx, hipStream_t s) {
   HIPCHK(hipEventRecord(r.ev[idx], s));
@@ -6017,6 +6029,10 @@ int ensure_scratch(rr_ctx* ctx, int n, int max_drops, const Dims& dm, bool need_
     const int D = grow_drops ? max_drops : ctx->cap_drops;
     const size_t fd = (size_t)F * (size_t)(D > 0 ? D : 1);
     const int Hp = (dm.He + 3) & ~3;
+    // nothing is held until the last array below exists: a failure half-way is followed by a full reallocation, not by a batch
+    // that fits the old record on arrays of mixed sizes
+    ctx->cap_frames = ctx->cap_drops = 0;
+    ctx->cap_dims = Dims{0, 0, 0, 0};
     int rc;
     if ((rc = dev_alloc(ctx, ctx->sc.plan, fd))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.comp, fd))) return rc;
@@ -6107,9 +6123,12 @@ int grow_arena(rr_ctx* ctx) {
   HIPCHK(hipMemcpy(&need, ctx->sc.need_max, sizeof(need), hipMemcpyDeviceToHost));
   if ((int64_t)need > ctx->arena_cap) {
     const int64_t cap = ((int64_t)need + (int64_t)need / 4 + (1 << 16) + 15) & ~15LL;
+    const int F = ctx->cap_frames;
+    ctx->cap_frames = 0;               // (ensure_scratch's record: a failure here is followed by a full reallocation)
     ctx->arena_cap = cap;
-    int rc = dev_alloc(ctx, ctx->sc.arena, (size_t)ctx->cap_frames * (size_t)cap);
+    int rc = dev_alloc(ctx, ctx->sc.arena, (size_t)F * (size_t)cap);
     if (rc) return rc;
+    ctx->cap_frames = F;
   }
   HIPCHK(hipMemset(ctx->sc.need_max, 0, sizeof(unsigned long long)));
   return RR_OK;
@@ -6501,15 +6520,10 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
   for (int f = 0; f < n; f++) wild = wild && !in[f].ext;
   if (wild) {
     const size_t need = (size_t)n * dm.H * dm.W;
-    if (need > ctx->pad_cap) {
-      HIPCHK(hipDeviceSynchronize());
-      int rc;
-      if ((rc = dev_alloc(ctx, ctx->d_pad_first, need))) return rc;
-      if ((rc = dev_alloc(ctx, ctx->d_eff_first, need))) return rc;
-      ctx->pad_cap = need;
-    }
-    sc.pad_first = ctx->d_pad_first;
-    sc.eff_first = ctx->d_eff_first;
+    int rc;
+    if ((rc = reserve(ctx, ctx->pad_first, need)) || (rc = reserve(ctx, ctx->eff_first, need))) return rc;
+    sc.pad_first = ctx->pad_first.p;
+    sc.eff_first = ctx->eff_first.p;
     HIPCHK(hipMemsetAsync(sc.pad_first, 0x7f, sizeof(int32_t) * need, s));
     HIPCHK(hipMemsetAsync(sc.eff_first, 0x7f, sizeof(int32_t) * need, s));
     ProfScope ps(ctx, s, "k_pad_visits");
@@ -6547,16 +6561,16 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     const rr_ctx::Slot::Lens& L = *lens->lens;
     {
       ProfScope ps(ctx, s, "lens_copy");
-      HIPCHK(hipMemcpyAsync(L.d_copy, lens->rgb, (size_t)n * (size_t)lens->rgb_stride, hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemsetAsync(L.d_label, 0, (size_t)n * dm.H * dm.W, s));
+      HIPCHK(hipMemcpyAsync(L.copy.p, lens->rgb, (size_t)n * (size_t)lens->rgb_stride, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemsetAsync(L.label.p, 0, (size_t)n * dm.H * dm.W, s));
     }
     if (L.n_work > 0) {
-      hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(L.h_block), reinterpret_cast<uint32_t*>(L.d_block),
+      hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(L.block.h), reinterpret_cast<uint32_t*>(L.block.d),
                          (int)(L.bytes / 4));
       ProfScope ps(ctx, s, "k_lens_drops_hwc");
-      hipLaunchKernelGGL(k_lens_drops_hwc<true>, dim3((unsigned)L.n_work), dim3(256), 0, s, L.d_copy, lens->rgb_stride, lens->rgb, lens->rgb_stride,
-                         (void*)L.d_label, reinterpret_cast<const LensTable*>(L.d_block), reinterpret_cast<const rr_lens_drop*>(L.d_block + L.off_recs),
-                         reinterpret_cast<const rrlens::WorkItem*>(L.d_block + L.off_work), dm.H, dm.W);
+      hipLaunchKernelGGL(k_lens_drops_hwc<true>, dim3((unsigned)L.n_work), dim3(256), 0, s, L.copy.p, lens->rgb_stride, lens->rgb, lens->rgb_stride,
+                         (void*)L.label.p, reinterpret_cast<const LensTable*>(L.block.d), reinterpret_cast<const rr_lens_drop*>(L.block.d + L.off_recs),
+                         reinterpret_cast<const rrlens::WorkItem*>(L.block.d + L.off_work), dm.H, dm.W);
     }
     want_png = want_png || lens_png;
   }
@@ -6568,20 +6582,15 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
   }
   if (lens_png) {
     ProfScope ps(ctx, s, "k_png_alpha");
-    hipLaunchKernelGGL(k_png_alpha, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, lens->lens->d_label, lens->lens->d_png,
+    hipLaunchKernelGGL(k_png_alpha, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, lens->lens->label.p, lens->lens->png.p,
                        lens->png_stride, dm);
   }
   if (want_png && ctx->png_deflate) {
     const int64_t n_bytes = (int64_t)dm.H * (1 + 4 * (int64_t)dm.W);
     const int nb = (int)rrz::blocks_of(n_bytes);
     const size_t need = (size_t)(lens_png ? 3 : 2) * n * nb;
-    if (need > ctx->pngz_cap) {
-      HIPCHK(hipDeviceSynchronize());
-      int rc;
-      if ((rc = dev_alloc(ctx, ctx->d_pngz_slots, need * rrz::SLOT_BYTES))) return rc;
-      if ((rc = dev_alloc(ctx, ctx->d_pngz_meta, need))) return rc;
-      ctx->pngz_cap = need;
-    }
+    int rc;
+    if ((rc = reserve(ctx, ctx->pngz_slots, need * rrz::SLOT_BYTES)) || (rc = reserve(ctx, ctx->pngz_meta, need))) return rc;
     if (!ctx->pngz_attr) {
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
@@ -6589,14 +6598,14 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     }
     ProfScope ps(ctx, s, "k_pngz");
     if (lens_png) {                                      // image, mask and the label: three streams per frame
-      const PngzLabel<3> label{lens->lens->d_png, lens->png_stride};
-      hipLaunchKernelGGL(k_pngz_blocks<3>, dim3(nb, 3 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots,
-                         ctx->d_pngz_meta, label);
-      hipLaunchKernelGGL(k_pngz_pack<3>, dim3(nb, 3 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta, label);
+      const PngzLabel<3> label{lens->lens->png.p, lens->png_stride};
+      hipLaunchKernelGGL(k_pngz_blocks<3>, dim3(nb, 3 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p,
+                         ctx->pngz_meta.p, label);
+      hipLaunchKernelGGL(k_pngz_pack<3>, dim3(nb, 3 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p, ctx->pngz_meta.p, label);
     } else {
-      hipLaunchKernelGGL(k_pngz_blocks<2>, dim3(nb, 2 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots,
-                         ctx->d_pngz_meta, PngzLabel<2>{});
-      hipLaunchKernelGGL(k_pngz_pack<2>, dim3(nb, 2 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->d_pngz_slots, ctx->d_pngz_meta, PngzLabel<2>{});
+      hipLaunchKernelGGL(k_pngz_blocks<2>, dim3(nb, 2 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p,
+                         ctx->pngz_meta.p, PngzLabel<2>{});
+      hipLaunchKernelGGL(k_pngz_pack<2>, dim3(nb, 2 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p, ctx->pngz_meta.p, PngzLabel<2>{});
     }
   }
   HIPCHK(hipGetLastError());
@@ -6658,6 +6667,8 @@ int enqueue_prepass(rr_ctx* ctx, int n, const rr_prepass_in* in, const rr_prepas
     const int we = We > ctx->pre_We ? We : ctx->pre_We;
     const size_t px = (size_t)H * W, ex = (size_t)H * (we > 0 ? we : 1);
     const bool pl = planes || ctx->pre_planes;
+    ctx->pre_frames = ctx->pre_H = ctx->pre_W = ctx->pre_We = 0;      // nothing held until the last array exists (see ensure_scratch)
+    ctx->pre_planes = false;
     int rc;
     if ((rc = dev_alloc(ctx, ctx->psc.fext, pl ? F * px : 1))) return rc;
     if ((rc = dev_alloc(ctx, ctx->psc.tmpF, pl ? F * px : 1))) return rc;
@@ -6759,7 +6770,7 @@ int enqueue_prepass(rr_ctx* ctx, int n, const rr_prepass_in* in, const rr_prepas
 int noise_states_drop(rr_ctx* ctx) {
   if (ctx->noise_blocks.empty() && ctx->noise_states.empty()) return RR_OK;
   HIPCHK(hipDeviceSynchronize());
-  for (void* b : ctx->noise_blocks) HIPCHK(hipFree(b));
+  for (void*& b : ctx->noise_blocks) ctx->mem.free(b);
   ctx->noise_blocks.clear();
   ctx->noise_states.clear();
   return RR_OK;
@@ -6843,10 +6854,11 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   const int m = (int)fresh.size();
   if (m > 0) {                       // one block: pristine records, state records, pristine counts, state counts
     const size_t recs = (size_t)m * (size_t)stride;
-    void* blk = nullptr;
-    HIPCHK(hipMalloc(&blk, 2 * recs * sizeof(rr_drop) + 2 * (size_t)m * sizeof(int32_t)));
+    char* blk = nullptr;
+    int rc;
+    if ((rc = dev_alloc(ctx, blk, 2 * recs * sizeof(rr_drop) + 2 * (size_t)m * sizeof(int32_t)))) return rc;
     ctx->noise_blocks.push_back(blk);
-    rr_drop* P = static_cast<rr_drop*>(blk);
+    rr_drop* P = reinterpret_cast<rr_drop*>(blk);
     int32_t* C = reinterpret_cast<int32_t*>(P + 2 * recs);
     for (int i = 0; i < m; i++) {
       rr_ctx::NoiseState st;
@@ -6892,11 +6904,7 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   const size_t bytes = b_sims + b_ch + b_ops;
   int rc;
   if (ctx->ev_noise_used) HIPCHK(hipStreamWaitEvent(s, ctx->ev_noise, 0));   // the previous call's chains (and descriptors) first
-  if (bytes > ctx->cap_noise_desc) {
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, ctx->d_noise_desc, bytes + bytes / 2))) return rc;
-    ctx->cap_noise_desc = bytes + bytes / 2;
-  }
+  if ((rc = reserve(ctx, ctx->noise_desc, bytes, bytes + bytes / 2))) return rc;
   int ring_idx;
   void* host;
   if ((rc = ring_acquire(ctx, ctx->ring_noise, bytes, ring_idx, host))) return rc;
@@ -6904,7 +6912,7 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
   if (m) memcpy(h8, fresh.data(), b_sims);
   memcpy(h8 + b_sims, chains.data(), b_ch);
   memcpy(h8 + b_sims + b_ch, ops.data(), b_ops);
-  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_noise_desc),
+  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->noise_desc.p),
                      (int)(bytes / 4));
   if ((rc = ring_commit(ctx, ctx->ring_noise, ring_idx, s))) return rc;
   if (m > 0) {                       // pristine streaks of the fresh states: filtered, tex_index = first texture of the block of ten
@@ -6912,14 +6920,14 @@ int enqueue_noise(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W, rr
     rr_drop* P = ctx->noise_states[fresh_id[0]].pristine;
     with_wind(ctx, [&](auto wnd, auto wa) {
       hipLaunchKernelGGL((k_particles<false, false, decltype(wnd)::value>), dim3(m), dim3(512), 0, s,
-                         reinterpret_cast<const rr_sim_frame*>(ctx->d_noise_desc), H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P,
+                         reinterpret_cast<const rr_sim_frame*>(ctx->noise_desc.p), H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, P,
                          stride, ctx->noise_states[fresh_id[0]].n_pristine, 0, 0.0, wa);
     });
   }
   {
     ProfScope ps(ctx, s, "k_noise_chains");
-    hipLaunchKernelGGL(k_noise_chains, dim3((unsigned)chains.size()), dim3(64), 0, s, reinterpret_cast<const NoiseChain*>(ctx->d_noise_desc + b_sims),
-                       reinterpret_cast<const NoiseOp*>(ctx->d_noise_desc + b_sims + b_ch), H, W, ctx->noise_std, ctx->noise_scale, drops_out,
+    hipLaunchKernelGGL(k_noise_chains, dim3((unsigned)chains.size()), dim3(64), 0, s, reinterpret_cast<const NoiseChain*>(ctx->noise_desc.p + b_sims),
+                       reinterpret_cast<const NoiseOp*>(ctx->noise_desc.p + b_sims + b_ch), H, W, ctx->noise_std, ctx->noise_scale, drops_out,
                        cap, n_out);
   }
   HIPCHK(hipGetLastError());
@@ -7064,17 +7072,13 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
   // the trajectory's rows travel behind the records, in the same buffer and the same copy: n_rows int32 <= n records' room
   const int n_buf = n + (traj ? (int)(((size_t)n_rows * sizeof(int32_t) + sizeof(rr_sim_frame) - 1) / sizeof(rr_sim_frame)) : 0);
   const size_t sims_bytes = sizeof(rr_sim_frame) * (size_t)n + sizeof(int32_t) * (size_t)n_rows;
-  if (n_buf > ctx->cap_sims) {
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, ctx->d_sims, (size_t)n_buf))) return rc;
-    ctx->cap_sims = n_buf;
-  }
+  if ((rc = reserve(ctx, ctx->sims, (size_t)n_buf))) return rc;
   int ring_idx;
   void* host;
   if ((rc = ring_acquire(ctx, ctx->ring_sims, sims_bytes, ring_idx, host))) return rc;
   memcpy(host, sims, sizeof(rr_sim_frame) * (size_t)n);
   if (traj) memcpy(static_cast<uint8_t*>(host) + sizeof(rr_sim_frame) * (size_t)n, ctx->traj_rows.data(), sizeof(int32_t) * (size_t)n_rows);
-  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_sims),
+  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->sims.p),
                      (int)(sims_bytes / 4));
   if ((rc = ring_commit(ctx, ctx->ring_sims, ring_idx, s))) return rc;
   if (field) {
@@ -7093,11 +7097,7 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     chunks = imax(1, imin(imin(chunks, 64), rounds));
     const int chunk_slots = ((rounds + chunks - 1) / chunks) * 512;
     chunks = (rounds * 512 + chunk_slots - 1) / chunk_slots;
-    if (chunks > 1 && (size_t)n * (size_t)chunks > ctx->cap_field_cnt) {
-      HIPCHK(hipDeviceSynchronize());
-      if ((rc = dev_alloc(ctx, ctx->d_field_cnt, (size_t)n * (size_t)chunks))) return rc;
-      ctx->cap_field_cnt = (size_t)n * (size_t)chunks;
-    }
+    if (chunks > 1 && (rc = reserve(ctx, ctx->field_cnt, (size_t)n * (size_t)chunks))) return rc;
     if (rig) {
       RigViews rv;
       memset(&rv, 0, sizeof rv);
@@ -7114,13 +7114,13 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
         TrajArgs<TRAJ> tj;
         if constexpr (TRAJ) {
           tj.poses = ctx->d_traj;
-          tj.rows = reinterpret_cast<const int32_t*>(ctx->d_sims + n);
+          tj.rows = reinterpret_cast<const int32_t*>(ctx->sims.p + n);
           tj.n_views = ctx->rig_n_views;
           for (int a = 0; a < RR_MAX_VIEWS; a++) tj.active[a] = a < rv.n_active ? ctx->rig_active[a] : 0;
         }
         auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, tj, wa, ga, ra);
+          hipLaunchKernelGGL(kern, dim3(chunks, n_wg), dim3(512), 0, s, ctx->sims.p, ctx->cam_hz, rv, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                             ctx->d_ratio_db, drops_out, cap, n_out, ctx->field_cnt.p, chunk_slots, ctx->jitter_deg, tj, wa, ga, ra);
         };
         if (chunks > 1) launch(k_rig_particles<true, false, false, TRAJ, WIND, GUST, RATE>);   // (a count depends neither on the draws nor on the jitter)
         with_draws(ctr, jit, [&](auto c, auto j) { launch(k_rig_particles<false, decltype(c)::value, decltype(j)::value, TRAJ, WIND, GUST, RATE>); });
@@ -7137,8 +7137,8 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
         with_rate(ctx, [&](auto rt, auto ra) {
           constexpr bool WIND = decltype(wnd)::value, GUST = decltype(gst)::value, RATE = decltype(rt)::value;
           auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->d_sims, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
-                               ctx->d_ratio_db, drops_out, cap, n_out, ctx->d_field_cnt, chunk_slots, ctx->jitter_deg, wa, ga, ra);
+            hipLaunchKernelGGL(kern, dim3(chunks, n), dim3(512), 0, s, ctx->sims.p, ctx->cam_hz, H, W, ctx->d_dgrid, ctx->d_cdf, ctx->n_grid,
+                               ctx->d_ratio_db, drops_out, cap, n_out, ctx->field_cnt.p, chunk_slots, ctx->jitter_deg, wa, ga, ra);
           };
           if (chunks > 1) launch(k_field_particles<true, false, false, WIND, GUST, RATE>);
           with_draws(ctr, jit, [&](auto c, auto j) { launch(k_field_particles<false, decltype(c)::value, decltype(j)::value, WIND, GUST, RATE>); });
@@ -7147,7 +7147,7 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
-      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, 0);
+      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->sims.p, drops_out, cap, n_out, 0);
     }
   } else if (n_noisy < n) {                                  // frames with angular noise are left to k_noise_chains
     {
@@ -7155,14 +7155,14 @@ int enqueue_particles(rr_ctx* ctx, int n, const rr_sim_frame* sims, int H, int W
       // skip_run: frames with run_pos != 0 are k_noise_chains' (none under the jitter or the counter draws: refused above)
       with_wind(ctx, [&](auto wnd, auto wa) {
         with_draws(ctr, jit, [&](auto c, auto j) {
-          hipLaunchKernelGGL((k_particles<decltype(c)::value, decltype(j)::value, decltype(wnd)::value>), dim3(n), dim3(512), 0, s, ctx->d_sims, H, W,
+          hipLaunchKernelGGL((k_particles<decltype(c)::value, decltype(j)::value, decltype(wnd)::value>), dim3(n), dim3(512), 0, s, ctx->sims.p, H, W,
                              ctx->d_dgrid, ctx->d_cdf, ctx->n_grid, ctx->d_ratio_db, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0, ctx->jitter_deg, wa);
         });
       });
     }
     if (!ctr) {
       ProfScope ps(ctx, s, "k_particle_draws");
-      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->d_sims, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
+      hipLaunchKernelGGL(k_particle_draws, dim3(n), dim3(64), 0, s, ctx->sims.p, drops_out, cap, n_out, n_noisy > 0 ? 1 : 0);
     }
   }
   HIPCHK(hipGetLastError());
@@ -7216,12 +7216,12 @@ int rr_create(rr_ctx** out, int device) {
   }
   float tab[128];
   build_cubic_tab(tab);
-  if (hipMalloc((void**)&ctx->d_ctab, sizeof(tab)) != hipSuccess ||
+  if (dev_alloc(ctx, ctx->d_ctab, 128) != RR_OK ||
       hipMemcpy(ctx->d_ctab, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess ||
       // arena-overflow flags (one per pipeline slot + one for the device-pointer calls + AUG_FLAG) and the sticky largest need
-      hipMalloc((void**)&ctx->sc.overflow, sizeof(int32_t) * (2 + RR_PIPE_SLOTS)) != hipSuccess ||
+      dev_alloc(ctx, ctx->sc.overflow, 2 + RR_PIPE_SLOTS) != RR_OK ||
       hipMemset(ctx->sc.overflow, 0, sizeof(int32_t) * (2 + RR_PIPE_SLOTS)) != hipSuccess ||
-      hipMalloc((void**)&ctx->sc.need_max, sizeof(unsigned long long)) != hipSuccess ||
+      dev_alloc(ctx, ctx->sc.need_max, 1) != RR_OK ||
       hipMemset(ctx->sc.need_max, 0, sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     rr_destroy(ctx);
     return RR_E_HIP;
@@ -7234,152 +7234,28 @@ int rr_destroy(rr_ctx* ctx) {
   if (!ctx) return RR_E_ARG;
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
-  if (ctx->own_tex) hipFree(ctx->d_tex);
-  hipFree(ctx->d_tex_h);
-  hipFree(ctx->d_tex_w);
-  hipFree(ctx->d_tex_off);
-  hipFree(ctx->d_tex_pad);
-  hipFree(ctx->d_tex_poff);
-  hipFree(ctx->d_ctab);
-  hipFree(ctx->d_lut);
-  hipFree(ctx->sc.plan);
-  hipFree(ctx->sc.comp);
-  hipFree(ctx->sc.comp32);
-  hipFree(ctx->sc.poly);
-  hipFree(ctx->sc.npts);
-  hipFree(ctx->sc.sizes);
-  hipFree(ctx->sc.list_rot);
-  hipFree(ctx->sc.fov_erec);
-  hipFree(ctx->sc.fov_pix);
-  hipFree(ctx->sc.fov_rec);
-  hipFree(ctx->sc.fov_order);
-  hipFree(ctx->sc.fov_slot);
-  hipFree(ctx->sc.rows_list);
-  hipFree(ctx->sc.rows_sorted);
-  hipFree(ctx->sc.rows_n);
-  hipFree(ctx->sc.rows_hist);
-  hipFree(ctx->sc.rows_fbase);
-  hipFree(ctx->sc.rows_bounds);
-  hipFree(ctx->d_tex_pair);
-  hipFree(ctx->d_tex_qoff);
-  hipFree(ctx->sc.fov_list);
-  hipFree(ctx->sc.fov_list_n);
-  hipFree(ctx->sc.list_gen);
-  hipFree(ctx->sc.list_slow);
-  hipFree(ctx->sc.blur_items);
-  hipFree(ctx->sc.counts);
-  hipFree(ctx->sc.canon);
-  hipFree(ctx->sc.bigs_list);
-  hipFree(ctx->sc.bigs_n);
-  hipFree(ctx->sc.tkey);
-  hipFree(ctx->sc.lrec);
-  hipFree(ctx->sc.list_big);
-  hipFree(ctx->sc.big_off);
-  hipFree(ctx->sc.htab);
-  hipFree(ctx->sc.list_small);
-  hipFree(ctx->sc.colpart);
-  hipFree(ctx->sc.wtab);
-  hipFree(ctx->sc.wtab_big);
-  hipFree(ctx->sc.spans);
-  hipFree(ctx->sc.bbox);
-  hipFree(ctx->sc.blended);
-  hipFree(ctx->d_pad_first);
-  hipFree(ctx->d_pngz_slots);
-  hipFree(ctx->d_pngz_meta);
-  hipFree(ctx->d_eff_first);
-  hipFree(ctx->sc.clist);
-  hipFree(ctx->sc.ccount);
-  hipFree(ctx->sc.prefix);
-  hipFree(ctx->sc.fband);
-  hipFree(ctx->sc.arena);
-  hipFree(ctx->sc.partial);
-  hipFree(ctx->sc.means);
-  hipFree(ctx->sc.arena_need);
-  hipFree(ctx->sc.overflow);
-  hipFree(ctx->sc.need_max);
-  hipFree(ctx->d_omega);
-  hipFree(ctx->d_omega32);
-  hipFree(ctx->d_aug);
-  hipFree(ctx->d_lens);
-  hipFree(ctx->d_dgrid);
-  hipFree(ctx->d_cdf);
-  hipFree(ctx->d_ratio_db);
-  hipFree(ctx->d_sims);
-  hipFree(ctx->d_traj);
-  hipFree(ctx->d_gust);
-  hipFree(ctx->d_rate);
-  hipFree(ctx->d_gen_drops);
-  hipFree(ctx->d_gen_counts);
-  hipFree(ctx->d_field_cnt);
-  for (void* b : ctx->noise_blocks) hipFree(b);
-  hipFree(ctx->d_noise_desc);
   if (ctx->ev_noise) hipEventDestroy(ctx->ev_noise);
   for (auto* r : {&ctx->ring_frames, &ctx->ring_pre, &ctx->ring_sims, &ctx->ring_noise, &ctx->ring_lens})
-    for (int k = 0; k < rr_ctx::DescRing::N; k++) {
-      if (r->host[k]) hipHostFree(r->host[k]);
+    for (int k = 0; k < rr_ctx::DescRing::N; k++)
       if (r->ev[k]) hipEventDestroy(r->ev[k]);
-    }
-  hipFree(ctx->d_frames);
-  hipFree(ctx->d_comp_out);
   for (auto& sl : ctx->slots) {
-    hipFree(sl.st.bg);
-    hipFree(sl.st.rainy);
-    hipFree(sl.st.env);
-    hipFree(sl.st.omega);
-    hipFree(sl.st.comp);
-    hipFree(sl.st.mask);
-    hipFree(sl.st.drops);
-    hipFree(sl.st.rgb);
-    hipFree(sl.st.mask_i);
-    hipFree(sl.st.status);
-    hipFree(sl.st.colour);
-    hipFree(sl.st.ndrops);
-    hipFree(sl.st.depth);
-    hipFree(sl.st.env_u8);
-    hipFree(sl.st.bg8);
-    hipFree(sl.st.png_i);
-    hipFree(sl.st.png_m);
     if (sl.ev_up) hipEventDestroy(sl.ev_up);
     if (sl.ev_comp) hipEventDestroy(sl.ev_comp);
     if (sl.ev_down) hipEventDestroy(sl.ev_down);
-    if (sl.h_flags) hipHostFree(sl.h_flags);
-    hipFree(sl.d_up);
-    hipFree(sl.d_down);
-    if (sl.h_up) hipHostFree(sl.h_up);
-    if (sl.h_down) hipHostFree(sl.h_down);
-    for (void* b : sl.ext_blobs) hipFree(b);
-    if (sl.lens.h_block) hipHostFree(sl.lens.h_block);
-    hipFree(sl.lens.d_block);
-    hipFree(sl.lens.d_copy);
-    hipFree(sl.lens.d_label);
-    hipFree(sl.lens.d_png);
-    hipFree(sl.d_src);
   }
   if (ctx->s_col) hipStreamDestroy(ctx->s_col);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
   if (ctx->s_up) hipStreamDestroy(ctx->s_up);
   if (ctx->s_down) hipStreamDestroy(ctx->s_down);
-  hipFree(ctx->d_esrc);
-  hipFree(ctx->d_etop);
-  hipFree(ctx->d_ebot);
-  hipFree(ctx->d_pre);
-  hipFree(ctx->psc.fext);
-  hipFree(ctx->psc.tmpF);
-  hipFree(ctx->psc.tmpL);
-  hipFree(ctx->psc.r8);
-  hipFree(ctx->d_need_h);
-  hipFree(ctx->psc.part);
-  hipFree(ctx->psc.mean);
-  hipFree(ctx->psc.epack);
-  hipFree(ctx->psc.etmp);
   for (auto& pe : ctx->prof_pending) {
     hipEventDestroy(pe.a);
     hipEventDestroy(pe.b);
   }
   for (auto e : ctx->ev_pool) hipEventDestroy(e);
-  for (auto& blk : ctx->host_allocs) hipHostFree(const_cast<char*>(blk.first));      // rr_host_alloc blocks the caller kept
   if (ctx->stream) hipStreamDestroy(ctx->stream);
+  for (auto& blk : ctx->host_allocs) hipHostFree(const_cast<char*>(blk.first));      // rr_host_alloc blocks the caller kept
+  ctx->mem.release_all();
   delete ctx;
   return RR_OK;
 }
@@ -7447,6 +7323,20 @@ static int set_db_meta(rr_ctx* ctx, const int32_t* tex_h, const int32_t* tex_w, 
   return RR_OK;
 }
 
+// A texel buffer of n_bytes of the context's own in place of the one it had.  The context has no database from here until
+// set_db_meta has made the tables for the new texels, so a copy, a broadcast or an allocation that fails in between leaves
+// "no streak database" behind, not the old tables over new or missing texels.
+static int install_tex(rr_ctx* ctx, int64_t n_bytes) {
+  ctx->have_db = false;
+  ctx->own_tex = false;
+  ctx->tex_bytes = 0;
+  const int rc = dev_alloc(ctx, ctx->d_tex, (size_t)n_bytes);
+  if (rc) return rc;
+  ctx->own_tex = true;
+  ctx->tex_bytes = n_bytes;
+  return RR_OK;
+}
+
 int rr_set_streak_db(rr_ctx* ctx, const uint8_t* texels, const int32_t* tex_h, const int32_t* tex_w, const int64_t* tex_off,
                      int32_t n_tex) {
   if (!ctx) return RR_E_ARG;
@@ -7465,12 +7355,9 @@ int rr_set_streak_db(rr_ctx* ctx, const uint8_t* texels, const int32_t* tex_h, c
     int64_t end = tex_off[i] + (int64_t)tex_h[i] * tex_w[i];
     if (end > total) total = end;
   }
-  if (ctx->own_tex && ctx->d_tex) hipFree(ctx->d_tex);
-  ctx->d_tex = nullptr;
-  HIPCHK(hipMalloc((void**)&ctx->d_tex, (size_t)total));
-  ctx->own_tex = true;
+  const int rc = install_tex(ctx, total);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(ctx->d_tex, texels, (size_t)total, hipMemcpyHostToDevice));
-  ctx->tex_bytes = total;
   return set_db_meta(ctx, tex_h, tex_w, tex_off, n_tex);
 }
 
@@ -7489,13 +7376,10 @@ int rr_set_streak_db_device(rr_ctx* ctx, const uint8_t* texels_dev, int64_t n_by
       return RR_E_ARG;
     }
   }
-  if (ctx->own_tex && ctx->d_tex) hipFree(ctx->d_tex);
-  ctx->d_tex = nullptr;
   // private copy: the caller's (broadcast) buffer may be released afterwards
-  HIPCHK(hipMalloc((void**)&ctx->d_tex, (size_t)n_bytes));
-  ctx->own_tex = true;
+  const int rc = install_tex(ctx, n_bytes);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(ctx->d_tex, texels_dev, (size_t)n_bytes, hipMemcpyDeviceToDevice));
-  ctx->tex_bytes = n_bytes;
   return set_db_meta(ctx, tex_h, tex_w, tex_off, n_tex);
 }
 
@@ -7572,9 +7456,14 @@ int rr_bcast_selftest(rr_ctx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipDeviceSynchronize());
   uint8_t* tmp = nullptr;
-  HIPCHK(hipMalloc((void**)&tmp, (size_t)ctx->tex_bytes));
-  HIPCHK(hipMemset(tmp, 0xa5, (size_t)ctx->tex_bytes));
-  int rc = rccl_bcast({ctx->device}, ctx->d_tex, {tmp}, {ctx->stream}, (size_t)ctx->tex_bytes, ctx->err);
+  int rc = dev_alloc(ctx, tmp, (size_t)ctx->tex_bytes);
+  if (rc) return rc;
+  if (hipMemset(tmp, 0xa5, (size_t)ctx->tex_bytes) != hipSuccess) {
+    ctx->mem.free(tmp);
+    ctx->err = "rr_bcast_selftest: hipMemset failed";
+    return RR_E_HIP;
+  }
+  rc = rccl_bcast({ctx->device}, ctx->d_tex, {tmp}, {ctx->stream}, (size_t)ctx->tex_bytes, ctx->err);
   if (rc == RR_OK) {
     std::vector<uint8_t> a((size_t)ctx->tex_bytes), b((size_t)ctx->tex_bytes);
     if (hipMemcpy(a.data(), ctx->d_tex, a.size(), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -7586,7 +7475,7 @@ int rr_bcast_selftest(rr_ctx* ctx) {
       rc = RR_E_HIP;
     }
   }
-  hipFree(tmp);
+  ctx->mem.free(tmp);
   return rc;
 }
 
@@ -7612,11 +7501,8 @@ int rr_bcast_streak_db(rr_ctx** ctxs, int32_t n_ctx) {
     rr_ctx* c = ctxs[i];
     HIPCHK_CTX(c, hipSetDevice(c->device));
     HIPCHK_CTX(c, hipDeviceSynchronize());
-    if (c->own_tex && c->d_tex) hipFree(c->d_tex);
-    c->d_tex = nullptr;
-    HIPCHK_CTX(c, hipMalloc((void**)&c->d_tex, (size_t)nb));
-    c->own_tex = true;
-    c->tex_bytes = nb;
+    const int rc = install_tex(c, nb);       // (no database on c from here until its set_db_meta below has succeeded)
+    if (rc) return rc;
     if (c->device == root->device) HIPCHK_CTX(c, hipMemcpy(c->d_tex, root->d_tex, (size_t)nb, hipMemcpyDeviceToDevice));
     else remote.push_back(c);
   }
@@ -7736,19 +7622,10 @@ int rr_generate_drops(rr_ctx* ctx, int32_t n, const rr_sim_frame* frames, int32_
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   const size_t nd = (size_t)n * (size_t)cap;
-  if (nd > ctx->cap_gen_drops) {
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, ctx->d_gen_drops, nd))) return rc;
-    ctx->cap_gen_drops = nd;
-  }
-  if ((size_t)n > ctx->cap_gen_counts) {
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, ctx->d_gen_counts, (size_t)n))) return rc;
-    ctx->cap_gen_counts = (size_t)n;
-  }
-  if ((rc = enqueue_particles(ctx, n, frames, H, W, ctx->d_gen_drops, cap, ctx->d_gen_counts, ctx->stream))) return rc;
-  HIPCHK(hipMemcpyAsync(n_out, ctx->d_gen_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(drops_out, ctx->d_gen_drops, sizeof(rr_drop) * nd, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = reserve(ctx, ctx->gen_drops, nd)) || (rc = reserve(ctx, ctx->gen_counts, (size_t)n))) return rc;
+  if ((rc = enqueue_particles(ctx, n, frames, H, W, ctx->gen_drops.p, cap, ctx->gen_counts.p, ctx->stream))) return rc;
+  HIPCHK(hipMemcpyAsync(n_out, ctx->gen_counts.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(drops_out, ctx->gen_drops.p, sizeof(rr_drop) * nd, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return RR_OK;
 }
@@ -8142,7 +8019,7 @@ bool host_is_pinned(const void* p) {
 
 // The copies of one direction of one slot.  Pieces whose host side is pinned and whose ends are 16-byte aligned (or that
 // are tiny) go into ONE launch of k_copy_pieces; the rest -- pageable or oddly aligned buffers -- one hipMemcpyAsync each.
-int issue(rr_ctx* ctx, const CopyList& cl, hipMemcpyKind kind, hipStream_t s, CopyPiece*& d_list, CopyPiece*& h_list, size_t& cap) {
+int issue(rr_ctx* ctx, const CopyList& cl, hipMemcpyKind kind, hipStream_t s, rrmem::MirrorBuf<CopyPiece>& list) {
   std::vector<CopyPiece> ker;
   const bool up = kind == hipMemcpyHostToDevice;
   const void* last_base = nullptr;
@@ -8166,21 +8043,12 @@ int issue(rr_ctx* ctx, const CopyList& cl, hipMemcpyKind kind, hipStream_t s, Co
     else HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, kind, s));
   }
   if (!ker.empty()) {
-    if (ker.size() > cap) {
-      HIPCHK(hipStreamSynchronize(s));
-      if (d_list) HIPCHK(hipFree(d_list));
-      if (h_list) HIPCHK(hipHostFree(h_list));
-      d_list = h_list = nullptr;
-      cap = 0;
-      const size_t want = ker.size() * 2 + 64;
-      HIPCHK(hipMalloc((void**)&d_list, want * sizeof(CopyPiece)));
-      HIPCHK(hipHostMalloc((void**)&h_list, want * sizeof(CopyPiece), hipHostMallocDefault));
-      cap = want;
-    }
+    int rc = reserve_after(ctx, list, ker.size(), ker.size() * 2 + 64, [s] { return (int)hipStreamSynchronize(s); });
+    if (rc) return rc;
     // (the slot is not in flight: its previous lists have been consumed)
-    memcpy(h_list, ker.data(), ker.size() * sizeof(CopyPiece));
-    HIPCHK(hipMemcpyAsync(d_list, h_list, ker.size() * sizeof(CopyPiece), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_copy_pieces, dim3(128), dim3(256), 0, s, d_list, (int)ker.size());
+    memcpy(list.h, ker.data(), ker.size() * sizeof(CopyPiece));
+    HIPCHK(hipMemcpyAsync(list.d, list.h, ker.size() * sizeof(CopyPiece), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_copy_pieces, dim3(128), dim3(256), 0, s, list.d, (int)ker.size());
   }
   return RR_OK;
 }
@@ -8212,6 +8080,8 @@ int slot_reserve(rr_ctx* ctx, rr_ctx::Staging& st, int n, int max_drops, const D
     HIPCHK(hipDeviceSynchronize());
     const Strides t = strides_of(dm);
     int F = n > st.frames ? n : st.frames, D = max_drops > st.drops_cap ? max_drops : st.drops_cap, rc;
+    st.frames = st.drops_cap = 0;                        // nothing held until the last array exists (see ensure_scratch)
+    st.dims = Dims{0, 0, 0, 0};
     if ((rc = dev_alloc(ctx, st.bg, F * t.px3d))) return rc;
     if ((rc = dev_alloc(ctx, st.rainy, F * t.px3d))) return rc;
     if ((rc = dev_alloc(ctx, st.env, F * t.ex3d))) return rc;
@@ -8245,8 +8115,7 @@ int slot_init(rr_ctx* ctx, rr_ctx::Slot& sl) {
   HIPCHK(hipEventCreateWithFlags(&sl.ev_up, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&sl.ev_comp, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&sl.ev_down, hipEventDisableTiming));
-  HIPCHK(hipHostMalloc((void**)&sl.h_flags, sizeof(int64_t) * 2, hipHostMallocDefault));
-  return RR_OK;
+  return pin_alloc(ctx, sl.h_flags, 2);
 }
 
 // The input stage of rr_set_input_resize on `s`: n frames of the armed source size at `src` (src_stride bytes apart, inside the
@@ -8455,7 +8324,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     return RR_E_ARG;
   }
   if ((rc = slot_init(ctx, sl))) return rc;
-  for (void* b : sl.ext_blobs) hipFree(b);             // the slot's previous batch is complete (not busy)
+  for (void*& b : sl.ext_blobs) ctx->mem.free(b);      // the slot's previous batch is complete (not busy)
   sl.ext_blobs.clear();
   auto& st = sl.st;
   // Staging strides that follow the caller's layout where that lets a whole array travel as one copy: drop tables laid
@@ -8525,17 +8394,12 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     rs_drows = rs_img + r16((size_t)R.sH * R.sW * 3);
     rs_dep = rs_drows + (pre[0].depth_f64 == RR_DEPTH_PNG_ROWS ? r16((size_t)R.dH * (1 + 2 * (size_t)R.dW)) : 0);
     rs_frame = rs_dep + r16((size_t)R.dH * R.dW * 4);
-    if ((size_t)n * rs_frame > sl.src_cap) {
-      HIPCHK(hipDeviceSynchronize());
-      sl.src_cap = 0;
-      if ((rc = dev_alloc(ctx, sl.d_src, (size_t)n * rs_frame))) return rc;
-      sl.src_cap = (size_t)n * rs_frame;
-    }
+    if ((rc = reserve(ctx, sl.src, (size_t)n * rs_frame))) return rc;
   }
   // ---- upload ----
   for (int f = 0; rsz && f < n; f++) {
     pin[f] = pre[f];
-    uint8_t* const fs = sl.d_src + (size_t)f * rs_frame;
+    uint8_t* const fs = sl.src.p + (size_t)f * rs_frame;
     const void* src = pre[f].bg_u8 ? (const void*)pre[f].bg_u8 : pre[f].bg;
     if (pre[f].in_types & RR_IN_BG_PNG_ROWS) up.add(fs + rs_irows, src, (size_t)R.sH * (1 + 3 * (size_t)R.sW));
     else up.add(fs + rs_img, src, (size_t)R.sH * R.sW * 3);
@@ -8652,7 +8516,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
         bytes += sizeof(double) * ((size_t)e.tw * e.th + 2 * (size_t)e.n_poly);
       }
       char* blob = nullptr;
-      HIPCHK(hipMalloc((void**)&blob, bytes));
+      if ((rc = dev_alloc(ctx, blob, bytes))) return rc;
       sl.ext_blobs.push_back(blob);
       std::vector<rr_ext_tile> dev(in[f].ext, in[f].ext + nd);
       size_t off = sizeof(rr_ext_tile) * (size_t)nd;
@@ -8680,7 +8544,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     (void)hipStreamSynchronize(s);
     return code;
   };
-  if ((rc = issue(ctx, up, hipMemcpyHostToDevice, ctx->s_up, sl.d_up, sl.h_up, sl.cap_up))) return drained(rc);
+  if ((rc = issue(ctx, up, hipMemcpyHostToDevice, ctx->s_up, sl.up_list))) return drained(rc);
   if (hipEventRecord(sl.ev_up, ctx->s_up) != hipSuccess || hipStreamWaitEvent(s, sl.ev_up, 0) != hipSuccess) {
     ctx->err = "pipeline: hipEventRecord / hipStreamWaitEvent failed";
     return drained(RR_E_HIP);
@@ -8690,16 +8554,16 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if ((pre[0].in_types & RR_IN_BG_PNG_ROWS) || pre[0].depth_f64 == RR_DEPTH_PNG_ROWS) {
       ProfScope ps(ctx, s, "k_png_unfilter");
       if (pre[0].in_types & RR_IN_BG_PNG_ROWS)
-        hipLaunchKernelGGL(k_png_unfilter<3>, dim3(n), dim3(64), 3 * (size_t)R.sW, s, sl.d_src + rs_irows, (int64_t)rs_frame, sl.d_src + rs_img,
+        hipLaunchKernelGGL(k_png_unfilter<3>, dim3(n), dim3(64), 3 * (size_t)R.sW, s, sl.src.p + rs_irows, (int64_t)rs_frame, sl.src.p + rs_img,
                            (int64_t)rs_frame, R.sH, R.sW);
       if (pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)
-        hipLaunchKernelGGL(k_png_unfilter<2>, dim3(n), dim3(64), 2 * (size_t)R.dW, s, sl.d_src + rs_drows, (int64_t)rs_frame, sl.d_src + rs_dep,
+        hipLaunchKernelGGL(k_png_unfilter<2>, dim3(n), dim3(64), 2 * (size_t)R.dW, s, sl.src.p + rs_drows, (int64_t)rs_frame, sl.src.p + rs_dep,
                            (int64_t)rs_frame, R.dH, R.dW);
     }
-    const uint8_t* const hi = sl.d_src + (size_t)n * rs_frame;
-    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, RSZ_BGR8, sl.d_src + rs_img, (int64_t)rs_frame, sl.d_src, hi, st.bg, (int64_t)(T.px3d * 8), s)))
+    const uint8_t* const hi = sl.src.p + (size_t)n * rs_frame;
+    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, RSZ_BGR8, sl.src.p + rs_img, (int64_t)rs_frame, sl.src.p, hi, st.bg, (int64_t)(T.px3d * 8), s)))
       return drained(rc);
-    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, pre[0].depth_f64 == 0 ? RSZ_DF32 : RSZ_D16, sl.d_src + rs_dep, (int64_t)rs_frame, sl.d_src, hi,
+    if ((rc = enqueue_resize(ctx, n, dm.H, dm.W, pre[0].depth_f64 == 0 ? RSZ_DF32 : RSZ_D16, sl.src.p + rs_dep, (int64_t)rs_frame, sl.src.p, hi,
                              st.depth, (int64_t)depth_stride, s)))
       return drained(rc);
   } else if (pre && ((pre[0].in_types & RR_IN_BG_PNG_ROWS) || pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)) {
@@ -8735,7 +8599,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if (out[f].n_drops_out && in[f].sim) down.add(out[f].n_drops_out, st.ndrops + f, sizeof(int32_t));
     if (out[f].rainy_png) down.add(out[f].rainy_png, dout[f].rainy_png, png_bytes);
     if (out[f].mask_png) down.add(out[f].mask_png, dout[f].mask_png, png_bytes);
-    if (sl.lens.armed && sl.lens.want_alpha && sl.lens.alpha_png[(size_t)f]) down.add(sl.lens.alpha_png[(size_t)f], sl.lens.d_png + (size_t)f * T.pngb, png_bytes);
+    if (sl.lens.armed && sl.lens.want_alpha && sl.lens.alpha_png[(size_t)f]) down.add(sl.lens.alpha_png[(size_t)f], sl.lens.png.p + (size_t)f * T.pngb, png_bytes);
   }
   for (int f = 0; pre && pre_out && f < n; f++) {
     if (pre_out[f].rainy_bg && pre[f].mode != RR_PRE_ENV_ONLY) down.add(pre_out[f].rainy_bg, pout[f].rainy_bg, px * 3 * rainy_el);
@@ -8763,7 +8627,7 @@ int host_wait(rr_ctx* ctx, int slot) {
     CopyList down;
     down.v = std::move(sl.down);
     sl.down.clear();
-    int rc = issue(ctx, down, hipMemcpyDeviceToHost, ctx->s_down, sl.d_down, sl.h_down, sl.cap_down);
+    int rc = issue(ctx, down, hipMemcpyDeviceToHost, ctx->s_down, sl.down_list);
     if (rc) {                                            // (nothing may keep writing the caller's buffers after an error)
       (void)hipStreamSynchronize(ctx->s_down);
       sl.busy = false;
@@ -8837,15 +8701,11 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   const size_t s_bg = rnd(px * 3 * (rsz ? 8 : bel)), s_rainy = rnd(px * 3 * 4), s_env = rnd((size_t)H * We * 3 * 4), s_mask = rnd(px * 8);
   const size_t b_drops = rnd((size_t)n * cap * sizeof(rr_drop)), b_counts = rnd((size_t)n * 4), s_dep = rsz_depth ? rnd(px * 4) : 0;
   const size_t need = (size_t)n * (s_bg + s_rainy + s_env + s_mask + s_dep) + b_drops + b_counts;
-  if (need > ctx->aug_bytes) {
-    HIPCHK(hipDeviceSynchronize());
-    if (ctx->d_aug) HIPCHK(hipFree(ctx->d_aug));
-    ctx->d_aug = nullptr;
-    ctx->aug_bytes = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_aug, need));
-    ctx->aug_bytes = need;
+  {
+    const int rc = reserve(ctx, ctx->aug, need);
+    if (rc) return rc;
   }
-  char* const bg = ctx->d_aug;
+  char* const bg = ctx->aug.p;
   char* const rainy = bg + (size_t)n * s_bg;
   char* const env = rainy + (size_t)n * s_rainy;
   char* const mask = env + (size_t)n * s_env;
@@ -9005,17 +8865,9 @@ int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
   if (work.empty()) return RR_OK;
   const size_t off_recs = sizeof(LensTable), off_work = off_recs + recs.size() * sizeof(rr_lens_drop);
   const size_t bytes = off_work + work.size() * sizeof(rrlens::WorkItem);
-  if (bytes > ctx->lens_bytes) {
-    HIPCHK(hipDeviceSynchronize());
-    if (ctx->d_lens) HIPCHK(hipFree(ctx->d_lens));
-    ctx->d_lens = nullptr;
-    ctx->lens_bytes = 0;
-    const size_t want = bytes + bytes / 2;
-    HIPCHK(hipMalloc((void**)&ctx->d_lens, want));
-    ctx->lens_bytes = want;
-  }
   int rc, ring_idx;
   void* host;
+  if ((rc = reserve(ctx, ctx->lens, bytes, bytes + bytes / 2))) return rc;
   if ((rc = ring_acquire(ctx, ctx->ring_lens, bytes, ring_idx, host))) return rc;
   LensTable* tab = static_cast<LensTable*>(host);
   memset(tab, 0, sizeof(LensTable));
@@ -9025,12 +8877,12 @@ int lens_drops(rr_ctx* ctx, const rr_lens_batch* b, hipStream_t s) {
   }
   memcpy(static_cast<char*>(host) + off_recs, recs.data(), recs.size() * sizeof(rr_lens_drop));
   memcpy(static_cast<char*>(host) + off_work, work.data(), work.size() * sizeof(rrlens::WorkItem));
-  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->d_lens),
+  hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->lens.p),
                      (int)(bytes / 4));
   if ((rc = ring_commit(ctx, ctx->ring_lens, ring_idx, s))) return rc;
-  const LensTable* d_tab = reinterpret_cast<const LensTable*>(ctx->d_lens);
-  const rr_lens_drop* d_recs = reinterpret_cast<const rr_lens_drop*>(ctx->d_lens + off_recs);
-  const rrlens::WorkItem* d_work = reinterpret_cast<const rrlens::WorkItem*>(ctx->d_lens + off_work);
+  const LensTable* d_tab = reinterpret_cast<const LensTable*>(ctx->lens.p);
+  const rr_lens_drop* d_recs = reinterpret_cast<const rr_lens_drop*>(ctx->lens.p + off_recs);
+  const rrlens::WorkItem* d_work = reinterpret_cast<const rrlens::WorkItem*>(ctx->lens.p + off_work);
   if (b->dtype == RR_TENSOR_U8_HWC) {
     ProfScope ps(ctx, s, "k_lens_drops_hwc");
     hipLaunchKernelGGL(k_lens_drops_hwc<false>, dim3((unsigned)work.size()), dim3(256), 0, s, static_cast<const uint8_t*>(b->images), (int64_t)(3 * px),
@@ -9099,37 +8951,19 @@ int set_lens(rr_ctx* ctx, int slot, const rr_pipeline_lens* b) {
   // (the slot is not in flight: nothing reads its blocks.  A failed allocation leaves the slot disarmed.)
   L.armed = false;
   L.alpha_png.clear();
-  if (bytes > L.block_cap) {
-    if (L.h_block) HIPCHK(hipHostFree(L.h_block));
-    if (L.d_block) HIPCHK(hipFree(L.d_block));
-    L.h_block = L.d_block = nullptr;
-    L.block_cap = 0;
-    const size_t want = bytes + bytes / 2;
-    HIPCHK(hipHostMalloc((void**)&L.h_block, want, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&L.d_block, want));
-    L.block_cap = want;
-  }
-  auto grow = [&](uint8_t*& p, size_t& cap, size_t need) -> int {
-    if (need <= cap) return RR_OK;
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    HIPCHK(hipMalloc((void**)&p, need));
-    cap = need;
-    return RR_OK;
-  };
   int rc;
-  if ((rc = grow(L.d_copy, L.copy_cap, (size_t)n * T.px3b))) return rc;
-  if ((rc = grow(L.d_label, L.label_cap, (size_t)n * H * W))) return rc;
-  if (want_alpha && (rc = grow(L.d_png, L.png_cap, (size_t)n * T.pngb))) return rc;
-  LensTable* tab = reinterpret_cast<LensTable*>(L.h_block);
+  if ((rc = reserve(ctx, L.block, bytes, bytes + bytes / 2, false))) return rc;
+  if ((rc = reserve(ctx, L.copy, (size_t)n * T.px3b, 0, false))) return rc;
+  if ((rc = reserve(ctx, L.label, (size_t)n * H * W, 0, false))) return rc;
+  if (want_alpha && (rc = reserve(ctx, L.png, (size_t)n * T.pngb, 0, false))) return rc;
+  LensTable* tab = reinterpret_cast<LensTable*>(L.block.h);
   memset(tab, 0, sizeof(LensTable));
   for (int c = 0; c < b->n_classes; c++) {
     tab->radius[c] = b->class_radius[c];
     memcpy(tab->w + c * rrlens::TAPS, b->weights + c * rrlens::TAPS, sizeof(float) * (size_t)(2 * b->class_radius[c] + 1));
   }
-  memcpy(L.h_block + off_recs, recs.data(), recs.size() * sizeof(rr_lens_drop));
-  memcpy(L.h_block + off_work, work.data(), work.size() * sizeof(rrlens::WorkItem));
+  memcpy(L.block.h + off_recs, recs.data(), recs.size() * sizeof(rr_lens_drop));
+  memcpy(L.block.h + off_work, work.data(), work.size() * sizeof(rrlens::WorkItem));
   L.bytes = bytes;
   L.off_recs = off_recs;
   L.off_work = off_work;
@@ -9439,7 +9273,10 @@ int rr_set_colormap(rr_ctx* ctx, const uint8_t* lut_rgba) {
     return RR_E_ARG;
   }
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->d_lut) HIPCHK(hipMalloc((void**)&ctx->d_lut, 1024));
+  if (!ctx->d_lut) {
+    const int rc = dev_alloc(ctx, ctx->d_lut, 1024);
+    if (rc) return rc;
+  }
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(ctx->d_lut, lut_rgba, 1024, hipMemcpyHostToDevice));
   ctx->have_lut = true;
@@ -9533,6 +9370,13 @@ int rr_profile_read(rr_ctx* ctx, rr_kernel_stat* out, int32_t cap) {
   if (n > cap) n = cap;
   for (int i = 0; i < n; i++) out[i] = ctx->prof_stats[i];
   return n;
+}
+
+// out[4] = the context's live device blocks, their bytes, its live pinned blocks, their bytes (rr_host_alloc blocks not counted)
+int rr_debug_mem(rr_ctx* ctx, int64_t out[4]) {
+  if (!ctx || !out) return RR_E_ARG;
+  ctx->mem.stats(out);
+  return RR_OK;
 }
 
 }  // extern "C"

@@ -183,7 +183,7 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
-           'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device']
+           'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device', 'rr_debug_mem']
 
 _lib = None
 
@@ -231,6 +231,7 @@ def load_library(path=None):
                                        ctypes.POINTER(rr_frame_in), ctypes.POINTER(rr_frame_out),
                                        ctypes.POINTER(rr_prepass_out)]
     lib.rr_batch_counts.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+    lib.rr_debug_mem.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
     lib.rr_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
     lib.rr_pipeline_submit.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(rr_prepass_in),
                                        ctypes.POINTER(rr_frame_in), ctypes.POINTER(rr_frame_out), ctypes.POINTER(rr_prepass_out)]
@@ -1389,6 +1390,12 @@ class RainHip:
         out = (ctypes.c_int32 * 8)()
         self._check(self.lib.rr_batch_counts(self.h, int(frame), out), 'rr_batch_counts')
         return list(out)
+
+    def debug_mem(self):
+        """(device blocks, their bytes, pinned blocks, their bytes) the context holds right now (see rr_debug_mem)."""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self.lib.rr_debug_mem(self.h, out), 'rr_debug_mem')
+        return tuple(out)
 
     def profile(self, on):
         self.lib.rr_profile_enable(self.h, 1 if on else 0)

@@ -49,3 +49,19 @@ def test_device_byte_code_under_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, ASAN_OPTIONS='detect_leaks=0'))
     assert run.returncode == 0, (run.stdout[-600:], run.stderr[-3000:])
     assert 'wrong 0' in run.stdout and 'unfilter: wrong 0' in run.stdout and 'coded' in run.stdout
+
+
+def test_memory_owner_under_sanitizers(tmp_path):
+    """The owner of a context's device and pinned memory (csrc/rr_mem.h) over a malloc backend that counts its blocks and
+    fails an allocation on request (tests/sanitize/mem_owner.cpp), with AddressSanitizer + UndefinedBehaviorSanitizer and the
+    leak check ON: nothing is freed twice, nothing is left behind, and a failed growth leaves null pointers and capacity 0."""
+    src = os.path.join(h.ROOT, 'tests', 'sanitize', 'mem_owner.cpp')
+    exe = str(tmp_path / 'mem_owner')
+    cc = ['g++', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-std=c++17',
+          '-I' + os.path.join(h.ROOT, 'include'), '-I' + os.path.join(h.ROOT, 'rain-rendering_amd', 'csrc'), src, '-o', exe]
+    r = subprocess.run(cc, capture_output=True, text=True)
+    if r.returncode != 0:
+        pytest.skip("no sanitizer build here: " + r.stderr[-300:])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS='detect_leaks=1'))
+    assert run.returncode == 0, (run.stdout[-600:], run.stderr[-3000:])
+    assert 'mem_owner: checks' in run.stdout and 'wrong 0' in run.stdout
