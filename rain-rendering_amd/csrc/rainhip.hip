@@ -182,6 +182,12 @@ __device__ inline int rainy_kind(const FrameDesc& fr) {
   if (fr.rainy_bg == fr.bg) return bg_kind(fr);
   return (fr.in_types & RR_IN_RAINY_U8) ? 2 : ((fr.in_types & RR_IN_RAINY_F32) ? 1 : 0);
 }
+// the same from a copy of in_types (the compositors read their descriptor once: see k_composite32)
+__device__ inline int bg_kind(int in_types) { return (in_types & RR_IN_BG_U8) ? 2 : ((in_types & RR_IN_BG_F32) ? 1 : 0); }
+__device__ inline int rainy_kind(int in_types, bool same_bg) {
+  if (same_bg) return bg_kind(in_types);
+  return (in_types & RR_IN_RAINY_U8) ? 2 : ((in_types & RR_IN_RAINY_F32) ? 1 : 0);
+}
 // float loads that may straddle an 8-byte boundary (rows of an odd-width map start on odd elements)
 typedef float float2_u __attribute__((ext_vector_type(2), aligned(4)));
 typedef float float4_u __attribute__((ext_vector_type(4), aligned(4)));
@@ -3706,7 +3712,16 @@ __global__ __launch_bounds__(256) void k_composite(const FrameDesc* frames, Dims
   if (tile >= ntiles) return;
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const FrameDesc& fr = frames[f];
+  // the descriptor's fields once, as scalar loads, before the first store (see k_composite32)
+  const const_ptr<FrameDesc> fr = as_constant(frames + f);
+  const void* const fr_bg = fr->bg;
+  const void* const fr_rainy = fr->rainy_bg;
+  const void* const fr_depth = fr->depth;
+  double* const fr_comp = fr->comp_out;
+  double* const fr_mask_f64 = fr->mask_f64;
+  int32_t* const fr_mask_i32 = fr->mask_i32;
+  const int fr_in_types = fr->in_types, fr_depth_f64 = fr->depth_f64;
+  const bool same_bg = fr_bg == fr_rainy;
   const int tx0 = txi * TILE, ty0 = tyi * TILE, tx1 = min(tx0 + TILE, dm.W), ty1 = min(ty0 + TILE, dm.H);
   // a wave owns one 8x8 quarter of the 16x16 tile (drops are narrow and tall: a square wave footprint has the most
   // lanes inside a drop's rectangle) and walks its OWN ordered list: only the drops that reach its quarter
@@ -3717,12 +3732,12 @@ __global__ __launch_bounds__(256) void k_composite(const FrameDesc* frames, Dims
   double c[3] = {0, 0, 0}, m = 0.0;
   double sum_b = 0.0;                // this pixel's share of sum(bg) for the mean shift (generator.py:462)
   if (live) {
-    load_px3(fr.rainy_bg, rainy_kind(fr), pix, c);
-    if (fr.bg == fr.rainy_bg) {      // no fog pre-pass: one read serves both
+    load_px3(fr_rainy, rainy_kind(fr_in_types, same_bg), pix, c);
+    if (same_bg) {      // no fog pre-pass: one read serves both
       sum_b = (c[0] + c[1]) + c[2];
     } else {
       double b[3];
-      load_px3(fr.bg, bg_kind(fr), pix, b);
+      load_px3(fr_bg, bg_kind(fr_in_types), pix, b);
       sum_b = (b[0] + b[1]) + b[2];
     }
   }
@@ -3734,8 +3749,8 @@ __global__ __launch_bounds__(256) void k_composite(const FrameDesc* frames, Dims
   // depth-occlusion option (default off; not part of the reference's output): a drop farther than the scene at a
   // pixel is hidden there
   double scene = 1.0e300;
-  if (fr.depth && live)
-    scene = fr.depth_f64 ? as_global((const double*)fr.depth)[pix] : (double)as_global((const float*)fr.depth)[pix];
+  if (fr_depth && live)
+    scene = fr_depth_f64 ? as_global((const double*)fr_depth)[pix] : (double)as_global((const float*)fr_depth)[pix];
   // the short form of the blend (see step) needs finite pixel values and an exposure whose reciprocal divides exactly
   const double ex = cam.exposure_s, ex_rcp = 1.0 / ex;
   const bool tame_px = !live || (fabs(c[0]) < 1.0e50 && fabs(c[1]) < 1.0e50 && fabs(c[2]) < 1.0e50);
@@ -3852,12 +3867,12 @@ __global__ __launch_bounds__(256) void k_composite(const FrameDesc* frames, Dims
   }
   double sum_c = 0.0;
   if (live) {
-    const global_ptr<double> o = as_global(fr.comp_out) + pix * 3;
+    const global_ptr<double> o = as_global(fr_comp) + pix * 3;
     o[0] = c[0];
     o[1] = c[1];
     o[2] = c[2];
-    if (fr.mask_f64) as_global(fr.mask_f64)[pix] = m;
-    if (fr.mask_i32) as_global(fr.mask_i32)[pix] = (int32_t)floor(m * 255.0);
+    if (fr_mask_f64) as_global(fr_mask_f64)[pix] = m;
+    if (fr_mask_i32) as_global(fr_mask_i32)[pix] = (int32_t)floor(m * 255.0);
     sum_c = (c[0] + c[1]) + c[2];
   }
   __shared__ double ra[256], rb[256], rlo[256], rhi[256];
@@ -3914,7 +3929,19 @@ __global__ __launch_bounds__(256, 5) void k_composite32(const FrameDesc* frames,
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   PH_DECL
-  const FrameDesc& fr = frames[f];
+  // Every field of the frame's descriptor is read ONCE, here, before the kernel's first store, through the constant address
+  // space: wave-uniform scalar loads into SGPRs.  Read through a reference into global memory, each field had to be fetched
+  // again behind every store (the store might have changed it) by a vector load with s_waitcnt vmcnt(0) -- and vmcnt counts
+  // stores too, so each of those waits also drained the store before it: the epilogue was eight serial round trips
+  // (profiles/compositor_epilogue_cost.md).  The descriptors are written by an earlier kernel (k_copy_small).
+  const const_ptr<FrameDesc> fr = as_constant(frames + f);
+  const void* const fr_bg = fr->bg;
+  const void* const fr_rainy = fr->rainy_bg;
+  const void* const fr_depth = fr->depth;
+  void* const fr_comp = fr->comp_out;
+  double* const fr_mask_f64 = fr->mask_f64;
+  int32_t* const fr_mask_i32 = fr->mask_i32;
+  const int fr_comp_f32 = fr->comp_f32, fr_in_types = fr->in_types, fr_depth_f64 = fr->depth_f64;
   const int tx0 = txi * TILE, ty0 = tyi * TILE32_H, tx1 = min(tx0 + TILE, dm.W), ty1 = min(ty0 + TILE32_H, dm.H);
   const int px = tx0 + 8 * (wave & 1) + (lane & 7);
   const int py0 = ty0 + 16 * (wave >> 1) + (lane >> 3), py1 = py0 + 8;
@@ -3933,19 +3960,19 @@ __global__ __launch_bounds__(256, 5) void k_composite32(const FrameDesc* frames,
   const int4* bbox = sc.bbox + (int64_t)f * max_drops;
   const int i_first = imin((int)as_global(clist)[imin(t, max_drops - 1)], max_drops - 1);      // (past the list's end: any valid index)
   const int64_t pq = (int64_t)ty0 * dm.W + tx0, pq0 = live0 ? pix0 : pq, pq1 = live1 ? pix1 : pq;
-  const int rk = rainy_kind(fr), bk = bg_kind(fr);
-  const bool same_bg = fr.bg == fr.rainy_bg;
+  const bool same_bg = fr_bg == fr_rainy;
+  const int rk = rainy_kind(fr_in_types, same_bg), bk = bg_kind(fr_in_types);
   RawPx qr0 = {0u, 0u, 0u, 0u, 0u, 0u}, qr1 = qr0, qb0 = qr0, qb1 = qr0;
-  load_px3_raw2(fr.rainy_bg, rk, pq0, pq1, qr0, qr1);
+  load_px3_raw2(fr_rainy, rk, pq0, pq1, qr0, qr1);
   const int4 bb_first = bbox[i_first];
-  if (!same_bg) load_px3_raw2(fr.bg, bk, pq0, pq1, qb0, qb1);
+  if (!same_bg) load_px3_raw2(fr_bg, bk, pq0, pq1, qb0, qb1);
   double scene0 = 1.0e300, scene1 = 1.0e300;
-  if (fr.depth) {
-    if (fr.depth_f64) {
-      scene0 = as_global((const double*)fr.depth)[pq0];
-      scene1 = as_global((const double*)fr.depth)[pq1];
+  if (fr_depth) {
+    if (fr_depth_f64) {
+      scene0 = as_global((const double*)fr_depth)[pq0];
+      scene1 = as_global((const double*)fr_depth)[pq1];
     } else {
-      const float d0 = as_global((const float*)fr.depth)[pq0], d1 = as_global((const float*)fr.depth)[pq1];
+      const float d0 = as_global((const float*)fr_depth)[pq0], d1 = as_global((const float*)fr_depth)[pq1];
       scene0 = (double)d0;
       scene1 = (double)d1;
     }
@@ -3984,7 +4011,7 @@ __global__ __launch_bounds__(256, 5) void k_composite32(const FrameDesc* frames,
     c1 = float2_t{(float)in0[1], (float)in1[1]};
     c2 = float2_t{(float)in0[2], (float)in1[2]};
   }
-  const bool has_depth = fr.depth != nullptr;
+  const bool has_depth = fr_depth != nullptr;
   const bool slow_wave = __ballot(!ok_px) != 0ull;
   const CompRec32* comp = sc.comp32 + (int64_t)f * max_drops;
   const CompRec* comp64 = sc.comp + (int64_t)f * max_drops;
@@ -4167,26 +4194,26 @@ __global__ __launch_bounds__(256, 5) void k_composite32(const FrameDesc* frames,
     part[2] = rlo[0];
     part[3] = rhi[0];
   }
-  const bool c16 = fr.comp_f32 == 2;
+  const bool c16 = fr_comp_f32 == 2;
   if (live0) {
     if (c16) {                                                    // four 16-bit words per pixel (the fourth is 0): one 8-byte store
-      as_global(reinterpret_cast<u32x2_t*>(fr.comp_out))[pix0] = u32x2_t{code16(c0.x) | (code16(c1.x) << 16), code16(c2.x)};
+      as_global(static_cast<u32x2_t*>(fr_comp))[pix0] = u32x2_t{code16(c0.x) | (code16(c1.x) << 16), code16(c2.x)};
     } else {
-      const global_ptr<float> o = as_global(reinterpret_cast<float*>(fr.comp_out)) + pix0 * 3;
+      const global_ptr<float> o = as_global(static_cast<float*>(fr_comp)) + pix0 * 3;
       o[0] = c0.x; o[1] = c1.x; o[2] = c2.x;
     }
-    if (fr.mask_f64) as_global(fr.mask_f64)[pix0] = m0;
-    if (fr.mask_i32) as_global(fr.mask_i32)[pix0] = (int32_t)floor(m0 * 255.0);
+    if (fr_mask_f64) as_global(fr_mask_f64)[pix0] = m0;
+    if (fr_mask_i32) as_global(fr_mask_i32)[pix0] = (int32_t)floor(m0 * 255.0);
   }
   if (live1) {
     if (c16) {
-      as_global(reinterpret_cast<u32x2_t*>(fr.comp_out))[pix1] = u32x2_t{code16(c0.y) | (code16(c1.y) << 16), code16(c2.y)};
+      as_global(static_cast<u32x2_t*>(fr_comp))[pix1] = u32x2_t{code16(c0.y) | (code16(c1.y) << 16), code16(c2.y)};
     } else {
-      const global_ptr<float> o = as_global(reinterpret_cast<float*>(fr.comp_out)) + pix1 * 3;
+      const global_ptr<float> o = as_global(static_cast<float*>(fr_comp)) + pix1 * 3;
       o[0] = c0.y; o[1] = c1.y; o[2] = c2.y;
     }
-    if (fr.mask_f64) as_global(fr.mask_f64)[pix1] = m1;
-    if (fr.mask_i32) as_global(fr.mask_i32)[pix1] = (int32_t)floor(m1 * 255.0);
+    if (fr_mask_f64) as_global(fr_mask_f64)[pix1] = m1;
+    if (fr_mask_i32) as_global(fr_mask_i32)[pix1] = (int32_t)floor(m1 * 255.0);
   }
   PH(6)
   PH_FLUSH(4)
