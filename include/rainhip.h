@@ -708,6 +708,67 @@ typedef struct {
 int rr_pipeline_set_lens(rr_ctx* ctx, int32_t slot, const rr_pipeline_lens* lens);
 int rr_sizeof_pipeline_lens(void);
 
+/* ---------------------------------------------------------------------------------------
+ * The rain layer of a frame (kernel and contract: csrc/rr_layer.h): what the streaks add to a pixel and how much of
+ * the background survives under them -- the third thing, beside the rainy frame and the rain-free target, that de-raining,
+ * rain-removal and rain-segmentation models are trained on.  rainy_mask is not it: an unbounded sum of alpha samples, no colour.
+ * For pixel p of frame f take the drops the compositor lists for p, in table order; A is the drop's alpha sample at p, 0 outside
+ * its footprint and, under RR_OPT_DEPTH_OCCLUSION, 0 where the drop is behind the scene (the compositor's rule).  Start with
+ * T = 1, L = (0, 0, 0); per drop
+ *     u = 1 - A te;   L_c <- u L_c + A kg_c  (c = B, G, R);   T <- u T              no clamp anywhere
+ * te = tau_one / exposure and kg_c = K_c g being the drop's blend factors as the colour kernel leaves them, rounded to float32.
+ * The device carries T and L in float32, one IEEE operation per step: Af = float(A), u = fma(Af, -te, 1),
+ * L_c = fma(u, L_c, Af * kg_c), T = u * T.  A drop whose factors are not tame, or whose tile is the caller's (rr_ext_tile), takes
+ * the float64 factors and makes the step in float64 on double(L_c), double(T), rounding each result once to float32.
+ * A pixel no listed drop reaches has T == 1 and L == 0 exactly.  T and L depend on neither bg nor rainy_bg, nor on which compositor
+ * made the image (float or float64 colours, RR_OPT_WILD_PIXELS, RR_OPT_COLOUR_STREAM); the colour constants follow RR_OPT_FOV_F32.
+ *   layer   float32 [H][W][4] = (L_B, L_G, L_R, T): 16 bytes per pixel, the pointer 16-byte aligned
+ *   shift   one double: the mean shift every finalize kernel subtracts, mean(composite) - mean(bg) of the frame
+ * Wherever no blend of the compositor clamped, the composite is T rainy_bg + L, so
+ *     rainy_rgb = uint8(clip01(T rainy_bg + L - shift) 255)                            within 1 LSB
+ * Sufficient for "no blend clamped": bg and rainy_bg lie in [0, 1] and kg_c <= te for every listed drop (each blend is then a
+ * convex combination).  The layer knows nothing of the lens pass (rr_pipeline_set_lens), exactly like the mask.
+ *
+ * rr_pipeline_set_layer ARMS a pipeline slot, modelled on rr_pipeline_set_lens: every batch submitted on it afterwards
+ * (rr_pipeline_submit; slot 0 also serves rr_pipeline_frames, rr_render_frames and rr_render_frames_device) runs ONE more kernel
+ * beside the compositor, k_rain_layer, over the compositor's own work lists, and a one-workgroup-per-frame kernel for the shift.
+ * frames[f] says where frame f's layer and shift go; either pointer may be NULL.  The pointers are of the kind the consuming
+ * entry point takes: HOST for the host-pointer entry points (they must stay valid until rr_pipeline_wait of every batch submitted
+ * while the slot is armed with them), DEVICE for rr_render_frames_device.  The table is copied by the call.  The armed state stays
+ * on the slot until it is replaced or disarmed (layer == NULL), and EVERY submit on the slot applies it once, the re-submit after
+ * RR_E_ARENA included.  With no layer armed the kernels of a call are what they were: nothing else changes.
+ * Device staging of the host entry points, allocated by the first armed batch and kept: 16 H W + 8 bytes per frame.
+ * RR_E_ARG, with nothing changed: a bad slot, n <= 0, a null table (frames), a layer pointer that is not 16-byte aligned.
+ * RR_E_STATE: the slot is in flight.  A submit on an armed slot returns RR_E_ARG with nothing enqueued when the batch's n is not the
+ * armed n or when the batch renders nothing (in == NULL; rr_prepass_frames runs on slot 0). */
+typedef struct {
+  float* layer;                          /* [H][W][4] float32 (L_B, L_G, L_R, T), or NULL */
+  double* shift;                         /* one double, or NULL */
+} rr_layer_out;                          /* 16 bytes */
+typedef struct {
+  int32_t n, reserved;
+  const rr_layer_out* frames;            /* HOST, n records */
+} rr_pipeline_layer;
+int rr_pipeline_set_layer(rr_ctx* ctx, int32_t slot, const rr_pipeline_layer* layer);
+int rr_sizeof_layer_out(void);
+int rr_sizeof_pipeline_layer(void);
+/* The same for rr_augment_frames_device: armed until replaced or disarmed (layer == NULL, or all three pointers NULL), every call
+ * (its re-enqueue after an arena growth included) fills, for its n frames at its H x W -- the render size under rr_set_input_resize --,
+ *   layer_out        DEVICE [n,4,H,W] planar float32 in the order R, G, B, T (L_R, L_G, L_B, T), or NULL
+ *   background_out   DEVICE [n,3,H,W] planar float32 RGB, or NULL: the fogged image the streaks were composited over -- the
+ *                    pre-pass output the hot path read, the float32 values themselves, not re-quantised
+ *   shift_out        DEVICE [n] double, or NULL
+ * always planar float32, whatever dtype and layout the images have (as mask_out is always float32).  The planes are written by a
+ * store variant of the same kernel: the lists are walked once.  No scratch of the library's: the caller's tensors are written
+ * directly.  RR_E_ARG: a pointer that is not aligned to its element. */
+typedef struct {
+  float* layer_out;
+  float* background_out;
+  double* shift_out;
+} rr_tensor_layer;
+int rr_augment_set_layer(rr_ctx* ctx, const rr_tensor_layer* layer);
+int rr_sizeof_tensor_layer(void);
+
 /* Options.  Those marked "tuning" change no result bit (tests/test_gpu_properties.py); every other one says what it
  * changes.  A retired option keeps its number and accepts only the value the library always runs with (it then does
  * nothing).  Unknown options or values are RR_E_ARG.  The library reads no environment variables. */

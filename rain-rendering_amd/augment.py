@@ -77,6 +77,15 @@ depth * 256); float32 images are widened, not re-quantised to bytes, so they mat
 the mask is identical either way.  Shapes that do not match, or a `depth_size` other than the render size without `source_size`,
 are a ValueError.
 
+`return_layer=True` (default False) returns one thing more, last: a `RainLayer`, the streaks of every image without the
+image -- what de-raining, rain-removal and rain-segmentation models train on beside the rainy frame and the rain-free target.
+`.colour` [B, 3, H, W] (L) and `.transmittance` [B, 1, H, W] (T) are float32 views of one tensor, `.background` [B, 3, H, W] is the
+fogged image the streaks were composited over (the rain-free target; the float32 values the compositor read) and `.shift` [B] the
+frame's mean shift (float64, on the device); `.over(x)` is clamp(T x + L - shift, 0, 1), which for x = `.background` gives `rainy`
+to the byte's last place wherever no blend saturated.  Always planar float32 at the render size, whatever the images' dtype and
+layout; under a rig the tensors gain the V axis the images have; with `lens=` the layer is that of the streaks alone (the lens pass
+comes after it, as for the mask).  It costs one more kernel over the compositor's work lists (k_rain_layer), no second render.
+
 One library call per batch (rr_augment_frames_device: particles, planar ingest, fog + environment-map pre-pass, hot path, planar
 finalize) on the caller's current stream; it returns once the batch is complete.  The set-up -- camera, simulation options, fog
 constants, particle tables, environment-map geometry and solid angles -- comes from the functions the driver uses.  Not offered:
@@ -163,12 +172,34 @@ def _empty_like_frames(shape, dtype, device, layout):
     return torch.empty(lead + (H, W, 3), dtype=dtype, device=device).permute(*range(nd), nd + 2, nd, nd + 1)
 
 
+class RainLayer:
+    """The streaks of a batch as colour and transmittance (RainAugment(return_layer=True); the contract: csrc/rr_layer.h).
+    colour [.., 3, H, W] and transmittance [.., 1, H, W] are views of the one float32 tensor [.., 4, H, W] (R, G, B, T) the library
+    wrote; background [.., 3, H, W] float32; shift [..] float64.  All on the images' device, planar, at the render size."""
+
+    def __init__(self, planes, background, shift):
+        self.planes, self.background, self.shift = planes, background, shift
+        self.colour = planes.narrow(-3, 0, 3)
+        self.transmittance = planes.narrow(-3, 3, 1)
+
+    def over(self, x):
+        """clamp(T x + L - shift, 0, 1) for x [.., 3, H, W] with values in [0, 1] (bytes: x / 255 first), evaluated in float64;
+        float32 out (float64 for a float64 x).  over(background) is the rainy image before its truncation to bytes."""
+        if not isinstance(x, torch.Tensor) or not x.is_floating_point() or x.shape != self.background.shape:
+            raise ValueError("x must be a floating-point tensor of shape %s" % (tuple(self.background.shape),))
+        v = self.transmittance.double() * x.double() + self.colour.double() - self.shift[..., None, None, None]
+        return v.clamp_(0.0, 1.0).to(torch.float64 if x.dtype == torch.float64 else torch.float32)
+
+
 class RainAugment:
-    """Callable: (images, depth, intensity, frame_index) -> (rainy, mask).  See the module docstring."""
+    """Callable: (images, depth, intensity, frame_index) -> (rainy, mask[, lens alpha][, RainLayer]).  See the module docstring."""
 
     def __init__(self, dataset='kitti', streaks_db='3rdparty/rainstreakdb', sequence=None, device=None, seed=0, particle_model='iid',
                  rig=None, views=None, draws='stream', jitter=0.0, trajectory=None, wind=(0.0, 0.0), lean=None, gusts=None, showers=None,
-                 lens=None, return_lens_alpha=False, source_size=None, depth_size=None):
+                 lens=None, return_lens_alpha=False, source_size=None, depth_size=None, return_layer=False):
+        if not isinstance(return_layer, bool):
+            raise ValueError("return_layer=%r: True or False" % (return_layer,))
+        self.return_layer = return_layer
         if lens is not None and not isinstance(lens, lensmod.LensDrops):
             raise TypeError("lens must be a tools.lens.LensDrops, got %r" % (type(lens).__name__,))
         if not isinstance(return_lens_alpha, bool) or (return_lens_alpha and lens is None):
@@ -514,7 +545,16 @@ class RainAugment:
                 # the legacy default stream is handle 0, which the library reads as "the context's own stream": what torch has
                 # queued on it (the inputs) is finished first, and the call's own wait covers the outputs
                 stream.synchronize()
-            hip.augment_frames_device(b, stream.cuda_stream)
+            layer = None
+            if self.return_layer:                # three more tensors for the call to fill: planar float32 / float64, the render size
+                layer = RainLayer(torch.empty((B, 4, H, W), dtype=torch.float32, device=dev),
+                                  torch.empty((B, 3, H, W), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.float64, device=dev))
+                hip.augment_set_layer(layer.planes.data_ptr(), layer.background.data_ptr(), layer.shift.data_ptr())
+            try:
+                hip.augment_frames_device(b, stream.cuda_stream)
+            finally:
+                if layer is not None:
+                    hip.augment_set_layer()
             alpha = None
             if self.lens is not None:            # the drops on the lens refract the rainy image: one more kernel on the same stream
                 idx = [int(f) for f in _as_list(frame_index, B if V is None else B // V, 'frame_index', 'index')]
@@ -523,7 +563,10 @@ class RainAugment:
         if V is not None:
             rainy, mask = rainy.unflatten(0, (B // V, V)), mask.reshape(B // V, V, 1, H, W)      # (a view in either layout)
             alpha = None if alpha is None else alpha.reshape(B // V, V, 1, H, W)
-        return (rainy, mask, alpha) if self.return_lens_alpha else (rainy, mask)
+            if layer is not None:
+                layer = RainLayer(layer.planes.reshape(B // V, V, 4, H, W), layer.background.reshape(B // V, V, 3, H, W), layer.shift.reshape(B // V, V))
+        out = (rainy, mask, alpha) if self.return_lens_alpha else (rainy, mask)
+        return out + (layer,) if self.return_layer else out
 
     def _lens_tables(self, idx):
         """The drop tables of a call, one per image of the library's batch: frame_index[i]'s; under a rig, V per instant, view v's own."""

@@ -4349,6 +4349,7 @@ __global__ __launch_bounds__(256) void k_finalize(const FrameDesc* frames, Dims 
 }
 
 #include "rr_tensor.h"
+#include "rr_layer.h"
 
 // ---------------------------------------------------------------------------
 // the two PNG files of a frame, ready for deflate  
@@ -5821,7 +5822,7 @@ struct rr_ctx {
     hipEvent_t ev[N] = {};
     bool used[N] = {};
     int next = 0;
-  } ring_frames, ring_pre, ring_sims, ring_noise, ring_lens;
+  } ring_frames, ring_pre, ring_sims, ring_noise, ring_lens, ring_layer;
   // last launch (for rr_synchronize bookkeeping)
   int last_n = 0;
   // host-pointer entry points: device staging per pipeline slot (slot 0 serves the synchronous calls)
@@ -5863,7 +5864,19 @@ struct rr_ctx {
     // rr_set_input_resize: the batch's source-size inputs (filtered rows, un-filtered bytes, samples), sized by the source and
     // allocated by the first armed batch (grown, never shrunk)
     rrmem::Buf<uint8_t> src;
+    // rr_pipeline_set_layer: the caller's per-frame pointers, copied by the arming call, and the device staging of
+    // the host entry points -- n layers of 16 H W bytes, then n shifts -- allocated by the first armed batch (grown, never shrunk)
+    struct Layer {
+      bool armed = false;
+      std::vector<rr_layer_out> frames;
+      rrmem::Buf<char> stage;
+    } layer;
   } slots[RR_PIPE_SLOTS];
+  // the rain layer: a batch's LayerDesc records on the device (written in stream order, like d_frames), and what
+  // rr_augment_set_layer armed rr_augment_frames_device with
+  rrmem::Buf<LayerDesc> layer_desc;
+  bool aug_layer_armed = false;
+  rr_tensor_layer aug_layer{};
   hipStream_t s_up = nullptr, s_down = nullptr;
   // pre-pass (fog + environment map)
   rrpre::Kernels pk{};
@@ -6180,7 +6193,7 @@ struct LensStage {
 };
 
 int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, hipStream_t s, int ovf_idx = 0,
-            const PlanarOut* planar = nullptr, const LensStage* lens = nullptr) {
+            const PlanarOut* planar = nullptr, const LensStage* lens = nullptr, const LayerDesc* layer = nullptr) {
   if (!ctx->have_cam || !ctx->have_db) {
     ctx->err = "streak DB and camera must be set before rendering";
     return RR_E_STATE;
@@ -6569,9 +6582,37 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     hipLaunchKernelGGL(k_composite, dim3(((ntiles + 7) / 8) * 8, n), dim3(256), 0, s, ctx->d_frames, dm, ctx->cam, D, tiles_x, tiles_y, ctiles_x, nct,
                        sc);
   }
+  // The rain layer of an armed call: beside the compositor -- records, boxes, lists and the arena are complete and
+  // the arena is not yet recycled -- on the lists and the 16 x 32 tiles of k_composite32, whichever compositor made the image.
+  if (layer) {
+    int rc, idx;
+    void* host;
+    if ((rc = reserve(ctx, ctx->layer_desc, (size_t)n))) return rc;
+    if ((rc = ring_acquire(ctx, ctx->ring_layer, sizeof(LayerDesc) * (size_t)n, idx, host))) return rc;
+    memcpy(host, layer, sizeof(LayerDesc) * (size_t)n);
+    hipLaunchKernelGGL(k_copy_small, dim3(16), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(host), reinterpret_cast<uint32_t*>(ctx->layer_desc.p),
+                       (int)(sizeof(LayerDesc) * (size_t)n / 4));
+    if ((rc = ring_commit(ctx, ctx->ring_layer, idx, s))) return rc;
+    const int tiles_y32 = (dm.H + TILE32_H - 1) / TILE32_H, nt32 = tiles_x * tiles_y32;
+    const dim3 grid(((nt32 + 7) / 8) * 8, n);
+    ProfScope ps(ctx, s, "k_rain_layer");
+    if (layer[0].planar)
+      hipLaunchKernelGGL(k_rain_layer<1>, grid, dim3(256), 0, s, ctx->d_frames, ctx->layer_desc.p, dm, ctx->cam.exposure_s, D, tiles_x, tiles_y32, ctiles_x, nct,
+                         ctx->arena_cap, sc);
+    else
+      hipLaunchKernelGGL(k_rain_layer<0>, grid, dim3(256), 0, s, ctx->d_frames, ctx->layer_desc.p, dm, ctx->cam.exposure_s, D, tiles_x, tiles_y32, ctiles_x, nct,
+                         ctx->arena_cap, sc);
+  }
   {
     ProfScope ps(ctx, s, "k_means");
     hipLaunchKernelGGL(k_means, dim3(n), dim3(256), 0, s, dm, ntiles_c, sc);
+  }
+  if (layer) {                                             // the shift k_means has just made, and the background where it is asked for
+    bool any_bg = false;
+    for (int f = 0; f < n; f++) any_bg = any_bg || layer[f].background;
+    ProfScope ps(ctx, s, "k_layer_finish");
+    hipLaunchKernelGGL(k_layer_finish, dim3(any_bg ? (unsigned)(((int64_t)dm.H * dm.W + 255) / 256) : 1u, n), dim3(256), 0, s, ctx->d_frames,
+                       ctx->layer_desc.p, dm, sc);
   }
   if (planar) {
     ProfScope ps(ctx, s, "k_finalize_planar");
@@ -7587,7 +7628,15 @@ int rr_render_frames_device(rr_ctx* ctx, int32_t n, const rr_frame_in* in, const
   if (!ctx) return RR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  return enqueue(ctx, n, in, out, s);
+  const rr_ctx::Slot::Layer& L = ctx->slots[0].layer;      // slot 0 armed with rr_pipeline_set_layer: DEVICE pointers here
+  if (!L.armed) return enqueue(ctx, n, in, out, s);
+  if ((int)L.frames.size() != n) {
+    ctx->err = "rr_render_frames_device: n = " + std::to_string(n) + ", slot 0 is armed with rr_pipeline_set_layer for n = " + std::to_string(L.frames.size());
+    return RR_E_ARG;
+  }
+  std::vector<LayerDesc> ld((size_t)n);
+  for (int f = 0; f < n; f++) ld[(size_t)f] = LayerDesc{L.frames[(size_t)f].layer, L.frames[(size_t)f].shift, nullptr, 0, 0};
+  return enqueue(ctx, n, in, out, s, 0, nullptr, nullptr, ld.data());
 }
 
 int rr_synchronize(rr_ctx* ctx) {
@@ -8350,6 +8399,12 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
                          std::to_string(sl.lens.W) + ": the batch has " + std::to_string(n) + " of " + std::to_string(dm.H) + " x " + std::to_string(dm.W);
     return RR_E_ARG;
   }
+  if (sl.layer.armed && (!in || (int)sl.layer.frames.size() != n)) {
+    ctx->err = !in ? "pipeline slot armed with rr_pipeline_set_layer: the batch renders nothing (in == NULL)"
+                   : "pipeline slot armed with rr_pipeline_set_layer for n = " + std::to_string(sl.layer.frames.size()) + " frames: the batch has n = " +
+                         std::to_string(n);
+    return RR_E_ARG;
+  }
   if ((rc = slot_init(ctx, sl))) return rc;
   for (void*& b : sl.ext_blobs) ctx->mem.free(b);      // the slot's previous batch is complete (not busy)
   sl.ext_blobs.clear();
@@ -8607,7 +8662,18 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
   if (in) {                           // the slot's own overflow flag, cleared in stream order before the batch's k_scan may set it
     hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, ctx->sc.overflow + 1 + slot, 0);
     const LensStage stage{&sl.lens, st.rgb, (int64_t)T.px3b, (int64_t)T.pngb};
-    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot, nullptr, sl.lens.armed ? &stage : nullptr))) return drained(rc);
+    std::vector<LayerDesc> ld;                           // an armed rain layer: staged on the device, downloaded with the rest
+    if (sl.layer.armed) {
+      if ((rc = reserve(ctx, sl.layer.stage, (size_t)n * (px * 16 + 8)))) return drained(rc);
+      ld.resize((size_t)n);
+      for (int f = 0; f < n; f++) {
+        const rr_layer_out& lo = sl.layer.frames[(size_t)f];
+        ld[(size_t)f] = LayerDesc{lo.layer ? reinterpret_cast<float*>(sl.layer.stage.p + (size_t)f * px * 16) : nullptr,
+                                  lo.shift ? reinterpret_cast<double*>(sl.layer.stage.p + (size_t)n * px * 16 + (size_t)f * 8) : nullptr, nullptr, 0, 0};
+      }
+    }
+    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot, nullptr, sl.lens.armed ? &stage : nullptr, sl.layer.armed ? ld.data() : nullptr)))
+      return drained(rc);
   }
   if (hipEventRecord(sl.ev_comp, s) != hipSuccess) {
     ctx->err = "pipeline: hipEventRecord failed";
@@ -8627,6 +8693,9 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if (out[f].rainy_png) down.add(out[f].rainy_png, dout[f].rainy_png, png_bytes);
     if (out[f].mask_png) down.add(out[f].mask_png, dout[f].mask_png, png_bytes);
     if (sl.lens.armed && sl.lens.want_alpha && sl.lens.alpha_png[(size_t)f]) down.add(sl.lens.alpha_png[(size_t)f], sl.lens.png.p + (size_t)f * T.pngb, png_bytes);
+    if (sl.layer.armed && sl.layer.frames[(size_t)f].layer) down.add(sl.layer.frames[(size_t)f].layer, sl.layer.stage.p + (size_t)f * px * 16, px * 16);
+    if (sl.layer.armed && sl.layer.frames[(size_t)f].shift)
+      down.add(sl.layer.frames[(size_t)f].shift, sl.layer.stage.p + (size_t)n * px * 16 + (size_t)f * 8, sizeof(double));
   }
   for (int f = 0; pre && pre_out && f < n; f++) {
     if (pre_out[f].rainy_bg && pre[f].mode != RR_PRE_ENV_ONLY) down.add(pre_out[f].rainy_bg, pout[f].rainy_bg, px * 3 * rainy_el);
@@ -8787,6 +8856,14 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
   }
   const PlanarOut pl{static_cast<char*>(b->rainy_out), b->mask_out, (int64_t)(px * 3 * el), b->dtype | (il ? TF_INTERLEAVED : 0)};
   const int64_t total = (int64_t)n * 3 * (int64_t)px;
+  std::vector<LayerDesc> ld;                             // rr_augment_set_layer: planar float32 outputs, whatever the images' format
+  if (ctx->aug_layer_armed) {
+    const rr_tensor_layer& a = ctx->aug_layer;
+    ld.resize((size_t)n);
+    for (int f = 0; f < n; f++)
+      ld[(size_t)f] = LayerDesc{a.layer_out ? a.layer_out + (size_t)f * 4 * px : nullptr, a.shift_out ? a.shift_out + f : nullptr,
+                                a.background_out ? a.background_out + (size_t)f * 3 * px : nullptr, 1, 0};
+  }
   for (int attempt = 0;; attempt++) {
     int rc;
     if ((rc = enqueue_particles(ctx, n, b->sims, H, W, drops, cap, counts, s))) return rc;
@@ -8831,7 +8908,7 @@ int augment(rr_ctx* ctx, const rr_tensor_batch* b, hipStream_t s) {
     }
     if ((rc = enqueue_prepass(ctx, n, pin.data(), pout.data(), s))) return rc;
     hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, s, ctx->sc.overflow + AUG_FLAG, 0);
-    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, AUG_FLAG, &pl))) return rc;
+    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, AUG_FLAG, &pl, nullptr, ld.empty() ? nullptr : ld.data()))) return rc;
     int32_t ovf = 0;
     HIPCHK(hipMemcpyAsync(&ovf, ctx->sc.overflow + AUG_FLAG, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -9004,9 +9081,64 @@ int set_lens(rr_ctx* ctx, int slot, const rr_pipeline_lens* b) {
   return RR_OK;
 }
 
+// rr_pipeline_set_layer: every check first; nothing of the slot changes before the last one has passed
+int set_layer(rr_ctx* ctx, int slot, const rr_pipeline_layer* b) {
+  if (slot < 0 || slot >= RR_PIPE_SLOTS) {
+    ctx->err = "rr_pipeline_set_layer: bad pipeline slot";
+    return RR_E_ARG;
+  }
+  rr_ctx::Slot& sl = ctx->slots[slot];
+  if (sl.busy) {
+    ctx->err = "rr_pipeline_set_layer: pipeline slot still in flight: call rr_pipeline_wait first";
+    return RR_E_STATE;
+  }
+  if (!b) {
+    sl.layer.armed = false;
+    sl.layer.frames.clear();
+    return RR_OK;
+  }
+  if (b->n <= 0) {
+    ctx->err = "rr_pipeline_set_layer: n must be positive";
+    return RR_E_ARG;
+  }
+  if (!b->frames) {
+    ctx->err = "rr_pipeline_set_layer: frames is NULL (the table of n rr_layer_out records)";
+    return RR_E_ARG;
+  }
+  for (int f = 0; f < b->n; f++)
+    if ((reinterpret_cast<uintptr_t>(b->frames[f].layer) & 15u) || (reinterpret_cast<uintptr_t>(b->frames[f].shift) & 7u)) {
+      ctx->err = "rr_pipeline_set_layer: frames[" + std::to_string(f) + "]: layer must be 16-byte aligned, shift 8-byte aligned";
+      return RR_E_ARG;
+    }
+  sl.layer.frames.assign(b->frames, b->frames + b->n);
+  sl.layer.armed = true;
+  return RR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rr_sizeof_layer_out(void) { return (int)sizeof(rr_layer_out); }
+int rr_sizeof_pipeline_layer(void) { return (int)sizeof(rr_pipeline_layer); }
+int rr_sizeof_tensor_layer(void) { return (int)sizeof(rr_tensor_layer); }
+
+int rr_pipeline_set_layer(rr_ctx* ctx, int32_t slot, const rr_pipeline_layer* layer) {
+  if (!ctx) return RR_E_ARG;
+  return set_layer(ctx, slot, layer);
+}
+
+int rr_augment_set_layer(rr_ctx* ctx, const rr_tensor_layer* layer) {
+  if (!ctx) return RR_E_ARG;
+  if (layer && ((reinterpret_cast<uintptr_t>(layer->layer_out) | reinterpret_cast<uintptr_t>(layer->background_out)) & 3u ||
+                (reinterpret_cast<uintptr_t>(layer->shift_out) & 7u))) {
+    ctx->err = "rr_augment_set_layer: layer_out and background_out must be 4-byte aligned, shift_out 8-byte aligned";
+    return RR_E_ARG;
+  }
+  ctx->aug_layer_armed = layer && (layer->layer_out || layer->background_out || layer->shift_out);
+  ctx->aug_layer = layer ? *layer : rr_tensor_layer{};
+  return RR_OK;
+}
 
 int rr_sizeof_pipeline_lens(void) { return (int)sizeof(rr_pipeline_lens); }
 

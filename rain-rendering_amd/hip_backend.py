@@ -4,6 +4,7 @@ per-frame drop table.
 There is no CPU implementation behind this module: if the shared library or a gfx950
 device is missing, construction fails loudly.
 """
+import contextlib
 import ctypes
 import os
 
@@ -170,6 +171,18 @@ class rr_pipeline_lens(ctypes.Structure):
                 ('weights', ctypes.c_void_p), ('alpha_png', ctypes.c_void_p)]
 
 
+class rr_layer_out(ctypes.Structure):                   # where one frame's rain layer goes (rr_pipeline_set_layer)
+    _fields_ = [('layer', ctypes.c_void_p), ('shift', ctypes.c_void_p)]
+
+
+class rr_pipeline_layer(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int32), ('reserved', ctypes.c_int32), ('frames', ctypes.c_void_p)]
+
+
+class rr_tensor_layer(ctypes.Structure):                # rr_augment_set_layer: device pointers, planar float32 / float64
+    _fields_ = [('layer_out', ctypes.c_void_p), ('background_out', ctypes.c_void_p), ('shift_out', ctypes.c_void_p)]
+
+
 EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_streak_db', 'rr_set_streak_db_device',
            'rr_set_camera', 'rr_render_frames', 'rr_render_frames_device', 'rr_synchronize', 'rr_profile_enable',
            'rr_profile_reset', 'rr_profile_read', 'rr_sizeof_drop', 'rr_sizeof_camera', 'rr_sizeof_frame_in',
@@ -183,7 +196,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_sim_frame', 'rr_set_particle_noise', 'rr_augment_frames_device', 'rr_sizeof_tensor_batch', 'rr_set_particle_model',
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
-           'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device', 'rr_debug_mem']
+           'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device', 'rr_debug_mem', 'rr_pipeline_set_layer',
+           'rr_augment_set_layer', 'rr_sizeof_layer_out', 'rr_sizeof_pipeline_layer', 'rr_sizeof_tensor_layer']
 
 _lib = None
 
@@ -299,6 +313,11 @@ def load_library(path=None):
     assert lib.rr_sizeof_lens_batch() == ctypes.sizeof(rr_lens_batch), (lib.rr_sizeof_lens_batch(), ctypes.sizeof(rr_lens_batch))
     lib.rr_pipeline_set_lens.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(rr_pipeline_lens)]
     assert lib.rr_sizeof_pipeline_lens() == ctypes.sizeof(rr_pipeline_lens), (lib.rr_sizeof_pipeline_lens(), ctypes.sizeof(rr_pipeline_lens))
+    lib.rr_pipeline_set_layer.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(rr_pipeline_layer)]
+    lib.rr_augment_set_layer.argtypes = [ctypes.c_void_p, ctypes.POINTER(rr_tensor_layer)]
+    assert lib.rr_sizeof_layer_out() == ctypes.sizeof(rr_layer_out) == 16, (lib.rr_sizeof_layer_out(), ctypes.sizeof(rr_layer_out))
+    assert lib.rr_sizeof_pipeline_layer() == ctypes.sizeof(rr_pipeline_layer), (lib.rr_sizeof_pipeline_layer(), ctypes.sizeof(rr_pipeline_layer))
+    assert lib.rr_sizeof_tensor_layer() == ctypes.sizeof(rr_tensor_layer), (lib.rr_sizeof_tensor_layer(), ctypes.sizeof(rr_tensor_layer))
     lib.rr_set_input_resize.argtypes = [ctypes.c_void_p] + [ctypes.c_int32] * 4
     lib.rr_resize_inputs_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -1019,12 +1038,14 @@ class RainHip:
         self.cam = cam
         self._check(self.lib.rr_set_camera(self.h, ctypes.byref(cam)), 'rr_set_camera')
 
-    def render_frames(self, frames, want_composite=True, want_colour=False):
+    def render_frames(self, frames, want_composite=True, want_colour=False, want_layer=False):
         """frames: list of dict(bg, rainy_bg, env_xyY, omega, drops[, opacity_attenuation]) with
         C-contiguous arrays and a DROP_DTYPE drop table.  The image arrays may be float32 or uint8 (uint8 = the bytes
         cv2.imread returned: value / 255.0), the map float32 (omega then travels as float32 too): rr_frame_in.in_types;
         anything else is taken as float64.  Returns a list of
-        dict(image_u8 RGB, rainy_bg, mask, mask_i32, status[, colour = (n, 3) BGR colour constants])."""
+        dict(image_u8 RGB, rainy_bg, mask, mask_i32, status[, colour = (n, 3) BGR colour constants]).
+        want_layer: slot 0 is armed for the call (pipeline_set_layer) and every dict gains layer ([H, W, 4] float32:
+        L_B, L_G, L_R, T) and shift (the frame's mean shift, a float)."""
         n = len(frames)
         fin = (rr_frame_in * n)()
         fout = (rr_frame_out * n)()
@@ -1098,7 +1119,8 @@ class RainHip:
             fout[k].drop_status = _ptr(o['status']) if len(drops) else None
             keep.append((bg, rb, env, om, drops))
             outs.append(o)
-        self._check(self.lib.rr_render_frames(self.h, n, fin, fout), 'rr_render_frames')
+        with self._layer_armed(outs, want_layer):
+            self._check(self.lib.rr_render_frames(self.h, n, fin, fout), 'rr_render_frames')
         for o in outs:                                 # a generated drop table: trim the per-drop outputs to its drop count
             if 'n_drops' in o:
                 nd = int(o['n_drops'][0])
@@ -1216,10 +1238,11 @@ class RainHip:
         return outs
 
     def pipeline_frames(self, frames, want_composite=False, want_rainy_bg=False, want_env_u8=False, want_mask_i32=True,
-                        fog_dtype=np.float64):
+                        fog_dtype=np.float64, want_layer=False):
         """Pre-pass + hot path without a host round trip.  frames: list of dict(bg, depth, fog, omega, drops
         [, opacity_attenuation, strategy]); omega None = the resident solid angles (set_solid_angles).  Returns what
-        render_frames returns (+ env_bgr_u8 / fog_bg, the fog layer as fog_dtype: its width on the device follows)."""
+        render_frames returns (+ env_bgr_u8 / fog_bg, the fog layer as fog_dtype: its width on the device follows;
+        want_layer: + layer and shift, as render_frames)."""
         n = len(frames)
         pin = (rr_prepass_in * n)()
         pout = (rr_prepass_out * n)()
@@ -1256,8 +1279,65 @@ class RainHip:
             pout[k].env_bgr_u8 = _ptr(o['env_bgr_u8'])
             keep.append((om, drops))
             outs.append(o)
-        self._check(self.lib.rr_pipeline_frames(self.h, n, pin, fin, fout, pout), 'rr_pipeline_frames')
+        with self._layer_armed(outs, want_layer):
+            self._check(self.lib.rr_pipeline_frames(self.h, n, pin, fin, fout, pout), 'rr_pipeline_frames')
         return outs
+
+    # ---- the rain layer ---------------------------------------------------------
+    def pipeline_set_layer(self, slot, outs):
+        """rr_pipeline_set_layer: arm pipeline slot `slot` so that every batch submitted on it also leaves its frames' rain layers,
+        or disarm it with outs=None.  outs: one dict per frame of the batches to come, dict(layer=C-contiguous float32 [H, W, 4]
+        array or None, shift=float64 array of one element or None) of caller-owned arrays (ideally from host_array) that the
+        library fills: (L_B, L_G, L_R, T) per pixel and the frame's mean shift.  They must stay alive and untouched until
+        pipeline_wait.  Slot 0 also serves render_frames / pipeline_frames (their want_layer= does this for one call)."""
+        if outs is None:
+            self._check(self.lib.rr_pipeline_set_layer(self.h, int(slot), None), 'rr_pipeline_set_layer')
+            getattr(self, '_layer_keep', {}).pop(int(slot), None)
+            return
+        n = len(outs)
+        tab = (rr_layer_out * max(n, 1))()
+        for k, o in enumerate(outs):
+            lay, sh = o.get('layer'), o.get('shift')
+            if lay is not None and not (isinstance(lay, np.ndarray) and lay.dtype == np.float32 and lay.flags['C_CONTIGUOUS'] and lay.ndim == 3
+                                        and lay.shape[2] == 4):
+                raise ValueError("layer: a C-contiguous float32 array [H, W, 4]")
+            if sh is not None and not (isinstance(sh, np.ndarray) and sh.dtype == np.float64 and sh.size >= 1 and sh.flags['C_CONTIGUOUS']):
+                raise ValueError("shift: a float64 array of one element")
+            tab[k].layer, tab[k].shift = _ptr(lay), _ptr(sh)
+        b = rr_pipeline_layer()
+        b.n, b.frames = n, ctypes.cast(tab, ctypes.c_void_p)
+        self._check(self.lib.rr_pipeline_set_layer(self.h, int(slot), ctypes.byref(b)), 'rr_pipeline_set_layer')
+        if not hasattr(self, '_layer_keep'):
+            self._layer_keep = {}
+        self._layer_keep[int(slot)] = outs               # (the library copied the table, not the arrays)
+
+    @contextlib.contextmanager
+    def _layer_armed(self, outs, want):
+        """want_layer= of the synchronous calls: slot 0 armed with fresh arrays for the call's frames, disarmed behind it."""
+        if not isinstance(want, (bool, np.bool_)):
+            raise ValueError("want_layer must be a bool, got %r" % (want,))
+        if not want:
+            yield
+            return
+        bufs = [dict(layer=np.zeros(o['image_u8'].shape[:2] + (4,), np.float32), shift=np.zeros(1, np.float64)) for o in outs]
+        self.pipeline_set_layer(0, bufs)
+        try:
+            yield
+        finally:
+            self.pipeline_set_layer(0, None)
+        for o, b in zip(outs, bufs):
+            o['layer'], o['shift'] = b['layer'], float(b['shift'][0])
+
+    def augment_set_layer(self, layer_ptr=None, background_ptr=None, shift_ptr=None):
+        """rr_augment_set_layer: from now on augment_frames_device also fills the DEVICE tensors at these addresses -- layer
+        [n, 4, H, W] float32 (R, G, B, T), background [n, 3, H, W] float32, shift [n] float64; each may be None -- until it is
+        called again; all None disarms."""
+        if not (layer_ptr or background_ptr or shift_ptr):
+            self._check(self.lib.rr_augment_set_layer(self.h, None), 'rr_augment_set_layer')
+            return
+        b = rr_tensor_layer()
+        b.layer_out, b.background_out, b.shift_out = layer_ptr or None, background_ptr or None, shift_ptr or None
+        self._check(self.lib.rr_augment_set_layer(self.h, ctypes.byref(b)), 'rr_augment_set_layer')
 
     # ---- device-resident path (bench / multi-frame pipelines) -------------------------------
     def render_frames_device(self, fin, fout, n, stream=None):
