@@ -256,7 +256,7 @@ struct Scratch {                    // per-batch device scratch, all indexed [fr
   double* wtab_big;                 // [frame][SLOW_CAP][2][MAX_R+1] the same for the first SLOW_CAP large-radius drops of a frame (k_blur_big_weights)
   const uint8_t* tex_pad;           // the textures with their 2-texel zero border, as k_tile stages them (k_pad_textures)
   const int64_t* tex_poff;          // [texture] offset of its padded copy (a multiple of 16)
-  uint4* fov_erec;                  // [frame][n_fov][drops] k_fov_dda's edge records (rr_device.h dda_edge_record: 16 bytes)
+  uint4* fov_erec;                  // [frame][n_fov + 1][drops] k_fov_dda's chain of edge records (rr_device.h fov_walk_make_records: 16 bytes)
   uint32_t* fov_pix;                // [frame][n_fov][drops] k_fov_dda's vertex pixels, x | y << 16 (a wave stores 256 contiguous bytes per vertex)
   int32_t* fov_list;                // [frame][drops] drops k_fov_dda leaves to k_fov_spans (wrapping polygons, float64 decisions)
   int32_t* fov_list_n;              // [frame] their number
@@ -896,9 +896,10 @@ __global__ __launch_bounds__(256) void k_fov_spans(const FrameDesc* frames, Dims
 //      a fraction of a percent of the drops.
 // r06, RR_OPT_FOV_FILL_RULE 1 (the default): the spans are what cv2.fillConvexPoly sets (rr_device.h fov_rowspan_cv: the
 // outline's Bresenham pixels + the 16.16 edge walkers) for the polygons OpenCV's rule applies to (every vertex on the map),
-// the span rule's otherwise.  Both by incremental cursors (rr_device.h DdaCursors): every edge's divisions are done once,
-// before the walk, into a 16-byte record per edge and lane (global memory: step, outline constants, the edge's pixels on its
-// first row, its lower end); a row costs adds and compares, and a cursor fetches its next record an edge ahead.  No LDS.
+// the span rule's otherwise.  Both by incremental cursors (rr_device.h FovWalk; DdaCursors there is the reference statement):
+// everything an edge needs is worked out once, before the walk, into a chain of 16-byte records per lane (global memory:
+// step, outline constants, the upper end, the merge span of the vertex row the edge starts on); a row costs adds and
+// compares, taking an edge is unpacking a record that was fetched an edge ahead.  No LDS.
 #ifndef RR_DDA_WAVES
 #define RR_DDA_WAVES 1          // waves per workgroup: 1 (r06: no LDS, no barrier -- single waves fit into whatever a CU has free: 5.57 -> 5.31 ms alone, step 27.9 -> 27.6)
 #endif
@@ -1040,8 +1041,9 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_vertices(const FrameDesc
 }
 
 // Part 2, a lane per SLOT (k_fov_sort: slot -> drop): the spans of the sure drops, two cursors down from the top vertex
-// (rr_device.h DdaCursors).  The wave executes the vertex path of a row when any one of its 64 cursor pairs stands on a
-// vertex -- 220 of the ~300 instructions per row -- which is why the drops of a wave are chosen to share vertex rows.
+// (rr_device.h FovWalk).  The wave executes the vertex path of a row when any one of its 64 cursor pairs stands on a
+// vertex -- a hand-over of ~25 vector instructions a side on top of the row's 45 (profiles/fov_walk_cost.md) -- which is
+// why the drops of a wave are chosen to share vertex rows.
 __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* frames, Dims dm, rr_camera cam, int max_drops, int Hp, int Dp, int cv_rule, Scratch sc) {
   const int f = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const FrameDesc& fr = frames[f];
@@ -1055,34 +1057,27 @@ __global__ __launch_bounds__(64 * DDA_WAVES) void k_fov_dda(const FrameDesc* fra
   if (__ballot(mine) == 0ull) return;                          // (the drops of other routes lie behind all of this kernel's)
   const int ytop = (int)dr.x, ybot = (int)dr.y, ktop = (int)(dr.w & 255u);
   const uint32_t top_xy = dr.z;
-  uint4* const erec = sc.fov_erec + (int64_t)f * N * max_drops + s;
+  uint4* const erec = sc.fov_erec + (int64_t)f * (N + 1) * max_drops + s;
   const uint32_t* const gpix = sc.fov_pix + (int64_t)f * N * max_drops + i;
   auto pixv = [&](int kk) -> uint32_t { return gpix[(int64_t)kk * max_drops]; };
-  // The records of the edges {k, k + 1} (upper end first) go to global memory, [frame][edge][slot], 16 bytes each: the
-  // walker's step, the packed outline constants, the edge's pixels on its first row and its lower end.  A wave stores 1 KB
-  // per edge in one piece, a cursor loads its next record an edge (~30 rows) ahead.  (In LDS they left room for 10 waves per
-  // CU instead of 24: 7.8 ms against 5.5 -- r06 A/B log.)  Round 6, second form: with the first row's pixels and the lower
-  // end in the record a lane that takes an edge evaluates neither DdaCursors' pixels() nor a vertex fetch.
+  // The records go to global memory as a chain, [frame][chain position][slot], 16 bytes each (rr_device.h
+  // fov_walk_make_records: side 0's edges, one terminator, side 1's edges; horizontal edges are folded into the merge span
+  // of the record that follows them; at most N + 1 positions).  A wave stores 1 KB per position in one piece, a side loads
+  // its next record an edge (~30 rows) ahead.  (In LDS the records left room for 10 waves per CU instead of 24: 7.8 ms
+  // against 5.5 -- r06 A/B log.)  Everything a lane needs when it takes an edge is in the record: the row loop below
+  // derives nothing and fetches no vertex.
   const bool cvr = cv_rule && (dr.w & 512u);                   // (a vertex off the map: the span rule, like the oracle)
-  if (mine) {
-    const uint32_t vfirst = pixv(0);
-    uint32_t va = vfirst;
-    for (int k = 0; k < N; k++) {
-      const uint32_t vb = k + 1 == N ? vfirst : pixv(k + 1);
-      const int x0 = (int)(va & 0xffffu), y0 = (int)(va >> 16), x1 = (int)(vb & 0xffffu), y1 = (int)(vb >> 16);
-      const bool swp = y1 < y0;
-      uint32_t r[4];
-      dda_edge_record(swp ? x1 : x0, swp ? y1 : y0, swp ? x0 : x1, swp ? y0 : y1, cvr, r);
-      erec[(int64_t)k * max_drops] = make_uint4(r[0], r[1], r[2], r[3]);
-      va = vb;
-    }
-  }
-  auto rec = [&](int kk, uint32_t r[4]) {
-    const uint4 v = erec[(int64_t)kk * max_drops];
+  auto rec = [&](int pos, uint32_t r[4]) {                     // pos in [0, N]: FovWalk clamps what it asks for to the chain
+    const uint4 v = erec[(int64_t)pos * max_drops];
     r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
   };
-  DdaCursors<decltype(rec)> cur;
-  if (mine) cur.init(rec, N, ktop, top_xy);
+  FovWalk<decltype(rec)> cur;
+  if (mine) {
+    const int n_pos = fov_walk_make_records(pixv, N, imin(ktop, N - 1), cvr, [&](int pos, const uint32_t r[4]) {
+      erec[(int64_t)pos * max_drops] = make_uint4(r[0], r[1], r[2], r[3]);      // pos <= N whatever the vertices are
+    });
+    cur.init(rec, n_pos, ytop, cvr);
+  }
   uint32_t* out = sc.spans + (int64_t)f * Hp * Dp + s;
   // the rows above and below every polygon of the wave: zeros, no cursor call
   // (both clamped to [0, Hp] here: no store of this kernel depends on where another function puts a vertex; the wave's
@@ -6090,7 +6085,7 @@ int ensure_scratch(rr_ctx* ctx, int n, int max_drops, const Dims& dm, bool need_
     if ((rc = dev_alloc(ctx, ctx->sc.rows_bounds, (size_t)RW_SHARE_MAX + 1))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.rows_fbase, (size_t)F * RW_TEX_MAX))) return rc;
     if ((rc = dev_alloc(ctx, ctx->sc.fov_list, fd))) return rc;
-    if ((rc = dev_alloc(ctx, ctx->sc.fov_erec, general ? 1 : fd * (size_t)(ctx->cam.n_fov > 0 ? ctx->cam.n_fov : RR_MAX_FOV)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->sc.fov_erec, general ? 1 : fd * (size_t)((ctx->cam.n_fov > 0 ? ctx->cam.n_fov : RR_MAX_FOV) + 1)))) return rc;      // a chain: n_fov edges and a terminator
     if ((rc = dev_alloc(ctx, ctx->sc.fov_pix, general ? 1 : fd * (size_t)(ctx->cam.n_fov > 0 ? ctx->cam.n_fov : RR_MAX_FOV)))) return rc;
     ctx->erec_nfov = ctx->cam.n_fov;
     if ((rc = dev_alloc(ctx, ctx->sc.fov_rec, general ? 1 : fd))) return rc;

@@ -1282,6 +1282,181 @@ struct DdaCursors {
   }
 };
 
+// ---- k_fov_dda's walk: the same rows as DdaCursors (which stays above as the reference statement; tests/hostemu pins both
+// against the rules), with an edge switch that is a hand-over instead of a computation ----
+// A wave executes DdaCursors' vertex path (advance_edge: ~125 instructions a side) on every row on which one of its 64
+// lanes stands on a vertex, which is most rows.  Everything that path derives is a function of the polygon's vertices, so
+// here the prologue (fov_walk_make_records: every lane busy, nothing diverges) leaves it in the records:
+//   * the records are a CHAIN in the order of the loop round the polygon from the top vertex upwards in index, horizontal
+//     edges left out: side 0's edges downwards (positions 0 .. m0 - 1), ONE terminator (m0), side 1's edges upwards
+//     (m0 + 1 .. m0 + m1).  Side 0 reads the chain from position 0 upwards, side 1 from the last position downwards; both
+//     end in the terminator.  At most N + 1 positions;
+//   * a record holds its edge's constants, the upper end's x (the cursor at the edge's SECOND row follows from them
+//     without a compare: Q = qs, R = rs, W = 2^15 + dx16) and the MERGE SPAN of the vertex row the edge starts on: the
+//     edge's own pixels on that row, the last row's pixels of the edge that ends there on the same side, and every vertex
+//     of a horizontal run on that row -- top, bottom or mid-side.  The terminator's merge span is the bottom row's: the
+//     last rows of both sides' final edges and the bottom run;
+//   * on the row an edge ends (y == yb) a side REPLACES its edge's pixels by the next record's merge span (so the clamp to
+//     the edge's own x range, which only binds on an edge's first and last row, and the walker's y < yb test leave the
+//     row path), takes the next record's fields and requests the record after it.  Every edge of the chain has den >= 1,
+//     so a side switches at most once per row: no loop, no count of edges -- after the terminator yb lies below ybot.
+// 16 bytes:  w0 = dx16   w1 = merge span, lo | hi << 16   w2 = hh | tl << 11 | den << 22   w3 = rs | same << 11 | xa << 16
+// (th = tl where same, else 2 den - tl).  Whether OpenCV's walker runs is the polygon's rule (cv), not the edge's.
+// Limits as above: den <= 1023, |dx| <= 4095, vertex coordinates in [0, 65535].
+typedef uint32_t fov_rec_words __attribute__((vector_size(16)));      // a record in flight: one 16-byte value, one register tuple
+struct FovWalkSide {
+  int yb;                                                    // the row the current edge ends on
+  int al, ah;                                                // xa + Q - hh, xa + Q + hh at the row the side stands on
+  int R, W;                                                  // W: (xa << 16) + 2^15 + t * dx16
+  int dn, tl, th, qs, rs, d16;
+  int pos;                                                   // chain position of the record in n0 .. n3
+  fov_rec_words nx;                                          // the NEXT record, fetched an edge ahead
+};
+// S: store(pos, r) puts a record at chain position pos; V: vtx(k) = vertex k, x | y << 16.  Returns the number of
+// positions written (<= n + 1 whatever the vertices are): FovWalk::init takes it, side 1 starts on the last one.
+template <class V, class S>
+RR_HD int fov_walk_make_records(const V& vtx, int n, int ktop, bool cv, const S& store) {
+  const int BIG = 1 << 30;
+  int p = 0;
+  int plo = BIG, phi = -BIG;                                 // the vertex row's span since the last edge of the chain
+  uint32_t q0 = 0u, q2 = 0u, q3 = 0u;                        // the record that waits for the rest of its merge span
+  int qlo = BIG, qhi = -BIG;
+  bool have = false, turned = false;
+  auto put = [&](uint32_t w0, int lo, int hi, uint32_t w2, uint32_t w3) {
+    uint32_t r[4] = {w0, (uint32_t)(lo & 0xffff) | ((uint32_t)(hi & 0xffff) << 16), w2, w3};
+    store(p, r);
+    p++;
+  };
+  int k = ktop;
+  uint32_t va = vtx(k);
+  plo = phi = (int)(va & 0xffffu);
+  for (int j = 0; j < n; j++) {
+    k = k + 1 == n ? 0 : k + 1;
+    const uint32_t vb = vtx(k);
+    const int x0 = (int)(va & 0xffffu), y0 = (int)(va >> 16), x1 = (int)(vb & 0xffffu), y1 = (int)(vb >> 16);
+    va = vb;
+    if (y1 == y0) {                                          // a horizontal edge: its far end joins the row's span
+      plo = imin(plo, x1);
+      phi = imax(phi, x1);
+      continue;
+    }
+    const bool down = y1 > y0;
+    const int xu = down ? x0 : x1, yu = down ? y0 : y1, xl = down ? x1 : x0, yl = down ? y1 : y0;
+    uint32_t r[4];
+    dda_edge_record(xu, yu, xl, yl, cv, r);                  // r[2]: the edge's pixels on its first row
+    const int flo = (int)(r[2] & 0xffffu), fhi = (int)(r[2] >> 16);
+    int llo, lhi;                                            // ... and on its last: t = den, Q = dx, R = 0
+    {
+      DdaSide L;
+      dda_take_edge(L, xu, yu, xl, yl, r[0], r[1]);
+      L.Q = xl - xu;
+      dda_pixels(L, yl, llo, lhi);
+    }
+    const uint32_t w2 = (r[1] & 0x3fffffu) | ((uint32_t)(yl - yu) << 22);
+    DdaSide T;
+    dda_take_edge(T, xu, yu, xl, yl, r[0], r[1]);
+    const uint32_t w3 = (uint32_t)T.rs | (((r[1] >> 22) & 1u) << 11) | ((uint32_t)xu << 16);
+    if (down) {                                              // side 0: the merge span is complete
+      if (have) put(q0, qlo, qhi, q2, q3);
+      qlo = imin(plo, flo);
+      qhi = imax(phi, fhi);
+      plo = llo;
+      phi = lhi;
+    } else {                                                 // side 1, met from below: the row above completes the record before
+      if (!turned) {
+        if (have) put(q0, qlo, qhi, q2, q3);
+        put(0u, imin(plo, llo), imax(phi, lhi), 1u << 22, 0u);      // the terminator: the bottom row, den = 1
+        turned = true;
+      } else {
+        put(q0, imin(qlo, imin(plo, llo)), imax(qhi, imax(phi, lhi)), q2, q3);
+      }
+      qlo = flo;
+      qhi = fhi;
+      plo = BIG;
+      phi = -BIG;
+    }
+    q0 = r[0]; q2 = w2; q3 = w3;
+    have = true;
+  }
+  if (have) put(q0, imin(qlo, plo), imax(qhi, phi), q2, q3);          // side 1's first edge and what is left of the top run
+  if (!turned) put(0u, plo, phi, 1u << 22, 0u);              // every vertex on one row
+  return p;
+}
+// E: rec(pos, r) = the record at chain position pos.
+template <class E>
+struct FovWalk {
+  FovWalkSide s0, s1;
+  int last;                                                  // the chain's last position
+  bool wk;                                                   // OpenCV's walker runs (the polygon's rule)
+  template <int C>
+  RR_HD void fetch(FovWalkSide& S, const E& rec, int pos) const {
+    uint32_t r[4];
+    S.pos = pos;
+    rec(pos, r);
+    S.nx = fov_rec_words{r[0], r[1], r[2], r[3]};
+  }
+  template <int C>
+  RR_HD void init_side(FovWalkSide& S, const E& rec, int ytop) const {
+    S.yb = ytop;                                             // "the edge before" ends on the top row: the first row hands over
+    S.al = S.ah = S.R = S.W = S.dn = S.tl = S.th = S.qs = S.rs = S.d16 = 0;
+    fetch<C>(S, rec, C == 0 ? 0 : last);
+  }
+  RR_HD void init(const E& rec, int n_pos, int ytop, bool cv) {      // n_pos: what fov_walk_make_records returned
+    last = n_pos - 1;
+    wk = cv;
+    init_side<0>(s0, rec, ytop);
+    init_side<1>(s1, rec, ytop);
+  }
+  template <int C>
+  RR_HD void side_row(FovWalkSide& S, const E& rec, int y, int& lo, int& hi) const {
+    int x0 = S.al + (S.R >= S.tl ? 1 : 0), x1 = S.ah + (S.R >= S.th ? 1 : 0);
+    if (wk) {
+      const int sx = S.W >> 16;
+      x0 = imin(x0, sx);
+      x1 = imax(x1, sx);
+    }
+    {                                                        // a row down the current edge
+      const int r = S.R + S.rs;
+      const int carry = r >= S.dn ? 1 : 0;
+      S.R = r - (carry ? S.dn : 0);
+      S.al += S.qs + carry;
+      S.ah += S.qs + carry;
+      S.W += S.d16;
+    }
+    if (y == S.yb) {                                         // a vertex row: the hand-over
+      const uint32_t w0 = S.nx[0], w1 = S.nx[1], w2 = S.nx[2], w3 = S.nx[3];
+      x0 = (int)(w1 & 0xffffu);
+      x1 = (int)(w1 >> 16);
+      const int hh = (int)(w2 & 0x7ffu), den = (int)(w2 >> 22), xa = (int)(w3 >> 16);
+      S.d16 = (int)w0;
+      S.qs = S.d16 >> 16;
+      S.tl = (int)((w2 >> 11) & 0x7ffu);
+      S.dn = 2 * den;
+      S.th = (w3 & 0x800u) ? S.tl : S.dn - S.tl;
+      S.yb += den;
+      S.rs = (int)(w3 & 0x7ffu);
+      S.R = S.rs;                                            // t = 1: rs < 2 den, no carry
+      S.al = xa + S.qs - hh;
+      S.ah = xa + S.qs + hh;
+      S.W = (int)((w3 & 0xffff0000u) + 32768u + w0);
+      // the request for the record after it, last: it lands in the registers just read, and nothing waits for it here
+      // (scheduled earlier, the load needs registers of its own and a copy behind a full wait on every vertex row)
+#if defined(__HIP_DEVICE_COMPILE__)
+      __builtin_amdgcn_sched_barrier(0);
+#endif
+      fetch<C>(S, rec, C == 0 ? imin(S.pos + 1, last) : imax(S.pos - 1, 0));      // (past the terminator: never used)
+    }
+    lo = imin(lo, x0);
+    hi = imax(hi, x1);
+  }
+  RR_HD void row(const E& rec, int y, int& lo, int& hi) {   // rows ytop .. ybot IN ASCENDING ORDER
+    lo = 1 << 30;
+    hi = -(1 << 30);
+    side_row<0>(s0, rec, y, lo, hi);
+    side_row<1>(s1, rec, y, lo, hi);
+  }
+};
+
 // number of times the vertices' row sequence changes direction around the loop (a closed monotone curve: 2; all on one row: 0)
 RR_HD int poly_row_turns(const int32_t* py, int n) {
   int turns = 0, dir = 0, dir_first = 0;

@@ -2,8 +2,8 @@
 """CPU model of k_fov_dda's vertex path: which drops should share a wave?
 
 k_fov_dda walks a drop's field-of-view polygon down the rows of the environment map, one lane per drop.  The wave
-executes the walk's vertex path -- about 220 of its ~300 instructions per row -- on every row on which ANY of its 64
-polygons has a vertex.  This script counts those wave-rows for a frame of the headline workload under several orders of
+executes the walk's vertex path -- a hand-over of 24 / 27 vector instructions per side on top of the row's 45 (before the
+records became a chain: about 220 of ~300 per row) -- on every row on which ANY of its 64 polygons has a vertex.  This script counts those wave-rows for a frame of the headline workload under several orders of
 the drops, so that a sort key can be tried here before the kernel is touched (k_fov_vertices writes the key, k_fov_sort
 sorts by it; the key must be a pure function of the drop's record and the camera).
 
@@ -19,8 +19,10 @@ outside the union of the wave's polygons):
     by distance in 0.25 m buckets, then top row (default)   0.597         0.18
 
 The first line is what the counters showed for the kernel in table order (89 %: profiles/r06_ab_log.md section 3), so
-the model counts the right thing.  With ~80 straight-path instructions per wave-row and ~247 more on a vertex row the
-instruction count falls by about a quarter at 0.60.  Keys tried and no better than 0.56 .. 0.60: other bucket widths
+the model counts the right thing.  With ~45 straight-path instructions per wave-row and ~34 more on a vertex row (static
+count of the row loop: 24 / 27 per side that takes an edge, 1.33 sides per vertex row; SQ_INSTS_VALU: 1.37 G per launch, of
+which the record-making prologue is 0.19 G -- profiles/fov_walk_cost.md) the order takes an eighth off the row loop's
+instructions at 0.60: (45 + 34 x 0.597) / (45 + 34 x 0.888) = 0.87.  (With the walker before, ~80 and ~247: a quarter.)  Keys tried and no better than 0.56 .. 0.60: other bucket widths
 (0.35 m: 0.593; 0.125 m: 0.668), the polygon's height in place of the distance (height / 8, top row: 0.565; top row / 4,
 height: 0.559), the middle row in place of the top row (0.579): the polygon depends on three continuous parameters and a
 frame holds 113 waves.
