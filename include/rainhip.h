@@ -752,6 +752,34 @@ typedef struct {
 int rr_pipeline_set_layer(rr_ctx* ctx, int32_t slot, const rr_pipeline_layer* layer);
 int rr_sizeof_layer_out(void);
 int rr_sizeof_pipeline_layer(void);
+/* The rain layer as a FILE: rr_pipeline_set_layer_png ARMS a pipeline slot so that every batch submitted on it
+ * afterwards also leaves each frame's layer as the payload of a straight-alpha 8-bit RGBA PNG -- what rainy_png is for the image: H rows
+ * of 1 + 4 W bytes, filter type 1 (Sub), or under RR_OPT_PNG_DEFLATE the RRZ1 stream -- for rr_png_write_scanlines /
+ * rr_io_write_frames_text.  From a pixel's float32 (L_B, L_G, L_R, T):
+ *     a  = 1.0f - T                                   (float32)
+ *     A8 = clamp(rint(a * 255.0f), 0, 255)            (float32 multiply, half to even, NaN -> 0)
+ *     A8 == 0: R = G = B = 0;  else C_c = clamp(rint(double(L_c) * (65025.0 / double(A8))), 0, 255)   (NaN -> 0; c = R, G, B)
+ *     file pixel = (C_R, C_G, C_B, A8)
+ * The reader's T' = 1 - A8 / 255 and L'_c = A8 C_c / 65025 (PNG's `over` with the file's own numbers is T' x + L').  Wherever
+ * 0 <= T <= 1 and 0 <= L_c <= 1 - T -- which holds when kg_c <= te for every listed drop -- |T' - T| and |L'_c - L_c| are at most
+ * 1 / 510 plus the float32 rounding of a * 255, so |T' x + L' - (T x + L)| <= 1 / 255 for x in [0, 1].
+ *   layer_png   n HOST pointers, each NULL or a buffer of H * (1 + 4 W) bytes; downloaded by rr_pipeline_wait with the batch's other
+ *               outputs, exactly as rr_pipeline_lens.alpha_png is.  The table is copied by the call.
+ * The kernels: k_rain_layer's byte-store variant (the same walk, once; it also stores the float layer where rr_pipeline_set_layer
+ * armed one on the slot -- the two armings are independent) and k_png_layer for the Sub filter; under RR_OPT_PNG_DEFLATE the layer is
+ * one more stream of the device coder.  Armed until replaced or disarmed (NULL); every submit on the slot applies it once, the
+ * re-submit after RR_E_ARENA included; slot 0 also serves rr_pipeline_frames / rr_render_frames.  With nothing armed the kernels of a
+ * call are what they were.  Device staging, allocated by the first armed batch and kept: 4 H W bytes per frame for the RGBA pixels
+ * plus H (1 + 4 W), rounded up to 16, for the scanlines.
+ * RR_E_ARG, with nothing changed: a bad slot, n, H or W <= 0, a null table.  RR_E_STATE: the slot is in flight.  A submit on an armed
+ * slot returns RR_E_ARG with nothing enqueued when the batch's n, H or W are not the armed ones or when the batch renders nothing
+ * (in == NULL); so does rr_render_frames_device while slot 0 is armed: the file route is the host entry points'. */
+typedef struct {
+  int32_t n, H, W, reserved;
+  uint8_t* const* layer_png;             /* n HOST pointers (each may be NULL) */
+} rr_pipeline_layer_png;                 /* 24 bytes */
+int rr_pipeline_set_layer_png(rr_ctx* ctx, int32_t slot, const rr_pipeline_layer_png* layer_png);
+int rr_sizeof_pipeline_layer_png(void);
 /* The same for rr_augment_frames_device: armed until replaced or disarmed (layer == NULL, or all three pointers NULL), every call
  * (its re-enqueue after an arena growth included) fills, for its n frames at its H x W -- the render size under rr_set_input_resize --,
  *   layer_out        DEVICE [n,4,H,W] planar float32 in the order R, G, B, T (L_R, L_G, L_B, T), or NULL
@@ -1023,6 +1051,13 @@ int rr_io_read_frames_scaled(int32_t n, const char* const* image_paths, const ch
                              int64_t depth_stride, int32_t threads, int32_t* status);
 int rr_io_write_frames(int32_t n, const char* const* image_paths, const char* const* mask_paths, const uint8_t* rows_image,
                        const uint8_t* rows_mask, int64_t rows_stride, int32_t W, int32_t H, int32_t threads, int32_t* status);
+/*   rr_io_write_frames_text  one file kind per call: frame k's rows + k * rows_stride to paths[k] (a NULL path is skipped), with
+ *                       one tEXt chunk `keyword` NUL texts[k] between IHDR and IDAT -- the layer file's `rain-shift`.  texts == NULL
+ *                       (or texts[k] == NULL) writes no chunk: the file is then byte for byte rr_io_write_frames'.  The library
+ *                       embeds the bytes as they are; the caller formats them.  RR_E_ARG: with texts, a keyword that is not 1 to
+ *                       79 bytes of printable Latin-1 (32..126, 161..255) without leading, trailing or doubled spaces. */
+int rr_io_write_frames_text(int32_t n, const char* const* paths, const uint8_t* rows, int64_t rows_stride, int32_t W, int32_t H,
+                            const char* keyword, const char* const* texts, int32_t threads, int32_t* status);
 /* The codec's checksums: zlib's adler32(adler, p, n) and crc32(crc, p, n) (same values, same chaining; start from 1 and 0),
  * computed with SSSE3 / carry-less multiplication where the CPU has them (zlib's own loops otherwise). */
 uint32_t rr_adler32(uint32_t adler, const uint8_t* p, int64_t n);

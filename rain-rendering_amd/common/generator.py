@@ -39,6 +39,7 @@ def _cpu_budget():
 
 
 class Generator:
+    rain_layer = False                                           # --rain_layer: off unless __init__ says otherwise
     lens_spec, lens_alpha, _lens = None, False, None             # --lens_drops / --lens_alpha: off unless __init__ / run() say otherwise
 
     def __init__(self, args):
@@ -160,6 +161,8 @@ class Generator:
         if self.lens_alpha and self.lens_spec is None:
             raise ValueError("--lens_alpha needs --lens_drops")
         self._lens = None                                        # the current run's LensDrops (run())
+        # --rain_layer: the frame's rain layer as a fourth file, <out_dir>/rain_layer/<name>.png
+        self.rain_layer = bool(getattr(args, 'rain_layer', False))
         self.sim_options = getattr(args, 'sim_options', {})
         self.batch = int(os.environ.get('RAIN_BATCH', '128'))     # frames per library call (three calls in flight); bench.py's host-inclusive leg uses the same
         self.rank, self.world = sharding.rank_world()
@@ -266,11 +269,13 @@ class Generator:
         Every array is one page-locked block with the frames back to back, each on a 16-byte boundary (RainHip.host_rows):
         the library then moves an array of the whole batch with ONE copy instead of one DMA request per frame."""
 
-        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False, resize=None):
+        def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False, resize=None,
+                     rain_layer=False):
             """png_rows: the image / depth blocks hold the files' filtered scanlines (rr_io_read_frames_rows: H rows of 1 + 3 W /
             1 + 2 W bytes per frame) instead of pixels.  lens_alpha: a third scanline block, the label file of --lens_alpha.
             resize = (sh, sw, dh, dw), with png_rows: the scanlines are those of sh x sw images and dh x dw depth files (the library
-            resizes them to H x W: --device_resize); the output blocks keep H x W."""
+            resizes them to H x W: --device_resize); the output blocks keep H x W.  rain_layer: one more scanline block, the layer file
+            of --rain_layer, and the B doubles that receive the frames' mean shifts."""
             self.B, self.H, self.W = B, H, W
             sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
             self._raw = []
@@ -293,6 +298,10 @@ class Generator:
             self.png_a = rows((row,), np.uint8) if lens_alpha else None
             self.raw_png_a = self._raw[-1] if lens_alpha else None
             self.lens_alpha = bool(lens_alpha)
+            self.png_l = rows((row,), np.uint8) if rain_layer else None
+            self.raw_png_l = self._raw[-1] if rain_layer else None
+            self.shift = rows((1,), np.float64) if rain_layer else None
+            self.rain_layer = bool(rain_layer)
             self.drops_cap = drops_cap
             self.key = (B, H, W, We, 'png rows' if png_rows else np.dtype(bg_dtype), 'png rows' if png_rows else np.dtype(depth_dtype), bool(save_envmap))
             if resize is not None:
@@ -304,8 +313,8 @@ class Generator:
             """Page-locked memory is only returned by rr_host_free (dropping the numpy views frees nothing): called when
             a slot is replaced by a larger / differently shaped one, after its batch has been collected and encoded."""
             assert not self.busy and not self.encodes
-            self.bg = self.depth = self.drops = self.status = self.png_i = self.png_m = self.env = self.png_a = None
-            self.raw_bg = self.raw_depth = self.raw_drops = self.raw_png_i = self.raw_png_m = self.raw_png_a = None
+            self.bg = self.depth = self.drops = self.status = self.png_i = self.png_m = self.env = self.png_a = self.png_l = self.shift = None
+            self.raw_bg = self.raw_depth = self.raw_drops = self.raw_png_i = self.raw_png_m = self.raw_png_a = self.raw_png_l = None
             self.prep = None
             for raw in self._raw:
                 hip.host_free(raw)
@@ -330,6 +339,9 @@ class Generator:
         if self.lens_alpha:
             os.makedirs(os.path.dirname(item['out_lens_alpha_path']), exist_ok=True)
             imgops.png_from_scanlines(item['out_lens_alpha_path'], slot.png_a[k], W, H)
+        if self.rain_layer:
+            os.makedirs(os.path.dirname(item['out_rain_layer_path']), exist_ok=True)
+            imgops.png_from_scanlines(item['out_rain_layer_path'], slot.png_l[k], W, H, text=self._shift_text(slot, k))
         if self.save_envmap:
             os.makedirs(os.path.dirname(item['out_env_path']), exist_ok=True)
             env_bgr = slot.env[k] / 255.0                                              # generator.py:469 (plt.imsave of a float map)
@@ -424,6 +436,8 @@ class Generator:
                         out_env_path=os.path.join(out_seq_dir, 'envmap', '{}.png'.format(file_name[:-4])))
             if self.lens_alpha:                                  # (the skip rule below stays the reference's: rainy or mask file)
                 item['out_lens_alpha_path'] = os.path.join(out_dir, 'lens_alpha', '{}.png'.format(file_name[:-4]))
+            if self.rain_layer:
+                item['out_rain_layer_path'] = os.path.join(out_dir, 'rain_layer', '{}.png'.format(file_name[:-4]))
             if os.path.exists(item['out_rainy_path']) or os.path.exists(item['out_rainy_mask_path']):
                 if self.conflict_strategy == "skip":
                     frames_exist_nb += 1
@@ -474,6 +488,21 @@ class Generator:
             return
         hip.pipeline_set_lens(si, tables, self._lens.weights(), sl.H, sl.W,
                               alpha_png=[sl.png_a[k] for k in range(len(tables))] if self.lens_alpha else None)
+
+    def _arm_layer(self, hip, si, sl, n):
+        """Before a batch of n frames is submitted on slot si with --rain_layer: the frames' layer-file buffers
+        (rr_pipeline_set_layer_png) and, through rr_pipeline_set_layer with no float layer, the doubles that receive their shifts.
+        The outputs go by slot position, so the frames a decode skipped leave no gap."""
+        if not self.rain_layer:
+            return
+        hip.pipeline_set_layer_png(si, [sl.png_l[k] for k in range(n)], sl.H, sl.W)
+        hip.pipeline_set_layer(si, [dict(layer=None, shift=sl.shift[k]) for k in range(n)])
+
+    @staticmethod
+    def _shift_text(sl, k):
+        """The layer file's tEXt chunk: (keyword, repr of frame k's mean shift)."""
+        from ..tools import layer_png
+        return layer_png.SHIFT_KEYWORD, repr(float(sl.shift[k][0]))
 
     def _mark(self, name):
         """set-up clock: seconds since run() began at which a stage of the set-up was finished (timing[...]['setup'])"""
@@ -730,8 +759,10 @@ class Generator:
             key += (tuple(resize),)
         sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
         lens_alpha = self._lens is not None and self.lens_alpha
+        rain_layer = self.rain_layer
         pkey = (tuple(float(v) for v in fog_const), float(self.opacity_attenuation), self.rendering_strategy, sims is not None)
-        for d in {os.path.dirname(it[k]) for it in work for k in ('out_rainy_path', 'out_rainy_mask_path') + (('out_lens_alpha_path',) if lens_alpha else ())}:
+        for d in {os.path.dirname(it[k]) for it in work for k in ('out_rainy_path', 'out_rainy_mask_path') + (('out_lens_alpha_path',) if lens_alpha else ())
+                  + (('out_rain_layer_path',) if rain_layer else ())}:
             os.makedirs(d, exist_ok=True)
         encodes = [None] * nslot                                 # the slot's encode job (future) and its frames
         done = [0]
@@ -739,13 +770,14 @@ class Generator:
         pending = {}                                             # slots being page-locked by the helper thread (see below)
 
         def new_slot():
-            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha, resize=resize)
+            return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha, resize=resize,
+                                   rain_layer=rain_layer)
 
         def slot_for(si):
             if si in pending:
                 slots[si] = pending.pop(si).result()
             sl = slots[si]
-            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha):
+            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha) or (rain_layer and not sl.rain_layer):
                 if sl is not None:
                     sl.free(hip)
                 sl = slots[si] = new_slot()
@@ -845,6 +877,13 @@ class Generator:
                 if st.any():
                     bad = int(np.nonzero(st)[0][0])
                     raise IOError("could not write %s (%d)" % (items[bad]['out_lens_alpha_path'], st[bad]))
+            if rain_layer:                                      # the layer files, each with its own shift in a tEXt chunk
+                kw = self._shift_text(sl, 0)[0]
+                st = hip_backend.io_write_frames_text([it['out_rain_layer_path'] for it in items], sl.raw_png_l, W, H, kw,
+                                                      [self._shift_text(sl, k)[1] for k in range(len(items))], threads)
+                if st.any():
+                    bad = int(np.nonzero(st)[0][0])
+                    raise IOError("could not write %s (%d)" % (items[bad]['out_rain_layer_path'], st[bad]))
             return [dict(file=it['out_rainy_path'], drops=nd, skipped=int(np.count_nonzero(sl.status[k][:nd])), gpu_ms=gpu_ms)
                     for k, (it, nd) in enumerate(zip(items, nds))]
 
@@ -885,7 +924,7 @@ class Generator:
         maker = None
         for si in range(1, min(nslot, len(batches))):
             sl = slots[si]
-            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha):
+            if sl is None or sl.key != key or sl.drops_cap < drops_cap or (lens_alpha and not sl.lens_alpha) or (rain_layer and not sl.rain_layer):
                 if sl is not None:
                     sl.free(hip)
                     slots[si] = None
@@ -918,6 +957,7 @@ class Generator:
                         sl.prep.set_drop_count(k, nd)
                 sl.t_submit = time.time()
                 self._arm_lens(hip, si, sl, getattr(sl, 'lens_tables', None))
+                self._arm_layer(hip, si, sl, sl.n_valid)
                 hip.pipeline_submit_prepared(si, sl.prep, sl.n_valid)
                 if bi == 0:
                     self._mark('first batch submitted')
@@ -929,7 +969,8 @@ class Generator:
             if bi + 1 < len(batches):                            # and decode the next one into the slot that is idle now
                 sn = (bi + 1) % nslot
                 finish(sn)
-                if slots[sn] is not None and (slots[sn].key != key or slots[sn].drops_cap < drops_cap or (lens_alpha and not slots[sn].lens_alpha)):
+                if slots[sn] is not None and (slots[sn].key != key or slots[sn].drops_cap < drops_cap or (lens_alpha and not slots[sn].lens_alpha) or
+                                              (rain_layer and not slots[sn].rain_layer)):
                     drain(sn)                                    # (a slot of another shape is replaced: its encoders first)
                 decoding = stage.submit(decode_job, slot_for(sn), batches[bi + 1])
             if self.verbose:
@@ -1028,11 +1069,11 @@ class Generator:
             key = (B, H, W, state['env_w'], bg0.dtype, dep0.dtype, bool(self.save_envmap))
             sl = slots[si]
             lens_alpha = self._lens is not None and self.lens_alpha
-            if sl is None or sl.key != key or sl.drops_cap < need_drops or (lens_alpha and not sl.lens_alpha):
+            if sl is None or sl.key != key or sl.drops_cap < need_drops or (lens_alpha and not sl.lens_alpha) or (self.rain_layer and not sl.rain_layer):
                 if sl is not None:                               # (finish / drain above left it idle)
                     sl.free(hip)
                 sl = slots[si] = Generator._Slot(hip, B, H, W, state['env_w'], bg0.dtype, dep0.dtype, self.save_envmap,
-                                                 max(need_drops + need_drops // 4, 1024), lens_alpha=lens_alpha)
+                                                 max(need_drops + need_drops // 4, 1024), lens_alpha=lens_alpha, rain_layer=self.rain_layer)
             # the batch's descriptors are made once per slot (the buffers do not move) and for the run's constants
             pkey = (tuple(float(v) for v in fog_const), float(self.opacity_attenuation), self.rendering_strategy)
             if getattr(sl, 'prep', None) is None or sl.pkey != pkey:
@@ -1060,6 +1101,7 @@ class Generator:
             sl.t_submit = time.time()
             if self._lens is not None:                           # the frames' lens drops, in slot order (skipped frames leave no gap)
                 self._arm_lens(hip, si, sl, self._lens_tables([it for it, _ in valid]))
+            self._arm_layer(hip, si, sl, sl.n_valid)
             hip.pipeline_submit_prepared(si, sl.prep, sl.n_valid)
             if t_first is None:
                 t_first = time.time()                            # set-up (pinned buffers, first decodes) ends here

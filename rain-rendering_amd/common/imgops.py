@@ -167,10 +167,23 @@ def viridis_lut():
     return _viridis
 
 
-def png_from_scanlines(path, rows, width, height, level=None, strategy=None):
+def png_keyword_ok(keyword):
+    """PNG's keyword rule: 1 to 79 bytes of printable Latin-1 (32..126, 161..255), no leading, trailing or doubled spaces."""
+    kw = keyword if isinstance(keyword, bytes) else str(keyword).encode('latin-1')
+    return (1 <= len(kw) <= 79 and all(32 <= c <= 126 or c >= 161 for c in kw) and not kw.startswith(b' ') and not kw.endswith(b' ')
+            and b'  ' not in kw)
+
+
+def png_from_scanlines(path, rows, width, height, level=None, strategy=None, text=None):
     """An RGBA PNG file from its filtered scanlines (height rows of 1 + 4*width bytes, as the library's
     rr_frame_out.rainy_png / mask_png deliver them): zlib deflate + chunk framing inside the library
-    (rr_png_write_scanlines), off the interpreter lock."""
+    (rr_png_write_scanlines), off the interpreter lock.
+    text: None, or (keyword, string) -- one tEXt chunk between IHDR and IDAT, as rr_io_write_frames_text writes it (the layer
+    files' `rain-shift`); ValueError for a keyword PNG refuses."""
+    if text is not None:
+        kw, val = (t if isinstance(t, bytes) else str(t).encode('latin-1') for t in text)
+        if not png_keyword_ok(kw) or b'\0' in val:
+            raise ValueError("png_from_scanlines: %r is not a PNG keyword (1 to 79 printable Latin-1 bytes), or the text holds a NUL" % (text[0],))
     from .. import hip_backend
     rows = np.ascontiguousarray(rows, np.uint8)
     assert rows.nbytes == height * (1 + 4 * width)
@@ -179,6 +192,30 @@ def png_from_scanlines(path, rows, width, height, level=None, strategy=None):
                                                            PNG_STRATEGY if strategy is None else int(strategy))
     if rc != 0:
         raise IOError("rr_png_write_scanlines(%s) failed (%d)" % (path, rc))
+    if text is not None:                  # the chunk goes in behind the 8-byte signature and the 25-byte IHDR chunk
+        import struct
+        import zlib
+        body = b'tEXt' + kw + b'\0' + val
+        with open(path, 'rb') as fh:
+            data = fh.read()
+        with open(path, 'wb') as fh:
+            fh.write(data[:33] + struct.pack('>I', len(body) - 4) + body + struct.pack('>I', zlib.crc32(body) & 0xffffffff) + data[33:])
+
+
+def read_rain_layer(path):
+    """A layer file of `main.py --rain_layer` -> (layer, shift): layer [H, W, 4] float64 in the order L_B, L_G, L_R, T
+    (tools/layer_png.py decode of the file's straight-alpha RGBA), shift the float of the file's tEXt chunk `rain-shift`, or None
+    where the file has none.  rainy_rgb is uint8(clip01(T rainy_bg + L - shift) 255) within 2 codes."""
+    from PIL import Image
+    from ..tools import layer_png
+    with Image.open(path) as im:
+        im.load()
+        if im.mode != 'RGBA':
+            raise ValueError("%s: a layer file is an 8-bit RGBA PNG, this one is %s" % (path, im.mode))
+        rgba = np.array(im)
+        txt = getattr(im, 'text', {}).get(layer_png.SHIFT_KEYWORD)
+    lb, lg, lr, t = layer_png.decode(rgba)
+    return np.stack([lb, lg, lr, t], axis=-1), (None if txt is None else float(txt))
 
 
 def imsave_scalar(path, a):

@@ -4633,6 +4633,8 @@ __global__ __launch_bounds__(RSZ_THREADS) void k_resize_depth(const ResizeArgs a
 // KINDS (a slot armed with rr_pipeline_set_lens that writes the label): 3 = file = 3 * frame + {image, mask, label}, the
 // label's scanlines (k_png_alpha) at label.rows + frame * label.stride.  KINDS = 2 is the kernel as it was: the argument is an empty
 // struct behind every other one, like WindArgs<false>.
+// KINDS - 2 is the number of EXTRA streams a frame has besides image and mask: none, one (the lens label, or the layer file of
+// rr_pipeline_set_layer_png, DESIGN.md 5r: k_png_layer's scanlines) or two (4 = file = 4 * frame + {image, mask, label, layer}).
 template <int KINDS>
 struct PngzLabel {};
 template <>
@@ -4640,9 +4642,20 @@ struct PngzLabel<3> {
   uint8_t* rows;
   int64_t stride;
 };
+template <>
+struct PngzLabel<4> {
+  uint8_t* rows;
+  int64_t stride;
+  uint8_t* rows2;
+  int64_t stride2;
+};
 template <int KINDS>
 __device__ inline uint8_t* pngz_rows(const FrameDesc* frames, int file, const PngzLabel<KINDS>& label) {
-  if constexpr (KINDS == 3) {
+  if constexpr (KINDS == 4) {
+    const int f = file >> 2, kind = file & 3;
+    return kind == 3 ? label.rows2 + (int64_t)f * label.stride2
+                     : (kind == 2 ? label.rows + (int64_t)f * label.stride : (kind == 1 ? frames[f].png_mask : frames[f].png_image));
+  } else if constexpr (KINDS == 3) {
     const int f = file / 3, kind = file - 3 * f;
     return kind == 2 ? label.rows + (int64_t)f * label.stride : (kind == 1 ? frames[f].png_mask : frames[f].png_image);
   } else {
@@ -5866,6 +5879,15 @@ struct rr_ctx {
       std::vector<rr_layer_out> frames;
       rrmem::Buf<char> stage;
     } layer;
+    // rr_pipeline_set_layer_png: the caller's n host buffers, copied by the arming call, and the device staging --
+    // the RGBA pixels k_rain_layer<2> leaves ([n][H][W][4]) and the scanlines k_png_layer makes of them (n blocks, Strides.pngb
+    // apart) -- allocated by the first armed batch (grown, never shrunk)
+    struct LayerPng {
+      bool armed = false;
+      int n = 0, H = 0, W = 0;
+      std::vector<uint8_t*> bufs;
+      rrmem::Buf<uint8_t> rgba, rows;
+    } lpng;
   } slots[RR_PIPE_SLOTS];
   // the rain layer: a batch's LayerDesc records on the device (written in stream order, like d_frames), and what
   // rr_augment_set_layer armed rr_augment_frames_device with
@@ -6187,8 +6209,18 @@ struct LensStage {
   int64_t rgb_stride, png_stride;
 };
 
+// The layer file of a batch on a slot armed with rr_pipeline_set_layer_png: the slot's RGBA staging and scanline blocks.
+// Given only together with `layer`, whose want_rgba flags name the frames.
+struct LayerPngStage {
+  uint8_t* rgba;
+  int64_t rgba_stride;
+  uint8_t* rows;
+  int64_t rows_stride;
+};
+
 int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, hipStream_t s, int ovf_idx = 0,
-            const PlanarOut* planar = nullptr, const LensStage* lens = nullptr, const LayerDesc* layer = nullptr) {
+            const PlanarOut* planar = nullptr, const LensStage* lens = nullptr, const LayerDesc* layer = nullptr,
+            const LayerPngStage* lpng = nullptr) {
   if (!ctx->have_cam || !ctx->have_db) {
     ctx->err = "streak DB and camera must be set before rendering";
     return RR_E_STATE;
@@ -6591,7 +6623,10 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     const int tiles_y32 = (dm.H + TILE32_H - 1) / TILE32_H, nt32 = tiles_x * tiles_y32;
     const dim3 grid(((nt32 + 7) / 8) * 8, n);
     ProfScope ps(ctx, s, "k_rain_layer");
-    if (layer[0].planar)
+    if (lpng)                                              // the file's bytes, and the float pixel where a frame has both: one walk
+      hipLaunchKernelGGL((k_rain_layer<2, LayerBytes>), grid, dim3(256), 0, s, ctx->d_frames, ctx->layer_desc.p, dm, ctx->cam.exposure_s, D, tiles_x, tiles_y32, ctiles_x, nct,
+                         ctx->arena_cap, sc, LayerBytes{lpng->rgba, lpng->rgba_stride});
+    else if (layer[0].planar)
       hipLaunchKernelGGL(k_rain_layer<1>, grid, dim3(256), 0, s, ctx->d_frames, ctx->layer_desc.p, dm, ctx->cam.exposure_s, D, tiles_x, tiles_y32, ctiles_x, nct,
                          ctx->arena_cap, sc);
     else
@@ -6648,19 +6683,36 @@ int enqueue(rr_ctx* ctx, int n, const rr_frame_in* in, const rr_frame_out* out, 
     hipLaunchKernelGGL(k_png_alpha, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, lens->lens->label.p, lens->lens->png.p,
                        lens->png_stride, dm);
   }
-  if (want_png && ctx->png_deflate) {
+  if (lpng) {                                            // the layer file's scanlines, of the bytes k_rain_layer<2> left
+    ProfScope ps(ctx, s, "k_png_layer");
+    hipLaunchKernelGGL(k_png_layer, dim3((unsigned)(((int64_t)dm.H * dm.W + 255) / 256), n), dim3(256), 0, s, ctx->layer_desc.p, lpng->rgba, lpng->rgba_stride,
+                       lpng->rows, lpng->rows_stride, dm);
+  }
+  if ((want_png || lpng) && ctx->png_deflate) {
     const int64_t n_bytes = (int64_t)dm.H * (1 + 4 * (int64_t)dm.W);
     const int nb = (int)rrz::blocks_of(n_bytes);
-    const size_t need = (size_t)(lens_png ? 3 : 2) * n * nb;
+    const int kinds = 2 + (lens_png ? 1 : 0) + (lpng ? 1 : 0);
+    const size_t need = (size_t)kinds * n * nb;
     int rc;
     if ((rc = reserve(ctx, ctx->pngz_slots, need * rrz::SLOT_BYTES)) || (rc = reserve(ctx, ctx->pngz_meta, need))) return rc;
     if (!ctx->pngz_attr) {
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pngz_blocks<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(rrz::BlockState)));
       ctx->pngz_attr = true;
     }
     ProfScope ps(ctx, s, "k_pngz");
-    if (lens_png) {                                      // image, mask and the label: three streams per frame
+    if (kinds == 4) {                                    // image, mask, the label and the layer: four streams per frame
+      const PngzLabel<4> extra{lens->lens->png.p, lens->png_stride, lpng->rows, lpng->rows_stride};
+      hipLaunchKernelGGL(k_pngz_blocks<4>, dim3(nb, 4 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p,
+                         ctx->pngz_meta.p, extra);
+      hipLaunchKernelGGL(k_pngz_pack<4>, dim3(nb, 4 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p, ctx->pngz_meta.p, extra);
+    } else if (lpng) {                                   // image, mask and the layer: the extra stream is the layer's
+      const PngzLabel<3> extra{lpng->rows, lpng->rows_stride};
+      hipLaunchKernelGGL(k_pngz_blocks<3>, dim3(nb, 3 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p,
+                         ctx->pngz_meta.p, extra);
+      hipLaunchKernelGGL(k_pngz_pack<3>, dim3(nb, 3 * n), dim3(256), 0, s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p, ctx->pngz_meta.p, extra);
+    } else if (lens_png) {                               // image, mask and the label: three streams per frame
       const PngzLabel<3> label{lens->lens->png.p, lens->png_stride};
       hipLaunchKernelGGL(k_pngz_blocks<3>, dim3(nb, 3 * n), dim3(rrz::NT), sizeof(rrz::BlockState), s, ctx->d_frames, n_bytes, nb, ctx->pngz_slots.p,
                          ctx->pngz_meta.p, label);
@@ -7623,6 +7675,10 @@ int rr_render_frames_device(rr_ctx* ctx, int32_t n, const rr_frame_in* in, const
   if (!ctx) return RR_E_ARG;
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if (ctx->slots[0].lpng.armed) {                          // (the file route downloads: it is the host entry points')
+    ctx->err = "rr_render_frames_device: slot 0 is armed with rr_pipeline_set_layer_png (host buffers): disarm it, or use a host entry point";
+    return RR_E_ARG;
+  }
   const rr_ctx::Slot::Layer& L = ctx->slots[0].layer;      // slot 0 armed with rr_pipeline_set_layer: DEVICE pointers here
   if (!L.armed) return enqueue(ctx, n, in, out, s);
   if ((int)L.frames.size() != n) {
@@ -8400,6 +8456,12 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
                          std::to_string(n);
     return RR_E_ARG;
   }
+  if (sl.lpng.armed && (!in || sl.lpng.n != n || sl.lpng.H != dm.H || sl.lpng.W != dm.W)) {
+    ctx->err = !in ? "pipeline slot armed with rr_pipeline_set_layer_png: the batch renders nothing (in == NULL)"
+                   : "pipeline slot armed with rr_pipeline_set_layer_png for " + std::to_string(sl.lpng.n) + " frames of " + std::to_string(sl.lpng.H) + " x " +
+                         std::to_string(sl.lpng.W) + ": the batch has " + std::to_string(n) + " of " + std::to_string(dm.H) + " x " + std::to_string(dm.W);
+    return RR_E_ARG;
+  }
   if ((rc = slot_init(ctx, sl))) return rc;
   for (void*& b : sl.ext_blobs) ctx->mem.free(b);      // the slot's previous batch is complete (not busy)
   sl.ext_blobs.clear();
@@ -8667,7 +8729,15 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
                                   lo.shift ? reinterpret_cast<double*>(sl.layer.stage.p + (size_t)n * px * 16 + (size_t)f * 8) : nullptr, nullptr, 0, 0};
       }
     }
-    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot, nullptr, sl.lens.armed ? &stage : nullptr, sl.layer.armed ? ld.data() : nullptr)))
+    LayerPngStage lstage{nullptr, 0, nullptr, 0};        // an armed layer file: independent of the float layer, the same records
+    if (sl.lpng.armed) {
+      if ((rc = reserve(ctx, sl.lpng.rgba, (size_t)n * px * 4)) || (rc = reserve(ctx, sl.lpng.rows, (size_t)n * T.pngb))) return drained(rc);
+      if (ld.empty()) ld.assign((size_t)n, LayerDesc{nullptr, nullptr, nullptr, 0, 0});
+      for (int f = 0; f < n; f++) ld[(size_t)f].want_rgba = sl.lpng.bufs[(size_t)f] ? 1 : 0;
+      lstage = LayerPngStage{sl.lpng.rgba.p, (int64_t)(px * 4), sl.lpng.rows.p, (int64_t)T.pngb};
+    }
+    if ((rc = enqueue(ctx, n, din.data(), dout.data(), s, 1 + slot, nullptr, sl.lens.armed ? &stage : nullptr, ld.empty() ? nullptr : ld.data(),
+                      sl.lpng.armed ? &lstage : nullptr)))
       return drained(rc);
   }
   if (hipEventRecord(sl.ev_comp, s) != hipSuccess) {
@@ -8688,6 +8758,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if (out[f].rainy_png) down.add(out[f].rainy_png, dout[f].rainy_png, png_bytes);
     if (out[f].mask_png) down.add(out[f].mask_png, dout[f].mask_png, png_bytes);
     if (sl.lens.armed && sl.lens.want_alpha && sl.lens.alpha_png[(size_t)f]) down.add(sl.lens.alpha_png[(size_t)f], sl.lens.png.p + (size_t)f * T.pngb, png_bytes);
+    if (sl.lpng.armed && sl.lpng.bufs[(size_t)f]) down.add(sl.lpng.bufs[(size_t)f], sl.lpng.rows.p + (size_t)f * T.pngb, png_bytes);
     if (sl.layer.armed && sl.layer.frames[(size_t)f].layer) down.add(sl.layer.frames[(size_t)f].layer, sl.layer.stage.p + (size_t)f * px * 16, px * 16);
     if (sl.layer.armed && sl.layer.frames[(size_t)f].shift)
       down.add(sl.layer.frames[(size_t)f].shift, sl.layer.stage.p + (size_t)n * px * 16 + (size_t)f * 8, sizeof(double));
@@ -9110,11 +9181,49 @@ int set_layer(rr_ctx* ctx, int slot, const rr_pipeline_layer* b) {
   return RR_OK;
 }
 
+// rr_pipeline_set_layer_png: every check first; nothing of the slot changes before the last one has passed
+int set_layer_png(rr_ctx* ctx, int slot, const rr_pipeline_layer_png* b) {
+  if (slot < 0 || slot >= RR_PIPE_SLOTS) {
+    ctx->err = "rr_pipeline_set_layer_png: bad pipeline slot";
+    return RR_E_ARG;
+  }
+  rr_ctx::Slot& sl = ctx->slots[slot];
+  if (sl.busy) {
+    ctx->err = "rr_pipeline_set_layer_png: pipeline slot still in flight: call rr_pipeline_wait first";
+    return RR_E_STATE;
+  }
+  if (!b) {
+    sl.lpng.armed = false;
+    sl.lpng.bufs.clear();
+    return RR_OK;
+  }
+  if (b->n <= 0 || b->H <= 0 || b->W <= 0 || (int64_t)b->H * b->W >= ((int64_t)1 << 31)) {
+    ctx->err = "rr_pipeline_set_layer_png: n, H and W must be positive (and H W below 2^31)";
+    return RR_E_ARG;
+  }
+  if (!b->layer_png) {
+    ctx->err = "rr_pipeline_set_layer_png: layer_png is NULL (the table of n host pointers)";
+    return RR_E_ARG;
+  }
+  sl.lpng.bufs.assign(b->layer_png, b->layer_png + b->n);
+  sl.lpng.n = b->n;
+  sl.lpng.H = b->H;
+  sl.lpng.W = b->W;
+  sl.lpng.armed = true;
+  return RR_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int rr_sizeof_layer_out(void) { return (int)sizeof(rr_layer_out); }
+int rr_sizeof_pipeline_layer_png(void) { return (int)sizeof(rr_pipeline_layer_png); }
+
+int rr_pipeline_set_layer_png(rr_ctx* ctx, int32_t slot, const rr_pipeline_layer_png* layer_png) {
+  if (!ctx) return RR_E_ARG;
+  return set_layer_png(ctx, slot, layer_png);
+}
 int rr_sizeof_pipeline_layer(void) { return (int)sizeof(rr_pipeline_layer); }
 int rr_sizeof_tensor_layer(void) { return (int)sizeof(rr_tensor_layer); }
 

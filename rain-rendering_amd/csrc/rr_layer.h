@@ -24,29 +24,66 @@
 // Sufficient for "no blend clamped": the inputs lie in [0, 1] and kg_c <= te for every listed drop -- each blend is then a convex
 // combination of the pixel and kg_c / te.  The layer knows nothing of the lens pass, exactly like the mask.
 //
-// Included by rainhip.hip inside its anonymous namespace, behind k_composite32 (TILE32_H, float2_t, u32x4_t), FrameDesc and Scratch.
+// The layer FILE (rr_pipeline_set_layer_png): the pixel as straight-alpha 8-bit RGBA, layer_rgba() below -- the
+// RR_HD statement k_rain_layer<2> calls on gfx950 and g++ compiles for the CPU tier (tests/test_layer_png_host.py), which holds it
+// equal, byte for byte, to its numpy statement in rain-rendering_amd/tools/layer_png.py (encode).
+//   k_rain_layer<2>        the same walk with the byte store: 4 bytes per pixel into the slot's [n][H][W][4] RGBA staging, and the
+//                          16-byte float pixel as well where the frame's float layer is armed
+//   k_png_layer            the staging as the file's scanlines: H rows of 1 + 4 W bytes, filter type 1 (Sub)
+//
+// Included by rainhip.hip inside its anonymous namespace, behind k_composite32 (TILE32_H, float2_t, u32x4_t), FrameDesc and Scratch;
+// the statement alone by a g++ source, behind rr_device.h and rr_lens.h.
 #ifndef RR_LAYER_H
 #define RR_LAYER_H
+
+// One pixel of the layer file from its float32 (L_B, L_G, L_R, T): the bytes R, G, B, A of a straight-alpha RGBA pixel, R in the
+// low byte of the word.  a = 1 - T in float32; A8 = clamp(rint(a * 255.0f), 0, 255), half to even, NaN -> 0 (lens_round_u8's rule);
+// the colour is divided by the QUANTISED alpha, in double: C_c = clamp(rint(L_c * (65025 / A8)), 0, 255), NaN -> 0; A8 == 0 gives
+// (0, 0, 0, 0).  The reader's T' = 1 - A8 / 255, L'_c = A8 C_c / 65025 then recompose over x as T' x + L' (PNG's `over`).
+RR_HD uint8_t layer_colour_u8(float l, double q) { return (uint8_t)(int)fmin(fmax(rint((double)l * q), 0.0), 255.0); }
+RR_HD uint32_t layer_rgba(float lb, float lg, float lr, float T) {
+  const float a = 1.0f - T;
+  const uint32_t A8 = rrlens::lens_round_u8(a * 255.0f);
+  if (A8 == 0u) return 0u;
+  const double q = 65025.0 / (double)A8;
+  return (uint32_t)layer_colour_u8(lr, q) | ((uint32_t)layer_colour_u8(lg, q) << 8) | ((uint32_t)layer_colour_u8(lb, q) << 16) | (A8 << 24);
+}
+
+#if defined(__HIPCC__)
 
 // where one frame's layer goes (device pointers, each may be null); uploaded per batch beside the frame descriptors
 struct LayerDesc {
   float* layer;                      // [H][W][4] (L_B, L_G, L_R, T), 16-byte aligned; planar: [4][H][W] in the order R, G, B, T
   double* shift;                     // one double
   float* background;                 // [3][H][W] R, G, B: float(rainy_bg), the values the compositor read
-  int32_t planar, reserved;
+  int32_t planar, want_rgba;         // want_rgba (k_rain_layer<2>, k_png_layer): the frame's layer file is asked for
 };
 static_assert(sizeof(LayerDesc) == 32, "LayerDesc is uploaded as 4-byte words");
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
+
+// MODE 2's own argument, the pack Extra of k_rain_layer<2, LayerBytes>: the slot's RGBA staging, frame f at rgba + f * stride (a
+// multiple of 4).  MODE 0 and 1 are instantiated with an empty pack: their arguments are what they were.
+struct LayerBytes {
+  uint8_t* rgba;
+  int64_t stride;
+};
+template <class T>
+__device__ inline const T& layer_extra(const T& t) { return t; }
 
 // The walk is k_composite32's: the same coarse list, the same split into four wave quadrants of a 16 x 32 tile, the same entry
 // order, a lane's two pixels eight rows apart -- so the layer sees exactly the entries the image saw.  What made that loop fast is
 // kept: the records of up to 64 entries in twelve vector registers handed out by v_readlane, the samples requested two entries
 // ahead behind static load counts, a sample outside the footprint read from the frame's zero line.  It loads no image, builds no
 // mask and reduces nothing over the tile.
-template <int PLANAR>
+// MODE: 0 the interleaved float pixel, 1 (PLANAR) the four float planes, 2 the file's RGBA bytes -- quantised in registers
+// (layer_rgba), one 4-byte store per pixel, a wave row of eight lanes 32 contiguous bytes -- and the interleaved float pixel too
+// where the frame has a float layer: the one walk stores both.
+template <int MODE, class... Extra>
 __global__ __launch_bounds__(256) void k_rain_layer(const FrameDesc* frames, const LayerDesc* outs, Dims dm, double exposure, int max_drops,
-                                                    int tiles_x, int tiles_y, int ctiles_x, int nct, int64_t arena_cap, Scratch sc) {
+                                                    int tiles_x, int tiles_y, int ctiles_x, int nct, int64_t arena_cap, Scratch sc, Extra... extra) {
+  static_assert(sizeof...(Extra) == (MODE == 2 ? 1 : 0), "MODE 2 takes LayerBytes, MODE 0 and 1 nothing");
+  constexpr int PLANAR = MODE == 1;
   const int f = blockIdx.y;
   const int ntiles = tiles_x * tiles_y, per_xcd = (ntiles + 7) / 8;
   const int tile = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);      // XCD k: the k-th eighth of the tiles (shared L2)
@@ -59,7 +96,9 @@ __global__ __launch_bounds__(256) void k_rain_layer(const FrameDesc* frames, con
   const void* const fr_depth = fr->depth;
   const int fr_depth_f64 = fr->depth_f64;
   float* const out = od->layer;
-  if (!out) return;                                                 // (the frame asks for its shift alone)
+  bool want_rgba = false;
+  if constexpr (MODE == 2) want_rgba = od->want_rgba != 0;
+  if (!out && !want_rgba) return;                                   // (the frame asks for its shift alone)
   const int tx0 = txi * TILE, ty0 = tyi * TILE32_H, tx1 = min(tx0 + TILE, dm.W), ty1 = min(ty0 + TILE32_H, dm.H);
   const int px = tx0 + 8 * (wave & 1) + (lane & 7);
   const int py0 = ty0 + 16 * (wave >> 1) + (lane >> 3), py1 = py0 + 8;
@@ -201,11 +240,40 @@ __global__ __launch_bounds__(256) void k_rain_layer(const FrameDesc* frames, con
     const global_ptr<float> o = as_global(out);
     if (live0) { o[pix0] = l2.x; o[np + pix0] = l1.x; o[2 * np + pix0] = l0.x; o[3 * np + pix0] = tr.x; }
     if (live1) { o[pix1] = l2.y; o[np + pix1] = l1.y; o[2 * np + pix1] = l0.y; o[3 * np + pix1] = tr.y; }
+  } else if constexpr (MODE == 2) {   // (both pointers wave-uniform: scalar loads of the descriptor)
+    if (want_rgba) {
+      const LayerBytes& bytes = layer_extra(extra...);
+      const global_ptr<uint32_t> o = as_global(reinterpret_cast<uint32_t*>(bytes.rgba + (int64_t)f * bytes.stride));
+      if (live0) o[pix0] = layer_rgba(l0.x, l1.x, l2.x, tr.x);
+      if (live1) o[pix1] = layer_rgba(l0.y, l1.y, l2.y, tr.y);
+    }
+    if (out) {
+      const global_ptr<float4_t> o = as_global(reinterpret_cast<float4_t*>(out));
+      if (live0) o[pix0] = float4_t{l0.x, l1.x, l2.x, tr.x};
+      if (live1) o[pix1] = float4_t{l0.y, l1.y, l2.y, tr.y};
+    }
   } else {
     const global_ptr<float4_t> o = as_global(reinterpret_cast<float4_t*>(out));
     if (live0) o[pix0] = float4_t{l0.x, l1.x, l2.x, tr.x};
     if (live1) o[pix1] = float4_t{l0.y, l1.y, l2.y, tr.y};
   }
+}
+
+// The layer file of a frame, ready for deflate: what k_png_image makes of an image, of the RGBA staging k_rain_layer<2> left -- H rows
+// of 1 + 4 W bytes, filter type 1 (Sub).  A pixel and its left neighbour are two aligned dwords of the staging; the row's bytes start
+// at an odd address, so they leave as bytes.  A frame whose file is not asked for is left alone.
+__global__ __launch_bounds__(256) void k_png_layer(const LayerDesc* outs, const uint8_t* rgba, int64_t rgba_stride, uint8_t* rows, int64_t rows_stride,
+                                                   Dims dm) {
+  const int f = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (!as_constant(outs + f)->want_rgba || pix >= (int64_t)dm.H * dm.W) return;
+  const int y = (int)(pix / dm.W), x = (int)(pix - (int64_t)y * dm.W);
+  const global_ptr<const uint32_t> s = as_global(reinterpret_cast<const uint32_t*>(rgba + (int64_t)f * rgba_stride)) + pix;
+  const uint32_t cur = s[0], left = x > 0 ? s[-1] : 0u;
+  const global_ptr<uint8_t> o = as_global(rows) + (int64_t)f * rows_stride + (int64_t)y * (1 + 4 * dm.W) + 1 + 4 * x;
+  if (x == 0) o[-1] = 1;                                // filter type: Sub
+#pragma unroll
+  for (int c = 0; c < 4; c++) o[c] = (uint8_t)((cur >> (8 * c)) - (left >> (8 * c)));
 }
 
 // Behind k_means: the frame's mean shift, and (rr_tensor_layer.background_out) the image the compositor blended over -- rainy_bg,
@@ -225,5 +293,7 @@ __global__ __launch_bounds__(256) void k_layer_finish(const FrameDesc* frames, c
   o[npix] = (float)in[1];
   o[2 * npix] = (float)in[0];
 }
+
+#endif  // __HIPCC__
 
 #endif  // RR_LAYER_H

@@ -1246,7 +1246,9 @@ static int rr_png_read_gray16_impl(const char* path, uint16_t* out, int32_t H, i
 // strategy: 0 zlib's default (LZ77 + Huffman), 1 Z_RLE (run lengths + Huffman: on filtered image data as small as
 // level 1 of the default strategy or smaller, at half the time), 2 Z_HUFFMAN_ONLY, 3 the library's own run-length +
 // dynamic-Huffman encoder (fast_deflate above; `level` is ignored).
-static int rr_png_write_scanlines_impl(const char* path, const uint8_t* rows, int32_t W, int32_t H, int32_t level, int32_t strategy) {
+// keyword / text (rr_io_write_frames_text): one tEXt chunk, keyword NUL text, between IHDR and IDAT; text == NULL: no chunk.
+static int rr_png_write_scanlines_impl(const char* path, const uint8_t* rows, int32_t W, int32_t H, int32_t level, int32_t strategy,
+                                       const char* keyword = nullptr, const char* text = nullptr) {
   if (!path || !rows || W <= 0 || H <= 0 || level < 0 || level > 9 || strategy < 0 || strategy > 3) return RR_E_ARG;
   const uLong n = (uLong)H * (1 + 4 * (uLong)W);
   std::vector<uint8_t> z;
@@ -1304,7 +1306,15 @@ static int rr_png_write_scanlines_impl(const char* path, const uint8_t* rows, in
   put32(ihdr, (uint32_t)W);
   put32(ihdr + 4, (uint32_t)H);
   ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
-  bool ok = fwrite(sig, 1, 8, fh) == 8 && chunk("IHDR", ihdr, 13) && chunk("IDAT", zdata, (uint32_t)clen) && chunk("IEND", nullptr, 0);
+  bool ok = fwrite(sig, 1, 8, fh) == 8 && chunk("IHDR", ihdr, 13);
+  if (ok && keyword && text) {
+    const size_t nk = strlen(keyword), nt = strlen(text);
+    std::vector<uint8_t> body(nk + 1 + nt);
+    memcpy(body.data(), keyword, nk + 1);
+    memcpy(body.data() + nk + 1, text, nt);
+    ok = chunk("tEXt", body.data(), (uint32_t)body.size());
+  }
+  ok = ok && chunk("IDAT", zdata, (uint32_t)clen) && chunk("IEND", nullptr, 0);
   ok = (fclose(fh) == 0) && ok;
   return ok ? RR_OK : RR_E_ARG;
 }
@@ -1642,6 +1652,36 @@ extern "C" int rr_io_write_frames(int32_t n, const char* const* image_paths, con
     rc2[(size_t)j] = rc;
   });
   for (int k = 0; k < n; k++) status[k] = rc2[2 * (size_t)k] ? rc2[2 * (size_t)k] : rc2[2 * (size_t)k + 1];
+  return RR_OK;
+}
+
+// PNG's keyword rule (section 11.3.4.2): 1 to 79 bytes of printable Latin-1, no leading, trailing or consecutive spaces
+static bool png_keyword_ok(const char* kw) {
+  if (!kw) return false;
+  const size_t n = strlen(kw);
+  if (n < 1 || n > 79 || kw[0] == ' ' || kw[n - 1] == ' ') return false;
+  for (size_t i = 0; i < n; i++) {
+    const unsigned c = (unsigned char)kw[i];
+    if (!((c >= 32 && c <= 126) || c >= 161) || (c == ' ' && kw[i + 1] == ' ')) return false;
+  }
+  return true;
+}
+
+extern "C" int rr_io_write_frames_text(int32_t n, const char* const* paths, const uint8_t* rows, int64_t rows_stride, int32_t W, int32_t H,
+                                       const char* keyword, const char* const* texts, int32_t threads, int32_t* status) {
+  if (n < 0 || H <= 0 || W <= 0 || !status || !paths || !rows || rows_stride < (int64_t)H * (1 + 4 * (int64_t)W)) return RR_E_ARG;
+  if (texts && !png_keyword_ok(keyword)) return RR_E_ARG;
+  rrpar::parallel_for(n, threads, [&](int k) {
+    int rc = RR_OK;
+    if (paths[k]) {
+      try {
+        rc = rr_png_write_scanlines_impl(paths[k], rows + (size_t)k * (size_t)rows_stride, W, H, 1, 3, keyword, texts ? texts[k] : nullptr);
+      } catch (...) {
+        rc = RR_E_PARSE;
+      }
+    }
+    status[k] = rc;
+  });
   return RR_OK;
 }
 

@@ -179,6 +179,10 @@ class rr_pipeline_layer(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('reserved', ctypes.c_int32), ('frames', ctypes.c_void_p)]
 
 
+class rr_pipeline_layer_png(ctypes.Structure):          # rr_pipeline_set_layer_png: the layer FILE's payloads, n host buffers
+    _fields_ = [('n', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('reserved', ctypes.c_int32), ('layer_png', ctypes.c_void_p)]
+
+
 class rr_tensor_layer(ctypes.Structure):                # rr_augment_set_layer: device pointers, planar float32 / float64
     _fields_ = [('layer_out', ctypes.c_void_p), ('background_out', ctypes.c_void_p), ('shift_out', ctypes.c_void_p)]
 
@@ -197,7 +201,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_set_particle_rig', 'rr_sizeof_rig_view', 'rr_set_particle_draws', 'rr_set_particle_jitter', 'rr_set_particle_wind', 'rr_set_particle_gusts', 'rr_set_particle_rate_series', 'rr_set_particle_trajectory',
            'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
            'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device', 'rr_debug_mem', 'rr_pipeline_set_layer',
-           'rr_augment_set_layer', 'rr_sizeof_layer_out', 'rr_sizeof_pipeline_layer', 'rr_sizeof_tensor_layer']
+           'rr_augment_set_layer', 'rr_sizeof_layer_out', 'rr_sizeof_pipeline_layer', 'rr_sizeof_tensor_layer',
+           'rr_pipeline_set_layer_png', 'rr_sizeof_pipeline_layer_png', 'rr_io_write_frames_text']
 
 _lib = None
 
@@ -318,6 +323,11 @@ def load_library(path=None):
     assert lib.rr_sizeof_layer_out() == ctypes.sizeof(rr_layer_out) == 16, (lib.rr_sizeof_layer_out(), ctypes.sizeof(rr_layer_out))
     assert lib.rr_sizeof_pipeline_layer() == ctypes.sizeof(rr_pipeline_layer), (lib.rr_sizeof_pipeline_layer(), ctypes.sizeof(rr_pipeline_layer))
     assert lib.rr_sizeof_tensor_layer() == ctypes.sizeof(rr_tensor_layer), (lib.rr_sizeof_tensor_layer(), ctypes.sizeof(rr_tensor_layer))
+    lib.rr_pipeline_set_layer_png.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(rr_pipeline_layer_png)]
+    assert lib.rr_sizeof_pipeline_layer_png() == ctypes.sizeof(rr_pipeline_layer_png) == 24, (lib.rr_sizeof_pipeline_layer_png(),
+                                                                                            ctypes.sizeof(rr_pipeline_layer_png))
+    lib.rr_io_write_frames_text.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_set_input_resize.argtypes = [ctypes.c_void_p] + [ctypes.c_int32] * 4
     lib.rr_resize_inputs_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -659,6 +669,32 @@ def io_write_frames(image_paths, mask_paths, rows_image_block, rows_mask_block, 
                                 int(threads), _ptr(status))
     if rc != 0:
         raise RuntimeError("rr_io_write_frames failed (%d)" % rc)
+    return status
+
+
+def io_write_frames_text(paths, rows_block, W, H, keyword=None, texts=None, threads=0):
+    """rr_io_write_frames_text: one file per frame from one scanline block ((n, stride) uint8), each with one tEXt chunk
+    keyword / texts[k] between IHDR and IDAT (the layer files' `rain-shift`).  texts None: no chunk, the files of io_write_frames.
+    keyword and texts are str (Latin-1) or bytes; a path may be None (skipped).  Per-frame status; ValueError for a keyword PNG refuses."""
+    lib = load_library()
+    n = len(paths)
+    pp, k1 = _c_paths(paths)
+    enc = lambda t: t if isinstance(t, bytes) else str(t).encode('latin-1')
+    tp, kw = None, None
+    if texts is not None:
+        if len(texts) != n:
+            raise ValueError("%d texts for %d paths" % (len(texts), n))
+        kw = enc(keyword if keyword is not None else '')
+        raw = [None if t is None else enc(t) for t in texts]
+        if any(t is not None and b'\0' in t for t in raw):
+            raise ValueError("a tEXt string holds no NUL byte")
+        tp = (ctypes.c_char_p * max(n, 1))(*raw)
+    status = np.zeros(n, np.int32)
+    rc = lib.rr_io_write_frames_text(n, pp, _ptr(rows_block), int(rows_block.strides[0]), int(W), int(H), kw, tp, int(threads), _ptr(status))
+    if rc == -1 and texts is not None:
+        raise ValueError("rr_io_write_frames_text: keyword %r is not a PNG keyword (1 to 79 printable Latin-1 bytes)" % (keyword,))
+    if rc != 0:
+        raise RuntimeError("rr_io_write_frames_text failed (%d)" % rc)
     return status
 
 
@@ -1310,6 +1346,28 @@ class RainHip:
         if not hasattr(self, '_layer_keep'):
             self._layer_keep = {}
         self._layer_keep[int(slot)] = outs               # (the library copied the table, not the arrays)
+
+    def pipeline_set_layer_png(self, slot, bufs, H=0, W=0):
+        """rr_pipeline_set_layer_png: arm pipeline slot `slot` so that every batch submitted on it also leaves each frame's
+        rain layer as the payload of a straight-alpha RGBA PNG (tools/layer_png.py encode; scanlines, or under RR_OPT_PNG_DEFLATE the
+        RRZ1 stream), or disarm it with bufs=None.  bufs: one entry per frame of the batches to come, each None or a C-contiguous
+        uint8 array of H * (1 + 4 W) bytes (ideally from host_array), filled by pipeline_wait; they must stay alive until then.
+        Independent of pipeline_set_layer: a slot may carry both, either or neither."""
+        if bufs is None:
+            self._check(self.lib.rr_pipeline_set_layer_png(self.h, int(slot), None), 'rr_pipeline_set_layer_png')
+            getattr(self, '_layer_png_keep', {}).pop(int(slot), None)
+            return
+        n = len(bufs)
+        for a in bufs:
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags['C_CONTIGUOUS'] and a.size == int(H) * (1 + 4 * int(W))):
+                raise ValueError("a layer_png buffer is a C-contiguous uint8 array of H * (1 + 4 W) bytes")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in bufs])
+        b = rr_pipeline_layer_png()
+        b.n, b.H, b.W, b.layer_png = n, int(H), int(W), ctypes.cast(ptrs, ctypes.c_void_p)
+        self._check(self.lib.rr_pipeline_set_layer_png(self.h, int(slot), ctypes.byref(b)), 'rr_pipeline_set_layer_png')
+        if not hasattr(self, '_layer_png_keep'):
+            self._layer_png_keep = {}
+        self._layer_png_keep[int(slot)] = bufs           # (the library copied the pointers, not the arrays)
 
     @contextlib.contextmanager
     def _layer_armed(self, outs, want):

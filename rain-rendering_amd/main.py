@@ -107,6 +107,10 @@ _FLAGS = [
                                   "--rig_view's own lens).  The rain mask does not show them")),
     (('--lens_alpha',), dict(action='store_true', help="with --lens_drops: also write <out_dir>/lens_alpha/<name>.png, the per-pixel "
                                                        "coverage of the drops on the lens as a grey level (0: no drop, 255: all drop)")),
+    (('--rain_layer',), dict(action='store_true', help="also write <out_dir>/rain_layer/<name>.png: the frame's streaks alone as a "
+                                                       "straight-alpha RGBA PNG (colour L over transparency, alpha 1 - T; any viewer shows "
+                                                       "it), the frame's mean shift in its tEXt chunk `rain-shift`; "
+                                                       "common.imgops.read_rain_layer reads it back.  rainy = T x fogged background + L - shift")),
     (('--device_resize',), dict(action='store_true',
                                help="resize full-size frames on the GPU: where a dataset renders at a fraction of its files' resolution "
                                     "(render_scale / depth_scale other than 1) the batch-native route uploads the files' own scanlines and the "
