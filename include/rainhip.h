@@ -138,7 +138,7 @@ typedef struct {
   const struct rr_sim_frame* sim;
 } rr_frame_in;
 
-enum { RR_IN_BG_F32 = 1, RR_IN_BG_U8 = 2, RR_IN_ENV_F32 = 4, RR_IN_RAINY_F32 = 8, RR_IN_RAINY_U8 = 16, RR_IN_BG_PNG_ROWS = 32 };
+enum { RR_IN_BG_F32 = 1, RR_IN_BG_U8 = 2, RR_IN_ENV_F32 = 4, RR_IN_RAINY_F32 = 8, RR_IN_RAINY_U8 = 16, RR_IN_BG_PNG_ROWS = 32, RR_IN_BG_JPEG = 64 };
 
 typedef struct {
   uint8_t* rainy_rgb;             /* H*W*3 RGB: what plt.imsave(rainy_image) stores (generator.py:461-466), alpha omitted */
@@ -252,7 +252,8 @@ typedef struct {
                                    * rr_pipeline_* / rr_prepass_frames (host pointers) also take RR_IN_BG_PNG_ROWS: `bg` holds the H rows of
                                    * 1 + 3*W bytes an 8-bit RGB PNG's IDAT stream inflates to (filter type + filtered R G B bytes, as
                                    * rr_io_read_frames_rows delivers them), and depth_f64 = RR_DEPTH_PNG_ROWS: `depth` holds the H rows of
-                                   * 1 + 2*W bytes of the 16-bit gray depth file; the filters are reversed on the device */
+                                   * 1 + 2*W bytes of the 16-bit gray depth file; the filters are reversed on the device.  And RR_IN_BG_JPEG:
+                                   * `bg` holds a baseline JPEG's coefficient record (rr_io_read_frames_jpeg; see "Baseline JPEG input frames" below) */
   int32_t reserved;
 } rr_prepass_in;
 
@@ -1062,6 +1063,47 @@ int rr_io_write_frames_text(int32_t n, const char* const* paths, const uint8_t* 
  * computed with SSSE3 / carry-less multiplication where the CPU has them (zlib's own loops otherwise). */
 uint32_t rr_adler32(uint32_t adler, const uint8_t* p, int64_t n);
 uint32_t rr_crc32(uint32_t crc, const uint8_t* p, int64_t n);
+
+/* Baseline JPEG input frames (csrc/rr_jpeg.h): the host parses the file and decodes its Huffman stream, the
+ * device dequantises, runs the 8x8 inverse DCT, upsamples chroma and converts to B G R (k_jpeg_idct, k_jpeg_bgr).  Between the
+ * two travels a frame's COEFFICIENT RECORD: an rr_jpeg_header, then int16 coefficients -- not dequantised, in natural
+ * (de-zigzagged) order, 64 per block, a component's blocks in raster order over its plane padded to whole MCUs, Y then Cb then Cr.
+ * Taken: SOF0, 8-bit samples, 8-bit tables, ONE interleaved scan of three components in 4:4:4, 4:2:2 (2x1,1x1,1x1) or 4:2:0
+ * (2x2,1x1,1x1) -- W >= 3 where chroma is subsampled horizontally -- or of one component; restart intervals.  Anything else
+ * (progressive, extended, arithmetic coding, 12 bits, other samplings, four components, several scans, 16-bit tables) is
+ * RR_E_UNSUPPORTED; truncated or inconsistent data RR_E_PARSE; an unreadable path or a size that is not the expected one
+ * RR_E_ARG.  rr_jpeg_last_error() gives the calling thread's last refusal in a line ("" after a success).
+ *   rr_jpeg_info          0 only for a file the reader takes; components 1 / 3, sampling an RR_JPEG_* code
+ *   rr_jpeg_record_bytes  a record's size for that frame size and sampling (< 0: bad arguments)
+ *   rr_jpeg_read_record   the record of `path` into dst (dst_bytes >= rr_jpeg_record_bytes of the file)
+ *   rr_jpeg_read_bgr8     the whole decode on the host through the same arithmetic: H*W*3 bytes, B G R -- byte for byte what
+ *                         the device makes of the record
+ *   rr_io_read_frames_jpeg  the batch form (see rr_io_read_frames_rows): frame k's record into records + k * record_stride,
+ *                         its 16-bit gray depth PNG as H rows of 1 + 2*W filtered bytes into depth_rows + k * depth_stride
+ *                         (RR_DEPTH_PNG_ROWS); status[k] as in the other batch readers
+ * rr_prepass_in.in_types = RR_IN_BG_JPEG (host-pointer entry points only: rr_pipeline_submit / rr_pipeline_frames /
+ * rr_prepass_frames): `bg` points at the frame's record.  For every frame of a batch or for none, not with bg_u8 or
+ * RR_PRE_ENV_ONLY, not while rr_set_input_resize is armed; every record's W, H the batch's and its sampling the first frame's
+ * (RR_E_ARG with nothing enqueued otherwise).  depth_f64 may be any kind. */
+#define RR_JPEG_MAGIC 0x314a5252u /* "RRJ1" */
+enum { RR_JPEG_444 = 0, RR_JPEG_422 = 1, RR_JPEG_420 = 2, RR_JPEG_GREY = 3 };
+typedef struct {
+  uint32_t magic;                 /* RR_JPEG_MAGIC */
+  int32_t W, H;
+  int32_t sampling;               /* RR_JPEG_* */
+  int32_t components;             /* 1 or 3 */
+  int32_t reserved[3];            /* 0 */
+  uint16_t q[3][64];              /* quantisation table of component c, natural order (unused components: 0) */
+} rr_jpeg_header;                 /* 416 bytes */
+int rr_jpeg_info(const char* path, int32_t* W, int32_t* H, int32_t* components, int32_t* sampling);
+int64_t rr_jpeg_record_bytes(int32_t W, int32_t H, int32_t sampling);
+int rr_jpeg_read_record(const char* path, void* dst, int64_t dst_bytes);
+int rr_jpeg_read_bgr8(const char* path, uint8_t* dst, int32_t H, int32_t W);
+int rr_io_read_frames_jpeg(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
+                           uint8_t* records, int64_t record_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
+                           int32_t* status);
+const char* rr_jpeg_last_error(void);
+int rr_sizeof_jpeg_header(void);
 
 /* sizes, for binding self-checks */
 int rr_sizeof_drop(void);

@@ -270,12 +270,13 @@ class Generator:
         the library then moves an array of the whole batch with ONE copy instead of one DMA request per frame."""
 
         def __init__(self, hip, B, H, W, We, bg_dtype, depth_dtype, save_envmap, drops_cap, png_rows=False, lens_alpha=False, resize=None,
-                     rain_layer=False):
+                     rain_layer=False, jpeg_bytes=0):
             """png_rows: the image / depth blocks hold the files' filtered scanlines (rr_io_read_frames_rows: H rows of 1 + 3 W /
             1 + 2 W bytes per frame) instead of pixels.  lens_alpha: a third scanline block, the label file of --lens_alpha.
             resize = (sh, sw, dh, dw), with png_rows: the scanlines are those of sh x sw images and dh x dw depth files (the library
             resizes them to H x W: --device_resize); the output blocks keep H x W.  rain_layer: one more scanline block, the layer file
-            of --rain_layer, and the B doubles that receive the frames' mean shifts."""
+            of --rain_layer, and the B doubles that receive the frames' mean shifts.  jpeg_bytes (with png_rows): the image block holds
+            the frames' JPEG coefficient records of that many bytes each (rr_io_read_frames_jpeg), the depth block scanlines as before."""
             self.B, self.H, self.W = B, H, W
             sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
             self._raw = []
@@ -285,7 +286,7 @@ class Generator:
                 self._raw.append(raw)
                 return views
             drops_cap = (drops_cap + 3) // 4 * 4
-            self.bg = rows((sh * (1 + 3 * sw),), np.uint8) if png_rows else rows((H, W, 3), bg_dtype)
+            self.bg = rows((jpeg_bytes,), np.uint8) if jpeg_bytes else rows((sh * (1 + 3 * sw),), np.uint8) if png_rows else rows((H, W, 3), bg_dtype)
             self.depth = rows((dh * (1 + 2 * dw),), np.uint8) if png_rows else rows((H, W), depth_dtype)
             self.drops = rows((drops_cap,), hip_backend.DROP_DTYPE)
             self.status = rows((drops_cap,), np.int32)
@@ -306,6 +307,8 @@ class Generator:
             self.key = (B, H, W, We, 'png rows' if png_rows else np.dtype(bg_dtype), 'png rows' if png_rows else np.dtype(depth_dtype), bool(save_envmap))
             if resize is not None:
                 self.key += (tuple(resize),)
+            if jpeg_bytes:
+                self.key += ('jpeg', int(jpeg_bytes))
             self.items, self.encodes, self.busy = [], [], False
             self.prep, self.pkey, self.n_valid = None, None, 0
 
@@ -430,14 +433,15 @@ class Generator:
             assert os.path.exists(image_file), "Image file {} does not exist".format(image_file)
             assert os.path.exists(depth_file), "Depth file {} does not exist".format(depth_file)
             file_name = os.path.split(image_file)[-1]
+            stem = os.path.splitext(file_name)[0]                # (.png / .jpg lose four characters as ever, .jpeg its whole suffix)
             item = dict(i=i, image_file=image_file, depth_file=depth_file,
-                        out_rainy_path=os.path.join(out_dir, 'rainy_image', '{}.png'.format(file_name[:-4])),
-                        out_rainy_mask_path=os.path.join(out_dir, 'rain_mask', '{}.png'.format(file_name[:-4])),
-                        out_env_path=os.path.join(out_seq_dir, 'envmap', '{}.png'.format(file_name[:-4])))
+                        out_rainy_path=os.path.join(out_dir, 'rainy_image', '{}.png'.format(stem)),
+                        out_rainy_mask_path=os.path.join(out_dir, 'rain_mask', '{}.png'.format(stem)),
+                        out_env_path=os.path.join(out_seq_dir, 'envmap', '{}.png'.format(stem)))
             if self.lens_alpha:                                  # (the skip rule below stays the reference's: rainy or mask file)
-                item['out_lens_alpha_path'] = os.path.join(out_dir, 'lens_alpha', '{}.png'.format(file_name[:-4]))
+                item['out_lens_alpha_path'] = os.path.join(out_dir, 'lens_alpha', '{}.png'.format(stem))
             if self.rain_layer:
-                item['out_rain_layer_path'] = os.path.join(out_dir, 'rain_layer', '{}.png'.format(file_name[:-4]))
+                item['out_rain_layer_path'] = os.path.join(out_dir, 'rain_layer', '{}.png'.format(stem))
             if os.path.exists(item['out_rainy_path']) or os.path.exists(item['out_rainy_mask_path']):
                 if self.conflict_strategy == "skip":
                     frames_exist_nb += 1
@@ -527,7 +531,7 @@ class Generator:
                          if os.path.isfile(os.path.join(self.images[sequence], p))]
                 depth_files = [os.path.join(depth_folder, d) for d in my_utils.os_listdir(depth_folder)]
                 im = files[0]
-                if im.endswith(".png"):
+                if im.endswith(".png") or im.lower().endswith((".jpg", ".jpeg")):
                     imH, imW = imgops.imread_bgr(im).shape[0:2]
                 elif im.endswith(".npy"):
                     imH, imW = np.load(im).shape[0:2]
@@ -643,7 +647,7 @@ class Generator:
             self._shower_fog[rate] = tuple(float(v) for v in add_attenuation.FogRain(**dict(self._shower_fog_params, rain_intensity=rate)).constants())
         return self._shower_fog[rate]
 
-    def _cap_batch(self, B, imH, imW, frame_render_dict, sims, resize=None):
+    def _cap_batch(self, B, imH, imW, frame_render_dict, sims, resize=None, jpeg_bytes=0):
         """Frames per library call, bounded by the page-locked memory a rank may hold: three slots of B frames, each frame
         its input bytes (image, float32 depth), both PNG scanline blocks and the drop / status tables -- about 15 bytes per
         pixel + 116 per drop: 7.9 MB at KITTI size (3 GB for 3 x 128 frames), 32 MB at Cityscapes full size.  Budget:
@@ -659,6 +663,8 @@ class Generator:
         if resize is not None:                       # --device_resize: the inputs are the files' scanlines at their own sizes
             sh, sw, dh, dw = resize
             per_frame += sh * (1 + 3 * sw) + dh * (1 + 2 * dw) - imH * imW * 7
+        if jpeg_bytes:                               # JPEG frames: a coefficient record and the depth file's scanlines
+            per_frame += jpeg_bytes + imH * (1 + 2 * imW) - imH * imW * 7
         return max(1, min(B, int(budget // (hip_backend.RR_PIPE_SLOTS * per_frame))))
 
     def _run_batches(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None):
@@ -668,13 +674,27 @@ class Generator:
         the batch-native route (one library call per batch and stage, nothing per frame under the interpreter lock);
         everything else the general one (per-frame Python on an I/O thread pool)."""
         ds = self.settings["depth_scale"]
-        B0, resize = B, None
+        B0, resize, jpeg = B, None, None
         B = self._cap_batch(B, imH, imW, frame_render_dict, sims)
         native = (work and int(rs) == rs and rs >= 1 and int(ds) == ds and ds >= 1 and
                   (sims is not None or not (bool(self.noise_std) and bool(self.noise_scale))) and not self.save_envmap and
-                  os.environ.get('RAIN_NATIVE_IO', '1') != '0' and
-                  all(it['image_file'].endswith('.png') and it['depth_file'].endswith('.png') for it in work))
-        if native:
+                  os.environ.get('RAIN_NATIVE_IO', '1') != '0')
+        # baseline JPEG frames (any letter case of .jpg / .jpeg) with PNG depth maps, at render scale 1: the library's reader decodes the
+        # Huffman streams, the device does the rest (DESIGN.md 5s).  The first frame decides, as for PNG.
+        jpeg_tree = bool(native and all(it['image_file'].lower().endswith(('.jpg', '.jpeg')) and it['depth_file'].endswith('.png') for it in work))
+        why_not = None
+        native = native and (jpeg_tree or all(it['image_file'].endswith('.png') and it['depth_file'].endswith('.png') for it in work))
+        if native and jpeg_tree:
+            j0, d0 = hip_backend.jpeg_info(work[0]['image_file']), imgops._native_png(work[0]['depth_file'])
+            if j0[0] != 0:
+                why_not = "%s: %s" % (work[0]['image_file'], j0[1])
+            elif not (rs == 1 and (j0[1], j0[2]) == (imW, imH) and d0 is not None and tuple(d0[3:5]) == (1, 16) and (d0[1], d0[2]) == (imW, imH) and ds == 1):
+                why_not = "%s: JPEG frames take the batch-native route at render scale 1 with 16-bit PNG depth maps of the frame's size" % work[0]['image_file']
+            native = why_not is None
+            if native:
+                jpeg = (int(j0[1]), int(j0[2]), int(j0[4]))
+                B = self._cap_batch(B0, imH, imW, frame_render_dict, sims, jpeg_bytes=hip_backend.jpeg_record_bytes(*jpeg))
+        elif native:
             # the first frame decides: files the library's readers take, whose scaled sizes are the run's frame size
             # (generator.py:355-381; a depth map of another size would make the reference crop the image: general route)
             i0, d0 = imgops._native_png(work[0]['image_file']), imgops._native_png(work[0]['depth_file'])
@@ -687,13 +707,14 @@ class Generator:
                 B = self._cap_batch(B0, imH, imW, frame_render_dict, sims, resize)
         if sims is not None:
             if work and not native:
-                raise NotImplementedError("--device_particles needs the batch-native route: PNG frames and depth maps of matching "
-                                          "scaled sizes, no environment-map files (RAIN_NATIVE_IO not 0)")
+                raise NotImplementedError("--device_particles needs the batch-native route: PNG or baseline JPEG frames and PNG depth maps of "
+                                          "matching scaled sizes, no environment-map files (RAIN_NATIVE_IO not 0)" +
+                                          ("" if why_not is None else " -- " + why_not))
             return self._run_batches_native(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num,
-                                            sim_t0, sims, resize=resize)
+                                            sim_t0, sims, resize=resize, jpeg=jpeg)
         if native:
             return self._run_batches_native(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num,
-                                            sim_t0, resize=resize)
+                                            sim_t0, resize=resize, jpeg=jpeg)
         return self._run_batches_general(hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0)
 
     @staticmethod
@@ -707,7 +728,7 @@ class Generator:
         hip.set_option(hip_backend.RR_OPT_PNG_DEFLATE, 0 if os.environ.get('RAIN_PNG_DEVICE', '1') == '0' else 1)
 
     def _run_batches_native(self, hip, work, B, rs, imW, imH, frame_render_dict, fog_const, map_generator, folder_idx, folders_num, sim_t0, sims=None,
-                            resize=None):
+                            resize=None, jpeg=None):
         """Batch-native route.  Per batch, three whole-batch jobs, each one call (or two) into the library:
           decode  rr_io_read_frames (image bytes + depth metres straight into the slot's page-locked input blocks) and
                   rr_host_pack_frames (filter, draws, drop records into the slot's drop block) -- one batch ahead of the GPU;
@@ -715,6 +736,8 @@ class Generator:
           encode  rr_io_write_frames (both files of every frame from the slot's scanline blocks) -- one batch behind.
         resize = (sh, sw, dh, dw) (--device_resize): decode is rr_io_read_frames_rows at the files' own sizes, and the library, armed
         with rr_set_input_resize, makes the H x W frames of them on the device; everything behind the inputs is unchanged.
+        jpeg = (W, H, sampling) (baseline JPEG frames, render scale 1): decode is rr_io_read_frames_jpeg -- the image comes as its
+        coefficient record (RR_IN_BG_JPEG: inverse DCT, upsampling and colour on the device), the depth file as scanlines.
         A slot's INPUT blocks are free again when its batch has been collected (the encoders only read the output
         blocks), so batch b+1 is decoded into slot (b+1) % 3 while batch b renders and batch b-1 is written."""
         stage = self._stage_pool()
@@ -753,10 +776,13 @@ class Generator:
         depth_dtype = np.uint16 if d16 else np.float32
         # ... and both files as the filtered scanlines their IDAT streams inflate to (rr_io_read_frames_rows): the scanline filters
         # are reversed on the device (k_png_unfilter), 40 % of the host's decode time.  RAIN_PNG_ROWS=0: pixels decoded by the host.
-        rows_in = resize is not None or (u8 and os.environ.get('RAIN_PNG_ROWS', '1') != '0')
+        rows_in = resize is not None or jpeg is not None or (u8 and os.environ.get('RAIN_PNG_ROWS', '1') != '0')
+        jpeg_bytes = hip_backend.jpeg_record_bytes(*jpeg) if jpeg is not None else 0
         key = (B, H, W, env_w, 'png rows' if rows_in else np.dtype(bg_dtype), 'png rows' if rows_in else np.dtype(depth_dtype), False)
         if resize is not None:
             key += (tuple(resize),)
+        if jpeg is not None:
+            key += ('jpeg', jpeg_bytes)
         sh, sw, dh, dw = resize if resize is not None else (H, W, H, W)
         lens_alpha = self._lens is not None and self.lens_alpha
         rain_layer = self.rain_layer
@@ -771,7 +797,7 @@ class Generator:
 
         def new_slot():
             return Generator._Slot(hip, B, H, W, env_w, bg_dtype, depth_dtype, False, drops_cap, png_rows=rows_in, lens_alpha=lens_alpha, resize=resize,
-                                   rain_layer=rain_layer)
+                                   rain_layer=rain_layer, jpeg_bytes=jpeg_bytes)
 
         def slot_for(si):
             if si in pending:
@@ -784,6 +810,7 @@ class Generator:
             if getattr(sl, 'prep', None) is None or sl.pkey != pkey:
                 inputs = ((lambda k: dict(bg_png_rows=sl.bg[k], shape=(sh, sw), depth_png_rows=sl.depth[k], depth_shape=(dh, dw), render_shape=(H, W)))
                           if resize is not None else
+                          (lambda k: dict(bg_jpeg=sl.bg[k], shape=(H, W), depth_png_rows=sl.depth[k])) if jpeg is not None else
                           (lambda k: dict(bg_png_rows=sl.bg[k], shape=(H, W), depth_png_rows=sl.depth[k])) if rows_in else
                           (lambda k: dict(bg=None if u8 else sl.bg[k], bg_u8=sl.bg[k] if u8 else None, depth=sl.depth[k])))
                 frames = [dict(inputs(k), fog=fog_const, omega=None, drops=sl.drops[k],
@@ -805,6 +832,12 @@ class Generator:
             if resize is not None:
                 st = hip_backend.io_read_frames_rows([it['image_file'] for it in items], [it['depth_file'] for it in items], sh, sw,
                                                      sl.raw_bg, sl.raw_depth, threads, depth_shape=(dh, dw))
+            elif jpeg is not None:
+                st = hip_backend.io_read_frames_jpeg([it['image_file'] for it in items], [it['depth_file'] for it in items], H, W,
+                                                     sl.raw_bg, sl.raw_depth, threads)
+                for k in range(len(items)):                      # a batch is of ONE sampling (the library refuses any other): the run's
+                    if st[k] == 0 and int(sl.bg[k][12:16].view(np.int32)[0]) != jpeg[2]:
+                        st[k] = -1
             elif rows_in:
                 st = hip_backend.io_read_frames_rows([it['image_file'] for it in items], [it['depth_file'] for it in items], H, W,
                                                      sl.raw_bg, sl.raw_depth, threads)
@@ -822,6 +855,23 @@ class Generator:
                                                  sl.drops_cap, sl.drops_cap, threads)
             ok = [True] * len(items)
             for k in np.nonzero(st)[0]:                          # not a file the fast readers take: the general loader
+                if jpeg is not None:
+                    # pixels from another decoder cannot be handed over as a record of this batch's kind: the image must be a file the
+                    # reader takes, of the run's size and sampling; the depth map may come through the general loader (as scanlines of
+                    # filter type 0).  Anything else skips the frame, like a missing depth map -- one odd file must not end the run.
+                    try:
+                        rec = hip_backend.jpeg_read_record(items[k]['image_file'])
+                        depth = imgops.imread_unchanged(items[k]['depth_file'])
+                        if rec.size != jpeg_bytes or tuple(int(v) for v in rec[4:16].view(np.int32)) != jpeg:
+                            raise RuntimeError("not a %d x %d frame of the run's chroma sampling" % (W, H))
+                        if depth is None or depth.dtype != np.uint16 or depth.shape != (H, W):
+                            raise RuntimeError("depth map %s is not a 16-bit file of the frame's size" % items[k]['depth_file'])
+                        np.copyto(sl.bg[k], rec)
+                        np.copyto(sl.depth[k], hip_backend.png_rows_of(depth))
+                    except RuntimeError as e:
+                        print("Skipping %s: %s" % (items[k]['image_file'], e))
+                        ok[k] = False
+                    continue
                 if resize is not None:                           # ... 's unscaled bytes and metres: the library resizes them
                     bg = imgops.imread_bgr(items[k]['image_file'])
                     depth = imgops.imread_unchanged(items[k]['depth_file'])

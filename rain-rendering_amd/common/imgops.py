@@ -97,9 +97,29 @@ def _native_png(path):
     return lib, w.value, h.value, c.value, d.value
 
 
+def _native_jpeg(path):
+    """(lib, W, H, components, sampling) when the library's baseline-JPEG reader takes the file (rr_jpeg_info), else None."""
+    import ctypes
+    from .. import hip_backend
+    if not str(path).lower().endswith(('.jpg', '.jpeg')):
+        return None
+    lib = hip_backend.load_library()
+    w, h, c, s = (ctypes.c_int32() for _ in range(4))
+    if lib.rr_jpeg_info(os.fsencode(path), ctypes.byref(w), ctypes.byref(h), ctypes.byref(c), ctypes.byref(s)) != 0:
+        return None
+    return lib, w.value, h.value, c.value, s.value
+
+
 def imread_bgr(path, out=None):
-    """cv2.imread(path): 8-bit, 3 channels, BGR order.  PNGs go through the library's reader (rr_png_read_bgr8: no
-    interpreter lock, straight into `out` when given); anything it does not take through PIL."""
+    """cv2.imread(path): 8-bit, 3 channels, BGR order.  PNGs and baseline JPEGs go through the library's readers (rr_png_read_bgr8 /
+    rr_jpeg_read_bgr8: no interpreter lock, straight into `out` when given); anything they do not take through PIL."""
+    jinfo = _native_jpeg(path)                         # (the markers up to the scan, for the size; the decode below reads the file once)
+    if jinfo is not None:
+        lib, w, h = jinfo[:3]
+        dst = out if out is not None else np.empty((h, w, 3), np.uint8)
+        if dst.shape == (h, w, 3) and dst.dtype == np.uint8 and dst.flags['C_CONTIGUOUS']:
+            if lib.rr_jpeg_read_bgr8(os.fsencode(path), dst.ctypes.data, h, w) == 0:
+                return dst
     info = _native_png(path)
     if info is not None and info[4] == 8:
         lib, w, h = info[:3]

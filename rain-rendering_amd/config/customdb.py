@@ -1,5 +1,5 @@
 """Template plug-in for a custom dataset (interface of reference config/customdb.py):
-<root>/<sequence>/rgb/*.png with depth in <root>/<sequence>/depth/."""
+<root>/<sequence>/rgb/*.png|*.jpg with depth in <root>/<sequence>/depth/."""
 import os
 
 import numpy as np

@@ -3,7 +3,7 @@
 The reference resolves its file lists through the nuScenes devkit (config/nuscenes/nusc_dataset.py: scene tokens ->
 CAM_FRONT sample paths) and leaves the sensor size to a preset compiled into its particle simulator ("system code 100",
 tools/simulation.py:308-321).  Neither exists here: this plug-in takes the plain folder layout of the custom-database
-template (<root>/<scene>/rgb/*.png, <root>/<scene>/depth/*.npy|*.png) and states the CAM_FRONT sensor, 1600 x 900,
+template (<root>/<scene>/rgb/*.png|*.jpg, <root>/<scene>/depth/*.npy|*.png) and states the CAM_FRONT sensor, 1600 x 900,
 explicitly -- what the particle generator (tools/particles.py, csrc/rr_particles.h) simulates on.  The frame index a
 nuScenes file maps to is the reference's (generator.py:304-312: the simulated frames spread over the scene's files)."""
 import os

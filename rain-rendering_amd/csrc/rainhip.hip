@@ -34,7 +34,7 @@
 //                      mean-contrast shift, clip, truncating u8 quantisation; optional drops on the lens (a pipeline slot armed with
 //                      rr_pipeline_set_lens); optional PNG scanlines / zlib streams
 //   elsewhere: k_particles / k_field_particles / k_particle_draws (drop tables born on the device), k_png_unfilter (input files' scanlines),
-//   k_pad_textures, k_pair_textures, k_copy_pieces / k_copy_small (batched copies, descriptors)
+//   k_jpeg_idct / k_jpeg_bgr (JPEG input frames: coefficient records -> B G R bytes, rr_jpeg.h), k_pad_textures, k_pair_textures, k_copy_pieces / k_copy_small (batched copies, descriptors)
 // rr_prepass.h holds the fog / environment-map pre-pass kernels, rr_host.cpp the host-only helpers.
 #include <hip/hip_runtime.h>
 
@@ -56,6 +56,7 @@
 #include "rr_prepass.h"
 #include "rr_deflate.h"
 #include "rr_pngrows.h"
+#include "rr_jpeg.h"
 #include "rr_particles.h"
 #include "rr_lens.h"
 #include "rr_resize.h"
@@ -4465,6 +4466,84 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t* rows_base, i
   }
 }
 
+// A baseline JPEG frame's coefficient record (rr_jpeg.h; the host decoded its Huffman stream) -> its component planes of bytes at their
+// padded sizes.  A wave takes eight blocks: lane 8 b + r loads row r of block b (16 bytes of coefficients, 16 of the component's table),
+// dequantises into a wave-private LDS tile (rows 9 words apart: neither pass meets a bank twice), runs the column pass on column r, the
+// row pass on row r, and stores its eight bytes at once.  grid (blocks / 8, frames).
+__global__ __launch_bounds__(64) void k_jpeg_idct(const uint8_t* rec_base, int64_t rec_stride, uint8_t* planes_base, int64_t planes_stride,
+                                                  rrjpeg::Geom g) {
+  __shared__ uint32_t ws[8][72];
+  const int lane = threadIdx.x, b = lane >> 3, r = lane & 7;
+  const int64_t blk = (int64_t)blockIdx.x * 8 + b;
+  const bool valid = blk < g.nblocks;
+  const uint8_t* rec = rec_base + (int64_t)blockIdx.y * rec_stride;
+  const int comp = blk >= g.blk0[2] ? 2 : (blk >= g.blk0[1] ? 1 : 0);
+  if (valid) {
+    const uint4 cv = *reinterpret_cast<const uint4*>(rec + sizeof(rr_jpeg_header) + blk * 128 + r * 16);
+    const uint4 qv = *reinterpret_cast<const uint4*>(rec + offsetof(rr_jpeg_header, q) + comp * 128 + r * 16);
+    const uint32_t c4[4] = {cv.x, cv.y, cv.z, cv.w}, q4[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      ws[b][r * 9 + 2 * k] = rrjpeg::dequant((int16_t)(c4[k] & 0xffffu), (uint16_t)(q4[k] & 0xffffu));
+      ws[b][r * 9 + 2 * k + 1] = rrjpeg::dequant((int16_t)(c4[k] >> 16), (uint16_t)(q4[k] >> 16));
+    }
+  }
+  __syncthreads();
+  uint32_t in[8], o[8];
+  if (valid) {                                          // column r of block b
+#pragma unroll
+    for (int y = 0; y < 8; y++) in[y] = ws[b][y * 9 + r];
+    rrjpeg::idct_1d(in, o);
+#pragma unroll
+    for (int y = 0; y < 8; y++) ws[b][y * 9 + r] = rrjpeg::idct_col_out(o[y]);
+  }
+  __syncthreads();
+  if (valid) {                                          // row r of block b
+#pragma unroll
+    for (int x = 0; x < 8; x++) in[x] = ws[b][r * 9 + x];
+    rrjpeg::idct_1d(in, o);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int x = 0; x < 4; x++) {
+      lo |= (uint32_t)rrjpeg::idct_row_out(o[x]) << (8 * x);
+      hi |= (uint32_t)rrjpeg::idct_row_out(o[4 + x]) << (8 * x);
+    }
+    const int64_t j = blk - g.blk0[comp];
+    const int bw = g.pw[comp] >> 3;
+    const int64_t by = j / bw, bx = j - by * bw;
+    uint8_t* pl = planes_base + (int64_t)blockIdx.y * planes_stride + g.blk0[comp] * 64;
+    *reinterpret_cast<uint2*>(pl + (by * 8 + r) * g.pw[comp] + bx * 8) = make_uint2(lo, hi);
+  }
+}
+
+// The component planes -> the frame's interleaved B G R bytes, where k_png_unfilter<3> leaves a PNG's: chroma upsampled as the
+// sampling says (rr_jpeg.h: jpeg_up_h2v1 / jpeg_up_h2v2), then YCbCr -> B G R.  A thread takes four pixels of a row and stores their
+// twelve bytes as three words where they lie on a 4-byte boundary (bytes at a row's end and in rows that start off one: 3 W is not
+// always a multiple of 4); grid (quads of a row / 64, rows, frames): no division.
+__global__ __launch_bounds__(64) void k_jpeg_bgr(const uint8_t* planes_base, int64_t planes_stride, uint8_t* out_base, int64_t out_stride,
+                                                 rrjpeg::Geom g, int sampling, int W) {
+  const int x0 = 4 * (int)(blockIdx.x * 64 + threadIdx.x), y = (int)blockIdx.y;
+  if (x0 >= W) return;
+  const int m = W - x0 < 4 ? W - x0 : 4;
+  const uint8_t* planes = planes_base + (int64_t)blockIdx.z * planes_stride;
+  uint8_t px[12];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    px[3 * k] = px[3 * k + 1] = px[3 * k + 2] = 0;
+    if (k < m) rrjpeg::pixel_bgr(planes, g, sampling, x0 + k, y, px + 3 * k);
+  }
+  uint8_t* o = out_base + (int64_t)blockIdx.z * out_stride + ((int64_t)y * W + x0) * 3;
+  if (m == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+#pragma unroll
+    for (int w = 0; w < 3; w++)
+      reinterpret_cast<uint32_t*>(o)[w] = (uint32_t)px[4 * w] | ((uint32_t)px[4 * w + 1] << 8) | ((uint32_t)px[4 * w + 2] << 16) | ((uint32_t)px[4 * w + 3] << 24);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 12; b++)
+      if (b < 3 * m) o[b] = px[b];
+  }
+}
+
 // The render-scale resize of the inputs (rr_set_input_resize; the arithmetic is csrc/rr_resize.h): full-size frames in,
 // the float64 B G R image / the float32 depth map of the render size out -- what the pre-pass and the hot path read as in_types = 0.
 //   k_resize_in<KIND>     RSZ_BGR8: the un-filtered file, interleaved B G R bytes; RSZ_RGB8P / RSZ_RGBF32P: a planar R G B tensor;
@@ -5872,6 +5951,9 @@ struct rr_ctx {
     // rr_set_input_resize: the batch's source-size inputs (filtered rows, un-filtered bytes, samples), sized by the source and
     // allocated by the first armed batch (grown, never shrunk)
     rrmem::Buf<uint8_t> src;
+    // RR_IN_BG_JPEG: the batch's coefficient records, then the component planes k_jpeg_idct makes of them, allocated
+    // by the first batch of JPEG frames (grown, never shrunk)
+    rrmem::Buf<uint8_t> jpeg;
     // rr_pipeline_set_layer: the caller's per-frame pointers, copied by the arming call, and the device staging of
     // the host entry points -- n layers of 16 H W bytes, then n shifts -- allocated by the first armed batch (grown, never shrunk)
     struct Layer {
@@ -8353,10 +8435,10 @@ int validate_host_batch(rr_ctx* ctx, int n, const rr_prepass_in* pre, const rr_f
         ctx->err = "null pre-pass pointer or zero irradiance denominator";
         return RR_E_ARG;
       }
-      const int bgk = pre[f].in_types & (RR_IN_BG_F32 | RR_IN_BG_U8 | RR_IN_BG_PNG_ROWS);
-      if ((pre[f].in_types & ~(RR_IN_BG_F32 | RR_IN_BG_U8 | RR_IN_BG_PNG_ROWS)) || (bgk & (bgk - 1)) ||
+      const int bgk = pre[f].in_types & (RR_IN_BG_F32 | RR_IN_BG_U8 | RR_IN_BG_PNG_ROWS | RR_IN_BG_JPEG);
+      if ((pre[f].in_types & ~(RR_IN_BG_F32 | RR_IN_BG_U8 | RR_IN_BG_PNG_ROWS | RR_IN_BG_JPEG)) || (bgk & (bgk - 1)) ||
           (pre_out && ((pre_out[f].out_types & ~(RR_OUT_RAINY_F32 | RR_OUT_ENV_F32)) || pre_out[f].out_types != pre_out[0].out_types))) {
-        ctx->err = "pre-pass: in_types is ONE of RR_IN_BG_F32 / RR_IN_BG_U8 / RR_IN_BG_PNG_ROWS (or 0), out_types RR_OUT_* bits, the same for every frame";
+        ctx->err = "pre-pass: in_types is ONE of RR_IN_BG_F32 / RR_IN_BG_U8 / RR_IN_BG_PNG_ROWS / RR_IN_BG_JPEG (or 0), out_types RR_OUT_* bits, the same for every frame";
         return RR_E_ARG;
       }
       // files handed over as filtered scanlines (rr_io_read_frames_rows): for every frame of the batch or for none (one launch
@@ -8366,6 +8448,26 @@ int validate_host_batch(rr_ctx* ctx, int n, const rr_prepass_in* pre, const rr_f
           ((pre[f].in_types & RR_IN_BG_PNG_ROWS) && pre[f].bg_u8) || pre[f].depth_f64 < 0 || pre[f].depth_f64 > RR_DEPTH_PNG_ROWS) {
         ctx->err = "pre-pass: PNG scanlines (RR_IN_BG_PNG_ROWS / RR_DEPTH_PNG_ROWS) for every frame of a batch or for none, not with bg_u8 or RR_PRE_ENV_ONLY";
         return RR_E_ARG;
+      }
+      // a baseline JPEG's coefficient record (rr_io_read_frames_jpeg): the rules of the scanlines, and a record that is what the
+      // batch says it is -- its size the batch's, its sampling the first frame's (one launch of each of the two kernels)
+      if (((pre[f].in_types ^ pre[0].in_types) & RR_IN_BG_JPEG) ||
+          ((pre[f].in_types & RR_IN_BG_JPEG) && (env_only || pre[f].bg_u8 || ctx->rsz.armed))) {
+        ctx->err = "pre-pass: JPEG coefficient records (RR_IN_BG_JPEG) for every frame of a batch or for none, not with bg_u8 or RR_PRE_ENV_ONLY, "
+                   "and not while rr_set_input_resize is armed";
+        return RR_E_ARG;
+      }
+      if (pre[f].in_types & RR_IN_BG_JPEG) {
+        rr_jpeg_header jh, j0;                              // (copied: the caller's buffer promises no alignment)
+        memcpy(&jh, pre[f].bg, sizeof jh);
+        memcpy(&j0, pre[0].bg, sizeof j0);
+        rrjpeg::Geom jg;
+        if (jh.magic != RR_JPEG_MAGIC || jh.W != dm.W || jh.H != dm.H || jh.sampling != j0.sampling || !rrjpeg::geom_of(jh.W, jh.H, jh.sampling, jg) ||
+            jh.components != jg.ncomp) {
+          ctx->err = "pre-pass: frame " + std::to_string(f) + "'s JPEG record is not one of the batch's " + std::to_string(dm.H) + " x " +
+                     std::to_string(dm.W) + " frames in the first frame's sampling";
+          return RR_E_ARG;
+        }
       }
       // rr_set_input_resize: the image arrives as bytes (or as a file's scanlines) and the depth map as float32 or uint16 samples
       // (or scanlines), one kind of depth for the whole batch (one launch of the resize kernel)
@@ -8535,6 +8637,21 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     rs_frame = rs_dep + r16((size_t)R.dH * R.dW * 4);
     if ((rc = reserve(ctx, sl.src, (size_t)n * rs_frame))) return rc;
   }
+  // RR_IN_BG_JPEG: the batch's records, then its component planes, in the slot's own block (a record does not always fit the
+  // fog-layer slot the scanlines wait in: MCU padding and the header exceed 24 bytes per pixel on tiny frames)
+  const bool jpg = pre && (pre[0].in_types & RR_IN_BG_JPEG);
+  rrjpeg::Geom jg{};
+  int jpg_sampling = 0;
+  size_t jpg_rec = 0, jpg_pl = 0;
+  if (jpg) {
+    rr_jpeg_header j0;
+    memcpy(&j0, pre[0].bg, sizeof j0);
+    jpg_sampling = j0.sampling;
+    rrjpeg::geom_of(dm.W, dm.H, jpg_sampling, jg);        // (validated above)
+    jpg_rec = ((size_t)rrjpeg::record_bytes(jg) + 15) & ~(size_t)15;
+    jpg_pl = ((size_t)jg.nblocks * 64 + 15) & ~(size_t)15;
+    if ((rc = reserve(ctx, sl.jpeg, (size_t)n * (jpg_rec + jpg_pl)))) return rc;
+  }
   // ---- upload ----
   for (int f = 0; rsz && f < n; f++) {
     pin[f] = pre[f];
@@ -8562,7 +8679,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     // the image in the caller's element type: bytes stay bytes (bg = bytes / 255.0 is formed where a kernel reads it)
     const void* src = pre[f].bg_u8 ? (const void*)pre[f].bg_u8 : pre[f].bg;
     const bool rows_i = (pre[f].in_types & RR_IN_BG_PNG_ROWS) != 0, rows_d = pre[f].depth_f64 == RR_DEPTH_PNG_ROWS;
-    pin[f].in_types = (pre[f].bg_u8 || rows_i) ? RR_IN_BG_U8 : pre[f].in_types;
+    pin[f].in_types = (pre[f].bg_u8 || rows_i || jpg) ? RR_IN_BG_U8 : pre[f].in_types;
     const size_t bg_el = (pin[f].in_types & RR_IN_BG_U8) ? 1 : ((pin[f].in_types & RR_IN_BG_F32) ? 4 : 8);
     pin[f].bg = bg_el == 1 ? (const void*)(st.bg8 + f * T.px3b) : (const void*)(st.bg + f * T.px3d);
     pin[f].bg_u8 = nullptr;
@@ -8570,6 +8687,7 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     // a file's filtered scanlines (k_png_unfilter makes the image bytes / the depth samples of them before the pre-pass) wait in
     // the frame's fog-layer / composite slots: free until the pre-pass / the compositor write them
     if (rows_i) up.add(st.rainy + f * T.px3d, src, (size_t)dm.H * (1 + 3 * (size_t)dm.W));
+    else if (jpg) up.add(sl.jpeg.p + (size_t)f * jpg_rec, src, (size_t)rrjpeg::record_bytes(jg));
     else up.add(const_cast<void*>(pin[f].bg), src, px * 3 * bg_el);
     const bool env_only = pre[f].mode == RR_PRE_ENV_ONLY;
     if (rows_d) {
@@ -8713,6 +8831,18 @@ int host_submit(rr_ctx* ctx, int slot, int32_t n, const rr_prepass_in* pre, cons
     if (pre[0].depth_f64 == RR_DEPTH_PNG_ROWS)
       hipLaunchKernelGGL(k_png_unfilter<2>, dim3(n), dim3(64), 2 * (size_t)dm.W, s, reinterpret_cast<const uint8_t*>(st.comp), (int64_t)(T.px3d * 8),
                          reinterpret_cast<uint8_t*>(st.depth), (int64_t)depth_stride, dm.H, dm.W);
+  }
+  if (jpg) {                          // records -> component planes -> the B G R bytes the pre-pass reads (st.bg8)
+    uint8_t* const planes = sl.jpeg.p + (size_t)n * jpg_rec;
+    {
+      ProfScope ps(ctx, s, "k_jpeg_idct");
+      hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((jg.nblocks + 7) / 8), n), dim3(64), 0, s, sl.jpeg.p, (int64_t)jpg_rec, planes, (int64_t)jpg_pl, jg);
+    }
+    {
+      ProfScope ps(ctx, s, "k_jpeg_bgr");
+      hipLaunchKernelGGL(k_jpeg_bgr, dim3((unsigned)(((dm.W + 3) / 4 + 63) / 64), dm.H, n), dim3(64), 0, s, planes, (int64_t)jpg_pl, st.bg8,
+                         (int64_t)T.px3b, jg, jpg_sampling, dm.W);
+    }
   }
   if (pre && (rc = enqueue_prepass(ctx, n, pin.data(), pout.data(), s))) return drained(rc);
   if (!sims.empty() && (rc = enqueue_particles(ctx, n, sims.data(), dm.H, dm.W, st.drops, drop_stride, st.ndrops, s))) return drained(rc);

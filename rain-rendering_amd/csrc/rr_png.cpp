@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "rainhip.h"
+#include "rr_jpeg_read.h"
 #include "rr_parallel.h"
 #include "rr_resize.h"
 
@@ -1514,6 +1515,121 @@ extern "C" int rr_io_read_frames_rows_sized(int32_t n, const char* const* image_
                                             int32_t depth_H, int32_t depth_W, uint8_t* image_rows, int64_t image_stride, uint8_t* depth_rows,
                                             int64_t depth_stride, int32_t threads, int32_t* status) {
   return read_frames_rows(n, image_paths, depth_paths, H, W, depth_H, depth_W, image_rows, image_stride, depth_rows, depth_stride, threads, status);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Baseline JPEG input frames (rr_jpeg_read.h: markers and Huffman decoding; rr_jpeg.h: the arithmetic the device shares).
+// ---------------------------------------------------------------------------------------------------------------------
+static thread_local char g_jpeg_msg[160] = "";
+static int jpeg_done(int rc, const rrjpeg::Refusal& r) {
+  snprintf(g_jpeg_msg, sizeof g_jpeg_msg, "%s", rc ? r.buf : "");
+  return rc;
+}
+static int jpeg_arg(const char* why) {
+  snprintf(g_jpeg_msg, sizeof g_jpeg_msg, "%s", why);
+  return RR_E_ARG;
+}
+static int rr_jpeg_info_impl(const char* path, int32_t* W, int32_t* H, int32_t* components, int32_t* sampling) {
+  if (!path) return jpeg_arg("jpeg: null path");
+  Pool<DecodeScratch>::Lease sc(g_decode_pool);
+  size_t fsize = 0;
+  if (read_file(path, sc->file, fsize)) return jpeg_arg("jpeg: the file cannot be read");
+  rrjpeg::Frame fr;
+  rrjpeg::Refusal r;
+  const int rc = rrjpeg::read_jpeg(sc->file.data(), fsize, fr, nullptr, nullptr, 0, r);
+  if (rc == RR_OK) {
+    if (W) *W = fr.W;
+    if (H) *H = fr.H;
+    if (components) *components = fr.ncomp;
+    if (sampling) *sampling = fr.sampling;
+  }
+  return jpeg_done(rc, r);
+}
+static int rr_jpeg_read_record_impl(const char* path, void* dst, int64_t dst_bytes, int32_t H, int32_t W) {
+  if (!path || !dst || dst_bytes < (int64_t)sizeof(rr_jpeg_header)) return jpeg_arg("jpeg: null pointer or a buffer below the record's header");
+  if ((uintptr_t)dst % 8) return jpeg_arg("jpeg: the record's buffer is not 8-byte aligned");
+  Pool<DecodeScratch>::Lease sc(g_decode_pool);
+  size_t fsize = 0;
+  if (read_file(path, sc->file, fsize)) return jpeg_arg("jpeg: the file cannot be read");
+  rrjpeg::Frame fr;
+  rrjpeg::Refusal r;
+  if (H > 0) fr.want_W = W, fr.want_H = H;                // (refused before the scan is decoded)
+  rr_jpeg_header* hdr = static_cast<rr_jpeg_header*>(dst);
+  const int rc = rrjpeg::read_jpeg(sc->file.data(), fsize, fr, hdr, reinterpret_cast<int16_t*>(hdr + 1),
+                                   (dst_bytes - (int64_t)sizeof(rr_jpeg_header)) / 128, r);
+  return jpeg_done(rc, r);
+}
+static int rr_jpeg_read_bgr8_impl(const char* path, uint8_t* dst, int32_t H, int32_t W) {
+  if (!path || !dst || H <= 0 || W <= 0) return jpeg_arg("jpeg: null pointer or bad size");
+  Pool<DecodeScratch>::Lease sc(g_decode_pool);
+  size_t fsize = 0;
+  if (read_file(path, sc->file, fsize)) return jpeg_arg("jpeg: the file cannot be read");
+  rrjpeg::Frame fr;
+  rrjpeg::Refusal r;
+  // one pass over the file: room for the largest record an H x W frame can have (4:4:4 padded to whole 16 x 16 MCUs); the reader
+  // refuses a file of another size before it decodes the scan
+  if (W > 65535 || H > 65535) return jpeg_arg("jpeg: the file is not of the expected size");
+  const size_t cap = 3 * (2 * (((size_t)W + 15) / 16)) * (2 * (((size_t)H + 15) / 16));
+  at_least(sc->raw, cap * 128);
+  at_least(sc->img, cap * 64);
+  fr.want_W = W, fr.want_H = H;
+  rr_jpeg_header hdr;
+  int16_t* coef = reinterpret_cast<int16_t*>(sc->raw.data());
+  const int rc = rrjpeg::read_jpeg(sc->file.data(), fsize, fr, &hdr, coef, (int64_t)cap, r);
+  if (rc) return jpeg_done(rc, r);
+  rrjpeg::Geom g;
+  if (!rrjpeg::geom_of(fr.W, fr.H, fr.sampling, g)) return jpeg_arg("jpeg: bad frame size");
+  rrjpeg::record_planes(hdr, g, coef, sc->img.data());
+  for (int y = 0; y < H; y++)
+    for (int x = 0; x < W; x++) rrjpeg::pixel_bgr(sc->img.data(), g, fr.sampling, x, y, dst + ((size_t)y * W + x) * 3);
+  return jpeg_done(RR_OK, r);
+}
+extern "C" int rr_jpeg_info(const char* path, int32_t* W, int32_t* H, int32_t* components, int32_t* sampling) {
+  try {
+    return rr_jpeg_info_impl(path, W, H, components, sampling);
+  } catch (...) {
+    return RR_E_PARSE;
+  }
+}
+extern "C" int64_t rr_jpeg_record_bytes(int32_t W, int32_t H, int32_t sampling) {
+  rrjpeg::Geom g;
+  return rrjpeg::geom_of(W, H, sampling, g) ? rrjpeg::record_bytes(g) : (int64_t)RR_E_ARG;
+}
+extern "C" int rr_jpeg_read_record(const char* path, void* dst, int64_t dst_bytes) {
+  try {
+    return rr_jpeg_read_record_impl(path, dst, dst_bytes, 0, 0);
+  } catch (...) {
+    return RR_E_PARSE;
+  }
+}
+extern "C" int rr_jpeg_read_bgr8(const char* path, uint8_t* dst, int32_t H, int32_t W) {
+  try {
+    return rr_jpeg_read_bgr8_impl(path, dst, H, W);
+  } catch (...) {
+    return RR_E_PARSE;
+  }
+}
+extern "C" const char* rr_jpeg_last_error(void) { return g_jpeg_msg; }
+extern "C" int rr_sizeof_jpeg_header(void) { return (int)sizeof(rr_jpeg_header); }
+
+extern "C" int rr_io_read_frames_jpeg(int32_t n, const char* const* image_paths, const char* const* depth_paths, int32_t H, int32_t W,
+                                      uint8_t* records, int64_t record_stride, uint8_t* depth_rows, int64_t depth_stride, int32_t threads,
+                                      int32_t* status) {
+  if (n < 0 || H <= 0 || W <= 0 || !status || (n > 0 && (!image_paths || !records)) || (depth_paths && !depth_rows) ||
+      record_stride < (int64_t)sizeof(rr_jpeg_header) || record_stride % 8 || (uintptr_t)records % 8 ||
+      (depth_paths && depth_stride < (int64_t)H * (1 + 2 * (int64_t)W)))
+    return RR_E_ARG;
+  rrpar::parallel_for(n, threads, [&](int k) {
+    int rc;
+    try {
+      rc = image_paths[k] ? rr_jpeg_read_record_impl(image_paths[k], records + (size_t)k * (size_t)record_stride, record_stride, H, W) : RR_E_ARG;
+      if (rc == RR_OK && depth_paths) rc = depth_paths[k] ? read_rows_impl(depth_paths[k], depth_rows + (size_t)k * (size_t)depth_stride, H, W, 2) : RR_E_ARG;
+    } catch (...) {
+      rc = RR_E_PARSE;
+    }
+    status[k] = rc;
+  });
+  return RR_OK;
 }
 
 // The resize tables of one axis and one output sample: csrc/rr_resize.h states both (the device's input stage reads the same header)

@@ -47,6 +47,9 @@ PARTICLE_DRAWS = {'stream': RR_DRAWS_STREAM, 'counter': RR_DRAWS_COUNTER}
 RR_MAX_VIEWS = 8
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
 RR_RESIZE_BGR_U8, RR_RESIZE_RGB_U8_PLANAR, RR_RESIZE_RGB_F32_PLANAR = 0, 1, 2   # rr_resize_inputs_device: image_kind
+RR_IN_BG_JPEG = 64                                        # a baseline JPEG's coefficient record (rr_io_read_frames_jpeg): IDCT and colour on the device
+RR_JPEG_444, RR_JPEG_422, RR_JPEG_420, RR_JPEG_GREY = 0, 1, 2, 3
+RR_JPEG_HEADER_BYTES = 416
 RR_IN_BG_PNG_ROWS, RR_DEPTH_PNG_ROWS = 32, 3              # a file's filtered scanlines (rr_io_read_frames_rows): un-filtered on the device
 RR_DEPTH_U16 = 2                                        # rr_prepass_in.depth_f64: the uint16 samples of the depth file (metres = sample / 256)
 RR_IN_BG_F32, RR_IN_BG_U8, RR_IN_ENV_F32, RR_IN_RAINY_F32, RR_IN_RAINY_U8 = 1, 2, 4, 8, 16      # rr_frame_in.in_types
@@ -202,7 +205,8 @@ EXPORTS = ['rr_version', 'rr_create', 'rr_destroy', 'rr_last_error', 'rr_set_str
            'rr_sizeof_traj_pose', 'rr_lens_drops_device', 'rr_sizeof_lens_drop', 'rr_sizeof_lens_batch', 'rr_pipeline_set_lens',
            'rr_sizeof_pipeline_lens', 'rr_set_input_resize', 'rr_resize_inputs_device', 'rr_debug_mem', 'rr_pipeline_set_layer',
            'rr_augment_set_layer', 'rr_sizeof_layer_out', 'rr_sizeof_pipeline_layer', 'rr_sizeof_tensor_layer',
-           'rr_pipeline_set_layer_png', 'rr_sizeof_pipeline_layer_png', 'rr_io_write_frames_text']
+           'rr_pipeline_set_layer_png', 'rr_sizeof_pipeline_layer_png', 'rr_io_write_frames_text', 'rr_jpeg_info', 'rr_jpeg_record_bytes',
+           'rr_jpeg_read_record', 'rr_jpeg_read_bgr8', 'rr_io_read_frames_jpeg', 'rr_jpeg_last_error', 'rr_sizeof_jpeg_header']
 
 _lib = None
 
@@ -279,6 +283,13 @@ def load_library(path=None):
                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
     lib.rr_io_read_frames_u16.argtypes = lib.rr_io_read_frames.argtypes
     lib.rr_io_read_frames_rows.argtypes = lib.rr_io_read_frames.argtypes
+    lib.rr_io_read_frames_jpeg.argtypes = lib.rr_io_read_frames.argtypes
+    lib.rr_jpeg_info.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(ctypes.c_int32)] * 4
+    lib.rr_jpeg_record_bytes.argtypes, lib.rr_jpeg_record_bytes.restype = [ctypes.c_int32] * 3, ctypes.c_int64
+    lib.rr_jpeg_read_record.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int64]
+    lib.rr_jpeg_read_bgr8.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+    lib.rr_jpeg_last_error.restype = ctypes.c_char_p
+    assert lib.rr_sizeof_jpeg_header() == RR_JPEG_HEADER_BYTES
     lib.rr_io_read_frames_rows_sized.argtypes = lib.rr_io_read_frames.argtypes[:5] + [ctypes.c_int32, ctypes.c_int32] + lib.rr_io_read_frames.argtypes[5:]
     lib.rr_io_read_frames_scaled.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
@@ -625,6 +636,62 @@ def io_read_frames_rows(image_paths, depth_paths, H, W, image_rows_block, depth_
                                         int(depth_rows_block.strides[0]), int(threads), _ptr(status))
     if rc != 0:
         raise RuntimeError("rr_io_read_frames_rows failed (%d)" % rc)
+    return status
+
+
+def jpeg_info(path):
+    """rr_jpeg_info: (0, W, H, components, sampling) for a baseline JPEG the library's reader takes, else (status, reason)."""
+    lib = load_library()
+    v = [ctypes.c_int32() for _ in range(4)]
+    rc = lib.rr_jpeg_info(os.fsencode(path), *[ctypes.byref(x) for x in v])
+    if rc != 0:
+        return rc, lib.rr_jpeg_last_error().decode('latin-1')
+    return (0,) + tuple(x.value for x in v)
+
+
+def jpeg_record_bytes(W, H, sampling):
+    """rr_jpeg_record_bytes: the size of the coefficient record of a W x H frame of that sampling (RR_JPEG_*)."""
+    n = load_library().rr_jpeg_record_bytes(int(W), int(H), int(sampling))
+    if n < 0:
+        raise ValueError("rr_jpeg_record_bytes(%d, %d, %d) failed (%d)" % (W, H, sampling, n))
+    return int(n)
+
+
+def jpeg_read_record(path):
+    """rr_jpeg_read_record: the file's coefficient record as a uint8 array; RuntimeError with the reader's reason for a file it refuses."""
+    info = jpeg_info(path)
+    if info[0] != 0:
+        raise RuntimeError("rr_jpeg_info(%s) failed (%d): %s" % (path, info[0], info[1]))
+    rec = np.zeros(jpeg_record_bytes(info[1], info[2], info[4]) // 8, np.int64).view(np.uint8)
+    lib = load_library()
+    rc = lib.rr_jpeg_read_record(os.fsencode(path), _ptr(rec), rec.size)
+    if rc != 0:
+        raise RuntimeError("rr_jpeg_read_record(%s) failed (%d): %s" % (path, rc, lib.rr_jpeg_last_error().decode('latin-1')))
+    return rec
+
+
+def jpeg_read_bgr8(path, H, W):
+    """rr_jpeg_read_bgr8: the whole decode on the host, (status, B G R bytes or the reader's reason)."""
+    lib = load_library()
+    out = np.empty((H, W, 3), np.uint8)
+    rc = lib.rr_jpeg_read_bgr8(os.fsencode(path), _ptr(out), int(H), int(W))
+    return (0, out) if rc == 0 else (rc, lib.rr_jpeg_last_error().decode('latin-1'))
+
+
+def io_read_frames_jpeg(image_paths, depth_paths, H, W, record_block, depth_rows_block, threads=0):
+    """rr_io_read_frames_jpeg: record_block[k] receives the coefficient record of frame k's baseline JPEG (rr_prepass_in:
+    RR_IN_BG_JPEG), depth_rows_block[k] the H rows of 1 + 2 W bytes of its 16-bit depth PNG (RR_DEPTH_PNG_ROWS).  Returns the
+    per-frame status."""
+    lib = load_library()
+    n = len(image_paths)
+    ip, k1 = _c_paths(image_paths)
+    dp, k2 = _c_paths(depth_paths)
+    status = np.zeros(n, np.int32)
+    assert record_block.dtype == np.uint8 and depth_rows_block.dtype == np.uint8 and record_block.shape[0] >= n and depth_rows_block.shape[0] >= n
+    rc = lib.rr_io_read_frames_jpeg(n, ip, dp, int(H), int(W), _ptr(record_block), int(record_block.strides[0]), _ptr(depth_rows_block),
+                                    int(depth_rows_block.strides[0]), int(threads), _ptr(status))
+    if rc != 0:
+        raise RuntimeError("rr_io_read_frames_jpeg failed (%d)" % rc)
     return status
 
 
@@ -1197,6 +1264,13 @@ class RainHip:
             pin.bg, pin.bg_u8, pin.in_types = _ptr(rows), None, RR_IN_BG_PNG_ROWS
             bg = np.empty((H, W, 3), np.uint8)              # (only its shape is used by the callers)
             keep.append(rows)
+        elif fr.get('bg_jpeg') is not None:                # a baseline JPEG's coefficient record (rr_io_read_frames_jpeg); 'shape' = (H, W)
+            rec = np.ascontiguousarray(fr['bg_jpeg'], np.uint8).reshape(-1)
+            H, W = fr['shape']
+            assert rec.size >= RR_JPEG_HEADER_BYTES and rec.ctypes.data % 8 == 0, rec.size
+            pin.bg, pin.bg_u8, pin.in_types = _ptr(rec), None, RR_IN_BG_JPEG
+            bg = np.empty((H, W, 3), np.uint8)              # (only its shape is used by the callers)
+            keep.append(rec)
         elif fr.get('bg_u8') is not None:
             bg = np.ascontiguousarray(fr['bg_u8'], np.uint8)
             pin.bg, pin.bg_u8, pin.in_types = None, _ptr(bg), 0

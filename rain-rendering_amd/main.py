@@ -115,7 +115,11 @@ _FLAGS = [
                                help="resize full-size frames on the GPU: where a dataset renders at a fraction of its files' resolution "
                                     "(render_scale / depth_scale other than 1) the batch-native route uploads the files' own scanlines and the "
                                     "library resizes image and depth map on the device (rr_set_input_resize) instead of on the host; the "
-                                    "output files are the same, byte for byte.  Without a resize to do the flag changes nothing")),
+                                    "output files are the same, byte for byte.  Without a resize to do the flag changes nothing.  JPEG frames at "
+                                    "such a scale stay on the host-resize path: their device decode (IDCT and colour) runs at render scale 1 only.  "
+                                    "(At render scale 1 a tree of baseline .jpg / .jpeg frames is decoded that way by itself; a frame of such a tree "
+                                    "that the JPEG reader refuses -- progressive, damaged, another size or chroma sampling -- is SKIPPED with a "
+                                    "message: no output files are written for it)")),
     (('--rig_view',), dict(type=int, default=0, help="with --particle_model rig: the view this run's camera folder shows; one run per "
                                                      "camera folder with the same seed gives a coherent set")),
 ]
