@@ -659,9 +659,19 @@ int emu_prepass(int H, int W, const void* bg, const void* depth, int depth_f64, 
   std::vector<uint8_t> r8(px * 3);
   PreScratch sc{fext.data(), tmpF.data(), tmpL.data(), r8.data(), nullptr, mean.data(), epack.data(), etmp.data()};
   PreFrame F{bg, depth, rainy, env_xyY, env_u8, want_env ? r8.data() : nullptr, beta_ext, beta_hg, irr_num, irr_den, depth_f64, types};
-  for (int c = 0; c < 3; c++) {         // k_fog_sum / k_fog_mean (sum order differs from the device's tree: ~1e-16)
+  for (int c = 0; c < 3; c++) {         // k_fog_sum / k_fog_mean in the device's order: a thread's strided terms, the tree of 256, the 64 blocks
     double s = 0;
-    for (size_t p = 0; p < px; p++) s += (irr_num * load_unit(bg, types, (int64_t)(p * 3 + c))) / irr_den;
+    for (int b = 0; b < FOG_BLOCKS; b++) {
+      double red[256];
+      for (int t = 0; t < 256; t++) {
+        double a = 0;
+        for (size_t p = (size_t)b * 256 + t; p < px; p += (size_t)FOG_BLOCKS * 256) a += (irr_num * load_unit(bg, types, (int64_t)(p * 3 + c))) / irr_den;
+        red[t] = a;
+      }
+      for (int st = 128; st > 0; st >>= 1)
+        for (int t = 0; t < st; t++) red[t] += red[t + st];
+      s += red[0];
+    }
     mean[c] = s / (double)px;
   }
   if (tiled) {

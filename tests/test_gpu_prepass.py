@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import helpers as h
+import prepass_cases as pc
 from oracle import prepass as op
 from oracle import render as orc
 
@@ -35,7 +36,10 @@ def test_prepass_matches_oracle(built, H, W, dtype):
     outs = rh.prepass_frames(frames, want_env=True, want_env_u8=True)
     for fr, o in zip(frames, outs):
         want = op.fog_rain_layer(fr['bg'], fr['depth'], 50, FNUM, EXPO, GAIN)
-        assert np.abs(o['rainy_bg'] - want).max() < 2e-7           # float32 expf of another libm, sum order of the mean
+        # float32 expf of another libm; the float64-depth path has its counted float64 bound (prepass_cases.bound_f64)
+        tol = pc.bound_f64(pc.fog_parts(fr['bg'], fr['depth'], 50, pc.fog_taps(25)), 25) if dtype is np.float64 else 2e-7
+        assert tol <= (pc.F64_LIMIT if dtype is np.float64 else 2e-7)
+        assert np.abs(o['rainy_bg'] - want).max() <= tol
         e_bgr = op.generate_env_map(o['rainy_bg'], FOCAL)           # map logic on the GPU's own fog output
         assert o['env_bgr_u8'].shape == (H, We, 3)
         assert np.array_equal(o['env_bgr_u8'], np.rint(e_bgr * 255).astype(np.uint8))
@@ -216,7 +220,8 @@ def test_pipeline_hands_float32_arrays_to_the_hot_path(tmp_path, built):
 def test_other_tap_counts_take_the_three_kernel_form(built):
     """rr_set_prepass_kernels with a tap count other than the reference's 25: k_fog_ext / k_fog_h / k_fog_v (float64 planes in
     HBM) instead of the one-kernel tile.  Against the host build of the same functions (tests/hostemu): equal up to the two
-    libms' expf."""
+    libms' expf; and against the reference with 9 taps (prepass_cases): the byte map of the device's own fog layer exactly, the
+    float64-depth fog layer within its counted bound."""
     import test_prepass_hostemu as tp
     H, W = 75, 131
     bg, depth = _scene(H, W, 4)
@@ -229,6 +234,15 @@ def test_other_tap_counts_take_the_three_kernel_form(built):
         want = tp.emu_prepass(bg, depth, 50, tiled=0, fog_taps=9, narrow=dt is np.float32)
         assert np.abs(o['rainy_bg'].astype(np.float64) - want[0]).max() < 3e-7
         assert np.abs(o['env_bgr_u8'].astype(int) - want[2].astype(int)).max() <= 1
+    wide = rh.prepass_frames([dict(bg=bg, depth=depth, fog=fog.constants())], want_env=True, want_env_u8=True)[0]
+    assert np.array_equal(wide['env_bgr_u8'], pc.map_bytes(pc.ref_env_map(wide['rainy_bg'], pc.env_taps(15))))
+    assert np.array_equal(o['env_bgr_u8'], wide['env_bgr_u8'])                     # (the float32 call's map: from the float64 layer's bytes)
+    d64 = depth.astype(np.float64)
+    o64 = rh.prepass_frames([dict(bg=bg, depth=d64, fog=fog.constants())], want_env=True, want_env_u8=True)[0]
+    parts = pc.fog_parts(bg, d64, 50, pc.fog_taps(9))
+    tol = pc.bound_f64(parts, 9)
+    assert tol <= pc.F64_LIMIT and np.abs(o64['rainy_bg'] - parts['rainy']).max() <= tol
+    assert np.array_equal(o64['env_bgr_u8'], pc.map_bytes(pc.ref_env_map(o64['rainy_bg'], pc.env_taps(15))))
     rh.close()
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers as h
+import prepass_cases as pc
 from oracle import prepass as op
 
 fogmod = importlib.import_module('rain-rendering_amd.common.add_attenuation')
@@ -24,21 +25,27 @@ def scene(H, W, seed, dtype=np.float32):
 PRE_BG_F32, PRE_BG_U8, PRE_RAINY_F32, PRE_ENV_F32, PRE_DEPTH_U16 = 1, 2, 4, 8, 16         # rrpre::PRE_* (csrc/rr_prepass.h)
 
 
-def emu_prepass(bg, depth, rain, focal_m=0.006, f_number=6.0, exposure=2, gain=20, tiled=1, seg_rows=64, narrow=False, fog_taps=25):
-    """bg: float64 / float32 / uint8 image; narrow: float32 rainy_bg and xyY map (the float64 results rounded once)."""
+def emu_prepass(bg, depth, rain, focal_m=0.006, f_number=6.0, exposure=2, gain=20, tiled=1, seg_rows=64, narrow=False, fog_taps=25,
+                env_taps=15, want_env=True):
+    """bg: float64 / float32 / uint8 image; narrow: float32 rainy_bg and xyY map (the float64 results rounded once).  A single tap is
+    [1.0]; want_env=False: the fog layer alone (any frame size; the map arrays come back with a width of 0)."""
     emu = h.hostemu()
     H, W = bg.shape[:2]
     fog = fogmod.FogRain(rain_intensity=rain, focal=focal_m, f_number=f_number, angle=90, exposure=exposure, camera_gain=gain)
     be, bh, num, den = fog.constants()
-    gen = envmod.EnvironmentMapGenerator(focal_m, W, H)
-    cw, uniq, first = gen.device_tables(H, W)
+    if want_env:
+        cw, uniq, first = envmod.EnvironmentMapGenerator(focal_m, W, H).device_tables(H, W)
+    else:
+        cw, uniq, first = 0, np.zeros(1, np.int32), np.zeros(1, np.int32)
     We = cw + 2 * (cw // 2)
     fw = np.ascontiguousarray(op.gaussian_kernel(fog_taps, fog_taps))
-    ew = np.ascontiguousarray(op.gaussian_kernel(15, 0))
+    ew = np.ascontiguousarray(op.gaussian_kernel(env_taps, 0))
     out_t = np.float32 if narrow else np.float64
-    rainy = np.zeros((H, W, 3), out_t)
-    env = np.zeros((H, We, 3), out_t)
-    env8 = np.zeros((H, We, 3), np.uint8)
+    # (each output with a guard row behind it: a store past the frame's last row shows)
+    guard = [np.full((H + 1, W, 3), -7.0, out_t), np.full((H + 1, We, 3), -7.0, out_t), np.full((H + 1, We, 3), 0xA5, np.uint8)]
+    rainy, env, env8 = [g[:H] for g in guard]
+    for a in (rainy, env, env8):
+        a[...] = 0
     bg = np.ascontiguousarray(bg)
     types = {np.dtype(np.float64): 0, np.dtype(np.float32): PRE_BG_F32, np.dtype(np.uint8): PRE_BG_U8}[bg.dtype]
     types |= (PRE_RAINY_F32 | PRE_ENV_F32) if narrow else 0
@@ -48,9 +55,11 @@ def emu_prepass(bg, depth, rain, focal_m=0.006, f_number=6.0, exposure=2, gain=2
     emu.emu_prepass.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + \
         [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + \
         [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3
-    rc = emu.emu_prepass(H, W, p(bg), p(depth), int(depth.dtype == np.float64), be, bh, num, den, fog_taps, p(fw), 15, p(ew),
-                         cw, len(uniq), p(uniq), p(first), p(rainy), p(env), p(env8), types, int(tiled), int(seg_rows))
+    rc = emu.emu_prepass(H, W, p(bg), p(depth), int(depth.dtype == np.float64), be, bh, num, den, fog_taps, p(fw), env_taps, p(ew),
+                         cw, len(uniq) if want_env else 0, p(uniq), p(first), p(rainy), p(env), p(env8), types, int(tiled), int(seg_rows))
     assert rc == We, rc
+    for g, fill in zip(guard, (-7.0, -7.0, 0xA5)):
+        assert (g[H] == fill).all(), 'a store past the last row of an output'
     return rainy, env, env8
 
 
@@ -59,8 +68,10 @@ def test_prepass_arithmetic_matches_oracle(H, W, dtype):
     bg, depth = scene(H, W, 5, dtype)
     rainy, env, env8 = emu_prepass(bg, depth, 50)
     want = op.fog_rain_layer(bg, depth, 50, 6.0, 2, 20)
-    # expf/exp come from different libms and the channel mean is summed in another order
-    assert np.abs(rainy - want).max() < 2e-7
+    # expf comes from different libms; the float64-depth path has its counted float64 bound (prepass_cases.bound_f64)
+    tol = pc.bound_f64(pc.fog_parts(bg, depth, 50, pc.fog_taps(25)), 25) if dtype is np.float64 else 2e-7
+    assert tol <= (pc.F64_LIMIT if dtype is np.float64 else 2e-7)
+    assert np.abs(rainy - want).max() <= tol
     # environment map from the emulator's OWN fog output, so that only the map logic is compared
     e_bgr = op.generate_env_map(rainy, 0.006)
     want8 = np.rint(e_bgr * 255).astype(np.uint8)
