@@ -324,7 +324,16 @@ int rr_set_input_resize(rr_ctx* ctx, int32_t src_H, int32_t src_W, int32_t depth
  * call waits for it).  Either side may be NULL.  image_kind: RR_RESIZE_*; depth_kind: 0 (float32 metres) or RR_DEPTH_U16. */
 enum { RR_RESIZE_BGR_U8 = 0,             /* [n,src_H,src_W,3] interleaved B G R bytes (the un-filtered file) */
        RR_RESIZE_RGB_U8_PLANAR = 1,      /* [n,3,src_H,src_W] planar R G B bytes */
-       RR_RESIZE_RGB_F32_PLANAR = 2 };   /* [n,3,src_H,src_W] planar R G B float32: widened, not divided */
+       RR_RESIZE_RGB_F32_PLANAR = 2,     /* [n,3,src_H,src_W] planar R G B float32: widened, not divided */
+       /* rr_tensor_batch's other formats, each the kernel rr_augment_frames_device runs for it while armed.  A frame is
+        * src_H * src_W * 3 elements; `images` is aligned to the element size (RR_E_ARG otherwise).  The half types enter as the
+        * float32 they widen to exactly (csrc/rr_convert.h). */
+       RR_RESIZE_RGB_U8 = 3,             /* [n,src_H,src_W,3] interleaved R G B bytes */
+       RR_RESIZE_RGB_F32 = 4,            /* [n,src_H,src_W,3] interleaved R G B float32 */
+       RR_RESIZE_RGB_F16_PLANAR = 5,     /* [n,3,src_H,src_W] planar R G B float16 */
+       RR_RESIZE_RGB_BF16_PLANAR = 6,    /* [n,3,src_H,src_W] planar R G B bfloat16 */
+       RR_RESIZE_RGB_F16 = 7,            /* [n,src_H,src_W,3] interleaved R G B float16 */
+       RR_RESIZE_RGB_BF16 = 8 };         /* [n,src_H,src_W,3] interleaved R G B bfloat16 */
 int rr_resize_inputs_device(rr_ctx* ctx, int32_t n, int32_t H, int32_t W, const void* images, int32_t image_kind, const void* depth,
                             int32_t depth_kind, double* bg_out, float* depth_out, void* stream);
 

@@ -8368,17 +8368,20 @@ int resize_inputs(rr_ctx* ctx, int n, int H, int W, const void* images, int imag
     ctx->err = "rr_resize_inputs_device: rr_set_input_resize first";
     return RR_E_STATE;
   }
-  if (n <= 0 || (images && !bg_out) || (depth && !depth_out) || (images && (image_kind < RR_RESIZE_BGR_U8 || image_kind > RR_RESIZE_RGB_F32_PLANAR)) ||
+  // element size and kernel of every image kind, in the order of RR_RESIZE_*
+  static const int kEl[] = {1, 1, 4, 1, 4, 2, 2, 2, 2};
+  static const int kKind[] = {RSZ_BGR8, RSZ_RGB8P, RSZ_RGBF32P, RSZ_RGB8I, RSZ_RGBF32I, RSZ_RGBF16P, RSZ_RGBBF16P, RSZ_RGBF16I, RSZ_RGBBF16I};
+  if (n <= 0 || (images && !bg_out) || (depth && !depth_out) || (images && (image_kind < RR_RESIZE_BGR_U8 || image_kind > RR_RESIZE_RGB_BF16)) ||
       (depth && depth_kind != 0 && depth_kind != RR_DEPTH_U16) ||
-      (images && image_kind == RR_RESIZE_RGB_F32_PLANAR && (reinterpret_cast<uintptr_t>(images) & 3u)) ||
+      (images && (reinterpret_cast<uintptr_t>(images) & (uintptr_t)(kEl[image_kind] - 1))) ||
       (depth && (reinterpret_cast<uintptr_t>(depth) & (depth_kind == RR_DEPTH_U16 ? 1u : 3u)))) {
     ctx->err = "rr_resize_inputs_device: bad argument (n, a kind, an output missing for its input, or a misaligned array)";
     return RR_E_ARG;
   }
   int rc;
   if (images) {
-    const int64_t fb = (int64_t)R.sH * R.sW * 3 * (image_kind == RR_RESIZE_RGB_F32_PLANAR ? 4 : 1);
-    const int kind = image_kind == RR_RESIZE_BGR_U8 ? RSZ_BGR8 : (image_kind == RR_RESIZE_RGB_U8_PLANAR ? RSZ_RGB8P : RSZ_RGBF32P);
+    const int64_t fb = (int64_t)R.sH * R.sW * 3 * kEl[image_kind];
+    const int kind = kKind[image_kind];
     if ((rc = enqueue_resize(ctx, n, H, W, kind, images, fb, images, static_cast<const char*>(images) + (int64_t)n * fb, bg_out,
                              (int64_t)H * W * 24, s)))
       return rc;

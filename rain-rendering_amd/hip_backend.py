@@ -47,6 +47,8 @@ PARTICLE_DRAWS = {'stream': RR_DRAWS_STREAM, 'counter': RR_DRAWS_COUNTER}
 RR_MAX_VIEWS = 8
 RR_OUT_RAINY_F32, RR_OUT_ENV_F32 = 1, 2                 # rr_prepass_out.out_types
 RR_RESIZE_BGR_U8, RR_RESIZE_RGB_U8_PLANAR, RR_RESIZE_RGB_F32_PLANAR = 0, 1, 2   # rr_resize_inputs_device: image_kind
+RR_RESIZE_RGB_U8, RR_RESIZE_RGB_F32 = 3, 4                                       # ... interleaved R G B bytes / float32
+RR_RESIZE_RGB_F16_PLANAR, RR_RESIZE_RGB_BF16_PLANAR, RR_RESIZE_RGB_F16, RR_RESIZE_RGB_BF16 = 5, 6, 7, 8   # ... the half types, planar / interleaved
 RR_IN_BG_JPEG = 64                                        # a baseline JPEG's coefficient record (rr_io_read_frames_jpeg): IDCT and colour on the device
 RR_JPEG_444, RR_JPEG_422, RR_JPEG_420, RR_JPEG_GREY = 0, 1, 2, 3
 RR_JPEG_HEADER_BYTES = 416
@@ -1483,39 +1485,85 @@ class RainHip:
         size) -- the cv2.resize of the reference's frame loader, bit for bit (csrc/rr_resize.h).  All zero: off."""
         self._check(self.lib.rr_set_input_resize(self.h, int(src_h), int(src_w), int(depth_h), int(depth_w)), 'rr_set_input_resize')
 
-    def resize_inputs(self, H, W, images=None, depth=None, planar=False):
+    def resize_inputs(self, H, W, images=None, depth=None, planar=False, kind=None, in_offset=0, guard=0):
         """rr_resize_inputs_device on numpy arrays (uploaded and downloaded here; a caller with device arrays uses the C entry point):
         images [n, sH, sW, 3] uint8 B G R -- or, planar, [n, 3, sH, sW] R G B uint8 / float32 -- and depth [n, dH, dW] uint16 samples or
-        float32 metres, at the sizes of set_input_resize.  The arrays travel through torch tensors (a process that uses this imports torch
-        before it loads the library, as augment.py does: torch brings its own HIP runtime).  Returns (bg [n, H, W, 3] float64 B G R | None, depth [n, H, W] float32 | None)."""
+        float32 metres, at the sizes of set_input_resize.  kind: an explicit RR_RESIZE_* for `images`, whose bytes are then taken as
+        they lie (float16 / bfloat16 travel as their uint16 bit patterns).  The arrays travel through torch tensors (a process that
+        uses this imports torch before it loads the library, as augment.py does: torch brings its own HIP runtime).
+        Returns (bg [n, H, W, 3] float64 B G R | None, depth [n, H, W] float32 | None).
+        in_offset: each input starts that many bytes past a 16-byte boundary inside a larger device buffer.  guard: each output lies
+        inside a larger buffer, `guard` elements of bytes 0xA5 before frame 0 and behind the last frame (the outputs themselves are
+        pre-filled with them too); with either, a third value is returned: {'bg_guard' / 'depth_guard': (the bytes before, the bytes
+        behind) after the call, 'images_buffer' / 'depth_buffer': (the whole input buffer as uploaded, after the call)}."""
         import torch
         dev = torch.device('cuda', self.device)
         n = len(images) if images is not None else len(depth)
+        in_offset, guard = int(in_offset), int(guard)
+        if not (0 <= in_offset < 16 and guard >= 0):
+            raise ValueError("in_offset in [0, 16), guard >= 0")
+        FILL = 0xA5
         t_img = t_dep = t_bg = t_out = None
         ik = dk = 0
+        info, host_in = {}, {}
+
+        def place(arr, name):
+            """The array's bytes at 16 + in_offset of a device buffer 48 bytes longer (torch allocations start on 512-byte boundaries)."""
+            raw = arr.view(np.uint8).reshape(-1)
+            buf = np.full(raw.size + 48, FILL, np.uint8)
+            buf[16 + in_offset:16 + in_offset + raw.size] = raw
+            host_in[name] = buf
+            t = torch.from_numpy(buf).to(dev)
+            assert t.data_ptr() % 16 == 0
+            return t
+
+        def guarded(shape, dtype):
+            el = torch.empty((), dtype=dtype).element_size()
+            count = int(np.prod(shape))
+            t = torch.full(((count + 2 * guard) * el,), FILL, dtype=torch.uint8, device=dev)
+            assert t.data_ptr() % 16 == 0
+            return t, el
+
         if images is not None:
             images = np.array(images, order='C')          # (a copy: torch wants writable memory)
-            if planar and images.dtype == np.float32:
+            if kind is not None:
+                ik = int(kind)
+            elif planar and images.dtype == np.float32:
                 ik = RR_RESIZE_RGB_F32_PLANAR
             elif images.dtype == np.uint8:
                 ik = RR_RESIZE_RGB_U8_PLANAR if planar else RR_RESIZE_BGR_U8
             else:
-                raise ValueError("images: uint8 (interleaved B G R or planar R G B) or planar float32, got %s" % images.dtype)
-            t_img = torch.from_numpy(images.view(np.uint8).reshape(-1)).to(dev)
-            t_bg = torch.empty((n, H, W, 3), dtype=torch.float64, device=dev)
+                raise ValueError("images: uint8 (interleaved B G R or planar R G B) or planar float32, got %s (or name the kind)" % images.dtype)
+            t_img = place(images, 'images_buffer')
+            t_bg, bg_el = guarded((n, H, W, 3), torch.float64)
         if depth is not None:
             depth = np.array(depth, order='C')
             if depth.dtype not in (np.uint16, np.float32):
                 raise ValueError("depth: uint16 samples or float32 metres, got %s" % depth.dtype)
             dk = RR_DEPTH_U16 if depth.dtype == np.uint16 else 0
-            t_dep = torch.from_numpy(depth.view(np.uint8).reshape(-1)).to(dev)
-            t_out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+            t_dep = place(depth, 'depth_buffer')
+            t_out, out_el = guarded((n, H, W), torch.float32)
         torch.cuda.synchronize(dev)
-        rc = self.lib.rr_resize_inputs_device(self.h, n, int(H), int(W), t_img.data_ptr() if t_img is not None else None, ik,
-                                              t_dep.data_ptr() if t_dep is not None else None, dk,
-                                              t_bg.data_ptr() if t_bg is not None else None, t_out.data_ptr() if t_out is not None else None, None)
+        rc = self.lib.rr_resize_inputs_device(self.h, n, int(H), int(W), t_img.data_ptr() + 16 + in_offset if t_img is not None else None, ik,
+                                              t_dep.data_ptr() + 16 + in_offset if t_dep is not None else None, dk,
+                                              t_bg.data_ptr() + guard * bg_el if t_bg is not None else None,
+                                              t_out.data_ptr() + guard * out_el if t_out is not None else None, None)
         self._check(rc, 'rr_resize_inputs_device')
-        return (t_bg.cpu().numpy() if t_bg is not None else None, t_out.cpu().numpy() if t_out is not None else None)
+        res = []
+        for t, el, shape, dtype, name in ((t_bg, 8, (n, H, W, 3), np.float64, 'bg_guard'), (t_out, 4, (n, H, W), np.float32, 'depth_guard')):
+            if t is None:
+                res.append(None)
+                continue
+            raw = t.cpu().numpy()
+            g = guard * el
+            res.append(raw[g:raw.size - g].view(dtype).reshape(shape).copy())
+            info[name] = (raw[:g].copy(), raw[raw.size - g:].copy())
+        for t, name in ((t_img, 'images_buffer'), (t_dep, 'depth_buffer')):
+            if t is not None:
+                info[name] = (host_in[name], t.cpu().numpy())
+        if in_offset or guard:
+            return res[0], res[1], info
+        return res[0], res[1]
 
     def augment_frames_device(self, batch, stream=None):
         """rr_augment_frames_device: `batch` an rr_tensor_batch (device pointers for the tensors, host pointers for the records

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "rainhip.h"
+#include "rr_convert.h"
 #include "rr_resize.h"
 
 namespace {
@@ -12,7 +13,16 @@ double image_sample(const void* src, int kind, int sH, int sW, int y, int x, int
   const int64_t px = (int64_t)y * sW + x, plane = (int64_t)sH * sW;
   if (kind == RR_RESIZE_BGR_U8) return rrresize::image_unit(static_cast<const uint8_t*>(src)[px * 3 + c]);
   if (kind == RR_RESIZE_RGB_U8_PLANAR) return rrresize::image_unit(static_cast<const uint8_t*>(src)[(2 - c) * plane + px]);
-  return (double)static_cast<const float*>(src)[(2 - c) * plane + px];
+  if (kind == RR_RESIZE_RGB_F32_PLANAR) return (double)static_cast<const float*>(src)[(2 - c) * plane + px];
+  // rr_tensor_batch's other formats: interleaved R G B, and the half types widened as the kernels widen them (csrc/rr_convert.h)
+  const int64_t il = rrconv::interleaved_index(px, 2 - c), pl = rrconv::planar_index(px, 2 - c, plane);
+  if (kind == RR_RESIZE_RGB_U8) return rrresize::image_unit(static_cast<const uint8_t*>(src)[il]);
+  if (kind == RR_RESIZE_RGB_F32) return (double)static_cast<const float*>(src)[il];
+  const uint16_t* hs = static_cast<const uint16_t*>(src);
+  if (kind == RR_RESIZE_RGB_F16_PLANAR) return (double)rrconv::bits_f32(rrconv::widen_bits<0>(hs[pl]));
+  if (kind == RR_RESIZE_RGB_BF16_PLANAR) return (double)rrconv::bits_f32(rrconv::widen_bits<1>(hs[pl]));
+  if (kind == RR_RESIZE_RGB_F16) return (double)rrconv::bits_f32(rrconv::widen_bits<0>(hs[il]));
+  return (double)rrconv::bits_f32(rrconv::widen_bits<1>(hs[il]));
 }
 
 double depth_sample(const void* src, int kind, int sW, int y, int x) {
@@ -26,7 +36,7 @@ extern "C" {
 
 // one frame: src (sH x sW, `kind`) -> out H x W x 3 float64 B G R
 int resize_emu_image(const void* src, int kind, int sH, int sW, int H, int W, double* out) {
-  if (!src || !out || kind < RR_RESIZE_BGR_U8 || kind > RR_RESIZE_RGB_F32_PLANAR || sH <= 0 || sW <= 0 || H <= 0 || W <= 0) return RR_E_ARG;
+  if (!src || !out || kind < RR_RESIZE_BGR_U8 || kind > RR_RESIZE_RGB_BF16 || sH <= 0 || sW <= 0 || H <= 0 || W <= 0) return RR_E_ARG;
   const bool identity = sH == H && sW == W;
   const double sx = rrresize::resize_scale(W, sW), sy = rrresize::resize_scale(H, sH);
   for (int y = 0; y < H; y++) {
